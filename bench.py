@@ -1,23 +1,29 @@
 #!/usr/bin/env python3
 """bench.py — gradient-steps/sec of the HER-sample + critic/actor update path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one agent.update(step): HER batch draw + gather, critic update, actor update when
 due, Polyak when due (reference src/agent.py:1378-1404 / src/env.py:384-385).  Steps are issued
 as the trainer issues them, `gradient_step` (40) at a time with the buffer untouched in between.
 Inputs (the replay ring) are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times exactly K steps, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given (DIR/<name>.npy: the step's returned tuple and the parameters it left; the
+inputs are seeded, so two builds can be compared array for array) and prints the JSON line.  Everything
+else below (profiler child, roofline / push legs, CPU baselines, the extra legs at N > 1) runs only with
+`--full`.
+
 N > 1: one process per GPU — under torchrun (RANK / WORLD_SIZE in the environment) or, when started as
 plain `python bench.py --gpus N`, N rank processes spawned by this script before it touches the GPU.
 Each rank owns a local ring and draws its own batch of B rows; gradients are all-reduced over RCCL —
 once per overlapped DDPG step (critic and actor blocks are adjacent), twice per step otherwise.
 Per-GPU work is fixed -> "scaling": "weak"; value = N x synchronised optimiser steps / s (batch-B-equivalent
-steps: one synchronised step consumes N x B rows — `value_semantics` in the line says so).  Two extra
+steps: one synchronised step consumes N x B rows — `value_semantics` in the line says so).  With --full, two extra
 untimed-by-the-headline legs at N > 1: `strong_scaling` (the batch of B rows split over the ranks) and
 `cfg5_sac_slide_b512` (BASELINE.json configs[4]).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields, and with --full also
   roofline         the dominant kernel.  DDPG (row-block path): rowchain_ddpg_kernel, the forward and
                    input-gradient chains of a step's two phases in one launch — algorithmic flops per launch /
                    the kernel's average duration vs the fp32 MFMA peak.  Other agents: the whole step.
@@ -262,18 +268,20 @@ def build_agent(w, args, rank, local_rank, batch=None):
     return agent, pool, t_fill
 
 
-def timed_region(agent, dp, w, steps, warmup, step0=1):
+def timed_region(agent, dp, w, steps, warmup, step0=1, last=None):
     """W warm-up steps, one untimed call of every chunk size the timed region will issue (lazily built graphs and
-    buffers exist before the clock starts), then exactly `steps` steps between barrier + synchronize pairs."""
+    buffers exist before the clock starts), then exactly `steps` steps between barrier + synchronize pairs.
+    `last` (a list): receives the tuple the timed region's final step returned."""
     import torch.distributed as dist
     gstep = w["gstep"]
 
     def run(s0, n):
-        done = 0
+        done, res = 0, None
         while done < n:
             m = min(gstep, n - done)
-            (agent if dp is None else dp).update_many(s0 + done, m)
+            res = (agent if dp is None else dp).update_many(s0 + done, m)
             done += m
+        return res
 
     if dp is not None:
         dist.barrier()          # the ranks finish filling their rings seconds apart: start the first exchange together
@@ -288,11 +296,13 @@ def timed_region(agent, dp, w, steps, warmup, step0=1):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(s0, steps)
+    res = run(s0, steps)
     torch.cuda.synchronize()
     if dp is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if last is not None:
+        last.append(res[-1])
     if dist.is_initialized() and dist.get_world_size() > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -360,7 +370,7 @@ def profiler_child(args, w):
     steps = 20 * w["gstep"]
     cmd = [tool, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out_dir, "-o", "p", "--", sys.executable,
            os.path.abspath(__file__), "--workload", args.workload, "--steps", str(steps), "--warmup", str(2 * w["gstep"]),
-           "--no-cpu-baseline", "--no-profiler", "--rng", args.rng, "--pipeline", str(args.pipeline)] + (["--no-graph"] if args.no_graph else [])
+           "--full", "--no-cpu-baseline", "--no-profiler", "--rng", args.rng, "--pipeline", str(args.pipeline)] + (["--no-graph"] if args.no_graph else [])
     env = dict(os.environ, TMPDIR="/tmp")
     try:
         r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -419,6 +429,29 @@ def push_leg(w):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, agent, metrics):
+    """--dump-outputs: what the last timed step computed, as its caller receives it — the update()'s returned tuple
+    (`metrics`, float64) and the parameters the step left (every network and target, and for SAC / TQC the actor's BatchNorm
+    statistics and log alpha; float32) — one DIR/<name>.npy each, at most 64 MB in all (the largest workload, TQC's five H = 512
+    critics and their targets, writes about 24 MB)."""
+    arrays = {"metrics": np.asarray(metrics, dtype=np.float64)}
+    views = [agent.actor] + ([agent.target_actor] if hasattr(agent, "target_actor") else []) + agent.critics + agent.target_critics
+    for v in views:
+        arrays[v.name] = v.flat()
+    if agent._sac:
+        for name in ("bn_running_mean", "bn_running_var", "log_alpha"):
+            arrays[name] = agent.actor._get(name)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_BUDGET_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -433,7 +466,13 @@ def main():
     ap.add_argument("--no-extra-legs", action="store_true", help="N > 1: skip the strong-scaling and cfg-5 (SAC) legs")
     ap.add_argument("--no-profiler", action="store_true", help="skip the rocprofv3 child run (kernel durations then come from HIP events)")
     ap.add_argument("--keep-profile", default=None, help="directory that keeps the child's rocprofv3 summary (kernel_stats.csv)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (its returned tuple, the parameters it left)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurement legs: rocprofv3 child, roofline and push legs, CPU baselines, the extra legs at N > 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)       # nothing above has touched the GPU
@@ -447,7 +486,7 @@ def main():
             print(json.dumps(dict(rank=rank, world=world, master=os.environ.get("MASTER_ADDR"), port=os.environ.get("MASTER_PORT"))))
         raise SystemExit(int(os.environ["GCRL_BENCH_SPAWN_ECHO"]) if rank == world - 1 else 0)
     prof, prof_why = None, "disabled (--no-profiler)" if args.no_profiler else "N > 1"
-    if world == 1 and not args.no_profiler and not int(os.environ.get("GCRL_FORCE_DP", "0")):
+    if args.full and world == 1 and not args.no_profiler and not int(os.environ.get("GCRL_FORCE_DP", "0")):
         prof, prof_why = profiler_child(args, WORKLOADS[args.workload])      # nothing above has touched the GPU
     # one rank per GPU; GCRL_DIST_BACKEND=gloo lets several ranks rehearse the DP path on ONE GPU
     backend = os.environ.get("GCRL_DIST_BACKEND", "nccl")
@@ -481,57 +520,50 @@ def main():
         # per-exchange Python loop); the fallback is taken only when asked for (GCRL_DP_PYTHON_EXCHANGE, gloo rehearsals)
         strict = backend == "nccl" and "GCRL_DIST_BACKEND" not in os.environ and not int(os.environ.get("GCRL_DP_PYTHON_EXCHANGE", "0"))
         dp = DataParallelUpdater(agent, require_native=strict) if (world > 1 or force_dp) else None
-        elapsed, next_step, extra_warm, run = timed_region(agent, dp, w, args.steps, args.warmup)
+        last_step = []
+        elapsed, next_step, extra_warm, run = timed_region(agent, dp, w, args.steps, args.warmup, last=last_step)
+        # the last timed step's returned tuple: finite, and (--dump-outputs) written out with the parameters it left
+        last = [float(x) for x in last_step[0]]
+        assert all(np.isfinite(last)), last
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, agent, last)
 
-        # ---- untimed measurement legs -------------------------------------------------------
-        # HER gather kernel: a hipEvent pair around every gather launch of 10 trainer cycles (on the launch stream)
-        her = agent.buffer.handle
-        check(lib.gcrl_her_profile_enable(her, 1))
-        run(next_step, 10 * gstep)
-        next_step += 10 * gstep
-        launches, ms, rows, dev_ms = C.c_int64(), C.c_double(), C.c_int64(), C.c_double()
-        check(lib.gcrl_her_profile_read(her, C.byref(launches), C.byref(ms), C.byref(rows), C.byref(dev_ms)))
-        check(lib.gcrl_her_profile_enable(her, 0))
-        # row-chain kernel: the engine's measurement hooks (plain launches, every row-chain launch bracketed by
-        # hipEvents on its stream + device clock stamps)
-        rc = None
-        if w["kind"] in ("DDPG", "TD3") and dp is None and w["H"] % 4 == 0:
-            check(lib.gcrl_agent_profile_enable(agent._h, 1))
+        if args.full:
+            # ---- untimed measurement legs -------------------------------------------------------
+            # HER gather kernel: a hipEvent pair around every gather launch of 10 trainer cycles (on the launch stream)
+            her = agent.buffer.handle
+            check(lib.gcrl_her_profile_enable(her, 1))
             run(next_step, 10 * gstep)
             next_step += 10 * gstep
-            n_l, ev_ms, clk_ms = C.c_int64(), C.c_double(), C.c_double()
-            check(lib.gcrl_agent_profile_read(agent._h, C.byref(n_l), C.byref(ev_ms), C.byref(clk_ms)))
-            check(lib.gcrl_agent_profile_enable(agent._h, 0))
-            if n_l.value:
-                rc = (n_l.value, ev_ms.value * 1e3 / n_l.value, clk_ms.value * 1e3 / n_l.value)
-        # a last metrics fetch proves the steps really ran to completion
-        last = [float(x) for x in (agent.update_many(next_step, 1)[0] if dp is None else dp.update(next_step))]
-        next_step += 1
-        assert all(np.isfinite(last)), last
+            launches, ms, rows, dev_ms = C.c_int64(), C.c_double(), C.c_int64(), C.c_double()
+            check(lib.gcrl_her_profile_read(her, C.byref(launches), C.byref(ms), C.byref(rows), C.byref(dev_ms)))
+            check(lib.gcrl_her_profile_enable(her, 0))
+            # row-chain kernel: the engine's measurement hooks (plain launches, every row-chain launch bracketed by
+            # hipEvents on its stream + device clock stamps)
+            rc = None
+            if w["kind"] in ("DDPG", "TD3") and dp is None and w["H"] % 4 == 0:
+                check(lib.gcrl_agent_profile_enable(agent._h, 1))
+                run(next_step, 10 * gstep)
+                next_step += 10 * gstep
+                n_l, ev_ms, clk_ms = C.c_int64(), C.c_double(), C.c_double()
+                check(lib.gcrl_agent_profile_read(agent._h, C.byref(n_l), C.byref(ev_ms), C.byref(clk_ms)))
+                check(lib.gcrl_agent_profile_enable(agent._h, 0))
+                if n_l.value:
+                    rc = (n_l.value, ev_ms.value * 1e3 / n_l.value, clk_ms.value * 1e3 / n_l.value)
+            # a last metrics fetch proves the steps really ran to completion
+            last = [float(x) for x in (agent.update_many(next_step, 1)[0] if dp is None else dp.update(next_step))]
+            next_step += 1
+            assert all(np.isfinite(last)), last
 
-        push = None
-        if rank == 0 and world == 1 and not force_dp:
-            try:
-                push = push_leg(w)
-            except Exception as e:   # noqa: BLE001  (a reporting leg never costs the headline line)
-                push = dict(error=f"{type(e).__name__}: {e}"[:300])
+            push = None
+            if rank == 0 and world == 1 and not force_dp:
+                try:
+                    push = push_leg(w)
+                except Exception as e:   # noqa: BLE001  (a reporting leg never costs the headline line)
+                    push = dict(error=f"{type(e).__name__}: {e}"[:300])
 
     out = None
     if rank == 0:
-        R = (2 * w["S"] + w["A"] + 2) * 4
-        alg_bytes_per_row = 2 * R                      # read the record + write the batch row
-        rows_per_launch = rows.value / max(1, launches.value)
-        ev_us = ms.value * 1e3 / max(1, launches.value)
-        ks = (prof or {}).get("kernel_stats", {})
-        g_us = ks.get("gather_main", {}).get("avg_us")
-        clock = "rocprofv3 kernel duration (child run of this command, profiler.command)" if g_us else \
-                f"HIP-event pair (profiler unavailable: {prof_why}); includes dispatch overhead"
-        use_us = g_us or ev_us
-        achieved = (alg_bytes_per_row * rows_per_launch) / (use_us * 1e-6) / 1e9 if use_us > 0 else 0.0
-        g_pmc = pmc_traffic(args.workload, "her_gather_update_kernel<false") or pmc_traffic(args.workload, "her_gather")
-        traffic = None
-        if g_pmc and g_pmc.get("rows_per_launch"):
-            traffic = g_pmc["hbm_bytes_per_launch_corrected"] / g_pmc["rows_per_launch"] * rows_per_launch
         sync_rate = args.steps / elapsed
         value = world * sync_rate
         out = {
@@ -553,19 +585,6 @@ def main():
                                 "sync_optimizer_steps_per_s (batch-%d-equivalent gradient steps)" % (w["B"], world, w["B"], w["B"], w["B"])),
             "sync_optimizer_steps_per_s": sync_rate,
             "warmup_extra_steps": extra_warm,
-            "roofline_gather": {"kernel": "her_gather_update_kernel<false> (a trainer cycle's main gather)", "bound": "hbm", "achieved": achieved,
-                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                                "traffic_source": (g_pmc or {}).get("source"),
-                                "avg_launch_us": use_us, "rows_per_launch": rows_per_launch,
-                                "algorithmic_bytes_per_row": alg_bytes_per_row, "timing": clock,
-                                "hip_event_us": ev_us, "hip_event_launches": launches.value,
-                                "achieved_hip_event": (alg_bytes_per_row * rows_per_launch) / (ev_us * 1e-6) / 1e9 if ev_us > 0 else None,
-                                "head_launch": ({"kernel": "her_gather_update_kernel<true>", "rows": head_batches(gstep, w["kind"]) * w["B"], **ks["gather_head"]} if "gather_head" in ks else None),
-                                "profiler": ks.get("gather_main"),
-                                "note": "a call's first launch gathers its first %d batches (indices read from the pinned upload block, carries the control "
-                                        "block) so that the first steps start while the host draws the rest; the main launch gathers the other "
-                                        "gradient_step - %d batches." % (head_batches(gstep, w["kind"]), head_batches(gstep, w["kind"])) + "  Below ~1e5 rows a launch is bounded by the ~1.3 us dispatch + two dependent "
-                                        "memory latencies, not by bandwidth (profiles/r03_gather_rows_curve.txt)"},
             "update_flops": {"gflop_per_step": flops_per_step(w) / 1e9,
                              "achieved_tflops": flops_per_step(w) * args.steps / elapsed / 1e12,
                              "peak_tflops": FP32_MFMA_PEAK_TF},
@@ -574,73 +593,101 @@ def main():
         if dp is not None:
             out["dp_exchange"] = dp.exchange
             out["dp_exchange_reason"] = getattr(dp, "exchange_reason", "")
-        # HER relabel + flush kernel: per episode read T*(2S+A+2+G)*4 B of staging, write (T + k(T-1)) rows of R bytes
-        T, G = 50, 3
-        ep_bytes = T * (2 * w["S"] + w["A"] + 2 + G) * 4 + (T + w["k"] * (T - 1)) * R
-        fl = {"kernel": "her_flush_kernel", "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_episode": ep_bytes,
-              "fill_rows_per_s": len(agent.buffer) / t_fill if t_fill > 0 else None,
-              "note": "launch-bound by construction: an episode is %d KB (0.01 us at 8 TB/s) against a ~10 us launch; a vector-env "
-                      "step's episodes share one launch (up to 8)" % (ep_bytes // 1024)}
-        for key, eps in (("flush_single", 1), ("flush_multi", 8)):
-            if key in ks:
-                us = ks[key]["avg_us"]
-                fl[key] = dict(episodes_per_launch=eps, **ks[key], achieved=eps * ep_bytes / (us * 1e-6) / 1e9, frac=eps * ep_bytes / (us * 1e-6) / 1e9 / HBM_PEAK_GBS)
-        if "flush_single" in fl:
-            fl["achieved"], fl["frac"] = fl["flush_single"]["achieved"], fl["flush_single"]["frac"]
-        if push is not None:
-            fl["push"] = push
-        out["roofline_flush"] = fl
-        if prof is not None:
-            out["profiler"] = {"tool": "rocprofv3 --kernel-trace --stats", "command": prof["command"], "steps": prof["steps"], "kernel_stats": ks}
-        else:
-            out["profiler"] = {"unavailable": prof_why}
-        if rc is not None and w["kind"] == "DDPG":
-            fl_ = chain_flops_per_launch(w)
-            r_pmc = pmc_traffic(args.workload, "rowchain")
-            r_us = ks.get("rowchain", {}).get("avg_us") or rc[1]
-            out["roofline"] = {
-                "kernel": "rowchain_ddpg_kernel", "bound": "mfma", "achieved": fl_ / (r_us * 1e-6) / 1e12,
-                "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": fl_ / (r_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TF,
-                "traffic": r_pmc["hbm_bytes_per_launch_corrected"] if r_pmc else None,
-                "traffic_source": (r_pmc or {}).get("source"),
-                "l2_to_cu_read_requests_per_launch": r_pmc.get("TCP_TCC_READ_REQ_sum") if r_pmc else None,
-                "avg_launch_us": r_us, "algorithmic_flops_per_launch": fl_,
-                "timing": "rocprofv3 kernel duration (child run of this command)" if "rowchain" in ks else "HIP-event pair (profiler unavailable)",
-                "profiler": ks.get("rowchain"),
-                "hip_event_us": rc[1], "hip_event_launches": rc[0], "device_clock_us": rc[2],
-                "share_of_step_time": r_us / (1e6 * elapsed / args.steps),
-                "note": "latency-bound chain (10 dependent 256-wide layer passes per phase, 128 of 256 CUs at B=256), see DESIGN.md §4"}
-            if "dw_adam" in ks:
-                # the step's other launch (round 5): every dW | db GEMM, the global-norm clip, Adam, Polyak, weight copies, metrics
-                S_, A_, H_, L_ = w["S"], w["A"], w["H"], w["L"]
-                n_par = (S_ * H_ + (L_ - 1) * H_ * H_ + H_ * A_ + L_ * H_ + A_) + ((S_ + A_) * H_ + (L_ - 1) * H_ * H_ + H_ + L_ * H_ + 1)   # actor + critic, weights and biases
-                o_us = ks["dw_adam"]["avg_us"]
-                out["optimiser_launch"] = {
-                    "kernel": "dw_adam_kernel (dW | db of both nets + clip + Adam + Polyak + [in][out] copies + metrics + control advance)",
-                    "bound": "latency (one cold operand round trip, two hand-offs through memory inside the launch)",
-                    "avg_launch_us": o_us, "profiler": ks["dw_adam"],
-                    "algorithmic_flops_per_launch": 2 * w["B"] * n_par, "achieved_tflops": 2 * w["B"] * n_par / (o_us * 1e-6) / 1e12,
-                    "algorithmic_bytes_per_launch": 28 * n_par + 2 * 4 * w["B"] * (w["H"] * 2 * w["L"]),
-                    "replaces": "gemm_batch_kernel<1,1,4> (7.2 us) + adam_pair_kernel (8.8 us): profiles/r04_kernel_stats_ddpg_pickplace_b256.csv",
-                    "share_of_step_time": o_us / (1e6 * elapsed / args.steps)}
-        else:
-            # many-kernel steps (TD3 / SAC / TQC): the step as a whole against the MFMA roofline, not one kernel
-            tf = flops_per_step(w) * args.steps / elapsed / 1e12
-            out["roofline"] = {"kernel": "whole update step (all launches; per-kernel shares in profiles/)", "bound": "mfma",
-                               "achieved": tf, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TF,
-                               "traffic": None, "timing": "algorithmic flops per step / measured step time"}
-        if not args.no_cpu_baseline and world == 1 and w.get("n_quantiles", 1) == 1:
-            out["cpu_baseline"] = cpu_baseline(w, pool, args.cpu_seconds)
-            out["speedup_vs_cpu_port"] = value / out["cpu_baseline"]["value"]
-            if w["cap"] > 100_000:
-                # BASELINE.md's sanity row is quoted with a 1e5-row deque: random.sample(deque) walks the deque, so the 1e6-row
-                # baseline above is slower for a reason that has nothing to do with the update arithmetic — report both
-                out["cpu_baseline_n1e5"] = cpu_baseline(dict(w, cap=100_000), pool, max(4.0, args.cpu_seconds / 2))
-                out["speedup_vs_cpu_port_n1e5"] = value / out["cpu_baseline_n1e5"]["value"]
+        if args.full:
+            R = (2 * w["S"] + w["A"] + 2) * 4
+            alg_bytes_per_row = 2 * R                      # read the record + write the batch row
+            rows_per_launch = rows.value / max(1, launches.value)
+            ev_us = ms.value * 1e3 / max(1, launches.value)
+            ks = (prof or {}).get("kernel_stats", {})
+            g_us = ks.get("gather_main", {}).get("avg_us")
+            clock = "rocprofv3 kernel duration (child run of this command, profiler.command)" if g_us else \
+                    f"HIP-event pair (profiler unavailable: {prof_why}); includes dispatch overhead"
+            use_us = g_us or ev_us
+            achieved = (alg_bytes_per_row * rows_per_launch) / (use_us * 1e-6) / 1e9 if use_us > 0 else 0.0
+            g_pmc = pmc_traffic(args.workload, "her_gather_update_kernel<false") or pmc_traffic(args.workload, "her_gather")
+            traffic = None
+            if g_pmc and g_pmc.get("rows_per_launch"):
+                traffic = g_pmc["hbm_bytes_per_launch_corrected"] / g_pmc["rows_per_launch"] * rows_per_launch
+            out["roofline_gather"] = {"kernel": "her_gather_update_kernel<false> (a trainer cycle's main gather)", "bound": "hbm", "achieved": achieved,
+                                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                                      "traffic_source": (g_pmc or {}).get("source"),
+                                      "avg_launch_us": use_us, "rows_per_launch": rows_per_launch,
+                                      "algorithmic_bytes_per_row": alg_bytes_per_row, "timing": clock,
+                                      "hip_event_us": ev_us, "hip_event_launches": launches.value,
+                                      "achieved_hip_event": (alg_bytes_per_row * rows_per_launch) / (ev_us * 1e-6) / 1e9 if ev_us > 0 else None,
+                                      "head_launch": ({"kernel": "her_gather_update_kernel<true>", "rows": head_batches(gstep, w["kind"]) * w["B"], **ks["gather_head"]} if "gather_head" in ks else None),
+                                      "profiler": ks.get("gather_main"),
+                                      "note": "a call's first launch gathers its first %d batches (indices read from the pinned upload block, carries the control "
+                                              "block) so that the first steps start while the host draws the rest; the main launch gathers the other "
+                                              "gradient_step - %d batches." % (head_batches(gstep, w["kind"]), head_batches(gstep, w["kind"])) + "  Below ~1e5 rows a launch is bounded by the ~1.3 us dispatch + two dependent "
+                                              "memory latencies, not by bandwidth (profiles/r03_gather_rows_curve.txt)"}
+            # HER relabel + flush kernel: per episode read T*(2S+A+2+G)*4 B of staging, write (T + k(T-1)) rows of R bytes
+            T, G = 50, 3
+            ep_bytes = T * (2 * w["S"] + w["A"] + 2 + G) * 4 + (T + w["k"] * (T - 1)) * R
+            fl = {"kernel": "her_flush_kernel", "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_episode": ep_bytes,
+                  "fill_rows_per_s": len(agent.buffer) / t_fill if t_fill > 0 else None,
+                  "note": "launch-bound by construction: an episode is %d KB (0.01 us at 8 TB/s) against a ~10 us launch; a vector-env "
+                          "step's episodes share one launch (up to 8)" % (ep_bytes // 1024)}
+            for key, eps in (("flush_single", 1), ("flush_multi", 8)):
+                if key in ks:
+                    us = ks[key]["avg_us"]
+                    fl[key] = dict(episodes_per_launch=eps, **ks[key], achieved=eps * ep_bytes / (us * 1e-6) / 1e9, frac=eps * ep_bytes / (us * 1e-6) / 1e9 / HBM_PEAK_GBS)
+            if "flush_single" in fl:
+                fl["achieved"], fl["frac"] = fl["flush_single"]["achieved"], fl["flush_single"]["frac"]
+            if push is not None:
+                fl["push"] = push
+            out["roofline_flush"] = fl
+            if prof is not None:
+                out["profiler"] = {"tool": "rocprofv3 --kernel-trace --stats", "command": prof["command"], "steps": prof["steps"], "kernel_stats": ks}
+            else:
+                out["profiler"] = {"unavailable": prof_why}
+            if rc is not None and w["kind"] == "DDPG":
+                fl_ = chain_flops_per_launch(w)
+                r_pmc = pmc_traffic(args.workload, "rowchain")
+                r_us = ks.get("rowchain", {}).get("avg_us") or rc[1]
+                out["roofline"] = {
+                    "kernel": "rowchain_ddpg_kernel", "bound": "mfma", "achieved": fl_ / (r_us * 1e-6) / 1e12,
+                    "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": fl_ / (r_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TF,
+                    "traffic": r_pmc["hbm_bytes_per_launch_corrected"] if r_pmc else None,
+                    "traffic_source": (r_pmc or {}).get("source"),
+                    "l2_to_cu_read_requests_per_launch": r_pmc.get("TCP_TCC_READ_REQ_sum") if r_pmc else None,
+                    "avg_launch_us": r_us, "algorithmic_flops_per_launch": fl_,
+                    "timing": "rocprofv3 kernel duration (child run of this command)" if "rowchain" in ks else "HIP-event pair (profiler unavailable)",
+                    "profiler": ks.get("rowchain"),
+                    "hip_event_us": rc[1], "hip_event_launches": rc[0], "device_clock_us": rc[2],
+                    "share_of_step_time": r_us / (1e6 * elapsed / args.steps),
+                    "note": "latency-bound chain (10 dependent 256-wide layer passes per phase, 128 of 256 CUs at B=256), see DESIGN.md §4"}
+                if "dw_adam" in ks:
+                    # the step's other launch (round 5): every dW | db GEMM, the global-norm clip, Adam, Polyak, weight copies, metrics
+                    S_, A_, H_, L_ = w["S"], w["A"], w["H"], w["L"]
+                    n_par = (S_ * H_ + (L_ - 1) * H_ * H_ + H_ * A_ + L_ * H_ + A_) + ((S_ + A_) * H_ + (L_ - 1) * H_ * H_ + H_ + L_ * H_ + 1)   # actor + critic, weights and biases
+                    o_us = ks["dw_adam"]["avg_us"]
+                    out["optimiser_launch"] = {
+                        "kernel": "dw_adam_kernel (dW | db of both nets + clip + Adam + Polyak + [in][out] copies + metrics + control advance)",
+                        "bound": "latency (one cold operand round trip, two hand-offs through memory inside the launch)",
+                        "avg_launch_us": o_us, "profiler": ks["dw_adam"],
+                        "algorithmic_flops_per_launch": 2 * w["B"] * n_par, "achieved_tflops": 2 * w["B"] * n_par / (o_us * 1e-6) / 1e12,
+                        "algorithmic_bytes_per_launch": 28 * n_par + 2 * 4 * w["B"] * (w["H"] * 2 * w["L"]),
+                        "replaces": "gemm_batch_kernel<1,1,4> (7.2 us) + adam_pair_kernel (8.8 us): profiles/r04_kernel_stats_ddpg_pickplace_b256.csv",
+                        "share_of_step_time": o_us / (1e6 * elapsed / args.steps)}
+            else:
+                # many-kernel steps (TD3 / SAC / TQC): the step as a whole against the MFMA roofline, not one kernel
+                tf = flops_per_step(w) * args.steps / elapsed / 1e12
+                out["roofline"] = {"kernel": "whole update step (all launches; per-kernel shares in profiles/)", "bound": "mfma",
+                                   "achieved": tf, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TF,
+                                   "traffic": None, "timing": "algorithmic flops per step / measured step time"}
+            if not args.no_cpu_baseline and world == 1 and w.get("n_quantiles", 1) == 1:
+                out["cpu_baseline"] = cpu_baseline(w, pool, args.cpu_seconds)
+                out["speedup_vs_cpu_port"] = value / out["cpu_baseline"]["value"]
+                if w["cap"] > 100_000:
+                    # BASELINE.md's sanity row is quoted with a 1e5-row deque: random.sample(deque) walks the deque, so the 1e6-row
+                    # baseline above is slower for a reason that has nothing to do with the update arithmetic — report both
+                    out["cpu_baseline_n1e5"] = cpu_baseline(dict(w, cap=100_000), pool, max(4.0, args.cpu_seconds / 2))
+                    out["speedup_vs_cpu_port_n1e5"] = value / out["cpu_baseline_n1e5"]["value"]
         print(json.dumps(out))
         sys.stdout.flush()
 
-    if world > 1 and not args.no_extra_legs:
+    if world > 1 and args.full and not args.no_extra_legs:
         # Extra legs AFTER the headline line is out (a leg that fails or hangs can no longer cost it); their results go to
         # stderr as one line.  After each leg every rank learns whether all ranks finished it (MIN over a flag): a rank-local
         # failure ends the legs on every rank together instead of leaving the others inside a collective.

@@ -5,6 +5,7 @@
 # Per kernel and launch: FETCH_SIZE (x2 on gfx950 for wide coalesced reads, MI355X_MICROARCH.md §HBM),
 # WRITE_SIZE, and the L2 request / hit / miss and L1->L2 read-request counts when the tool lists them.
 set -e
+root=$(cd "$(dirname "$0")/.." && pwd)
 tag=${1:-pmc}; shift || true
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
@@ -18,7 +19,7 @@ pass() {  # name, counters...
   done
   if [ -z "$have" ]; then echo "pass $name: none of [$*] listed, skipped"; return 0; fi
   echo "pass $name:$have"
-  rocprofv3 --kernel-trace --pmc $have --output-format csv -d $out/$name -o p -- python3 $GRAFT_REPO_ROOT/bench.py --no-graph --no-cpu-baseline --no-profiler --steps 200 --warmup 40 $BENCH_ARGS > $out/$name.log 2>&1
+  rocprofv3 --kernel-trace --pmc $have --output-format csv -d $out/$name -o p -- python3 $root/bench.py --full --no-graph --no-cpu-baseline --no-profiler --steps 200 --warmup 40 $BENCH_ARGS > $out/$name.log 2>&1
 }
 BENCH_ARGS="$*"
 pass fetch FETCH_SIZE

@@ -11,10 +11,10 @@ out=gpurun_out/$tag
 mkdir -p $out
 timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/bench_driver_cmd.json 2> $out/bench_driver_cmd.err
 echo "driver cmd: $(grep -o '"value": [0-9.]*' $out/bench_driver_cmd.json | head -1)"
-timeout -k 10 500 python bench.py --keep-profile $out/prof_ddpg_pickplace_b256 > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 500 python bench.py --full --keep-profile $out/prof_ddpg_pickplace_b256 > $out/bench_default.json 2> $out/bench_default.err
 echo "default: $(grep -o '"value": [0-9.]*' $out/bench_default.json | head -1)"
 for w in ddpg_reach_b256 ddpg_reach_b1024 td3_pickplace_b2048 sac_slide_b512 tqc_push_b2048 tqc_quantile_push_b2048; do
-  timeout -k 10 500 python bench.py --no-cpu-baseline --workload $w --steps 1000 --warmup 120 --keep-profile $out/prof_$w 2>/dev/null | tail -1 > $out/bench_$w.json
+  timeout -k 10 500 python bench.py --full --no-cpu-baseline --workload $w --steps 1000 --warmup 120 --keep-profile $out/prof_$w 2>/dev/null | tail -1 > $out/bench_$w.json
   echo "$w $(grep -o '"value": [0-9.]*' $out/bench_$w.json | head -1) $(grep -o '"ms_per_step": [0-9.]*' $out/bench_$w.json | head -1)"
 done
 root=$PWD
