@@ -36,6 +36,7 @@
 #include "rowchain.h"
 #include "sac_heads.h"
 #include "xchg_ipc.h"
+#include "pop.h"
 
 using namespace gcrl;
 
@@ -179,6 +180,7 @@ struct gcrl_agent {
   // the dW | db GEMMs, the clip and the optimiser step of the row-chain DDPG step as ONE launch (dw_adam.hip; GCRL_NO_OPT_FUSE=1: the
   // two launches): per net [critic 0 | actor] two arrays of of_stride 64-bit norm slots and a launch count on its own line
   bool opt_fuse = false, opt_fuse_can = false;
+  long long of_wgs = 0;       // workgroups of the fused optimiser launch of the overlapped step (2 nets x the wider net's tiles)
   float *of_slots = nullptr, *of_seq = nullptr;
   long long of_stride = 0;
   float* rc_bar = nullptr;    // meeting counters of the row blocks [2][nblk][32 words]
@@ -984,7 +986,7 @@ int enqueue_phases(gcrl_agent* a, hipStream_t st, int variant, int mask) {
 // identical steps is replayed with a single launch
 int run_step(gcrl_agent* a, hipStream_t st, int variant, int mask, int count = 1) {
   if (a->rowchain && a->wt_dirty) TRY(rc_rebuild_wt(a, st));
-  if (!graph_on(a)) {
+  if (!graph_on(a) || pop_recording()) {
     for (int c = 0; c < count; ++c) TRY(enqueue_phases(a, st, variant, mask));
     return GCRL_OK;
   }
@@ -1435,6 +1437,7 @@ int build(gcrl_agent* a) {
       a->opt_fuse_can = a->rowchain && kind_ok && L + 1 <= kFusedMaxLayers && form1 && B < 2048 &&
                         std::max(tc, ta) <= 256LL * kFusedMaxSlotsPerThread && 2 * std::max(tc, ta) <= cap;
       a->opt_fuse = a->opt_fuse_can && !meet_device_shared() && !std::getenv("GCRL_NO_OPT_FUSE");
+      a->of_wgs = 2 * std::max(tc, ta);
       if (a->opt_fuse_can) {
         wants.push_back({&a->of_slots, (long long)(C + 1) * 2 * a->of_stride * 2});
         wants.push_back({&a->of_seq, (long long)(C + 1) * 32});
@@ -2403,3 +2406,5 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
 }
 
 }  // extern "C"
+
+#include "agent_pop.inc"

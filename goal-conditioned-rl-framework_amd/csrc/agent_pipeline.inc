@@ -241,7 +241,7 @@ int run_ddpg_pipe(gcrl_agent* a, hipStream_t st, int what_flags, int seg = -1, i
     }
     return GCRL_OK;
   };
-  if (!graph_on(a) || a->prof) return enqueue(st);
+  if (!graph_on(a) || a->prof || pop_recording()) return enqueue(st);
   const int key = 0x100000 | what_flags | ((seg + 1) << 5) | (n << 8);
   auto it = a->graphs.find(key);
   if (it == a->graphs.end()) {

@@ -8,6 +8,7 @@
 
 #include "adam_math.h"
 #include "meet.h"
+#include "pop.h"
 
 namespace gcrl {
 namespace {
@@ -90,205 +91,16 @@ struct DwAdamK {
 };
 
 __global__ __launch_bounds__(256, 5) void dw_adam_kernel(DwAdamK a) {
-#ifdef GCRL_OF_STAMPS
-  unsigned long long of_t[5];
-#endif
-  OF_STAMP(0);
-  __shared__ float s_ss[4];
-  __shared__ double dred[4];
-  __shared__ float s_coef;
-  __shared__ float tile_p[16][17], tile_t[16][17];
-  const DwNetK& on = a.net[blockIdx.y];
-  DwNetHead o = on.h;          // first round trip: 16 dwords
-  pin(o);
-  if ((int)blockIdx.x >= o.ntiles) return;   // (a paired launch is sized for the larger net; uniform per workgroup, before any barrier)
-  // XCD-aware workgroup -> tile order (gemm_mfma.h xcd_tile_of, here for the 2-D grid: workgroup (x, y) runs on XCD
-  // (x + y * gridDim.x) % 8): an XCD takes a contiguous range of the net's tiles — whole tile rows of a layer, i.e. that layer's
-  // activations enter ONE L2 instead of eight.  A wrong guess about the placement costs speed, never correctness.
-  const unsigned long long t_start = wall_clock64();
-  int bid = (int)blockIdx.x;
-  {
-    const int per = o.ntiles >> 3;
-    if (bid < (per << 3)) bid = ((bid + (int)blockIdx.y * o.grid_x) & 7) * per + (bid >> 3);
-  }
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  const int pi = (bid >= o.tile0[0]) + (bid >= o.tile0[1]) + (bid >= o.tile0[2]) + (bid >= o.tile0[3]);
-  const int t0 = pi == 0 ? 0 : o.tile0[0] * (pi == 1) + o.tile0[1] * (pi == 2) + o.tile0[2] * (pi == 3) + o.tile0[3] * (pi == 4);
-  // second round trip: the problem, the net's arrays, the step's scalars (the control block's copy, written by the launch in front)
-  // and the launch count — the last two through the scalar cache (constant address space): uniform, and nothing in this launch
-  // writes them before they are read
-  DwProb pr = on.prob[pi];
-  DwNetPtrs ptr = on.ptr;
-  StepCtrl c = load_uniform(o.cur);
-  unsigned long long sq = load_uniform(reinterpret_cast<const unsigned long long*>(o.seq));
-  pin(pr); pin(ptr); pin(c); pin(sq);   // (all four requested, then waited for together)
-  gfloat* const gp = (gfloat*)ptr.p; gfloat* const gm = (gfloat*)ptr.m; gfloat* const gv = (gfloat*)ptr.v; gfloat* const gt = (gfloat*)ptr.target;
-  gfloat* const gwt = (gfloat*)ptr.wt; gfloat* const gwtt = (gfloat*)ptr.wt_target;
-  gu64* const gslots = (gu64*)o.slots;
-  const unsigned int seq = (unsigned int)sq, fault = (unsigned int)(sq >> 32);   // (fault: the test hook gcrl_agent_debug_meet_fault — workgroup 1's slot never arrives, once)
-  const int t = bid - t0;
-  const int tn = t % pr.tiles_n, tm = t / pr.tiles_n;
-  const int m0 = tm << 4, n0 = tn << 4;
-  const int in = pr.in, out = pr.out;   // the problem is [out][in | 1]: column `in` is the bias gradient
-  struct { long long pw, pb, wt_dst; int slot0; } lay = {pr.pw, pr.pb, pr.wt_dst, pr.slot0};
+  const unsigned bx = blockIdx.x, by = blockIdx.y;
+#include "dw_adam_body.inc"
+}
 
-  const AdamStepScalars sc = adam_scalars(c, o.which);
-  const int em = m0 + 4 * lg + wave, en = n0 + li;   // this lane's element of the tile (gemm_batch_tile's k-split layout)
-  long long my_i = -1;
-  if (em < out) {
-    if (en < in) my_i = lay.pw + (long long)em * in + en;
-    else if (en == in) my_i = lay.pb + em;
-  }
-  const bool pk = ptr.target && o.polyak;
-
-  // the problem as the batched launch's tile body wants it (agent.hip bwd_dw): everything else of the record is a literal here
-  GemmDesc d;
-  d.A = pr.G; d.a_rs = 1; d.a_cs = pr.ldg;
-  d.B = pr.X + (pr.x_slot ? (long long)c.batch_slot * pr.x_slot : 0); d.b_rs = pr.ldx; d.b_cs = 1;
-  // (ones_col through an opaque register: as a literal, the compiler turned the tile body's `ones column ? 1 : loaded value` selects
-  // into a branch around the B loads of every chunk and drained the loads in flight — s_waitcnt vmcnt(0) — at each of them)
-  int one = 1;
-  asm volatile("" : "+s"(one));
-  d.C = pr.dW; d.c_rs = pr.in; d.col_out = pr.db; d.ones_col = one;
-  d.M = pr.out; d.N = pr.in + 1; d.K = pr.K;
-  d.bias = nullptr; d.H = nullptr; d.h_rs = 0; d.epi = EPI_NONE; d.mul = MUL_NONE;
-  d.slot = nullptr; d.a_slot = d.b_slot = d.c_slot = d.h_slot = 0;
-  d.sumsq_out = nullptr; d.bn_part = nullptr;
-  d.a_vec = d.b_vec = d.a_rvec = d.b_rvec = 0;   // (operands are batch-major: k runs along rows)
-  d.tile0 = 0; d.tiles_n = pr.tiles_n; d.ntiles = 0x7fffffff;
-  d.shape_hint = 0; d.ksplit = 0; d.kpart = nullptr; d.kticket = nullptr;
-  float x, ss;
-  OF_STAMP(1);
-  gemm_batch_tile<1, 1, 4>(d, t, x, ss);   // (the gradient element is also stored: get("grad:...") reads it)
-
-  // the tile's sum of squares in the order adam_kernel adds up the batched launch's four per-wave partials of a tile
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
-  if (lane == 0) s_ss[wave] = ss;
-  __syncthreads();
-  gu64* mine = gslots + (long long)(seq & 1u) * o.slot_stride;
-  if (threadIdx.x == 0 && !(fault && bid == 1)) {
-    const double dt = ((double)s_ss[0] + (double)s_ss[1]) + ((double)s_ss[2] + (double)s_ss[3]);
-    const int slot = lay.slot0 + t;
-    __hip_atomic_store(mine + slot, (unsigned long long)__double_as_longlong(dt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
-    gslots[(long long)((seq & 1u) ^ 1u) * o.slot_stride + slot] = kSlotEmpty;   // nobody reads the other array in this launch; the kernel boundary publishes it
-  }
-  // this lane's parameter, moments and target: requested now, they arrive while the slots are awaited.  (In front of the tile body
-  // they cost it a round trip: its k-loop's header waits for every load in flight — the registers its loads return in are reused
-  // per iteration — and so the operand requests went out only after these had landed.)
-  float pre_p = 0.f, pre_m = 0.f, pre_v = 0.f, pre_t = 0.f;
-  if (my_i >= 0) {
-    pre_p = gp[my_i]; pre_m = gm[my_i]; pre_v = gv[my_i];
-    if (pk) pre_t = gt[my_i];
-  }
-  OF_STAMP(2);
-  // riders of the net's first workgroup, while the other workgroups' slots arrive
-  float* met = a.metrics + (long long)c.metrics_slot * kMetricFloats;
-  if (bid == 0) {
-    if (on.mean_x) rider_mean_metric(on.mean_x, on.mean_n, on.mean_scale, met + on.mean_index);
-    if (on.td_q) rider_td_metrics(on.td_q, on.td_y, on.td_n, on.td_C, on.td_loss_kind, met);
-  }
-  // ||g||: the net's slots summed in ONE order (thread t: slots t, t + 256, ...; then lanes, then waves), in fp64.  Nets of
-  // >= kLeaderMinTiles tiles: only the first eight workgroups of the net — one per XCD under round-robin dispatch — sweep the
-  // slots; each leaves the sum in a result word (again its own flag), and every other workgroup polls the ONE word of the leader
-  // that shares its XCD.  With every workgroup sweeping every slot the early finishers kept ~5 MB of slot loads per round in
-  // flight in front of the operand loads of the workgroups still working (measured: the last tile done at 10-15 us instead of
-  // 7.5); a leader's sweep is 37 lines.  Smaller nets: every workgroup sweeps (a few KB in all).
-  {
-    const bool lead_mode = a.leaders && o.ntiles >= kLeaderMinTiles;
-    const bool sweeper = !lead_mode || blockIdx.x < 8;
-    const int xc = ((int)blockIdx.x + (int)blockIdx.y * o.grid_x) & 7;
-    gu64* res = mine + (o.slot_stride - 8);
-    bool ok = true;
-    double s = 0.0;
-    if (sweeper) {
-      // a lane re-loads only the slots it has not seen yet
-      unsigned long long w[kFusedMaxSlotsPerThread];
-      int spins = 0;
-      for (int i = 0; i < a.poll_first_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-      for (int i = 0; i < 4096 && (long long)(wall_clock64() - t_start) < (long long)a.poll_gate; ++i) __builtin_amdgcn_s_sleep(2);
-#pragma unroll
-      for (int u = 0; u < kFusedMaxSlotsPerThread; ++u) {
-        const int i = (int)threadIdx.x + 256 * u;
-        w[u] = i < o.ntiles ? __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-      }
-      for (;;) {
-        bool all = true;
-#pragma unroll
-        for (int u = 0; u < kFusedMaxSlotsPerThread; ++u) all = all && w[u] != kSlotEmpty;
-        if (all) break;
-        if (++spins >= kMeetSpinMax) { ok = false; break; }
-        for (int i = 0; i < a.poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-        for (int u = 0; u < kFusedMaxSlotsPerThread; ++u)
-          if (w[u] == kSlotEmpty) w[u] = __hip_atomic_load(mine + (int)threadIdx.x + 256 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int u = 0; u < kFusedMaxSlotsPerThread; ++u)
-        if ((int)threadIdx.x + 256 * u < o.ntiles) s += __longlong_as_double((long long)w[u]);
-      if (!ok) s = __longlong_as_double(0x7ff8000000000000ll);   // a slot never arrived: the step is poisoned (and reported below)
-      s = wave_sum_d(s);
-      if (lane == 0) dred[wave] = s;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        s = dred[0] + dred[1] + dred[2] + dred[3];
-        if (lead_mode) {
-          __hip_atomic_store(res + xc, (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
-          gslots[(long long)((seq & 1u) ^ 1u) * o.slot_stride + (o.slot_stride - 8) + xc] = kSlotEmpty;
-        }
-      }
-    } else if (threadIdx.x == 0) {
-      // (measured: four polls in flight, a quarter of a round trip apart, instead of one at a time — no gain, 52.5-52.7 vs
-      // 52.2 us/step: the hop costs the store's way to the memory side plus one load round trip, not the sampling period)
-      unsigned long long w = __hip_atomic_load(res + xc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int spins = 0; w == kSlotEmpty; ) {
-        if (++spins >= kMeetSpinMax) { ok = false; w = 0x7ff8000000000000ull; break; }
-        for (int i = 0; i < a.poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-        w = __hip_atomic_load(res + xc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      s = __longlong_as_double((long long)w);
-    }
-    if (!ok && a.status) __hip_atomic_fetch_or(a.status, (unsigned int)MEET_ERR_DW_ADAM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // the host learns it (meet.h)
-    if (threadIdx.x == 0) {
-      float post;
-      s_coef = clip_coef(s, c.grad_scale, ptr.clip, &post);
-      if (bid == 0 && a.metrics) met[on.metric_index] = post;
-    }
-  }
-  __syncthreads();
-  OF_STAMP(3);
-  const float gmul = c.grad_scale * s_coef;
-  float p_new = 0.f, t_new = 0.f;
-  if (my_i >= 0) {
-    const AdamElem e = adam_elem(x, pre_p, pre_m, pre_v, gmul, sc, a.beta2, a.w1, a.w2, a.eps);
-    gp[my_i] = e.p; gm[my_i] = e.m; gv[my_i] = e.v;
-    p_new = e.p;
-    if (pk) { t_new = polyak_elem(a.tau, e.p, a.one_m_tau, pre_t); gt[my_i] = t_new; }
-  }
-  if (lay.wt_dst >= 0) {   // (uniform per workgroup) the [in][out] copy of a hidden layer's weight: 16 consecutive outputs per run
-    tile_p[4 * lg + wave][li] = p_new;
-    tile_t[4 * lg + wave][li] = t_new;
-    __syncthreads();
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    const int k = n0 + ty, oo = m0 + tx;
-    if (k < in && oo < out) {
-      const long long at = lay.wt_dst + (long long)k * out + oo;
-      gwt[at] = tile_p[tx][ty];
-      if (pk && ptr.wt_target) gwtt[at] = tile_t[tx][ty];
-    }
-  }
-  OF_STAMP(4);
-#ifdef GCRL_OF_STAMPS
-  if (a.stamps && threadIdx.x == 0)
-    for (int k = 0; k < 5; ++k) a.stamps[((long long)blockIdx.y * 2048 + blockIdx.x) * 8 + k] = of_t[k];
-#endif
-  if (bid == 0 && threadIdx.x == 0) {
-    ((gu32*)o.seq)[1] = 0u;
-    ((gu32*)o.seq)[0] = seq + 1u;   // every workgroup of this launch read it before it published, and this workgroup has seen every slot
-    if (blockIdx.y == 0 && a.advance) ctrl_advance(a.advance);
-  }
+// population form (agent.hip gcrl_pop_*): member blockIdx.z runs its own arguments tab[blockIdx.z]; its norm slots, launch count and
+// control block are its own, so the members' workgroups never wait for each other
+__global__ __launch_bounds__(256, 5) void dw_adam_pop_kernel(const DwAdamK* __restrict__ tab) {
+  const DwAdamK& a = tab[blockIdx.z];
+  const unsigned bx = blockIdx.x, by = blockIdx.y;
+#include "dw_adam_body.inc"
 }
 
 }  // namespace
@@ -342,7 +154,22 @@ int launch_dw_adam(hipStream_t st, DwAdamArgs& a) {
   }
   // (the residency of widest * nnets workgroups is the caller's admission check — dw_adam_capacity — made once per agent)
   for (int i = 0; i < a.nnets; ++i) k.net[i].h.grid_x = widest;
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
+    return pop_record(r, POP_DW_ADAM, 0, dim3((unsigned)widest, (unsigned)a.nnets), 0, &k, sizeof(k), [k, g = dim3((unsigned)widest, (unsigned)a.nnets)](hipStream_t s) -> int {
+      hipLaunchKernelGGL(dw_adam_kernel, g, dim3(256), 0, s, k);
+      GCRL_HIP(hipGetLastError());
+      return GCRL_OK;
+    });
   hipLaunchKernelGGL(dw_adam_kernel, dim3((unsigned)widest, (unsigned)a.nnets), dim3(256), 0, st, k);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+long long dw_adam_pop_capacity() { return meet_capacity((const void*)dw_adam_pop_kernel, 256, 0); }
+
+int launch_dw_adam_pop(hipStream_t st, const void* tab, int members, dim3 grid) {
+  GCRL_CHECK_ARG(members >= 1 && members <= 65535 && grid.y >= 1 && grid.y <= 2 && grid.z == 1, "dw_adam population: bad launch");
+  hipLaunchKernelGGL(dw_adam_pop_kernel, dim3(grid.x, grid.y, (unsigned)members), dim3(256), 0, st, static_cast<const DwAdamK*>(tab));
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "gemm_tiled.h"
+#include "pop.h"
 
 namespace gcrl {
 
@@ -175,6 +176,10 @@ int gemm_prepare_ksplit(GemmDesc& d) {
 
 int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape) {
   GCRL_CHECK_ARG(n >= 1 && n <= kMaxProb, "launch_gemm_batch: %d problems (max %d)", n, kMaxProb);
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    std::vector<GemmDesc> v(descs, descs + n);
+    return pop_defer(r, [v, shape](hipStream_t s) mutable { return launch_gemm_batch(s, v.data(), (int)v.size(), shape); });
+  }
   int shapes[kMaxProb];
   for (int i = 0; i < n; ++i) {
     GemmDesc& d = descs[i];

@@ -8,6 +8,7 @@
 #include "ops.h"
 #include "adam_math.h"
 #include "meet.h"
+#include "pop.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,6 +35,18 @@ __global__ void begin_step_kernel(CtrlBlock* cb, int shift) {
   if (threadIdx.x == 0) {
     const int c = cb->cursor;
     if (shift) cb->prev = cb->cur;
+    cb->cur = cb->table[c];
+    cb->cursor = c + 1;
+  }
+}
+
+// population form (agent.hip gcrl_pop_*): workgroup m advances member m's control block
+struct BeginStepPop { CtrlBlock* cb; int shift; };
+__global__ void begin_step_pop_kernel(const BeginStepPop* __restrict__ tab) {
+  if (threadIdx.x == 0) {
+    CtrlBlock* cb = tab[blockIdx.x].cb;
+    const int c = cb->cursor;
+    if (tab[blockIdx.x].shift) cb->prev = cb->cur;
     cb->cur = cb->table[c];
     cb->cursor = c + 1;
   }
@@ -426,7 +439,18 @@ __global__ void polyak_kernel(const float* p, float* tp, long long n, float tau,
 static inline unsigned reduce_threads(long long n) { return (unsigned)std::min<long long>(1024, std::max<long long>(256, (n + 63) / 64 * 64)); }
 
 int launch_begin_step(hipStream_t st, CtrlBlock* cb, int shift) {
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    const BeginStepPop b{cb, shift};
+    return pop_record(r, POP_BEGIN_STEP, 0, dim3(1), 0, &b, sizeof(b), [cb, shift](hipStream_t s) { return launch_begin_step(s, cb, shift); });
+  }
   hipLaunchKernelGGL(begin_step_kernel, dim3(1), dim3(64), 0, st, cb, shift);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_begin_step_pop(hipStream_t st, const void* tab, int members) {
+  GCRL_CHECK_ARG(members >= 1, "begin_step population: %d members", members);
+  hipLaunchKernelGGL(begin_step_pop_kernel, dim3((unsigned)members), dim3(64), 0, st, static_cast<const BeginStepPop*>(tab));
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
@@ -491,6 +515,7 @@ int launch_sumsq2(hipStream_t st, const float* g0, long long n0, float* partial0
 }
 
 int launch_adam(hipStream_t st, const AdamArgs& a) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [a](hipStream_t s) { return launch_adam(s, a); });   // (pop.h)
   GCRL_CHECK_ARG(a.nets >= 1 && a.nets <= kMaxCritics, "adam: bad net count %d", a.nets);
   const unsigned rider = (a.mean_x || a.td_q) ? 1u : 0u;   // (the riders' own workgroup: adam_kernel)
   hipLaunchKernelGGL(adam_kernel, dim3((a.n_seg ? (unsigned)a.seg_blocks : adam_blocks(a.n)) + rider, a.nets), dim3(256), 0, st, a);
@@ -499,6 +524,7 @@ int launch_adam(hipStream_t st, const AdamArgs& a) {
 }
 
 int launch_adam_pair(hipStream_t st, const AdamArgs& a0, const AdamArgs& a1) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [a0, a1](hipStream_t s) { return launch_adam_pair(s, a0, a1); });   // (pop.h)
   GCRL_CHECK_ARG(a0.nets == 1 && a1.nets == 1, "adam_pair: single-net argument sets only");
   const unsigned b0 = a0.n_seg ? (unsigned)a0.seg_blocks : adam_blocks(a0.n);
   const unsigned b1 = a1.n_seg ? (unsigned)a1.seg_blocks : adam_blocks(a1.n);

@@ -89,6 +89,27 @@ class _AlphaView:
         return float(buf[0])
 
 
+def native_config(kind: int, obs_dim: int, ac_dim: int, config, gradient_step: int, *, num_critics: int = 1, top_drop: int = 0,
+                  n_quantiles: int = 1, device_index: int = 0, use_graph=True, pipeline=True, seed=None) -> _ffi.AgentConfig:
+    """The engine's gcrl_agent_config of an agent (no device work)."""
+    return _ffi.AgentConfig(
+        kind=kind, obs_dim=obs_dim, ac_dim=ac_dim, hidden_dim=config.hidden_dim,
+        layer_count=config.layer_count, batch_size=config.batch_size,
+        num_critics=num_critics, top_drop=top_drop,
+        ac_update_freq=config.ac_update_freq, gradient_step=gradient_step, polyak_every=40,
+        gamma=config.gamma, tau=config.tau,
+        grad_clip=-1.0 if config.grad_clip is None else float(config.grad_clip),
+        policy_noise=config.policy_noise, noise_clamp=config.noise_clamp,
+        actor_lr=config.actor_lr, actor_lr_min=config.actor_lr_min,
+        critic_lr=config.critic_lr, critic_lr_min=config.critic_lr_min,
+        alpha_lr=float(getattr(config, "alpha_lr", 0.0003)),
+        ac_scheduler_steps=config.ac_scheduler_steps, cr_scheduler_steps=config.cr_scheduler_steps,
+        alpha_min_steps=float(getattr(config, "alpha_min_steps", 10000)),
+        device=device_index, use_graph=int(use_graph), pipeline_steps=(2 if pipeline is True else int(pipeline)),
+        n_quantiles=n_quantiles,
+        seed=0 if seed is None else int(seed))
+
+
 class _EngineAgent:
     KIND_NAME = "DDPG"
     TD_INDEX = {6: 2, 4: 1}  # position of td_error in the tuple, by tuple length
@@ -96,7 +117,7 @@ class _EngineAgent:
     def __init__(self, obs_dim: int, ac_dim: int, config, weights, nenvs: int, gradient_step: int, *,
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
-                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1):
+                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1, _member=None):
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
         self.device = "cuda"
@@ -130,23 +151,14 @@ class _EngineAgent:
         if self.n_quantiles > 1 and kind == 3:
             self.num_critics = int(num_critics)
 
-        cfg = _ffi.AgentConfig(
-            kind=kind, obs_dim=obs_dim, ac_dim=ac_dim, hidden_dim=config.hidden_dim,
-            layer_count=config.layer_count, batch_size=config.batch_size,
-            num_critics=self.num_critics, top_drop=self.top_quantiles_to_drop if kind == 3 else 0,
-            ac_update_freq=config.ac_update_freq, gradient_step=self.gradient_step, polyak_every=40,
-            gamma=config.gamma, tau=config.tau,
-            grad_clip=-1.0 if config.grad_clip is None else float(config.grad_clip),
-            policy_noise=config.policy_noise, noise_clamp=config.noise_clamp,
-            actor_lr=config.actor_lr, actor_lr_min=config.actor_lr_min,
-            critic_lr=config.critic_lr, critic_lr_min=config.critic_lr_min,
-            alpha_lr=float(getattr(config, "alpha_lr", 0.0003)),
-            ac_scheduler_steps=config.ac_scheduler_steps, cr_scheduler_steps=config.cr_scheduler_steps,
-            alpha_min_steps=float(getattr(config, "alpha_min_steps", 10000)),
-            device=device_index, use_graph=int(use_graph), pipeline_steps=(2 if pipeline is True else int(pipeline)),
-            n_quantiles=self.n_quantiles,
-            seed=0 if seed is None else int(seed))
-        self._h = _ffi.check_ptr(lib.gcrl_agent_create(C.byref(cfg)), "gcrl_agent_create")
+        cfg = native_config(kind, obs_dim, ac_dim, config, self.gradient_step, num_critics=self.num_critics,
+                            top_drop=self.top_quantiles_to_drop if kind == 3 else 0, n_quantiles=self.n_quantiles,
+                            device_index=device_index, use_graph=use_graph, pipeline=pipeline, seed=seed)
+        if _member is None:
+            self._owner = None
+            self._h = _ffi.check_ptr(lib.gcrl_agent_create(C.byref(cfg)), "gcrl_agent_create")
+        else:   # a population member (src/population.py): the population made the handle and owns it
+            self._owner, self._h = _member(cfg)
         self._metric_cache: dict[int, list[float]] = {}
         self._live = collections.deque()      # (ticket, n) of returned tuples, oldest first
         self._lazy: dict[int, list] = {}      # ticket -> weak references to its unresolved LazyScalars
@@ -199,7 +211,7 @@ class _EngineAgent:
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
-        if h:
+        if h and getattr(self, "_owner", None) is None:
             lib.gcrl_agent_destroy(h)
 
     def set_meetings(self, on: bool = True) -> int:

@@ -324,6 +324,21 @@ int gcrl_agent_update(gcrl_agent* a, gcrl_her* her, int64_t step,
  * tickets_out[n], tuple_len_out[n] optional. */
 int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
                         int64_t* tickets_out, int32_t* tuple_len_out, void* stream);
+/* DDPG populations: `members` (1..16) independent DDPG agents of equal shapes whose update steps share launches.  Members
+ * must share kind (DDPG), obs_dim, ac_dim, hidden_dim, layer_count, batch_size, num_critics, gradient_step, ac_update_freq,
+ * polyak_every, pipeline_steps (2: the row-chain step), use_graph (0 or 1) and device; they may differ in seed, gamma, tau,
+ * grad_clip and the learning-rate schedules.  A refusal names the field and happens before any device work.
+ * gcrl_pop_member: member i as a full agent handle, owned by the population (every gcrl_agent_* entry works on it).
+ * gcrl_pop_update_n: gcrl_agent_update_n(member i, rings[i], step0, n, ...) for every member, the members' launches of each
+ * stage issued together; each member computes bit for bit what its own gcrl_agent_update_n computes.  Batches are drawn
+ * from the rings in member order.  tickets_out / tuple_len_out: [members][n], optional. */
+typedef struct gcrl_pop gcrl_pop;
+gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members);
+int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out);
+int32_t gcrl_pop_size(const gcrl_pop* p);
+int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,
+                      int32_t* tuple_len_out, void* stream);
+void gcrl_pop_destroy(gcrl_pop* p);
 /* Metrics of a ticket, in the reference's tuple order, as fp32 (waits for that step only).
  * n = tuple length returned by the update. */
 int gcrl_agent_metrics(gcrl_agent* a, int64_t ticket, double* out_host, int n);

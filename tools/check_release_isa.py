@@ -26,7 +26,7 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--c
 # translation unit -> substrings of the (mangled) kernel names that must pass, and must be present
 UNITS = {
     "bn_slab.hip": ["bn_linear_fwd_slab_kernel", "bn_linear_bwd_slab_kernel", "bn_linear_bwd_slab_fold_kernel"],
-    "rowchain.hip": ["rowchain_split_kernel", "rowchain_ddpg_kernel", "rowchain_split_heads_kernel"],
+    "rowchain.hip": ["rowchain_split_kernel", "rowchain_ddpg_kernel", "rowchain_split_heads_kernel", "rowchain_ddpg_pop_kernel"],
     "rowtile.hip": ["rowtile_ddpg_kernel"],
     "gemm_mfma.hip": ["gemm_tiled_kernel"],
     "xchg_ipc.hip": ["xchg_two_shot_kernel"],
@@ -116,7 +116,7 @@ def scratch_report(asm_text, unit):
 # write-through store and every poll of it must bypass the L1: a plain store or load here would be a silent stale read.
 # The row groups of a BatchNorm slab (bn_slab.hip slab_exchange_df, round 5) exchange their column partials the same way: the row-split
 # instantiations (template argument NT = 1) must contain such stores and loads.
-def slot_report(asm_text, unit="dw_adam.hip", patterns=("dw_adam_kernel",)):
+def slot_report(asm_text, unit="dw_adam.hip", patterns=("dw_adam_kernel", "dw_adam_pop_kernel")):
     bad, lines = 0, []
     for name, body in kernels(asm_text):
         if not any(p in name for p in patterns):

@@ -1,0 +1,114 @@
+"""Aggregate update throughput of a DDPG population (src/population.py) against the same P agents stepped one after another in
+the same process.  One JSON line per (shape, P, form):
+
+    python tools/population_bench.py [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
+
+Each agent trains from its own HER ring of synthetic episodes, `gradient_step` (40) steps per update call as the trainer does
+(src/env.py:384-385).  Timing: hipEvents on the stream the updates run on, around `calls` calls after `warmup` untimed ones and
+a device synchronise; steps per member = calls x 40.  Forms: "population" (one DDPGPopulation.update_many per call) and
+"sequential" (each standalone DDPG's update_many per call, in member order)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import gcrl_amd  # noqa: E402
+from oracle import her_oracle  # noqa: E402
+from oracle.agent_oracle import make_config  # noqa: E402
+
+SHAPES = {   # bench.py WORKLOADS: ddpg_reach_b256 (cfg 1) and the ddpg_pickplace_b256 headline
+    "cfg1": dict(S=10, A=3, H=64, L=3, B=256),
+    "headline": dict(S=23, A=4, H=256, L=3, B=256),
+}
+GSTEP = 40
+
+
+def _cfgs(sh, P):
+    return [make_config("DDPG", hidden_dim=sh["H"], layer_count=sh["L"], batch_size=sh["B"], max_len=100_000, gamma=0.98,
+                        tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.1 * i), critic_lr=1e-3 * (1 + 0.1 * i)) for i in range(P)]
+
+
+def _fill(ag, sh, i):
+    gen = np.random.default_rng(1000 + i)
+    for ep in range(12):
+        for st in her_oracle.synthetic_episode(gen, 50, sh["S"], sh["A"]):
+            ag.push_her(ep % 2, *st)
+
+
+def _time(step_fn, calls, warmup):
+    for c in range(warmup):
+        step_fn(1 + c * GSTEP)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for c in range(calls):
+        step_fn(1 + (warmup + c) * GSTEP)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / 1e3, time.perf_counter() - t0
+
+
+def run(shape, P, calls, warmup):
+    sh = SHAPES[shape]
+    cfgs = _cfgs(sh, P)
+    seeds = list(range(7, 7 + P))
+    out = []
+    pop = gcrl_amd.DDPGPopulation(sh["S"], sh["A"], cfgs, 2, GSTEP, rng="engine", seeds=seeds)
+    for i, m in enumerate(pop.members):
+        _fill(m, sh, i)
+    forms = [m.meetings() for m in pop.members]
+    dev_s, wall_s = _time(lambda s0: pop.update_many(s0, GSTEP), calls, warmup)
+    out.append(dict(form="population", dev_s=dev_s, wall_s=wall_s, member_meeting_forms=forms[0]))
+    del pop
+    solo = [gcrl_amd.DDPG(sh["S"], sh["A"], c, None, nenvs=2, gradient_step=GSTEP, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
+    for i, a in enumerate(solo):
+        _fill(a, sh, i)
+
+    def seq(s0):
+        for a in solo:
+            a.update_many(s0, GSTEP)
+    dev_s, wall_s = _time(seq, calls, warmup)
+    out.append(dict(form="sequential", dev_s=dev_s, wall_s=wall_s, member_meeting_forms=solo[0].meetings()))
+    del solo
+    steps = calls * GSTEP
+    for r in out:
+        r.update(shape=shape, members=P, steps_per_member=steps, calls=calls, warmup_calls=warmup,
+                 agg_steps_per_s=round(P * steps / r["dev_s"], 1), us_per_step_per_member=round(r["dev_s"] / (P * steps) * 1e6, 3),
+                 **{k: sh[k] for k in ("S", "A", "H", "L", "B")})
+        r["dev_s"], r["wall_s"] = round(r["dev_s"], 6), round(r["wall_s"], 6)
+    out[0]["speedup_vs_sequential"] = round(out[1]["dev_s"] / out[0]["dev_s"], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="cfg1,headline")
+    ap.add_argument("--members", default="1,2,4,8")
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert a.calls * GSTEP >= 2000 or os.environ.get("POP_BENCH_SHORT"), "at least 2 000 timed steps per member"
+    f = open(a.out, "a") if a.out else None
+    for shape in a.shapes.split(","):
+        for P in [int(x) for x in a.members.split(",")]:
+            for r in run(shape, P, a.calls, a.warmup):
+                line = json.dumps(r)
+                print(line, flush=True)
+                if f:
+                    f.write(line + "\n")
+                    f.flush()
+    if f:
+        f.close()
+
+
+if __name__ == "__main__":
+    main()
