@@ -566,6 +566,19 @@ int sac_actor_forwards(gcrl_agent* a, hipStream_t st, int variant, bool with_cur
 // launch itself idles the GPU ~8 us).  use_graph = 2 forces graphs everywhere.
 // (SAC keeps ~35 BatchNorm / head launches per step around its two row-block launches: graphs stay on)
 // (SyncBN: the statistics exchanges sit between a step's launches — plain launches only)
+// Row-chain form decisions of the build that gcrl_pop_create must know before any device work (agent_pop.inc): one definition each.
+// Rows per workgroup / 4: the fewest that keep a launch within one wave of blocks (DDPG launches both phases together).
+int row_rg_of(int kind, int B) {
+  const int phases = kind == GCRL_AGENT_DDPG ? 2 : 1;
+  int rg = 1;
+  while (rg < 4 && phases * ((B + 4 * rg - 1) / (4 * rg)) > 256) rg *= 2;
+  if (const char* e = std::getenv("GCRL_ROW_RG")) rg = std::max(1, std::min(4, std::atoi(e)));   // experiment knob
+  return rg;
+}
+// TD3's critic phase as role-parallel launches once the batch fills the chip (cfg 3: 183.5 -> 178.4 us/step; below that the fused
+// launch is the shorter chain)
+bool td3_split_k_rule(int B, int rg) { return (B + 4 * rg - 1) / (4 * rg) >= 256 && !std::getenv("GCRL_NO_SPLIT_TD3"); }
+
 bool graph_on(const gcrl_agent* a) {
   if (a->bn_sync.world > 1 && !a->bn_xchg_h) return false;   // (an exchange that is a kernel of the sequence replays like any other)
   return a->cfg.use_graph >= 2 || (a->cfg.use_graph == 1 && (!a->rowchain || a->sac));
@@ -1365,11 +1378,7 @@ int build(gcrl_agent* a) {
     a->wt_net[2] = 2 * align_up(per_a, 64); a->wt_net[3] = a->wt_net[2] + C * a->wt_cstride;
     wants.push_back({&a->wt, a->wt_net[3] + C * a->wt_cstride});
     a->row_ldl = round_up(std::max(H, a->ldx), 4) + 4;
-    // fewest rows per block that keep a launch within one wave of blocks (DDPG launches both phases together)
-    const int phases = c.kind == GCRL_AGENT_DDPG ? 2 : 1;
-    a->row_rg = 1;
-    while (a->row_rg < 4 && phases * ((B + 4 * a->row_rg - 1) / (4 * a->row_rg)) > 256) a->row_rg *= 2;
-    if (const char* e = std::getenv("GCRL_ROW_RG")) a->row_rg = std::max(1, std::min(4, std::atoi(e)));   // experiment knob
+    a->row_rg = row_rg_of(c.kind, B);
     a->rowchain = (c.kind == GCRL_AGENT_DDPG || c.kind == GCRL_AGENT_TD3 || c.kind == GCRL_AGENT_SAC) && H % 4 == 0 &&
                   c.pipeline_steps >= 2 &&
                   rowchain_lds_bytes(a->row_rg, a->row_ldl, A, H, C) <= 160 * 1024;
@@ -1386,9 +1395,7 @@ int build(gcrl_agent* a) {
                     rowchain_merge_ok(a->row_rg, a->row_ldl, A, H, C, B);
       if (a->rc_merge) { a->rc_bar_words = 2 * nblk * 32; wants.push_back({&a->rc_bar, a->rc_bar_words}); }
     }
-    // TD3 once the batch fills the chip (cfg 3: 183.5 -> 178.4 us/step; below that the fused launch is the shorter chain)
-    a->split_k = a->rowchain && c.kind == GCRL_AGENT_TD3 && C == 2 && (B + 4 * a->row_rg - 1) / (4 * a->row_rg) >= 256 &&
-                 !std::getenv("GCRL_NO_SPLIT_TD3");
+    a->split_k = a->rowchain && c.kind == GCRL_AGENT_TD3 && C == 2 && td3_split_k_rule(B, a->row_rg);
     // ... and its two launches (forward | backward) as ONE: the online-critic workgroups go on to their backward chains once the
     // target roles of their rows have reported in (producers / consumers: no residency requirement, meet.h)
     a->rc_merge_k = a->split_k && !meet_device_shared() && !std::getenv("GCRL_NO_RC_MERGE");

@@ -1,10 +1,10 @@
-// agent_pop.inc — DDPG populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
+// agent_pop.inc — DDPG and TD3 populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
 //
-// P independent DDPG agents of equal shapes whose update steps share launches.  Each member is an ordinary gcrl_agent (its own
+// P independent DDPG or TD3 agents of one kind and equal shapes whose update steps share launches.  Each member is an ordinary gcrl_agent (its own
 // parameters, optimiser state, control block, metric ring and meeting counters), so every single-agent entry works on it.  A
 // population call records each member's launch sequence of the call (pop.h: the launchers record instead of launching), then
 // issues position k of all sequences together: one launch of the kernel's population form (rowchain_ddpg_pop_kernel,
-// dw_adam_pop_kernel, begin_step_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
+// dw_adam_pop_kernel, begin_step_pop_kernel, gemm_batch_pop_kernel<1, 1, 4>, adam_pop_kernel, adam_pair_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
 // arithmetic in the same order as the member's own launch, so each member computes bit for bit what it computes alone.
 // Launches without a population form are issued member by member at their position.
 //
@@ -15,6 +15,7 @@ struct gcrl_pop {
   std::vector<gcrl_agent*> m;
   std::map<std::string, void*> tabs;   // device argument tables of the population launches, by content (they repeat call after call)
   std::vector<PopRec> rec;
+  int64_t merged = 0, alone = 0;       // recorded positions issued as one population launch / member by member (gcrl_pop_launch_counts)
 };
 
 namespace {
@@ -59,26 +60,33 @@ int pop_issue(gcrl_pop* p, size_t k, hipStream_t st) {
     ops[i] = &p->rec[i].ops[k];
     const PopOp& o = *ops[i];
     const PopOp& o0 = *ops[0];
-    merge = merge && o.kind != POP_ALONE && o.kind == o0.kind && o.sub == o0.sub && o.grid.x == o0.grid.x && o.grid.y == o0.grid.y &&
+    merge = merge && pop_mergeable(o.kind, o.sub) && o.kind == o0.kind && o.sub == o0.sub && o.grid.x == o0.grid.x && o.grid.y == o0.grid.y &&
             o.grid.z == o0.grid.z && o.lds == o0.lds && o.args.size() == o0.args.size();
   }
   if (!merge || P == 1) {
     for (const PopOp* o : ops) TRY(o->issue(st));
+    p->alone++;
     return GCRL_OK;
   }
   void* tab = nullptr;
   TRY(pop_table(p, ops, st, &tab));
   const PopOp& o = *ops[0];
+  p->merged++;
   switch (o.kind) {
     case POP_ROWCHAIN: return launch_rowchain_ddpg_pop(st, tab, (int)P, o.sub, o.grid, o.lds);
     case POP_DW_ADAM: return launch_dw_adam_pop(st, tab, (int)P, o.grid);
     case POP_BEGIN_STEP: return launch_begin_step_pop(st, tab, (int)P);
+    case POP_GEMM_BATCH: return launch_gemm_batch_pop(st, tab, (int)P, o.sub, o.grid);
+    case POP_ADAM: return launch_adam_pop(st, tab, (int)P, o.grid);
+    case POP_ADAM_PAIR: return launch_adam_pair_pop(st, tab, (int)P, o.grid);
     default: return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: launch kind %d has no population form", o.kind);
   }
 }
 
 // record member a's launches of m planned steps (stream capture around the recording: a launch that bypassed the recorder would
-// land in the captured graph instead of running out of order — refused below)
+// land in the captured graph instead of running out of order — refused below).  DDPG: the overlapped schedule of
+// gcrl_agent_update_n (run_steps_ddpg); TD3: its per-step phases with the variant bits gcrl_agent_update_n gives them on the
+// row-chain path (every step pre-advanced, its last launch advancing the control block)
 int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>& plans, PopRec* rec) {
   rec->ops.clear();
   std::vector<int> variants(plans.size());
@@ -86,7 +94,12 @@ int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>&
   GCRL_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
   pop_rec() = rec;
   g_pop_recorders.fetch_add(1);
-  const int rc = run_steps_ddpg(a, cs, variants.data(), (int)variants.size(), /*first_pre=*/true);
+  int rc = GCRL_OK;
+  if (a->cfg.kind == GCRL_AGENT_TD3) {
+    for (size_t i = 0; i < variants.size() && !rc; ++i) rc = run_step(a, cs, variants[i] | norm_bits(a) | V_ADV | V_PRE, 7, 1);
+  } else {
+    rc = run_steps_ddpg(a, cs, variants.data(), (int)variants.size(), /*first_pre=*/true);
+  }
   g_pop_recorders.fetch_sub(1);
   pop_rec() = nullptr;
   hipGraph_t g = nullptr;
@@ -123,20 +136,28 @@ gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) {
   if (members < 1 || members > kMaxPopMembers) return bad("members", "a population has 1..16 members");
   for (int i = 0; i < members; ++i) {
     const gcrl_agent_config& c = cfgs[i];
-    if (c.kind != GCRL_AGENT_DDPG) return bad("kind", "populations are DDPG only (TD3 / SAC / TQC populations are not implemented)");
+    if (c.kind != GCRL_AGENT_DDPG && c.kind != GCRL_AGENT_TD3) return bad("kind", "populations are DDPG or TD3 (SAC / TQC populations are not implemented)");
     if (const char* f = pop_mismatch(cfgs[0], c)) return bad(f, "members must share kind, shapes, batch_size, gradient_step, ac_update_freq, polyak_every, pipeline_steps, use_graph and device");
     if (c.pipeline_steps != 2) return bad("pipeline_steps", "the population runs the row-chain DDPG step: pipeline_steps = 2");
     if (c.hidden_dim < 4 || c.hidden_dim % 4 != 0) return bad("hidden_dim", "the row-chain DDPG step needs hidden_dim % 4 == 0");
     if (c.ac_dim < 1 || c.ac_dim > 16 || c.obs_dim < 1 || c.layer_count < 1 || c.layer_count > 8 || c.batch_size < 1) return bad("shape", "bad obs_dim / ac_dim / layer_count / batch_size");
     if (c.use_graph >= 2) return bad("use_graph", "the population issues its launches itself (use_graph 0 or 1)");
   }
-  {   // the row-chain launch's LDS (agent.hip build: the same rule)
-    const gcrl_agent_config& c = cfgs[0];
-    const int H = c.hidden_dim, ldx = round_up(c.obs_dim + c.ac_dim, 4);
-    const int ldl = round_up(std::max(H, ldx), 4) + 4;
-    int rg = 1;
-    while (rg < 4 && 2 * ((c.batch_size + 4 * rg - 1) / (4 * rg)) > 256) rg *= 2;
-    if (rowchain_lds_bytes(rg, ldl, c.ac_dim, H, 1) > 160 * 1024) return bad("hidden_dim", "the row-chain launch of this shape does not fit the LDS");
+  const bool td3 = cfgs[0].kind == GCRL_AGENT_TD3;
+  const int C = td3 ? 2 : 1;
+  if (td3 && cfgs[0].num_critics != 2) return bad("num_critics", "a TD3 agent has two critics");
+  // the row-chain launch (agent.hip build: the same rules, row_rg_of / td3_split_k_rule): its rows per workgroup and LDS
+  const gcrl_agent_config& c0 = cfgs[0];
+  const int H = c0.hidden_dim, ldx = round_up(c0.obs_dim + c0.ac_dim, 4);
+  const int ldl = round_up(std::max(H, ldx), 4) + 4;
+  const int rg = row_rg_of(c0.kind, c0.batch_size);
+  if (rowchain_lds_bytes(rg, ldl, c0.ac_dim, H, C) > 160 * 1024) return bad("hidden_dim", "the row-chain launch of this shape does not fit the LDS");
+  if (td3) {
+    // TD3 at a batch that fills the chip runs forms without a population form: the split dW problems (B >= 2048) and the
+    // role-split critic phase (split_k / rc_merge_k: >= 256 row blocks)
+    if (c0.batch_size >= 2048) return bad("batch_size", "TD3 populations run batch_size < 2048 (the split dW form has no population form)");
+    if (td3_split_k_rule(c0.batch_size, rg))
+      return bad("batch_size", "at this batch TD3 runs the role-split critic phase (split_k / rc_merge_k), which has no population form");
   }
   gcrl_pop* p = new gcrl_pop;
   for (int i = 0; i < members; ++i) {
@@ -144,6 +165,10 @@ gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) {
     if (!a) { gcrl_pop_destroy(p); return nullptr; }
     p->m.push_back(a);
     if (!a->rowchain) { gcrl_pop_destroy(p); return bad("hidden_dim", "this configuration does not run the row-chain DDPG step"); }
+    if (td3 && i == 0 && (a->split_k || a->rc_merge_k || a->dw_split_c > 1 || a->dw_split_a > 1)) {
+      gcrl_pop_destroy(p);
+      return bad("batch_size", "this TD3 configuration runs the role-split critic phase or the split dW form, which have no population form");
+    }
   }
   p->rec.resize(members);
   return p;
@@ -157,6 +182,13 @@ int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out) {
 }
 
 int32_t gcrl_pop_size(const gcrl_pop* p) { return p ? (int32_t)p->m.size() : -1; }
+
+int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_launch_counts: null handle");
+  if (merged) *merged = p->merged;
+  if (alone) *alone = p->alone;
+  return GCRL_OK;
+}
 
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out, int32_t* tuple_len_out,
                       void* stream) {

@@ -465,21 +465,15 @@ __device__ __forceinline__ bool gemm_batch_tile(const GemmDesc& d, const int t, 
 
 template <int TM, int TN, int KSPLIT>
 __global__ __launch_bounds__(256) void gemm_batch_kernel(GemmBatch gb) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int bid = xcd_tile_of((int)blockIdx.x, (int)gridDim.x);
-  const int wtile = (KSPLIT == 4) ? bid : bid * 4 + wave;
-  const int pi = gemm_problem_of(gb, wtile);
-  const GemmDesc& d = gb.d[pi];
-  gemm_pin(d);
-  const int t = wtile - d.tile0;
-  float x, ss;
-  if (!gemm_batch_tile<TM, TN, KSPLIT>(d, t, x, ss)) return;
-  if (d.sumsq_out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
-    if (lane == 0) d.sumsq_out[(long long)t * KSPLIT + (KSPLIT == 4 ? wave : 0)] = ss;
-  }
+#include "gemm_batch_body.inc"
+}
+
+// population form (agent.hip gcrl_pop_*; gemm_mfma.hip instantiates <1, 1, 4>): member blockIdx.y runs its own problem set
+// tab[blockIdx.y] on the workgroups blockIdx.x of its single-agent launch
+template <int TM, int TN, int KSPLIT>
+__global__ __launch_bounds__(256) void gemm_batch_pop_kernel(const GemmBatch* __restrict__ tab) {
+  const GemmBatch& gb = tab[blockIdx.y];
+#include "gemm_batch_body.inc"
 }
 
 // 1: one 16x16 tile per workgroup with K split over its waves (the form that can produce bn_part), 2-4: larger forms

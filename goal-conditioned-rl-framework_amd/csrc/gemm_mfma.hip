@@ -2,14 +2,17 @@
 #include "gemm_mfma.h"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "gemm_tiled.h"
 #include "pop.h"
 
 namespace gcrl {
 
 namespace {
+// Every form's launch is prepared (tile bookkeeping in the GemmBatch, workgroup count) and then issued (issue_shape), so that a
+// population recording (pop.h) can hold the prepared launch of each form.
 template <int TM, int TN, int KSPLIT>
-int launch_shape(hipStream_t st, GemmBatch& gb) {
+int prep_shape(GemmBatch& gb) {
   int tiles = 0;
   for (int i = 0; i < gb.n; ++i) {
     GemmDesc& d = gb.d[i];
@@ -22,9 +25,7 @@ int launch_shape(hipStream_t st, GemmBatch& gb) {
   }
   const int grid = (KSPLIT == 4) ? tiles : (tiles + 3) / 4;
   for (int i = 0; i < kMaxProb; ++i) gb.tile0[i] = i < gb.n ? gb.d[i].tile0 : 0x7fffffff;
-  hipLaunchKernelGGL((gemm_batch_kernel<TM, TN, KSPLIT>), dim3(grid), dim3(256), 0, st, gb);
-  GCRL_HIP(hipGetLastError());
-  return GCRL_OK;
+  return grid;
 }
 
 // The tile shape is a function of the PROBLEM alone, never of what else shares the launch: the
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void gemm_outer_kernel(GemmBatch gb) {
     *(v4f*)(C + (long long)m * d.c_rs + n) = v;
   }
 }
-int launch_outer(hipStream_t st, GemmBatch& gb) {
+int prep_outer(GemmBatch& gb) {
   int wgs = 0;
   for (int i = 0; i < gb.n; ++i) {
     GemmDesc& d = gb.d[i];
@@ -128,12 +129,10 @@ int launch_outer(hipStream_t st, GemmBatch& gb) {
     wgs += d.ntiles;
   }
   for (int i = 0; i < kMaxProb; ++i) gb.tile0[i] = i < gb.n ? gb.d[i].tile0 : 0x7fffffff;
-  hipLaunchKernelGGL(gemm_outer_kernel, dim3(wgs), dim3(256), 0, st, gb);
-  GCRL_HIP(hipGetLastError());
-  return GCRL_OK;
+  return wgs;
 }
 
-int launch_tiled(hipStream_t st, GemmBatch& gb) {
+int prep_tiled(GemmBatch& gb) {
   static const bool trace = std::getenv("GCRL_GEMM_TRACE") != nullptr;
   if (trace) {
     std::fprintf(stderr, "[tiled] %d problems:", gb.n);
@@ -155,7 +154,23 @@ int launch_tiled(hipStream_t st, GemmBatch& gb) {
     tiles += d.ntiles;
   }
   for (int i = 0; i < kMaxProb; ++i) gb.tile0[i] = i < gb.n ? gb.d[i].tile0 : 0x7fffffff;
-  hipLaunchKernelGGL(gemm_tiled_kernel, dim3(tiles), dim3(256), 0, st, gb);
+  return tiles;
+}
+
+// workgroups of form `s` (1..5) for the prepared problem set (< 0: refused)
+int prep_form(int s, GemmBatch& gb) {
+  return s == 1 ? prep_shape<1, 1, 4>(gb)
+                : (s == 2 ? prep_shape<1, 1, 1>(gb) : (s == 3 ? prep_shape<2, 2, 1>(gb) : (s == 4 ? prep_tiled(gb) : prep_outer(gb))));
+}
+
+int issue_shape(hipStream_t st, int s, const GemmBatch& gb, int grid) {
+  switch (s) {
+    case 1: hipLaunchKernelGGL((gemm_batch_kernel<1, 1, 4>), dim3(grid), dim3(256), 0, st, gb); break;
+    case 2: hipLaunchKernelGGL((gemm_batch_kernel<1, 1, 1>), dim3(grid), dim3(256), 0, st, gb); break;
+    case 3: hipLaunchKernelGGL((gemm_batch_kernel<2, 2, 1>), dim3(grid), dim3(256), 0, st, gb); break;
+    case 4: hipLaunchKernelGGL(gemm_tiled_kernel, dim3(grid), dim3(256), 0, st, gb); break;
+    default: hipLaunchKernelGGL(gemm_outer_kernel, dim3(grid), dim3(256), 0, st, gb); break;
+  }
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
@@ -176,10 +191,6 @@ int gemm_prepare_ksplit(GemmDesc& d) {
 
 int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape) {
   GCRL_CHECK_ARG(n >= 1 && n <= kMaxProb, "launch_gemm_batch: %d problems (max %d)", n, kMaxProb);
-  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
-    std::vector<GemmDesc> v(descs, descs + n);
-    return pop_defer(r, [v, shape](hipStream_t s) mutable { return launch_gemm_batch(s, v.data(), (int)v.size(), shape); });
-  }
   int shapes[kMaxProb];
   for (int i = 0; i < n; ++i) {
     GemmDesc& d = descs[i];
@@ -201,15 +212,25 @@ int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape) {
   for (int i = 0; i < n; ++i) GCRL_CHECK_ARG(shapes[i] != 5 || outer_ok(descs[i]), "launch_gemm_batch: problem %d is not an aligned K = 1 outer product", i);
   for (int s = 1; s <= 5; ++s) {  // one launch per shape present (almost always exactly one)
     GemmBatch gb;
-    gb.n = 0;
+    std::memset(&gb, 0, sizeof(gb));   // (whole bytes: a population keys its device tables by the recorded argument bytes)
     for (int i = 0; i < n; ++i)
       if (shapes[i] == s) gb.d[gb.n++] = descs[i];
     if (gb.n == 0) continue;
-    int rc = s == 1 ? launch_shape<1, 1, 4>(st, gb)
-             : (s == 2 ? launch_shape<1, 1, 1>(st, gb)
-                       : (s == 3 ? launch_shape<2, 2, 1>(st, gb) : (s == 4 ? launch_tiled(st, gb) : launch_outer(st, gb))));
-    if (rc) return rc;
+    const int grid = prep_form(s, gb);
+    if (grid < 0) return grid;
+    if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h): each form's launch is one op
+      pop_record(r, POP_GEMM_BATCH, s, dim3((unsigned)grid), 0, &gb, sizeof(gb), [gb, s, grid](hipStream_t q) { return issue_shape(q, s, gb, grid); });
+      continue;
+    }
+    if (const int rc = issue_shape(st, s, gb, grid)) return rc;
   }
+  return GCRL_OK;
+}
+
+int launch_gemm_batch_pop(hipStream_t st, const void* tab, int members, int shape, dim3 grid) {
+  GCRL_CHECK_ARG(shape == 1 && members >= 1 && members <= 65535 && grid.y == 1 && grid.z == 1, "gemm_batch population: bad launch");
+  hipLaunchKernelGGL((gemm_batch_pop_kernel<1, 1, 4>), dim3(grid.x, (unsigned)members), dim3(256), 0, st, static_cast<const GemmBatch*>(tab));
+  GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
 

@@ -188,6 +188,7 @@ struct AdamArgs {
 };
 int launch_adam(hipStream_t st, const AdamArgs& a);
 int launch_adam_pair(hipStream_t st, const AdamArgs& a0, const AdamArgs& a1);  // two single-net steps, one launch
+struct AdamPairArgs { AdamArgs a0, a1; };   // a member's arguments of the paired launch's population form (pop.h)
 int launch_polyak(hipStream_t st, const float* p, float* target, long long n, double tau);
 
 // ---- dw_adam.hip: weight gradients + global-norm clip + Adam(W) (+ Polyak, [in][out] copies, metrics, control advance) of up

@@ -1,4 +1,4 @@
-// pop.h — launch recording of a DDPG population (agent.hip gcrl_pop_*).
+// pop.h — launch recording of a DDPG or TD3 population (agent.hip gcrl_pop_*).
 //
 // A population step issues each member's ordinary launch sequence with a recorder installed on the calling thread: the
 // launchers below then record the launch (its arguments, grid, LDS and a closure that would issue it alone) instead of
@@ -22,7 +22,12 @@ enum PopKind {
   POP_ROWCHAIN = 1,    // rowchain_ddpg_kernel<sub> (sub = rows per block / 4)
   POP_DW_ADAM = 2,     // dw_adam_kernel
   POP_BEGIN_STEP = 3,  // begin_step_kernel
+  POP_GEMM_BATCH = 4,  // one form's launch of launch_gemm_batch (sub = the form, 1..5; only form 1, gemm_batch_kernel<1, 1, 4>, merges)
+  POP_ADAM = 5,        // adam_kernel
+  POP_ADAM_PAIR = 6,   // adam_pair_kernel (args: AdamPairArgs)
 };
+// whether a recorded launch of this kind and sub has a population form
+inline bool pop_mergeable(int kind, int sub) { return kind != POP_ALONE && (kind != POP_GEMM_BATCH || sub == 1); }
 
 struct PopOp {
   int kind = POP_ALONE;
@@ -60,6 +65,9 @@ inline int pop_defer(PopRec* r, std::function<int(hipStream_t)> issue) {
 int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int rg, dim3 grid, size_t lds);
 int launch_dw_adam_pop(hipStream_t st, const void* tab, int members, dim3 grid);
 int launch_begin_step_pop(hipStream_t st, const void* tab, int members);
+int launch_gemm_batch_pop(hipStream_t st, const void* tab, int members, int shape, dim3 grid);
+int launch_adam_pop(hipStream_t st, const void* tab, int members, dim3 grid);
+int launch_adam_pair_pop(hipStream_t st, const void* tab, int members, dim3 grid);
 long long dw_adam_pop_capacity();   // workgroups of the population form resident at once (0: shared device / query failed)
 
 }  // namespace gcrl

@@ -324,20 +324,26 @@ int gcrl_agent_update(gcrl_agent* a, gcrl_her* her, int64_t step,
  * tickets_out[n], tuple_len_out[n] optional. */
 int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
                         int64_t* tickets_out, int32_t* tuple_len_out, void* stream);
-/* DDPG populations: `members` (1..16) independent DDPG agents of equal shapes whose update steps share launches.  Members
- * must share kind (DDPG), obs_dim, ac_dim, hidden_dim, layer_count, batch_size, num_critics, gradient_step, ac_update_freq,
+/* DDPG and TD3 populations: `members` (1..16) independent agents of one kind (DDPG or TD3) and equal shapes whose update steps
+ * share launches.  Members must share kind, obs_dim, ac_dim, hidden_dim, layer_count, batch_size, num_critics, gradient_step, ac_update_freq,
  * polyak_every, pipeline_steps (2: the row-chain step), use_graph (0 or 1) and device; they may differ in seed, gamma, tau,
- * grad_clip and the learning-rate schedules.  A refusal names the field and happens before any device work.
+ * grad_clip and the learning-rate schedules.  A refusal names the field and happens before any device work.  TD3 populations run
+ * batch_size < 2048 below the role-split critic phase (at most 255 row blocks, i.e. batch_size <= 1020); other TD3 configurations
+ * are refused naming batch_size.
  * gcrl_pop_member: member i as a full agent handle, owned by the population (every gcrl_agent_* entry works on it).
  * gcrl_pop_update_n: gcrl_agent_update_n(member i, rings[i], step0, n, ...) for every member, the members' launches of each
  * stage issued together; each member computes bit for bit what its own gcrl_agent_update_n computes.  Batches are drawn
- * from the rings in member order.  tickets_out / tuple_len_out: [members][n], optional. */
+ * from the rings in member order.  tickets_out / tuple_len_out: [members][n], optional.
+ * gcrl_pop_launch_counts: how the recorded launch positions of every gcrl_pop_update_n since creation were issued — `merged`: as one
+ * launch of the kernel's population form for all members; `alone`: member by member (a launch without a population form, members
+ * whose launches differ, or a one-member population).  Either pointer may be null. */
 typedef struct gcrl_pop gcrl_pop;
 gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members);
 int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out);
 int32_t gcrl_pop_size(const gcrl_pop* p);
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,
                       int32_t* tuple_len_out, void* stream);
+int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone);
 void gcrl_pop_destroy(gcrl_pop* p);
 /* Metrics of a ticket, in the reference's tuple order, as fp32 (waits for that step only).
  * n = tuple length returned by the update. */

@@ -87,7 +87,7 @@ def check_kernel(body):
 # by-value argument struct made hipcc copy the whole 3.7 KB struct to every thread's private memory — a 3 us kernel took 36 us
 # (rowchain_act_inline_kernel, round 4).  `.amdhsa_private_segment_fixed_size` says it all.
 SCRATCH_UNITS = ["her_ring.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "rowchain.hip", "agent.hip", "normalizer.hip", "abi_misc.hip",
-                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip"]
+                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip"]
 SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
     "rowchain_split_kernelILi4E": 64,   # 16 rows per workgroup: register spills; never selected by default (GCRL_ROW_RG=4)
     "gemm_tiled_kernel": 16,                                                   # three spilled dwords outside the k-loop

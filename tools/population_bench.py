@@ -1,12 +1,13 @@
-"""Aggregate update throughput of a DDPG population (src/population.py) against the same P agents stepped one after another in
-the same process.  One JSON line per (shape, P, form):
+"""Aggregate update throughput of a DDPG or TD3 population (src/population.py) against the same P agents stepped one after another
+in the same process.  One JSON line per (shape, P, form):
 
-    python tools/population_bench.py [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
+    python tools/population_bench.py [--kind DDPG|TD3] [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
 
 Each agent trains from its own HER ring of synthetic episodes, `gradient_step` (40) steps per update call as the trainer does
 (src/env.py:384-385).  Timing: hipEvents on the stream the updates run on, around `calls` calls after `warmup` untimed ones and
-a device synchronise; steps per member = calls x 40.  Forms: "population" (one DDPGPopulation.update_many per call) and
-"sequential" (each standalone DDPG's update_many per call, in member order)."""
+a device synchronise; steps per member = calls x 40.  Forms: "population" (one DDPGPopulation / TD3Population.update_many per
+call) and "sequential" (each standalone agent's update_many per call, in member order).  TD3 (--kind TD3; its lines carry
+"kind": "TD3") steps its actor every second step with target smoothing on (policy_noise 0.2, noise_clamp 0.5)."""
 import argparse
 import json
 import os
@@ -30,9 +31,14 @@ SHAPES = {   # bench.py WORKLOADS: ddpg_reach_b256 (cfg 1) and the ddpg_pickplac
 GSTEP = 40
 
 
-def _cfgs(sh, P):
-    return [make_config("DDPG", hidden_dim=sh["H"], layer_count=sh["L"], batch_size=sh["B"], max_len=100_000, gamma=0.98,
-                        tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.1 * i), critic_lr=1e-3 * (1 + 0.1 * i)) for i in range(P)]
+KINDS = {"DDPG": (gcrl_amd.DDPGPopulation, gcrl_amd.DDPG, {}),
+         "TD3": (gcrl_amd.TD3Population, gcrl_amd.TD3Agent, dict(ac_update_freq=2, policy_noise=0.2, noise_clamp=0.5))}
+
+
+def _cfgs(sh, P, kind="DDPG"):
+    return [make_config(kind, hidden_dim=sh["H"], layer_count=sh["L"], batch_size=sh["B"], max_len=100_000, gamma=0.98,
+                        tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.1 * i), critic_lr=1e-3 * (1 + 0.1 * i), **KINDS[kind][2])
+            for i in range(P)]
 
 
 def _fill(ag, sh, i):
@@ -56,19 +62,20 @@ def _time(step_fn, calls, warmup):
     return e0.elapsed_time(e1) / 1e3, time.perf_counter() - t0
 
 
-def run(shape, P, calls, warmup):
+def run(shape, P, calls, warmup, kind="DDPG"):
     sh = SHAPES[shape]
-    cfgs = _cfgs(sh, P)
+    cfgs = _cfgs(sh, P, kind)
     seeds = list(range(7, 7 + P))
     out = []
-    pop = gcrl_amd.DDPGPopulation(sh["S"], sh["A"], cfgs, 2, GSTEP, rng="engine", seeds=seeds)
+    pop_cls, agent_cls = KINDS[kind][:2]
+    pop = pop_cls(sh["S"], sh["A"], cfgs, 2, GSTEP, rng="engine", seeds=seeds)
     for i, m in enumerate(pop.members):
         _fill(m, sh, i)
     forms = [m.meetings() for m in pop.members]
     dev_s, wall_s = _time(lambda s0: pop.update_many(s0, GSTEP), calls, warmup)
     out.append(dict(form="population", dev_s=dev_s, wall_s=wall_s, member_meeting_forms=forms[0]))
     del pop
-    solo = [gcrl_amd.DDPG(sh["S"], sh["A"], c, None, nenvs=2, gradient_step=GSTEP, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
+    solo = [agent_cls(sh["S"], sh["A"], c, None, nenvs=2, gradient_step=GSTEP, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
     for i, a in enumerate(solo):
         _fill(a, sh, i)
 
@@ -84,12 +91,15 @@ def run(shape, P, calls, warmup):
                  agg_steps_per_s=round(P * steps / r["dev_s"], 1), us_per_step_per_member=round(r["dev_s"] / (P * steps) * 1e6, 3),
                  **{k: sh[k] for k in ("S", "A", "H", "L", "B")})
         r["dev_s"], r["wall_s"] = round(r["dev_s"], 6), round(r["wall_s"], 6)
+        if kind != "DDPG":
+            r["kind"] = kind
     out[0]["speedup_vs_sequential"] = round(out[1]["dev_s"] / out[0]["dev_s"], 3)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="DDPG", choices=sorted(KINDS))
     ap.add_argument("--shapes", default="cfg1,headline")
     ap.add_argument("--members", default="1,2,4,8")
     ap.add_argument("--calls", type=int, default=50)
@@ -100,7 +110,7 @@ def main():
     f = open(a.out, "a") if a.out else None
     for shape in a.shapes.split(","):
         for P in [int(x) for x in a.members.split(",")]:
-            for r in run(shape, P, a.calls, a.warmup):
+            for r in run(shape, P, a.calls, a.warmup, a.kind):
                 line = json.dumps(r)
                 print(line, flush=True)
                 if f:
