@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""The stand-in trainer loop (examples/trainer_standin.py; reference src/env.py:334-406) for a POPULATION: P independent DDPG or TD3
+agents, each with its own synthetic vector env, HER ring and normalisers, driven through the population's calls —
+
+    pop.observe_act -> P env steps -> pop.process_step -> every `max_episode` episodes: pop.update_many(gradient_step)
+
+— one launch per call and stage for all members instead of one per member.  Reports env steps/s and gradient steps/s in aggregate
+(over all members) and every member's success rate.
+
+    python examples/population_trainer.py --agent DDPG --members 4 --cycles 40
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from trainer_standin import PointReachVecEnv  # noqa: E402
+
+
+def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
+          seed=0, verbose=True):
+    import gcrl_amd
+    from gcrl_amd.src.synthetic import agent_config as make_config
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+
+    np.random.seed(seed)
+    envs = [PointReachVecEnv(num_envs, seed=seed + i) for i in range(members)]
+    e0 = envs[0]
+    # members of one shape; here they differ in seed and learning rate (a small sweep)
+    cfgs = [make_config(agent_name, hidden_dim=hidden, layer_count=layers, batch_size=batch, max_len=200_000, k_future=4, gamma=0.95,
+                        tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.25 * i), critic_lr=1e-3 * (1 + 0.25 * i),
+                        ac_update_freq=2 if agent_name == "TD3" else 1, policy_noise=0.2 if agent_name == "TD3" else 0.0)
+            for i in range(members)]
+    cls = dict(DDPG=gcrl_amd.DDPGPopulation, TD3=gcrl_amd.TD3Population)[agent_name]
+    pop = cls(e0.obs_dim + e0.goal_dim, e0.ac_dim, cfgs, num_envs, gradient_step, rng="engine", seeds=[seed + i for i in range(members)])
+    for m, env in zip(pop.members, envs):   # what GoalEnvHER.__init__ injects (src/env.py:93-105), device normalisers
+        m.buffer.obs_normalizer = DeviceRunningNormalizer(env.obs_dim)
+        m.buffer.dg_normalizer = DeviceRunningNormalizer(env.goal_dim)
+        m.buffer.compute_reward = env.compute_reward
+
+    states = [env.reset()[0] for env in envs]
+    grad_counter, env_steps = 1, 0
+    success = [[] for _ in range(members)]
+    t_env = t_upd = 0.0
+    t0 = time.perf_counter()
+    for cycle in range(1, cycles + 1):
+        episodes = 0
+        tc = time.perf_counter()
+        while episodes < max_episode:       # (episodes of member 0's env: all envs run the same fixed-length episodes)
+            actions = [np.asarray(a, np.float32) for a in pop.observe_act([s["observation"] for s in states], [s["desired_goal"] for s in states])]
+            stepped = [env.step(a) for env, a in zip(envs, actions)]
+            pop.process_step(states, actions, [s[0] for s in stepped], [s[1] for s in stepped], [s[2] for s in stepped])
+            env_steps += num_envs * members
+            nxt = []
+            for i, (env, (obs, _, term, trunc, _)) in enumerate(zip(envs, stepped)):
+                done = np.logical_or(term, trunc)
+                if done.any():
+                    idx = np.nonzero(done)[0]
+                    d = np.linalg.norm(obs["achieved_goal"][idx] - obs["desired_goal"][idx], axis=1)
+                    success[i].extend((d < env.thr).tolist())
+                    if i == 0:
+                        episodes += len(idx)
+                    env._reset(idx)
+                    obs = env._obs()
+                nxt.append(obs)
+            states = nxt
+        t_env += time.perf_counter() - tc
+        tu = time.perf_counter()
+        if all(m.is_buffer_filled() for m in pop.members):
+            infos = pop.update_many(grad_counter, gradient_step)
+            grad_counter += gradient_step
+            for info in infos:
+                float(info[-1][0])          # reads one metric per member: waits for the cycle's updates
+        t_upd += time.perf_counter() - tu
+        if verbose and cycle % 10 == 0:
+            print(f"cycle {cycle:4d}  success(last {max_episode} episodes) " + " ".join(f"{np.mean(s[-max_episode:]):.2f}" for s in success))
+    return dict(success=[float(np.mean(s[-10 * max_episode:])) for s in success], env_steps=env_steps,
+                gradient_steps=(grad_counter - 1) * members, wall_s=time.perf_counter() - t0, acting_counts=pop.acting_counts(),
+                env_steps_per_s=env_steps / max(t_env, 1e-9), gradient_steps_per_s=(grad_counter - 1) * members / max(t_upd, 1e-9))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agent", default="DDPG", choices=["DDPG", "TD3"])
+    ap.add_argument("--members", type=int, default=4)
+    ap.add_argument("--cycles", type=int, default=40)
+    ap.add_argument("--nenv", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed)
+    print(f"{args.agent} x {args.members}: success over the last 10 cycles " + " ".join(f"{s:.2f}" for s in out["success"]) +
+          f"; {out['env_steps']} env steps in aggregate ({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} "
+          f"gradient steps in aggregate ({out['gradient_steps_per_s']:.0f}/s in the update phase), {out['wall_s']:.1f} s; "
+          f"acting calls / launches {out['acting_counts'][:4]}")

@@ -127,6 +127,10 @@ PROTOTYPES = {
     "gcrl_pop_size": (C.c_int32, [_vp]),
     "gcrl_pop_update_n": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
     "gcrl_pop_launch_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_pop_observe_act": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "gcrl_pop_process_step": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_int32, C.c_int32, _vp, _vp]),
+    "gcrl_pop_acting_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_destroy": (None, [_vp]),
     "gcrl_agent_update_phase": (C.c_int, [_vp, _vp, _i64, C.c_int, C.POINTER(UpdateInputs), _f32, C.POINTER(_i64), _vp]),
     "gcrl_agent_grad_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_i64)]),

@@ -16,11 +16,33 @@ struct gcrl_pop {
   std::map<std::string, void*> tabs;   // device argument tables of the population launches, by content (they repeat call after call)
   std::vector<PopRec> rec;
   int64_t merged = 0, alone = 0;       // recorded positions issued as one population launch / member by member (gcrl_pop_launch_counts)
+  // acting side (gcrl_pop_observe_act, gcrl_pop_process_step; counts: gcrl_pop_acting_counts)
+  PopTabCache act_tabs;                // device tables of the members' RowActArgs
+  // fast form: one pinned, mapped block [noise | actions | flags | rows] for kPopActRows rows per member (rowchain.h RowActPop)
+  char *act_blk_host = nullptr, *act_blk_dev = nullptr;
+  unsigned long long act_seq = 0;
+  // staged form (more rows per member than the block holds): pinned staging and its device twin, batch_size rows per member
+  char *act_st_host = nullptr, *act_st_dev = nullptr;
+  std::vector<int64_t> act_ordered;    // per member: its `calls` when the acting stream last waited for its update work
+  PopProcStep proc;
+  int64_t act_calls = 0, act_launches = 0, act_staged = 0;
 };
 
 namespace {
 
 constexpr int kMaxPopMembers = 16;
+constexpr int kPopActRows = 32;   // rows per member the pinned block of gcrl_pop_observe_act holds (more: the staged form)
+
+// [members][stride_n] rows of S floats, noise and actions of A doubles, one flag per workgroup: offsets into one block (doubles first)
+struct PopActLayout {
+  size_t noise, out, flags, rows, bytes;
+  PopActLayout(int P, int stride_n, int S, int A) {
+    const size_t d = (size_t)P * stride_n * A * sizeof(double);
+    noise = 0; out = d; flags = 2 * d;
+    rows = flags + (size_t)P * ((stride_n + 3) / 4) * sizeof(unsigned long long);
+    bytes = rows + (size_t)P * stride_n * S * sizeof(float);
+  }
+};
 
 const char* pop_mismatch(const gcrl_agent_config& a, const gcrl_agent_config& b) {
 #define GCRL_POP_SAME(f) if (a.f != b.f) return #f;
@@ -247,9 +269,176 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
   return GCRL_OK;
 }
 
+int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
+                         const float* dg_host, int32_t goal_dim, int32_t n, const double* noise_host, const int32_t* modes, double* out_host,
+                         void* stream) {
+  // every refusal before any device work
+  GCRL_CHECK_ARG(obs_host, "gcrl_pop_observe_act: obs_host: null array");
+  GCRL_CHECK_ARG(dg_host, "gcrl_pop_observe_act: dg_host: null array");
+  GCRL_CHECK_ARG(modes, "gcrl_pop_observe_act: modes: null array");
+  GCRL_CHECK_ARG(out_host, "gcrl_pop_observe_act: out_host: null array");
+  GCRL_CHECK_ARG(modes[0] >= -1 && modes[0] <= 2, "gcrl_pop_observe_act: modes: member 0 has mode %d (-1 skipped, 0, 1 or 2)", modes[0]);
+  GCRL_CHECK_ARG(p, "gcrl_pop_observe_act: pop: null handle");
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  const int D = obs_dim, G = goal_dim, A = a0->A, S = a0->S;
+  GCRL_CHECK_ARG(n >= 1 && n <= a0->B, "gcrl_pop_observe_act: n: %d rows per member (1..batch_size = %d)", n, a0->B);
+  GCRL_CHECK_ARG(D >= 1 && G >= 0 && D + G == S, "gcrl_pop_observe_act: obs_dim %d + goal_dim %d != state_dim %d", D, G, S);
+  unsigned int live = 0, noisy = 0;
+  for (int i = 0; i < P; ++i) {
+    GCRL_CHECK_ARG(modes[i] >= -1 && modes[i] <= 2, "gcrl_pop_observe_act: modes: member %d has mode %d (-1 skipped, 0, 1 or 2)", i, modes[i]);
+    gcrl_normalizer* zo = nz_obs ? nz_obs[i] : nullptr;
+    gcrl_normalizer* zg = nz_dg ? nz_dg[i] : nullptr;
+    // the kernel indexes mean[j] / var[j] for j < obs_dim (goal_dim): a normaliser of another size is an argument error, never an out-of-bounds access
+    GCRL_CHECK_ARG(!zo || gcrl_normalizer_size(zo) == D, "gcrl_pop_observe_act: nz_obs: member %d's observation normaliser has size %d for obs_dim %d", i, gcrl_normalizer_size(zo), D);
+    GCRL_CHECK_ARG(!zg || gcrl_normalizer_size(zg) == G, "gcrl_pop_observe_act: nz_dg: member %d's goal normaliser has size %d for goal_dim %d", i, gcrl_normalizer_size(zg), G);
+    if (modes[i] >= 0) live |= 1u << i;
+    if (modes[i] == 1 && noise_host) noisy |= 1u << i;
+  }
+  GCRL_CHECK_ARG(4 * round_up(S, 4) <= 2 * kRowThreads || !(nz_obs || nz_dg), "gcrl_pop_observe_act: obs_dim: fused normalisation supports state_dim <= 128");
+  p->act_calls++;
+  const size_t oD = (size_t)n * D, oG = (size_t)n * G, oA = (size_t)n * A;
+  if (P == 1) {   // nothing to merge: the member's own entry
+    if (!live) return GCRL_OK;
+    return gcrl_agent_observe_act(a0, nz_obs ? nz_obs[0] : nullptr, nz_dg ? nz_dg[0] : nullptr, obs_host, D, dg_host, G, n, noise_host, modes[0], out_host, stream);
+  }
+  if (!live) return GCRL_OK;   // every member on the epsilon-random branch: no network, no launch
+  hipStream_t st = a0->pick(stream);
+  // after every member's last update call (DESIGN.md 4c: the event that closes a handle's update work), and on fresh [in][out] copies
+  p->act_ordered.resize(P, 0);
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    if (a->calls != p->act_ordered[i]) {
+      GCRL_HIP(hipStreamWaitEvent(st, a->call_ev[(a->calls - 1) % kEventRing], 0));
+      p->act_ordered[i] = a->calls;
+    }
+    if (((live >> i) & 1u) && a->wt_dirty) TRY(rc_rebuild_wt(a, st));
+  }
+  // the members' table: what belongs to the member (a skipped member keeps a slot; its post mode there is never read)
+  RowActArgs tab[kMaxPopMembers];
+  int fill = 1;
+  for (int i = P - 1; i >= 0; --i) if (modes[i] >= 0) fill = modes[i];   // (the first live member's mode: the table then repeats whoever is skipped)
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    RowActArgs& ra = tab[i];
+    std::memset(&ra, 0, sizeof(ra));
+    ra.actor = make_rownet(a, a->actor, a->P_actor(), 0);
+    ra.ld_obs = S; ra.out = a->dact; ra.ld_out = a->Apad;
+    ra.n = n; ra.S = S; ra.A = A; ra.ldl = a->row_ldl;
+    ra.D = D;
+    gcrl::normalizer_view(nz_obs ? nz_obs[i] : nullptr, &ra.nz_mean, &ra.nz_var, nullptr, &ra.nz_clip, &ra.nz_mode);
+    gcrl::normalizer_view(nz_dg ? nz_dg[i] : nullptr, &ra.nzg_mean, &ra.nzg_var, nullptr, &ra.nzg_clip, &ra.nzg_mode);
+    const int mode = modes[i] < 0 ? fill : modes[i];
+    ra.post = mode == 1 ? 1 : (mode == 0 ? 2 : 3);
+  }
+  void* tab_dev = nullptr;
+  if (p->act_tabs.get(tab, sizeof(RowActArgs) * P, st, &tab_dev)) return fail(GCRL_ERR_HIP, "gcrl_pop_observe_act: argument table upload failed");
+  const bool fast = n <= kPopActRows;
+  const int stride_n = fast ? kPopActRows : a0->B;
+  const PopActLayout lay(P, stride_n, S, A);
+  char* host = nullptr;
+  if (fast) {
+    if (!p->act_blk_host) {
+      GCRL_HIP(hipHostMalloc((void**)&p->act_blk_host, lay.bytes, hipHostMallocMapped | hipHostMallocCoherent));
+      std::memset(p->act_blk_host, 0, lay.bytes);
+      GCRL_HIP(hipHostGetDevicePointer((void**)&p->act_blk_dev, p->act_blk_host, 0));
+    }
+    host = p->act_blk_host;
+  } else {
+    if (!p->act_st_host) {
+      GCRL_HIP(hipHostMalloc((void**)&p->act_st_host, lay.bytes, hipHostMallocDefault));
+      GCRL_HIP(hipMalloc((void**)&p->act_st_dev, lay.bytes));
+    }
+    host = p->act_st_host;
+  }
+  char* dev = fast ? p->act_blk_dev : p->act_st_dev;
+  float* h_rows = reinterpret_cast<float*>(host + lay.rows);
+  double* h_noise = reinterpret_cast<double*>(host + lay.noise);
+  for (int i = 0; i < P; ++i) {
+    if (!((live >> i) & 1u)) continue;
+    float* r = h_rows + (size_t)i * stride_n * S;
+    for (int e = 0; e < n; ++e) {
+      std::memcpy(r + (size_t)e * S, obs_host + i * oD + (size_t)e * D, sizeof(float) * D);
+      std::memcpy(r + (size_t)e * S + D, dg_host + i * oG + (size_t)e * G, sizeof(float) * G);
+    }
+    if ((noisy >> i) & 1u) std::memcpy(h_noise + (size_t)i * stride_n * A, noise_host + i * oA, sizeof(double) * oA);
+  }
+  RowActPop c;
+  c.tab = static_cast<const RowActArgs*>(tab_dev);
+  c.rows = reinterpret_cast<const float*>(dev + lay.rows);
+  c.noise = reinterpret_cast<const double*>(dev + lay.noise);
+  c.out = reinterpret_cast<double*>(dev + lay.out);
+  c.flags = fast ? reinterpret_cast<unsigned long long*>(dev + lay.flags) : nullptr;
+  c.seq = ++p->act_seq;
+  c.live = live; c.noisy = noisy; c.stride_n = stride_n;
+  const double* h_out = reinterpret_cast<const double*>(host + lay.out);
+  if (fast) {
+    // ONE launch and nothing else: the host's stores to the block precede the launch, the kernel reads them there, and the host
+    // waits for the live members' flags (a bounded spin; then the ordinary synchronisation says what happened)
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    TRY(launch_rowchain_act_pop(st, c, P, n, a0->row_ldl, A, a0->H));
+    p->act_launches++;
+    const int nwg = (n + 3) / 4;
+    volatile unsigned long long* flags = reinterpret_cast<volatile unsigned long long*>(host + lay.flags);
+    bool seen = false;
+    for (long spin = 0; spin < 4000000 && !seen; ++spin) {
+      seen = true;
+      for (int i = 0; i < P && seen; ++i)
+        if ((live >> i) & 1u)
+          for (int w = 0; w < nwg; ++w) seen = seen && flags[(size_t)i * nwg + w] == c.seq;
+      if (!seen) __builtin_ia32_pause();
+    }
+    if (!seen) GCRL_HIP(hipStreamSynchronize(st));
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  } else {
+    // the exception: copies up, the same one launch, copy down, one synchronisation (noise, actions and flags lie before the rows)
+    if (noisy) GCRL_HIP(hipMemcpyAsync(dev + lay.noise, host + lay.noise, lay.out - lay.noise, hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipMemcpyAsync(dev + lay.rows, host + lay.rows, lay.bytes - lay.rows, hipMemcpyHostToDevice, st));
+    TRY(launch_rowchain_act_pop(st, c, P, n, a0->row_ldl, A, a0->H));
+    p->act_launches++;
+    p->act_staged++;
+    GCRL_HIP(hipMemcpyAsync(host + lay.out, dev + lay.out, lay.flags - lay.out, hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < P; ++i)
+    if ((live >> i) & 1u) std::memcpy(out_host + i * oA, h_out + (size_t)i * stride_n * A, sizeof(double) * oA);
+  return GCRL_OK;
+}
+
+int gcrl_pop_process_step(gcrl_pop* p, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int32_t update_stats, gcrl_normalizer* const* nz_dg,
+                          int32_t update_goal_stats, const float* obs_host, const float* next_obs_host, int32_t obs_dim, const float* dg_host,
+                          const float* next_dg_host, const float* ag_host, const float* next_ag_host, const float* actions_host,
+                          const float* rewards_host, const uint8_t* dones_host, int32_t env0, int32_t n, int64_t* rows_out, void* stream) {
+  // every refusal before any device work (the per-member ones: her_process_step_pop)
+  GCRL_CHECK_ARG(rings, "gcrl_pop_process_step: rings: null array");
+  GCRL_CHECK_ARG(obs_host && next_obs_host, "gcrl_pop_process_step: obs_host / next_obs_host: null array");
+  GCRL_CHECK_ARG(dg_host && next_dg_host && next_ag_host, "gcrl_pop_process_step: dg_host / next_dg_host / next_ag_host: null array");
+  GCRL_CHECK_ARG(actions_host && rewards_host && dones_host, "gcrl_pop_process_step: actions_host / rewards_host / dones_host: null array");
+  GCRL_CHECK_ARG(rows_out, "gcrl_pop_process_step: rows_out: null array");
+  GCRL_CHECK_ARG(p, "gcrl_pop_process_step: pop: null handle");
+  return her_process_step_pop(&p->proc, (int)p->m.size(), rings, nz_obs, update_stats, nz_dg, update_goal_stats, obs_host, next_obs_host, obs_dim,
+                              dg_host, next_dg_host, ag_host, next_ag_host, actions_host, rewards_host, dones_host, env0, n, rows_out, stream);
+}
+
+int gcrl_pop_acting_counts(const gcrl_pop* p, int64_t* act_calls, int64_t* act_launches, int64_t* proc_calls, int64_t* proc_launches,
+                           int64_t* act_staged) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_acting_counts: pop: null handle");
+  if (act_calls) *act_calls = p->act_calls;
+  if (act_launches) *act_launches = p->act_launches;
+  if (proc_calls) *proc_calls = p->proc.calls;
+  if (proc_launches) *proc_launches = p->proc.launches;
+  if (act_staged) *act_staged = p->act_staged;
+  return GCRL_OK;
+}
+
 void gcrl_pop_destroy(gcrl_pop* p) {
   if (!p) return;
   for (gcrl_agent* a : p->m) gcrl_agent_destroy(a);   // (synchronises the device)
+  p->act_tabs.release();
+  if (p->act_blk_host) (void)hipHostFree(p->act_blk_host);
+  if (p->act_st_host) (void)hipHostFree(p->act_st_host);
+  if (p->act_st_dev) (void)hipFree(p->act_st_dev);
+  her_process_step_pop_release(&p->proc);
   for (auto& kv : p->tabs) (void)hipFree(kv.second);
   delete p;
 }

@@ -174,4 +174,25 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src = nullptr,
                       void* cp_dst = nullptr, size_t cp_bytes = 0);
 
+// gcrl_pop_process_step (her_ring.hip): one vector-env step of `members` rings as ONE her_process_step_pop_kernel launch (workgroup m =
+// member m), then each ring's finish_vector_step in member order.  The members' raw rows and payloads travel in a pinned, mapped block
+// the kernel reads directly (no staged copy): kSlots slots used in rotation, each guarded by an event recorded after its launch — nothing
+// waits for this launch, so a slot is refilled only once the launch that read it is known to be over (as ps_pinned / epi_ev above).
+// The mapping is coherent host memory, which the device does not cache, and the host's writes precede the launch.
+struct PopProcStep {
+  static constexpr int kSlots = 8;
+  char* blk_host = nullptr; char* blk_dev = nullptr;
+  size_t slot_floats = 0;
+  hipEvent_t ev[kSlots] = {};
+  int next = 0;
+  void* tabs = nullptr;    // PopTabCache of the members' ProcArgs tables (pop.h)
+  int64_t calls = 0, launches = 0;
+};
+int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int update_stats,
+                         gcrl_normalizer* const* nz_dg, int update_goal_stats, const float* obs_host, const float* next_obs_host, int obs_dim,
+                         const float* dg_host, const float* next_dg_host, const float* ag_host, const float* next_ag_host,
+                         const float* actions_host, const float* rewards_host, const uint8_t* dones_host, int env0, int n,
+                         int64_t* rows_out, void* stream);
+void her_process_step_pop_release(PopProcStep* ps);
+
 }  // namespace gcrl

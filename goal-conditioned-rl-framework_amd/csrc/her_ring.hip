@@ -8,6 +8,7 @@
 #include "her_ring.h"
 #include "norm_math.h"
 #include "ring_book.h"
+#include "pop.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -149,6 +150,13 @@ __global__ __launch_bounds__(256) void her_process_step_kernel(ProcArgs p) { her
 constexpr int kProcInlineFloats = 896;
 struct ProcArgsInline { ProcArgs p; int raw_floats; float data[kProcInlineFloats]; };
 __global__ __launch_bounds__(256) void her_process_step_inline_kernel(ProcArgsInline q) { her_process_step_body(q.p, q.data, q.data + q.raw_floats); }
+// population form (gcrl_pop_process_step): workgroup m runs member m's step on tab[m] (its own staging area, its own normalisers and
+// their update flags; raw / pay there are ignored) and on its slice [raw | payload] of `data` ([members][stride] floats)
+__global__ __launch_bounds__(256) void her_process_step_pop_kernel(const ProcArgs* tab, const float* data, int stride, int raw_floats) {
+  const ProcArgs& p = tab[blockIdx.x];
+  const float* d = data + (size_t)blockIdx.x * stride;
+  her_process_step_body(p, d, d + raw_floats);
+}
 
 // ---------------------------------------------------------------- relabel + flush
 struct FlushArgs {
@@ -1284,3 +1292,138 @@ int gcrl_her_read_rows(gcrl_her* h, int64_t first, int64_t n, float* s, float* a
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- population form of gcrl_her_process_step_g (her_ring.h PopProcStep)
+namespace gcrl {
+
+int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int update_stats,
+                         gcrl_normalizer* const* nz_dg, int update_goal_stats, const float* obs_host, const float* next_obs_host, int obs_dim,
+                         const float* dg_host, const float* next_dg_host, const float* ag_host, const float* next_ag_host,
+                         const float* actions_host, const float* rewards_host, const uint8_t* dones_host, int env0, int n,
+                         int64_t* rows_out, void* stream) {
+  const int P = members;
+  // every refusal before any device work
+  gcrl_her* h0 = rings[0];
+  GCRL_CHECK_ARG(h0, "gcrl_pop_process_step: rings: member 0 has no replay ring");
+  const int D = obs_dim, G = h0->G, A = h0->A;
+  bool any_g = false;
+  for (int i = 0; i < P; ++i) {
+    gcrl_her* h = rings[i];
+    GCRL_CHECK_ARG(h, "gcrl_pop_process_step: rings: member %d has no replay ring", i);
+    for (int j = 0; j < i; ++j) GCRL_CHECK_ARG(rings[j] != h, "gcrl_pop_process_step: rings: members %d and %d share a replay ring", j, i);
+    GCRL_CHECK_ARG(h->S == h0->S && h->A == A && h->G == G && h->cfg.flush_len == h0->cfg.flush_len,
+                   "gcrl_pop_process_step: rings: member %d's ring has other dimensions than member 0's", i);
+    GCRL_CHECK_ARG(D >= 1 && D <= 128 && D + G == h->S, "gcrl_pop_process_step: obs_dim %d + goal_dim %d != state_dim %d (obs_dim <= 128)", D, G, h->S);
+    GCRL_CHECK_ARG(n >= 1 && env0 >= 0 && env0 + n <= h->cfg.nenvs, "gcrl_pop_process_step: n: envs [%d, %d) outside [0, %d) (member %d)", env0, env0 + n, h->cfg.nenvs, i);
+    GCRL_CHECK_ARG(3 + A + G <= kPayW, "gcrl_pop_process_step: action_dim + goal_dim too large for the payload");
+    gcrl_normalizer* zo = nz_obs ? nz_obs[i] : nullptr;
+    gcrl_normalizer* zg = nz_dg ? nz_dg[i] : nullptr;
+    GCRL_CHECK_ARG(!zo || gcrl_normalizer_size(zo) == D, "gcrl_pop_process_step: nz_obs: member %d's observation normaliser has size %d for obs_dim %d", i, gcrl_normalizer_size(zo), D);
+    GCRL_CHECK_ARG(!zg || (ag_host && gcrl_normalizer_size(zg) == G), "gcrl_pop_process_step: nz_dg: member %d's goal normaliser needs ag_host and size goal_dim = %d", i, G);
+    GCRL_CHECK_ARG(!(zg && h->cfg.reward_kind == GCRL_REWARD_HOST), "gcrl_pop_process_step: nz_dg: a goal normaliser together with a host-callback "
+                   "compute_reward is not supported by the fused entry (member %d): use the separate calls", i);
+    any_g = any_g || zg;
+  }
+  ps->calls++;
+  const size_t oD = (size_t)n * D, oG = (size_t)n * G, oA = (size_t)n * A;
+  if (P == 1) {   // nothing to merge: the member's own entry
+    const int64_t r = gcrl_her_process_step_g(h0, nz_obs ? nz_obs[0] : nullptr, update_stats, nz_dg ? nz_dg[0] : nullptr, update_goal_stats, obs_host,
+                                              next_obs_host, D, dg_host, next_dg_host, ag_host, next_ag_host, actions_host, rewards_host, dones_host,
+                                              env0, n, stream);
+    rows_out[0] = r;
+    return r < 0 ? (int)r : GCRL_OK;
+  }
+  hipStream_t st = h0->pick(stream);
+  // a member's slice: raw rows [obs | next_obs | dg | next_dg | ag | next_ag (any goal normaliser)], then the per-env payload
+  const size_t raw = (size_t)n * (2 * D + (any_g ? 4 : 2) * G), stride = (raw + (size_t)n * kPayW + 3) & ~(size_t)3;
+  const size_t need = (size_t)P * stride;
+  if (need > ps->slot_floats) {
+    GCRL_HIP(hipDeviceSynchronize());
+    if (ps->blk_host) GCRL_HIP(hipHostFree(ps->blk_host));
+    ps->blk_host = nullptr;
+    int max_envs = 0;
+    for (int i = 0; i < P; ++i) max_envs = std::max(max_envs, rings[i]->cfg.nenvs);
+    const size_t want = std::max(need, (size_t)P * (((size_t)max_envs * (2 * D + 4 * G + kPayW) + 3) & ~(size_t)3));
+    GCRL_HIP(hipHostMalloc((void**)&ps->blk_host, want * sizeof(float) * PopProcStep::kSlots, hipHostMallocMapped | hipHostMallocCoherent));
+    GCRL_HIP(hipHostGetDevicePointer((void**)&ps->blk_dev, ps->blk_host, 0));
+    for (int s = 0; s < PopProcStep::kSlots; ++s)
+      if (!ps->ev[s]) GCRL_HIP(hipEventCreateWithFlags(&ps->ev[s], hipEventDisableTiming));
+    ps->slot_floats = want;
+  }
+  if (!ps->tabs) ps->tabs = new PopTabCache;
+  const int slot = ps->next;
+  ps->next = (slot + 1) % PopProcStep::kSlots;
+  GCRL_HIP(hipEventSynchronize(ps->ev[slot]));   // (the launch that read this slot, kSlots calls ago)
+  float* blk = reinterpret_cast<float*>(ps->blk_host) + (size_t)slot * ps->slot_floats;
+  ProcArgs tab[32];
+  GCRL_CHECK_ARG(P <= 32, "gcrl_pop_process_step: members: %d", P);
+  for (int i = 0; i < P; ++i) {
+    gcrl_her* h = rings[i];
+    float* pin = blk + (size_t)i * stride;
+    std::memcpy(pin, obs_host + i * oD, sizeof(float) * oD);
+    std::memcpy(pin + oD, next_obs_host + i * oD, sizeof(float) * oD);
+    std::memcpy(pin + 2 * oD, dg_host + i * oG, sizeof(float) * oG);
+    std::memcpy(pin + 2 * oD + oG, next_dg_host + i * oG, sizeof(float) * oG);
+    if (any_g) {
+      std::memcpy(pin + 2 * oD + 2 * oG, ag_host + i * oG, sizeof(float) * oG);
+      std::memcpy(pin + 2 * oD + 3 * oG, next_ag_host + i * oG, sizeof(float) * oG);
+    }
+    float* pay = pin + raw;
+    for (int e = 0; e < n; ++e) {
+      float* pw = pay + (size_t)e * kPayW;
+      const int t = h->staged[env0 + e];
+      std::memcpy(&pw[0], &t, sizeof(int));
+      pw[1] = rewards_host[(size_t)i * n + e];
+      pw[2] = dones_host[(size_t)i * n + e] ? 1.0f : 0.0f;
+      std::memcpy(pw + 3, actions_host + i * oA + (size_t)e * A, sizeof(float) * A);
+      std::memcpy(pw + 3 + A, next_ag_host + i * oG + (size_t)e * G, sizeof(float) * G);
+      std::memcpy(&h->ag_mirror[((size_t)(env0 + e) * h->cfg.flush_len + t) * G], next_ag_host + i * oG + (size_t)e * G, sizeof(float) * G);
+    }
+    ProcArgs& pa = tab[i];
+    std::memset(&pa, 0, sizeof(pa));
+    pa.stage = h->stage;
+    gcrl_normalizer* zo = nz_obs ? nz_obs[i] : nullptr;
+    gcrl_normalizer* zg = nz_dg ? nz_dg[i] : nullptr;
+    const double *mean = nullptr, *var = nullptr;
+    gcrl::normalizer_view(zo, &mean, &var, &pa.count, &pa.clip, &pa.mode);
+    pa.mean = const_cast<double*>(mean); pa.var = const_cast<double*>(var);
+    pa.update = (zo && update_stats) ? 1 : 0;
+    if (zg) {
+      const double *gm = nullptr, *gv = nullptr;
+      gcrl::normalizer_view(zg, &gm, &gv, &pa.gcount, &pa.gclip, &pa.gmode);
+      pa.gmean = const_cast<double*>(gm); pa.gvar = const_cast<double*>(gv);
+      pa.gupdate = update_goal_stats ? 1 : 0;
+    }
+    pa.n = n; pa.env0 = env0; pa.flush_len = h->cfg.flush_len; pa.D = D; pa.S = h->S; pa.A = A; pa.G = G;
+    pa.SA4 = h->SA4; pa.S4 = h->S4; pa.RG = h->RG;
+  }
+  void* tab_dev = nullptr;
+  if (static_cast<PopTabCache*>(ps->tabs)->get(tab, sizeof(ProcArgs) * P, st, &tab_dev)) return gcrl::fail(GCRL_ERR_HIP, "gcrl_pop_process_step: argument table upload failed");
+  const float* data_dev = reinterpret_cast<const float*>(ps->blk_dev) + (size_t)slot * ps->slot_floats;
+  hipLaunchKernelGGL(her_process_step_pop_kernel, dim3(P), dim3(256), 0, st, static_cast<const ProcArgs*>(tab_dev), data_dev, (int)stride, (int)raw);
+  GCRL_HIP(hipGetLastError());
+  GCRL_HIP(hipEventRecord(ps->ev[slot], st));
+  ps->launches++;
+  for (int i = 0; i < P; ++i) {
+    if (tab[i].update) gcrl::normalizer_updated(nz_obs[i]);
+    if (tab[i].gupdate) gcrl::normalizer_updated(nz_dg[i]);
+  }
+  // the flush launches stay per member, in member order: their "future" draws come from the host generator, which python-mode
+  // members share — member order makes the stream equal the standalone calls made in member order
+  for (int i = 0; i < P; ++i) {
+    const int64_t r = finish_vector_step(rings[i], env0, n, dones_host + (size_t)i * n, st);
+    rows_out[i] = r;
+    if (r < 0) return (int)r;
+  }
+  return GCRL_OK;
+}
+
+void her_process_step_pop_release(PopProcStep* ps) {
+  if (!ps) return;
+  if (ps->blk_host) (void)hipHostFree(ps->blk_host);
+  for (int s = 0; s < PopProcStep::kSlots; ++s) if (ps->ev[s]) (void)hipEventDestroy(ps->ev[s]);
+  if (ps->tabs) { static_cast<PopTabCache*>(ps->tabs)->release(); delete static_cast<PopTabCache*>(ps->tabs); }
+  *ps = PopProcStep{};
+}
+
+}  // namespace gcrl

@@ -12,6 +12,8 @@
 #include <atomic>
 #include <cstring>
 #include <functional>
+#include <map>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -60,6 +62,38 @@ inline int pop_record(PopRec* r, int kind, int sub, dim3 grid, size_t lds, const
 inline int pop_defer(PopRec* r, std::function<int(hipStream_t)> issue) {
   return pop_record(r, POP_ALONE, 0, dim3(1), 0, nullptr, 0, std::move(issue));
 }
+
+// Device copies of the argument tables of the population ACTING launches (gcrl_pop_observe_act, gcrl_pop_process_step), by content.
+// A table repeats call after call (it holds what belongs to the members, not to the call), so the usual call is one memcmp with the
+// table of the call before.  A table is never rewritten: a launch still in flight may be reading it.
+struct PopTabCache {
+  std::map<std::string, void*> tabs;
+  const std::string* last = nullptr;
+  void* last_dev = nullptr;
+  int get(const void* bytes, size_t n, hipStream_t st, void** out) {
+    if (last && last->size() == n && std::memcmp(last->data(), bytes, n) == 0) { *out = last_dev; return 0; }
+    std::string key((const char*)bytes, n);
+    auto it = tabs.find(key);
+    if (it == tabs.end()) {
+      if (tabs.size() >= 64) {   // (a bound: regimes and modes give a handful of tables)
+        if (hipStreamSynchronize(st) != hipSuccess) return -2;
+        release();
+      }
+      void* d = nullptr;
+      if (hipMalloc(&d, n) != hipSuccess) return -2;
+      if (hipMemcpy(d, bytes, n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return -2; }
+      it = tabs.emplace(std::move(key), d).first;
+    }
+    last = &it->first; last_dev = it->second;
+    *out = last_dev;
+    return 0;
+  }
+  void release() {
+    for (auto& kv : tabs) (void)hipFree(kv.second);
+    tabs.clear();
+    last = nullptr; last_dev = nullptr;
+  }
+};
 
 // population launches: `tab` is a device array of `members` argument structs
 int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int rg, dim3 grid, size_t lds);

@@ -350,6 +350,24 @@ struct RowActInline {
   double noise_inl[kActInlineNoise];
 };
 int launch_rowchain_act_inline(hipStream_t st, const RowActInline& a);
+// Population form (gcrl_pop_observe_act): grid (ceil(n / 4), members), member = blockIdx.y.  Member m's workgroups read tab[m] (its own
+// actor, normaliser statistics and regime bits, post mode; obs / noise / out64 there are ignored) and its slices of rows / noise / out:
+// [members][stride_n][S] floats, [members][stride_n][A] doubles, [members][stride_n][A] doubles.  What changes from call to call travels
+// in the kernel arguments, so the table stays the same call after call: bit m of `live` clear = member m is skipped (DDPG's
+// epsilon-random action needs no network: its workgroups exit at once and write nothing), bit m of `noisy` = its noise slice is added.
+// Fast form: rows, noise, out and flags are the device addresses of a pinned, mapped block the host fills before the launch and
+// polls after it (flags[m * nwg + workgroup] = seq once that workgroup's rows are out).  Staged form: device buffers, flags == null.
+// A later call cannot read an earlier call's rows: every row and noise element is read by a system-scope load (sc0 sc1: past the L1
+// and the L2), and the mapping is coherent host memory, which the device does not cache.
+struct RowActPop {
+  const RowActArgs* tab;
+  const float* rows; const double* noise; double* out;
+  unsigned long long* flags;
+  unsigned long long seq;
+  unsigned int live, noisy;
+  int stride_n;
+};
+int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int n, int ldl, int A, int H);
 
 // Weight-slice form of the DDPG launch (rowtile.hip): a workgroup owns the 16 x 16 tile (row block, column block) of every
 // layer of its role's chain; the H / 16 workgroups of a row block hand the layer outputs to each other inside the launch.

@@ -601,6 +601,25 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_act_inline_kernel(RowAct
   if (threadIdx.x == 0) __hip_atomic_store(a.flag_host + blockIdx.x, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// population form (rowchain.h RowActPop): member blockIdx.y on its own arguments tab[blockIdx.y] and its own slices of the rows, the
+// noise and the actions — the same body text as the inline kernel, so each member's rows go through its own arithmetic in its own order
+__global__ __launch_bounds__(kRowThreads) void rowchain_act_pop_kernel(RowActPop c) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const unsigned int m = blockIdx.y;
+  if (!((c.live >> m) & 1u)) return;   // skipped member: nothing read, nothing written
+  const RowActArgs& a = c.tab[m];      // (a reference into the device table: uniform loads, no copy of the struct)
+  const float* rows = c.rows + (size_t)m * c.stride_n * a.ld_obs;
+  const double* noise = c.noise + (size_t)m * c.stride_n * a.A;
+  double* out = c.out + (size_t)m * c.stride_n * a.A;
+  rowchain_act_body<true>(a, [&](long long i) { return __hip_atomic_load(rows + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); },
+                          [&](long long t) { return __hip_atomic_load(noise + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); },
+                          ((c.noisy >> m) & 1u) != 0, out, lds);
+  // this workgroup's rows are out as write-through stores: drain them, then raise its flag (system scope: the host polls it)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0 && c.flags) __hip_atomic_store(c.flags + (size_t)m * gridDim.x + blockIdx.x, c.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Wt[wt[l] + k*H + o] = P[w[l] + o*in_l + k]; layer 0 rows in..jpad0-1 are zero
 __global__ void wt_rebuild_kernel(RowNet net, float* Wt) {
   const int l = blockIdx.y;
@@ -732,6 +751,21 @@ int launch_rowchain_act_inline(hipStream_t st, const RowActInline& a) {
     raised = lds;
   }
   hipLaunchKernelGGL(rowchain_act_inline_kernel, dim3((b.n + 3) / 4), dim3(kRowThreads), lds, st, a);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int n, int ldl, int A, int H) {
+  GCRL_CHECK_ARG(c.tab && c.rows && c.noise && c.out && members >= 1 && members <= 32 && n >= 1 && n <= c.stride_n, "rowchain act (population): bad launch");
+  GCRL_CHECK_ARG(H % 4 == 0 && ldl % 4 == 0 && A >= 1 && A <= 16, "rowchain act (population): unsupported shape");
+  const size_t lds = (size_t)(3 * 4 * ldl + 2 * 4 * 4 * kRowChunk + 4 * 16 + A * H + 32) * sizeof(float);
+  GCRL_CHECK_ARG(lds <= 160 * 1024, "rowchain act: %zu bytes of LDS needed", lds);
+  static thread_local size_t raised = 0;
+  if (lds > 64 * 1024 && lds > raised) {
+    GCRL_HIP(hipFuncSetAttribute((const void*)rowchain_act_pop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised = lds;
+  }
+  hipLaunchKernelGGL(rowchain_act_pop_kernel, dim3((n + 3) / 4, (unsigned)members), dim3(kRowThreads), lds, st, c);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }

@@ -7,11 +7,14 @@ training step once for all members (csrc/agent_pop.inc), and every member comput
 
 `.members` are ordinary `DDPG` / `TD3Agent` objects (own `HERBuffer`, the whole single-agent API, including `update` /
 `update_many` on the member alone); `update_many(step0, n)` steps all of them and returns, per member, what the agent's own
-`update_many` returns.
+`update_many` returns.  `observe_act` / `process_step` are the members' fused acting entries for all members at once: one launch
+per call (gcrl_pop_observe_act, gcrl_pop_process_step), the host generators consumed in member order.
 """
 from __future__ import annotations
 
 import ctypes as C
+
+import numpy as np
 
 from .. import _ffi
 from .._ffi import lib
@@ -115,6 +118,148 @@ class _Population:
         """One step of every member: the members' `update(step)` tuples, in member order."""
         return [r[0] for r in self.update_many(step, 1)]
 
+    # ------------------------------------------------------------------ acting side
+    # populations of at least this many members issue the population launches; smaller ones call the members' own entries (a
+    # one-member population has nothing to merge).  Measured (DESIGN.md 4f, profiles/r08_population_acting.jsonl): at P = 2 a DDPG
+    # population's two calls take 55-63 us per vector step against 53-58 us member by member — the host work per member outweighs one
+    # saved launch pair — while TD3 wins from P = 2 (51-63 against 58-65 us) and both win from P = 4 (1.4-1.7 x) to P = 16 (2.1-2.8 x)
+    MERGE_ACTING_FROM = 2
+
+    def _staging(self, tag: str, key: tuple, shapes):
+        """Persistent host staging of the acting entries (as `_EngineAgent._staging`: fixed addresses, ctypes pointers built once)."""
+        cache = self.__dict__.setdefault("_stage_cache", {})
+        st = cache.get(tag)
+        if st is None or st[0] != key:
+            arrs = {k: np.empty(shp, dt) for k, (shp, dt) in shapes().items()}
+            P = len(self.members)
+            st = cache[tag] = (key, arrs, {k: C.c_void_p(v.ctypes.data) for k, v in arrs.items()},
+                               dict(nzo=(C.c_void_p * P)(), nzg=(C.c_void_p * P)(), rings=(C.c_void_p * P)(), rows=(C.c_int64 * P)()))
+        return st[1], st[2], st[3]
+
+    def _per_member(self, name: str, seq):
+        if len(seq) != len(self.members):
+            self._refuse("members", f"{name} has {len(seq)} entries for {len(self.members)} members")
+
+    def observe_act(self, observations, desired_goals, eval_action: bool = False, obs_normalize: bool = True, g_normalize: bool = False):
+        """`members[i].observe_act(observations[i], desired_goals[i], ...)` for every member as ONE native call and one launch;
+        returns the members' float64 action arrays [n, A] in member order.  The host generators (`random`, `np.random`, the
+        shared stream) are consumed member after member, exactly as by the members' own calls made in member order; a DDPG
+        member on its epsilon-random branch takes no part in the launch.  Runs the members' own methods one after another
+        when a normaliser this step needs is a host object or the members' row counts differ."""
+        self._per_member("observations", observations)
+        self._per_member("desired_goals", desired_goals)
+        ms = self.members
+        P = len(ms)
+        obs = [x if isinstance(x, np.ndarray) else np.asarray(x) for x in observations]
+        dgs = [x if isinstance(x, np.ndarray) else np.asarray(x) for x in desired_goals]
+        nzs = [m._device_normalizers(obs_normalize, g_normalize) for m in ms]
+        shp, gshp = obs[0].shape, dgs[0].shape
+        if (P < self.MERGE_ACTING_FROM or any(z is None for z in nzs) or len(shp) != 2 or len(gshp) != 2
+                or any(o.shape != shp for o in obs) or any(g.shape != gshp for g in dgs)):
+            return [m.observe_act(o, g, eval_action, obs_normalize, g_normalize) for m, o, g in zip(ms, obs, dgs)]
+        n, D, G, A = shp[0], shp[1], gshp[1], ms[0].ac_dim
+        if n > int(ms[0].config.batch_size):      # (before a generator is touched)
+            raise ValueError(f"{type(self).__name__}.observe_act: n: {n} rows per member (1..batch_size = {ms[0].config.batch_size})")
+        buf, ptr, arr = self._staging("act", (n, D, G, A), lambda: dict(obs=((P, n, D), np.float32), dg=((P, n, G), np.float32),
+                                                                         noise=((P, n, A), np.float64), out=((P, n, A), np.float64),
+                                                                         modes=((P,), np.int32)))
+        modes, b_obs, b_dg, b_noise = buf["modes"], buf["obs"], buf["dg"], buf["noise"]
+        nzo, nzg = arr["nzo"], arr["nzg"]
+        out = [None] * P
+        with_noise = False
+        for i, m in enumerate(ms):
+            m.set_eval()
+            m._rows_dtypes(obs[i].dtype, dgs[i].dtype, obs_normalize, g_normalize)
+            noise, mode = m._act_noise(n, eval_action)
+            nzo[i], nzg[i] = nzs[i]
+            if mode is None:
+                modes[i], out[i] = -1, noise              # DDPG's epsilon-random action: no network involved
+                continue
+            modes[i] = mode
+            np.copyto(b_obs[i], obs[i], casting="unsafe")
+            np.copyto(b_dg[i], dgs[i], casting="unsafe")
+            if noise is not None:
+                np.copyto(b_noise[i], noise)
+                with_noise = True
+        _ffi.check(lib.gcrl_pop_observe_act(self._pop.h, nzo, nzg, ptr["obs"], D, ptr["dg"], G, n, ptr["noise"] if with_noise else None,
+                                            ptr["modes"], ptr["out"], _ffi.stream_handle()))
+        b_out = buf["out"]
+        for i in range(P):
+            if out[i] is None:
+                out[i] = b_out[i].copy()
+        return out
+
+    def process_step(self, states, actions, next_obs_raws, rewards, dones, obs_normalize: bool = True, g_normalize: bool = False):
+        """`members[i].process_step(states[i], actions[i], next_obs_raws[i], rewards[i], dones[i], ...)` for every member as ONE
+        native call: one launch stages all members' transitions (each with its own normalisers), the members' episode flushes
+        follow in member order.  Returns the rows appended per member.  Runs the members' own methods one after another when
+        a normaliser this step needs is a host object, compute_reward runs through the host callback with g_normalize, or
+        the members' row counts differ."""
+        for name, seq in (("states", states), ("actions", actions), ("next_obs_raws", next_obs_raws), ("rewards", rewards), ("dones", dones)):
+            self._per_member(name, seq)
+        ms = self.members
+        P = len(ms)
+        as_arr = lambda x: x if isinstance(x, np.ndarray) else np.asarray(x)
+        nzs = [m._device_normalizers(obs_normalize, g_normalize) for m in ms]
+        rows_in = []
+        for st, ac, nx in zip(states, actions, next_obs_raws):
+            rows_in.append((as_arr(st["observation"]), as_arr(nx["observation"]), as_arr(st["desired_goal"]), as_arr(nx["desired_goal"]),
+                            as_arr(nx["achieved_goal"]), as_arr(st["achieved_goal"]) if g_normalize else None, as_arr(ac)))
+        merged = P >= self.MERGE_ACTING_FROM and all(z is not None for z in nzs)
+        if merged:
+            o0, _, g0, _, a0, _, c0 = rows_in[0]
+            merged = all(r[0].shape == o0.shape and r[2].shape == g0.shape and r[4].shape == a0.shape and r[6].shape == c0.shape for r in rows_in)
+        if merged:
+            n, D, G, A = o0.shape[0], o0.shape[1], g0.shape[1], c0.shape[1]
+            for m in ms:   # (the rings — and with them the reward kinds — exist from here on)
+                m.buffer._ensure(D + G, A, a0.shape[1])
+            merged = not (g_normalize and any(m.buffer._reward_cfg[0] == 2 for m in ms))
+        if not merged:
+            return [m.process_step(s, a, nx, r, d, obs_normalize, g_normalize)
+                    for m, s, a, nx, r, d in zip(ms, states, actions, next_obs_raws, rewards, dones)]
+        f32 = np.float32
+        b, p, arr = self._staging("proc", (n, D, G, A), lambda: dict(obs=((P, n, D), f32), nobs=((P, n, D), f32), dg=((P, n, G), f32),
+                                                                      ndg=((P, n, G), f32), ag=((P, n, G), f32), nag=((P, n, G), f32),
+                                                                      act=((P, n, A), f32), rew=((P, n), f32), dn=((P, n), np.uint8)))
+        cp = np.copyto
+        nzo, nzg, rings = arr["nzo"], arr["nzg"], arr["rings"]
+        for i, (m, (obs_i, nobs_i, dg_i, ndg_i, nag_i, ag_i, act_i)) in enumerate(zip(ms, rows_in)):
+            # np.concatenate's result type, as the reference's update_normalizers forms it (src/agent.py:343-350)
+            odt = obs_i.dtype if obs_i.dtype == nobs_i.dtype else np.result_type(obs_i.dtype, nobs_i.dtype)
+            gdt = dg_i.dtype
+            if g_normalize and not (dg_i.dtype == ndg_i.dtype == ag_i.dtype == nag_i.dtype):
+                gdt = np.result_type(dg_i.dtype, ndg_i.dtype, ag_i.dtype, nag_i.dtype)
+            m._rows_dtypes(odt, gdt, obs_normalize, g_normalize)
+            cp(b["obs"][i], obs_i, casting="unsafe"); cp(b["nobs"][i], nobs_i, casting="unsafe"); cp(b["dg"][i], dg_i, casting="unsafe")
+            cp(b["ndg"][i], ndg_i, casting="unsafe"); cp(b["nag"][i], nag_i, casting="unsafe"); cp(b["act"][i], act_i, casting="unsafe")
+            cp(b["rew"][i], np.reshape(rewards[i], -1), casting="unsafe")
+            cp(b["dn"][i], np.reshape(dones[i], -1), casting="unsafe")
+            if g_normalize:
+                cp(b["ag"][i], ag_i, casting="unsafe")
+            nzo[i], nzg[i] = nzs[i]
+            rings[i] = m.buffer.handle
+        streams = list({id(m.buffer.rng): m.buffer.rng for m in ms}.values())   # (python mode: the one shared stream)
+        for r in streams:
+            r.pull()
+        rc = lib.gcrl_pop_process_step(self._pop.h, rings, nzo, 1 if obs_normalize else 0, nzg, 1 if g_normalize else 0, p["obs"], p["nobs"], D,
+                                       p["dg"], p["ndg"], p["ag"] if g_normalize else None, p["nag"], p["act"], p["rew"], p["dn"], 0, n,
+                                       arr["rows"], _ffi.stream_handle())
+        for m in ms:
+            m.buffer._check_rows(0)      # (a failure caused by a compute_reward callable re-raises ITS exception)
+        _ffi.check(rc)
+        for r in streams:
+            r.push_back()
+        return [int(x) for x in arr["rows"]]
+
+    def acting_counts(self):
+        """(act_calls, act_launches, proc_calls, proc_launches, act_staged): native calls of `observe_act` / `process_step` and the
+        kernel launches they issued for the network / the process-step stage (flush launches not counted); act_staged: network
+        launches that took the staged form (more rows per member than the pinned block holds).  Calls that ran the members'
+        own methods advance none of them (include/gcrl.h gcrl_pop_acting_counts)."""
+        v = [C.c_int64() for _ in range(5)]
+        _ffi.check(lib.gcrl_pop_acting_counts(self._pop.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     def launch_counts(self):
         """(merged, alone): how the recorded launch positions of every update call so far were issued — as one launch of the
         kernel's population form for all members, or member by member (include/gcrl.h gcrl_pop_launch_counts)."""
@@ -127,6 +272,7 @@ class DDPGPopulation(_Population):
     """1..16 `DDPG` agents of equal shapes stepped together."""
     AGENT = DDPG
     NUM_CRITICS = 1
+    MERGE_ACTING_FROM = 4
 
 
 class TD3Population(_Population):

@@ -336,14 +336,45 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * from the rings in member order.  tickets_out / tuple_len_out: [members][n], optional.
  * gcrl_pop_launch_counts: how the recorded launch positions of every gcrl_pop_update_n since creation were issued — `merged`: as one
  * launch of the kernel's population form for all members; `alone`: member by member (a launch without a population form, members
- * whose launches differ, or a one-member population).  Either pointer may be null. */
+ * whose launches differ, or a one-member population).  Either pointer may be null.
+ *
+ * The acting side of a population, one launch per call for all members (the trainer's loop, src/env.py:334-406, calls both per
+ * vector-env step and per agent).  Every host array has a leading [members] dimension; each member computes bit for bit what its
+ * own entry computes.  Refusals name the field and happen before any device work.  A one-member population hands the call to
+ * the member's own entry.
+ * gcrl_pop_observe_act: gcrl_agent_observe_act (src/env.py:348-355 + src/agent.py:1345-1366 / :253-270) of every member.
+ * nz_obs[members] / nz_dg[members]: each member's normalisers (an entry, or the whole array, may be NULL: that part raw);
+ * obs_host [members][n][obs_dim], dg_host [members][n][goal_dim], noise_host [members][n][A] float64 or NULL, out_host
+ * [members][n][A] float64.  modes[i] is gcrl_agent_observe_act's mode of member i (0, 1, 2), or -1: the member is skipped — DDPG's
+ * epsilon-random branch (src/agent.py:1348) involves no network and stays with the caller — and its out_host rows are left
+ * untouched.  n <= batch_size.  Runs after every member's last update call and on its current weights.  Up to 32 rows per
+ * member travel through a pinned, mapped block (one launch, no copy, no stream synchronisation); more rows take staged copies
+ * around the same launch.
+ * gcrl_pop_process_step: gcrl_her_process_step_g (src/env.py:163-201, :167-175, :222-223) of every member's ring rings[i] with its
+ * own normalisers: one launch stages all members' transitions, then each ring's episode flushes follow in member order (their
+ * relabelling draws come from the rings' generators in that order).  The row arrays are those of gcrl_her_process_step_g, each
+ * [members][n][.] (rewards_host, dones_host: [members][n]); ag_host is needed with a goal normaliser only.  rows_out[i] = what
+ * member i's own gcrl_her_process_step_g returns.
+ * gcrl_pop_acting_counts: calls of the two entries since creation and the kernel launches they issued for the network /
+ * for the process-step stage (flush launches and a one-member population's own entries not counted); act_staged: how many of the
+ * network launches took the staged form.  Any pointer may be null. */
 typedef struct gcrl_pop gcrl_pop;
+typedef struct gcrl_normalizer gcrl_normalizer;   /* (the device RunningNormalizer, declared below) */
 gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members);
 int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out);
 int32_t gcrl_pop_size(const gcrl_pop* p);
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,
                       int32_t* tuple_len_out, void* stream);
 int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone);
+int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
+                         const float* dg_host, int32_t goal_dim, int32_t n, const double* noise_host, const int32_t* modes, double* out_host,
+                         void* stream);
+int gcrl_pop_process_step(gcrl_pop* p, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int32_t update_stats, gcrl_normalizer* const* nz_dg,
+                          int32_t update_goal_stats, const float* obs_host, const float* next_obs_host, int32_t obs_dim, const float* dg_host,
+                          const float* next_dg_host, const float* ag_host, const float* next_ag_host, const float* actions_host,
+                          const float* rewards_host, const uint8_t* dones_host, int32_t env0, int32_t n, int64_t* rows_out, void* stream);
+int gcrl_pop_acting_counts(const gcrl_pop* p, int64_t* act_calls, int64_t* act_launches, int64_t* proc_calls, int64_t* proc_launches,
+                           int64_t* act_staged);
 void gcrl_pop_destroy(gcrl_pop* p);
 /* Metrics of a ticket, in the reference's tuple order, as fp32 (waits for that step only).
  * n = tuple length returned by the update. */

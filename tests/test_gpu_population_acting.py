@@ -1,0 +1,325 @@
+"""GPU (-m gpu): the acting side of a population (src/population.py observe_act / process_step / acting_counts; gcrl_pop_observe_act,
+gcrl_pop_process_step: rowchain_act_pop_kernel and her_process_step_pop_kernel, one launch per call for all members) held to BITWISE
+equality with standalone `DDPG` / `TD3Agent` twins built with the same configs, seeds and ring settings and driven by their own
+`observe_act` / `process_step` in member order, `random` and `np.random` seeded identically before each side.  The rows differ on
+every call, so a population launch that read an earlier call's rows would be caught."""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+
+from oracle import her_oracle
+
+import test_gpu_population as tp
+import test_gpu_population_td3 as tp3
+
+pytestmark = pytest.mark.gpu
+
+CFG1 = dict(D=7, G=3, A=3, H=64, B=64)          # state 10 = observation 7 + goal 3
+CFG1_FULL = dict(D=7, G=3, A=3, H=64, B=256)    # the cfg 1 shapes
+HEADLINE = dict(D=20, G=3, A=4, H=256, B=256)   # state 23 = observation 20 + goal 3
+NENVS = 8
+
+
+def _normalizers(gcrl, ag, sh, i):
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    ag.buffer.obs_normalizer = DeviceRunningNormalizer(sh["D"])
+    ag.buffer.dg_normalizer = DeviceRunningNormalizer(sh["G"])
+    ag.buffer.compute_reward = her_oracle.sparse_reward
+    gen = np.random.default_rng(500 + i)           # each member its own weights
+    for v in [ag.actor] + list(ag.critics):
+        v.set_flat((v.flat() + 0.05 * gen.standard_normal(v.numel())).astype(np.float32))
+    ag.update_target_network()
+
+
+def _twins(gcrl, kind, P, sh, rng="engine", nenvs=NENVS, gstep=8, seed0=900):
+    helper = tp if kind == "DDPG" else tp3
+    cfgs = helper._cfgs(P, sh["H"], sh["B"])
+    seeds = list(range(seed0, seed0 + P))
+    S = sh["D"] + sh["G"]
+    pop_cls = gcrl.DDPGPopulation if kind == "DDPG" else gcrl.TD3Population
+    cls = gcrl.DDPG if kind == "DDPG" else gcrl.TD3Agent
+    pop = pop_cls(S, sh["A"], cfgs, nenvs, gstep, rng=rng, seeds=seeds)
+    pop.MERGE_ACTING_FROM = 2      # the population launches at every P >= 2 (the class default is a measured dispatch threshold)
+    solo = [cls(S, sh["A"], c, None, nenvs=nenvs, gradient_step=gstep, rng=rng, seed=s) for c, s in zip(cfgs, seeds)]
+    for i in range(P):
+        _normalizers(gcrl, pop.members[i], sh, i)
+        _normalizers(gcrl, solo[i], sh, i)
+    return pop, solo
+
+
+def _rows(step, i, sh, n=NENVS, obs_dtype=np.float32):
+    """member i's raw rows of vector step `step` (float32-valued, different on every call and for every member)"""
+    gen = np.random.default_rng(100_000 * (i + 1) + step)
+    f = lambda *s: gen.standard_normal(s).astype(np.float32)
+    state = dict(observation=f(n, sh["D"]).astype(obs_dtype), achieved_goal=f(n, sh["G"]), desired_goal=f(n, sh["G"]))
+    nxt = dict(observation=f(n, sh["D"]).astype(obs_dtype), achieved_goal=f(n, sh["G"]), desired_goal=f(n, sh["G"]))
+    rewards = -(gen.random(n) > 0.5).astype(np.float32)
+    return state, nxt, rewards
+
+
+def _both(seed, f_pop, f_solo):
+    """run both sides from identically seeded host generators; the generators must end in the same state"""
+    random.seed(seed); np.random.seed(seed)
+    got = f_pop()
+    st = (random.getstate(), np.random.get_state())
+    random.seed(seed); np.random.seed(seed)
+    want = f_solo()
+    st2 = (random.getstate(), np.random.get_state())
+    assert st[0] == st2[0], "python `random` consumed differently"
+    assert all(np.array_equal(a, b) for a, b in zip(st[1], st2[1])), "np.random consumed differently"
+    return got, want
+
+
+def _same(got, want, what):
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        g, w = np.asarray(g), np.asarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, i, g.dtype, w.dtype, g.shape, w.shape)
+        assert np.array_equal(g.view(np.uint64) if g.dtype == np.float64 else g, w.view(np.uint64) if w.dtype == np.float64 else w), (what, i, g, w)
+
+
+def _act(pop, solo, step, sh, n=NENVS, obs_dtype=np.float32, **kw):
+    rows = [_rows(step, i, sh, n, obs_dtype) for i in range(len(solo))]
+    obs = [r[0]["observation"] for r in rows]
+    dg = [r[0]["desired_goal"] for r in rows]
+    got, want = _both(7000 + step, lambda: pop.observe_act(obs, dg, **kw), lambda: [a.observe_act(o, g, **kw) for a, o, g in zip(solo, obs, dg)])
+    _same(got, want, f"actions of step {step}")
+    return rows, got
+
+
+def _proc(pop, solo, step, rows, acts, dones, **kw):
+    P = len(solo)
+    states, nxts, rews = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+    acts = [np.asarray(a, np.float32) for a in acts]
+    dn = [np.asarray(dones, bool)] * P
+    got, want = _both(8000 + step, lambda: pop.process_step(states, acts, nxts, rews, dn, **kw),
+                      lambda: [a.process_step(s, ac, nx, r, d, **kw) for a, s, ac, nx, r, d in zip(solo, states, acts, nxts, rews, dn)])
+    assert got == want, (step, got, want)
+
+
+def _mt_state(ag):
+    from gcrl_amd._ffi import check, lib
+    buf = (C.c_uint32 * 625)()
+    check(lib.gcrl_mt_get_state(ag.buffer.rng.handle, buf))
+    return np.array(buf[:], np.uint32)
+
+
+def _nz_state(nz):
+    mean, var, count = nz._state()
+    return np.concatenate([mean, var, [count]]).view(np.uint64), nz.float32
+
+
+def _compare_members(pop, solo, goal_nz=False):
+    for i, (m, a) in enumerate(zip(pop.members, solo)):
+        for name in ("obs_normalizer",) + (("dg_normalizer",) if goal_nz else ()):
+            g, w = _nz_state(getattr(m.buffer, name)), _nz_state(getattr(a.buffer, name))
+            assert np.array_equal(g[0], w[0]) and g[1] == w[1], (i, name)
+        assert len(m.buffer) == len(a.buffer), (i, len(m.buffer), len(a.buffer))
+        for g, w in zip(m.buffer.rows(), a.buffer.rows()):
+            assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), f"member {i}: ring rows differ"
+        assert np.array_equal(_mt_state(m), _mt_state(a)), f"member {i}: Mersenne Twister state differs"
+
+
+def _dones(step):
+    """an env finishing on a fixed schedule: some steps none, some one, one step all eight; env 0 is never done after step 5,
+    so it runs to the 50-step flush length at step 55"""
+    d = np.zeros(NENVS, bool)
+    if step == 2:
+        d[3] = True
+    elif step == 5:
+        d[:] = True
+    elif step == 17:
+        d[1] = True
+    elif step == 30:
+        d[[2, 6]] = True
+    elif step == 44:
+        d[7] = True
+    return d
+
+
+def _update_and_compare(pop, solo, tuples=tp._tuples, state=tp._state):
+    got = pop.update_many(1, 8)
+    want = [a.update_many(1, 8) for a in solo]
+    for i in range(len(solo)):
+        g, w = tuples(got[i]), tuples(want[i])
+        if isinstance(g, tuple):
+            assert g[1] == w[1]
+            g, w = g[0], w[0]
+        assert np.array_equal(g.view(np.uint64), w.view(np.uint64)), (i, g, w)
+        assert np.array_equal(state(pop.members[i]), state(solo[i])), f"member {i}: engine state differs"
+
+
+def test_trajectory(gcrl):
+    pop, solo = _twins(gcrl, "DDPG", 3, CFG1)
+    for step in range(60):
+        rows, acts = _act(pop, solo, step, CFG1)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    assert all(len(m.buffer) >= 64 for m in pop.members)
+    counts = pop.acting_counts()
+    assert counts[0] == 60 and 0 < counts[1] <= 60 and counts[2:4] == (60, 60)
+    _compare_members(pop, solo)
+    _update_and_compare(pop, solo)
+
+
+@pytest.mark.parametrize("P", [1, 4, 8, 16])
+@pytest.mark.parametrize("shape", ["cfg1", "headline"])
+def test_shapes_and_sizes(gcrl, P, shape):
+    sh = CFG1_FULL if shape == "cfg1" else HEADLINE
+    pop, solo = _twins(gcrl, "DDPG", P, sh)
+    for step in range(10):
+        rows, acts = _act(pop, solo, step, sh)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    _compare_members(pop, solo)
+
+
+def test_td3(gcrl):
+    pop, solo = _twins(gcrl, "TD3", 4, CFG1)
+    for step in range(12):
+        rows, acts = _act(pop, solo, step, CFG1, eval_action=(step % 3 == 2))   # eval: the raw network output (mode 2)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    _compare_members(pop, solo)
+    calls, launches = pop.acting_counts()[:2]
+    assert (calls, launches) == (12, 12)
+    _update_and_compare(pop, solo, tp3._tuples, tp3._state)
+
+
+def test_mixed_branches(gcrl):
+    """rng="python": DDPG's epsilon-random branch draws `random.random() < 0.2` per member and call from the shared stream.  Seed 18
+    gives, over 20 observe_act calls at P = 4, epsilon-branch members per call 2, 0, 0, 0, 0, 0, 1, 0, 0, 2, 1, 0, 1, 0, 4, 0, 0, 1, 1, 0."""
+    P, K = 4, 20
+    pop, solo = _twins(gcrl, "DDPG", P, CFG1, rng="python")
+    rows = [[_rows(step, i, CFG1) for i in range(P)] for step in range(K)]
+    random.seed(18); np.random.seed(18)
+    got, eps = [], []
+    for step in range(K):
+        before = pop.acting_counts()
+        r = random.Random(); r.setstate(random.getstate())
+        eps.append([r.random() < 0.2 for _ in range(P)])       # (what the P members are about to draw)
+        got.append(pop.observe_act([x[0]["observation"] for x in rows[step]], [x[0]["desired_goal"] for x in rows[step]]))
+        after = pop.acting_counts()
+        assert after[0] == before[0] + 1
+        assert after[1] == before[1] + (0 if all(eps[-1]) else 1), (step, eps[-1])
+    st = (random.getstate(), np.random.get_state())
+    assert any(any(e) and not all(e) for e in eps), "no call with both branches"
+    assert any(all(e) for e in eps), "no call with every member on the epsilon branch"
+    random.seed(18); np.random.seed(18)
+    for step in range(K):
+        want = [a.observe_act(x[0]["observation"], x[0]["desired_goal"]) for a, x in zip(solo, rows[step])]
+        _same(got[step], want, f"actions of call {step}")
+    assert st[0] == random.getstate() and all(np.array_equal(a, b) for a, b in zip(st[1], np.random.get_state()))
+
+
+def test_normaliser_regimes(gcrl):
+    P = 4
+    pop, solo = _twins(gcrl, "DDPG", P, CFG1)
+    # member 2's observation normaliser was loaded: float32 statistics, float32 arithmetic (the regime bits are per member)
+    gen = np.random.default_rng(3)
+    mean, var = gen.standard_normal(CFG1["D"]).astype(np.float32), (0.5 + gen.random(CFG1["D"])).astype(np.float32)
+    for ag in (pop.members[2], solo[2]):
+        ag.buffer.obs_normalizer.set_state(mean, var, 40.0)
+    assert pop.members[2].buffer.obs_normalizer.float32 and not pop.members[1].buffer.obs_normalizer.float32
+    step = 0
+    for obs_dtype, kw in [(np.float32, {}), (np.float64, {}), (np.float64, dict(g_normalize=True)), (np.float32, dict(g_normalize=True)),
+                          (np.float32, dict(obs_normalize=False)), (np.float64, dict(obs_normalize=False, g_normalize=True)), (np.float32, {})]:
+        for _ in range(3):
+            rows, acts = _act(pop, solo, step, CFG1, obs_dtype=obs_dtype, **kw)
+            _proc(pop, solo, step, rows, acts, _dones(step), **kw)
+            step += 1
+    _compare_members(pop, solo, goal_nz=True)
+    counts = pop.acting_counts()
+    assert counts[0] == counts[2] == step and counts[3] == step
+
+
+def test_fresh_weights(gcrl):
+    P = 3
+    pop, solo = _twins(gcrl, "DDPG", P, CFG1)
+    for i in range(P):
+        tp._fill(pop.members[i], 10, 3, i)
+        tp._fill(solo[i], 10, 3, i)
+    for k in range(5):
+        got = pop.update_many(1 + 8 * k, 8)
+        want = [a.update_many(1 + 8 * k, 8) for a in solo]
+        for i in range(P):
+            assert np.array_equal(tp._tuples(got[i]).view(np.uint64), tp._tuples(want[i]).view(np.uint64)), (k, i)
+        _act(pop, solo, k, CFG1, eval_action=True)
+        _act(pop, solo, 100 + k, CFG1, eval_action=True)
+
+
+def test_counts_and_host_normaliser_fallback(gcrl):
+    from gcrl_amd.src.utils import RunningNormalizer
+    P, K = 4, 6
+    pop, solo = _twins(gcrl, "DDPG", P, CFG1)
+    assert pop.acting_counts() == (0, 0, 0, 0, 0)
+    for step in range(K):
+        rows, acts = _act(pop, solo, step, CFG1, eval_action=True)      # (eval: every call reaches the network)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    assert pop.acting_counts() == (K, K, K, K, 0)                       # one launch per call, not one per member
+    for ag in (pop.members[1], solo[1]):
+        ag.buffer.obs_normalizer = RunningNormalizer(CFG1["D"])          # a host object: the members' own methods, one after another
+    for step in range(K, K + 3):
+        rows, acts = _act(pop, solo, step, CFG1, eval_action=True)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    assert pop.acting_counts() == (K, K, K, K, 0)
+    for i in (0, 2, 3):
+        assert np.array_equal(_nz_state(pop.members[i].buffer.obs_normalizer)[0], _nz_state(solo[i].buffer.obs_normalizer)[0])
+    assert np.array_equal(pop.members[1].buffer.obs_normalizer.mean, solo[1].buffer.obs_normalizer.mean)
+
+
+def test_small_ddpg_population_dispatches_member_by_member(gcrl):
+    """the class default: a DDPG population below 4 members calls the members' own entries (measured slower merged)"""
+    pop, solo = _twins(gcrl, "DDPG", 2, CFG1)
+    del pop.MERGE_ACTING_FROM
+    assert type(pop).MERGE_ACTING_FROM == 4 and gcrl.TD3Population.MERGE_ACTING_FROM == 2
+    for step in range(4):
+        rows, acts = _act(pop, solo, step, CFG1)
+        _proc(pop, solo, step, rows, acts, _dones(step))
+    assert pop.acting_counts() == (0, 0, 0, 0, 0)
+    _compare_members(pop, solo)
+
+
+def test_staged_form(gcrl):
+    """64 rows per member are more than the pinned block holds (32): copies around the same one launch"""
+    P, n = 16, 64
+    pop, solo = _twins(gcrl, "DDPG", P, HEADLINE, nenvs=n)
+    for step in range(3):
+        rows, acts = _act(pop, solo, step, HEADLINE, n=n, eval_action=(step == 2))
+    calls, launches, _, _, staged = pop.acting_counts()
+    assert (calls, launches, staged) == (3, 3, 3)
+    _act(pop, solo, 10, HEADLINE, n=8)                                   # and back on the fast form
+    assert pop.acting_counts()[:2] == (4, 4) and pop.acting_counts()[4] == 3
+    acts = [np.zeros((n, HEADLINE["A"]), np.float32) + 0.01 * i for i in range(P)]
+    for step in (20, 21, 22):
+        _proc(pop, solo, step, [_rows(step, i, HEADLINE, n) for i in range(P)], acts, (np.arange(n) % 5 == 0) & (step == 22))
+    assert pop.acting_counts()[2:4] == (3, 3)
+    _compare_members(pop, solo)
+
+
+def test_refusals_on_the_device(gcrl):
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    P = 3
+    pop, solo = _twins(gcrl, "DDPG", P, CFG1)
+    rows = [_rows(0, i, CFG1) for i in range(P)]
+    obs, dg = [r[0]["observation"] for r in rows], [r[0]["desired_goal"] for r in rows]
+    with pytest.raises(gcrl._ffi.GcrlError, match="members"):
+        pop.observe_act(obs[:2], dg[:2])
+    with pytest.raises(gcrl._ffi.GcrlError, match="members"):
+        pop.process_step([r[0] for r in rows], [np.zeros((NENVS, 3), np.float32)] * 2, [r[1] for r in rows], [r[2] for r in rows],
+                         [np.zeros(NENVS, bool)] * P)
+    big = [_rows(0, i, CFG1, n=CFG1["B"] + 1) for i in range(P)]
+    with pytest.raises(ValueError, match=r"\bn\b"):
+        pop.observe_act([r[0]["observation"] for r in big], [r[0]["desired_goal"] for r in big])
+    keep = pop.members[1].buffer.obs_normalizer
+    pop.members[1].buffer.obs_normalizer = DeviceRunningNormalizer(CFG1["D"] + 1)
+    with pytest.raises(ValueError, match="nz_obs"):
+        pop.observe_act(obs, dg, eval_action=True)
+    with pytest.raises(ValueError, match="nz_obs"):
+        pop.process_step([r[0] for r in rows], [np.zeros((NENVS, 3), np.float32)] * P, [r[1] for r in rows], [r[2] for r in rows],
+                         [np.zeros(NENVS, bool)] * P)
+    pop.members[1].buffer.obs_normalizer = keep
+    assert pop.acting_counts()[1] == 0 and pop.acting_counts()[3] == 0   # refused before any launch
+    for step in range(3):                                                # and the population still works
+        r, acts = _act(pop, solo, step, CFG1)
+        _proc(pop, solo, step, r, acts, _dones(step))
+    _compare_members(pop, solo)

@@ -94,20 +94,59 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 }
 
 
+# kernels the scratch lint reports by name whatever their figure (and misses when they are gone): the population acting launches
+SCRATCH_NAMED = {"rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"]}
+
+
 def scratch_report(asm_text, unit):
     bad, lines = 0, []
     kernel = None
+    named = {w: 0 for w in SCRATCH_NAMED.get(unit, [])}
     for line in asm_text.splitlines():
         m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
         if m:
             kernel = m.group(1)
         m = re.match(r"\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
+        if m and kernel and int(m.group(1)) == 0:
+            for w in named:
+                if w in kernel:
+                    named[w] += 1
+                    lines.append(f"{unit}: {kernel}: 0 bytes of scratch per thread: ok")
         if m and kernel and int(m.group(1)) > 0:
             n = int(m.group(1))
             allowed = max([v for k, v in SCRATCH_ALLOWED.items() if k in kernel] + [0])
             ok = n <= allowed
             lines.append(f"{unit}: {kernel}: {n} bytes of scratch per thread: {'tolerated' if ok else 'FAIL'}")
             bad += 0 if ok else 1
+    for w, n in named.items():
+        if n == 0:
+            lines.append(f"{unit}: {w}: not found without scratch (renamed, or it spills: see above): FAIL")
+            bad += 1
+    return bad, lines
+
+
+# Release lint of a kernel whose publication AND arrival are system-scope stores to host-visible memory (rowchain_act_pop_kernel: the
+# float64 actions, then one 8-byte flag per workgroup that the host polls): the flag is the listing's last such store, and an
+# `s_waitcnt vmcnt(0)` must stand between the store before it and the flag.
+FLAG_UNITS = {"rowchain.hip": ["rowchain_act_pop_kernel"]}
+STORE_SYS = re.compile(r"^\s*global_store_dwordx2\s.*\bsc0 sc1\b")
+
+
+def flag_report(asm_text, unit):
+    bad, lines = 0, []
+    for w in FLAG_UNITS.get(unit, []):
+        found = False
+        for name, body in kernels(asm_text):
+            if w not in name or name.endswith(".kd"):
+                continue
+            found = True
+            at = [i for i, l in enumerate(body) if STORE_SYS.match(l)]
+            ok = len(at) >= 2 and any(WAIT0.match(l) for l in body[at[-2] + 1:at[-1]])
+            lines.append(f"{unit}: {name}: {max(len(at) - 1, 0)} system-scope action stores, then the flag store after s_waitcnt vmcnt(0): {'ok' if ok else 'FAIL'}")
+            bad += 0 if ok else 1
+        if not found:
+            lines.append(f"{unit}: {w} not found (pattern changed?)")
+            bad += 1
     return bad, lines
 
 
@@ -168,6 +207,9 @@ def main():
                 if n == 0:
                     report.append(f"{unit}: no instantiation of {w} with a publication found (pattern changed?)")
                     bad += 1
+            b5, lines = flag_report(text, unit)
+            report += lines
+            bad += b5
         sbad = 0
         for unit in SCRATCH_UNITS:
             asm = os.path.join(out_dir, unit + ".s")

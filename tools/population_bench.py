@@ -7,7 +7,15 @@ Each agent trains from its own HER ring of synthetic episodes, `gradient_step` (
 (src/env.py:384-385).  Timing: hipEvents on the stream the updates run on, around `calls` calls after `warmup` untimed ones and
 a device synchronise; steps per member = calls x 40.  Forms: "population" (one DDPGPopulation / TD3Population.update_many per
 call) and "sequential" (each standalone agent's update_many per call, in member order).  TD3 (--kind TD3; its lines carry
-"kind": "TD3") steps its actor every second step with target smoothing on (policy_noise 0.2, noise_clamp 0.5)."""
+"kind": "TD3") steps its actor every second step with target smoothing on (policy_noise 0.2, noise_clamp 0.5).
+
+    python tools/population_bench.py --acting [--kind DDPG|TD3] [--shapes cfg1,headline] [--members 1,2,4,8,16] [--rounds 5] [--steps 3000]
+
+times the ACTING side instead: per vector-env step of 8 envs, `pop.observe_act` + `pop.process_step` ("population") against the same
+members' own `observe_act` + `process_step` made one after another ("members"), device normalisers, an episode of every env ending
+every 50th step so that the flush launches are in.  Both sides run in one process, alternating round by round; wall-clock time per
+round (the calls wait for their results or are host-bound), a device synchronise inside each round's bracket.  One JSON line per
+configuration: median and min-max of the rounds, in microseconds per vector step, per side."""
 import argparse
 import json
 import os
@@ -97,6 +105,63 @@ def run(shape, P, calls, warmup, kind="DDPG"):
     return out
 
 
+def run_acting(shape, P, rounds, steps, kind="DDPG", nenvs=8):
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    sh = SHAPES[shape]
+    G = 3
+    D = sh["S"] - G
+    cfgs = _cfgs(sh, P, kind)
+    seeds = list(range(7, 7 + P))
+    pop_cls, agent_cls = KINDS[kind][:2]
+    pop = pop_cls(sh["S"], sh["A"], cfgs, nenvs, GSTEP, rng="engine", seeds=seeds)
+    for m in pop.members:
+        m.buffer.obs_normalizer = DeviceRunningNormalizer(D)
+        m.buffer.dg_normalizer = DeviceRunningNormalizer(G)
+        m.buffer.compute_reward = her_oracle.sparse_reward
+    gen = np.random.default_rng(5)
+    K = 64    # distinct vector steps, cycled (rows differ from call to call)
+    f = lambda *shp: gen.standard_normal(shp).astype(np.float32)
+    data = [[(dict(observation=f(nenvs, D), achieved_goal=f(nenvs, G), desired_goal=f(nenvs, G)),
+              dict(observation=f(nenvs, D), achieved_goal=f(nenvs, G), desired_goal=f(nenvs, G)),
+              -(gen.random(nenvs) > 0.5).astype(np.float32)) for _ in range(P)] for _ in range(K)]
+    none, alld = [np.zeros(nenvs, bool)] * P, [np.ones(nenvs, bool)] * P
+    ms = pop.members
+
+    def population(k, dn):
+        d = data[k % K]
+        acts = pop.observe_act([x[0]["observation"] for x in d], [x[0]["desired_goal"] for x in d])
+        pop.process_step([x[0] for x in d], [a.astype(np.float32) for a in acts], [x[1] for x in d], [x[2] for x in d], dn)
+
+    def members(k, dn):
+        d = data[k % K]
+        for m, x, dd in zip(ms, d, dn):
+            a = m.observe_act(x[0]["observation"], x[0]["desired_goal"])
+            m.process_step(x[0], a.astype(np.float32), x[1], x[2], dd)
+
+    sides = {"population": population, "members": members}
+    t = {k: [] for k in sides}
+    k = 0
+    for rnd in range(-1, rounds):          # round -1: warm-up, untimed
+        for name, fn in sides.items():
+            n = steps if rnd >= 0 else 200
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                k += 1
+                fn(k, alld if k % 50 == 0 else none)
+            torch.cuda.synchronize()
+            if rnd >= 0:
+                t[name].append((time.perf_counter() - t0) / n * 1e6)
+    counts = pop.acting_counts()
+    r = dict(bench="acting", kind=kind, shape=shape, members=P, nenvs=nenvs, rounds=rounds, steps_per_round=steps,
+             acting_counts=counts, merged=bool(counts[1]), **{k: sh[k] for k in ("S", "A", "H", "L", "B")})
+    for name, v in t.items():
+        r[name + "_us_per_vector_step"] = dict(median=round(float(np.median(v)), 2), min=round(min(v), 2), max=round(max(v), 2),
+                                               rounds=[round(x, 2) for x in v])
+    r["members_over_population"] = round(float(np.median(t["members"]) / np.median(t["population"])), 3)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", default="DDPG", choices=sorted(KINDS))
@@ -105,7 +170,22 @@ def main():
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--acting", action="store_true", help="time observe_act + process_step instead of the update side")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=3000, help="--acting: vector steps per round and side")
     a = ap.parse_args()
+    if a.acting:
+        assert a.rounds >= 5 and a.steps >= 3000 or os.environ.get("POP_BENCH_SHORT"), "at least five rounds of 3 000 vector steps"
+        members = "1,2,4,8,16" if a.members == "1,2,4,8" else a.members
+        with open(a.out, "a") if a.out else open(os.devnull, "w") as f:
+            for shape in a.shapes.split(","):
+                for P in [int(x) for x in members.split(",")]:
+                    for r in run_acting(shape, P, a.rounds, a.steps, a.kind):
+                        line = json.dumps(r)
+                        print(line, flush=True)
+                        f.write(line + "\n")
+                        f.flush()
+        return
     assert a.calls * GSTEP >= 2000 or os.environ.get("POP_BENCH_SHORT"), "at least 2 000 timed steps per member"
     f = open(a.out, "a") if a.out else None
     for shape in a.shapes.split(","):
