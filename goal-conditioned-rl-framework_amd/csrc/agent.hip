@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "act_bn.h"
 #include "dw_adam.h"
 #include "gemm_mfma.h"
 #include "her_ring.h"
@@ -131,6 +132,8 @@ struct gcrl_agent {
   char *oa_pinned = nullptr, *oa_dev = nullptr;   // staging of gcrl_agent_observe_act (raw rows, noise, actions)
   // ... and of its inline form (rowchain.h RowActInline): float64 actions + one flag per workgroup, host-visible
   char* act_fl_host = nullptr; char* act_fl_dev = nullptr; unsigned long long act_seq = 0;
+  // what gcrl_agent_observe_act has issued since creation (gcrl_agent_acting_counts): calls, kernel launches, copies, stream synchronisations
+  long long oa_calls = 0, oa_launches = 0, oa_copies = 0, oa_syncs = 0;
   size_t oa_bytes = 0;
   // row-block DDPG path (rowchain.h): [in][out] weight copies of actor | target actor | critic 0 |
   // target critic 0, per-layer gradient buffers, TD targets
@@ -2320,17 +2323,90 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
   // layout: doubles first (alignment): noise [B*A], out [B*A]; then floats: obs, dg, eps
   double* p_noise = (double*)a->oa_pinned; double* p_out = p_noise + d_cnt; float* p_f = (float*)(p_out + d_cnt);
   double* d_noise = (double*)a->oa_dev; double* d_out = d_noise + d_cnt; float* d_f = (float*)(d_out + d_cnt);
-  if (a->rowchain && !a->sac && n * a->S <= kActInlineFloats && n * A <= kActInlineNoise && !std::getenv("GCRL_ACT_STAGED")) {
-    // ONE launch and nothing else (round 4): the raw rows and the noise travel INSIDE the kernel arguments, the float64 actions come
-    // back through host-visible memory followed by a flag per workgroup, and the host waits for the flags — no staged copies, no
-    // stream synchronisation.  (Before: two copies up, the launch, a copy down, hipStreamSynchronize = 30 us per vector step.)
-    if (a->wt_dirty) TRY(rc_rebuild_wt(a, st));
-    constexpr size_t kFlagOff = 2048;
+  a->oa_calls += 1;
+  const bool staged_knob = std::getenv("GCRL_ACT_STAGED") != nullptr;
+  const bool fits_inline = n * a->S <= kActInlineFloats && n * A <= kActInlineNoise;
+  constexpr size_t kFlagOff = 2048;
+  auto flag_block = [&]() -> int {   // the pinned, mapped block of the inline forms: [n][A] float64 actions, then one flag per workgroup
     if (!a->act_fl_host) {
       GCRL_HIP(hipHostMalloc((void**)&a->act_fl_host, 4096, hipHostMallocMapped));
       std::memset(a->act_fl_host, 0, 4096);
       GCRL_HIP(hipHostGetDevicePointer((void**)&a->act_fl_dev, a->act_fl_host, 0));
     }
+    return GCRL_OK;
+  };
+  auto wait_flags = [&](int nwg, unsigned long long seq) -> int {
+    volatile unsigned long long* flags = reinterpret_cast<volatile unsigned long long*>(a->act_fl_host + kFlagOff);
+    bool seen = false;
+    for (long spin = 0; spin < 4000000 && !seen; ++spin) {      // (~ms: then the ordinary synchronisation says what happened)
+      seen = true;
+      for (int w = 0; w < nwg; ++w) seen = seen && flags[w] == seq;
+      if (!seen) __builtin_ia32_pause();
+    }
+    if (!seen) { GCRL_HIP(hipStreamSynchronize(st)); a->oa_syncs += 1; }   // (defined before sync_stream: the same count)
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    std::memcpy(out_host, a->act_fl_host, sizeof(double) * n * A);
+    return GCRL_OK;
+  };
+  // every copy and synchronisation of this entry goes through these two, which is where they are counted
+  auto copy_async = [&](void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) -> int {
+    GCRL_HIP(hipMemcpyAsync(dst, src, nbytes, kind, st));
+    a->oa_copies += 1;
+    return GCRL_OK;
+  };
+  auto sync_stream = [&]() -> int {
+    GCRL_HIP(hipStreamSynchronize(st));
+    a->oa_syncs += 1;
+    return GCRL_OK;
+  };
+  auto rebuild_wt = [&]() -> int {   // (the row-chain actors' [in][out] weight copies after a parameter write)
+    if (!a->wt_dirty) return GCRL_OK;
+    a->oa_launches += 1 + (a->has_target_actor ? 1 : 0) + 2 * a->C;
+    return rc_rebuild_wt(a, st);
+  };
+  if (a->sac && !staged_knob) {
+    // The BatchNorm actor (SAC / TQC, round 9): ONE launch of act_bn.hip on the live parameter vector and running statistics — the
+    // normaliser prologue, the hidden blocks, both heads and the sampling.  (GCRL_ACT_STAGED=1: the chain of separate launches below.)
+    ActBnInline bi;
+    ActBnArgs& ba = bi.base;
+    std::memset(&ba, 0, sizeof(ba));
+    ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
+    ba.S = a->S; ba.H = a->H; ba.L = a->L; ba.A = A; ba.n = n; ba.D = D;
+    ba.ldl = (std::max(a->S, a->H) + 3) / 4 * 4;
+    ba.warm = std::getenv("GCRL_ACT_BN_WARM") ? 1 : 0;   // (measured slower at both shapes, profiles/r09_sac_acting.jsonl: off unless asked for)
+    gcrl::normalizer_view(nz_obs, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
+    gcrl::normalizer_view(nz_dg, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
+    if (fits_inline) {
+      TRY(flag_block());
+      for (int i = 0; i < n; ++i) {
+        std::memcpy(bi.obs_inl + (size_t)i * a->S, obs_host + (size_t)i * D, sizeof(float) * D);
+        std::memcpy(bi.obs_inl + (size_t)i * a->S + D, dg_host + (size_t)i * G, sizeof(float) * G);
+      }
+      bi.with_eps = noise_host ? 1 : 0;
+      if (noise_host) std::memcpy(bi.eps_inl, noise_host, sizeof(double) * n * A);
+      bi.out_host = reinterpret_cast<double*>(a->act_fl_dev);
+      bi.flag_host = reinterpret_cast<unsigned long long*>(a->act_fl_dev + kFlagOff);
+      bi.seq = ++a->act_seq;
+      TRY(launch_act_bn_inline(st, bi));
+      a->oa_launches += 1;
+      return wait_flags((n + kActBnRows - 1) / kActBnRows, bi.seq);
+    }
+    // more rows than the kernel arguments hold: one copy up (rows, then the eps as float32), the same body, one copy down
+    for (int i = 0; i < n; ++i) {
+      std::memcpy(p_f + (size_t)i * a->S, obs_host + (size_t)i * D, sizeof(float) * D);
+      std::memcpy(p_f + (size_t)i * a->S + D, dg_host + (size_t)i * G, sizeof(float) * G);
+    }
+    if (noise_host) for (int i = 0; i < n * A; ++i) p_f[(size_t)n * a->S + i] = (float)noise_host[i];
+    TRY(copy_async(d_f, p_f, sizeof(float) * ((size_t)n * a->S + (noise_host ? (size_t)n * A : 0)), hipMemcpyHostToDevice));
+    ba.rows = d_f; ba.eps = noise_host ? d_f + (size_t)n * a->S : nullptr; ba.out64 = d_out;
+    TRY(launch_act_bn(st, ba));
+    a->oa_launches += 1;
+  } else if (a->rowchain && !a->sac && fits_inline && !staged_knob) {
+    // ONE launch and nothing else (round 4): the raw rows and the noise travel INSIDE the kernel arguments, the float64 actions come
+    // back through host-visible memory followed by a flag per workgroup, and the host waits for the flags — no staged copies, no
+    // stream synchronisation.  (Before: two copies up, the launch, a copy down, hipStreamSynchronize = 30 us per vector step.)
+    TRY(rebuild_wt());
+    TRY(flag_block());
     RowActInline ri;
     RowActArgs& ra = ri.base;
     std::memset(&ra, 0, sizeof(ra));
@@ -2351,23 +2427,12 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
     ri.flag_host = reinterpret_cast<unsigned long long*>(a->act_fl_dev + kFlagOff);
     ri.seq = ++a->act_seq;
     TRY(launch_rowchain_act_inline(st, ri));
-    const int nwg = (n + 3) / 4;
-    volatile unsigned long long* flags = reinterpret_cast<volatile unsigned long long*>(a->act_fl_host + kFlagOff);
-    bool seen = false;
-    for (long spin = 0; spin < 4000000 && !seen; ++spin) {      // (~ms: then the ordinary synchronisation says what happened)
-      seen = true;
-      for (int w = 0; w < nwg; ++w) seen = seen && flags[w] == ri.seq;
-      if (!seen) __builtin_ia32_pause();
-    }
-    if (!seen) GCRL_HIP(hipStreamSynchronize(st));
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    std::memcpy(out_host, a->act_fl_host, sizeof(double) * n * A);
-    return GCRL_OK;
-  }
-  if (a->rowchain && !a->sac) {
+    a->oa_launches += 1;
+    return wait_flags((n + 3) / 4, ri.seq);
+  } else if (a->rowchain && !a->sac) {
     // ONE launch: raw [observation | goal] rows up, normalisation in the row-chain act kernel's prologue, select_action's
     // tanh / noise / clip in its epilogue
-    if (a->wt_dirty) TRY(rc_rebuild_wt(a, st));
+    TRY(rebuild_wt());
     for (int i = 0; i < n; ++i) {
       std::memcpy(p_f + (size_t)i * a->S, obs_host + (size_t)i * D, sizeof(float) * D);
       std::memcpy(p_f + (size_t)i * a->S + D, dg_host + (size_t)i * G, sizeof(float) * G);
@@ -2375,8 +2440,8 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
     const bool with_noise = noise_host && mode == 1;
     if (with_noise) std::memcpy(p_noise, noise_host, sizeof(double) * n * A);
     // noise [B*A doubles], out [B*A doubles] and the rows are contiguous in the staging block: one copy covers what is used
-    if (with_noise) GCRL_HIP(hipMemcpyAsync(d_noise, p_noise, sizeof(double) * n * A, hipMemcpyHostToDevice, st));
-    GCRL_HIP(hipMemcpyAsync(d_f, p_f, sizeof(float) * (size_t)n * a->S, hipMemcpyHostToDevice, st));
+    if (with_noise) TRY(copy_async(d_noise, p_noise, sizeof(double) * n * A, hipMemcpyHostToDevice));
+    TRY(copy_async(d_f, p_f, sizeof(float) * (size_t)n * a->S, hipMemcpyHostToDevice));
     RowActArgs ra;
     std::memset(&ra, 0, sizeof(ra));
     ra.actor = make_rownet(a, a->actor, a->P_actor(), 0);
@@ -2388,6 +2453,7 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
     ra.post = mode == 1 ? 1 : (mode == 0 ? 2 : 3);
     ra.noise = with_noise ? d_noise : nullptr; ra.out64 = d_out;
     TRY(launch_rowchain_act(st, ra));
+    a->oa_launches += 1;
   } else {
   std::memcpy(p_f, obs_host, sizeof(float) * n * D);
   std::memcpy(p_f + (size_t)n * D, dg_host, sizeof(float) * n * G);
@@ -2396,8 +2462,8 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
     if (eps_act) for (int i = 0; i < n * A; ++i) p_f[(size_t)n * (D + G) + i] = (float)noise_host[i];
     else std::memcpy(p_noise, noise_host, sizeof(double) * n * A);
   }
-  if (noise_host && !eps_act) GCRL_HIP(hipMemcpyAsync(d_noise, p_noise, sizeof(double) * n * A, hipMemcpyHostToDevice, st));
-  GCRL_HIP(hipMemcpyAsync(d_f, p_f, sizeof(float) * ((size_t)n * (D + G) + (eps_act ? (size_t)n * A : 0)), hipMemcpyHostToDevice, st));
+  if (noise_host && !eps_act) TRY(copy_async(d_noise, p_noise, sizeof(double) * n * A, hipMemcpyHostToDevice));
+  TRY(copy_async(d_f, p_f, sizeof(float) * ((size_t)n * (D + G) + (eps_act ? (size_t)n * A : 0)), hipMemcpyHostToDevice));
   TRY(gcrl::normalizer_apply_dev(nz_obs, d_f, n, D, D, a->act_in, a->S, 0, st));
   if (G) TRY(gcrl::normalizer_apply_dev(nz_dg, d_f + (size_t)n * D, n, G, G, a->act_in, a->S, D, st));
   TRY(gcrl_agent_act(a, a->act_in, n, a->S, a->dact, a->Apad, eps_act ? d_f + (size_t)n * (D + G) : nullptr, stream));
@@ -2405,10 +2471,23 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
   hipLaunchKernelGGL(act_post_kernel, dim3((n * A + 255) / 256), dim3(256), 0, st, a->dact, a->Apad, n, A,
                      (noise_host && !eps_act) ? d_noise : nullptr, pm, d_out);
   GCRL_HIP(hipGetLastError());
+  // the normaliser launch(es) and act_post_kernel issued here, plus what gcrl_agent_act issues for this agent kind (BatchNorm actor: a
+  // GEMM and a BatchNorm launch per hidden block, the heads' GEMMs, the sampling; else a GEMM launch per layer) — that part is
+  // DECLARED from gcrl_agent_act's definition, not observed (the function is shared with select_action and left as it is)
+  a->oa_launches += 1 + (G ? 1 : 0) + (a->sac ? 2 * a->L + 2 : a->L + 1) + 1;
   }
-  GCRL_HIP(hipMemcpyAsync(p_out, d_out, sizeof(double) * n * A, hipMemcpyDeviceToHost, st));
-  GCRL_HIP(hipStreamSynchronize(st));
+  TRY(copy_async(p_out, d_out, sizeof(double) * n * A, hipMemcpyDeviceToHost));
+  TRY(sync_stream());
   std::memcpy(out_host, p_out, sizeof(double) * n * A);
+  return GCRL_OK;
+}
+
+int gcrl_agent_acting_counts(const gcrl_agent* a, int64_t* calls, int64_t* launches, int64_t* copies, int64_t* syncs) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_acting_counts: null handle");
+  if (calls) *calls = a->oa_calls;
+  if (launches) *launches = a->oa_launches;
+  if (copies) *copies = a->oa_copies;
+  if (syncs) *syncs = a->oa_syncs;
   return GCRL_OK;
 }
 

@@ -17,8 +17,7 @@
 namespace gcrl {
 namespace {
 
-constexpr float kBnEps = 1e-5f;       // nn.BatchNorm1d default eps
-// (kBnMomentum, bn_running_update, tanh_gauss_elem: sac_select.h)
+// (kBnEps, kBnMomentum, bn_relu_eval_elem, bn_running_update, tanh_gauss_elem: sac_select.h)
 
 __device__ inline float wave_sum(float v) {
 #pragma unroll
@@ -239,8 +238,7 @@ __global__ void bn_relu_eval_kernel(const float* z, int B, int H, const float* g
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)B * H) return;
   const int col = (int)(i % H);
-  const float y = (z[i] - rmean[col]) * (1.0f / sqrtf(rvar[col] + kBnEps)) * gamma[col] + beta[col];
-  h[i] = y > 0.f ? y : 0.f;
+  h[i] = bn_relu_eval_elem(z[i], rmean[col], rvar[col], gamma[col], beta[col]);
 }
 
 // backward: dy = dh (+ dh2) where the forward's output was positive.  The mask is recomputed from xhat exactly as the
@@ -373,7 +371,7 @@ __device__ inline void tanh_gauss_fwd_row(const TanhGaussArgs& a, int b) {
   float lp = 0.f;
   for (int j = 0; j < a.A; ++j) {
     const float mu = a.mu[(long long)b * a.ld_head + j];
-    if (a.deterministic) { act[j] = (float)tanh((double)mu); continue; }
+    if (a.deterministic) { act[j] = tanh_gauss_mean(mu); continue; }
     const long long i = (long long)b * a.A + j;
     const TgElem r = tanh_gauss_elem(a, c, mu, a.ls_raw[(long long)b * a.ld_head + j], i);
     act[j] = r.t;

@@ -29,15 +29,14 @@ __device__ inline float sel_block_sum(float v, float* scratch) {
 
 // one (row, action) element of SACActorModel.sample: action t, std sd, the log-prob term, the eps used
 struct TgElem { float t, sd, term, e; };
-// (eps: injected N(0,1) [B][A] or null: the counter hash, stream `rng_stream` of `seed`, at the step's counter + i)
-__device__ inline TgElem tanh_gauss_elem_raw(const float* eps, unsigned long long seed, int rng_stream, const StepCtrl& c, float mu, float ls_raw, long long i) {
+// (eps_at(): this element's N(0,1) draw, asked for once, after the scale is formed)
+template <typename EpsAt>
+__device__ inline TgElem tanh_gauss_elem_with(EpsAt eps_at, float mu, float ls_raw) {
   const float ls = fminf(fmaxf(ls_raw, -20.0f), 2.0f);
   // exp / tanh / log go through fp64 and round once: log(1 - tanh^2 + 1e-8) amplifies a 1-ulp
   // tanh difference by 2|t|/(1-t^2), so the closer to correctly rounded, the closer to torch
   const float sd = (float)exp((double)ls);
-  const float e = eps ? eps[i]
-                        : hash_normal(seed + (unsigned long long)rng_stream,
-                                      (((unsigned long long)c.rng_hi << 32) | c.rng_lo) + (unsigned long long)i);
+  const float e = eps_at();
   const float x = __fadd_rn(mu, __fmul_rn(e, sd));  // rsample: loc + eps*scale
   const float t = (float)tanh((double)x);
   // Normal(mu, sd).log_prob(x) - log(1 - tanh(x)^2 + 1e-8), every op rounded to fp32 as torch does
@@ -49,11 +48,27 @@ __device__ inline TgElem tanh_gauss_elem_raw(const float* eps, unsigned long lon
   term = __fsub_rn(term, (float)log((double)om));
   return {t, sd, term, e};
 }
+// the deterministic action of SACActorModel (eval: tanh of the mean head), rounded once like the sample above
+__device__ inline float tanh_gauss_mean(float mu) { return (float)tanh((double)mu); }
+// (eps: injected N(0,1) [B][A] or null: the counter hash, stream `rng_stream` of `seed`, at the step's counter + i)
+__device__ inline TgElem tanh_gauss_elem_raw(const float* eps, unsigned long long seed, int rng_stream, const StepCtrl& c, float mu, float ls_raw, long long i) {
+  return tanh_gauss_elem_with([&]() {
+    return eps ? eps[i]
+               : hash_normal(seed + (unsigned long long)rng_stream,
+                             (((unsigned long long)c.rng_hi << 32) | c.rng_lo) + (unsigned long long)i);
+  }, mu, ls_raw);
+}
 __device__ inline TgElem tanh_gauss_elem(const TanhGaussArgs& a, const StepCtrl& c, float mu, float ls_raw, long long i) {
   return tanh_gauss_elem_raw(a.eps, a.seed, a.rng_stream, c, mu, ls_raw, i);
 }
 
 constexpr float kBnMomentum = 0.1f;   // nn.BatchNorm1d's default momentum
+constexpr float kBnEps = 1e-5f;       // nn.BatchNorm1d default eps
+// BatchNorm1d(eval) + ReLU of one element (src/model.py:106-108 with the running statistics)
+__device__ inline float bn_relu_eval_elem(float z, float rmean, float rvar, float gamma, float beta) {
+  const float y = (z - rmean) * (1.0f / sqrtf(rvar + kBnEps)) * gamma + beta;
+  return y > 0.f ? y : 0.f;
+}
 // running statistics from the batch statistics of the slab launches (bn_slab.hip), momentum 0.1, unbiased variance
 __device__ inline void bn_running_update(const BnRunning& r) {
   const float ub = r.B > 1 ? (float)r.B / (float)(r.B - 1) : 1.0f;

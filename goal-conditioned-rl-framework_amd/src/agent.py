@@ -423,6 +423,14 @@ class _EngineAgent:
                                               ptr["noise"] if noise is not None else None, mode, ptr["out"], _ffi.stream_handle()))
         return buf["out"].copy()
 
+    def acting_counts(self) -> dict:
+        """What `observe_act`'s native entry has issued since this agent was created: calls, kernel launches, host <-> device copies
+        and stream synchronisations (include/gcrl.h gcrl_agent_acting_counts).  The one-launch forms add one launch and nothing else
+        per call; calls that never reach the entry (host normalisers, DDPG's epsilon-random action) are not counted."""
+        v = [C.c_int64(0) for _ in range(4)]
+        _ffi.check(lib.gcrl_agent_acting_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "launches", "copies", "syncs"), (int(x.value) for x in v)))
+
     def _act_noise(self, n, eval_action):
         """-> (noise or None, mode); DDPG overrides for the epsilon branch."""
         if eval_action:

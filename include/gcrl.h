@@ -559,6 +559,17 @@ int gcrl_normalizer_set_rows_float64(gcrl_normalizer* z, int on);
 int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, const float* obs_host, int obs_dim,
                            const float* dg_host, int goal_dim, int n, const double* noise_host, int mode, double* out_host,
                            void* stream);
+/* How gcrl_agent_observe_act has done its work since the agent was created: calls, the kernel launches, the host <-> device
+ * copies and the stream synchronisations it issued.  Up to the rows the kernel arguments hold (n * state_dim <= 640, n * action_dim
+ * <= 96) every agent kind takes ONE launch, no copy and no synchronisation per call: DDPG / TD3 the row-chain act kernel
+ * (src/model.py:32-49 + src/agent.py:1345-1366 / :253-270), SAC / TQC the BatchNorm actor's (src/model.py:118-141 in eval mode +
+ * src/agent.py:641-647); more rows: copies up, the same launch, a copy down, one synchronisation.  GCRL_ACT_STAGED=1 in the
+ * environment selects the staged forms (SAC / TQC: the chain of separate launches: normalisers, a GEMM and a BatchNorm launch per
+ * hidden block, the heads, the sampling, the float64 conversion).  A launch that rebuilds weight copies after a parameter write is
+ * counted with the call that issued it.  Copies and synchronisations are counted where they are issued, and so are the launches of
+ * the one-launch forms; the launches of the staged chain (gcrl_agent_act's part) and of a weight-copy rebuild are declared from
+ * those functions' definitions.  Refuses a NULL handle; any of the four pointers may be NULL. */
+int gcrl_agent_acting_counts(const gcrl_agent* a, int64_t* calls, int64_t* launches, int64_t* copies, int64_t* syncs);
 /* _process_step for one vector-env step (src/env.py:163-201) from raw host rows: normaliser update with [obs ; next_obs]
  * (when update_stats), state = [normalize(obs) | dg], next_state = [normalize(next_obs) | next_dg] built on the device
  * from the UPDATED statistics, then the n pushes of gcrl_her_push_batch (achieved goal = next_ag, done = dones).

@@ -10,7 +10,8 @@ global atomic add that follows write-through stores in the listing is preceded â
 `s_waitcnt vmcnt(0)`.  Listing order is not control flow, so this is a lint, not a proof; it catches exactly the
 regression the advisor found in the ISA.
 
-usage: tools/check_release_isa.py [--keep DIR]      exit code 0 = every checked kernel passes
+usage: tools/check_release_isa.py [--keep DIR] [--units a.hip,b.hip]      exit code 0 = every checked kernel passes
+(--units: only these translation units, for a test that is about one of them)
 """
 import os
 import re
@@ -32,6 +33,7 @@ UNITS = {
     "xchg_ipc.hip": ["xchg_two_shot_kernel"],
     "ops.hip": ["td_loss_kernelILi3ELi0ELb1"],
     "ops_sac.hip": ["actor_select_alpha_mb_kernel"],
+    "act_bn.hip": [],   # no arrivals at counters: its flag store is checked by flag_report below
 }
 
 STORE_WT = re.compile(r"^\s*(buffer_store|global_store|flat_store)\S*\s.*\bsc1\b")
@@ -87,7 +89,7 @@ def check_kernel(body):
 # by-value argument struct made hipcc copy the whole 3.7 KB struct to every thread's private memory â€” a 3 us kernel took 36 us
 # (rowchain_act_inline_kernel, round 4).  `.amdhsa_private_segment_fixed_size` says it all.
 SCRATCH_UNITS = ["her_ring.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "rowchain.hip", "agent.hip", "normalizer.hip", "abi_misc.hip",
-                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip"]
+                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip", "act_bn.hip"]
 SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
     "rowchain_split_kernelILi4E": 64,   # 16 rows per workgroup: register spills; never selected by default (GCRL_ROW_RG=4)
     "gemm_tiled_kernel": 16,                                                   # three spilled dwords outside the k-loop
@@ -95,7 +97,9 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 
 
 # kernels the scratch lint reports by name whatever their figure (and misses when they are gone): the population acting launches
-SCRATCH_NAMED = {"rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"]}
+# ... and the BatchNorm actor's acting launches (act_bn.hip)
+SCRATCH_NAMED = {"rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"],
+                 "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel"]}
 
 
 def scratch_report(asm_text, unit):
@@ -128,7 +132,7 @@ def scratch_report(asm_text, unit):
 # Release lint of a kernel whose publication AND arrival are system-scope stores to host-visible memory (rowchain_act_pop_kernel: the
 # float64 actions, then one 8-byte flag per workgroup that the host polls): the flag is the listing's last such store, and an
 # `s_waitcnt vmcnt(0)` must stand between the store before it and the flag.
-FLAG_UNITS = {"rowchain.hip": ["rowchain_act_pop_kernel"]}
+FLAG_UNITS = {"rowchain.hip": ["rowchain_act_pop_kernel"], "act_bn.hip": ["act_bn_inline_kernel"]}
 STORE_SYS = re.compile(r"^\s*global_store_dwordx2\s.*\bsc0 sc1\b")
 
 
@@ -148,6 +152,21 @@ def flag_report(asm_text, unit):
             lines.append(f"{unit}: {w} not found (pattern changed?)")
             bad += 1
     return bad, lines
+
+
+# Scalar-memory lint: no kernel of a checked unit writes memory through the scalar unit â€” scalar stores (plain, buffer, scratch), scalar
+# atomics, or the scalar data cache's write-back / discard.  Values leave through vector stores.  (The mnemonics are assembled from
+# pieces here so that this file does not contain them.)
+SCALAR_WRITE = re.compile(r"^\s*s_(buffer_|scratch_)?(" + "sto" + "re|" + "ato" + "mic)|^\s*s_" + "dca" + "che_(wb|discard)")
+SCALAR_NAMED = ["act_bn.hip"]   # reported by name even when clean
+
+
+def scalar_report(asm_text, unit):
+    hits = [l.strip() for l in asm_text.splitlines() if SCALAR_WRITE.match(l)]
+    lines = [f"{unit}: scalar-unit write `{h}`: FAIL" for h in hits[:5]]
+    if not hits and unit in SCALAR_NAMED:
+        lines.append(f"{unit}: no scalar-unit stores, atomics or data-cache write-backs: ok")
+    return len(hits), lines
 
 
 # Third lint (round 5): the fused dW + optimiser launch (dw_adam.hip) hands a workgroup's sum of squares to every other workgroup as
@@ -176,11 +195,16 @@ def main():
     if "--keep" in sys.argv:
         keep = sys.argv[sys.argv.index("--keep") + 1]
         os.makedirs(keep, exist_ok=True)
+    only = None
+    if "--units" in sys.argv:
+        only = set(sys.argv[sys.argv.index("--units") + 1].split(","))
     bad = 0
     report = []
     with tempfile.TemporaryDirectory() as tmp:
         out_dir = keep or tmp
         for unit, wanted in UNITS.items():
+            if only is not None and unit not in only:
+                continue
             src = os.path.join(CSRC, unit)
             if not os.path.exists(src):
                 report.append(f"{unit}: MISSING source")
@@ -212,20 +236,27 @@ def main():
             bad += b5
         sbad = 0
         for unit in SCRATCH_UNITS:
+            if only is not None and unit not in only:
+                continue
             asm = os.path.join(out_dir, unit + ".s")
             if not os.path.exists(asm):
                 subprocess.run([HIPCC] + FLAGS + ["-x", "hip", os.path.join(CSRC, unit), "-o", asm], check=True, cwd=CSRC)
             b, lines = scratch_report(open(asm).read(), unit)
             sbad += b
             report += lines
-        b3, lines = slot_report(open(os.path.join(out_dir, "dw_adam.hip.s")).read())
-        report += lines
-        sbad += b3
+            b6, lines = scalar_report(open(asm).read(), unit)
+            sbad += b6
+            report += lines
+        if only is None or "dw_adam.hip" in only:
+            b3, lines = slot_report(open(os.path.join(out_dir, "dw_adam.hip.s")).read())
+            report += lines
+            sbad += b3
         # (mangled names: bn_linear_fwd_slab_kernelILb<VEC>ELi<NT>ELi<WV>EE / bn_linear_bwd_slab_kernelILi<NT>ELi<WV>EE)
-        b4, lines = slot_report(open(os.path.join(out_dir, "bn_slab.hip.s")).read(), "bn_slab.hip",
-                                ("bn_linear_fwd_slab_kernelILb1ELi1E", "bn_linear_fwd_slab_kernelILb0ELi1E", "bn_linear_bwd_slab_kernelILi1E", "bn_linear_bwd_slab_fold_kernel"))
-        report += lines
-        sbad += b4
+        if only is None or "bn_slab.hip" in only:
+            b4, lines = slot_report(open(os.path.join(out_dir, "bn_slab.hip.s")).read(), "bn_slab.hip",
+                                    ("bn_linear_fwd_slab_kernelILb1ELi1E", "bn_linear_fwd_slab_kernelILb0ELi1E", "bn_linear_bwd_slab_kernelILi1E", "bn_linear_bwd_slab_fold_kernel"))
+            report += lines
+            sbad += b4
     print("\n".join(report))
     print("release check:", "PASS" if bad == 0 else f"FAIL ({bad})")
     print("scratch check:", "PASS" if sbad == 0 else f"FAIL ({sbad})")
