@@ -123,10 +123,13 @@ PROTOTYPES = {
     "gcrl_agent_update_n": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     "gcrl_agent_metrics": (C.c_int, [_vp, _i64, _vp, C.c_int]),
     "gcrl_pop_create": (_vp, [C.POINTER(AgentConfig), C.c_int32]),
+    "gcrl_pop_create_forms": (_vp, [C.POINTER(AgentConfig), C.c_int32]),
     "gcrl_pop_member": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp)]),
     "gcrl_pop_size": (C.c_int32, [_vp]),
     "gcrl_pop_update_n": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
     "gcrl_pop_launch_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_pop_forms": (C.c_int, [_vp]),
+    "gcrl_pop_forms_terms": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_observe_act": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "gcrl_pop_process_step": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         C.c_int32, C.c_int32, _vp, _vp]),

@@ -581,6 +581,11 @@ int row_rg_of(int kind, int B) {
 // TD3's critic phase as role-parallel launches once the batch fills the chip (cfg 3: 183.5 -> 178.4 us/step; below that the fused
 // launch is the shorter chain)
 bool td3_split_k_rule(int B, int rg) { return (B + 4 * rg - 1) / (4 * rg) >= 256 && !std::getenv("GCRL_NO_SPLIT_TD3"); }
+// SAC: the BatchNorm actor's slab launches (bn_slab.hip), the twin critics' role-split chain launches while the fused form leaves CUs idle, and the
+// actor's heads folded into them — the path a SAC population needs
+bool sac_slab_rule(int B, int H) { return bn_slab_ok(B, H) && !std::getenv("GCRL_NO_BN_SLAB"); }
+bool sac_split_roles_rule(int C, int B, int rg) { return C == 2 && (B + 4 * rg - 1) / (4 * rg) <= 256 && !std::getenv("GCRL_NO_SPLIT_ROLES"); }
+bool sac_heads_fold_env_off() { return std::getenv("GCRL_NO_HEADS_FOLD") != nullptr; }
 
 bool graph_on(const gcrl_agent* a) {
   if (a->bn_sync.world > 1 && !a->bn_xchg_h) return false;   // (an exchange that is a kernel of the sequence replays like any other)
@@ -799,6 +804,8 @@ int enqueue_phase1_body(gcrl_agent* a, hipStream_t st, int variant) {
   bool sel_deferred = false;
   ActorSelArgs as_d;
   AlphaArgs al_d;
+  std::memset(&as_d, 0, sizeof(as_d));   // (padding too: population launches cache their argument tables by content)
+  std::memset(&al_d, 0, sizeof(al_d));
   if (a->sac) {
     ActorSelArgs as;
     std::memset(&as, 0, sizeof(as));
@@ -820,7 +827,7 @@ int enqueue_phase1_body(gcrl_agent* a, hipStream_t st, int variant) {
       TRY(launch_alpha_update(st, al));
     } else if (a->rowchain) {
       sel_deferred = true;   // metrics + log-alpha gradient only on this path: rides on the tanh-Gaussian backward launch below
-      as_d = as; al_d = al;
+      std::memcpy(&as_d, &as, sizeof(as)); std::memcpy(&al_d, &al, sizeof(al));
     } else {
       if (met_rider) { as.mean_x = a->qt; as.mean_n = C * B * a->Q; as.mean_index = MET_Q; }
       if (!a->red_off) { as.part = a->red_sel(); as.ticket = a->red_ticket(1); }
@@ -1340,7 +1347,7 @@ int build(gcrl_agent* a) {
   // dgamma | dbeta of every BatchNorm layer: one slot per 16-column slab (bn_slab.hip; the GEMM + BatchNorm launches use the
   // first ceil(H/64) of a layer's slots, the rest stay zero)
   a->bn_slots = (H + 15) / 16;
-  a->bn_slab = a->sac && bn_slab_ok(B, H) && !std::getenv("GCRL_NO_BN_SLAB");
+  a->bn_slab = a->sac && sac_slab_rule(B, H);
   {
     // (the row groups of a slab wait for each other inside the launch: all (H/16) x ceil(B/128) x 2 workgroups of 512 threads
     // must be resident at once — by the kernels' own occupancy on a device this process has to itself: bn_slab_row_split, meet.h)
@@ -1387,8 +1394,7 @@ int build(gcrl_agent* a) {
                   rowchain_lds_bytes(a->row_rg, a->row_ldl, A, H, C) <= 160 * 1024;
     // SAC (the BatchNorm actor runs outside the chain kernels, both phases are critic-only): split by roles while the
     // fused form leaves CUs idle, i.e. up to ~one workgroup per CU per role pair
-    a->split_roles = a->rowchain && c.kind == GCRL_AGENT_SAC && C == 2 && (B + 4 * a->row_rg - 1) / (4 * a->row_rg) <= 256 &&
-                     !std::getenv("GCRL_NO_SPLIT_ROLES");
+    a->split_roles = a->rowchain && c.kind == GCRL_AGENT_SAC && sac_split_roles_rule(C, B, a->row_rg);
     for (int i = 0; i < 4; ++i) a->split_rg[i] = a->row_rg;
     {
       const long long nblk = (B + 4 * a->row_rg - 1) / (4 * a->row_rg);

@@ -1,20 +1,28 @@
-// agent_pop.inc — DDPG and TD3 populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
+// agent_pop.inc — DDPG, TD3 and SAC populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
 //
-// P independent DDPG or TD3 agents of one kind and equal shapes whose update steps share launches.  Each member is an ordinary gcrl_agent (its own
+// P independent DDPG, TD3 or SAC agents of one kind and equal shapes whose update steps share launches.  Each member is an ordinary gcrl_agent (its own
 // parameters, optimiser state, control block, metric ring and meeting counters), so every single-agent entry works on it.  A
 // population call records each member's launch sequence of the call (pop.h: the launchers record instead of launching), then
 // issues position k of all sequences together: one launch of the kernel's population form (rowchain_ddpg_pop_kernel,
-// dw_adam_pop_kernel, begin_step_pop_kernel, gemm_batch_pop_kernel<1, 1, 4>, adam_pop_kernel, adam_pair_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
+// dw_adam_pop_kernel, begin_step_pop_kernel, gemm_batch_pop_kernel<1, 1, 4>, adam_pop_kernel, adam_pair_pop_kernel; SAC: the slab launches' bn_linear_*_slab_*pop_kernel, rowchain_split_[heads_]pop_kernel, tanh_gauss_bwd_select_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
 // arithmetic in the same order as the member's own launch, so each member computes bit for bit what it computes alone.
 // Launches without a population form are issued member by member at their position.
 //
 // Admission (meet.h): a launch whose workgroups wait for each other is issued in its waiting form only when the WHOLE population
-// launch is resident at once; otherwise the members record the no-wait form of that stage (same bits).
+// launch is resident at once; otherwise the members record the no-wait form of that stage (same bits — except SAC's slab launches, whose
+// row-split and one-workgroup forms sum a column in different orders: gcrl_pop_forms says which the population runs, and a member is bitwise a
+// standalone agent running the same forms).
 
 struct gcrl_pop {
   std::vector<gcrl_agent*> m;
   std::map<std::string, void*> tabs;   // device argument tables of the population launches, by content (they repeat call after call)
   std::vector<PopRec> rec;
+  // SAC: whether P x a member's workgroups of the row-split slab launches / of part 3 of the split chain launch are resident at once (fixed at
+  // creation: a function of P, the shapes and whether the device is shared)
+  // admission of the waiting forms, per form bit (1 row-split slab launches, 2 merged chain launch / DDPG's k-split critic phase, 8 fused
+  // optimiser launch): P x a member's workgroups of the form against what is resident at once (gcrl_pop_forms_terms)
+  long long want[3] = {0, 0, 0}, cap[3] = {0, 0, 0};
+  bool no_waits = false;               // GCRL_POP_NO_WAITS=1 at creation: the population admits no waiting form (A/B knob)
   int64_t merged = 0, alone = 0;       // recorded positions issued as one population launch / member by member (gcrl_pop_launch_counts)
   // acting side (gcrl_pop_observe_act, gcrl_pop_process_step; counts: gcrl_pop_acting_counts)
   PopTabCache act_tabs;                // device tables of the members' RowActArgs
@@ -101,13 +109,19 @@ int pop_issue(gcrl_pop* p, size_t k, hipStream_t st) {
     case POP_GEMM_BATCH: return launch_gemm_batch_pop(st, tab, (int)P, o.sub, o.grid);
     case POP_ADAM: return launch_adam_pop(st, tab, (int)P, o.grid);
     case POP_ADAM_PAIR: return launch_adam_pair_pop(st, tab, (int)P, o.grid);
+    case POP_BN_FWD: return launch_bn_fwd_slab_pop(st, tab, (int)P, o.sub, o.grid);
+    case POP_BN_BWD: return launch_bn_bwd_slab_pop(st, tab, (int)P, o.sub, o.grid);
+    case POP_BN_BWD_FOLD: return launch_bn_bwd_slab_fold_pop(st, tab, (int)P, o.sub, o.grid);
+    case POP_RC_SPLIT: return launch_rowchain_split_pop(st, tab, (int)P, o.sub, false, o.grid, o.lds);
+    case POP_RC_SPLIT_HEADS: return launch_rowchain_split_pop(st, tab, (int)P, o.sub, true, o.grid, o.lds);
+    case POP_TG_BWD_SELECT: return launch_tanh_gauss_bwd_select_pop(st, tab, (int)P, o.grid);
     default: return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: launch kind %d has no population form", o.kind);
   }
 }
 
 // record member a's launches of m planned steps (stream capture around the recording: a launch that bypassed the recorder would
 // land in the captured graph instead of running out of order — refused below).  DDPG: the overlapped schedule of
-// gcrl_agent_update_n (run_steps_ddpg); TD3: its per-step phases with the variant bits gcrl_agent_update_n gives them on the
+// gcrl_agent_update_n (run_steps_ddpg); TD3 and SAC: their per-step phases with the variant bits gcrl_agent_update_n gives them on the
 // row-chain path (every step pre-advanced, its last launch advancing the control block)
 int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>& plans, PopRec* rec) {
   rec->ops.clear();
@@ -117,7 +131,7 @@ int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>&
   pop_rec() = rec;
   g_pop_recorders.fetch_add(1);
   int rc = GCRL_OK;
-  if (a->cfg.kind == GCRL_AGENT_TD3) {
+  if (a->cfg.kind == GCRL_AGENT_TD3 || a->cfg.kind == GCRL_AGENT_SAC) {
     for (size_t i = 0; i < variants.size() && !rc; ++i) rc = run_step(a, cs, variants[i] | norm_bits(a) | V_ADV | V_PRE, 7, 1);
   } else {
     rc = run_steps_ddpg(a, cs, variants.data(), (int)variants.size(), /*first_pre=*/true);
@@ -137,6 +151,20 @@ int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>&
   return GCRL_OK;
 }
 
+// the waiting forms the next update call records (bits as gcrl_agent_get_meetings: 1 row-split slab launches, 2 merged chain launch, 8 fused
+// optimiser launch): every member has the form on, the device is this process's own, and the WHOLE population launch is resident at once
+int pop_forms_now(const gcrl_pop* p) {
+  const int P = (int)p->m.size();
+  bool on[3];
+  for (int f = 0; f < 3; ++f) on[f] = !meet_device_shared() && !p->no_waits && (P == 1 || (p->want[f] > 0 && p->want[f] <= p->cap[f]));
+  for (gcrl_agent* a : p->m) {
+    on[0] = on[0] && a->bn_rsplit > 1;
+    on[1] = on[1] && (a->sac ? a->rc_merge : a->ddpg_ksplit);
+    on[2] = on[2] && a->opt_fuse;
+  }
+  return (on[0] ? 1 : 0) | (on[1] ? 2 : 0) | (on[2] ? 8 : 0);
+}
+
 }  // namespace
 
 std::atomic<int> gcrl::g_pop_recorders{0};
@@ -146,9 +174,11 @@ PopRec*& gcrl::pop_rec() {
   return r;
 }
 
-extern "C" {
+namespace {
 
-gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) {
+// same_forms: the caller accepts "bitwise a standalone agent RUNNING THE SAME FORMS" (gcrl_pop_create_forms) — the only guarantee a SAC
+// population can give; gcrl_pop_create promises bit for bit a standalone agent whatever its forms, and keeps refusing SAC
+gcrl_pop* pop_create(const gcrl_agent_config* cfgs, int32_t members, bool same_forms) {
   auto bad = [](const char* field, const char* why) -> gcrl_pop* {
     fail(GCRL_ERR_ARG, "gcrl_pop_create: %s: %s", field, why);
     return nullptr;
@@ -158,16 +188,28 @@ gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) {
   if (members < 1 || members > kMaxPopMembers) return bad("members", "a population has 1..16 members");
   for (int i = 0; i < members; ++i) {
     const gcrl_agent_config& c = cfgs[i];
-    if (c.kind != GCRL_AGENT_DDPG && c.kind != GCRL_AGENT_TD3) return bad("kind", "populations are DDPG or TD3 (SAC / TQC populations are not implemented)");
+    if (c.kind != GCRL_AGENT_DDPG && c.kind != GCRL_AGENT_TD3 && c.kind != GCRL_AGENT_SAC) return bad("kind", "populations are DDPG, TD3 or SAC (TQC populations are not implemented)");
+    if (c.kind == GCRL_AGENT_SAC && !same_forms)
+      return bad("kind", "a SAC population is bitwise a standalone agent running the same launch forms only (gcrl_pop_forms): create it with gcrl_pop_create_forms");
     if (const char* f = pop_mismatch(cfgs[0], c)) return bad(f, "members must share kind, shapes, batch_size, gradient_step, ac_update_freq, polyak_every, pipeline_steps, use_graph and device");
-    if (c.pipeline_steps != 2) return bad("pipeline_steps", "the population runs the row-chain DDPG step: pipeline_steps = 2");
-    if (c.hidden_dim < 4 || c.hidden_dim % 4 != 0) return bad("hidden_dim", "the row-chain DDPG step needs hidden_dim % 4 == 0");
+    if (c.pipeline_steps != 2) return bad("pipeline_steps", "the population runs the row-chain step: pipeline_steps = 2");
+    if (c.hidden_dim < 4 || c.hidden_dim % 4 != 0) return bad("hidden_dim", "the row-chain step needs hidden_dim % 4 == 0");
     if (c.ac_dim < 1 || c.ac_dim > 16 || c.obs_dim < 1 || c.layer_count < 1 || c.layer_count > 8 || c.batch_size < 1) return bad("shape", "bad obs_dim / ac_dim / layer_count / batch_size");
     if (c.use_graph >= 2) return bad("use_graph", "the population issues its launches itself (use_graph 0 or 1)");
   }
-  const bool td3 = cfgs[0].kind == GCRL_AGENT_TD3;
-  const int C = td3 ? 2 : 1;
+  const bool td3 = cfgs[0].kind == GCRL_AGENT_TD3, sac = cfgs[0].kind == GCRL_AGENT_SAC;
+  const int C = (td3 || sac) ? 2 : 1;
   if (td3 && cfgs[0].num_critics != 2) return bad("num_critics", "a TD3 agent has two critics");
+  if (sac) {
+    // the path cfg 5 runs (agent.hip build: the same rules): BatchNorm slab launches, role-split chain launches with the actor's heads folded in
+    const gcrl_agent_config& c = cfgs[0];
+    if (c.num_critics != 2) return bad("num_critics", "a SAC population runs the twin-critic role-split chain launches: num_critics = 2");
+    if (c.batch_size > 512) return bad("batch_size", "SAC populations run the BatchNorm slab launches: batch_size <= 512");
+    if (c.hidden_dim < 16 || c.hidden_dim % 16 != 0) return bad("hidden_dim", "SAC populations run the BatchNorm slab launches: hidden_dim % 16 == 0");
+    if (!sac_slab_rule(c.batch_size, c.hidden_dim)) return bad("GCRL_NO_BN_SLAB", "SAC populations run the BatchNorm slab launches, which this environment switches off");
+    if (!sac_split_roles_rule(c.num_critics, c.batch_size, row_rg_of(c.kind, c.batch_size))) return bad("GCRL_NO_SPLIT_ROLES", "SAC populations run the role-split chain launches, which this environment switches off");
+    if (sac_heads_fold_env_off()) return bad("GCRL_NO_HEADS_FOLD", "SAC populations run the chain launches with the actor's heads folded in, which this environment switches off");
+  }
   // the row-chain launch (agent.hip build: the same rules, row_rg_of / td3_split_k_rule): its rows per workgroup and LDS
   const gcrl_agent_config& c0 = cfgs[0];
   const int H = c0.hidden_dim, ldx = round_up(c0.obs_dim + c0.ac_dim, 4);
@@ -186,15 +228,41 @@ gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) {
     gcrl_agent* a = gcrl_agent_create(&cfgs[i]);
     if (!a) { gcrl_pop_destroy(p); return nullptr; }
     p->m.push_back(a);
-    if (!a->rowchain) { gcrl_pop_destroy(p); return bad("hidden_dim", "this configuration does not run the row-chain DDPG step"); }
+    if (!a->rowchain) { gcrl_pop_destroy(p); return bad("hidden_dim", "this configuration does not run the row-chain step"); }
     if (td3 && i == 0 && (a->split_k || a->rc_merge_k || a->dw_split_c > 1 || a->dw_split_a > 1)) {
       gcrl_pop_destroy(p);
       return bad("batch_size", "this TD3 configuration runs the role-split critic phase or the split dW form, which have no population form");
     }
   }
+  if (sac) {
+    for (gcrl_agent* a : p->m)
+      if (!(a->split_roles && a->slab_on() && heads_fold_on(a))) {
+        gcrl_pop_destroy(p);
+        return bad("kind", "this SAC configuration does not run the slab launches and the role-split chain launches with folded heads");
+      }
+  }
+  {
+    gcrl_agent* a0 = p->m[0];
+    const long long nblk = (a0->B + 4 * a0->row_rg - 1) / (4 * a0->row_rg);
+    if (sac) {
+      bn_slab_pop_row_split_terms(a0->B, a0->H, a0->A, members, &p->want[0], &p->cap[0]);
+      rowchain_pop_merge_terms(a0->row_rg, a0->row_ldl, a0->A, a0->H, a0->C, a0->B, members, &p->want[1], &p->cap[1]);
+    } else {   // DDPG's k-split critic phase: three roles per row block, one workgroup per CU
+      p->want[1] = (long long)members * 3 * nblk; p->cap[1] = std::max(a0->n_cus, 1);
+    }
+    p->want[2] = (long long)members * a0->of_wgs; p->cap[2] = dw_adam_pop_capacity();
+    p->no_waits = std::getenv("GCRL_POP_NO_WAITS") != nullptr;
+  }
   p->rec.resize(members);
   return p;
 }
+
+}  // namespace
+
+extern "C" {
+
+gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) { return pop_create(cfgs, members, false); }
+gcrl_pop* gcrl_pop_create_forms(const gcrl_agent_config* cfgs, int32_t members) { return pop_create(cfgs, members, true); }
 
 int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out) {
   GCRL_CHECK_ARG(p && out, "gcrl_pop_member: null argument");
@@ -209,6 +277,17 @@ int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone) {
   GCRL_CHECK_ARG(p, "gcrl_pop_launch_counts: null handle");
   if (merged) *merged = p->merged;
   if (alone) *alone = p->alone;
+  return GCRL_OK;
+}
+
+int gcrl_pop_forms(gcrl_pop* p) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_forms: pop: null handle");
+  return pop_forms_now(p);
+}
+
+int gcrl_pop_forms_terms(const gcrl_pop* p, int64_t* want, int64_t* capacity) {
+  GCRL_CHECK_ARG(p && want && capacity, "gcrl_pop_forms_terms: null argument");
+  for (int f = 0; f < 3; ++f) { want[f] = p->want[f]; capacity[f] = p->cap[f]; }
   return GCRL_OK;
 }
 
@@ -229,18 +308,21 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
   gcrl_agent* a0 = p->m[0];
   hipStream_t st = a0->pick(stream);
   // admission of the forms whose workgroups wait for each other: the whole population launch resident at once
-  const long long nblk = (a0->B + 4 * a0->row_rg - 1) / (4 * a0->row_rg);
-  bool ksplit = true, ofuse = true;
-  for (gcrl_agent* a : p->m) { ksplit = ksplit && a->ddpg_ksplit; ofuse = ofuse && a->opt_fuse; }
-  ksplit = ksplit && !meet_device_shared() && (long long)P * 3 * nblk <= std::max(a0->n_cus, 1);
-  ofuse = ofuse && !meet_device_shared() && (P == 1 || (long long)P * a0->of_wgs <= dw_adam_pop_capacity());
-  struct Forms { bool ksplit, ofuse, rowtile; };
+  const int forms = pop_forms_now(p);
+  const bool sac = a0->cfg.kind == GCRL_AGENT_SAC;
+  const bool ksplit = !sac && (forms & 2) != 0, ofuse = (forms & 8) != 0, rsplit = (forms & 1) != 0, merge = sac && (forms & 2) != 0;
+  struct Forms { bool ksplit, ofuse, rowtile, rc_merge; int bn_rsplit; };
   std::vector<Forms> saved(P);
   for (int i = 0; i < P; ++i) {
     gcrl_agent* a = p->m[i];
-    saved[i] = Forms{a->ddpg_ksplit, a->opt_fuse, a->rowtile};
+    saved[i] = Forms{a->ddpg_ksplit, a->opt_fuse, a->rowtile, a->rc_merge, a->bn_rsplit};
   }
-  auto restore = [&]() { for (int i = 0; i < P; ++i) { p->m[i]->ddpg_ksplit = saved[i].ksplit; p->m[i]->opt_fuse = saved[i].ofuse; p->m[i]->rowtile = saved[i].rowtile; } };
+  auto restore = [&]() {
+    for (int i = 0; i < P; ++i) {
+      gcrl_agent* a = p->m[i];
+      a->ddpg_ksplit = saved[i].ksplit; a->opt_fuse = saved[i].ofuse; a->rowtile = saved[i].rowtile; a->rc_merge = saved[i].rc_merge; a->bn_rsplit = saved[i].bn_rsplit;
+    }
+  };
   const int chunk = std::min(kMaxStepsPerCall, a0->Mmax);
   for (int done = 0; done < n; done += chunk) {
     const int m = std::min(chunk, n - done);
@@ -256,6 +338,7 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
     for (int i = 0; i < P && !rc; ++i) {
       gcrl_agent* a = p->m[i];
       a->ddpg_ksplit = ksplit; a->opt_fuse = ofuse; a->rowtile = false;
+      if (sac) { a->rc_merge = merge; if (!rsplit) a->bn_rsplit = 1; }
       rc = pop_record_steps(a, a0->cap_stream, plans[i], &p->rec[i]);
     }
     restore();
@@ -281,6 +364,8 @@ int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_norma
   GCRL_CHECK_ARG(p, "gcrl_pop_observe_act: pop: null handle");
   const int P = (int)p->m.size();
   gcrl_agent* a0 = p->m[0];
+  // (a BatchNorm actor has no row-chain network to build the launch's table from: its members act through gcrl_agent_observe_act)
+  GCRL_CHECK_ARG(!a0->sac, "gcrl_pop_observe_act: kind: a SAC population has no merged acting launch (call gcrl_agent_observe_act on each member)");
   const int D = obs_dim, G = goal_dim, A = a0->A, S = a0->S;
   GCRL_CHECK_ARG(n >= 1 && n <= a0->B, "gcrl_pop_observe_act: n: %d rows per member (1..batch_size = %d)", n, a0->B);
   GCRL_CHECK_ARG(D >= 1 && G >= 0 && D + G == S, "gcrl_pop_observe_act: obs_dim %d + goal_dim %d != state_dim %d", D, G, S);

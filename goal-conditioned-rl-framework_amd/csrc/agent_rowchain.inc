@@ -115,7 +115,11 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
       hfold.eps_next = a->hf_eps_next; hfold.eps_cur = a->hf_eps_cur;
       hfold.logp_next = a->logp_next;
       hfold.pi = a->pi_buf; hfold.logp = a->logp; hfold.save_eps = a->epsbuf; hfold.save_std = a->stdbuf; hfold.head = a->headA;
-      if (what & 1) hfold.run = BnRunning{{a->bn_bstat, a->hf_nf == 2 ? a->bn_bstat + (long long)an.L * 2 * a->H : nullptr}, a->hf_nf, a->bn_rmean, a->bn_rvar, an.L, a->H, a->B};
+      if (what & 1) {   // (field by field into the zeroed record: a temporary's padding would reach the population's content-keyed table cache)
+        BnRunning& r = hfold.run;
+        r.bstat[0] = a->bn_bstat; r.bstat[1] = a->hf_nf == 2 ? a->bn_bstat + (long long)an.L * 2 * a->H : nullptr;
+        r.n = a->hf_nf; r.rmean = a->bn_rmean; r.rvar = a->bn_rvar; r.layers = an.L; r.H = a->H; r.B = a->B;
+      }
     }
     // actor steps: pi(s) by the critic phase's online roles (rowchain.h cur_in_k; GCRL_HEADS_CUR_IN_P=1: by the actor phase's critic roles)
     static const bool cur_in_p = std::getenv("GCRL_HEADS_CUR_IN_P") != nullptr;

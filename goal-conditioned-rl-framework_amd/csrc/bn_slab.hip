@@ -21,7 +21,9 @@
 
 #include "gemm_mfma.h"
 #include "meet.h"
+#include "pop.h"
 #include "sac_select.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #ifdef GCRL_SLAB_STAMPS
@@ -303,88 +305,20 @@ struct FwdArgs {
 
 template <bool VEC, int NT, int WV>
 __global__ __launch_bounds__(64 * WV) void bn_linear_fwd_slab_kernel(FwdArgs g) {
-  __shared__ float red[WV][16];
-  __shared__ unsigned int s_flag;
-  __shared__ __attribute__((aligned(16))) float stage[WV][16 * NT * kCK];   // wave-private images of the A operand
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-  const int prob = NT == 1 ? (int)blockIdx.z : (int)blockIdx.y, rgrp = NT == 1 ? (int)blockIdx.y : 0;
-  const FwdProb me = g.p[prob];
-  const int B = g.B, H = g.H;
-  constexpr int kRowsWg = 16 * NT * WV;
-  const int col0 = blockIdx.x * 16, col = col0 + li, row0 = rgrp * kRowsWg + wave * 16 * NT;
-  const int nl = min(kRowsWg, B - rgrp * kRowsWg);              // rows of this workgroup (>= 1: launcher)
-  const long long sl = (g.slot && me.x_slot) ? (long long)*g.slot : 0;
-  v4f acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = (v4f){0.f, 0.f, 0.f, 0.f};
-  // epilogue operands first: their latency hides behind the GEMM
-  const float bias = col < H ? g.bias[col] : 0.f, gm = col < H ? g.gamma[col] : 0.f, bt = col < H ? g.beta[col] : 0.f;
-  const int xslot = prob * (H / 16) + (int)blockIdx.x;
-  unsigned long long seq = 0;
-  if (NT == 1 && g.RS > 1 && g.x.df) seq = slab_seq_load(g.x, xslot);   // (its round trip hides behind the GEMM)
-  SLAB_STAMP(0);
-  slab_gemm<VEC, true, NT, SlabStages<NT, WV>::value>(acc, stage[wave], me.X + sl * me.x_slot, g.ldx, g.W, g.K, g.K, B, H, row0, col0, lane);
-  SLAB_STAMP(1);
-  // acc[t][r] = z[row0 + 16 t + 4 lg + r][col] - bias
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      acc[t][r] += bias;
-      if (row0 + 16 * t + 4 * lg + r < B) s += acc[t][r];
-    }
-  asm volatile("" ::"v"(seq));                                      // the launch count has arrived in every wave before the barriers below
-  float mean = col_sum<WV>(s, red, wave, li, lg) / (float)nl;      // of this workgroup's rows
-  float q = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (row0 + 16 * t + 4 * lg + r < B) { const float d = acc[t][r] - mean; q += d * d; }
-  float m2 = col_sum<WV>(q, red, wave, li, lg);
-  SLAB_STAMP(2);
-  if (NT == 1 && g.RS > 1) {
-    // merge of the row groups' (n_j, mean_j, M2_j) in index order: mean = sum n_j mean_j / B, M2 = sum (M2_j + n_j (mean_j - mean)^2)
-    float pm[8], pq[8];
-    const bool ok = g.x.df ? slab_exchange_df(g.x, xslot, g.RS, rgrp, seq, mean, m2, wave, li, lg, pm, pq)
-                           : slab_exchange(g.x, xslot, g.RS, rgrp, mean, m2, wave, li, lg, pm, pq, &s_flag);
-    float sm = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) if (j < g.RS) sm += pm[j] * (float)min(kRowsWg, B - j * kRowsWg);
-    mean = sm / (float)B;
-    m2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < g.RS) { const float dm = pm[j] - mean; m2 += pq[j] + dm * dm * (float)min(kRowsWg, B - j * kRowsWg); }
-    if (!ok) mean = __builtin_nanf("");                        // a timed-out exchange must not pass for a result
-  }
-  SLAB_STAMP(3);
-  const float var = m2 / (float)B;                              // biased: what normalises the batch
-  const float invstd = 1.0f / sqrtf(var + kEps);
-  if (col < H) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = row0 + 16 * t + 4 * lg + r;
-        if (row >= B) continue;
-        const float xh = (acc[t][r] - mean) * invstd;
-        const float y = xh * gm + bt;
-        const long long idx = (long long)row * H + col;
-        me.h[idx] = y > 0.f ? y : 0.f;
-        if (me.xhat) me.xhat[idx] = xh;
-      }
-    if (rgrp == 0 && wave == 0 && lg == 0) {
-      if (me.invstd) me.invstd[col] = invstd;
-      me.bstat[col] = mean;
-      me.bstat[H + col] = var;
-    }
-  }
-#ifdef GCRL_SLAB_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  SLAB_STAMP(4);
-#endif
+#define GCRL_SLAB_FWD_PROB (NT == 1 ? (int)blockIdx.z : (int)blockIdx.y)
+#include "bn_slab_fwd_body.inc"
+#undef GCRL_SLAB_FWD_PROB
+}
+
+// population form (agent_pop.inc, pop.h): the member's own FwdArgs from the device table, the same body text.  The member index rides in
+// blockIdx.z; the row-split form already uses z for its input, so there z = member * n_in + input.
+template <bool VEC, int NT, int WV>
+__global__ __launch_bounds__(64 * WV) void bn_linear_fwd_slab_pop_kernel(const FwdArgs* __restrict__ tab, int n_in) {
+  const int member = NT == 1 ? (int)blockIdx.z / n_in : (int)blockIdx.z;
+  const FwdArgs& g = tab[member];
+#define GCRL_SLAB_FWD_PROB (NT == 1 ? (int)blockIdx.z - member * n_in : (int)blockIdx.y)
+#include "bn_slab_fwd_body.inc"
+#undef GCRL_SLAB_FWD_PROB
 }
 
 struct BwdArgs {
@@ -535,6 +469,26 @@ __global__ __launch_bounds__(64 * WV) void bn_linear_bwd_slab_fold_kernel(BwdFol
   bn_linear_bwd_slab_body<1, WV, true>(f.g, &f.tg);
 }
 
+// population forms: member blockIdx.z (the single-agent grids use x and y) on its own arguments from the device table
+template <int NT, int WV>
+__global__ __launch_bounds__(64 * WV) void bn_linear_bwd_slab_pop_kernel(const BwdArgs* __restrict__ tab) {
+  bn_linear_bwd_slab_body<NT, WV, false>(tab[blockIdx.z], nullptr);
+}
+template <int WV>
+__global__ __launch_bounds__(64 * WV) void bn_linear_bwd_slab_fold_pop_kernel(const BwdFoldArgs* __restrict__ tab) {
+  const BwdFoldArgs& f = tab[blockIdx.z];
+  if ((int)blockIdx.x == f.g.H / 16) {   // the selection + log-alpha workgroup (its row groups > 0: nothing to do)
+    if (blockIdx.y != 0 || !f.rider) return;
+    __shared__ float scratch[16];
+    // (inlined as in the single-agent kernel: as an out-of-line call the block cost every thread 8 bytes of scratch)
+    [[clang::always_inline]] actor_select_body(f.sel, scratch);
+    __syncthreads();
+    [[clang::always_inline]] alpha_body(f.al, scratch);
+    return;
+  }
+  bn_linear_bwd_slab_body<1, WV, true>(f.g, &f.tg);
+}
+
 bool aligned16(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
 
 }  // namespace
@@ -598,6 +552,7 @@ bool bn_slab_bwd_can_fold(int B, int H, int A) {
 int launch_bn_linear_fwd_slab(hipStream_t st, const BnSlabFwd& f) {
   GCRL_CHECK_ARG(bn_slab_ok(f.B, f.H) && (f.n == 1 || f.n == 2) && f.K >= 1, "bn_linear_fwd_slab: B=%d H=%d K=%d n=%d", f.B, f.H, f.K, f.n);
   FwdArgs g;
+  std::memset(&g, 0, sizeof(g));   // (padding too: a population's device tables are cached by content, pop.h)
   for (int i = 0; i < 2; ++i) {
     const BnSlabFwdProb& p = f.p[i < f.n ? i : 0];
     g.p[i] = FwdProb{p.X, p.x_slot, p.h, p.xhat, p.invstd, p.bstat};
@@ -608,6 +563,11 @@ int launch_bn_linear_fwd_slab(hipStream_t st, const BnSlabFwd& f) {
   for (int i = 0; i < f.n; ++i) vec = vec && aligned16(f.p[i].X) && f.p[i].x_slot % 4 == 0;
   g.RS = row_split(f.rsplit, f.B, f.xchg, f.bar, fwd_split_kernel(vec), (long long)(f.H / 16) * f.n);
   g.x = Xchg{f.xchg, f.bar, f.status, split_df(), 2 * (f.H / 16)};
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    const int form = g.RS > 1 ? (split_waves() == 4 ? 1 : 2) : 0;
+    const dim3 grid = g.RS > 1 ? dim3(f.H / 16, g.RS, f.n) : dim3(f.H / 16, f.n);
+    return pop_record(r, POP_BN_FWD, (vec ? 1 : 0) | (form << 1) | (f.n << 4), grid, 0, &g, sizeof(g), [fc = f](hipStream_t s) { return launch_bn_linear_fwd_slab(s, fc); });
+  }
 #ifdef GCRL_SLAB_STAMPS
   static unsigned long long* stamps_dev = nullptr;
   static long long launches = 0;
@@ -649,6 +609,7 @@ int launch_bn_linear_fwd_slab(hipStream_t st, const BnSlabFwd& f) {
 int launch_bn_linear_bwd_slab(hipStream_t st, const BnSlabBwd& b) {
   GCRL_CHECK_ARG(bn_slab_ok(b.B, b.H) && (b.nup == 1 || b.nup == 2), "bn_linear_bwd_slab: B=%d H=%d nup=%d", b.B, b.H, b.nup);
   BwdArgs g;
+  std::memset(&g, 0, sizeof(g));   // (padding too: a population's device tables are cached by content, pop.h)
   g.nup = b.nup;
   for (int u = 0; u < 2; ++u) {
     const int v = u < b.nup ? u : 0;
@@ -671,19 +632,95 @@ int launch_bn_linear_bwd_slab(hipStream_t st, const BnSlabBwd& b) {
                    "bn_linear_bwd_slab: the folded sampling backward needs the row-split form and the two heads as consumers (RS=%d, nup=%d, A=%d)", g.RS, b.nup, t.A);
     BwdFoldArgs f;
     std::memset(&f, 0, sizeof(f));
-    f.g = g; f.tg = t;
-    if (b.fold_sel) { f.sel = *b.fold_sel; f.al = *b.fold_al; f.rider = 1; }
+    // (byte copies of records their builders zeroed first, padding included: a population's device tables are cached by content)
+    std::memcpy(&f.g, &g, sizeof(g)); std::memcpy(&f.tg, &t, sizeof(t));
+    if (b.fold_sel) { std::memcpy(&f.sel, b.fold_sel, sizeof(f.sel)); std::memcpy(&f.al, b.fold_al, sizeof(f.al)); f.rider = 1; }
     const dim3 grid(b.H / 16 + 1, g.RS);
+    if (PopRec* r = pop_recording())   // (the closure owns copies of the records the caller's pointers name)
+      return pop_record(r, POP_BN_BWD_FOLD, split_waves(), grid, 0, &f, sizeof(f), [bc = b, fc = f](hipStream_t s) {
+        BnSlabBwd q = bc;
+        q.fold_tg = &fc.tg; q.fold_sel = fc.rider ? &fc.sel : nullptr; q.fold_al = fc.rider ? &fc.al : nullptr;
+        return launch_bn_linear_bwd_slab(s, q);
+      });
     if (split_waves() == 4) hipLaunchKernelGGL((bn_linear_bwd_slab_fold_kernel<4>), grid, dim3(64 * 4), 0, st, f);
     else hipLaunchKernelGGL((bn_linear_bwd_slab_fold_kernel<8>), grid, dim3(64 * 8), 0, st, f);
     GCRL_HIP(hipGetLastError());
     return GCRL_OK;
   }
+  if (PopRec* r = pop_recording())
+    return pop_record(r, POP_BN_BWD, g.RS > 1 ? (split_waves() == 4 ? 1 : 2) : 0, g.RS > 1 ? dim3(b.H / 16, g.RS) : dim3(b.H / 16), 0, &g, sizeof(g),
+                      [bc = b](hipStream_t s) { return launch_bn_linear_bwd_slab(s, bc); });
   if (g.RS > 1 && split_waves() == 4) hipLaunchKernelGGL((bn_linear_bwd_slab_kernel<1, 4>), dim3(b.H / 16, g.RS), dim3(64 * 4), 0, st, g);
   else if (g.RS > 1) hipLaunchKernelGGL((bn_linear_bwd_slab_kernel<1, 8>), dim3(b.H / 16, g.RS), dim3(64 * 8), 0, st, g);
   else hipLaunchKernelGGL((bn_linear_bwd_slab_kernel<4, kWaves>), dim3(b.H / 16), dim3(64 * kWaves), 0, st, g);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
+}
+
+// ---- population launches (pop.h): `tab` holds `members` argument structs as the launchers above recorded them; `sub` names the instance
+int launch_bn_fwd_slab_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid) {
+  const bool vec = (sub & 1) != 0;
+  const int form = (sub >> 1) & 3, n_in = sub >> 4;
+  GCRL_CHECK_ARG(tab && members >= 1 && form <= 2 && (n_in == 1 || n_in == 2) && (form == 0 ? (grid.y == (unsigned)n_in && grid.z == 1) : grid.z == (unsigned)n_in) &&
+                     (long long)members * n_in <= 65535, "bn_linear_fwd_slab (population): bad launch");
+  const FwdArgs* t = static_cast<const FwdArgs*>(tab);
+  if (form == 0) {
+    const dim3 g(grid.x, grid.y, (unsigned)members);
+    if (vec) hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<true, 4, kWaves>), g, dim3(64 * kWaves), 0, st, t, n_in);
+    else hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<false, 4, kWaves>), g, dim3(64 * kWaves), 0, st, t, n_in);
+  } else {
+    const dim3 g(grid.x, grid.y, (unsigned)(members * n_in));
+    if (form == 1) {
+      if (vec) hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<true, 1, 4>), g, dim3(64 * 4), 0, st, t, n_in);
+      else hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<false, 1, 4>), g, dim3(64 * 4), 0, st, t, n_in);
+    } else {
+      if (vec) hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<true, 1, 8>), g, dim3(64 * 8), 0, st, t, n_in);
+      else hipLaunchKernelGGL((bn_linear_fwd_slab_pop_kernel<false, 1, 8>), g, dim3(64 * 8), 0, st, t, n_in);
+    }
+  }
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_bn_bwd_slab_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid) {
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && sub >= 0 && sub <= 2 && grid.z == 1 && (sub != 0 || grid.y == 1), "bn_linear_bwd_slab (population): bad launch");
+  const BwdArgs* t = static_cast<const BwdArgs*>(tab);
+  const dim3 g(grid.x, grid.y, (unsigned)members);
+  if (sub == 1) hipLaunchKernelGGL((bn_linear_bwd_slab_pop_kernel<1, 4>), g, dim3(64 * 4), 0, st, t);
+  else if (sub == 2) hipLaunchKernelGGL((bn_linear_bwd_slab_pop_kernel<1, 8>), g, dim3(64 * 8), 0, st, t);
+  else hipLaunchKernelGGL((bn_linear_bwd_slab_pop_kernel<4, kWaves>), g, dim3(64 * kWaves), 0, st, t);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_bn_bwd_slab_fold_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid) {
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && (sub == 4 || sub == 8) && grid.z == 1, "bn_linear_bwd_slab fold (population): bad launch");
+  const BwdFoldArgs* t = static_cast<const BwdFoldArgs*>(tab);
+  const dim3 g(grid.x, grid.y, (unsigned)members);
+  if (sub == 4) hipLaunchKernelGGL((bn_linear_bwd_slab_fold_pop_kernel<4>), g, dim3(64 * 4), 0, st, t);
+  else hipLaunchKernelGGL((bn_linear_bwd_slab_fold_pop_kernel<8>), g, dim3(64 * 8), 0, st, t);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+// The row groups of a slab wait for each other: the population's row-split launches are admitted when `members` times the largest member grid
+// (the two-input forward launch; the backward launch, plain and folded) is resident at once by the POPULATION kernels' own occupancy.
+// As one comparison: *want = members x slabs x row groups x 2 inputs (the forward launch) against *cap = the least of the forward kernels'
+// capacities and TWICE the backward kernels' (their launches are half the size).  want 0: the shape has no row split.
+void bn_slab_pop_row_split_terms(int B, int H, int A, int members, long long* want, long long* cap) {
+  const int wv = split_waves(), rows = 16 * wv;
+  *want = 0; *cap = 0;
+  if (!bn_slab_ok(B, H) || B <= rows || members < 1) return;
+  const long long rs = (B + rows - 1) / rows, slabs = H / 16;
+  const void* kf[2] = {wv == 4 ? (const void*)bn_linear_fwd_slab_pop_kernel<true, 1, 4> : (const void*)bn_linear_fwd_slab_pop_kernel<true, 1, 8>,
+                       wv == 4 ? (const void*)bn_linear_fwd_slab_pop_kernel<false, 1, 4> : (const void*)bn_linear_fwd_slab_pop_kernel<false, 1, 8>};
+  const void* kb = wv == 4 ? (const void*)bn_linear_bwd_slab_pop_kernel<1, 4> : (const void*)bn_linear_bwd_slab_pop_kernel<1, 8>;
+  const void* kd = wv == 4 ? (const void*)bn_linear_bwd_slab_fold_pop_kernel<4> : (const void*)bn_linear_bwd_slab_fold_pop_kernel<8>;
+  *want = members * slabs * rs * 2;
+  long long c = std::min(meet_capacity(kf[0], 64 * wv, 0), meet_capacity(kf[1], 64 * wv, 0));
+  c = std::min(c, 2 * meet_capacity(kb, 64 * wv, 0));
+  if (A >= 1 && A <= 16) c = std::min(c, 2 * meet_capacity(kd, 64 * wv, 0));
+  *cap = c;
 }
 
 }  // namespace gcrl

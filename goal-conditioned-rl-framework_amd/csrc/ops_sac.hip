@@ -9,10 +9,12 @@
 #include "gemm_mfma.h"   // v4f
 #include "sac_heads.h"
 #include "sac_select.h"
+#include "pop.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 namespace gcrl {
 namespace {
@@ -528,6 +530,17 @@ __global__ __launch_bounds__(256) void tanh_gauss_bwd_select_kernel(TanhGaussBwd
   alpha_body(al, scratch);
 }
 
+// population form (pop.h): member blockIdx.y on its own three argument records from the device table
+struct TgBwdSelectPop { TanhGaussBwdArgs a; ActorSelArgs s; AlphaArgs al; };
+__global__ __launch_bounds__(256) void tanh_gauss_bwd_select_pop_kernel(const TgBwdSelectPop* __restrict__ tab) {
+  const TgBwdSelectPop& e = tab[blockIdx.y];
+  if (blockIdx.x + 1 < gridDim.x) { tanh_gauss_bwd_body(e.a); return; }
+  __shared__ float scratch[16];
+  actor_select_body(e.s, scratch);
+  __syncthreads();
+  alpha_body(e.al, scratch);
+}
+
 // lane i holds element i of the row (+inf beyond `width`): 21 compare-exchange rounds with the
 // partner lane i^j, direction from bit k of the lane id -> ascending order across the wave.
 __global__ __launch_bounds__(256) void sort_trunc_kernel(const float* in, long long rows, int width, int drop,
@@ -818,7 +831,22 @@ int launch_tanh_gauss_bwd(hipStream_t st, const TanhGaussBwdArgs& a) {
 
 int launch_tanh_gauss_bwd_select(hipStream_t st, const TanhGaussBwdArgs& a, const ActorSelArgs& s, const AlphaArgs& al) {
   GCRL_CHECK_ARG(s.C >= 1 && s.C <= kMaxCritics && s.drop >= 0 && s.drop < s.C, "actor_select: bad C=%d drop=%d", s.C, s.drop);
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    TgBwdSelectPop e;
+    std::memset(&e, 0, sizeof(e));
+    // (byte copies of records their builder zeroed first, padding included: the device tables are cached by content)
+    std::memcpy(&e.a, &a, sizeof(a)); std::memcpy(&e.s, &s, sizeof(s)); std::memcpy(&e.al, &al, sizeof(al));
+    return pop_record(r, POP_TG_BWD_SELECT, 0, dim3((a.B * a.A + 255) / 256 + 1), 0, &e, sizeof(e),
+                      [e](hipStream_t q) { return launch_tanh_gauss_bwd_select(q, e.a, e.s, e.al); });
+  }
   hipLaunchKernelGGL(tanh_gauss_bwd_select_kernel, dim3((a.B * a.A + 255) / 256 + 1), dim3(256), 0, st, a, s, al);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_tanh_gauss_bwd_select_pop(hipStream_t st, const void* tab, int members, dim3 grid) {
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && grid.x >= 2 && grid.y == 1 && grid.z == 1, "tanh_gauss_bwd_select (population): bad launch");
+  hipLaunchKernelGGL(tanh_gauss_bwd_select_pop_kernel, dim3(grid.x, (unsigned)members), dim3(256), 0, st, static_cast<const TgBwdSelectPop*>(tab));
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }

@@ -1,4 +1,4 @@
-// pop.h — launch recording of a DDPG or TD3 population (agent.hip gcrl_pop_*).
+// pop.h — launch recording of a DDPG, TD3 or SAC population (agent.hip gcrl_pop_*).
 //
 // A population step issues each member's ordinary launch sequence with a recorder installed on the calling thread: the
 // launchers below then record the launch (its arguments, grid, LDS and a closure that would issue it alone) instead of
@@ -27,6 +27,13 @@ enum PopKind {
   POP_GEMM_BATCH = 4,  // one form's launch of launch_gemm_batch (sub = the form, 1..5; only form 1, gemm_batch_kernel<1, 1, 4>, merges)
   POP_ADAM = 5,        // adam_kernel
   POP_ADAM_PAIR = 6,   // adam_pair_kernel (args: AdamPairArgs)
+  // SAC (bn_slab.hip, rowchain.hip, ops_sac.hip): `sub` names the template instance, so only identical forms merge
+  POP_BN_FWD = 7,          // bn_linear_fwd_slab_kernel<VEC, NT, WV> (sub = VEC | form << 1 | inputs << 4; form 0: <4, 8>, 1: <1, 4>, 2: <1, 8>)
+  POP_BN_BWD = 8,          // bn_linear_bwd_slab_kernel<NT, WV> (sub = form, as above)
+  POP_BN_BWD_FOLD = 9,     // bn_linear_bwd_slab_fold_kernel<WV> (sub = WV)
+  POP_RC_SPLIT = 10,       // rowchain_split_kernel<RG> (sub = RG | part << 4 | phase << 8; args: RowChainArgs, phase, part)
+  POP_RC_SPLIT_HEADS = 11, // rowchain_split_heads_kernel<RG> (sub as above; args: RowChainArgs, phase, part, HeadsFold)
+  POP_TG_BWD_SELECT = 12,  // tanh_gauss_bwd_select_kernel (args: TanhGaussBwdArgs, ActorSelArgs, AlphaArgs)
 };
 // whether a recorded launch of this kind and sub has a population form
 inline bool pop_mergeable(int kind, int sub) { return kind != POP_ALONE && (kind != POP_GEMM_BATCH || sub == 1); }
@@ -102,6 +109,17 @@ int launch_begin_step_pop(hipStream_t st, const void* tab, int members);
 int launch_gemm_batch_pop(hipStream_t st, const void* tab, int members, int shape, dim3 grid);
 int launch_adam_pop(hipStream_t st, const void* tab, int members, dim3 grid);
 int launch_adam_pair_pop(hipStream_t st, const void* tab, int members, dim3 grid);
+// SAC: member = blockIdx.z (slab launches; the row-split forward, whose grid uses all three dimensions, takes member * inputs + input there) or
+// blockIdx.y (chain launches, sampling backward)
+int launch_bn_fwd_slab_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
+int launch_bn_bwd_slab_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
+int launch_bn_bwd_slab_fold_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
+int launch_rowchain_split_pop(hipStream_t st, const void* tab, int members, int sub, bool heads, dim3 grid, size_t lds);
+int launch_tanh_gauss_bwd_select_pop(hipStream_t st, const void* tab, int members, dim3 grid);
+// admission of the waiting forms for a population of `members`: the two sides of the comparison (cap 0: shared device or the query failed)
+// (*want: `members` times a member's workgroups of the form; *cap: what is resident at once; want 0: the shape does not have the form)
+void bn_slab_pop_row_split_terms(int B, int H, int A, int members, long long* want, long long* cap);
+void rowchain_pop_merge_terms(int rg, int ldl, int A, int H, int C, int B, int members, long long* want, long long* cap);
 long long dw_adam_pop_capacity();   // workgroups of the population form resident at once (0: shared device / query failed)
 
 }  // namespace gcrl

@@ -493,6 +493,21 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_split_heads_kernel(RowCh
   rowchain_split_body<RG, true>(a, phase, part, (int)blockIdx.x, hf);
 }
 
+// population forms (pop.h): member blockIdx.y runs its own launch — arguments, phase, part and, for the heads form, the HeadsFold record, all
+// from the device table — on the workgroups blockIdx.x of its single-agent launch.  The body reads the records in place (references into the
+// table: uniform loads, no copy); a member's meeting counters, exchange words and status word are its own, so its workgroups meet only each other.
+struct RowSplitPop { RowChainArgs a; int phase, part; HeadsFold hf; };
+template <int RG>
+__global__ __launch_bounds__(kRowThreads) void rowchain_split_pop_kernel(const RowSplitPop* __restrict__ tab) {
+  const RowSplitPop& e = tab[blockIdx.y];
+  rowchain_split_body<RG>(e.a, e.phase, e.part, (int)blockIdx.x);
+}
+template <int RG>
+__global__ __launch_bounds__(kRowThreads) void rowchain_split_heads_pop_kernel(const RowSplitPop* __restrict__ tab) {
+  const RowSplitPop& e = tab[blockIdx.y];
+  rowchain_split_body<RG, true>(e.a, e.phase, e.part, (int)blockIdx.x, e.hf);
+}
+
 // `row_at(i)`: element i of the launch's input rows ([n][ld_obs] flattened); `noise_at(t)`: exploration noise of action element t —
 // functors, so that the inline form reads the kernel-argument segment by plain indexed loads (a POINTER into a by-value argument
 // struct made hipcc copy the whole struct into every thread's scratch: 36 us for this kernel, round 4).  SYS: the float64 actions
@@ -691,6 +706,18 @@ int launch_rowchain_split(hipStream_t st, const RowChainArgs& a, int rg, int pha
   // on a device the process has to itself)
   GCRL_CHECK_ARG(part != 3 || (phase == 0 && a.producers_first && !meet_device_shared()) || rowchain_merge_ok(rg, a.ldl, a.A, a.critic[0].H, a.C, a.B),
                  "rowchain split: %d workgroups of %zu bytes of LDS cannot all be resident (or the device is shared)", roles * nblk, lds);
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    GCRL_CHECK_ARG(!(hf && hf->on) || (a.given_next && a.p_critic_only && part != 2 && a.A <= 16), "rowchain split: the folded heads need the SAC form (given_next, critic-only actor phase)");
+    RowSplitPop e;
+    std::memset(&e, 0, sizeof(e));
+    // (byte copies of records their builders zeroed first, padding included: the device tables are cached by content)
+    std::memcpy(&e.a, &a, sizeof(a)); e.phase = phase; e.part = part;
+    const bool heads = hf && hf->on;
+    if (heads) std::memcpy(&e.hf, hf, sizeof(*hf));
+    const int grid = roles * nblk + ((heads && phase == 0) ? (hf->cur_in_k ? nblk : (hf->run.layers ? 1 : 0)) : 0);
+    return pop_record(r, heads ? POP_RC_SPLIT_HEADS : POP_RC_SPLIT, rg | (part << 4) | (phase << 8), dim3(grid), lds, &e, sizeof(e),
+                      [e, rg, heads](hipStream_t s) { return launch_rowchain_split(s, e.a, rg, e.phase, e.part, heads ? &e.hf : nullptr); });
+  }
   auto go = [&](auto kern) -> int {
     static thread_local size_t raised = 0;
     if (lds > 64 * 1024 && lds > raised) {
@@ -782,6 +809,46 @@ int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int r
   else hipLaunchKernelGGL(rowchain_ddpg_pop_kernel<4>, g, dim3(kRowThreads), lds, st, t);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
+}
+
+int launch_rowchain_split_pop(hipStream_t st, const void* tab, int members, int sub, bool heads, dim3 grid, size_t lds) {
+  const int rg = sub & 15;
+  GCRL_CHECK_ARG(rg == 1 || rg == 2 || rg == 4, "rowchain split (population): rows per block must be 4, 8 or 16");
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && grid.y == 1 && grid.z == 1 && lds <= 160 * 1024, "rowchain split (population): bad launch");
+  const RowSplitPop* t = static_cast<const RowSplitPop*>(tab);
+  const dim3 g(grid.x, (unsigned)members);
+  auto go = [&](auto kern) -> int {
+    static thread_local size_t raised = 0;   // (per kernel: a generic lambda's statics belong to its instantiation)
+    if (lds > 64 * 1024 && lds > raised) {
+      GCRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      raised = lds;
+    }
+    hipLaunchKernelGGL(kern, g, dim3(kRowThreads), lds, st, t);
+    GCRL_HIP(hipGetLastError());
+    return GCRL_OK;
+  };
+  if (heads) {
+    if (rg == 1) return go(rowchain_split_heads_pop_kernel<1>);
+    if (rg == 2) return go(rowchain_split_heads_pop_kernel<2>);
+    return go(rowchain_split_heads_pop_kernel<4>);
+  }
+  if (rg == 1) return go(rowchain_split_pop_kernel<1>);
+  if (rg == 2) return go(rowchain_split_pop_kernel<2>);
+  return go(rowchain_split_pop_kernel<4>);
+}
+
+// part 3 of a population: `members` times the 2C x nblk role workgroups resident at once by the population kernels' occupancy at this LDS size
+void rowchain_pop_merge_terms(int rg, int ldl, int A, int H, int C, int B, int members, long long* want, long long* cap) {
+  const size_t lds = rowchain_lds_bytes(rg, ldl, A, H, C);
+  *want = 0; *cap = 0;
+  if (lds > 160 * 1024 || members < 1) return;
+  const void* k = rg == 1 ? (const void*)rowchain_split_pop_kernel<1> : (rg == 2 ? (const void*)rowchain_split_pop_kernel<2> : (const void*)rowchain_split_pop_kernel<4>);
+  const void* kh = rg == 1 ? (const void*)rowchain_split_heads_pop_kernel<1> : (rg == 2 ? (const void*)rowchain_split_heads_pop_kernel<2> : (const void*)rowchain_split_heads_pop_kernel<4>);
+  if (lds > 64 * 1024 && (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+                          hipFuncSetAttribute(kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)) return;
+  const long long nblk = (B + 4 * rg - 1) / (4 * rg);
+  *want = (long long)members * 2 * C * nblk;
+  *cap = std::min(meet_capacity(k, kRowThreads, lds), meet_capacity(kh, kRowThreads, lds));
 }
 
 int launch_wt_rebuild(hipStream_t st, const RowNet& net, float* Wt) {

@@ -1,9 +1,10 @@
-"""DDPGPopulation / TD3Population — P independent agents of one kind whose update steps share launches (include/gcrl.h gcrl_pop_*).
+"""DDPGPopulation / TD3Population / SACPopulation — P independent agents of one kind whose update steps share launches (include/gcrl.h gcrl_pop_*).
 
 RL results are reported over several seeds and hyper-parameter searches run many trials of one shape; with one agent per
-trial, N agents cost N times one agent.  A population of 1..16 DDPG or TD3 agents of equal shapes issues each stage of a
+trial, N agents cost N times one agent.  A population of 1..16 DDPG, TD3 or SAC agents of equal shapes issues each stage of a
 training step once for all members (csrc/agent_pop.inc), and every member computes bit for bit what a standalone `DDPG` /
-`TD3Agent` with the same config, seed and ring computes.
+`TD3Agent` / `SACAgent` with the same config, seed and ring computes (SAC: a standalone agent running the launch forms `forms()`
+reports).
 
 `.members` are ordinary `DDPG` / `TD3Agent` objects (own `HERBuffer`, the whole single-agent API, including `update` /
 `update_many` on the member alone); `update_many(step0, n)` steps all of them and returns, per member, what the agent's own
@@ -18,22 +19,23 @@ import numpy as np
 
 from .. import _ffi
 from .._ffi import lib
-from .agent import DDPG, KIND, TD3Agent, native_config
+from .agent import DDPG, KIND, SACAgent, TD3Agent, native_config
 from .buffer import MTStream
 
 MAX_MEMBERS = 16
 
 # fields every member must share (the population runs one launch pattern); the others (seed, gamma, tau, grad_clip, learning
-# rates and their schedules, the ring's own settings) may differ
+# rates and their schedules, SAC's alpha_lr and alpha_min_steps, the ring's own settings) may differ
 SHARED = ("hidden_dim", "layer_count", "batch_size", "ac_update_freq")
 
 
 class _PopHandle:
     """Owner of the native population; the members keep it alive."""
 
-    def __init__(self, cfgs):
+    def __init__(self, cfgs, same_forms=False):
         arr = (_ffi.AgentConfig * len(cfgs))(*cfgs)
-        self.h = _ffi.check_ptr(lib.gcrl_pop_create(arr, len(cfgs)), "gcrl_pop_create")
+        create = lib.gcrl_pop_create_forms if same_forms else lib.gcrl_pop_create
+        self.h = _ffi.check_ptr(create(arr, len(cfgs)), "gcrl_pop_create")
 
     def member(self, i: int) -> int:
         out = C.c_void_p()
@@ -49,6 +51,7 @@ class _PopHandle:
 class _Population:
     AGENT = None          # the member class
     NUM_CRITICS = 1
+    SAME_FORMS = False    # the class's guarantee is "a standalone agent running the same forms" (gcrl_pop_create_forms)
 
     def _refuse(self, field: str, why: str):
         raise _ffi.GcrlError(f"{type(self).__name__}: {field}: {why}")
@@ -72,7 +75,7 @@ class _Population:
         kind = KIND[self.AGENT.KIND_NAME]
         cfgs = [native_config(kind, obs_dim, ac_dim, c, int(gradient_step), num_critics=self.NUM_CRITICS, device_index=device_index, seed=s)
                 for c, s in zip(configs, seeds)]
-        self._pop = _PopHandle(cfgs)   # (the engine checks the rest — kind, row-chain shape — before it touches the device)
+        self._pop = _PopHandle(cfgs, self.SAME_FORMS)   # (the engine checks the rest — kind, row-chain shape — before it touches the device)
         pop = self._pop
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
@@ -111,6 +114,8 @@ class _Population:
         out = []
         for i, m in enumerate(self.members):
             m.beta_scheduler(step0 + n - 1)
+            if m._sac:   # (as the agent's own update_many: BatchNorm's forward count, one per actor forward)
+                m.actor.num_batches_tracked += sum(1 + (1 if lens[i * n + j] == 9 else 0) for j in range(n))
             out.append([m._tuple(int(tickets[i * n + j]), int(lens[i * n + j])) for j in range(n)])
         return out
 
@@ -124,6 +129,7 @@ class _Population:
     # population's two calls take 55-63 us per vector step against 53-58 us member by member — the host work per member outweighs one
     # saved launch pair — while TD3 wins from P = 2 (51-63 against 58-65 us) and both win from P = 4 (1.4-1.7 x) to P = 16 (2.1-2.8 x)
     MERGE_ACTING_FROM = 2
+    MERGE_PROCESS_FROM = None   # process_step's own threshold (None: MERGE_ACTING_FROM)
 
     def _staging(self, tag: str, key: tuple, shapes):
         """Persistent host staging of the acting entries (as `_EngineAgent._staging`: fixed addresses, ctypes pointers built once)."""
@@ -205,7 +211,7 @@ class _Population:
         for st, ac, nx in zip(states, actions, next_obs_raws):
             rows_in.append((as_arr(st["observation"]), as_arr(nx["observation"]), as_arr(st["desired_goal"]), as_arr(nx["desired_goal"]),
                             as_arr(nx["achieved_goal"]), as_arr(st["achieved_goal"]) if g_normalize else None, as_arr(ac)))
-        merged = P >= self.MERGE_ACTING_FROM and all(z is not None for z in nzs)
+        merged = P >= (self.MERGE_ACTING_FROM if self.MERGE_PROCESS_FROM is None else self.MERGE_PROCESS_FROM) and all(z is not None for z in nzs)
         if merged:
             o0, _, g0, _, a0, _, c0 = rows_in[0]
             merged = all(r[0].shape == o0.shape and r[2].shape == g0.shape and r[4].shape == a0.shape and r[6].shape == c0.shape for r in rows_in)
@@ -267,12 +273,39 @@ class _Population:
         _ffi.check(lib.gcrl_pop_launch_counts(self._pop.h, C.byref(merged), C.byref(alone)))
         return int(merged.value), int(alone.value)
 
+    def forms(self):
+        """Bits of the launch forms with waits between workgroups the next `update_many` runs, as `agent.meetings()` reports them
+        for one agent: 1 row-split BatchNorm slab launches (SAC), 2 merged chain launch, 8 fused optimiser launch.  A form is on when
+        every member has it on, the device is this process's own and the whole population launch is resident at once
+        (include/gcrl.h gcrl_pop_forms)."""
+        return _ffi.check(lib.gcrl_pop_forms(self._pop.h))
+
+    def forms_terms(self):
+        """{bit: (want, capacity)} for the form bits 1, 2 and 8: `len(self)` times a member's workgroups of the form against the
+        workgroups of the population kernel resident at once, as fixed at creation (include/gcrl.h gcrl_pop_forms_terms)."""
+        want, cap = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        _ffi.check(lib.gcrl_pop_forms_terms(self._pop.h, want, cap))
+        return {bit: (int(want[i]), int(cap[i])) for i, bit in enumerate((1, 2, 8))}
+
 
 class DDPGPopulation(_Population):
     """1..16 `DDPG` agents of equal shapes stepped together."""
     AGENT = DDPG
     NUM_CRITICS = 1
     MERGE_ACTING_FROM = 4
+
+
+class SACPopulation(_Population):
+    """1..16 `SACAgent`s of equal shapes stepped together (batch_size <= 512, hidden_dim % 16 == 0: the slab launches and the
+    role-split chain launches with the actor's heads folded in); update_many returns, per member, `SACAgent.update_many`'s tuples (9
+    entries on actor steps, 6 on critic-only steps).  Every member is bitwise a standalone `SACAgent` running the launch forms
+    `forms()` reports.  `observe_act` calls the members' own one-launch entries in member order (a population form of the BatchNorm
+    actors' acting kernel does not exist); `process_step` is the merged launch."""
+    AGENT = SACAgent
+    NUM_CRITICS = 2
+    SAME_FORMS = True
+    MERGE_ACTING_FROM = MAX_MEMBERS + 1   # observe_act: member by member
+    MERGE_PROCESS_FROM = 2                # process_step: the merged launch (it does not involve the network)
 
 
 class TD3Population(_Population):

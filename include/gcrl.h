@@ -324,16 +324,34 @@ int gcrl_agent_update(gcrl_agent* a, gcrl_her* her, int64_t step,
  * tickets_out[n], tuple_len_out[n] optional. */
 int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
                         int64_t* tickets_out, int32_t* tuple_len_out, void* stream);
-/* DDPG and TD3 populations: `members` (1..16) independent agents of one kind (DDPG or TD3) and equal shapes whose update steps
+/* DDPG, TD3 and SAC populations: `members` (1..16) independent agents of one kind (DDPG, TD3 or SAC) and equal shapes whose update steps
  * share launches.  Members must share kind, obs_dim, ac_dim, hidden_dim, layer_count, batch_size, num_critics, gradient_step, ac_update_freq,
  * polyak_every, pipeline_steps (2: the row-chain step), use_graph (0 or 1) and device; they may differ in seed, gamma, tau,
  * grad_clip and the learning-rate schedules.  A refusal names the field and happens before any device work.  TD3 populations run
  * batch_size < 2048 below the role-split critic phase (at most 255 row blocks, i.e. batch_size <= 1020); other TD3 configurations
- * are refused naming batch_size.
+ * are refused naming batch_size.  SAC populations run the path of the twin-critic SAC step at batch_size <= 512: the BatchNorm slab
+ * launches, the role-split chain launches and the actor's heads folded into them (hidden_dim % 16 == 0, ac_dim <= 16, num_critics 2,
+ * pipeline_steps 2); anything else is refused naming batch_size, hidden_dim, num_critics, pipeline_steps, or the environment switch
+ * (GCRL_NO_BN_SLAB, GCRL_NO_SPLIT_ROLES, GCRL_NO_HEADS_FOLD) that takes the path away.  TQC populations are not implemented (kind).
+ * alpha_lr and alpha_min_steps may differ between SAC members like the other rates.
+ * gcrl_pop_create promises each member bit for bit a standalone agent, whatever launch forms that agent runs; a SAC population can only
+ * promise that against an agent running the same forms (gcrl_pop_forms below), so gcrl_pop_create refuses SAC naming kind and
+ * gcrl_pop_create_forms — the same entry for a caller that accepts the qualified guarantee — admits DDPG, TD3 and SAC.
  * gcrl_pop_member: member i as a full agent handle, owned by the population (every gcrl_agent_* entry works on it).
  * gcrl_pop_update_n: gcrl_agent_update_n(member i, rings[i], step0, n, ...) for every member, the members' launches of each
  * stage issued together; each member computes bit for bit what its own gcrl_agent_update_n computes.  Batches are drawn
  * from the rings in member order.  tickets_out / tuple_len_out: [members][n], optional.
+ * gcrl_pop_forms: which launch forms with waits between workgroups the population's next update call runs, as bits of
+ * gcrl_agent_get_meetings' result (1: row-split BatchNorm slab launches, 2: merged chain launch, 8: fused optimiser launch) — a form is
+ * on when every member has it on, the device is this process's own and `members` times a member's workgroups of it are resident at
+ * once.  Forms 2 and 8 compute the same bits as the launches that replace them.  Form 1 (SAC) sums a column's batch statistics in
+ * another order than the one-workgroup slab launch: a SAC member is bit for bit a standalone agent RUNNING THE SAME FORMS (a
+ * standalone agent's switches: GCRL_NO_BN_RSPLIT=1, GCRL_NO_RC_MERGE=1, GCRL_NO_OPT_FUSE=1).  Negative: an error code.
+ * gcrl_pop_forms_terms: the two sides of the residency comparison, fixed at creation, for the forms of bits 1, 2 and 8 in this order:
+ * want[3] = `members` times a member's workgroups of the form (0: the shape does not have it), capacity[3] = workgroups of the population
+ * kernel resident at once (0: the device was shared or the occupancy query failed).  A population of two or more members runs form f when
+ * 0 < want[f] <= capacity[f], every member has the form on and the device is not shared; a one-member population runs its member's forms.
+ * GCRL_POP_NO_WAITS=1 in the environment at creation: the population admits no such form (A/B switch).
  * gcrl_pop_launch_counts: how the recorded launch positions of every gcrl_pop_update_n since creation were issued — `merged`: as one
  * launch of the kernel's population form for all members; `alone`: member by member (a launch without a population form, members
  * whose launches differ, or a one-member population).  Either pointer may be null.
@@ -349,7 +367,8 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * epsilon-random branch (src/agent.py:1348) involves no network and stays with the caller — and its out_host rows are left
  * untouched.  n <= batch_size.  Runs after every member's last update call and on its current weights.  Up to 32 rows per
  * member travel through a pinned, mapped block (one launch, no copy, no stream synchronisation); more rows take staged copies
- * around the same launch.
+ * around the same launch.  A SAC population is refused (GCRL_ERR_ARG, naming kind): a BatchNorm actor acts through its own one-launch
+ * gcrl_agent_observe_act, member by member.
  * gcrl_pop_process_step: gcrl_her_process_step_g (src/env.py:163-201, :167-175, :222-223) of every member's ring rings[i] with its
  * own normalisers: one launch stages all members' transitions, then each ring's episode flushes follow in member order (their
  * relabelling draws come from the rings' generators in that order).  The row arrays are those of gcrl_her_process_step_g, each
@@ -361,11 +380,14 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
 typedef struct gcrl_pop gcrl_pop;
 typedef struct gcrl_normalizer gcrl_normalizer;   /* (the device RunningNormalizer, declared below) */
 gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members);
+gcrl_pop* gcrl_pop_create_forms(const gcrl_agent_config* cfgs, int32_t members);
 int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out);
 int32_t gcrl_pop_size(const gcrl_pop* p);
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,
                       int32_t* tuple_len_out, void* stream);
 int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone);
+int gcrl_pop_forms(gcrl_pop* p);
+int gcrl_pop_forms_terms(const gcrl_pop* p, int64_t* want, int64_t* capacity);
 int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
                          const float* dg_host, int32_t goal_dim, int32_t n, const double* noise_host, const int32_t* modes, double* out_host,
                          void* stream);

@@ -1,7 +1,8 @@
-"""Aggregate update throughput of a DDPG or TD3 population (src/population.py) against the same P agents stepped one after another
+"""Aggregate update throughput of a DDPG, TD3 or SAC population (src/population.py) against the same P agents stepped one after another
 in the same process.  One JSON line per (shape, P, form):
 
-    python tools/population_bench.py [--kind DDPG|TD3] [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
+    python tools/population_bench.py [--kind DDPG|TD3|SAC] [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
+    python tools/population_bench.py --kind SAC --shapes cfg5,sac_h64 --update-rounds 5     (both sides alive, timed in alternation: median, min-max)
 
 Each agent trains from its own HER ring of synthetic episodes, `gradient_step` (40) steps per update call as the trainer does
 (src/env.py:384-385).  Timing: hipEvents on the stream the updates run on, around `calls` calls after `warmup` untimed ones and
@@ -35,12 +36,15 @@ from oracle.agent_oracle import make_config  # noqa: E402
 SHAPES = {   # bench.py WORKLOADS: ddpg_reach_b256 (cfg 1) and the ddpg_pickplace_b256 headline
     "cfg1": dict(S=10, A=3, H=64, L=3, B=256),
     "headline": dict(S=23, A=4, H=256, L=3, B=256),
+    "cfg5": dict(S=28, A=4, H=256, L=3, B=512),      # sac_slide_b512
+    "sac_h64": dict(S=10, A=3, H=64, L=3, B=256),
 }
 GSTEP = 40
 
 
 KINDS = {"DDPG": (gcrl_amd.DDPGPopulation, gcrl_amd.DDPG, {}),
-         "TD3": (gcrl_amd.TD3Population, gcrl_amd.TD3Agent, dict(ac_update_freq=2, policy_noise=0.2, noise_clamp=0.5))}
+         "TD3": (gcrl_amd.TD3Population, gcrl_amd.TD3Agent, dict(ac_update_freq=2, policy_noise=0.2, noise_clamp=0.5)),
+         "SAC": (gcrl_amd.SACPopulation, gcrl_amd.SACAgent, dict(ac_update_freq=2))}
 
 
 def _cfgs(sh, P, kind="DDPG"):
@@ -105,6 +109,40 @@ def run(shape, P, calls, warmup, kind="DDPG"):
     return out
 
 
+def run_rounds(shape, P, calls, warmup, kind, rounds):
+    """population and sequential agents alive together, timed in alternation for `rounds` rounds: median and min-max of the aggregate rate"""
+    sh = SHAPES[shape]
+    cfgs = _cfgs(sh, P, kind)
+    seeds = list(range(7, 7 + P))
+    pop_cls, agent_cls = KINDS[kind][:2]
+    pop = pop_cls(sh["S"], sh["A"], cfgs, 2, GSTEP, rng="engine", seeds=seeds)
+    solo = [agent_cls(sh["S"], sh["A"], c, None, nenvs=2, gradient_step=GSTEP, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
+    for i in range(P):
+        _fill(pop.members[i], sh, i)
+        _fill(solo[i], sh, i)
+
+    def seq(s0):
+        for a in solo:
+            a.update_many(s0, GSTEP)
+    steps = calls * GSTEP
+    rates = dict(population=[], sequential=[])
+    for r in range(rounds):
+        for form, fn in (("population", lambda s0: pop.update_many(s0, GSTEP)), ("sequential", seq)):
+            dev_s, _ = _time(fn, calls, warmup if r == 0 else 1)
+            rates[form].append(P * steps / dev_s)
+    merged, alone = pop.launch_counts()
+    out = []
+    for form, v in rates.items():
+        v = sorted(v)
+        out.append(dict(bench="update_rounds", kind=kind, shape=shape, members=P, form=form, rounds=rounds, steps_per_member_per_round=steps,
+                        agg_steps_per_s_median=round(v[len(v) // 2], 1), agg_steps_per_s_min=round(v[0], 1), agg_steps_per_s_max=round(v[-1], 1),
+                        forms=pop.forms() if form == "population" else solo[0].meetings(), **{k: sh[k] for k in ("S", "A", "H", "L", "B")}))
+    out[0].update(launch_positions_merged=merged, launch_positions_alone=alone,
+                  speedup_median=round(out[0]["agg_steps_per_s_median"] / out[1]["agg_steps_per_s_median"], 3),
+                  ranges_overlap=not (out[0]["agg_steps_per_s_min"] > out[1]["agg_steps_per_s_max"] or out[0]["agg_steps_per_s_max"] < out[1]["agg_steps_per_s_min"]))
+    return out
+
+
 def run_acting(shape, P, rounds, steps, kind="DDPG", nenvs=8):
     from gcrl_amd.src.utils import DeviceRunningNormalizer
     sh = SHAPES[shape]
@@ -165,6 +203,7 @@ def run_acting(shape, P, rounds, steps, kind="DDPG", nenvs=8):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", default="DDPG", choices=sorted(KINDS))
+    ap.add_argument("--update-rounds", type=int, default=1, help="> 1: population and sequential agents timed in alternation this many times")
     ap.add_argument("--shapes", default="cfg1,headline")
     ap.add_argument("--members", default="1,2,4,8")
     ap.add_argument("--calls", type=int, default=50)
@@ -190,7 +229,7 @@ def main():
     f = open(a.out, "a") if a.out else None
     for shape in a.shapes.split(","):
         for P in [int(x) for x in a.members.split(",")]:
-            for r in run(shape, P, a.calls, a.warmup, a.kind):
+            for r in (run_rounds(shape, P, a.calls, a.warmup, a.kind, a.update_rounds) if a.update_rounds > 1 else run(shape, P, a.calls, a.warmup, a.kind)):
                 line = json.dumps(r)
                 print(line, flush=True)
                 if f:
