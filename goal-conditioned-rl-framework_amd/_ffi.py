@@ -131,6 +131,7 @@ PROTOTYPES = {
     "gcrl_pop_forms": (C.c_int, [_vp]),
     "gcrl_pop_forms_terms": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_observe_act": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "gcrl_pop_observe_act_bn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "gcrl_pop_process_step": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         C.c_int32, C.c_int32, _vp, _vp]),
     "gcrl_pop_acting_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),

@@ -40,4 +40,21 @@ struct ActBnInline {
 };
 int launch_act_bn_inline(hipStream_t st, const ActBnInline& a);
 
+// Population forms (gcrl_pop_observe_act_bn): grid (ceil(n / kActBnRows), members), member = blockIdx.y.  Member m's workgroups read
+// tab[m] (its own parameter vector, running statistics, normaliser views and the shared shapes; rows / eps / out64 there are ignored) and
+// its slices of rows / eps / out: [members][stride_n][S] floats, [members][stride_n][A] doubles (the eps as the ABI carries it; used as
+// (float)), [members][stride_n][A] doubles.  What changes from call to call travels in the kernel arguments, so the table stays the
+// same call after call.  Fast form (flags != null): rows, eps, out and flags are the device addresses of a pinned, mapped, coherent
+// block the host fills before the launch and polls after it (flags[m * workgroups + workgroup] = seq once that workgroup's rows are
+// out); rows and eps are read by system-scope loads.  Staged form (flags == null): device buffers, plain loads and stores.
+struct ActBnPop {
+  const ActBnArgs* tab;
+  const float* rows; const double* eps; double* out;
+  unsigned long long* flags;
+  unsigned long long seq;
+  int with_eps, stride_n;
+};
+// `shape`: a host copy of one member's arguments, for the shape checks and the LDS size (the members share S, H, L, A, n, ldl)
+int launch_act_bn_pop(hipStream_t st, const ActBnPop& c, const ActBnArgs& shape, int members);
+
 }  // namespace gcrl

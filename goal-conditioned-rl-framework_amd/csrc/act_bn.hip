@@ -217,6 +217,39 @@ __global__ __launch_bounds__(kActBnThreads) void act_bn_inline_kernel(ActBnInlin
   if (threadIdx.x == 0) __hip_atomic_store(a.flag_host + blockIdx.x, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Population forms (act_bn.h ActBnPop): member blockIdx.y on its own arguments tab[blockIdx.y] and its own slices of the rows, the eps
+// and the actions — the same body, so each member's rows go through its own arithmetic in its own order.  `a` is a COPY of the table
+// entry made before anything else: uniform addresses and nothing stored yet, so the whole struct arrives by scalar loads and stays in
+// scalar registers (a reference into the table left the loads behind the first barrier as vector loads: 174 vector registers against 129).
+// Fast form: the block is pinned, mapped, coherent host memory — rows and eps by system-scope loads (a later call cannot read an
+// earlier call's rows), actions as system-scope stores, then one flag per (member, workgroup).
+__global__ __launch_bounds__(kActBnThreads) void act_bn_pop_kernel(ActBnPop c) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const unsigned int m = blockIdx.y;
+  const ActBnArgs a = c.tab[m];
+  const float* rows = c.rows + (size_t)m * c.stride_n * a.S;
+  const double* eps = c.eps + (size_t)m * c.stride_n * a.A;
+  double* out = c.out + (size_t)m * c.stride_n * a.A;
+  act_bn_body<true>(a, [&](long long i) { return __hip_atomic_load(rows + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); },
+                    [&](long long t) { return (float)__hip_atomic_load(eps + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); },
+                    c.with_eps != 0, out, lds);
+  // this workgroup's rows are out as write-through stores: drain them, then raise its flag (system scope: the host polls it)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(c.flags + (size_t)m * gridDim.x + blockIdx.x, c.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Staged form: device buffers the host entry copies into and out of — plain loads and stores, no flags.
+__global__ __launch_bounds__(kActBnThreads) void act_bn_pop_staged_kernel(ActBnPop c) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const unsigned int m = blockIdx.y;
+  const ActBnArgs a = c.tab[m];
+  const float* rows = c.rows + (size_t)m * c.stride_n * a.S;
+  const double* eps = c.eps + (size_t)m * c.stride_n * a.A;
+  double* out = c.out + (size_t)m * c.stride_n * a.A;
+  act_bn_body<false>(a, [&](long long i) { return rows[i]; }, [&](long long t) { return (float)eps[t]; }, c.with_eps != 0, out, lds);
+}
+
 int check_shape(const ActBnArgs& a, size_t* lds) {
   GCRL_CHECK_ARG(a.P && a.rmean && a.rvar && a.n >= 1 && a.S >= 1 && a.H >= 1 && a.L >= 1 && a.A >= 1 && a.A <= 16 && a.D >= 0 && a.D <= a.S,
                  "act_bn: unsupported shape (S=%d, H=%d, L=%d, A=%d, n=%d)", a.S, a.H, a.L, a.A, a.n);
@@ -254,6 +287,25 @@ int launch_act_bn_inline(hipStream_t st, const ActBnInline& a) {
     raised = lds;
   }
   hipLaunchKernelGGL(act_bn_inline_kernel, dim3((b.n + R - 1) / R), dim3(kActBnThreads), lds, st, a);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_act_bn_pop(hipStream_t st, const ActBnPop& c, const ActBnArgs& shape, int members) {
+  size_t lds = 0;
+  if (int rc = check_shape(shape, &lds)) return rc;   // (the members share their shapes: one check)
+  GCRL_CHECK_ARG(c.tab && c.rows && c.out && (c.eps || !c.with_eps) && members >= 1 && members <= 65535 && shape.n <= c.stride_n,
+                 "act_bn (population): bad launch (%d members, %d rows of %d per member)", members, shape.n, c.stride_n);
+  const bool fast = c.flags != nullptr;
+  static thread_local size_t raised[2] = {0, 0};
+  if (lds > 64 * 1024 && lds > raised[fast]) {
+    GCRL_HIP(hipFuncSetAttribute(fast ? (const void*)act_bn_pop_kernel : (const void*)act_bn_pop_staged_kernel,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised[fast] = lds;
+  }
+  const dim3 grid((shape.n + R - 1) / R, (unsigned)members);
+  if (fast) hipLaunchKernelGGL(act_bn_pop_kernel, grid, dim3(kActBnThreads), lds, st, c);
+  else hipLaunchKernelGGL(act_bn_pop_staged_kernel, grid, dim3(kActBnThreads), lds, st, c);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }

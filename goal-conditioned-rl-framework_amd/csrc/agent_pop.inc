@@ -7,6 +7,8 @@
 // dw_adam_pop_kernel, begin_step_pop_kernel, gemm_batch_pop_kernel<1, 1, 4>, adam_pop_kernel, adam_pair_pop_kernel; SAC: the slab launches' bn_linear_*_slab_*pop_kernel, rowchain_split_[heads_]pop_kernel, tanh_gauss_bwd_select_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
 // arithmetic in the same order as the member's own launch, so each member computes bit for bit what it computes alone.
 // Launches without a population form are issued member by member at their position.
+// The acting side (one launch per vector-env step for all members): gcrl_pop_observe_act (row-chain actors), gcrl_pop_observe_act_bn
+// (SAC's BatchNorm actors), gcrl_pop_process_step.
 //
 // Admission (meet.h): a launch whose workgroups wait for each other is issued in its waiting form only when the WHOLE population
 // launch is resident at once; otherwise the members record the no-wait form of that stage (same bits — except SAC's slab launches, whose
@@ -24,8 +26,8 @@ struct gcrl_pop {
   long long want[3] = {0, 0, 0}, cap[3] = {0, 0, 0};
   bool no_waits = false;               // GCRL_POP_NO_WAITS=1 at creation: the population admits no waiting form (A/B knob)
   int64_t merged = 0, alone = 0;       // recorded positions issued as one population launch / member by member (gcrl_pop_launch_counts)
-  // acting side (gcrl_pop_observe_act, gcrl_pop_process_step; counts: gcrl_pop_acting_counts)
-  PopTabCache act_tabs;                // device tables of the members' RowActArgs
+  // acting side (gcrl_pop_observe_act, gcrl_pop_observe_act_bn, gcrl_pop_process_step; counts: gcrl_pop_acting_counts)
+  PopTabCache act_tabs;                // device tables of the members' RowActArgs (SAC: ActBnArgs)
   // fast form: one pinned, mapped block [noise | actions | flags | rows] for kPopActRows rows per member (rowchain.h RowActPop)
   char *act_blk_host = nullptr, *act_blk_dev = nullptr;
   unsigned long long act_seq = 0;
@@ -487,6 +489,127 @@ int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_norma
   }
   for (int i = 0; i < P; ++i)
     if ((live >> i) & 1u) std::memcpy(out_host + i * oA, h_out + (size_t)i * stride_n * A, sizeof(double) * oA);
+  return GCRL_OK;
+}
+
+// The BatchNorm actors' (SAC) population acting: the population forms of act_bn.hip on the members' live parameter vectors and running
+// statistics — no [in][out] copies are involved.  The pinned block, the staging pair, the sequence number and the table cache are the
+// ones of gcrl_pop_observe_act (a population is of one kind: the two entries never share a block in use).
+int gcrl_pop_observe_act_bn(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
+                            const float* dg_host, int32_t goal_dim, int32_t n, const double* eps_host, double* out_host, void* stream) {
+  // every refusal before any device work
+  GCRL_CHECK_ARG(obs_host, "gcrl_pop_observe_act_bn: obs_host: null array");
+  GCRL_CHECK_ARG(dg_host, "gcrl_pop_observe_act_bn: dg_host: null array");
+  GCRL_CHECK_ARG(out_host, "gcrl_pop_observe_act_bn: out_host: null array");
+  GCRL_CHECK_ARG(p, "gcrl_pop_observe_act_bn: pop: null handle");
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  GCRL_CHECK_ARG(a0->sac, "gcrl_pop_observe_act_bn: kind: the members are not BatchNorm actors (call gcrl_pop_observe_act)");
+  const int D = obs_dim, G = goal_dim, A = a0->A, S = a0->S;
+  GCRL_CHECK_ARG(n >= 1 && n <= a0->B, "gcrl_pop_observe_act_bn: n: %d rows per member (1..batch_size = %d)", n, a0->B);
+  GCRL_CHECK_ARG(D >= 1 && G >= 0 && D + G == S, "gcrl_pop_observe_act_bn: obs_dim %d + goal_dim %d != state_dim %d", D, G, S);
+  for (int i = 0; i < P; ++i) {
+    gcrl_normalizer* zo = nz_obs ? nz_obs[i] : nullptr;
+    gcrl_normalizer* zg = nz_dg ? nz_dg[i] : nullptr;
+    // the kernel indexes mean[j] / var[j] for j < obs_dim (goal_dim): a normaliser of another size is an argument error, never an out-of-bounds access
+    GCRL_CHECK_ARG(!zo || gcrl_normalizer_size(zo) == D, "gcrl_pop_observe_act_bn: nz_obs: member %d's observation normaliser has size %d for obs_dim %d", i, gcrl_normalizer_size(zo), D);
+    GCRL_CHECK_ARG(!zg || gcrl_normalizer_size(zg) == G, "gcrl_pop_observe_act_bn: nz_dg: member %d's goal normaliser has size %d for goal_dim %d", i, gcrl_normalizer_size(zg), G);
+  }
+  p->act_calls++;
+  const size_t oD = (size_t)n * D, oG = (size_t)n * G, oA = (size_t)n * A;
+  if (P == 1)   // nothing to merge: the member's own entry
+    return gcrl_agent_observe_act(a0, nz_obs ? nz_obs[0] : nullptr, nz_dg ? nz_dg[0] : nullptr, obs_host, D, dg_host, G, n, eps_host, 2, out_host, stream);
+  hipStream_t st = a0->pick(stream);
+  // after every member's last update call (DESIGN.md 4c: the event that closes a handle's update work)
+  p->act_ordered.resize(P, 0);
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    if (a->calls != p->act_ordered[i]) {
+      GCRL_HIP(hipStreamWaitEvent(st, a->call_ev[(a->calls - 1) % kEventRing], 0));
+      p->act_ordered[i] = a->calls;
+    }
+  }
+  // the members' table: what belongs to the member, filled as gcrl_agent_observe_act fills its own arguments
+  ActBnArgs tab[kMaxPopMembers];
+  const int warm = std::getenv("GCRL_ACT_BN_WARM") ? 1 : 0;
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    ActBnArgs& ba = tab[i];
+    std::memset(&ba, 0, sizeof(ba));
+    ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
+    ba.S = S; ba.H = a->H; ba.L = a->L; ba.A = A; ba.n = n; ba.D = D;
+    ba.ldl = (std::max(S, a->H) + 3) / 4 * 4;
+    ba.warm = warm;
+    gcrl::normalizer_view(nz_obs ? nz_obs[i] : nullptr, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
+    gcrl::normalizer_view(nz_dg ? nz_dg[i] : nullptr, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
+  }
+  void* tab_dev = nullptr;
+  if (p->act_tabs.get(tab, sizeof(ActBnArgs) * P, st, &tab_dev)) return fail(GCRL_ERR_HIP, "gcrl_pop_observe_act_bn: argument table upload failed");
+  const bool fast = n <= kPopActRows;
+  const int stride_n = fast ? kPopActRows : a0->B;
+  const PopActLayout lay(P, stride_n, S, A);
+  char* host = nullptr;
+  if (fast) {
+    if (!p->act_blk_host) {
+      GCRL_HIP(hipHostMalloc((void**)&p->act_blk_host, lay.bytes, hipHostMallocMapped | hipHostMallocCoherent));
+      std::memset(p->act_blk_host, 0, lay.bytes);
+      GCRL_HIP(hipHostGetDevicePointer((void**)&p->act_blk_dev, p->act_blk_host, 0));
+    }
+    host = p->act_blk_host;
+  } else {
+    if (!p->act_st_host) {
+      GCRL_HIP(hipHostMalloc((void**)&p->act_st_host, lay.bytes, hipHostMallocDefault));
+      GCRL_HIP(hipMalloc((void**)&p->act_st_dev, lay.bytes));
+    }
+    host = p->act_st_host;
+  }
+  char* dev = fast ? p->act_blk_dev : p->act_st_dev;
+  float* h_rows = reinterpret_cast<float*>(host + lay.rows);
+  double* h_eps = reinterpret_cast<double*>(host + lay.noise);
+  for (int i = 0; i < P; ++i) {
+    float* r = h_rows + (size_t)i * stride_n * S;
+    for (int e = 0; e < n; ++e) {
+      std::memcpy(r + (size_t)e * S, obs_host + i * oD + (size_t)e * D, sizeof(float) * D);
+      std::memcpy(r + (size_t)e * S + D, dg_host + i * oG + (size_t)e * G, sizeof(float) * G);
+    }
+    if (eps_host) std::memcpy(h_eps + (size_t)i * stride_n * A, eps_host + i * oA, sizeof(double) * oA);
+  }
+  ActBnPop c;
+  c.tab = static_cast<const ActBnArgs*>(tab_dev);
+  c.rows = reinterpret_cast<const float*>(dev + lay.rows);
+  c.eps = reinterpret_cast<const double*>(dev + lay.noise);
+  c.out = reinterpret_cast<double*>(dev + lay.out);
+  c.flags = fast ? reinterpret_cast<unsigned long long*>(dev + lay.flags) : nullptr;
+  c.seq = ++p->act_seq;
+  c.with_eps = eps_host ? 1 : 0; c.stride_n = stride_n;
+  const double* h_out = reinterpret_cast<const double*>(host + lay.out);
+  if (fast) {
+    // ONE launch and nothing else: the host's stores to the block precede the launch, the kernel reads them there, and the host
+    // waits for the members' flags (a bounded spin; then the ordinary synchronisation says what happened)
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    TRY(launch_act_bn_pop(st, c, tab[0], P));
+    p->act_launches++;
+    const int nwg = (n + kActBnRows - 1) / kActBnRows;
+    volatile unsigned long long* flags = reinterpret_cast<volatile unsigned long long*>(host + lay.flags);
+    bool seen = false;
+    for (long spin = 0; spin < 4000000 && !seen; ++spin) {
+      seen = true;
+      for (int w = 0; w < P * nwg && seen; ++w) seen = flags[w] == c.seq;
+      if (!seen) __builtin_ia32_pause();
+    }
+    if (!seen) GCRL_HIP(hipStreamSynchronize(st));
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  } else {
+    // the exception: copies up, the same one launch, copy down, one synchronisation (eps, actions and flags lie before the rows)
+    if (eps_host) GCRL_HIP(hipMemcpyAsync(dev + lay.noise, host + lay.noise, lay.out - lay.noise, hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipMemcpyAsync(dev + lay.rows, host + lay.rows, lay.bytes - lay.rows, hipMemcpyHostToDevice, st));
+    TRY(launch_act_bn_pop(st, c, tab[0], P));
+    p->act_launches++;
+    p->act_staged++;
+    GCRL_HIP(hipMemcpyAsync(host + lay.out, dev + lay.out, lay.flags - lay.out, hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < P; ++i) std::memcpy(out_host + i * oA, h_out + (size_t)i * stride_n * A, sizeof(double) * oA);
   return GCRL_OK;
 }
 

@@ -9,7 +9,8 @@ reports).
 `.members` are ordinary `DDPG` / `TD3Agent` objects (own `HERBuffer`, the whole single-agent API, including `update` /
 `update_many` on the member alone); `update_many(step0, n)` steps all of them and returns, per member, what the agent's own
 `update_many` returns.  `observe_act` / `process_step` are the members' fused acting entries for all members at once: one launch
-per call (gcrl_pop_observe_act, gcrl_pop_process_step), the host generators consumed in member order.
+per call (gcrl_pop_observe_act — SAC's BatchNorm actors: gcrl_pop_observe_act_bn —, gcrl_pop_process_step), the host generators
+consumed in member order.
 """
 from __future__ import annotations
 
@@ -146,6 +147,11 @@ class _Population:
         if len(seq) != len(self.members):
             self._refuse("members", f"{name} has {len(seq)} entries for {len(self.members)} members")
 
+    def _native_observe_act(self, nzo, nzg, ptr, D, G, n, with_noise):
+        """The native call of `observe_act` on the filled staging arrays (the row-chain actors' entry; SACPopulation overrides)."""
+        return lib.gcrl_pop_observe_act(self._pop.h, nzo, nzg, ptr["obs"], D, ptr["dg"], G, n, ptr["noise"] if with_noise else None,
+                                        ptr["modes"], ptr["out"], _ffi.stream_handle())
+
     def observe_act(self, observations, desired_goals, eval_action: bool = False, obs_normalize: bool = True, g_normalize: bool = False):
         """`members[i].observe_act(observations[i], desired_goals[i], ...)` for every member as ONE native call and one launch;
         returns the members' float64 action arrays [n, A] in member order.  The host generators (`random`, `np.random`, the
@@ -187,8 +193,7 @@ class _Population:
             if noise is not None:
                 np.copyto(b_noise[i], noise)
                 with_noise = True
-        _ffi.check(lib.gcrl_pop_observe_act(self._pop.h, nzo, nzg, ptr["obs"], D, ptr["dg"], G, n, ptr["noise"] if with_noise else None,
-                                            ptr["modes"], ptr["out"], _ffi.stream_handle()))
+        _ffi.check(self._native_observe_act(nzo, nzg, ptr, D, G, n, with_noise))
         b_out = buf["out"]
         for i in range(P):
             if out[i] is None:
@@ -299,13 +304,22 @@ class SACPopulation(_Population):
     """1..16 `SACAgent`s of equal shapes stepped together (batch_size <= 512, hidden_dim % 16 == 0: the slab launches and the
     role-split chain launches with the actor's heads folded in); update_many returns, per member, `SACAgent.update_many`'s tuples (9
     entries on actor steps, 6 on critic-only steps).  Every member is bitwise a standalone `SACAgent` running the launch forms
-    `forms()` reports.  `observe_act` calls the members' own one-launch entries in member order (a population form of the BatchNorm
-    actors' acting kernel does not exist); `process_step` is the merged launch."""
+    `forms()` reports.  `process_step` is the merged launch.  `observe_act` has one too (gcrl_pop_observe_act_bn: the population form
+    of the BatchNorm actors' acting kernel, every member bit for bit its own `observe_act`), taken from `MERGE_ACTING_FROM` members
+    on; below that the members' own one-launch entries run in member order."""
     AGENT = SACAgent
     NUM_CRITICS = 2
     SAME_FORMS = True
-    MERGE_ACTING_FROM = MAX_MEMBERS + 1   # observe_act: member by member
+    # observe_act: the threshold is set from a measurement (DESIGN.md 4f: the smallest P from which the merged form's whole range lies
+    # below the member-by-member range at both shapes), never guessed.  The merged launch has not been timed yet, so the default stays
+    # member by member; `pop.MERGE_ACTING_FROM = 2` takes the merged launch.
+    MERGE_ACTING_FROM = MAX_MEMBERS + 1
     MERGE_PROCESS_FROM = 2                # process_step: the merged launch (it does not involve the network)
+
+    def _native_observe_act(self, nzo, nzg, ptr, D, G, n, with_noise):
+        # (SAC's _act_noise: mode 2 for every member, and eps for every member or — eval — for none)
+        return lib.gcrl_pop_observe_act_bn(self._pop.h, nzo, nzg, ptr["obs"], D, ptr["dg"], G, n, ptr["noise"] if with_noise else None,
+                                           ptr["out"], _ffi.stream_handle())
 
 
 class TD3Population(_Population):

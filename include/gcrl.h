@@ -367,8 +367,15 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * epsilon-random branch (src/agent.py:1348) involves no network and stays with the caller — and its out_host rows are left
  * untouched.  n <= batch_size.  Runs after every member's last update call and on its current weights.  Up to 32 rows per
  * member travel through a pinned, mapped block (one launch, no copy, no stream synchronisation); more rows take staged copies
- * around the same launch.  A SAC population is refused (GCRL_ERR_ARG, naming kind): a BatchNorm actor acts through its own one-launch
- * gcrl_agent_observe_act, member by member.
+ * around the same launch.  A SAC population is refused (GCRL_ERR_ARG, naming kind): a BatchNorm actor has no row-chain network;
+ * its population acts through gcrl_pop_observe_act_bn.
+ * gcrl_pop_observe_act_bn: the same for a population of BatchNorm actors (SAC): one launch of the population form of the members'
+ * one-launch acting kernel, on each member's live parameter vector and running statistics.  eps_host [members][n][A] float64 is the
+ * rsample eps of every member, or NULL: every member's deterministic action tanh(mean); there are no modes and no skipped members.
+ * The other arrays, the row limits, the ordering after the members' update calls, the two forms (pinned block up to 32 rows per
+ * member, staged copies beyond) and the counts are gcrl_pop_observe_act's.  Refused (GCRL_ERR_ARG, before any device work, out_host
+ * untouched): a null handle or array, a population whose members are not BatchNorm actors (naming kind), n outside 1..batch_size,
+ * obs_dim + goal_dim != state_dim, a member's normaliser of another size (naming the member).
  * gcrl_pop_process_step: gcrl_her_process_step_g (src/env.py:163-201, :167-175, :222-223) of every member's ring rings[i] with its
  * own normalisers: one launch stages all members' transitions, then each ring's episode flushes follow in member order (their
  * relabelling draws come from the rings' generators in that order).  The row arrays are those of gcrl_her_process_step_g, each
@@ -391,6 +398,8 @@ int gcrl_pop_forms_terms(const gcrl_pop* p, int64_t* want, int64_t* capacity);
 int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
                          const float* dg_host, int32_t goal_dim, int32_t n, const double* noise_host, const int32_t* modes, double* out_host,
                          void* stream);
+int gcrl_pop_observe_act_bn(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,
+                            const float* dg_host, int32_t goal_dim, int32_t n, const double* eps_host, double* out_host, void* stream);
 int gcrl_pop_process_step(gcrl_pop* p, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int32_t update_stats, gcrl_normalizer* const* nz_dg,
                           int32_t update_goal_stats, const float* obs_host, const float* next_obs_host, int32_t obs_dim, const float* dg_host,
                           const float* next_dg_host, const float* ag_host, const float* next_ag_host, const float* actions_host,

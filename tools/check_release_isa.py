@@ -99,7 +99,7 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 # kernels the scratch lint reports by name whatever their figure (and misses when they are gone): the population acting launches
 # ... and the BatchNorm actor's acting launches (act_bn.hip)
 SCRATCH_NAMED = {"rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"],
-                 "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel"]}
+                 "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel", "act_bn_pop_kernel", "act_bn_pop_staged_kernel"]}
 
 
 def scratch_report(asm_text, unit):
@@ -132,7 +132,7 @@ def scratch_report(asm_text, unit):
 # Release lint of a kernel whose publication AND arrival are system-scope stores to host-visible memory (rowchain_act_pop_kernel: the
 # float64 actions, then one 8-byte flag per workgroup that the host polls): the flag is the listing's last such store, and an
 # `s_waitcnt vmcnt(0)` must stand between the store before it and the flag.
-FLAG_UNITS = {"rowchain.hip": ["rowchain_act_pop_kernel"], "act_bn.hip": ["act_bn_inline_kernel"]}
+FLAG_UNITS = {"rowchain.hip": ["rowchain_act_pop_kernel"], "act_bn.hip": ["act_bn_inline_kernel", "act_bn_pop_kernel"]}
 STORE_SYS = re.compile(r"^\s*global_store_dwordx2\s.*\bsc0 sc1\b")
 
 

@@ -16,7 +16,14 @@ times the ACTING side instead: per vector-env step of 8 envs, `pop.observe_act` 
 members' own `observe_act` + `process_step` made one after another ("members"), device normalisers, an episode of every env ending
 every 50th step so that the flush launches are in.  Both sides run in one process, alternating round by round; wall-clock time per
 round (the calls wait for their results or are host-bound), a device synchronise inside each round's bracket.  One JSON line per
-configuration: median and min-max of the rounds, in microseconds per vector step, per side."""
+configuration: median and min-max of the rounds, in microseconds per vector step, per side.
+
+    python tools/population_bench.py --acting --kind SAC [--shapes sac_h64,cfg5] [--members 2,4,8,16] [--rounds 5] [--steps 3000]
+
+times a SAC population's `observe_act` alone (process_step is the same merged launch on both sides): the merged launch
+(gcrl_pop_observe_act_bn) against the same population with `MERGE_ACTING_FROM` forced above P (the members' own one-launch entries in
+member order), each side of each round in a fresh child process, the sides alternating; wall clock per call, the Python wrapper
+included.  One JSON line per (shape, P)."""
 import argparse
 import json
 import os
@@ -200,8 +207,75 @@ def run_acting(shape, P, rounds, steps, kind="DDPG", nenvs=8):
     return [r]
 
 
+def acting_sac_child(shape, members, steps, merged, nenvs=8):
+    """One side of one round, in this (fresh) process: wall clock per `pop.observe_act` call (sampled actions, device normalisers,
+    the Python wrapper included; the call returns the actions, so it has waited for them) of a SAC population with the merged launch
+    on (`MERGE_ACTING_FROM = 2`) or forced off (above P: the members' own one-launch entries in member order)."""
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    sh = SHAPES[shape]
+    G = 3
+    D = sh["S"] - G
+    out = []
+    for P in members:
+        pop = gcrl_amd.SACPopulation(sh["S"], sh["A"], _cfgs(sh, P, "SAC"), nenvs, GSTEP, rng="engine", seeds=list(range(7, 7 + P)))
+        pop.MERGE_ACTING_FROM = 2 if merged else P + 1
+        gen = np.random.default_rng(5)
+        for m in pop.members:
+            m.buffer.obs_normalizer = DeviceRunningNormalizer(D)
+            m.buffer.dg_normalizer = DeviceRunningNormalizer(G)
+            m.buffer.obs_normalizer.update(gen.standard_normal((64, D)).astype(np.float32))
+        K = 64    # distinct vector steps, cycled (rows differ from call to call)
+        f = lambda *shp: gen.standard_normal(shp).astype(np.float32)
+        data = [([f(nenvs, D) for _ in range(P)], [f(nenvs, G) for _ in range(P)]) for _ in range(K)]
+        torch.manual_seed(3)
+        for k in range(300):
+            pop.observe_act(*data[k % K])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(steps):
+            pop.observe_act(*data[k % K])
+        torch.cuda.synchronize()
+        us = (time.perf_counter() - t0) / steps * 1e6
+        counts = pop.acting_counts()
+        assert bool(counts[1]) == bool(merged), counts
+        out.append(dict(shape=shape, members=P, merged=bool(merged), us_per_call=round(us, 2), acting_counts=counts))
+        del pop
+    return out
+
+
+def run_acting_sac(shapes, members, rounds, steps, write):
+    """`rounds` alternating rounds of fresh child processes per shape — merged launch, then member by member — each child timing every
+    population size; one JSON line per (shape, P): median and min-max of the rounds per side, and whether the merged side's whole
+    range lies below the other's (the rule that sets SACPopulation.MERGE_ACTING_FROM)."""
+    import subprocess
+    for shape in shapes:
+        t = {(side, P): [] for side in ("merged", "members") for P in members}
+        for rnd in range(rounds):
+            for side in ("merged", "members"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--kind", "SAC", "--acting", "--child", side, "--shapes", shape,
+                       "--members", ",".join(str(P) for P in members), "--steps", str(steps)]
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+                assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+                for line in r.stdout.splitlines():
+                    if line.startswith("CHILD "):
+                        c = json.loads(line[6:])
+                        t[(side, c["members"])].append(c["us_per_call"])
+                print(f"# {shape} round {rnd} {side}: " + ", ".join(f"P={P}: {t[(side, P)][-1]}" for P in members), flush=True)
+        sh = SHAPES[shape]
+        for P in members:
+            r = dict(bench="sac_pop_acting", kind="SAC", shape=shape, members=P, nenvs=8, rounds=rounds, steps_per_round=steps,
+                     **{k: sh[k] for k in ("S", "A", "H", "L", "B")})
+            for side in ("merged", "members"):
+                v = t[(side, P)]
+                r[side + "_us_per_call"] = dict(median=round(float(np.median(v)), 2), min=round(min(v), 2), max=round(max(v), 2), rounds=v)
+            r["members_over_merged"] = round(r["members_us_per_call"]["median"] / r["merged_us_per_call"]["median"], 3)
+            r["merged_range_below_members"] = r["merged_us_per_call"]["max"] < r["members_us_per_call"]["min"]
+            write(json.dumps(r))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--child", default=None, choices=["merged", "members"], help="(internal) --kind SAC --acting: one side of one round in this process")
     ap.add_argument("--kind", default="DDPG", choices=sorted(KINDS))
     ap.add_argument("--update-rounds", type=int, default=1, help="> 1: population and sequential agents timed in alternation this many times")
     ap.add_argument("--shapes", default="cfg1,headline")
@@ -216,6 +290,20 @@ def main():
     if a.acting:
         assert a.rounds >= 5 and a.steps >= 3000 or os.environ.get("POP_BENCH_SHORT"), "at least five rounds of 3 000 vector steps"
         members = "1,2,4,8,16" if a.members == "1,2,4,8" else a.members
+        if a.kind == "SAC":
+            Ps = [int(x) for x in (("2,4,8,16" if a.members == "1,2,4,8" else a.members).split(","))]
+            if a.child:
+                for shape in a.shapes.split(","):
+                    for c in acting_sac_child(shape, Ps, a.steps, a.child == "merged"):
+                        print("CHILD " + json.dumps(c), flush=True)
+                return
+            with open(a.out, "a") if a.out else open(os.devnull, "w") as f:
+                def write(line):
+                    print(line, flush=True)
+                    f.write(line + "\n")
+                    f.flush()
+                run_acting_sac(a.shapes.split(","), Ps, a.rounds, a.steps, write)
+            return
         with open(a.out, "a") if a.out else open(os.devnull, "w") as f:
             for shape in a.shapes.split(","):
                 for P in [int(x) for x in members.split(",")]:
