@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The stand-in trainer loop (examples/trainer_standin.py; reference src/env.py:334-406) for a POPULATION: P independent DDPG, TD3 or SAC
+"""The stand-in trainer loop (examples/trainer_standin.py; reference src/env.py:334-406) for a POPULATION: P independent DDPG, TD3, SAC or TQC
 agents, each with its own synthetic vector env, HER ring and normalisers, driven through the population's calls —
 
     pop.observe_act -> P env steps -> pop.process_step -> every `max_episode` episodes: pop.update_many(gradient_step)
@@ -37,7 +37,7 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
                         tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.25 * i), critic_lr=1e-3 * (1 + 0.25 * i),
                         ac_update_freq=1 if agent_name == "DDPG" else 2, policy_noise=0.2 if agent_name == "TD3" else 0.0)
             for i in range(members)]
-    cls = dict(DDPG=gcrl_amd.DDPGPopulation, TD3=gcrl_amd.TD3Population, SAC=gcrl_amd.SACPopulation)[agent_name]
+    cls = dict(DDPG=gcrl_amd.DDPGPopulation, TD3=gcrl_amd.TD3Population, SAC=gcrl_amd.SACPopulation, TQC=gcrl_amd.TQCPopulation)[agent_name]
     pop = cls(e0.obs_dim + e0.goal_dim, e0.ac_dim, cfgs, num_envs, gradient_step, rng="engine", seeds=[seed + i for i in range(members)])
     for m, env in zip(pop.members, envs):   # what GoalEnvHER.__init__ injects (src/env.py:93-105), device normalisers
         m.buffer.obs_normalizer = DeviceRunningNormalizer(env.obs_dim)
@@ -87,7 +87,7 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--agent", default="DDPG", choices=["DDPG", "TD3", "SAC"])
+    ap.add_argument("--agent", default="DDPG", choices=["DDPG", "TD3", "SAC", "TQC"])
     ap.add_argument("--members", type=int, default=4)
     ap.add_argument("--cycles", type=int, default=40)
     ap.add_argument("--nenv", type=int, default=8)

@@ -11,8 +11,8 @@ The directory name carries a hyphen, so import it through the repo-root shim: `i
 from . import _ffi  # noqa: F401  (loads the shared library; ImportError if it was not built)
 from .src import agent, buffer, model, utils  # noqa: F401
 from .src.agent import DDPG, SACAgent, TD3Agent, TQCAgent  # noqa: F401
-from .src.population import DDPGPopulation, SACPopulation, TD3Population  # noqa: F401
+from .src.population import DDPGPopulation, SACPopulation, TD3Population, TQCPopulation  # noqa: F401
 from .src.buffer import HERBuffer, MTStream, PERBuffer, ReplayBuffer  # noqa: F401
 
-__all__ = ["DDPG", "DDPGPopulation", "TD3Agent", "TD3Population", "SACAgent", "SACPopulation", "TQCAgent", "HERBuffer", "ReplayBuffer", "PERBuffer", "MTStream", "agent", "buffer",
+__all__ = ["DDPG", "DDPGPopulation", "TD3Agent", "TD3Population", "SACAgent", "SACPopulation", "TQCAgent", "TQCPopulation", "HERBuffer", "ReplayBuffer", "PERBuffer", "MTStream", "agent", "buffer",
            "model", "utils"]

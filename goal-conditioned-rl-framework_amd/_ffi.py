@@ -124,6 +124,7 @@ PROTOTYPES = {
     "gcrl_agent_metrics": (C.c_int, [_vp, _i64, _vp, C.c_int]),
     "gcrl_pop_create": (_vp, [C.POINTER(AgentConfig), C.c_int32]),
     "gcrl_pop_create_forms": (_vp, [C.POINTER(AgentConfig), C.c_int32]),
+    "gcrl_pop_create_layered": (_vp, [C.POINTER(AgentConfig), C.c_int32]),
     "gcrl_pop_member": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp)]),
     "gcrl_pop_size": (C.c_int32, [_vp]),
     "gcrl_pop_update_n": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),

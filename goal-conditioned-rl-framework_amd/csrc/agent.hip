@@ -506,7 +506,11 @@ int sac_actor_forward_multi(gcrl_agent* a, hipStream_t st, const ActorFwd* f, in
     tg[i].seed = a->cfg.seed; tg[i].rng_stream = f[i].rng_stream;
   }
   if (slab)   // the running statistics of every layer, from the batch statistics the slab launches left: input 0's, then input 1's
-    tg[0].run = BnRunning{{a->bn_bstat, nf == 2 ? a->bn_bstat + (long long)net.L * 2 * H : nullptr}, nf, a->bn_rmean, a->bn_rvar, net.L, H, B};
+  {   // (field by field into the zeroed record, padding untouched: a population caches its device tables by the recorded argument bytes)
+    BnRunning& run = tg[0].run;
+    run.bstat[0] = a->bn_bstat; run.bstat[1] = nf == 2 ? a->bn_bstat + (long long)net.L * 2 * H : nullptr;
+    run.n = nf; run.rmean = a->bn_rmean; run.rvar = a->bn_rvar; run.layers = net.L; run.H = H; run.B = B;
+  }
   if (heads_fused) {
     HeadsSampleArgs hs;
     std::memset(&hs, 0, sizeof(hs));

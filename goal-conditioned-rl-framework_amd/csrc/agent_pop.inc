@@ -1,4 +1,4 @@
-// agent_pop.inc — DDPG, TD3 and SAC populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
+// agent_pop.inc — DDPG, TD3, SAC and TQC populations (include/gcrl.h gcrl_pop_*; included at the end of agent.hip).
 //
 // P independent DDPG, TD3 or SAC agents of one kind and equal shapes whose update steps share launches.  Each member is an ordinary gcrl_agent (its own
 // parameters, optimiser state, control block, metric ring and meeting counters), so every single-agent entry works on it.  A
@@ -7,6 +7,8 @@
 // dw_adam_pop_kernel, begin_step_pop_kernel, gemm_batch_pop_kernel<1, 1, 4>, adam_pop_kernel, adam_pair_pop_kernel; SAC: the slab launches' bn_linear_*_slab_*pop_kernel, rowchain_split_[heads_]pop_kernel, tanh_gauss_bwd_select_pop_kernel), in which member m's workgroups read member m's own argument struct — the same
 // arithmetic in the same order as the member's own launch, so each member computes bit for bit what it computes alone.
 // Launches without a population form are issued member by member at their position.
+// TQC (gcrl_pop_create_layered): members on the layer-per-launch schedule; new forms tanh_gauss_fwd[2]_pop_kernel and tanh_gauss_bwd_pop_kernel;
+// the TD-loss launch and the single-workgroup metric launch of a step have none yet (DESIGN.md 4f).
 // The acting side (one launch per vector-env step for all members): gcrl_pop_observe_act (row-chain actors), gcrl_pop_observe_act_bn
 // (SAC's BatchNorm actors), gcrl_pop_process_step.
 //
@@ -117,6 +119,8 @@ int pop_issue(gcrl_pop* p, size_t k, hipStream_t st) {
     case POP_RC_SPLIT: return launch_rowchain_split_pop(st, tab, (int)P, o.sub, false, o.grid, o.lds);
     case POP_RC_SPLIT_HEADS: return launch_rowchain_split_pop(st, tab, (int)P, o.sub, true, o.grid, o.lds);
     case POP_TG_BWD_SELECT: return launch_tanh_gauss_bwd_select_pop(st, tab, (int)P, o.grid);
+    case POP_TG_FWD: return launch_tanh_gauss_fwd_pop(st, tab, (int)P, o.sub, o.grid);
+    case POP_TG_BWD: return launch_tanh_gauss_bwd_pop(st, tab, (int)P, o.grid);
     default: return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: launch kind %d has no population form", o.kind);
   }
 }
@@ -124,7 +128,9 @@ int pop_issue(gcrl_pop* p, size_t k, hipStream_t st) {
 // record member a's launches of m planned steps (stream capture around the recording: a launch that bypassed the recorder would
 // land in the captured graph instead of running out of order — refused below).  DDPG: the overlapped schedule of
 // gcrl_agent_update_n (run_steps_ddpg); TD3 and SAC: their per-step phases with the variant bits gcrl_agent_update_n gives them on the
-// row-chain path (every step pre-advanced, its last launch advancing the control block)
+// row-chain path (every step pre-advanced, its last launch advancing the control block); TQC: the layer-per-launch schedule with the bits
+// pop_layer_adv gives (gcrl_agent_update_n's rule)
+bool pop_layer_adv(const gcrl_agent* a) { return a->sac && !a->rowchain && a->Q == 1 && a->cfg.ac_update_freq == 1 && !a->layer_adv_off; }
 int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>& plans, PopRec* rec) {
   rec->ops.clear();
   std::vector<int> variants(plans.size());
@@ -135,6 +141,11 @@ int pop_record_steps(gcrl_agent* a, hipStream_t cs, const std::vector<StepPlan>&
   int rc = GCRL_OK;
   if (a->cfg.kind == GCRL_AGENT_TD3 || a->cfg.kind == GCRL_AGENT_SAC) {
     for (size_t i = 0; i < variants.size() && !rc; ++i) rc = run_step(a, cs, variants[i] | norm_bits(a) | V_ADV | V_PRE, 7, 1);
+  } else if (a->cfg.kind == GCRL_AGENT_TQC) {
+    // every step starts with its begin_step launch — unless every step is an actor step: then the actor's optimiser launch advances the
+    // control block and the TD-loss launch refreshes the copies it reads, as in the standalone agent's call
+    const int adv = pop_layer_adv(a) ? (V_ADV | V_PRE) : 0;
+    for (size_t i = 0; i < variants.size() && !rc; ++i) rc = run_step(a, cs, variants[i] | norm_bits(a) | adv, 7, 1);
   } else {
     rc = run_steps_ddpg(a, cs, variants.data(), (int)variants.size(), /*first_pre=*/true);
   }
@@ -259,10 +270,58 @@ gcrl_pop* pop_create(const gcrl_agent_config* cfgs, int32_t members, bool same_f
   return p;
 }
 
+// TQC populations (gcrl_pop_create_layered): members on the layer-per-launch schedule — scalar critics, the BatchNorm actor's slab launches
+gcrl_pop* pop_create_layered(const gcrl_agent_config* cfgs, int32_t members) {
+  auto bad = [](const char* field, const char* why) -> gcrl_pop* {
+    fail(GCRL_ERR_ARG, "gcrl_pop_create_layered: %s: %s", field, why);
+    return nullptr;
+  };
+  // every refusal before any device work
+  if (!cfgs) return bad("cfgs", "null config array");
+  if (members < 1 || members > kMaxPopMembers) return bad("members", "a population has 1..16 members");
+  bool any_tqc = false;
+  for (int i = 0; i < members; ++i) any_tqc = any_tqc || cfgs[i].kind == GCRL_AGENT_TQC;
+  for (int i = 0; i < members; ++i) {
+    const gcrl_agent_config& c = cfgs[i];
+    if (c.kind != GCRL_AGENT_TQC)
+      return bad("kind", any_tqc ? "members must share kind: every member of this population is a TQC agent"
+                                 : "this entry creates TQC populations (DDPG and TD3: gcrl_pop_create; SAC: gcrl_pop_create_forms)");
+    if (c.n_quantiles > 1) return bad("n_quantiles", "TQC populations run the scalar critics: n_quantiles = 1 (the distributional variant has no population)");
+    if (c.num_critics < 2 || c.num_critics > kMaxCritics) return bad("num_critics", "a TQC population has 2..8 critics");
+    if (const char* f = pop_mismatch(cfgs[0], c)) return bad(f, "members must share kind, shapes, batch_size, num_critics, gradient_step, ac_update_freq, polyak_every, pipeline_steps, use_graph and device");
+    if (c.top_drop < 0 || c.top_drop >= c.num_critics) return bad("top_drop", "0 <= top_drop < num_critics");
+    if (c.ac_dim < 1 || c.ac_dim > 16 || c.obs_dim < 1 || c.layer_count < 1 || c.layer_count > 8 || c.batch_size < 1) return bad("shape", "bad obs_dim / ac_dim / layer_count / batch_size");
+    if (c.batch_size > 512) return bad("batch_size", "TQC populations run the BatchNorm slab launches: batch_size <= 512");
+    if (c.hidden_dim < 16 || c.hidden_dim % 16 != 0) return bad("hidden_dim", "TQC populations run the BatchNorm slab launches: hidden_dim % 16 == 0");
+    if (!sac_slab_rule(c.batch_size, c.hidden_dim)) return bad("GCRL_NO_BN_SLAB", "TQC populations run the BatchNorm slab launches, which this environment switches off");
+    if (c.use_graph >= 2) return bad("use_graph", "the population issues its launches itself (use_graph 0 or 1)");
+  }
+  gcrl_pop* p = new gcrl_pop;
+  for (int i = 0; i < members; ++i) {
+    gcrl_agent* a = gcrl_agent_create(&cfgs[i]);
+    if (!a) { gcrl_pop_destroy(p); return nullptr; }
+    p->m.push_back(a);
+    if (a->rowchain || !a->slab_on() || a->Q != 1) {
+      gcrl_pop_destroy(p);
+      return bad("kind", "this TQC configuration does not run the layer-per-launch step with the slab launches");
+    }
+  }
+  gcrl_agent* a0 = p->m[0];
+  // form bit 1: the row-split slab launches; bit 2 has no meaning on this schedule (want 0); bit 8: no TQC agent runs the fused optimiser
+  // launch (a row-chain form), so its terms only say what the launch would take
+  bn_slab_pop_row_split_terms(a0->B, a0->H, a0->A, members, &p->want[0], &p->cap[0]);
+  p->want[1] = 0; p->cap[1] = 0;
+  p->want[2] = a0->opt_fuse_can ? (long long)members * a0->of_wgs : 0; p->cap[2] = a0->opt_fuse_can ? dw_adam_pop_capacity() : 0;
+  p->no_waits = std::getenv("GCRL_POP_NO_WAITS") != nullptr;
+  p->rec.resize(members);
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
 
+gcrl_pop* gcrl_pop_create_layered(const gcrl_agent_config* cfgs, int32_t members) { return pop_create_layered(cfgs, members); }
 gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members) { return pop_create(cfgs, members, false); }
 gcrl_pop* gcrl_pop_create_forms(const gcrl_agent_config* cfgs, int32_t members) { return pop_create(cfgs, members, true); }
 
@@ -311,7 +370,8 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
   hipStream_t st = a0->pick(stream);
   // admission of the forms whose workgroups wait for each other: the whole population launch resident at once
   const int forms = pop_forms_now(p);
-  const bool sac = a0->cfg.kind == GCRL_AGENT_SAC;
+  const bool tqc = a0->cfg.kind == GCRL_AGENT_TQC;
+  const bool sac = a0->cfg.kind == GCRL_AGENT_SAC || tqc;   // (the BatchNorm actors: their slab launches have the row-split form)
   const bool ksplit = !sac && (forms & 2) != 0, ofuse = (forms & 8) != 0, rsplit = (forms & 1) != 0, merge = sac && (forms & 2) != 0;
   struct Forms { bool ksplit, ofuse, rowtile, rc_merge; int bn_rsplit; };
   std::vector<Forms> saved(P);
@@ -334,7 +394,7 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
       gcrl_agent* a = p->m[i];
       if (a->wt_dirty) TRY(rc_rebuild_wt(a, st));
       TRY(begin_call(a, rings[i], step0 + done, m, nullptr, 1.0f, st, plans[i], tickets_out ? tickets_out + (size_t)i * n + done : nullptr,
-                     tuple_len_out ? tuple_len_out + (size_t)i * n + done : nullptr, /*defer_rest=*/false, /*pre_advanced=*/true));
+                     tuple_len_out ? tuple_len_out + (size_t)i * n + done : nullptr, /*defer_rest=*/false, /*pre_advanced=*/!tqc || pop_layer_adv(a)));
     }
     int rc = GCRL_OK;
     for (int i = 0; i < P && !rc; ++i) {

@@ -313,6 +313,8 @@ int launch_begin_step_pop(hipStream_t st, const void* tab, int members) {
 
 int launch_td_loss(hipStream_t st, const TdLossArgs& a) {
   GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.B >= 1, "td_loss: bad C=%d B=%d", a.C, a.B);
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h): no population form, issued member by member
+    return pop_defer(r, [a](hipStream_t s) { return launch_td_loss(s, a); });
   const bool mb = a.part && a.ticket && a.B >= 1024;
   const dim3 th(mb ? 256 : reduce_threads(a.B)), gr(mb ? (a.B + 255) / 256 : 1);
 #define GCRL_TD(T, L) if (a.target_kind == T && a.loss_kind == L) { if (mb) hipLaunchKernelGGL((td_loss_kernel<T, L, true>), gr, th, 0, st, a); \
@@ -327,12 +329,14 @@ int launch_td_loss(hipStream_t st, const TdLossArgs& a) {
 
 int launch_mean_metric(hipStream_t st, const StepCtrl* cur, const float* x, int n, float scale,
                        float* metrics, int idx) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_mean_metric(s, cur, x, n, scale, metrics, idx); });
   hipLaunchKernelGGL(mean_metric_kernel, dim3(1), dim3(reduce_threads(n)), 0, st, cur, x, n, scale, metrics, idx);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
 
 int launch_fill(hipStream_t st, float* x, long long n, float v) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_fill(s, x, n, v); });
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, v);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -340,6 +344,7 @@ int launch_fill(hipStream_t st, float* x, long long n, float v) {
 
 int launch_td3_smooth(hipStream_t st, const StepCtrl* cur, float* act, long long slot_stride, int ld,
                       int B, int A, const float* eps, float pn, float nc, unsigned long long seed) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_td3_smooth(s, cur, act, slot_stride, ld, B, A, eps, pn, nc, seed); });
   hipLaunchKernelGGL(td3_smooth_kernel, dim3((B * A + 255) / 256), dim3(256), 0, st, cur, act,
                      slot_stride, ld, B, A, eps, pn, nc, seed);
   GCRL_HIP(hipGetLastError());
@@ -348,6 +353,7 @@ int launch_td3_smooth(hipStream_t st, const StepCtrl* cur, float* act, long long
 
 int launch_sumsq(hipStream_t st, const float* g, long long n, long long net_stride, int nets,
                  float* partial) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_sumsq(s, g, n, net_stride, nets, partial); });
   hipLaunchKernelGGL(sumsq_kernel, dim3(kNormBlocks, nets), dim3(256), 0, st, g, n, net_stride, partial);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -365,6 +371,7 @@ static unsigned adam_blocks(long long n) {
 
 int launch_sumsq2(hipStream_t st, const float* g0, long long n0, float* partial0, const float* g1, long long n1,
                   float* partial1) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_sumsq2(s, g0, n0, partial0, g1, n1, partial1); });
   hipLaunchKernelGGL(sumsq2_kernel, dim3(kNormBlocks, 2), dim3(256), 0, st, g0, n0, g1, n1, partial0, partial1);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -395,6 +402,7 @@ int launch_adam_pair(hipStream_t st, const AdamArgs& a0, const AdamArgs& a1) {
 }
 
 int launch_polyak(hipStream_t st, const float* p, float* target, long long n, double tau) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_polyak(s, p, target, n, tau); });
   hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, target, n,
                      (float)tau, (float)(1.0 - tau));
   GCRL_HIP(hipGetLastError());

@@ -393,6 +393,21 @@ __global__ void tanh_gauss_fwd2_kernel(TanhGaussArgs a0, TanhGaussArgs a1) {
   else tanh_gauss_fwd_body(a1);
 }
 
+// population forms (pop.h; TQC on the layer-per-launch schedule): member blockIdx.y (two inputs: blockIdx.z) on its own argument record(s)
+// from the device table, the workgroups blockIdx.x (and input blockIdx.y) of its single-agent launch
+struct TgFwd2Pop { TanhGaussArgs a0, a1; };
+__global__ __launch_bounds__(256) void tanh_gauss_fwd_pop_kernel(const TanhGaussArgs* __restrict__ tab) {
+  const TanhGaussArgs& a = tab[blockIdx.y];
+  if (a.run.layers && blockIdx.x == gridDim.x - 1) { bn_running_update(a.run); return; }
+  [[clang::always_inline]] tanh_gauss_fwd_body(a);   // (inlined as in the single-agent kernels: no call, no per-thread scratch)
+}
+__global__ __launch_bounds__(256) void tanh_gauss_fwd2_pop_kernel(const TgFwd2Pop* __restrict__ tab) {
+  const TgFwd2Pop& e = tab[blockIdx.z];
+  if (e.a0.run.layers && blockIdx.x == gridDim.x - 1) { if (blockIdx.y == 0) bn_running_update(e.a0.run); return; }
+  const TanhGaussArgs& a = blockIdx.y == 0 ? e.a0 : e.a1;   // (uniform per workgroup)
+  [[clang::always_inline]] tanh_gauss_fwd_body(a);
+}
+
 // The two heads and the sampling of one or two inputs as one launch (sac_heads.h): workgroup (x, y) owns rows [16 x, 16 x + 16) of
 // input y.  (The last workgroup of row y = 0 is the running-statistics rider when tg[0].run.layers.)
 __global__ __launch_bounds__(256) void heads_sample_kernel(HeadsSampleArgs h) {
@@ -452,6 +467,8 @@ __device__ inline void tanh_gauss_bwd_body(const TanhGaussBwdArgs& a) {
   a.gls[(long long)b * a.ld_g + j] = gls;
 }
 __global__ __launch_bounds__(256) void tanh_gauss_bwd_kernel(TanhGaussBwdArgs a) { tanh_gauss_bwd_body(a); }
+// population form (pop.h): member blockIdx.y on its own argument record
+__global__ __launch_bounds__(256) void tanh_gauss_bwd_pop_kernel(const TanhGaussBwdArgs* __restrict__ tab) { tanh_gauss_bwd_body(tab[blockIdx.y]); }
 
 __global__ __launch_bounds__(1024) void alpha_update_kernel(AlphaArgs a) {
   __shared__ float scratch[16];
@@ -776,6 +793,8 @@ int launch_bn_relu_bwd(hipStream_t st, const float* dh, const float* dh2, const 
 
 int launch_heads_sample(hipStream_t st, HeadsSampleArgs& h) {
   GCRL_CHECK_ARG(h.n == 1 || h.n == 2, "heads_sample: %d inputs", h.n);
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h): no population form, issued member by member
+    return pop_defer(r, [hc = h](hipStream_t s) mutable { return launch_heads_sample(s, hc); });
   int blocks = 0;
   for (int i = 0; i < h.n; ++i) {
     const TanhGaussArgs& a = h.tg[i];
@@ -793,12 +812,22 @@ int launch_heads_sample(hipStream_t st, HeadsSampleArgs& h) {
 }
 
 int launch_tanh_gauss_fwd(hipStream_t st, const TanhGaussArgs& a) {
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
+    return pop_record(r, POP_TG_FWD, 1, dim3((a.B + 255) / 256 + (a.run.layers ? 1 : 0)), 0, &a, sizeof(a), [a](hipStream_t s) { return launch_tanh_gauss_fwd(s, a); });
   hipLaunchKernelGGL(tanh_gauss_fwd_kernel, dim3((a.B + 255) / 256 + (a.run.layers ? 1 : 0)), dim3(256), 0, st, a);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
 
 int launch_tanh_gauss_fwd2(hipStream_t st, const TanhGaussArgs& a0, const TanhGaussArgs& a1) {
+  if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
+    TgFwd2Pop e;
+    std::memset(&e, 0, sizeof(e));
+    // (byte copies of records their builder zeroed first, padding included: the device tables are cached by content)
+    std::memcpy(&e.a0, &a0, sizeof(a0)); std::memcpy(&e.a1, &a1, sizeof(a1));
+    return pop_record(r, POP_TG_FWD, 2, dim3((std::max(a0.B, a1.B) + 255) / 256 + (a0.run.layers ? 1 : 0), 2), 0, &e, sizeof(e),
+                      [e](hipStream_t s) { return launch_tanh_gauss_fwd2(s, e.a0, e.a1); });
+  }
   hipLaunchKernelGGL(tanh_gauss_fwd2_kernel, dim3((std::max(a0.B, a1.B) + 255) / 256 + (a0.run.layers ? 1 : 0), 2), dim3(256), 0, st, a0, a1);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -806,6 +835,7 @@ int launch_tanh_gauss_fwd2(hipStream_t st, const TanhGaussArgs& a0, const TanhGa
 
 int launch_actor_select(hipStream_t st, const ActorSelArgs& a) {
   GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C, "actor_select: bad C=%d drop=%d", a.C, a.drop);
+  if (PopRec* r = pop_recording()) return pop_defer(r, [a](hipStream_t s) { return launch_actor_select(s, a); });
   hipLaunchKernelGGL(actor_select_kernel, dim3(1), dim3(reduce_threads(a.B)), 0, st, a);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -813,6 +843,8 @@ int launch_actor_select(hipStream_t st, const ActorSelArgs& a) {
 
 int launch_actor_select_alpha(hipStream_t st, const ActorSelArgs& a, const AlphaArgs& al) {
   GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C, "actor_select: bad C=%d drop=%d", a.C, a.drop);
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h): no population form, issued member by member
+    return pop_defer(r, [a, al](hipStream_t s) { return launch_actor_select_alpha(s, a, al); });
   if (a.part && a.ticket && a.B >= 1024 && al.phase == 0 && al.B == a.B) {
     hipLaunchKernelGGL(actor_select_alpha_mb_kernel, dim3((a.B + 255) / 256 + (a.mean_x ? 1 : 0)), dim3(256), 0, st, a, al);
     GCRL_HIP(hipGetLastError());
@@ -824,6 +856,8 @@ int launch_actor_select_alpha(hipStream_t st, const ActorSelArgs& a, const Alpha
 }
 
 int launch_tanh_gauss_bwd(hipStream_t st, const TanhGaussBwdArgs& a) {
+  if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
+    return pop_record(r, POP_TG_BWD, 0, dim3((a.B * a.A + 255) / 256), 0, &a, sizeof(a), [a](hipStream_t s) { return launch_tanh_gauss_bwd(s, a); });
   hipLaunchKernelGGL(tanh_gauss_bwd_kernel, dim3((a.B * a.A + 255) / 256), dim3(256), 0, st, a);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -851,7 +885,25 @@ int launch_tanh_gauss_bwd_select_pop(hipStream_t st, const void* tab, int member
   return GCRL_OK;
 }
 
+// population launches of the sampling forward (sub = inputs: 1 or 2) and backward
+int launch_tanh_gauss_fwd_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid) {
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && (sub == 1 || sub == 2) && grid.x >= 1 && grid.y == (unsigned)sub && grid.z == 1,
+                 "tanh_gauss_fwd (population): bad launch");
+  if (sub == 1) hipLaunchKernelGGL(tanh_gauss_fwd_pop_kernel, dim3(grid.x, (unsigned)members), dim3(256), 0, st, static_cast<const TanhGaussArgs*>(tab));
+  else hipLaunchKernelGGL(tanh_gauss_fwd2_pop_kernel, dim3(grid.x, 2, (unsigned)members), dim3(256), 0, st, static_cast<const TgFwd2Pop*>(tab));
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int launch_tanh_gauss_bwd_pop(hipStream_t st, const void* tab, int members, dim3 grid) {
+  GCRL_CHECK_ARG(tab && members >= 1 && members <= 65535 && grid.x >= 1 && grid.y == 1 && grid.z == 1, "tanh_gauss_bwd (population): bad launch");
+  hipLaunchKernelGGL(tanh_gauss_bwd_pop_kernel, dim3(grid.x, (unsigned)members), dim3(256), 0, st, static_cast<const TanhGaussBwdArgs*>(tab));
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
 int launch_alpha_update(hipStream_t st, const AlphaArgs& a) {
+  if (PopRec* r = pop_recording()) return pop_defer(r, [a](hipStream_t s) { return launch_alpha_update(s, a); });
   hipLaunchKernelGGL(alpha_update_kernel, dim3(1), dim3(256), 0, st, a);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;
@@ -861,6 +913,7 @@ int launch_sort_truncate_mean(hipStream_t st, const float* in, long long rows, i
                               float* sorted, float* mean) {
   GCRL_CHECK_ARG(in && rows >= 1 && width >= 1 && width <= 64 && drop >= 0 && drop < width,
                  "sort_truncate_mean: need 1 <= width <= 64 and 0 <= drop < width");
+  if (PopRec* r = pop_recording()) return pop_defer(r, [=](hipStream_t s) { return launch_sort_truncate_mean(s, in, rows, width, drop, sorted, mean); });
   hipLaunchKernelGGL(sort_trunc_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, in, rows, width,
                      drop, sorted, mean);
   GCRL_HIP(hipGetLastError());

@@ -34,6 +34,9 @@ enum PopKind {
   POP_RC_SPLIT = 10,       // rowchain_split_kernel<RG> (sub = RG | part << 4 | phase << 8; args: RowChainArgs, phase, part)
   POP_RC_SPLIT_HEADS = 11, // rowchain_split_heads_kernel<RG> (sub as above; args: RowChainArgs, phase, part, HeadsFold)
   POP_TG_BWD_SELECT = 12,  // tanh_gauss_bwd_select_kernel (args: TanhGaussBwdArgs, ActorSelArgs, AlphaArgs)
+  // TQC on the layer-per-launch schedule (ops_sac.hip)
+  POP_TG_FWD = 13,         // tanh_gauss_fwd_kernel (sub = 1; args: TanhGaussArgs) / tanh_gauss_fwd2_kernel (sub = 2; args: two of them)
+  POP_TG_BWD = 14,         // tanh_gauss_bwd_kernel (args: TanhGaussBwdArgs)
 };
 // whether a recorded launch of this kind and sub has a population form
 inline bool pop_mergeable(int kind, int sub) { return kind != POP_ALONE && (kind != POP_GEMM_BATCH || sub == 1); }
@@ -116,6 +119,9 @@ int launch_bn_bwd_slab_pop(hipStream_t st, const void* tab, int members, int sub
 int launch_bn_bwd_slab_fold_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
 int launch_rowchain_split_pop(hipStream_t st, const void* tab, int members, int sub, bool heads, dim3 grid, size_t lds);
 int launch_tanh_gauss_bwd_select_pop(hipStream_t st, const void* tab, int members, dim3 grid);
+// TQC: member = blockIdx.y (the two-input sampling forward, whose grid uses blockIdx.y for the input: blockIdx.z)
+int launch_tanh_gauss_fwd_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
+int launch_tanh_gauss_bwd_pop(hipStream_t st, const void* tab, int members, dim3 grid);
 // admission of the waiting forms for a population of `members`: the two sides of the comparison (cap 0: shared device or the query failed)
 // (*want: `members` times a member's workgroups of the form; *cap: what is resident at once; want 0: the shape does not have the form)
 void bn_slab_pop_row_split_terms(int B, int H, int A, int members, long long* want, long long* cap);

@@ -1,10 +1,10 @@
-"""DDPGPopulation / TD3Population / SACPopulation — P independent agents of one kind whose update steps share launches (include/gcrl.h gcrl_pop_*).
+"""DDPGPopulation / TD3Population / SACPopulation / TQCPopulation — P independent agents of one kind whose update steps share launches (include/gcrl.h gcrl_pop_*).
 
 RL results are reported over several seeds and hyper-parameter searches run many trials of one shape; with one agent per
-trial, N agents cost N times one agent.  A population of 1..16 DDPG, TD3 or SAC agents of equal shapes issues each stage of a
+trial, N agents cost N times one agent.  A population of 1..16 DDPG, TD3, SAC or TQC agents of equal shapes issues each stage of a
 training step once for all members (csrc/agent_pop.inc), and every member computes bit for bit what a standalone `DDPG` /
-`TD3Agent` / `SACAgent` with the same config, seed and ring computes (SAC: a standalone agent running the launch forms `forms()`
-reports).
+`TD3Agent` / `SACAgent` / `TQCAgent` with the same config, seed and ring computes (SAC, TQC: a standalone agent running the launch
+forms `forms()` reports).
 
 `.members` are ordinary `DDPG` / `TD3Agent` objects (own `HERBuffer`, the whole single-agent API, including `update` /
 `update_many` on the member alone); `update_many(step0, n)` steps all of them and returns, per member, what the agent's own
@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import _ffi
 from .._ffi import lib
-from .agent import DDPG, KIND, SACAgent, TD3Agent, native_config
+from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, native_config
 from .buffer import MTStream
 
 MAX_MEMBERS = 16
@@ -33,10 +33,9 @@ SHARED = ("hidden_dim", "layer_count", "batch_size", "ac_update_freq")
 class _PopHandle:
     """Owner of the native population; the members keep it alive."""
 
-    def __init__(self, cfgs, same_forms=False):
+    def __init__(self, cfgs, entry="gcrl_pop_create"):
         arr = (_ffi.AgentConfig * len(cfgs))(*cfgs)
-        create = lib.gcrl_pop_create_forms if same_forms else lib.gcrl_pop_create
-        self.h = _ffi.check_ptr(create(arr, len(cfgs)), "gcrl_pop_create")
+        self.h = _ffi.check_ptr(getattr(lib, entry)(arr, len(cfgs)), entry)
 
     def member(self, i: int) -> int:
         out = C.c_void_p()
@@ -53,6 +52,12 @@ class _Population:
     AGENT = None          # the member class
     NUM_CRITICS = 1
     SAME_FORMS = False    # the class's guarantee is "a standalone agent running the same forms" (gcrl_pop_create_forms)
+    ENTRY = None          # the engine entry that creates the population (None: gcrl_pop_create_forms / gcrl_pop_create by SAME_FORMS)
+
+    def _native_configs(self, kind, obs_dim, ac_dim, configs, seeds, gradient_step, device_index):
+        """The members' gcrl_agent_config records, as the member agents' own constructors form them (no device work)."""
+        return [native_config(kind, obs_dim, ac_dim, c, int(gradient_step), num_critics=self.NUM_CRITICS, device_index=device_index, seed=s)
+                for c, s in zip(configs, seeds)]
 
     def _refuse(self, field: str, why: str):
         raise _ffi.GcrlError(f"{type(self).__name__}: {field}: {why}")
@@ -74,9 +79,9 @@ class _Population:
                 if getattr(c, f) != getattr(configs[0], f):
                     self._refuse(f, f"member {i} has {getattr(c, f)!r}, member 0 {getattr(configs[0], f)!r}: members must share shapes")
         kind = KIND[self.AGENT.KIND_NAME]
-        cfgs = [native_config(kind, obs_dim, ac_dim, c, int(gradient_step), num_critics=self.NUM_CRITICS, device_index=device_index, seed=s)
-                for c, s in zip(configs, seeds)]
-        self._pop = _PopHandle(cfgs, self.SAME_FORMS)   # (the engine checks the rest — kind, row-chain shape — before it touches the device)
+        cfgs = self._native_configs(kind, obs_dim, ac_dim, configs, seeds, gradient_step, device_index)
+        entry = self.ENTRY or ("gcrl_pop_create_forms" if self.SAME_FORMS else "gcrl_pop_create")
+        self._pop = _PopHandle(cfgs, entry)   # (the engine checks the rest — kind, row-chain shape — before it touches the device)
         pop = self._pop
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
@@ -327,3 +332,29 @@ class TD3Population(_Population):
     returns, per member, `TD3Agent.update_many`'s tuples (8 entries on actor steps, 6 on critic-only steps)."""
     AGENT = TD3Agent
     NUM_CRITICS = 2
+
+
+class TQCPopulation(_Population):
+    """1..16 `TQCAgent`s of equal shapes stepped together (scalar critics, batch_size <= 512, hidden_dim % 16 == 0: the layer-per-launch
+    step with the BatchNorm actor's slab launches; engine entry gcrl_pop_create_layered).  `num_critics` (2..8) comes from the configs
+    as `TQCAgent` reads it and must be shared; `top_quantiles_to_drop` may differ per member.  update_many returns, per member,
+    `TQCAgent.update_many`'s tuples (9 entries on actor steps, 6 on critic-only steps).  Every member is bitwise a standalone
+    `TQCAgent` running the launch forms `forms()` reports.  Acting is SAC's (the same BatchNorm actor): `process_step` is the merged
+    launch, `observe_act` has one too and — untimed for this kind — takes it only once `MERGE_ACTING_FROM` is lowered."""
+    AGENT = TQCAgent
+    NUM_CRITICS = None    # from the configs
+    SAME_FORMS = True
+    ENTRY = "gcrl_pop_create_layered"
+    MERGE_ACTING_FROM = MAX_MEMBERS + 1   # (DESIGN.md 4g's rule: the merged acting launch is untimed for this kind)
+    MERGE_PROCESS_FROM = 2
+    _native_observe_act = SACPopulation._native_observe_act   # the BatchNorm actors' entry (gcrl_pop_observe_act_bn)
+
+    def _native_configs(self, kind, obs_dim, ac_dim, configs, seeds, gradient_step, device_index):
+        # (TQCAgent's own reading of the two keys: src/agent.py)
+        ncs = [int(getattr(c, "num_critics", 5)) for c in configs]
+        for i, nc in enumerate(ncs):
+            if nc != ncs[0]:
+                self._refuse("num_critics", f"member {i} has {nc}, member 0 {ncs[0]}: members must share the critic count")
+        return [native_config(kind, obs_dim, ac_dim, c, int(gradient_step), num_critics=nc, top_drop=int(getattr(c, "top_quantiles_to_drop", 2)),
+                              n_quantiles=1, device_index=device_index, seed=s)
+                for c, nc, s in zip(configs, ncs, seeds)]

@@ -332,11 +332,20 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * are refused naming batch_size.  SAC populations run the path of the twin-critic SAC step at batch_size <= 512: the BatchNorm slab
  * launches, the role-split chain launches and the actor's heads folded into them (hidden_dim % 16 == 0, ac_dim <= 16, num_critics 2,
  * pipeline_steps 2); anything else is refused naming batch_size, hidden_dim, num_critics, pipeline_steps, or the environment switch
- * (GCRL_NO_BN_SLAB, GCRL_NO_SPLIT_ROLES, GCRL_NO_HEADS_FOLD) that takes the path away.  TQC populations are not implemented (kind).
+ * (GCRL_NO_BN_SLAB, GCRL_NO_SPLIT_ROLES, GCRL_NO_HEADS_FOLD) that takes the path away.  These two entries refuse TQC (kind: "TQC
+ * populations are not implemented" by them): TQC populations are created with gcrl_pop_create_layered below.
  * alpha_lr and alpha_min_steps may differ between SAC members like the other rates.
  * gcrl_pop_create promises each member bit for bit a standalone agent, whatever launch forms that agent runs; a SAC population can only
  * promise that against an agent running the same forms (gcrl_pop_forms below), so gcrl_pop_create refuses SAC naming kind and
  * gcrl_pop_create_forms — the same entry for a caller that accepts the qualified guarantee — admits DDPG, TD3 and SAC.
+ * gcrl_pop_create_layered: a population of TQC agents, whose step runs the layer-per-launch schedule (one launch per layer and
+ * direction, the BatchNorm actor's slab launches), not the row chain.  Its guarantee is gcrl_pop_create_forms': each member is bit for
+ * bit a standalone TQC agent running the forms gcrl_pop_forms reports (only bit 1, the row-split slab launches, exists on this schedule:
+ * want[1] = want[2] = 0).  Admitted: kind TQC for every member (anything else is refused naming kind), n_quantiles <= 1 (the
+ * distributional variant: n_quantiles), num_critics 2..8 and shared (num_critics), batch_size <= 512 and hidden_dim % 16 == 0 with the
+ * slab launches on (batch_size, hidden_dim, GCRL_NO_BN_SLAB), use_graph 0 or 1, and the shared fields above; pipeline_steps is whatever a
+ * standalone TQC agent is given (it never selects the row chain for this kind).  top_drop, alpha_lr and alpha_min_steps may differ between
+ * members.  The members act through gcrl_pop_observe_act_bn.
  * gcrl_pop_member: member i as a full agent handle, owned by the population (every gcrl_agent_* entry works on it).
  * gcrl_pop_update_n: gcrl_agent_update_n(member i, rings[i], step0, n, ...) for every member, the members' launches of each
  * stage issued together; each member computes bit for bit what its own gcrl_agent_update_n computes.  Batches are drawn
@@ -368,8 +377,8 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * untouched.  n <= batch_size.  Runs after every member's last update call and on its current weights.  Up to 32 rows per
  * member travel through a pinned, mapped block (one launch, no copy, no stream synchronisation); more rows take staged copies
  * around the same launch.  A SAC population is refused (GCRL_ERR_ARG, naming kind): a BatchNorm actor has no row-chain network;
- * its population acts through gcrl_pop_observe_act_bn.
- * gcrl_pop_observe_act_bn: the same for a population of BatchNorm actors (SAC): one launch of the population form of the members'
+ * its population acts through gcrl_pop_observe_act_bn (so does a TQC population).
+ * gcrl_pop_observe_act_bn: the same for a population of BatchNorm actors (SAC, TQC): one launch of the population form of the members'
  * one-launch acting kernel, on each member's live parameter vector and running statistics.  eps_host [members][n][A] float64 is the
  * rsample eps of every member, or NULL: every member's deterministic action tanh(mean); there are no modes and no skipped members.
  * The other arrays, the row limits, the ordering after the members' update calls, the two forms (pinned block up to 32 rows per
@@ -388,6 +397,7 @@ typedef struct gcrl_pop gcrl_pop;
 typedef struct gcrl_normalizer gcrl_normalizer;   /* (the device RunningNormalizer, declared below) */
 gcrl_pop* gcrl_pop_create(const gcrl_agent_config* cfgs, int32_t members);
 gcrl_pop* gcrl_pop_create_forms(const gcrl_agent_config* cfgs, int32_t members);
+gcrl_pop* gcrl_pop_create_layered(const gcrl_agent_config* cfgs, int32_t members);
 int gcrl_pop_member(gcrl_pop* p, int32_t i, gcrl_agent** out);
 int32_t gcrl_pop_size(const gcrl_pop* p);
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,

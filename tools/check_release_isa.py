@@ -98,7 +98,9 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 
 # kernels the scratch lint reports by name whatever their figure (and misses when they are gone): the population acting launches
 # ... and the BatchNorm actor's acting launches (act_bn.hip)
+# ... and the population forms of the sampling launches a TQC population step issues (ops_sac.hip)
 SCRATCH_NAMED = {"rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"],
+                 "ops_sac.hip": ["tanh_gauss_fwd_pop_kernel", "tanh_gauss_fwd2_pop_kernel", "tanh_gauss_bwd_pop_kernel"],
                  "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel", "act_bn_pop_kernel", "act_bn_pop_staged_kernel"]}
 
 

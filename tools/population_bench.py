@@ -1,8 +1,9 @@
-"""Aggregate update throughput of a DDPG, TD3 or SAC population (src/population.py) against the same P agents stepped one after another
+"""Aggregate update throughput of a DDPG, TD3, SAC or TQC population (src/population.py) against the same P agents stepped one after another
 in the same process.  One JSON line per (shape, P, form):
 
-    python tools/population_bench.py [--kind DDPG|TD3|SAC] [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
+    python tools/population_bench.py [--kind DDPG|TD3|SAC|TQC] [--shapes cfg1,headline] [--members 1,2,4,8] [--calls 50] [--warmup 5] [--out FILE]
     python tools/population_bench.py --kind SAC --shapes cfg5,sac_h64 --update-rounds 5     (both sides alive, timed in alternation: median, min-max)
+    python tools/population_bench.py --kind TQC --members 1,2,4,8 --update-rounds 5           (shapes tqc_h64 and tqc_h256: five critics, two dropped)
 
 Each agent trains from its own HER ring of synthetic episodes, `gradient_step` (40) steps per update call as the trainer does
 (src/env.py:384-385).  Timing: hipEvents on the stream the updates run on, around `calls` calls after `warmup` untimed ones and
@@ -45,13 +46,16 @@ SHAPES = {   # bench.py WORKLOADS: ddpg_reach_b256 (cfg 1) and the ddpg_pickplac
     "headline": dict(S=23, A=4, H=256, L=3, B=256),
     "cfg5": dict(S=28, A=4, H=256, L=3, B=512),      # sac_slide_b512
     "sac_h64": dict(S=10, A=3, H=64, L=3, B=256),
+    "tqc_h64": dict(S=10, A=3, H=64, L=3, B=64),      # --kind TQC's defaults: a small shape and one at H 256 / B 256
+    "tqc_h256": dict(S=28, A=4, H=256, L=3, B=256),
 }
 GSTEP = 40
 
 
 KINDS = {"DDPG": (gcrl_amd.DDPGPopulation, gcrl_amd.DDPG, {}),
          "TD3": (gcrl_amd.TD3Population, gcrl_amd.TD3Agent, dict(ac_update_freq=2, policy_noise=0.2, noise_clamp=0.5)),
-         "SAC": (gcrl_amd.SACPopulation, gcrl_amd.SACAgent, dict(ac_update_freq=2))}
+         "SAC": (gcrl_amd.SACPopulation, gcrl_amd.SACAgent, dict(ac_update_freq=2)),
+         "TQC": (gcrl_amd.TQCPopulation, gcrl_amd.TQCAgent, dict(ac_update_freq=2, num_critics=5, top_quantiles_to_drop=2))}
 
 
 def _cfgs(sh, P, kind="DDPG"):
@@ -314,6 +318,8 @@ def main():
                         f.flush()
         return
     assert a.calls * GSTEP >= 2000 or os.environ.get("POP_BENCH_SHORT"), "at least 2 000 timed steps per member"
+    if a.kind == "TQC" and a.shapes == "cfg1,headline":
+        a.shapes = "tqc_h64,tqc_h256"
     f = open(a.out, "a") if a.out else None
     for shape in a.shapes.split(","):
         for P in [int(x) for x in a.members.split(",")]:
