@@ -8,6 +8,10 @@ agents, each with its own synthetic vector env, HER ring and normalisers, driven
 (over all members) and every member's success rate.
 
     python examples/population_trainer.py --agent DDPG --members 4 --cycles 40
+
+`--pbt N`: population-based training — every N cycles the bottom quarter of the members by success rate `exploit`s the top quarter
+(weights, optimiser state and replay ring, one launch for all pairs) and `explore`s by x0.8 / x1.25 on both learning rates; the
+overwritten slots are printed.  Without the flag the members run to the end as fixed trials.
 """
 import argparse
 import os
@@ -24,7 +28,7 @@ from trainer_standin import PointReachVecEnv  # noqa: E402
 
 
 def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
-          seed=0, verbose=True):
+          seed=0, verbose=True, pbt=0):
     import gcrl_amd
     from gcrl_amd.src.synthetic import agent_config as make_config
     from gcrl_amd.src.utils import DeviceRunningNormalizer
@@ -78,6 +82,20 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
             for info in infos:
                 float(info[-1][0])          # reads one metric per member: waits for the cycle's updates
         t_upd += time.perf_counter() - tu
+        if pbt and cycle % pbt == 0 and members >= 2 and all(len(s) >= max_episode for s in success):
+            # exploit: the bottom quarter takes over the top quarter's state; explore: both learning rates x0.8 or x1.25
+            rate = [float(np.mean(s[-4 * max_episode:])) for s in success]
+            order = sorted(range(members), key=lambda i: (rate[i], i))
+            q = max(1, members // 4)
+            pairs = list(zip(order[::-1][:q], order[:q]))
+            pop.exploit(pairs, copy_ring=True)
+            gen = np.random.default_rng(seed + cycle)
+            for src, dst in pairs:
+                f = float(gen.choice([0.8, 1.25]))
+                c = pop.members[src].config
+                pop.explore(dst, actor_lr=c.actor_lr * f, critic_lr=c.critic_lr * f)
+                success[dst] = list(success[src])
+            print(f"cycle {cycle:4d}  pbt: overwritten slots " + ", ".join(f"{d} <- {s} (success {rate[d]:.2f} <- {rate[s]:.2f}, lr {pop.members[d].config.actor_lr:.2e})" for s, d in pairs))
         if verbose and cycle % 10 == 0:
             print(f"cycle {cycle:4d}  success(last {max_episode} episodes) " + " ".join(f"{np.mean(s[-max_episode:]):.2f}" for s in success))
     return dict(success=[float(np.mean(s[-10 * max_episode:])) for s in success], env_steps=env_steps,
@@ -92,8 +110,9 @@ if __name__ == "__main__":
     ap.add_argument("--cycles", type=int, default=40)
     ap.add_argument("--nenv", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--pbt", type=int, default=0, metavar="N", help="every N cycles the bottom quarter exploits the top quarter and explores (0: off)")
     args = ap.parse_args()
-    out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed)
+    out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, pbt=args.pbt)
     print(f"{args.agent} x {args.members}: success over the last 10 cycles " + " ".join(f"{s:.2f}" for s in out["success"]) +
           f"; {out['env_steps']} env steps in aggregate ({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} "
           f"gradient steps in aggregate ({out['gradient_steps_per_s']:.0f}/s in the update phase), {out['wall_s']:.1f} s; "

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCRL_HIP_LIB") or os.path.join(_HERE, "libgcrl_hip.so")
 
 STREAM_LEGACY = 1  # GCRL_STREAM_LEGACY
+CLONE_AGENT, CLONE_RING = 1, 2  # GCRL_CLONE_AGENT, GCRL_CLONE_RING
 XCHG_HANDLE_BYTES = 256  # GCRL_XCHG_HANDLE_BYTES
 
 
@@ -48,6 +49,15 @@ class AgentConfig(C.Structure):
         ("alpha_min_steps", C.c_double),
         ("device", C.c_int32), ("use_graph", C.c_int32), ("seed", C.c_uint64),
         ("pipeline_steps", C.c_int32), ("n_quantiles", C.c_int32),
+    ]
+
+
+class HParams(C.Structure):
+    _fields_ = [
+        ("actor_lr", C.c_double), ("actor_lr_min", C.c_double), ("critic_lr", C.c_double), ("critic_lr_min", C.c_double),
+        ("ac_scheduler_steps", C.c_int64), ("cr_scheduler_steps", C.c_int64),
+        ("gamma", C.c_double), ("tau", C.c_double), ("grad_clip", C.c_double),
+        ("alpha_lr", C.c_double), ("alpha_min_steps", C.c_double),
     ]
 
 
@@ -137,6 +147,9 @@ PROTOTYPES = {
                                         C.c_int32, C.c_int32, _vp, _vp]),
     "gcrl_pop_acting_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_destroy": (None, [_vp]),
+    "gcrl_pop_clone": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _u32, _vp]),
+    "gcrl_agent_set_hparams": (C.c_int, [_vp, C.POINTER(HParams)]),
+    "gcrl_pop_replace": (C.c_int, [_vp, C.c_int32, C.POINTER(AgentConfig)]),
     "gcrl_agent_update_phase": (C.c_int, [_vp, _vp, _i64, C.c_int, C.POINTER(UpdateInputs), _f32, C.POINTER(_i64), _vp]),
     "gcrl_agent_grad_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_i64)]),
     "gcrl_agent_dp_begin": (C.c_int, [_vp, _vp, _i64, C.c_int, _f32, _vp, _vp, _vp]),

@@ -38,6 +38,7 @@
 #include "sac_heads.h"
 #include "xchg_ipc.h"
 #include "pop.h"
+#include "pbt_host.h"
 
 using namespace gcrl;
 

@@ -38,6 +38,7 @@ struct gcrl_pop {
   std::vector<int64_t> act_ordered;    // per member: its `calls` when the acting stream last waited for its update work
   PopProcStep proc;
   int64_t act_calls = 0, act_launches = 0, act_staged = 0;
+  PopTabCache clone_tabs;              // device segment tables of gcrl_pop_clone (pbt_host.h CloneSeg), by content
 };
 
 namespace {
@@ -56,14 +57,7 @@ struct PopActLayout {
   }
 };
 
-const char* pop_mismatch(const gcrl_agent_config& a, const gcrl_agent_config& b) {
-#define GCRL_POP_SAME(f) if (a.f != b.f) return #f;
-  GCRL_POP_SAME(kind) GCRL_POP_SAME(obs_dim) GCRL_POP_SAME(ac_dim) GCRL_POP_SAME(hidden_dim) GCRL_POP_SAME(layer_count)
-  GCRL_POP_SAME(batch_size) GCRL_POP_SAME(num_critics) GCRL_POP_SAME(gradient_step) GCRL_POP_SAME(ac_update_freq)
-  GCRL_POP_SAME(polyak_every) GCRL_POP_SAME(pipeline_steps) GCRL_POP_SAME(use_graph) GCRL_POP_SAME(device) GCRL_POP_SAME(n_quantiles)
-#undef GCRL_POP_SAME
-  return nullptr;
-}
+// (pop_mismatch — the first field in which two members' configurations may not differ — lives in pbt_host.h)
 
 // device copy of the members' argument structs of one population launch (cached: the same pointers every call)
 int pop_table(gcrl_pop* p, const std::vector<const PopOp*>& ops, hipStream_t st, void** out) {
@@ -699,10 +693,148 @@ int gcrl_pop_acting_counts(const gcrl_pop* p, int64_t* act_calls, int64_t* act_l
   return GCRL_OK;
 }
 
+// ---------------------------------------------------------------- population-based training: clone, re-tune, replace (pbt_host.h)
+
+int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, const int32_t* dst, int32_t pairs, uint32_t what, void* stream) {
+  // every refusal before any device work
+  GCRL_CHECK_ARG(p, "gcrl_pop_clone: pop: null handle");
+  const int P = (int)p->m.size();
+  char why[256];
+  if (!pop_clone_check(P, src, dst, pairs, what, why, sizeof(why))) return fail(GCRL_ERR_ARG, "gcrl_pop_clone: %s", why);
+  const bool with_agent = (what & GCRL_CLONE_AGENT) != 0, with_ring = (what & GCRL_CLONE_RING) != 0;
+  if (with_ring) {
+    GCRL_CHECK_ARG(rings, "gcrl_pop_clone: rings: null array with GCRL_CLONE_RING");
+    for (int k = 0; k < pairs; ++k) {
+      const gcrl_her* s = rings[src[k]];
+      const gcrl_her* d = rings[dst[k]];
+      GCRL_CHECK_ARG(s, "gcrl_pop_clone: rings: member %d has no replay ring", src[k]);
+      GCRL_CHECK_ARG(d, "gcrl_pop_clone: rings: member %d has no replay ring", dst[k]);
+      GCRL_CHECK_ARG(s != d, "gcrl_pop_clone: rings: members %d and %d share a replay ring", src[k], dst[k]);
+#define GCRL_RING_SAME(expr, field) \
+  GCRL_CHECK_ARG(s->expr == d->expr, "gcrl_pop_clone: %s: member %d's ring has %lld, member %d's %lld", field, src[k], (long long)s->expr, dst[k], (long long)d->expr)
+      GCRL_RING_SAME(cfg.capacity, "capacity");
+      GCRL_RING_SAME(S, "state_dim"); GCRL_RING_SAME(A, "action_dim"); GCRL_RING_SAME(G, "goal_dim");
+      GCRL_RING_SAME(RS, "record_floats"); GCRL_RING_SAME(RG, "staged_record_floats");
+      GCRL_RING_SAME(cfg.nenvs, "nenvs"); GCRL_RING_SAME(cfg.flush_len, "flush_len"); GCRL_RING_SAME(cfg.k_future, "k_future");
+#undef GCRL_RING_SAME
+    }
+  }
+  uint32_t involved = 0;
+  for (int k = 0; k < pairs; ++k) involved |= (1u << src[k]) | (1u << dst[k]);
+  for (int i = 0; i < P; ++i)
+    if ((involved >> i) & 1u) GCRL_CHECK_ARG(!p->m[i]->deferred.her, "gcrl_pop_clone: member %d is inside an update call", i);
+  // the segment table: one entry per state allocation and pair (what gcrl_agent_save_state puts in its blob), then the rings' filled parts
+  std::vector<CloneSeg> segs;
+  for (int k = 0; k < pairs; ++k) {
+    gcrl_agent* s = p->m[src[k]];
+    gcrl_agent* d = p->m[dst[k]];
+    if (with_agent) {
+      const unsigned long long bn = (unsigned long long)std::max(1, s->L * s->H) * sizeof(float);
+      clone_add(segs, s->params, d->params, (unsigned long long)s->n_params * sizeof(float));
+      clone_add(segs, s->adam_m, d->adam_m, (unsigned long long)s->n_grads * sizeof(float));
+      clone_add(segs, s->adam_v, d->adam_v, (unsigned long long)s->n_grads * sizeof(float));
+      clone_add(segs, s->bn_rmean, d->bn_rmean, bn);
+      clone_add(segs, s->bn_rvar, d->bn_rvar, bn);
+      clone_add(segs, s->alpha_dev, d->alpha_dev, sizeof(float));
+    }
+    if (with_ring) {
+      const gcrl_her* hs = rings[src[k]];
+      gcrl_her* hd = rings[dst[k]];
+      clone_add(segs, hs->stage, hd->stage, (unsigned long long)hs->cfg.nenvs * hs->cfg.flush_len * hs->RG * sizeof(float));
+      clone_add_ring_rows(segs, hs->ring, hd->ring, hs->head, hs->len, hs->cfg.capacity, hs->RS);
+    }
+  }
+  gcrl_agent* a0 = p->m[0];
+  hipStream_t st = a0->pick(stream);
+  // after the last update call of every member involved (DESIGN.md 4c: the event that closes a handle's update work)
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    if (((involved >> i) & 1u) && a->calls > 0) GCRL_HIP(hipStreamWaitEvent(st, a->call_ev[(a->calls - 1) % kEventRing], 0));
+  }
+  void* tab_dev = nullptr;
+  if (p->clone_tabs.get(segs.data(), segs.size() * sizeof(CloneSeg), st, &tab_dev)) return fail(GCRL_ERR_HIP, "gcrl_pop_clone: segment table upload failed");
+  TRY(launch_pop_clone(st, tab_dev, (int)segs.size(), clone_chunks(segs, 128)));
+  // host state, and the destination's derived state as gcrl_agent_load_state / gcrl_her_load_state leave it
+  for (int k = 0; k < pairs; ++k) {
+    const gcrl_agent* s = p->m[src[k]];
+    gcrl_agent* d = p->m[dst[k]];
+    if (with_agent) {
+      d->t_actor = s->t_actor; d->t_critic = s->t_critic; d->t_alpha = s->t_alpha;
+      d->lr_actor = s->lr_actor; d->lr_critic = s->lr_critic; d->rng_ctr = s->rng_ctr;
+      d->wt_dirty = true;
+    }
+    if (with_ring) {
+      const gcrl_her* hs = rings[src[k]];
+      gcrl_her* hd = rings[dst[k]];
+      hd->staged = hs->staged;
+      hd->head = 0; hd->len = hs->len;
+      hd->episodes_flushed = hs->episodes_flushed; hd->draws_done = hs->draws_done; hd->mutation_epoch = hs->mutation_epoch + 1;
+    }
+  }
+  // the launch closes the work so far of every member involved: a destination's next update, acting or metrics call, and a source's
+  // next write, are ordered after it on whatever stream they run
+  for (int i = 0; i < P; ++i)
+    if ((involved >> i) & 1u) TRY(end_call(p->m[i], st));
+  return GCRL_OK;
+}
+
+int gcrl_agent_set_hparams(gcrl_agent* a, const gcrl_hparams* h) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_set_hparams: agent: null handle");
+  char why[256];
+  if (!hparams_check(h, a->sac, why, sizeof(why))) return fail(GCRL_ERR_ARG, "gcrl_agent_set_hparams: %s", why);
+  GCRL_CHECK_ARG(!a->deferred.her && a->dp_pos >= a->dp_segs.size(), "gcrl_agent_set_hparams: agent: the handle is inside an update call");
+  if (!a->graphs.empty()) {   // captured steps hold the old gamma / tau / clip as kernel arguments
+    GCRL_HIP(hipDeviceSynchronize());
+    for (auto& kv : a->graphs) (void)hipGraphExecDestroy(kv.second);
+    a->graphs.clear();
+  }
+  gcrl_agent_config& c = a->cfg;
+  c.actor_lr = h->actor_lr; c.actor_lr_min = h->actor_lr_min; c.ac_scheduler_steps = h->ac_scheduler_steps;
+  c.critic_lr = h->critic_lr; c.critic_lr_min = h->critic_lr_min; c.cr_scheduler_steps = h->cr_scheduler_steps;
+  c.gamma = h->gamma; c.tau = h->tau; c.grad_clip = h->grad_clip;
+  if (a->sac) { c.alpha_lr = h->alpha_lr; c.alpha_min_steps = h->alpha_min_steps; }
+  // positions kept: the rate an agent constructed with the new schedule holds after the same number of scheduler steps
+  a->lr_actor = cosine_lr_at(c.actor_lr, c.actor_lr_min, c.ac_scheduler_steps, a->t_actor);
+  a->lr_critic = cosine_lr_at(c.critic_lr, c.critic_lr_min, c.cr_scheduler_steps, a->t_critic);
+  return GCRL_OK;
+}
+
+int gcrl_pop_replace(gcrl_pop* p, int32_t i, const gcrl_agent_config* cfg) {
+  // every refusal before any device work
+  GCRL_CHECK_ARG(p, "gcrl_pop_replace: pop: null handle");
+  GCRL_CHECK_ARG(i >= 0 && i < (int32_t)p->m.size(), "gcrl_pop_replace: i: member %d of %d", i, (int)p->m.size());
+  GCRL_CHECK_ARG(cfg, "gcrl_pop_replace: cfg: null config");
+  gcrl_agent* a = p->m[i];
+  // (the member's own configuration holds every shared field of the population, and everything the creating entry checked about shapes)
+  if (const char* f = pop_mismatch(a->cfg, *cfg)) return fail(GCRL_ERR_ARG, "gcrl_pop_replace: %s: the new member must share it with the population", f);
+  if (cfg->kind == GCRL_AGENT_TQC) GCRL_CHECK_ARG(cfg->top_drop >= 0 && cfg->top_drop < cfg->num_critics, "gcrl_pop_replace: top_drop: 0 <= top_drop < num_critics");
+  {   // the re-tunable fields as gcrl_agent_set_hparams takes them
+    const gcrl_hparams h = hparams_of(*cfg);
+    char why[256];
+    if (!hparams_check(&h, a->sac, why, sizeof(why))) return fail(GCRL_ERR_ARG, "gcrl_pop_replace: %s", why);
+  }
+  GCRL_CHECK_ARG(!a->deferred.her && !a->xchg && a->bn_sync.world <= 1, "gcrl_pop_replace: i: member %d is inside an update call or a data-parallel group", i);
+  GCRL_HIP(hipDeviceSynchronize());
+  TRY(meet_check(a));
+  for (auto& kv : a->graphs) (void)hipGraphExecDestroy(kv.second);   // captured steps hold the old gamma / tau / clip as kernel arguments
+  a->graphs.clear();
+  a->cfg = *cfg;
+  a->lr_actor = cfg->actor_lr; a->lr_critic = cfg->critic_lr;
+  a->t_actor = a->t_critic = a->t_alpha = 0;
+  a->rng_ctr = 0;
+  GCRL_HIP(hipMemset(a->adam_m, 0, (size_t)a->n_grads * sizeof(float)));
+  GCRL_HIP(hipMemset(a->adam_v, 0, (size_t)a->n_grads * sizeof(float)));
+  GCRL_HIP(hipMemset(a->grads, 0, (size_t)a->n_grads * sizeof(float)));
+  GCRL_HIP(hipMemset(a->params, 0, (size_t)a->n_params * sizeof(float)));
+  // step counts are zero: the call below takes its construction path (BatchNorm affine and statistics, hard-copied targets, log_alpha)
+  return gcrl_agent_init_weights(a, cfg->seed, 1);
+}
+
 void gcrl_pop_destroy(gcrl_pop* p) {
   if (!p) return;
   for (gcrl_agent* a : p->m) gcrl_agent_destroy(a);   // (synchronises the device)
   p->act_tabs.release();
+  p->clone_tabs.release();
   if (p->act_blk_host) (void)hipHostFree(p->act_blk_host);
   if (p->act_st_host) (void)hipHostFree(p->act_st_host);
   if (p->act_st_dev) (void)hipFree(p->act_st_dev);

@@ -122,6 +122,8 @@ int launch_tanh_gauss_bwd_select_pop(hipStream_t st, const void* tab, int member
 // TQC: member = blockIdx.y (the two-input sampling forward, whose grid uses blockIdx.y for the input: blockIdx.z)
 int launch_tanh_gauss_fwd_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid);
 int launch_tanh_gauss_bwd_pop(hipStream_t st, const void* tab, int members, dim3 grid);
+// gcrl_pop_clone (pop_clone.hip): `tab` is a device array of `segments` CloneSeg (pbt_host.h); grid (chunks, segments)
+int launch_pop_clone(hipStream_t st, const void* tab, int segments, unsigned chunks);
 // admission of the waiting forms for a population of `members`: the two sides of the comparison (cap 0: shared device or the query failed)
 // (*want: `members` times a member's workgroups of the form; *cap: what is resident at once; want 0: the shape does not have the form)
 void bn_slab_pop_row_split_terms(int B, int H, int A, int members, long long* want, long long* cap);

@@ -110,6 +110,39 @@ def native_config(kind: int, obs_dim: int, ac_dim: int, config, gradient_step: i
         seed=0 if seed is None else int(seed))
 
 
+# the fields `set_hyperparameters` (and a population's `explore`) may change on a live agent — the reference's config field names; what a
+# population lets its members differ in (src/population.py SHARED lists the fields it does not)
+HPARAM_FIELDS = ("actor_lr", "actor_lr_min", "critic_lr", "critic_lr_min", "ac_scheduler_steps", "cr_scheduler_steps", "gamma", "tau", "grad_clip")
+HPARAM_FIELDS_SAC = ("alpha_lr", "alpha_min_steps")
+_FIXED_FIELDS = ("hidden_dim", "layer_count", "batch_size", "ac_update_freq", "num_critics")
+
+
+def check_hyperparameters(who: str, sac: bool, hparams: dict):
+    """Refusals of `set_hyperparameters` that must come before any device work: unknown or fixed fields, values that are not
+    numbers, non-positive learning rates.  Raises GcrlError naming the field.  Everything else about the values is the engine's
+    to judge (include/gcrl.h gcrl_agent_set_hparams), which takes gamma, tau and grad_clip as a constructor takes them."""
+    import math
+    allowed = HPARAM_FIELDS + (HPARAM_FIELDS_SAC if sac else ())
+
+    def refuse(field, why):
+        raise _ffi.GcrlError(f"{who}: {field}: {why}")
+    if not hparams:
+        refuse("hparams", "no field given")
+    for k, v in hparams.items():
+        if k in _FIXED_FIELDS:
+            refuse(k, "fixed when the agent is built (it sets shapes and the launch pattern)")
+        if k not in allowed:
+            refuse(k, f"not a hyper-parameter of a live {'SAC / TQC' if sac else 'DDPG / TD3'} agent (one of {', '.join(allowed)})")
+        if k == "grad_clip" and v is None:      # (no clipping, as in the reference's config)
+            continue
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
+            refuse(k, f"{v!r} is not a finite number")
+        if k in ("actor_lr", "critic_lr", "alpha_lr") and v <= 0:
+            refuse(k, f"{v!r}: a learning rate is > 0")
+        if k in ("ac_scheduler_steps", "cr_scheduler_steps") and int(v) != v:
+            refuse(k, f"{v!r}: a scheduler length is an integer")
+
+
 class _EngineAgent:
     KIND_NAME = "DDPG"
     TD_INDEX = {6: 2, 4: 1}  # position of td_error in the tuple, by tuple length
@@ -582,6 +615,31 @@ class _EngineAgent:
                     nz.mean, nz.var = np.array(d["mean"], dtype=dt), np.array(d["var"], dtype=dt)
                     nz.count, nz.clip_range = d["count"], d["clip_range"]
         self._metric_cache.clear()
+
+    def set_hyperparameters(self, **hparams):
+        """Change learning rates (with their minima and scheduler lengths), gamma, tau, grad_clip — SAC / TQC: alpha_lr and
+        alpha_min_steps too — of this live agent, between update calls (include/gcrl.h gcrl_agent_set_hparams).  Field names are the
+        reference config's.  From the next step on the agent computes bit for bit what an agent constructed with the new values
+        computes from the same state; scheduler positions are kept.  `self.config` becomes a copy holding the new values (configs
+        are often shared between agents), so `save_state` and a later `replace` see the truth.  Refusals name the field and come
+        before any device work."""
+        check_hyperparameters(type(self).__name__, self._sac, hparams)
+        self._apply_hyperparameters(hparams)
+
+    def _apply_hyperparameters(self, hparams: dict):
+        """`set_hyperparameters` after its host-side check (a population's `explore` has made it under its own name)."""
+        import copy
+        cfg = copy.copy(self.config)
+        for k, v in hparams.items():
+            setattr(cfg, k, int(v) if k.endswith("scheduler_steps") else v)
+        h = _ffi.HParams(actor_lr=cfg.actor_lr, actor_lr_min=cfg.actor_lr_min, critic_lr=cfg.critic_lr, critic_lr_min=cfg.critic_lr_min,
+                         ac_scheduler_steps=cfg.ac_scheduler_steps, cr_scheduler_steps=cfg.cr_scheduler_steps,
+                         gamma=cfg.gamma, tau=cfg.tau, grad_clip=-1.0 if cfg.grad_clip is None else float(cfg.grad_clip),
+                         alpha_lr=float(getattr(cfg, "alpha_lr", 0.0003)), alpha_min_steps=float(getattr(cfg, "alpha_min_steps", 10000)))
+        _ffi.check(lib.gcrl_agent_set_hparams(self._h, C.byref(h)))
+        self.config = cfg
+        self.gamma, self.tau, self.grad_clip = cfg.gamma, cfg.tau, cfg.grad_clip
+        self.alpha_min_steps = getattr(cfg, "alpha_min_steps", 10000)
 
     def reset(self):
         """Re-initialise Linear layers (src/agent.py:1461-1465, :760-769)."""

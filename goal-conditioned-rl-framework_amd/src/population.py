@@ -20,10 +20,12 @@ import numpy as np
 
 from .. import _ffi
 from .._ffi import lib
-from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, native_config
+from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
 from .buffer import MTStream
 
 MAX_MEMBERS = 16
+MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
+MANIFEST = "population.json"
 
 # fields every member must share (the population runs one launch pattern); the others (seed, gamma, tau, grad_clip, learning
 # rates and their schedules, SAC's alpha_lr and alpha_min_steps, the ring's own settings) may differ
@@ -296,6 +298,189 @@ class _Population:
         want, cap = (C.c_int64 * 3)(), (C.c_int64 * 3)()
         _ffi.check(lib.gcrl_pop_forms_terms(self._pop.h, want, cap))
         return {bit: (int(want[i]), int(cap[i])) for i, bit in enumerate((1, 2, 8))}
+
+
+    # ------------------------------------------------------------------ population-based training: exploit / explore / replace
+    def _check_pairs(self, pairs):
+        """`exploit`'s argument as two index lists; every refusal names the argument and needs no device."""
+        P = len(self.members)
+        try:
+            pairs = [(int(s), int(d)) for s, d in pairs]
+        except (TypeError, ValueError):
+            self._refuse("pairs", "a list of (source, destination) member indices")
+        if not 1 <= len(pairs) <= MAX_PAIRS:
+            self._refuse("pairs", f"{len(pairs)} pairs in one call (1..{MAX_PAIRS})")
+        for s, d in pairs:
+            if not 0 <= s < P:
+                self._refuse("src", f"member {s} of {P}")
+            if not 0 <= d < P:
+                self._refuse("dst", f"member {d} of {P}")
+        dsts = [d for _, d in pairs]
+        for d in dsts:
+            if dsts.count(d) > 1:
+                self._refuse("dst", f"member {d} is a destination twice")
+        both = sorted({s for s, _ in pairs} & set(dsts))
+        if both:
+            self._refuse("dst", f"member {both[0]} is both a source and a destination in one call")
+        return pairs
+
+    def exploit(self, pairs, copy_ring: bool = False):
+        """For every `(src, dst)` of `pairs`, member `dst` takes over member `src`'s training state — parameters and targets, Adam
+        moments, step counts and scheduler positions, BatchNorm statistics, alpha, the device-RNG position — in ONE launch for all
+        pairs and without a host synchronisation (include/gcrl.h gcrl_pop_clone); bit for bit what `src.save_state` followed by
+        `dst.load_state` leaves.  The destination keeps its own config (gamma, tau, grad_clip, the schedules' base and minimum
+        rates and lengths, alpha_lr, seed): change those with `explore`.  On the Python side the destination gets what `load_state`
+        sets: `beta`, the actor's `num_batches_tracked`, an empty metric cache.  With `copy_ring` the replay ring (rows, staged
+        partial episodes, counters) travels in the same launch, an engine-mode index stream is copied, and the observation / goal
+        normalisers' statistics are copied through `set_state` (a host round trip of a few hundred bytes per normaliser, as
+        `load_state` does it — not device to device).  One source may serve several destinations; a member cannot be both in one call."""
+        pairs = self._check_pairs(pairs)
+        ms = self.members
+        P, n = len(ms), len(pairs)
+        rings = None
+        if copy_ring:
+            for s, d in pairs:
+                if ms[s].buffer.handle is None:
+                    self._refuse("copy_ring", f"member {s} has no replay ring yet (nothing was pushed)")
+                ms[d].buffer._ensure(*ms[s].buffer._dims)
+            rings = (C.c_void_p * P)(*[m.buffer.handle for m in ms])
+        src = (C.c_int32 * n)(*[s for s, _ in pairs])
+        dst = (C.c_int32 * n)(*[d for _, d in pairs])
+        what = _ffi.CLONE_AGENT | (_ffi.CLONE_RING if copy_ring else 0)
+        _ffi.check(lib.gcrl_pop_clone(self._pop.h, rings, src, dst, n, what, _ffi.stream_handle()))
+        for s, d in pairs:
+            a, b = ms[s], ms[d]
+            b.beta = a.beta
+            b.actor.num_batches_tracked = int(a.actor.num_batches_tracked)
+            b._metric_cache.clear()
+            if copy_ring:
+                if a.buffer.rng.mode == "engine" and b.buffer.rng.mode == "engine":
+                    _ffi.check(lib.gcrl_mt_get_state(a.buffer.rng.handle, a.buffer.rng._buf))
+                    _ffi.check(lib.gcrl_mt_set_state(b.buffer.rng.handle, a.buffer.rng._buf))
+                for name in ("obs_normalizer", "dg_normalizer"):
+                    za, zb = getattr(a.buffer, name, None), getattr(b.buffer, name, None)
+                    if za is None or zb is None:
+                        continue
+                    mean, var = np.asarray(za.mean), np.asarray(za.var)
+                    f32 = bool(mean.dtype == np.float32)
+                    if hasattr(zb, "set_state"):
+                        zb.set_state(mean.astype(np.float64), var.astype(np.float64), float(za.count), float(za.clip_range), float32=f32)
+                    else:
+                        zb.mean, zb.var = mean.copy(), var.copy()
+                        zb.count, zb.clip_range = float(za.count), float(za.clip_range)
+
+    def explore(self, i: int, **hparams):
+        """`members[i].set_hyperparameters(**hparams)`: new learning rates (minima, scheduler lengths), gamma, tau, grad_clip — SAC /
+        TQC: alpha_lr, alpha_min_steps — for one member of the live population; the others are untouched and no launch form
+        changes.  Fields every member must share (`SHARED`, num_critics) and unknown fields are refused naming the field."""
+        if not 0 <= int(i) < len(self.members):
+            self._refuse("i", f"member {i} of {len(self.members)}")
+        m = self.members[int(i)]
+        check_hyperparameters(type(self).__name__, m._sac, hparams)
+        m._apply_hyperparameters(hparams)
+
+    def _check_replace(self, i, config):
+        if not 0 <= int(i) < len(self.members):
+            self._refuse("i", f"member {i} of {len(self.members)}")
+        cur = self.members[int(i)].config
+        if getattr(config, "buffer_type", "HER") != "HER":
+            self._refuse("buffer_type", f"populations train from HER rings only, got {config.buffer_type!r}")
+        for f in SHARED + (("num_critics",) if self.NUM_CRITICS is None else ()):
+            if getattr(config, f, None) != getattr(cur, f, None):
+                self._refuse(f, f"the new member has {getattr(config, f, None)!r}, the population {getattr(cur, f, None)!r}: members must share shapes")
+        for f in ("max_len", "max_eps_len", "k_future"):
+            if getattr(config, f) != getattr(cur, f):
+                self._refuse(f, f"the new member has {getattr(config, f)!r}, the slot's replay ring {getattr(cur, f)!r}: the ring is kept")
+
+    def replace(self, i: int, config, seed=None):
+        """Member `i` becomes what the population's constructor would have made of `config` / `seed` in that slot: freshly
+        initialised weights, hard-copied targets, zero moments and step counts, initial BatchNorm statistics and log_alpha, a re-keyed
+        device RNG (include/gcrl.h gcrl_pop_replace: in place, nothing of the agent reallocated, the other members and `forms()`
+        unaffected) and fresh Python-side state.  Its replay ring is emptied: the same `HERBuffer` object with its reward function,
+        but the ring's device memory is released here and allocated again by the next push — a fresh ring's counters and device index
+        stream, at the price of one free and one allocation per replacement.  The normalisers stay the same objects (a trainer may hold
+        them) and are reset in place to a new normaliser's statistics.  `config` must agree with the population in `SHARED` (TQC:
+        num_critics too) and with the slot's ring settings; refusals name the field and come before any device work."""
+        self._check_replace(i, config)
+        i = int(i)
+        m = self.members[i]
+        kind = KIND[self.AGENT.KIND_NAME]
+        cfg = self._native_configs(kind, m.obs_dim, m.ac_dim, [config], [seed], m.gradient_step, m.device_index)[0]
+        _ffi.check(lib.gcrl_pop_replace(self._pop.h, i, C.byref(cfg)))
+        m.config = config
+        m.noise_std, m.noise_clamp, m.policy_noise = config.noise_std, config.noise_clamp, config.policy_noise
+        m.gamma, m.tau, m.grad_clip = config.gamma, config.tau, config.grad_clip
+        m.beta = m.beta_start = config.beta
+        m.beta_end = config.beta_end
+        m.alpha_min = getattr(config, "alpha_min", 0.05)
+        m.alpha_min_steps = getattr(config, "alpha_min_steps", 10000)
+        if kind == 3:
+            m.top_quantiles_to_drop = int(getattr(config, "top_quantiles_to_drop", 2))
+        m.actor.num_batches_tracked = 0
+        m._metric_cache.clear()
+        m._live.clear()
+        m._lazy.clear()
+        buf = m.buffer
+        if buf._h is not None:     # an emptied ring is a fresh one: the next push creates it (counters and device index stream at zero)
+            h, buf._h = buf._h, None
+            lib.gcrl_her_destroy(h)
+            buf._dims = buf._reward_cfg = None
+        if buf.rng is not getattr(self, "_shared_rng", None):        # (python mode: one stream for all members, which no member's seed touches)
+            buf.rng.seed_value = 0 if seed is None else int(seed)
+            if buf.rng.mode == "engine":
+                buf.rng.seed(buf.rng.seed_value)
+        for name in ("obs_normalizer", "dg_normalizer"):
+            z = getattr(buf, name, None)
+            if z is None:
+                continue
+            # in place, as a new normaliser starts: mean 0, var 1, count eps, float64 statistics (src/utils.py)
+            size, eps = int(np.asarray(z.mean).shape[0]), float(getattr(z, "eps", 1e-8))
+            if hasattr(z, "set_state"):
+                z.set_state(np.zeros(size), np.ones(size), eps, float32=False)
+            else:
+                z.mean, z.var, z.count = np.zeros(size), np.ones(size), eps
+
+    # ------------------------------------------------------------------ resume state of the whole population
+    def _manifest(self):
+        c0 = self.members[0].config
+        shared = {f: getattr(c0, f) for f in SHARED}
+        if self.NUM_CRITICS is None:
+            shared["num_critics"] = int(self.members[0].num_critics)
+        return dict(kind=self.AGENT.KIND_NAME, members=len(self.members), obs_dim=int(self.members[0].obs_dim), ac_dim=int(self.members[0].ac_dim),
+                    shared=shared)
+
+    def _check_manifest(self, got: dict):
+        """A saved population's manifest against this population: kind, size and shapes, refused before anything is overwritten."""
+        want = self._manifest()
+        for f in ("kind", "members", "obs_dim", "ac_dim"):
+            if got.get(f) != want[f]:
+                self._refuse(f, f"the saved population has {got.get(f)!r}, this one {want[f]!r}")
+        for f, v in want["shared"].items():
+            if got.get("shared", {}).get(f) != v:
+                self._refuse(f, f"the saved population has {got.get('shared', {}).get(f)!r}, this one {v!r}")
+
+    def save_state(self, path: str):
+        """Every member's `save_state` under `path`/member_00 ..., and `population.json` (kind, member count, shared fields)."""
+        import json
+        import os
+        os.makedirs(path, exist_ok=True)
+        for i, m in enumerate(self.members):
+            m.save_state(os.path.join(path, f"member_{i:02d}"))
+        with open(os.path.join(path, MANIFEST), "w") as f:
+            json.dump(self._manifest(), f)
+
+    def load_state(self, path: str):
+        """The members' `load_state` from a directory `save_state` wrote; a population of another kind, size or shape is refused
+        (naming the field) before any member is overwritten."""
+        import json
+        import os
+        with open(os.path.join(path, MANIFEST)) as f:
+            self._check_manifest(json.load(f))
+        for i in range(len(self.members)):
+            if not os.path.isdir(os.path.join(path, f"member_{i:02d}")):
+                self._refuse("members", f"{path} holds no member_{i:02d}")
+        for i, m in enumerate(self.members):
+            m.load_state(os.path.join(path, f"member_{i:02d}"))
 
 
 class DDPGPopulation(_Population):

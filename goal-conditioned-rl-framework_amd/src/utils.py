@@ -103,6 +103,7 @@ class RunningNormalizer:
         self.mean = np.zeros(size)
         self.var = np.ones(size)
         self.count = eps
+        self.eps = eps
         self.clip_range = clip_range
 
     def update(self, x):
@@ -154,6 +155,7 @@ class DeviceRunningNormalizer:
         self._ffi, self._C = _ffi, C
         self.size = int(size)
         self._clip = float(clip_range)
+        self.eps = float(eps)
         self._h = _ffi.check_ptr(_ffi.lib.gcrl_normalizer_create(self.size, self._clip, float(eps), int(device_index)),
                                  "gcrl_normalizer_create")
 

@@ -417,6 +417,53 @@ int gcrl_pop_process_step(gcrl_pop* p, gcrl_her* const* rings, gcrl_normalizer* 
 int gcrl_pop_acting_counts(const gcrl_pop* p, int64_t* act_calls, int64_t* act_launches, int64_t* proc_calls, int64_t* proc_launches,
                            int64_t* act_staged);
 void gcrl_pop_destroy(gcrl_pop* p);
+
+/* Population-based training on a live population (extension: the reference's search driver prunes a trial and starts another,
+ * src/param_search.py; here the slot is reused in place).  Refusals are GCRL_ERR_ARG, name the argument or field and happen before any
+ * device work.
+ * gcrl_pop_clone: for every pair k, member dst[k] receives member src[k]'s training state — ONE launch of pop_clone_kernel for all
+ * pairs, no host synchronisation.  what & GCRL_CLONE_AGENT: everything gcrl_agent_save_state puts in its blob (parameters and targets,
+ * Adam moments, BatchNorm running statistics, alpha, the optimiser step counts, the two current learning rates and the device-RNG
+ * counter); afterwards gcrl_agent_save_state(dst) is byte for byte what gcrl_agent_load_state(dst, blob of src) leaves.  What the blob
+ * does not carry — the configuration: gamma, tau, grad_clip, the schedules' base / minimum rates and lengths, alpha_lr,
+ * alpha_min_steps, seed — stays the destination's own.  what & GCRL_CLONE_RING: rings[members] are the members' replay rings (as
+ * gcrl_pop_update_n takes them; NULL without this bit): rows (the filled part, in logical order from physical row 0), staged partial
+ * episodes, length and counters, bit for bit what gcrl_her_save_state / gcrl_her_load_state leave; rings of another capacity or
+ * record layout are refused naming the field.  The launch is ordered after the last update call of every member involved; it then
+ * closes the work of every member involved — sources too — with the event that closes an update call, so a destination's next
+ * update / acting / get call, and a source's next write, are ordered after the launch on whatever stream they run (ring work: by
+ * `stream`, the stream of the rings' pushes).  No host synchronisation once the segment table of a call is on the device: tables are
+ * cached by content like the other population tables, so a call with new content — new pairs, or with GCRL_CLONE_RING a ring whose
+ * head or length moved, i.e. nearly every ring clone — uploads its table with one allocation and one blocking copy of a few KiB, and
+ * every 64th distinct table frees the cache, which synchronises the device.  A
+ * destination's derived state is invalidated as gcrl_agent_load_state does it.  Refused: an index out of range (src / dst), a member
+ * that is both a source and a destination, a destination listed twice (dst), pairs outside 1..16, an unknown or empty mask (what).  One
+ * source may serve several destinations.
+ * gcrl_agent_set_hparams: between update calls, the fields population members may differ in.  From the next step on the agent computes
+ * bit for bit what an agent CONSTRUCTED with these values computes from the same state (parameters, moments, step counts, RNG
+ * position).  Scheduler positions are kept: the two current rates become the new schedules evaluated at the kept positions
+ * (csrc/lr_sched.cc, the recursion replayed from the new base rate: O(steps taken) host work).  Works on a standalone agent and on a
+ * population member; no launch form changes.  alpha_lr / alpha_min_steps are read for SAC / TQC only.  The creating entries validate
+ * none of these fields, so only what cannot be stepped with is refused, naming the field: a value that is not a number, a learning
+ * rate that is not finite and > 0, a negative minimum, a scheduler length < 1 (grad_clip < 0: no clipping).
+ * gcrl_pop_replace: member i becomes what the creating entry would have made of *cfg in that slot: weights from cfg->seed, targets
+ * hard-copied, moments, step counts and scheduler positions zero, BatchNorm statistics and log_alpha initial, device RNG re-keyed.  cfg
+ * must agree with the population in every shared field, and its rates must be what gcrl_agent_set_hparams accepts (refused naming the
+ * field, member i untouched).  Nothing of the agent is reallocated (the member's replay ring is the caller's: src/population.py); the
+ * other members, the device tables and admission are unaffected; captured graphs of the member are dropped.  Synchronises the device
+ * (it uploads the initial weights from the host). */
+#define GCRL_CLONE_AGENT 1u
+#define GCRL_CLONE_RING 2u
+typedef struct gcrl_hparams {
+  double actor_lr, actor_lr_min, critic_lr, critic_lr_min;
+  int64_t ac_scheduler_steps, cr_scheduler_steps;
+  double gamma, tau;
+  double grad_clip;       /* < 0: no clipping */
+  double alpha_lr, alpha_min_steps;   /* SAC / TQC */
+} gcrl_hparams;
+int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, const int32_t* dst, int32_t pairs, uint32_t what, void* stream);
+int gcrl_agent_set_hparams(gcrl_agent* a, const gcrl_hparams* h);
+int gcrl_pop_replace(gcrl_pop* p, int32_t i, const gcrl_agent_config* cfg);
 /* Metrics of a ticket, in the reference's tuple order, as fp32 (waits for that step only).
  * n = tuple length returned by the update. */
 int gcrl_agent_metrics(gcrl_agent* a, int64_t ticket, double* out_host, int n);

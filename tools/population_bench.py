@@ -24,7 +24,14 @@ configuration: median and min-max of the rounds, in microseconds per vector step
 times a SAC population's `observe_act` alone (process_step is the same merged launch on both sides): the merged launch
 (gcrl_pop_observe_act_bn) against the same population with `MERGE_ACTING_FROM` forced above P (the members' own one-launch entries in
 member order), each side of each round in a fresh child process, the sides alternating; wall clock per call, the Python wrapper
-included.  One JSON line per (shape, P)."""
+included.  One JSON line per (shape, P).
+
+    python tools/population_bench.py --clone [--kinds DDPG,TD3,SAC,TQC] [--shapes cfg1,headline] [--members 4,16] [--rounds 5] [--out profiles/r13_pbt_clone.jsonl]
+
+times `pop.exploit` of a quarter of the members (one launch for all pairs, src/population.py) against the only way the tree had before:
+the members' save_state / load_state round trip through host memory (with the ring: through a file), pair by pair — both in the same
+process on the same population, in alternating rounds; wall clock and device time (events around the calls) per call, median and
+min-max of the rounds, with and without the replay ring, and the bytes the clone moves.  One JSON line per (kind, shape, P, ring)."""
 import argparse
 import json
 import os
@@ -277,8 +284,86 @@ def run_acting_sac(shapes, members, rounds, steps, write):
             write(json.dumps(r))
 
 
+class _AgentStateHeader(__import__("ctypes").Structure):
+    """csrc/agent.hip AgentStateHeader: the head of a gcrl_agent_save_state blob (it says how many floats each state vector holds)"""
+    _c = __import__("ctypes")
+    _fields_ = ([("magic", _c.c_uint32), ("version", _c.c_uint32)] + [(k, _c.c_int32) for k in ("kind", "S", "A", "H", "L", "B", "C", "pad")] +
+                [(k, _c.c_int64) for k in ("n_params", "n_grads", "bn_n", "t_actor", "t_critic", "t_alpha")] +
+                [("lr_actor", _c.c_double), ("lr_critic", _c.c_double), ("rng_ctr", _c.c_uint64)])
+
+
+def _ring_segment_bytes(buf):
+    """bytes of a ring clone's segments (csrc/her_ring.h): [nenvs][flush_len][RG] staged floats and len x RS row floats"""
+    from gcrl_amd.src.buffer import FLUSH_LEN
+    r16 = lambda x, m: (x + m - 1) // m * m
+    S, A, G = buf._dims
+    rw = r16(S + A, 4) + r16(S, 4) + 2
+    return 4 * (buf.nenvs * FLUSH_LEN * r16(rw + G, 16) + len(buf) * r16(rw, 16))
+
+
+def run_clone(shape, P, kind, rounds, reps, tmp):
+    import ctypes as C
+    from gcrl_amd._ffi import check, lib
+    sh = SHAPES[shape]
+    pop_cls = KINDS[kind][0]
+    pop = pop_cls(sh["S"], sh["A"], _cfgs(sh, P, kind), 2, GSTEP, rng="engine", seeds=list(range(7, 7 + P)))
+    for i, m in enumerate(pop.members):
+        _fill(m, sh, i)
+    pop.update_many(1, GSTEP)
+    q = max(1, P // 4)
+    pairs = [(i, P - 1 - i) for i in range(q)]
+    n = int(lib.gcrl_agent_state_size(pop.members[0]._h))
+    blob = np.empty(n, np.uint8)
+    check(lib.gcrl_agent_save_state(pop.members[0]._h, blob.ctypes.data, n))
+    hdr = _AgentStateHeader.from_buffer_copy(blob[:C.sizeof(_AgentStateHeader)].tobytes())
+    agent_bytes = 4 * (hdr.n_params + 2 * hdr.n_grads + 2 * hdr.bn_n + 1)
+    assert agent_bytes == n - C.sizeof(_AgentStateHeader), (agent_bytes, n)
+    out = []
+    for ring in (False, True):
+        def clone():
+            pop.exploit(pairs, copy_ring=ring)
+
+        def host():
+            for s, d in pairs:
+                if ring:
+                    pop.members[s].save_state(os.path.join(tmp, "m"))
+                    pop.members[d].load_state(os.path.join(tmp, "m"))
+                else:
+                    check(lib.gcrl_agent_save_state(pop.members[s]._h, blob.ctypes.data, n))
+                    check(lib.gcrl_agent_load_state(pop.members[d]._h, blob.ctypes.data, n))
+        res = {"clone": ([], []), "host": ([], [])}
+        clone(); host()
+        for _ in range(rounds):
+            for name, fn in (("clone", clone), ("host", host)):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                res[name][0].append((time.perf_counter() - t0) / reps * 1e6)
+                res[name][1].append(e0.elapsed_time(e1) / reps * 1e3)
+        # what the kernel's segments hold: per pair the agent's state vectors (the named vectors the blob carries: parameters with their
+        # targets, both Adam moments, BatchNorm running statistics, alpha), with the ring the staged records and the filled rows
+        moved = q * agent_bytes + (q * _ring_segment_bytes(pop.members[0].buffer) if ring else 0)
+        r = dict(bench="clone", kind=kind, shape=shape, members=P, pairs=q, ring=ring, rounds=rounds, calls_per_round=reps, bytes_moved=int(moved),
+                 **{k: sh[k] for k in ("S", "A", "H", "L", "B")})
+        for name in ("clone", "host"):
+            for j, what in enumerate(("wall_us", "dev_us")):
+                v = sorted(res[name][j])
+                r[f"{name}_{what}"] = dict(median=round(float(np.median(v)), 2), min=round(v[0], 2), max=round(v[-1], 2))
+        r["ranges_overlap_wall"] = not (r["clone_wall_us"]["max"] < r["host_wall_us"]["min"] or r["host_wall_us"]["max"] < r["clone_wall_us"]["min"])
+        out.append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clone", action="store_true", help="time pop.exploit against the members' save_state / load_state round trip")
+    ap.add_argument("--kinds", default="DDPG,TD3,SAC,TQC", help="--clone: the kinds to time")
+    ap.add_argument("--reps", type=int, default=10, help="--clone: calls per round and side")
     ap.add_argument("--child", default=None, choices=["merged", "members"], help="(internal) --kind SAC --acting: one side of one round in this process")
     ap.add_argument("--kind", default="DDPG", choices=sorted(KINDS))
     ap.add_argument("--update-rounds", type=int, default=1, help="> 1: population and sequential agents timed in alternation this many times")
@@ -291,6 +376,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=3000, help="--acting: vector steps per round and side")
     a = ap.parse_args()
+    if a.clone:
+        import tempfile
+        members = "4,16" if a.members == "1,2,4,8" else a.members
+        with tempfile.TemporaryDirectory() as tmp, (open(a.out, "a") if a.out else open(os.devnull, "w")) as f:
+            for kind in a.kinds.split(","):
+                for shape in a.shapes.split(","):
+                    for P in [int(x) for x in members.split(",")]:
+                        for r in run_clone(shape, P, kind, a.rounds, a.reps, tmp):
+                            line = json.dumps(r)
+                            print(line, flush=True)
+                            f.write(line + "\n")
+                            f.flush()
+        return
     if a.acting:
         assert a.rounds >= 5 and a.steps >= 3000 or os.environ.get("POP_BENCH_SHORT"), "at least five rounds of 3 000 vector steps"
         members = "1,2,4,8,16" if a.members == "1,2,4,8" else a.members
