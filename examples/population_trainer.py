@@ -12,6 +12,9 @@ agents, each with its own synthetic vector env, HER ring and normalisers, driven
 `--pbt N`: population-based training — every N cycles the bottom quarter of the members by success rate `exploit`s the top quarter
 (weights, optimiser state and replay ring, one launch for all pairs) and `explore`s by x0.8 / x1.25 on both learning rates; the
 overwritten slots are printed.  Without the flag the members run to the end as fixed trials.
+
+`--shared-ring`: the members learn from ONE replay ring (and one pair of normalisers) that all their envs fill — every member sees the
+experience every member collects; with `--pbt` an exploit then copies weights and optimiser state only (there is no ring to copy).
 """
 import argparse
 import os
@@ -28,7 +31,7 @@ from trainer_standin import PointReachVecEnv  # noqa: E402
 
 
 def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
-          seed=0, verbose=True, pbt=0):
+          seed=0, verbose=True, pbt=0, shared_ring=False):
     import gcrl_amd
     from gcrl_amd.src.synthetic import agent_config as make_config
     from gcrl_amd.src.utils import DeviceRunningNormalizer
@@ -42,8 +45,10 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
                         ac_update_freq=1 if agent_name == "DDPG" else 2, policy_noise=0.2 if agent_name == "TD3" else 0.0)
             for i in range(members)]
     cls = dict(DDPG=gcrl_amd.DDPGPopulation, TD3=gcrl_amd.TD3Population, SAC=gcrl_amd.SACPopulation, TQC=gcrl_amd.TQCPopulation)[agent_name]
-    pop = cls(e0.obs_dim + e0.goal_dim, e0.ac_dim, cfgs, num_envs, gradient_step, rng="engine", seeds=[seed + i for i in range(members)])
-    for m, env in zip(pop.members, envs):   # what GoalEnvHER.__init__ injects (src/env.py:93-105), device normalisers
+    pop = cls(e0.obs_dim + e0.goal_dim, e0.ac_dim, cfgs, num_envs, gradient_step, rng="engine", seeds=[seed + i for i in range(members)],
+              shared_ring=shared_ring)
+    # (shared_ring: every member's .buffer is the one ring: its normalisers and reward are set once)
+    for m, env in zip(pop.members[:1] if shared_ring else pop.members, envs):   # what GoalEnvHER.__init__ injects (src/env.py:93-105), device normalisers
         m.buffer.obs_normalizer = DeviceRunningNormalizer(env.obs_dim)
         m.buffer.dg_normalizer = DeviceRunningNormalizer(env.goal_dim)
         m.buffer.compute_reward = env.compute_reward
@@ -88,7 +93,7 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
             order = sorted(range(members), key=lambda i: (rate[i], i))
             q = max(1, members // 4)
             pairs = list(zip(order[::-1][:q], order[:q]))
-            pop.exploit(pairs, copy_ring=True)
+            pop.exploit(pairs, copy_ring=not shared_ring)
             gen = np.random.default_rng(seed + cycle)
             for src, dst in pairs:
                 f = float(gen.choice([0.8, 1.25]))
@@ -111,8 +116,10 @@ if __name__ == "__main__":
     ap.add_argument("--nenv", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--pbt", type=int, default=0, metavar="N", help="every N cycles the bottom quarter exploits the top quarter and explores (0: off)")
+    ap.add_argument("--shared-ring", action="store_true", help="all members learn from one replay ring that all their envs fill")
     args = ap.parse_args()
-    out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, pbt=args.pbt)
+    out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, pbt=args.pbt,
+                shared_ring=args.shared_ring)
     print(f"{args.agent} x {args.members}: success over the last 10 cycles " + " ".join(f"{s:.2f}" for s in out["success"]) +
           f"; {out['env_steps']} env steps in aggregate ({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} "
           f"gradient steps in aggregate ({out['gradient_steps_per_s']:.0f}/s in the update phase), {out['wall_s']:.1f} s; "

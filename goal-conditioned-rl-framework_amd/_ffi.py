@@ -139,6 +139,8 @@ PROTOTYPES = {
     "gcrl_pop_size": (C.c_int32, [_vp]),
     "gcrl_pop_update_n": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
     "gcrl_pop_launch_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_pop_set_gather_merge": (C.c_int, [_vp, C.c_int32]),
+    "gcrl_pop_gather_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_forms": (C.c_int, [_vp]),
     "gcrl_pop_forms_terms": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_pop_observe_act": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),

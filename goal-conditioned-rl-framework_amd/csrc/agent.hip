@@ -1144,10 +1144,25 @@ int finish_deferred_draw(gcrl_agent* a, hipStream_t st) {
                            a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st);
 }
 
+// begin_call in two parts.  begin_call_plan consumes the tickets and the upload slot, plans the steps, draws the indices into the
+// pinned block and says — as a CallGather — what the call's first gather is; begin_call_issue uploads and launches it.  A single
+// agent runs the two back to back; gcrl_pop_update_n plans every member in member order (the rings' index streams), then issues
+// all members' gathers as one population launch (begin_call_issue_pop).
+struct CallGather {
+  bool injected = false;
+  bool head_form = false;      // the gather reads its indices from the pinned block and carries the control block as a side copy
+  bool host_idx = false;
+  int slot = 0;
+  UploadBlock* ub = nullptr;
+  const uint32_t* idx_pinned = nullptr;
+  size_t bytes = 0, cb_bytes = 0;
+  GatherCall g;                // idx / cp_* are filled by the issue, by the form it takes
+};
+
 int order_after_other_handles(gcrl_agent* a, hipStream_t st);
-int begin_call(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_update_inputs* in, float grad_scale,
-               hipStream_t st, std::vector<StepPlan>& plans, int64_t* tickets, int32_t* lens, bool defer_rest = false,
-               bool pre_advanced = false) {
+int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_update_inputs* in, float grad_scale,
+                    hipStream_t st, std::vector<StepPlan>& plans, int64_t* tickets, int32_t* lens, bool defer_rest,
+                    bool pre_advanced, CallGather* cg) {
   TRY(finish_deferred_draw(a, st));   // (never pending here; cheap safety)
   TRY(order_after_other_handles(a, st));
   GCRL_CHECK_ARG(n >= 1 && n <= kMaxStepsPerCall && n <= a->Mmax, "update: n=%d steps per call (max %d)", n, std::min(kMaxStepsPerCall, a->Mmax));
@@ -1198,21 +1213,83 @@ int begin_call(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_up
   }
   const bool host_idx = !injected && !(device_rng && !explicit_idx);
   const int64_t rows_now = (int64_t)(a->deferred.her ? a->deferred.next : n) * a->B;
-  if (!injected && (!host_idx || rows_now <= (int64_t)a->head_batches * a->B)) {
-    // One launch starts the call: the gather reads its (<= 2 B) indices straight from the pinned block and carries the
-    // control block to the device (header + the n table entries in use) — before, two staged copies and their launch
-    // gaps (19 us) preceded the first gather.
-    const size_t cb_bytes = (offsetof(UploadBlock, cb) + offsetof(CtrlBlock, table) + (size_t)n * sizeof(StepCtrl) + 15) & ~(size_t)15;
-    TRY(her_gather_update(her, host_idx ? idx : nullptr, rows_now, a->sa, a->nsa, a->rowchain ? nullptr : a->spa, a->ldx, a->rbuf,
-                          a->dbuf, st, ub, a->upload_dev, cb_bytes));
-    GCRL_HIP(hipEventRecord(a->upload_ev[slot], st));
+  cg->injected = injected;
+  cg->host_idx = host_idx;
+  cg->slot = slot;
+  cg->ub = ub;
+  cg->idx_pinned = idx;
+  cg->bytes = bytes;
+  // One launch starts the call: the gather reads its (<= 2 B) indices straight from the pinned block and carries the
+  // control block to the device (header + the n table entries in use) — before, two staged copies and their launch
+  // gaps (19 us) preceded the first gather.
+  cg->head_form = !injected && (!host_idx || rows_now <= (int64_t)a->head_batches * a->B);
+  cg->cb_bytes = (offsetof(UploadBlock, cb) + offsetof(CtrlBlock, table) + (size_t)n * sizeof(StepCtrl) + 15) & ~(size_t)15;
+  GatherCall& g = cg->g;
+  g = GatherCall{};
+  g.h = her;
+  if (!injected) g.gen = her->last_gen;   // (device-RNG mode: this member's draws, also when other members share the ring)
+  g.n = rows_now;
+  g.sa = a->sa; g.nsa = a->nsa; g.spa = a->rowchain ? nullptr : a->spa; g.ldx = a->ldx; g.r = a->rbuf; g.d = a->dbuf;
+  return GCRL_OK;
+}
+
+// the form a planned gather takes: head (indices in the pinned block, control block as a side copy) or main (both uploaded before)
+void call_gather_form(gcrl_agent* a, CallGather* cg, bool head) {
+  GatherCall& g = cg->g;
+  g.idx = !cg->host_idx ? nullptr : (head ? cg->idx_pinned : a->idx_dev());
+  g.cp_src = head ? cg->ub : nullptr;
+  g.cp_dst = head ? a->upload_dev : nullptr;
+  g.cp_bytes = head ? cg->cb_bytes : 0;
+}
+
+int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
+  const GatherCall& g = cg->g;
+  call_gather_form(a, cg, cg->head_form);
+  if (cg->head_form) {
+    TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes));
+    GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
   } else {
-    GCRL_HIP(hipMemcpyAsync(a->upload_dev, ub, bytes, hipMemcpyHostToDevice, st));
-    GCRL_HIP(hipEventRecord(a->upload_ev[slot], st));
-    if (!injected)
-      TRY(her_gather_update(her, host_idx ? a->idx_dev() : nullptr, rows_now, a->sa, a->nsa, a->rowchain ? nullptr : a->spa, a->ldx,
-                            a->rbuf, a->dbuf, st));
+    GCRL_HIP(hipMemcpyAsync(a->upload_dev, cg->ub, cg->bytes, hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
+    if (!cg->injected) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st));
   }
+  return GCRL_OK;
+}
+
+int begin_call(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_update_inputs* in, float grad_scale,
+               hipStream_t st, std::vector<StepPlan>& plans, int64_t* tickets, int32_t* lens, bool defer_rest = false,
+               bool pre_advanced = false) {
+  CallGather cg;
+  TRY(begin_call_plan(a, her, step0, n, in, grad_scale, st, plans, tickets, lens, defer_rest, pre_advanced, &cg));
+  return begin_call_issue(a, &cg, st);
+}
+
+// The planned gathers of P population members (none injected) as one launch: the head form where every member would take it on
+// its own, otherwise every member's upload followed by one merged main gather.  upload_ev per member as in begin_call_issue.
+// merge == false (gcrl_pop_set_gather_merge): each member's own begin_call_issue, in member order.
+int begin_call_issue_pop(gcrl_agent* const* m, CallGather* cg, int P, bool merge, hipStream_t st, bool* merged) {
+  *merged = false;
+  if (!merge || P < 2) {
+    for (int i = 0; i < P; ++i) {
+      cg[i].g.h->last_gen = cg[i].g.gen;   // (a shared ring: the launch reads the generator of this member's turn)
+      TRY(begin_call_issue(m[i], &cg[i], st));
+    }
+    return GCRL_OK;
+  }
+  bool head = true;
+  for (int i = 0; i < P; ++i) head = head && cg[i].head_form;
+  GatherCall calls[kGatherPopMax];
+  for (int i = 0; i < P; ++i) {
+    call_gather_form(m[i], &cg[i], head);
+    calls[i] = cg[i].g;
+    if (!head) {
+      GCRL_HIP(hipMemcpyAsync(m[i]->upload_dev, cg[i].ub, cg[i].bytes, hipMemcpyHostToDevice, st));
+      GCRL_HIP(hipEventRecord(m[i]->upload_ev[cg[i].slot], st));
+    }
+  }
+  TRY(her_gather_update_pop(calls, P, st, merged));
+  if (head)
+    for (int i = 0; i < P; ++i) GCRL_HIP(hipEventRecord(m[i]->upload_ev[cg[i].slot], st));
   return GCRL_OK;
 }
 

@@ -28,6 +28,9 @@ struct gcrl_pop {
   long long want[3] = {0, 0, 0}, cap[3] = {0, 0, 0};
   bool no_waits = false;               // GCRL_POP_NO_WAITS=1 at creation: the population admits no waiting form (A/B knob)
   int64_t merged = 0, alone = 0;       // recorded positions issued as one population launch / member by member (gcrl_pop_launch_counts)
+  // replay side of an update call (gcrl_pop_set_gather_merge, gcrl_pop_gather_counts): the members' gathers as one population launch
+  bool gather_merge = false;
+  int64_t upd_calls = 0, gather_merged = 0, gather_alone = 0;
   // acting side (gcrl_pop_observe_act, gcrl_pop_observe_act_bn, gcrl_pop_process_step; counts: gcrl_pop_acting_counts)
   PopTabCache act_tabs;                // device tables of the members' RowActArgs (SAC: ActBnArgs)
   // fast form: one pinned, mapped block [noise | actions | flags | rows] for kPopActRows rows per member (rowchain.h RowActPop)
@@ -335,6 +338,20 @@ int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone) {
   return GCRL_OK;
 }
 
+int gcrl_pop_set_gather_merge(gcrl_pop* p, int32_t on) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_set_gather_merge: pop: null handle");
+  p->gather_merge = on != 0;
+  return GCRL_OK;
+}
+
+int gcrl_pop_gather_counts(const gcrl_pop* p, int64_t* calls, int64_t* merged, int64_t* alone) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_gather_counts: pop: null handle");
+  if (calls) *calls = p->upd_calls;
+  if (merged) *merged = p->gather_merged;
+  if (alone) *alone = p->gather_alone;
+  return GCRL_OK;
+}
+
 int gcrl_pop_forms(gcrl_pop* p) {
   GCRL_CHECK_ARG(p, "gcrl_pop_forms: pop: null handle");
   return pop_forms_now(p);
@@ -356,7 +373,8 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
     GCRL_CHECK_ARG(rings[i], "gcrl_pop_update_n: member %d has no replay ring", i);
     GCRL_CHECK_ARG(!a->xchg && a->bn_sync.world <= 1, "gcrl_pop_update_n: member %d is in a data-parallel group", i);
     GCRL_CHECK_ARG(!a->prof, "gcrl_pop_update_n: member %d has launch profiling on", i);
-    for (int j = 0; j < i; ++j) GCRL_CHECK_ARG(rings[j] != rings[i], "gcrl_pop_update_n: members %d and %d share a replay ring", j, i);
+    // (members may share a ring: its index stream — the ring's generator, or draws_done in device-RNG mode — is then consumed in
+    // member order, as by standalone agents that share the ring and are called in that order)
     // a process that arrived on this device after the handle was built: the forms with waits go off (as gcrl_agent_update_n)
     if ((a->calls & 31) == 0 && !meet_device_shared()) { const int rc = gcrl_agent_get_meetings(a); if (rc < 0) return rc; }
   }
@@ -383,13 +401,21 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
   for (int done = 0; done < n; done += chunk) {
     const int m = std::min(chunk, n - done);
     std::vector<std::vector<StepPlan>> plans(P);
-    // every member's batches first (their rings' index streams in member order), each gathered by its ring
+    // every member's batches first (their rings' index streams in member order), then the gathers: one population launch for all
+    // members' rings, or — gather_merge off — each member's own launch
+    CallGather cgs[kMaxPopMembers];
     for (int i = 0; i < P; ++i) {
       gcrl_agent* a = p->m[i];
       if (a->wt_dirty) TRY(rc_rebuild_wt(a, st));
-      TRY(begin_call(a, rings[i], step0 + done, m, nullptr, 1.0f, st, plans[i], tickets_out ? tickets_out + (size_t)i * n + done : nullptr,
-                     tuple_len_out ? tuple_len_out + (size_t)i * n + done : nullptr, /*defer_rest=*/false, /*pre_advanced=*/!tqc || pop_layer_adv(a)));
+      TRY(begin_call_plan(a, rings[i], step0 + done, m, nullptr, 1.0f, st, plans[i], tickets_out ? tickets_out + (size_t)i * n + done : nullptr,
+                          tuple_len_out ? tuple_len_out + (size_t)i * n + done : nullptr, /*defer_rest=*/false, /*pre_advanced=*/!tqc || pop_layer_adv(a),
+                          &cgs[i]));
     }
+    bool one = false;
+    TRY(begin_call_issue_pop(p->m.data(), cgs, P, p->gather_merge, st, &one));
+    p->upd_calls++;
+    if (one) p->gather_merged++;
+    else p->gather_alone += P;
     int rc = GCRL_OK;
     for (int i = 0; i < P && !rc; ++i) {
       gcrl_agent* a = p->m[i];

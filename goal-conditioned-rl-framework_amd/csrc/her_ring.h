@@ -174,6 +174,26 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src = nullptr,
                       void* cp_dst = nullptr, size_t cp_bytes = 0);
 
+// One her_gather_update call stated before it is issued (the update engine's begin_call plans it, gcrl_pop_update_n issues the
+// members' calls together).  `gen` is the ring's IdxGen as of the member's turn: members that share a ring each keep their own.
+struct GatherCall {
+  gcrl_her* h = nullptr;
+  const uint32_t* idx = nullptr;
+  IdxGen gen{};
+  int64_t n = 0;
+  float *sa = nullptr, *nsa = nullptr, *spa = nullptr;
+  int ldx = 0;
+  float *r = nullptr, *d = nullptr;
+  const void* cp_src = nullptr; void* cp_dst = nullptr; size_t cp_bytes = 0;
+};
+constexpr int kGatherPopMax = 16;   // members of one population gather launch (their argument records travel by value)
+
+// The gathers of P members as ONE her_gather_update_pop_kernel launch (grid (ceil(rows / 64), P), member = blockIdx.y; the head
+// form when any member carries a side copy); given the same indices, bit for bit the members' own her_gather_update launches.
+// *merged says whether that launch was issued: with P == 1, unequal record layouts, a ring with gather timing on or the
+// development gather variants, the members' own launches run in member order instead.
+int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merged);
+
 // gcrl_pop_process_step (her_ring.hip): one vector-env step of `members` rings as ONE her_process_step_pop_kernel launch (workgroup m =
 // member m), then each ring's finish_vector_step in member order.  The members' raw rows and payloads travel in a pinned, mapped block
 // the kernel reads directly (no staged copy): kSlots slots used in rotation, each guarded by an event recorded after its launch — nothing

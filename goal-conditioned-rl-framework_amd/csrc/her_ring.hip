@@ -460,72 +460,26 @@ __device__ inline void store4_nt(float* p, float4 v) {
 // control-block side copy) from a cycle's main gather.
 template <bool kHead, bool kNT = true>
 __global__ __launch_bounds__(256) void her_gather_update_kernel(GatherUpdArgs p) {
-  extern __shared__ float gather_lds[];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int sub = lane >> 4, v4 = lane & 15;
-  if (kHead)
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < p.cp_n16; i += gridDim.x * 256) p.cp_dst[i] = p.cp_src[i];
-  const int SA4 = p.SA4, S4 = p.S4, o_r = SA4 + S4;
-  const int nq = 4 * SA4;                                   // 16-byte quads of a [16][SA4] tile
-  float* tile = gather_lds + (size_t)w * (8 * nq + 32);     // [sa 16 x SA4 | nsa 16 x SA4 | r 16 | d 16]
-  float* t_ns = tile + 4 * nq;
-  float* t_rd = tile + 8 * nq;
-  const long long r0 = ((long long)blockIdx.x * 4 + w) * 16;
-  if (r0 >= p.n) return;
-  uint32_t ph32 = 0;
-  if (lane < 16 && r0 + lane < p.n) {
-    unsigned long long phys = (unsigned long long)p.head + (p.idx ? p.idx[r0 + lane] : gcrl::idxgen_at(p.gen, r0 + lane));
-    if (phys >= (unsigned long long)p.cap) phys -= (unsigned long long)p.cap;    // head, index < cap
-    ph32 = (uint32_t)phys;
-  }
-  const bool full = r0 + 16 <= p.n;
-  // records wider than 64 floats (state dims above ~28) take further 64-float column passes
-  for (int cc = 0; cc <= o_r; cc += 64) {
-    const int c0 = cc + v4 * 4;
-    const bool useful = c0 <= o_r;
-    float4 val[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t ph = __shfl(ph32, u * 4 + sub, 64);
-      val[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (useful && r0 + u * 4 + sub < p.n) val[u] = *reinterpret_cast<const float4*>(p.ring + (size_t)ph * p.RS + c0);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int rl = u * 4 + sub;
-      const long long row = r0 + rl;
-      if (!useful || row >= p.n) continue;
-      if (p.spa && c0 < S4) *reinterpret_cast<float4*>(p.spa + row * p.ldx + c0) = val[u];   // layer-per-launch schedules only
-      if (full) {
-        if (c0 < SA4) *reinterpret_cast<float4*>(tile + rl * SA4 + c0) = val[u];
-        else if (c0 < o_r) *reinterpret_cast<float4*>(t_ns + rl * SA4 + (c0 - SA4)) = val[u];
-        else { t_rd[rl] = val[u].x; t_rd[16 + rl] = val[u].y; }
-      } else {   // the launch's last, partial wave: straight from the load lanes
-        if (c0 < SA4) *reinterpret_cast<float4*>(p.sa + row * p.ldx + c0) = val[u];
-        else if (c0 < o_r) *reinterpret_cast<float4*>(p.nsa + row * p.ldx + (c0 - SA4)) = val[u];
-        else { p.r[row] = val[u].x; p.d[row] = val[u].y; }
-      }
-    }
-  }
-  if (!full) return;
-  const int zq = (SA4 - S4) >> 2;          // quads of an nsa row beyond the record's ns group (<= 5: action_dim <= 16)
-  if (v4 < zq) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) *reinterpret_cast<float4*>(t_ns + (u * 4 + sub) * SA4 + S4 + v4 * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  // the tile is private to this wave and a wave's LDS operations execute in order: no barrier, only the compiler is held back
-  __builtin_amdgcn_wave_barrier();
-  float* sa = p.sa + r0 * p.ldx;
-  float* nsa = p.nsa + r0 * p.ldx;
-  const bool rd_vec = ((reinterpret_cast<size_t>(p.r) | reinterpret_cast<size_t>(p.d)) & 15) == 0;
-  const int Q = 2 * nq + (rd_vec ? 8 : 0);
-  for (int q = lane; q < Q; q += 64) {
-    const float4 v = *reinterpret_cast<const float4*>(tile + q * 4);
-    float* dst = q < nq ? sa + q * 4 : q < 2 * nq ? nsa + (q - nq) * 4 : q < 2 * nq + 4 ? p.r + r0 + (q - 2 * nq) * 4 : p.d + r0 + (q - 2 * nq - 4) * 4;
-    if (kNT) store4_nt(dst, v);
-    else *reinterpret_cast<float4*>(dst) = v;
-  }
-  if (!rd_vec && lane < 32) (lane < 16 ? p.r : p.d)[r0 + (lane & 15)] = t_rd[lane];
+#include "her_gather_update_body.inc"
+}
+
+// Population form (gcrl_pop_update_n): grid (ceil(rows / 64), P), member = blockIdx.y, each member's own GatherUpdArgs — its ring
+// (or the ring all members share), head, capacity, indices or IdxGen, batch matrices and, in the head form, the side copy of its
+// control block.  The P entries travel BY VALUE in the kernel-argument block (16 x 152 B = 2432 of the 4096 bytes): they change
+// on every call (the upload slot rotates, head and length move with the pushes), so a device table would cost a copy per call.
+// The member's entry is copied into a local struct before anything else: a uniform address with nothing stored yet, so it arrives
+// by scalar loads and lives in scalar registers like the single-agent kernel's argument.  No scratch, no waits, no
+// atomics; blocks past a member's rows, and a member with nothing to gather, exit at once.
+struct GatherUpdPopArgs {
+  GatherUpdArgs m[gcrl::kGatherPopMax];
+};
+
+template <bool kHead>
+__global__ __launch_bounds__(256) void her_gather_update_pop_kernel(GatherUpdPopArgs pp) {
+  constexpr bool kNT = true;
+  const GatherUpdArgs p = pp.m[blockIdx.y];
+  if (p.n <= 0) return;
+#include "her_gather_update_body.inc"
 }
 
 // round 2's form of the same gather (per-lane index loads, stores straight from the load lanes), kept for same-box A/B runs:
@@ -797,6 +751,48 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
   else hipLaunchKernelGGL(her_gather_update_kernel<false>, dim3(blocks), dim3(256), lds, st, ga);
   GCRL_HIP(hipGetLastError());
   return prof_end(h, st, n);
+}
+
+int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merged) {
+  if (merged) *merged = false;
+  if (P < 1 || P > kGatherPopMax) return fail(GCRL_ERR_ARG, "her_gather_update_pop: %d members (1..%d)", P, kGatherPopMax);
+  static const bool dev_variant = std::getenv("GCRL_GATHER_R2") || std::getenv("GCRL_GATHER_PLAIN");   // development A/B knobs: the members' own launches
+  bool one = P >= 2 && !dev_variant;
+  for (int i = 0; i < P; ++i) {
+    const GatherCall& g = c[i];
+    if (g.cp_bytes % 16 != 0 || (g.cp_bytes && (!g.cp_src || !g.cp_dst))) return fail(GCRL_ERR_ARG, "her_gather_update_pop: member %d: bad side copy (%zu bytes)", i, g.cp_bytes);
+    if (g.ldx != g.h->SA4) return fail(GCRL_ERR_ARG, "her_gather_update_pop: member %d: batch row stride %d != roundup(S+A,4) = %d", i, g.ldx, g.h->SA4);
+    // one x extent and one LDS tile for all: equal record layouts; a ring that times its gather launches keeps its own launch
+    one = one && !g.h->prof && g.h->SA4 == c[0].h->SA4 && g.h->S4 == c[0].h->S4 && g.h->RS == c[0].h->RS;
+  }
+  if (!one) {
+    for (int i = 0; i < P; ++i) {
+      const GatherCall& g = c[i];
+      g.h->last_gen = g.gen;   // (members sharing a ring: each launch computes its own member's draws)
+      if (int rc = her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes)) return rc;
+    }
+    return GCRL_OK;
+  }
+  GatherUpdPopArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  int64_t rows = 0;
+  bool head = false;
+  for (int i = 0; i < P; ++i) {
+    const GatherCall& g = c[i];
+    gcrl_her* h = g.h;
+    pa.m[i] = GatherUpdArgs{h->ring, g.idx, g.gen, g.n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, g.ldx, g.sa, g.nsa, g.spa, g.r, g.d,
+                            (const uint4*)g.cp_src, (uint4*)g.cp_dst, (int)(g.cp_bytes / 16)};
+    rows = std::max<int64_t>(rows, g.n);
+    head = head || g.cp_bytes != 0;
+  }
+  if (rows <= 0) return GCRL_OK;
+  const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)P);
+  const size_t lds = 4 * ((size_t)32 * c[0].h->SA4 + 32) * sizeof(float);
+  if (head) hipLaunchKernelGGL(her_gather_update_pop_kernel<true>, grid, dim3(256), lds, st, pa);
+  else hipLaunchKernelGGL(her_gather_update_pop_kernel<false>, grid, dim3(256), lds, st, pa);
+  GCRL_HIP(hipGetLastError());
+  if (merged) *merged = true;
+  return GCRL_OK;
 }
 
 }  // namespace gcrl

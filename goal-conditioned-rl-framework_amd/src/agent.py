@@ -470,14 +470,16 @@ class _EngineAgent:
             return None, self._ACT_MODE_EVAL
         return np.ascontiguousarray(np.random.normal(0, self.noise_std, size=(n, self.ac_dim))), self._ACT_MODE_EXPLORE
 
-    def process_step(self, state, actions, next_obs_raw, rewards, dones, obs_normalize: bool = True, g_normalize: bool = False):
+    def process_step(self, state, actions, next_obs_raw, rewards, dones, obs_normalize: bool = True, g_normalize: bool = False,
+                     env0: int = 0):
         """The reference trainer's `_process_step` (src/env.py:163-201) for one vector-env step as ONE native call:
         normaliser update with [obs ; next_obs], both normalised state matrices built on the device from the updated
         statistics, all envs pushed (episode flush + HER relabel on the device when an env finishes).  `state` /
         `next_obs_raw`: the env's dict observations; `dones` = `terminated` (src/env.py:372).  With `g_normalize` the goal
         normaliser is updated from [dg ; next_dg ; ag ; next_ag] and goals are normalised on the device too (src/env.py:167-175,
         :222-223).  Falls back to the separate calls when a normaliser this step needs is a host object (or, with
-        g_normalize, when compute_reward runs through the host callback)."""
+        g_normalize, when compute_reward runs through the host callback).  `env0`: the ring's episode slot of this call's first
+        env (agents that share one ring each push into their own slots)."""
         nz = self._device_normalizers(obs_normalize, g_normalize)
         buf = self.buffer
         if nz is not None and g_normalize:   # (the ring — and with it the reward kind — exists from here on)
@@ -489,7 +491,7 @@ class _EngineAgent:
                                      next_obs_raw["achieved_goal"]], obs_normalize, g_normalize)
             s = torch.from_numpy(self.normalize_state_batch(state["observation"], state["desired_goal"], obs_normalize, g_normalize)).float().cuda()
             ns = torch.from_numpy(self.normalize_state_batch(next_obs_raw["observation"], next_obs_raw["desired_goal"], obs_normalize, g_normalize)).float().cuda()
-            return buf.push_batch(s, actions, ns, rewards, dones, self.normalize_goal(next_obs_raw["achieved_goal"], g_normalize))
+            return buf.push_batch(s, actions, ns, rewards, dones, self.normalize_goal(next_obs_raw["achieved_goal"], g_normalize), env0=int(env0))
         as_arr = lambda x: x if isinstance(x, np.ndarray) else np.asarray(x)
         obs_i, nobs_i = as_arr(state["observation"]), as_arr(next_obs_raw["observation"])
         dg_i, ndg_i, nag_i = as_arr(state["desired_goal"]), as_arr(next_obs_raw["desired_goal"]), as_arr(next_obs_raw["achieved_goal"])
@@ -517,7 +519,7 @@ class _EngineAgent:
         buf.rng.pull()
         rows = lib.gcrl_her_process_step_g(buf.handle, nz[0], 1 if obs_normalize else 0, nz[1], 1 if g_normalize else 0, p["obs"],
                                            p["nobs"], D, p["dg"], p["ndg"], p["ag"] if g_normalize else None, p["nag"], p["act"], p["rew"],
-                                           p["dn"], 0, n, _ffi.stream_handle())
+                                           p["dn"], int(env0), n, _ffi.stream_handle())
         buf._check_rows(rows)
         buf.rng.push_back()
         return int(rows)

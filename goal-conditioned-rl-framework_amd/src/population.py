@@ -21,7 +21,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import lib
 from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
-from .buffer import MTStream
+from .buffer import HERBuffer, MTStream
 
 MAX_MEMBERS = 16
 MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
@@ -30,6 +30,8 @@ MANIFEST = "population.json"
 # fields every member must share (the population runs one launch pattern); the others (seed, gamma, tau, grad_clip, learning
 # rates and their schedules, SAC's alpha_lr and alpha_min_steps, the ring's own settings) may differ
 SHARED = ("hidden_dim", "layer_count", "batch_size", "ac_update_freq")
+# the replay ring's own settings: with `shared_ring` there is one ring, built from member 0's, so these must agree too
+RING_FIELDS = ("max_len", "max_eps_len", "k_future")
 
 
 class _PopHandle:
@@ -64,10 +66,17 @@ class _Population:
     def _refuse(self, field: str, why: str):
         raise _ffi.GcrlError(f"{type(self).__name__}: {field}: {why}")
 
+    # update calls gather all members' batches in one launch (gcrl_pop_set_gather_merge) from this many members on.  DESIGN.md 4g's
+    # rule: the smallest P from which the merged side's whole range lies below the member-by-member range at both shapes
+    # (tools/population_bench.py --gather), never guessed; not measured yet, so no population merges by default and
+    # `pop.merge_gather = True` takes the population launch.
+    MERGE_GATHER_FROM = MAX_MEMBERS + 1
+
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
-                 seeds=None, device_index: int = 0):
+                 seeds=None, device_index: int = 0, shared_ring: bool = False):
         configs = list(configs)
         P = len(configs)
+        self.shared_ring = bool(shared_ring)
         # every refusal before any device work
         if not 1 <= P <= MAX_MEMBERS:
             self._refuse("members", f"a population has 1..{MAX_MEMBERS} members, got {P}")
@@ -80,6 +89,11 @@ class _Population:
             for f in SHARED:
                 if getattr(c, f) != getattr(configs[0], f):
                     self._refuse(f, f"member {i} has {getattr(c, f)!r}, member 0 {getattr(configs[0], f)!r}: members must share shapes")
+            if self.shared_ring:
+                for f in RING_FIELDS:
+                    if getattr(c, f) != getattr(configs[0], f):
+                        self._refuse(f, f"member {i} has {getattr(c, f)!r}, member 0 {getattr(configs[0], f)!r}: with shared_ring the members "
+                                        "learn from one replay ring, built from member 0's settings")
         kind = KIND[self.AGENT.KIND_NAME]
         cfgs = self._native_configs(kind, obs_dim, ac_dim, configs, seeds, gradient_step, device_index)
         entry = self.ENTRY or ("gcrl_pop_create_forms" if self.SAME_FORMS else "gcrl_pop_create")
@@ -90,6 +104,18 @@ class _Population:
             self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index,
                                            _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
+        self._merge_gather = False
+        if P >= self.MERGE_GATHER_FROM:
+            self.merge_gather = True
+        if self.shared_ring:
+            # ONE ring for all members (as the agent's own constructor builds it, with an episode slot per env of every member:
+            # member i's envs stage in slots i * nenvs ...), its normalisers shared with it; seeded as member 0's ring
+            c0 = configs[0]
+            self.nenvs = int(nenvs)
+            self.buffer = HERBuffer(c0.max_len, c0.max_eps_len, int(nenvs) * P, k_future=c0.k_future, rng=rng, seed=seeds[0],
+                                    device_index=device_index)
+            for m in self.members:
+                m.buffer = self.buffer
         if rng == "python":
             # every use of a python-mode stream is bracketed by pull / push_back of `random`'s state, so the members may share one
             # generator — and a population call then draws member after member from one stream, exactly as the standalone
@@ -126,6 +152,24 @@ class _Population:
                 m.actor.num_batches_tracked += sum(1 + (1 if lens[i * n + j] == 9 else 0) for j in range(n))
             out.append([m._tuple(int(tickets[i * n + j]), int(lens[i * n + j])) for j in range(n)])
         return out
+
+    @property
+    def merge_gather(self) -> bool:
+        """Whether an update call gathers all members' batches in ONE launch of the gather kernel's population form (include/gcrl.h
+        gcrl_pop_set_gather_merge) or member by member; the bits are the same either way."""
+        return self._merge_gather
+
+    @merge_gather.setter
+    def merge_gather(self, on: bool):
+        _ffi.check(lib.gcrl_pop_set_gather_merge(self._pop.h, 1 if on else 0))
+        self._merge_gather = bool(on)
+
+    def gather_counts(self):
+        """(calls, merged, alone): update calls so far (one per chunk of at most the engine's steps-per-call limit), population
+        gather launches, and member-by-member gather launches (include/gcrl.h gcrl_pop_gather_counts)."""
+        v = [C.c_int64() for _ in range(3)]
+        _ffi.check(lib.gcrl_pop_gather_counts(self._pop.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def update(self, step: int):
         """One step of every member: the members' `update(step)` tuples, in member order."""
@@ -217,6 +261,14 @@ class _Population:
             self._per_member(name, seq)
         ms = self.members
         P = len(ms)
+        if getattr(self, "shared_ring", False):
+            # one ring and one pair of normalisers: the merged staging launch would update them from P members at once, so the members
+            # push one after another, each into its own episode slots
+            for i, a in enumerate(actions):
+                if np.shape(a)[0] > self.nenvs:
+                    self._refuse("actions", f"member {i} steps {np.shape(a)[0]} envs, the shared ring has {self.nenvs} episode slots per member")
+            return [m.process_step(s, a, nx, r, d, obs_normalize, g_normalize, env0=i * self.nenvs)
+                    for i, (m, s, a, nx, r, d) in enumerate(zip(ms, states, actions, next_obs_raws, rewards, dones))]
         as_arr = lambda x: x if isinstance(x, np.ndarray) else np.asarray(x)
         nzs = [m._device_normalizers(obs_normalize, g_normalize) for m in ms]
         rows_in = []
@@ -335,6 +387,8 @@ class _Population:
         normalisers' statistics are copied through `set_state` (a host round trip of a few hundred bytes per normaliser, as
         `load_state` does it — not device to device).  One source may serve several destinations; a member cannot be both in one call."""
         pairs = self._check_pairs(pairs)
+        if copy_ring and getattr(self, "shared_ring", False):
+            self._refuse("copy_ring", "the members learn from one shared replay ring (shared_ring=True): there is no ring to copy")
         ms = self.members
         P, n = len(ms), len(pairs)
         rings = None
@@ -420,6 +474,8 @@ class _Population:
         m._metric_cache.clear()
         m._live.clear()
         m._lazy.clear()
+        if getattr(self, "shared_ring", False):   # the ring and its normalisers belong to all members: kept as they are
+            return
         buf = m.buffer
         if buf._h is not None:     # an emptied ring is a fresh one: the next push creates it (counters and device index stream at zero)
             h, buf._h = buf._h, None
@@ -463,6 +519,8 @@ class _Population:
         """Every member's `save_state` under `path`/member_00 ..., and `population.json` (kind, member count, shared fields)."""
         import json
         import os
+        if getattr(self, "shared_ring", False):
+            self._refuse("shared_ring", "save_state of a population with one shared replay ring is not supported yet")
         os.makedirs(path, exist_ok=True)
         for i, m in enumerate(self.members):
             m.save_state(os.path.join(path, f"member_{i:02d}"))
@@ -474,6 +532,8 @@ class _Population:
         (naming the field) before any member is overwritten."""
         import json
         import os
+        if getattr(self, "shared_ring", False):
+            self._refuse("shared_ring", "load_state into a population with one shared replay ring is not supported yet")
         with open(os.path.join(path, MANIFEST)) as f:
             self._check_manifest(json.load(f))
         for i in range(len(self.members)):

@@ -364,6 +364,15 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n,
  * gcrl_pop_launch_counts: how the recorded launch positions of every gcrl_pop_update_n since creation were issued — `merged`: as one
  * launch of the kernel's population form for all members; `alone`: member by member (a launch without a population form, members
  * whose launches differ, or a one-member population).  Either pointer may be null.
+ * The replay side of gcrl_pop_update_n: every member's indices are drawn first, in member order, then the members' gathers are
+ * issued — as ONE launch of the gather kernel's population form (each member's own ring, indices or index generator, batch
+ * matrices and control-block side copy; given the same indices bit for bit the members' own launches), or member by member.
+ * rings[] may name one ring several times: those members draw from that ring's index stream in member order (device-RNG mode: the
+ * ring's draw counter advances per member) and behave bit for bit like standalone agents sharing the ring, called in member order.
+ * gcrl_pop_set_gather_merge: on != 0: the population gather launch; 0 (the state at creation): each member's own gather launch.
+ * gcrl_pop_gather_counts: since creation — `calls`: update calls (one per chunk of at most the steps-per-call limit); `merged`:
+ * population gather launches; `alone`: member-by-member gather launches (gcrl_pop_launch_counts does not count gathers).  Any
+ * pointer may be null.
  *
  * The acting side of a population, one launch per call for all members (the trainer's loop, src/env.py:334-406, calls both per
  * vector-env step and per agent).  Every host array has a leading [members] dimension; each member computes bit for bit what its
@@ -403,6 +412,8 @@ int32_t gcrl_pop_size(const gcrl_pop* p);
 int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_t n, int64_t* tickets_out,
                       int32_t* tuple_len_out, void* stream);
 int gcrl_pop_launch_counts(const gcrl_pop* p, int64_t* merged, int64_t* alone);
+int gcrl_pop_set_gather_merge(gcrl_pop* p, int32_t on);
+int gcrl_pop_gather_counts(const gcrl_pop* p, int64_t* calls, int64_t* merged, int64_t* alone);
 int gcrl_pop_forms(gcrl_pop* p);
 int gcrl_pop_forms_terms(const gcrl_pop* p, int64_t* want, int64_t* capacity);
 int gcrl_pop_observe_act(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, const float* obs_host, int32_t obs_dim,

@@ -101,7 +101,7 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 # ... and the population forms of the sampling launches a TQC population step issues (ops_sac.hip)
 # ... and the one-launch device copy of gcrl_pop_clone (pop_clone.hip)
 SCRATCH_NAMED = {"pop_clone.hip": ["pop_clone_kernel"],
-                 "rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel"],
+                 "rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel", "her_gather_update_pop_kernel"],
                  "ops_sac.hip": ["tanh_gauss_fwd_pop_kernel", "tanh_gauss_fwd2_pop_kernel", "tanh_gauss_bwd_pop_kernel"],
                  "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel", "act_bn_pop_kernel", "act_bn_pop_staged_kernel"]}
 

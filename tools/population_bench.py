@@ -31,7 +31,14 @@ included.  One JSON line per (shape, P).
 times `pop.exploit` of a quarter of the members (one launch for all pairs, src/population.py) against the only way the tree had before:
 the members' save_state / load_state round trip through host memory (with the ring: through a file), pair by pair — both in the same
 process on the same population, in alternating rounds; wall clock and device time (events around the calls) per call, median and
-min-max of the rounds, with and without the replay ring, and the bytes the clone moves.  One JSON line per (kind, shape, P, ring)."""
+min-max of the rounds, with and without the replay ring, and the bytes the clone moves.  One JSON line per (kind, shape, P, ring).
+
+    python tools/population_bench.py --gather [--kind DDPG] [--shapes cfg1,headline] [--members 2,4,8,16] [--rounds 5] [--calls 50] [--out profiles/r14_pop_gather.jsonl]
+
+times the replay side of an update call: ONE population, `merge_gather` toggled (one population gather launch per call against the
+members' own gather launches), the same process, the sides alternating round by round; wall clock per `update_many` call (a device
+synchronise inside each round's bracket) at two call lengths, n = 40 and n = 1.  One JSON line per (shape, P, n): median and min-max
+of the rounds per side, in microseconds per call, and whether the two ranges overlap."""
 import argparse
 import json
 import os
@@ -292,6 +299,38 @@ class _AgentStateHeader(__import__("ctypes").Structure):
                 [("lr_actor", _c.c_double), ("lr_critic", _c.c_double), ("rng_ctr", _c.c_uint64)])
 
 
+def run_gather(shape, P, kind, rounds, calls, warmup):
+    sh = SHAPES[shape]
+    pop_cls = KINDS[kind][0]
+    pop = pop_cls(sh["S"], sh["A"], _cfgs(sh, P, kind), 2, GSTEP, rng="engine", seeds=list(range(7, 7 + P)))
+    for i, m in enumerate(pop.members):
+        _fill(m, sh, i)
+    out = []
+    step = 1
+    for n in (GSTEP, 1):
+        us = {True: [], False: []}
+        for r in range(rounds):
+            for merged in (True, False):
+                pop.merge_gather = merged
+                for _ in range(warmup if r == 0 else 2):
+                    pop.update_many(step, n)
+                    step += n
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    pop.update_many(step, n)
+                    step += n
+                torch.cuda.synchronize()
+                us[merged].append((time.perf_counter() - t0) / calls * 1e6)
+        a, b = sorted(us[True]), sorted(us[False])
+        out.append(dict(bench="gather", kind=kind, shape=shape, members=P, steps_per_call=n, rounds=rounds, calls_per_round=calls,
+                        merged_us_per_call_median=round(a[len(a) // 2], 2), merged_us_per_call_min=round(a[0], 2), merged_us_per_call_max=round(a[-1], 2),
+                        members_us_per_call_median=round(b[len(b) // 2], 2), members_us_per_call_min=round(b[0], 2), members_us_per_call_max=round(b[-1], 2),
+                        merged_whole_range_below=a[-1] < b[0], ranges_overlap=not (a[-1] < b[0] or b[-1] < a[0]),
+                        gather_counts=list(pop.gather_counts()), **{k: sh[k] for k in ("S", "A", "H", "L", "B")}))
+    return out
+
+
 def _ring_segment_bytes(buf):
     """bytes of a ring clone's segments (csrc/her_ring.h): [nenvs][flush_len][RG] staged floats and len x RS row floats"""
     from gcrl_amd.src.buffer import FLUSH_LEN
@@ -375,7 +414,20 @@ def main():
     ap.add_argument("--acting", action="store_true", help="time observe_act + process_step instead of the update side")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=3000, help="--acting: vector steps per round and side")
+    ap.add_argument("--gather", action="store_true", help="time update_many with merge_gather on against off, same population")
     a = ap.parse_args()
+    if a.gather:
+        assert a.rounds >= 5 or os.environ.get("POP_BENCH_SHORT"), "at least five alternating rounds"
+        members = "2,4,8,16" if a.members == "1,2,4,8" else a.members
+        with (open(a.out, "a") if a.out else open(os.devnull, "w")) as f:
+            for shape in a.shapes.split(","):
+                for P in [int(x) for x in members.split(",")]:
+                    for r in run_gather(shape, P, a.kind, a.rounds, a.calls, a.warmup):
+                        line = json.dumps(r)
+                        print(line, flush=True)
+                        f.write(line + "\n")
+                        f.flush()
+        return
     if a.clone:
         import tempfile
         members = "4,16" if a.members == "1,2,4,8" else a.members
