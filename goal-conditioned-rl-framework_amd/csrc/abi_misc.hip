@@ -228,6 +228,171 @@ int gcrl_bn_linear_slab_bwd_f32(const float* g_up, int64_t ldg, int K_up, const 
   return gcrl::launch_bn_linear_bwd_slab(as_stream(stream), b);
 }
 
+}  // extern "C"
+
+// ---- the stage kernels as single problems (test entry points) -----------------------------------------------------------
+namespace {
+// Device scratch of one call: the control record every stage kernel reads (zeroed: batch slot 0, metrics slot 0) with
+// `do_alpha`, the device scalars log_alpha / alpha, a zeroed ticket word on its own line, `part_floats` floats of partial sums.
+// Freed, after the stream has drained, when the call returns.
+struct StageScratch {
+  static constexpr size_t kScalars = 64, kTicket = 128, kPart = 256;
+  static_assert(sizeof(gcrl::StepCtrl) <= kScalars, "control record");
+  char* base = nullptr;
+  hipStream_t st = nullptr;
+  ~StageScratch() {
+    if (!base) return;
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(base);
+  }
+  int init(hipStream_t stream, int do_alpha, float log_alpha, float alpha, size_t part_floats) {
+    st = stream;
+    GCRL_HIP(hipMalloc((void**)&base, kPart + part_floats * sizeof(float)));
+    char img[kPart];
+    std::memset(img, 0, sizeof(img));
+    gcrl::StepCtrl c;
+    std::memset(&c, 0, sizeof(c));
+    c.do_alpha = do_alpha;
+    std::memcpy(img, &c, sizeof(c));
+    const float sc[2] = {log_alpha, alpha};
+    std::memcpy(img + kScalars, sc, sizeof(sc));
+    GCRL_HIP(hipMemcpyAsync(base, img, sizeof(img), hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipStreamSynchronize(st));   // (img is on this stack)
+    return GCRL_OK;
+  }
+  const gcrl::StepCtrl* ctrl() const { return reinterpret_cast<const gcrl::StepCtrl*>(base); }
+  float* log_alpha() const { return reinterpret_cast<float*>(base + kScalars); }
+  float* alpha() const { return reinterpret_cast<float*>(base + kScalars) + 1; }
+  unsigned int* ticket() const { return reinterpret_cast<unsigned int*>(base + kTicket); }
+  float* part() const { return reinterpret_cast<float*>(base + kPart); }
+};
+// "not written" before a repeated launch: all-ones words (NaN as fp32)
+int stage_poison(hipStream_t st, float* p, size_t n) {
+  if (p) GCRL_HIP(hipMemsetAsync(p, 0xff, n * sizeof(float), st));
+  return GCRL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gcrl_td_loss_f32(const float* r, const float* d, const float* qt, const float* q, const float* logp_next, float alpha, const float* w,
+                     int B, int C, int drop, int target_kind, int loss_kind, float gamma, float clamp_lo, int multi_block, float* dq,
+                     float* td_abs, float* metrics, void* stream) {
+  GCRL_CHECK_ARG(r && d && qt && q && dq && metrics && B >= 1 && B <= (1 << 24) && C >= 1 && C <= gcrl::kMaxCritics,
+                 "gcrl_td_loss_f32: bad arguments (B=%d C=%d)", B, C);
+  GCRL_CHECK_ARG(target_kind >= gcrl::TGT_DDPG && target_kind <= gcrl::TGT_TRUNC_ENT && (loss_kind == gcrl::LOSS_MSE || loss_kind == gcrl::LOSS_SMOOTH_L1),
+                 "gcrl_td_loss_f32: bad target kind %d / loss kind %d", target_kind, loss_kind);
+  GCRL_CHECK_ARG(target_kind == gcrl::TGT_TRUNC_ENT ? (drop >= 0 && drop < C) : drop == 0, "gcrl_td_loss_f32: bad drop=%d (C=%d)", drop, C);
+  GCRL_CHECK_ARG(target_kind == gcrl::TGT_DDPG ? C == 1 : (target_kind == gcrl::TGT_TRUNC_ENT || C == 2),
+                 "gcrl_td_loss_f32: target kind %d with C=%d", target_kind, C);
+  GCRL_CHECK_ARG((target_kind == gcrl::TGT_MIN_ENT || target_kind == gcrl::TGT_TRUNC_ENT) ? logp_next != nullptr : true,
+                 "gcrl_td_loss_f32: the entropy targets need logp_next");
+  GCRL_CHECK_ARG(multi_block >= 0 && multi_block <= 4 && (multi_block == 0 || B >= 1024),
+                 "gcrl_td_loss_f32: bad multi_block=%d (the multi-workgroup form starts at B = 1024)", multi_block);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, 0.f, multi_block ? (size_t)64 * ((B + 255) / 256) : 0)) return rc;
+  gcrl::TdLossArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cur = s.ctrl();
+  a.r = r; a.d = d; a.qt = qt; a.q = q; a.logp_next = logp_next; a.alpha_const = alpha; a.dq = dq; a.w = w; a.td_abs = td_abs;
+  a.metrics = metrics;
+  a.B = B; a.C = C; a.drop = drop; a.target_kind = target_kind; a.loss_kind = loss_kind; a.gamma = gamma; a.clamp_lo = clamp_lo;
+  if (multi_block) { a.part = s.part(); a.ticket = s.ticket(); }
+  int rc = gcrl::launch_td_loss(st, a);
+  for (int i = 1; !rc && i < multi_block; ++i) {   // again: the ticket must have come back to zero by itself
+    if ((rc = stage_poison(st, dq, (size_t)C * B)) || (rc = stage_poison(st, td_abs, (size_t)B)) ||
+        (rc = stage_poison(st, metrics, gcrl::kMetricFloats))) break;
+    rc = gcrl::launch_td_loss(st, a);
+  }
+  return rc;
+}
+
+int gcrl_tanh_gauss_fwd_f32(const float* mu, const float* ls_raw, int ld_head, const float* eps, int B, int A, int deterministic,
+                            float* act, int ld_act, float* logp, float* save_eps, float* save_std, void* stream) {
+  GCRL_CHECK_ARG(mu && act && B >= 1 && A >= 1 && ld_head >= A && ld_act >= A && (long long)B * std::max(ld_head, ld_act) < (1ll << 31),
+                 "gcrl_tanh_gauss_fwd_f32: bad arguments (B=%d A=%d ld_head=%d ld_act=%d)", B, A, ld_head, ld_act);
+  GCRL_CHECK_ARG(deterministic || (ls_raw && eps && logp), "gcrl_tanh_gauss_fwd_f32: sampling needs ls_raw, eps and logp");
+  GCRL_CHECK_ARG((save_eps == nullptr) == (save_std == nullptr), "gcrl_tanh_gauss_fwd_f32: save_eps and save_std go together");
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, 0.f, 0)) return rc;
+  gcrl::TanhGaussArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cur = s.ctrl();
+  a.mu = mu; a.ls_raw = ls_raw; a.ld_head = ld_head; a.eps = eps;
+  a.act = act; a.ld_act = ld_act; a.logp = logp; a.save_eps = save_eps; a.save_std = save_std;
+  a.B = B; a.A = A; a.deterministic = deterministic ? 1 : 0;
+  return gcrl::launch_tanh_gauss_fwd(st, a);   // (run.layers = 0: no running-statistics rider)
+}
+
+int gcrl_tanh_gauss_bwd_f32(const float* dact, int C, int ld_dact, const float* act, int ld_act, const float* eps, const float* std_dev,
+                            const float* ls_raw, int ld_head, float alpha, int B, int A, float* gmu, float* gls, int ld_g, void* stream) {
+  GCRL_CHECK_ARG(dact && act && eps && std_dev && ls_raw && gmu && gls && B >= 1 && A >= 1 && C >= 1 && C <= gcrl::kMaxCritics &&
+                 ld_dact >= A && ld_act >= A && ld_head >= A && ld_g >= A &&
+                 (long long)B * std::max(std::max(ld_dact, ld_act), std::max(ld_head, ld_g)) < (1ll << 31),
+                 "gcrl_tanh_gauss_bwd_f32: bad arguments (B=%d A=%d C=%d)", B, A, C);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, 0.f, 0)) return rc;
+  gcrl::TanhGaussBwdArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.dact = dact; a.C = C; a.ld_dact = ld_dact; a.dact_stride = (long long)B * ld_dact;
+  a.act = act; a.ld_act = ld_act; a.cur = s.ctrl();
+  a.eps = eps; a.std = std_dev; a.ls_raw = ls_raw; a.ld_head = ld_head;
+  a.alpha_const = alpha;
+  a.gmu = gmu; a.gls = gls; a.ld_g = ld_g;
+  a.B = B; a.A = A;
+  return gcrl::launch_tanh_gauss_bwd(st, a);
+}
+
+int gcrl_actor_select_f32(const float* q, const float* logp, float alpha, int B, int C, int drop, int min_of_two, int do_alpha,
+                          float target_entropy, float log_alpha, int form, float* dq, float* metrics, float* grad_log_alpha, void* stream) {
+  GCRL_CHECK_ARG(q && logp && dq && metrics && B >= 1 && B <= (1 << 24) && C >= 1 && C <= gcrl::kMaxCritics && drop >= 0 && drop < C,
+                 "gcrl_actor_select_f32: bad arguments (B=%d C=%d drop=%d)", B, C, drop);
+  GCRL_CHECK_ARG(!min_of_two || (C == 2 && drop == 0), "gcrl_actor_select_f32: min_of_two needs C = 2, drop = 0 (C=%d drop=%d)", C, drop);
+  GCRL_CHECK_ARG(form >= 0 && form <= 3 && (form == 0 || grad_log_alpha) && (form < 2 || B >= 1024),
+                 "gcrl_actor_select_f32: bad form=%d (1..3 need grad_log_alpha; the multi-workgroup form starts at B = 1024)", form);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, do_alpha ? 1 : 0, log_alpha, alpha, form >= 2 ? (size_t)8 * ((B + 255) / 256) : 0)) return rc;
+  gcrl::ActorSelArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cur = s.ctrl();
+  a.q = q; a.logp = logp; a.dq = dq; a.metrics = metrics;
+  a.B = B; a.C = C; a.drop = drop; a.min2 = min_of_two ? 1 : 0;
+  if (form == 0) {
+    a.alpha_const = alpha;
+    return gcrl::launch_actor_select(st, a);
+  }
+  a.alpha_dev = s.alpha();
+  a.mean_x = q; a.mean_n = C * B; a.mean_index = gcrl::MET_Q;   // the rider: mean of the critics' outputs
+  if (form >= 2) { a.part = s.part(); a.ticket = s.ticket(); }
+  gcrl::AlphaArgs al;
+  std::memset(&al, 0, sizeof(al));
+  al.cur = s.ctrl();
+  al.logp = logp; al.B = B; al.target_entropy = target_entropy;
+  al.log_alpha = s.log_alpha(); al.alpha = s.alpha(); al.grad_out = grad_log_alpha;
+  al.metrics = metrics;
+  al.phase = 0;
+  int rc = gcrl::launch_actor_select_alpha(st, a, al);
+  if (!rc && form == 2) {   // again: the ticket must have come back to zero by itself
+    if ((rc = stage_poison(st, dq, (size_t)C * B)) || (rc = stage_poison(st, metrics, gcrl::kMetricFloats)) ||
+        (rc = stage_poison(st, do_alpha ? grad_log_alpha : nullptr, 1))) return rc;   // (no gradient is written without do_alpha)
+    rc = gcrl::launch_actor_select_alpha(st, a, al);
+  }
+  return rc;
+}
+
+int gcrl_td3_smooth_f32(float* act, int ld, int B, int A, const float* eps, float policy_noise, float noise_clip, void* stream) {
+  GCRL_CHECK_ARG(act && eps && B >= 1 && A >= 1 && ld >= A && (long long)B * ld < (1ll << 31) && noise_clip >= 0.f,
+                 "gcrl_td3_smooth_f32: bad arguments (B=%d A=%d ld=%d)", B, A, ld);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, 0.f, 0)) return rc;
+  return gcrl::launch_td3_smooth(st, s.ctrl(), act, 0, ld, B, A, eps, policy_noise, noise_clip, 0ull);
+}
+
 int gcrl_set_shared_device(int shared) {
   gcrl::meet_set_device_shared(shared != 0);
   return GCRL_OK;

@@ -816,7 +816,7 @@ int enqueue_phase1_body(gcrl_agent* a, hipStream_t st, int variant) {
     std::memset(&as, 0, sizeof(as));
     as.cur = a->cur(); as.q = a->q2; as.logp = a->logp; as.dq = a->dq2; as.metrics = a->metrics_dev;
     as.B = B; as.C = nac;
-    if (kind == GCRL_AGENT_SAC) { as.alpha_const = 0.2f; as.drop = 0; }
+    if (kind == GCRL_AGENT_SAC) { as.alpha_const = 0.2f; as.drop = 0; as.min2 = 1; }
     else { as.alpha_dev = a->alpha_dev; as.drop = a->cfg.top_drop; }
     // ... and, in the same launch, the log-alpha gradient + loss metric (the optimiser step itself is in phase 2)
     AlphaArgs al;

@@ -340,6 +340,9 @@ struct ActorSelArgs {
   float* dq;           // [C][B]
   float* metrics;
   int B, C, drop;
+  // 1: sel = torch.min(q_0, q_1) (SAC, C = 2); 0: mean of the lowest C - drop of the sorted ensemble (TQC — with drop = 0 the
+  // plain mean, src/agent.py:922-923, also at C = 2)
+  int min2;
   // rider (launch_actor_select_alpha only): metrics[mean_index] = mean(mean_x[0 .. mean_n)) by a second workgroup — the q_value
   // metric of the re-evaluated critics (launch_mean_metric's sums), one single-workgroup launch less per step
   const float* mean_x; int mean_n, mean_index;

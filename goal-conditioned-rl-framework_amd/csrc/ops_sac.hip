@@ -834,7 +834,7 @@ int launch_tanh_gauss_fwd2(hipStream_t st, const TanhGaussArgs& a0, const TanhGa
 }
 
 int launch_actor_select(hipStream_t st, const ActorSelArgs& a) {
-  GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C, "actor_select: bad C=%d drop=%d", a.C, a.drop);
+  GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C && (!a.min2 || (a.C == 2 && a.drop == 0)), "actor_select: bad C=%d drop=%d", a.C, a.drop);
   if (PopRec* r = pop_recording()) return pop_defer(r, [a](hipStream_t s) { return launch_actor_select(s, a); });
   hipLaunchKernelGGL(actor_select_kernel, dim3(1), dim3(reduce_threads(a.B)), 0, st, a);
   GCRL_HIP(hipGetLastError());
@@ -842,7 +842,7 @@ int launch_actor_select(hipStream_t st, const ActorSelArgs& a) {
 }
 
 int launch_actor_select_alpha(hipStream_t st, const ActorSelArgs& a, const AlphaArgs& al) {
-  GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C, "actor_select: bad C=%d drop=%d", a.C, a.drop);
+  GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.drop >= 0 && a.drop < a.C && (!a.min2 || (a.C == 2 && a.drop == 0)), "actor_select: bad C=%d drop=%d", a.C, a.drop);
   if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h): no population form, issued member by member
     return pop_defer(r, [a, al](hipStream_t s) { return launch_actor_select_alpha(s, a, al); });
   if (a.part && a.ticket && a.B >= 1024 && al.phase == 0 && al.B == a.B) {
@@ -864,7 +864,7 @@ int launch_tanh_gauss_bwd(hipStream_t st, const TanhGaussBwdArgs& a) {
 }
 
 int launch_tanh_gauss_bwd_select(hipStream_t st, const TanhGaussBwdArgs& a, const ActorSelArgs& s, const AlphaArgs& al) {
-  GCRL_CHECK_ARG(s.C >= 1 && s.C <= kMaxCritics && s.drop >= 0 && s.drop < s.C, "actor_select: bad C=%d drop=%d", s.C, s.drop);
+  GCRL_CHECK_ARG(s.C >= 1 && s.C <= kMaxCritics && s.drop >= 0 && s.drop < s.C && (!s.min2 || (s.C == 2 && s.drop == 0)), "actor_select: bad C=%d drop=%d", s.C, s.drop);
   if (PopRec* r = pop_recording()) {   // a population step is being recorded (pop.h)
     TgBwdSelectPop e;
     std::memset(&e, 0, sizeof(e));

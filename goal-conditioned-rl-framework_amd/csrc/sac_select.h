@@ -120,7 +120,7 @@ __device__ inline float actor_select_acc(const ActorSelArgs& a, bool mb) {
   auto finish = [&](SelRow& w, int b) {
     float* q = w.q;
     float sel;
-    if (C == 2 && a.drop == 0) {
+    if (a.min2) {
       // torch.min(q1, q2): gradient to the smaller, split on ties
       sel = fminf(q[0], q[1]);
       const float w0 = q[0] < q[1] ? 1.f : (q[0] == q[1] ? 0.5f : 0.f);

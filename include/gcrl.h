@@ -745,6 +745,58 @@ int gcrl_bn_linear_slab_bwd_f32(const float* g_up_dev, int64_t ldg, int K_up, co
                                 const float* invstd_dev, const float* gamma_dev, const float* beta_dev, int B, int H,
                                 float* dgamma_dev, float* dbeta_dev, int row_split, void* stream);
 
+/* The small kernels between the GEMM stages of an update step, as single problems on the engine's own launchers (the launcher
+ * picks the launch form, as it does inside a step).  Stand-alone for tests: every call builds its control record (batch slot 0,
+ * metrics slot 0) and its scratch on the device and frees them before it returns.  All pointers are device memory.
+ * `metrics_dev`: one record of 32 floats — [0..7] per-critic loss, [16] mean max_c |q_c - y|, [17] mean q, [18] actor loss,
+ * [20] alpha loss, [21] alpha.
+ *
+ * gcrl_td_loss_f32: TD target, critic loss gradient and metrics.  r, d [B]; qt, q [C][B]; logp_next [B] (entropy targets) or
+ * null; w [B] importance weights or null -> dq [C][B] = d loss_c / d q_c, td_abs [B] = max_c |q_c - y| (or null), metrics.
+ *   target_kind 0: y = clamp(r + gamma (1 - d) qt_0, clamp_lo, 0)                         (src/agent.py:1317, C = 1)
+ *               1: y = r + gamma (1 - d) min(qt_0, qt_1)                                   (src/agent.py:174-184, C = 2)
+ *               2: ... min(qt_0, qt_1) - alpha logp_next                                   (src/agent.py:566-569, C = 2)
+ *               3: ... mean of the C - drop lowest of the sorted qt_c - alpha logp_next    (src/agent.py:971-974)
+ *   loss_kind   0: mse_loss, 1: smooth_l1_loss; with w: (w * loss(reduction="none")).mean() (src/agent.py:1320-1325)
+ *   multi_block 0: the single-workgroup form.  n >= 1: the multi-workgroup form (taken at B >= 1024) with its partial-sum
+ *               scratch and a zeroed ticket, launched n times into the same outputs; the ticket is zeroed once, and the
+ *               outputs are filled with NaN patterns before every launch after the first, so what is read back is the
+ *               last launch's work alone. */
+int gcrl_td_loss_f32(const float* r_dev, const float* d_dev, const float* qt_dev, const float* q_dev, const float* logp_next_dev,
+                     float alpha, const float* w_dev, int B, int C, int drop, int target_kind, int loss_kind, float gamma,
+                     float clamp_lo, int multi_block, float* dq_dev, float* td_abs_dev, float* metrics_dev, void* stream);
+
+/* SACActorModel.sample (src/model.py:118-141) on given head outputs: mu, ls_raw [B, ld_head] (first A columns), eps [B, A]
+ * -> act [B, ld_act] (first A columns), logp [B], save_eps / save_std [B, A].  deterministic: act = tanh(mu) only (ls_raw,
+ * eps, logp, save_eps, save_std may be null). */
+int gcrl_tanh_gauss_fwd_f32(const float* mu_dev, const float* ls_raw_dev, int ld_head, const float* eps_dev, int B, int A,
+                            int deterministic, float* act_dev, int ld_act, float* logp_dev, float* save_eps_dev,
+                            float* save_std_dev, void* stream);
+/* Its backward under the actor loss mean(alpha * logp - sel): dact [C][B][ld_dact] (the critics' action gradients, summed over
+ * C), act [B, ld_act], eps / std [B, A] as the forward saved them, ls_raw [B, ld_head] -> gmu, gls [B, ld_g]: the gradients of
+ * the two heads' outputs. */
+int gcrl_tanh_gauss_bwd_f32(const float* dact_dev, int C, int ld_dact, const float* act_dev, int ld_act, const float* eps_dev,
+                            const float* std_dev, const float* ls_raw_dev, int ld_head, float alpha, int B, int A,
+                            float* gmu_dev, float* gls_dev, int ld_g, void* stream);
+
+/* Actor-loss selection (src/agent.py:516-521: torch.min of two critics; :916-925: mean of the C - drop lowest of the sorted
+ * ensemble) and the log-alpha loss / gradient (src/agent.py:532-546).  q [C][B], logp [B] -> dq [C][B] = d loss / d q_c,
+ * metrics, grad_log_alpha (one float).  min_of_two (C = 2, drop = 0 only): SAC's torch.min; else the sorted form, which with
+ * drop = 0 is the plain mean over the critics.  do_alpha = 0 stands for `gradient_step <= alpha_min_steps`.
+ *   form 0: selection only (alpha as a literal; metrics[18]).
+ *        1: selection + log-alpha gradient in one single-workgroup launch (alpha read from the device; metrics[18], [20],
+ *           [21] when do_alpha = 0, and metrics[17] = mean(q) by the launch's rider workgroup).
+ *        2: the same on the multi-workgroup form (taken at B >= 1024), launched twice as gcrl_td_loss_f32 does.
+ *        3: form 2 launched once. */
+int gcrl_actor_select_f32(const float* q_dev, const float* logp_dev, float alpha, int B, int C, int drop, int min_of_two,
+                          int do_alpha, float target_entropy, float log_alpha, int form, float* dq_dev, float* metrics_dev,
+                          float* grad_log_alpha_dev, void* stream);
+
+/* TD3 target-policy smoothing (src/agent.py:174-179), in place: act [B, ld] (first A columns) <- clamp(act +
+ * clamp(eps * policy_noise, -noise_clip, noise_clip), -1, 1), eps [B, A]. */
+int gcrl_td3_smooth_f32(float* act_dev, int ld, int B, int A, const float* eps_dev, float policy_noise, float noise_clip,
+                        void* stream);
+
 /* The device-RNG mode's Gaussian: out[i] = hash_normal(seed, ctr0 + i), the counter-hash Box-Muller normal that stands in
  * for torch.randn_like (src/agent.py:175, TD3 target smoothing) and Normal.rsample's eps (src/model.py:134) whenever an
  * update is not given injected noise.  Not torch's stream; restated in oracle/device_rng_oracle.py and tested against it. */
