@@ -217,6 +217,21 @@ PROTOTYPES = {
     "gcrl_agent_get_meetings": (C.c_int, [_vp]),
     "gcrl_agent_debug_meet_fault": (C.c_int, [_vp]),
     "gcrl_hash_normal_fill": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
+    "gcrl_per_attach": (C.c_int, [_vp, _f32, _f32]),
+    "gcrl_per_attached": (C.c_int, [_vp]),
+    "gcrl_per_levels": (C.c_int, [_vp]),
+    "gcrl_per_level_size": (_i64, [_vp, C.c_int]),
+    "gcrl_per_draw": (C.c_int, [_vp, C.c_int, _f32, _vp, _vp, _vp]),
+    "gcrl_per_update": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "gcrl_per_set_betas": (C.c_int, [_vp, _vp, C.c_int]),
+    "gcrl_per_get_priorities": (C.c_int, [_vp, _vp, _i64]),
+    "gcrl_per_set_priorities": (C.c_int, [_vp, _vp, _i64]),
+    "gcrl_per_read_level": (C.c_int, [_vp, C.c_int, _vp, _i64]),
+    "gcrl_her_sample_dev": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
+    "gcrl_her_set_head": (C.c_int, [_vp, _i64]),
+    "gcrl_per_get_draw_counter": (_i64, [_vp]),
+    "gcrl_per_set_draw_counter": (C.c_int, [_vp, _i64]),
+    "gcrl_per_launches": (_i64, [_vp]),
     "gcrl_event_create": (_vp, []),
     "gcrl_event_destroy": (None, [_vp]),
     "gcrl_event_record": (C.c_int, [_vp, _vp]),

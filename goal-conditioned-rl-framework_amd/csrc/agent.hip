@@ -32,6 +32,7 @@
 #include "dw_adam.h"
 #include "gemm_mfma.h"
 #include "her_ring.h"
+#include "per_tree.h"
 #include "meet.h"
 #include "ops.h"
 #include "rowchain.h"
@@ -126,6 +127,8 @@ struct gcrl_agent {
   float *logp = nullptr, *logp_next = nullptr, *epsbuf = nullptr, *stdbuf = nullptr;
   float *noise_in = nullptr, *eps_next_in = nullptr, *eps_cur_in = nullptr, *norm_partial = nullptr;
   float *w_in = nullptr, *td_abs = nullptr;   // prioritised replay: IS weights of the batch [B], per-sample |td| [B]
+  bool per_call = false;                      // set by run_per_device around its begin_call: the only entry that draws from a priority tree
+  float* per_hist = nullptr;                  // device-drawn prioritised replay: |td| of every step of the last call [Mmax][B]
   float *act_in = nullptr, *act_tmp[2] = {};
   float *qy = nullptr, *q_row_loss = nullptr, *q_row_td = nullptr;   // distributional TQC: kept target atoms [B][64], per-row sums
   float* pi_buf = nullptr;   // SAC row-chain path: pi(s) [B][Apad] (the layer-per-launch paths keep it in spa's action columns)
@@ -1150,6 +1153,7 @@ int finish_deferred_draw(gcrl_agent* a, hipStream_t st) {
 // all members' gathers as one population launch (begin_call_issue_pop).
 struct CallGather {
   bool injected = false;
+  bool per_dev = false;        // no gather with the call's upload: every step draws and gathers its own rows
   bool head_form = false;      // the gather reads its indices from the pinned block and carries the control block as a side copy
   bool host_idx = false;
   int slot = 0;
@@ -1173,6 +1177,8 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     GCRL_CHECK_ARG(her->S == a->S && her->A == a->A, "update: ring dims (S=%d,A=%d) differ from the agent's (S=%d,A=%d)", her->S, her->A, a->S, a->A);
     if (her->len < a->B) return fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
   }
+  GCRL_CHECK_ARG(injected || (in && in->idx_host) || !her->per || a->per_call,
+                 "update: this entry does not draw from a ring's priority tree (per_draw=\"device\"): use gcrl_agent_update / gcrl_agent_update_n");
   if (!injected && in && in->idx_host)     // every argument is checked before a ticket, slot or plan is consumed
     for (int i = 0; i < a->B; ++i)
       GCRL_CHECK_ARG((int64_t)in->idx_host[i] < her->len, "update: row index %u outside the ring (len %lld)", in->idx_host[i], (long long)her->len);
@@ -1193,12 +1199,13 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   }
   ub->cb.cur = table[0];
   size_t bytes = sizeof(UploadBlock);
-  const bool device_rng = !injected && her->cfg.rng_mode != GCRL_RNG_CPYTHON_MT;
   const bool explicit_idx = !injected && in && in->idx_host;
+  const bool per_dev = !injected && !explicit_idx && her->per;   // the priority tree draws every step's rows on the device (run_per_device)
+  const bool device_rng = !injected && !per_dev && her->cfg.rng_mode != GCRL_RNG_CPYTHON_MT;
   if (explicit_idx) {   // prioritised replay: the caller drew the rows
     for (int i = 0; i < a->B; ++i) idx[i] = in->idx_host[i];
     bytes += (size_t)a->B * sizeof(uint32_t);
-  } else if (!injected && !device_rng) {
+  } else if (!injected && !device_rng && !per_dev) {
     const int head = a->head_batches;
     defer_rest = defer_rest && n > head;
     const int now = defer_rest ? head : n;   // same MT stream order either way: the head's batches now, the rest once that many steps are issued
@@ -1214,6 +1221,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   const bool host_idx = !injected && !(device_rng && !explicit_idx);
   const int64_t rows_now = (int64_t)(a->deferred.her ? a->deferred.next : n) * a->B;
   cg->injected = injected;
+  cg->per_dev = per_dev;
   cg->host_idx = host_idx;
   cg->slot = slot;
   cg->ub = ub;
@@ -1222,7 +1230,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   // One launch starts the call: the gather reads its (<= 2 B) indices straight from the pinned block and carries the
   // control block to the device (header + the n table entries in use) — before, two staged copies and their launch
   // gaps (19 us) preceded the first gather.
-  cg->head_form = !injected && (!host_idx || rows_now <= (int64_t)a->head_batches * a->B);
+  cg->head_form = !injected && !per_dev && (!host_idx || rows_now <= (int64_t)a->head_batches * a->B);
   cg->cb_bytes = (offsetof(UploadBlock, cb) + offsetof(CtrlBlock, table) + (size_t)n * sizeof(StepCtrl) + 15) & ~(size_t)15;
   GatherCall& g = cg->g;
   g = GatherCall{};
@@ -1251,7 +1259,7 @@ int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
   } else {
     GCRL_HIP(hipMemcpyAsync(a->upload_dev, cg->ub, cg->bytes, hipMemcpyHostToDevice, st));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
-    if (!cg->injected) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st));
+    if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st));
   }
   return GCRL_OK;
 }
@@ -1459,7 +1467,7 @@ int build(gcrl_agent* a) {
       {&a->parts_c, (long long)C * a->nparts_c}, {&a->parts_a, (long long)a->nparts_a},
       {&a->hC2, (long long)C * L * BH}, {&a->gC2, 2 * BH}, {&a->bn_part, 2LL * ((B + 15) / 16) * H},
       {&a->rc_gC, (long long)C * L * BH}, {&a->rc_gA, L * BH}, {&a->ybuf, B}, {&a->pi_buf, (long long)B * a->Apad},
-      {&a->w_in, B}, {&a->td_abs, B}, {&a->red_scratch, 72LL * ((B + 255) / 256) + 64},
+      {&a->w_in, B}, {&a->td_abs, B}, {&a->per_hist, (long long)a->Mmax * B}, {&a->red_scratch, 72LL * ((B + 255) / 256) + 64},
       {&a->bn_bstat, 2LL * 2 * L * H}, {&a->bn_xchg, bn_slab_xchg_floats(H)}, {&a->bn_bar, bn_slab_bar_words(H)}, {&a->zN, BH}, {&a->hN, 2 * BH}, {&a->headN, (long long)B * 2 * a->Apad}, {&a->bn_partN, 2LL * ((B + 15) / 16) * H}};
   // row-block path: plain DDPG nets whose rows fit the 16-byte column ownership
   {
@@ -1661,6 +1669,9 @@ int build(gcrl_agent* a) {
     reg("adam_v:critic_" + s, a->adam_v + a->goff_critic + i * a->critic_stride, a->critic.numel);
   }
   reg("td_abs", a->td_abs, B);
+  reg("w_in", a->w_in, B);
+  reg("per_td_hist", a->per_hist, (long long)a->Mmax * B);                         // rows = the steps of the last device-drawn call
+  reg("per_idx_hist", reinterpret_cast<float*>(a->idx_dev()), (long long)a->Mmax * B);   // their drawn indices (uint32 bit patterns)
   if (a->sac) {
     reg("log_alpha", a->P_logalpha(), 1);
     reg("grad:log_alpha", a->grads + a->goff_alpha, 1);
@@ -1956,9 +1967,55 @@ int gcrl_agent_profile_read(gcrl_agent* a, int64_t* launches_out, double* total_
   return GCRL_OK;
 }
 
+// Device-drawn prioritised replay (per_tree.hip): the ring carries a priority tree and the caller gave no indices.  Per step, in
+// stream order: refresh of the rows pushed since the last draw, draw, weights, gather of that step's B rows, the layer-per-launch
+// step with V_WEIGHTS, priority update.  No host synchronisation and no pageable copy: the control block goes up from its pinned
+// slot, each step's beta is a kernel argument.  The draw, gather and update launches run uncaptured (a captured graph would
+// freeze beta, head, len and the draw counter); the step itself replays its graph as on the host-drawn path.
+int run_per_device(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_update_inputs* in, int64_t* tickets_out, int32_t* lens_out,
+                   hipStream_t st) {
+  GCRL_CHECK_ARG(!a->rowchain && a->Q == 1 && a->cfg.pipeline_steps == 0,
+                 "update: per_draw=\"device\" (a ring with a priority tree) needs the layer-per-launch schedule (pipeline_steps = 0) and scalar critics");
+  GCRL_CHECK_ARG(!a->xchg, "update: per_draw=\"device\" does not run under a gradient exchange");
+  GCRL_CHECK_ARG(!in || (n == 1 && !in->weights_host), "update: per_draw=\"device\": injected noise drives one step; weights come from the tree");
+  GCRL_CHECK_ARG(n >= 1, "update: n must be >= 1");
+  if (her->per->betas.size() - her->per->beta_pos < (size_t)n)    // checked before a ticket, slot or plan is consumed
+    return fail(GCRL_ERR_STATE, "update: per_draw=\"device\": %zu beta values queued for %d steps from step %lld (gcrl_per_set_betas)",
+                her->per->betas.size() - her->per->beta_pos, n, (long long)step0);
+  const int B = a->B, chunk = std::min(kMaxStepsPerCall, a->Mmax);
+  int extra = V_WEIGHTS;
+  for (int done = 0; done < n; done += chunk) {
+    const int m = std::min(chunk, n - done);
+    std::vector<StepPlan> plans;
+    a->per_call = true;
+    const int rc = begin_call(a, her, step0 + done, m, nullptr, a->xchg_scale(), st, plans, tickets_out ? tickets_out + done : nullptr,
+                              lens_out ? lens_out + done : nullptr);
+    a->per_call = false;
+    if (rc) return rc;
+    if (in) TRY(stage_injected(a, in, st, &extra));   // (injected noise / eps: device-to-device copies)
+    for (int i = 0; i < m; ++i) {
+      float beta = 0.0f;
+      (void)per_next_beta(her, &beta);
+      uint32_t* idx = a->idx_dev() + (size_t)i * B;
+      TRY(per_draw(her, B, beta, idx, a->w_in, st));
+      TRY(her_gather_update(her, idx, B, a->sa + i * a->slot_x, a->nsa + i * a->slot_x, a->spa + i * a->slot_x, a->ldx, a->rbuf + i * a->slot_rd,
+                            a->dbuf + i * a->slot_rd, st));
+      TRY(run_step(a, st, plans[i].variant | norm_bits(a) | extra, 7));
+      TRY(per_update(her, idx, a->td_abs, B, a->per_hist + (size_t)i * B, st));
+    }
+    TRY(end_call(a, st));
+  }
+  return GCRL_OK;
+}
+
 int gcrl_agent_update(gcrl_agent* a, gcrl_her* her, int64_t step, const gcrl_update_inputs* in, int64_t* ticket_out, void* stream) {
   GCRL_CHECK_ARG(a, "gcrl_agent_update: null handle");
   hipStream_t st = a->pick(stream);
+  if (her && her->per && !(in && (in->s_dev || in->idx_host))) {
+    int32_t plen = 0;
+    TRY(run_per_device(a, her, step, 1, in, ticket_out, &plen, st));
+    return plen;
+  }
   std::vector<StepPlan> plans;
   int32_t len = 0;
   TRY(begin_call(a, her, step, 1, in, a->xchg_scale(), st, plans, ticket_out, &len));
@@ -1980,6 +2037,7 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, int6
   // a process that arrived on this device after the handle was built: its kernels hold CUs, so no more waits inside launches
   if ((a->calls & 31) == 0 && !meet_device_shared()) { const int rc = gcrl_agent_get_meetings(a); if (rc < 0) return rc; }   // (probes, and switches the forms off)
   hipStream_t st = a->pick(stream);
+  if (her->per) return run_per_device(a, her, step0, n, nullptr, tickets_out, lens_out, st);
   const int chunk = std::min(kMaxStepsPerCall, a->Mmax);
   for (int done = 0; done < n; done += chunk) {
     const int m = std::min(chunk, n - done);

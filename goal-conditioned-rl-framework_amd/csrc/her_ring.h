@@ -79,6 +79,8 @@ __host__ __device__ inline uint32_t idxgen_at(const IdxGen& g, long long row) {
 
 }  // namespace gcrl
 
+struct gcrl_per_tree;
+
 struct gcrl_her {
   gcrl_her_config cfg;
   int S, A, G, SA4, S4, RW, RS, RG;   // o_ns = SA4, o_r = SA4+S4, o_d = o_r+1, o_ag = RW
@@ -95,6 +97,8 @@ struct gcrl_her {
   gcrl::IdxGen last_gen{};        // device-RNG mode: what the next gather launch computes its indices from
   bool idx_on_device = true;      // false: no index array was uploaded (device-RNG mode)
   uint64_t mutation_epoch = 0;    // bumped by every flush
+  uint64_t rows_pushed = 0;       // rows ever appended (>= len): what the priority tree measures its pending pushes against
+  gcrl_per_tree* per = nullptr;   // device-resident prioritised replay (per_tree.h), or null
 
   // index upload: pinned host slots -> idx_dev
   static constexpr int kSlots = 8;
@@ -150,6 +154,10 @@ struct gcrl_her {
 struct gcrl_normalizer;
 
 namespace gcrl {
+
+// the ring's priority tree (per_tree.hip): freed with the ring; marked stale when the rows are reloaded into other slots
+void per_release(gcrl_her* h);
+void per_mark_stale(gcrl_her* h);
 
 // device RunningNormalizer (normalizer.hip): statistics update from device rows; out[:, col0:col0+D] = normalize(x)
 // (z == null: plain copy)

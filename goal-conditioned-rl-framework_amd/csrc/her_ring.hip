@@ -687,6 +687,7 @@ int launch_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, const uin
   // deque(maxlen) bookkeeping: `total` rows appended, the oldest fell off the front
   h->head = book.head;
   h->len = book.len;
+  h->rows_pushed += (uint64_t)total;
   h->episodes_flushed += nep;
   h->mutation_epoch++;
   *rows_out = total;
@@ -855,6 +856,7 @@ gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng) {
 void gcrl_her_destroy(gcrl_her* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  gcrl::per_release(h);
   for (int i = 0; i < gcrl_her::kSlots; ++i) {
     if (h->idx_pinned[i]) (void)hipHostFree(h->idx_pinned[i]);
     if (h->epi_pinned[i]) (void)hipHostFree(h->epi_pinned[i]);
@@ -984,6 +986,7 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
   GCRL_HIP(hipGetLastError());
   book.append(1);                              // deque(maxlen): at capacity the oldest row falls off
   h->head = book.head; h->len = book.len;
+  h->rows_pushed += 1;
   h->mutation_epoch++;
   return 1;
 }
@@ -1176,6 +1179,28 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
   return prof_end(h, st, n);
 }
 
+int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* out_s, int ld_s, float* out_a, int ld_a, float* out_r,
+                        float* out_ns, int ld_ns, float* out_d, void* stream) {
+  GCRL_CHECK_ARG(h && idx_dev && out_s && out_a && out_r && out_ns && out_d, "gcrl_her_sample_dev: null argument");
+  GCRL_CHECK_ARG(n >= 1, "gcrl_her_sample_dev: n must be >= 1");
+  GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample_dev: row stride smaller than the row");
+  if (h->len < 1) return gcrl::fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
+  hipStream_t st = h->pick(stream);
+  GatherArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
+                out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns};
+  if (int rc = prof_begin(h, st)) return rc;
+  if (h->RS <= 64) {
+    int blocks = (int)std::min<long long>((n + 63) / 64, 8192);
+    hipLaunchKernelGGL(her_gather_kernel, dim3(blocks), dim3(256), 0, st, ga);
+  } else {
+    constexpr int kUnroll = 2;
+    int blocks = (int)std::min<long long>((n + 4 * 4 * kUnroll - 1) / (4 * 4 * kUnroll), 4096);
+    hipLaunchKernelGGL(her_gather_wide_kernel<kUnroll>, dim3(blocks), dim3(256), 0, st, ga);
+  }
+  GCRL_HIP(hipGetLastError());
+  return prof_end(h, st, n);
+}
+
 int gcrl_her_profile_enable(gcrl_her* h, int on) {
   GCRL_CHECK_ARG(h, "gcrl_her_profile_enable: null handle");
   if (on && h->prof_a.empty()) {
@@ -1256,7 +1281,37 @@ int gcrl_her_load_state(gcrl_her* h, const void* src_host, int64_t n) {
   GCRL_HIP(hipMemcpy(h->stage, o, stage_bytes, hipMemcpyHostToDevice)); o += stage_bytes;
   GCRL_HIP(hipMemcpy(h->ring, o, (size_t)hd.len * h->RS * sizeof(float), hipMemcpyHostToDevice));
   h->head = 0; h->len = hd.len;
+  h->rows_pushed += (uint64_t)hd.len;
+  if (h->per) gcrl::per_mark_stale(h);   // the rows moved to other slots: the priorities follow through gcrl_per_set_priorities
   h->episodes_flushed = hd.episodes_flushed; h->draws_done = hd.draws_done; h->mutation_epoch = hd.mutation_epoch + 1;
+  return GCRL_OK;
+}
+
+// gcrl_her_load_state leaves the rows at head 0; a priority tree's sums depend on WHERE its leaves lie, so a bitwise resume of the
+// device-resident prioritised replay puts a full ring's rows back at the head they were saved with (device-to-device copies)
+int gcrl_her_set_head(gcrl_her* h, int64_t head) {
+  GCRL_CHECK_ARG(h, "gcrl_her_set_head: null handle");
+  const int64_t cap = h->cfg.capacity;
+  GCRL_CHECK_ARG(head >= 0 && head < cap, "gcrl_her_set_head: head %lld outside [0, %lld)", (long long)head, (long long)cap);
+  if (head == h->head) return GCRL_OK;
+  GCRL_CHECK_ARG(h->len == cap, "gcrl_her_set_head: only a full ring has a head other than 0 (len %lld of %lld)", (long long)h->len, (long long)cap);
+  GCRL_HIP(hipDeviceSynchronize());
+  const size_t row = (size_t)h->RS * sizeof(float);
+  float* tmp = nullptr;
+  GCRL_HIP(hipMalloc((void**)&tmp, (size_t)cap * row));
+  // tmp <- the rows in logical order, then back to their slots under the new head
+  const int64_t first = cap - h->head;
+  hipError_t e = hipMemcpy(tmp, h->ring + (size_t)h->head * h->RS, (size_t)first * row, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && h->head) e = hipMemcpy((char*)tmp + (size_t)first * row, h->ring, (size_t)h->head * row, hipMemcpyDeviceToDevice);
+  const int64_t nfirst = cap - head;
+  if (e == hipSuccess) e = hipMemcpy(h->ring + (size_t)head * h->RS, tmp, (size_t)nfirst * row, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && head) e = hipMemcpy(h->ring, (char*)tmp + (size_t)nfirst * row, (size_t)head * row, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  (void)hipFree(tmp);
+  GCRL_HIP(e);
+  h->head = head;
+  h->mutation_epoch++;
+  if (h->per) gcrl::per_mark_stale(h);
   return GCRL_OK;
 }
 

@@ -1,0 +1,41 @@
+// per_tree.h — device-resident prioritised replay on a replay ring (per_tree.hip): the priority tree in HBM and the entries
+// the update engine calls between its gather and its step.  Layout and host arithmetic: per_host.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "per_host.h"
+
+struct gcrl_her;
+
+struct gcrl_per_tree {
+  gcrl::PerLayout L;
+  float* tree = nullptr;        // all levels, L.total floats
+  float alpha = 0.6f, eps = 1e-6f;
+  uint64_t draws = 0;           // draw counter: draw number of the next batch
+  uint64_t synced_rows = 0;     // the ring's rows_pushed as of the last refresh
+  bool stale = false;           // the ring was reloaded: the leaves belong to another physical order until set_priorities
+  float* p_drawn = nullptr;     // [p_cap] leaf priorities of the last draw
+  int p_cap = 0;
+  std::vector<float> betas;     // per-step beta values queued for the engine's next steps (gcrl_per_set_betas)
+  size_t beta_pos = 0;
+  int64_t launches = 0;         // kernel launches issued by this tree
+};
+
+namespace gcrl {
+
+constexpr uint64_t kPerKey = 0x5045525f54524545ull;   // "PER_TREE": key of the draw's uniform stream
+
+void per_release(gcrl_her* h);
+// priority 1.0 for the rows pushed since the last refresh, their ancestors recomputed: at most one launch up to kPerRefreshOne
+// pending rows (beyond that: one fill launch and a rebuild)
+int per_refresh(gcrl_her* h, hipStream_t st);
+// refresh, then B proportional draws -> idx_dev[B] (logical indices), then their importance-sampling weights -> w_dev[B]
+int per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, hipStream_t st);
+// leaves of idx_dev[B] <- (|td| + eps)^alpha, last occurrence wins, ancestors recomputed; hist_dev (may be null) <- td
+int per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B, float* hist_dev, hipStream_t st);
+// next queued beta of the engine's steps; false: none queued
+bool per_next_beta(gcrl_her* h, float* beta);
+
+}  // namespace gcrl

@@ -22,7 +22,7 @@ import torch
 
 from .. import _ffi
 from .._ffi import lib
-from .buffer import HERBuffer, PERBuffer, ReplayBuffer
+from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -70,6 +70,42 @@ class LazyScalar:
     __lt__ = _bin(lambda a, b: a < b)
     __gt__ = _bin(lambda a, b: a > b)
     del _bin
+
+
+class LazyTdError:
+    """td_error of a device-drawn prioritised step (per_draw="device"): the reference's [B, 1] float32 array (src/agent.py:1387),
+    fetched on first use from the engine's per-call history buffer [n][B].  The buffer belongs to the LAST update call: a read
+    after a later call has overwritten it raises TdHistoryOverwritten rather than returning another step's values."""
+    __slots__ = ("_agent", "_call", "_row", "_val")
+
+    def __init__(self, agent, call, row):
+        self._agent, self._call, self._row, self._val = agent, call, row, None
+
+    def _value(self) -> np.ndarray:
+        if self._val is None:
+            a = self._agent
+            if a is None or self._row < 0 or a._per_call != self._call:
+                raise TdHistoryOverwritten("td_error of a per_draw='device' step was read after a later update call overwrote the "
+                                           "history buffer: read it before the next update()/update_many()")
+            B = a.batch_size
+            hist = np.empty(a._per_rows * B, np.float32)
+            _ffi.check(lib.gcrl_agent_get(a._h, b"per_td_hist", hist.ctypes.data, hist.size))
+            self._val = hist.reshape(-1, B)[self._row].reshape(-1, 1).copy()
+            self._agent = None
+        return self._val
+
+    def __array__(self, dtype=None, copy=None):
+        return np.asarray(self._value(), dtype=dtype or np.float32)
+
+    @property
+    def shape(self):
+        return self._value().shape
+
+    def __getitem__(self, k):
+        return self._value()[k]
+
+    def __repr__(self):
+        return f"LazyTdError({self._value()!r})"
 
 
 class _AlphaView:
@@ -150,7 +186,21 @@ class _EngineAgent:
     def __init__(self, obs_dim: int, ac_dim: int, config, weights, nenvs: int, gradient_step: int, *,
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
-                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1, _member=None):
+                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", _member=None):
+        # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
+        # Every refusal before any device work.
+        if per_draw not in ("host", "device"):
+            raise ValueError(f"per_draw must be 'host' or 'device', got {per_draw!r}")
+        if per_draw == "device":
+            who = type(self).__name__
+            if config.buffer_type != "PER":
+                raise _ffi.GcrlError(f"{who}: per_draw: 'device' needs buffer_type 'PER', got {config.buffer_type!r}")
+            if _member is not None:
+                raise _ffi.GcrlError(f"{who}: per_draw: populations train from HER rings and do not take per_draw='device'")
+            if self.KIND_NAME == "TQC" and int(n_quantiles) > 1:
+                raise _ffi.GcrlError(f"{who}: per_draw: the distributional TQC variant (n_quantiles > 1) has no importance-weighted loss; "
+                                     "per_draw='device' needs scalar critics")
+        self.per_draw = per_draw
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
         self.device = "cuda"
@@ -164,7 +214,7 @@ class _EngineAgent:
 
         # buffer factory of the reference (src/agent.py:1214-1228 and its copies)
         if config.buffer_type == "PER":
-            self.buffer = PERBuffer(config.max_len, config.alpha, rng=rng, seed=seed, device_index=device_index)
+            self.buffer = PERBuffer(config.max_len, config.alpha, draw=per_draw, rng=rng, seed=seed, device_index=device_index)
             pipeline = 0      # importance-sampling weights enter the loss in the layer-per-launch schedule
         elif config.buffer_type == "REPLAY":
             self.buffer = ReplayBuffer(config.max_len, rng=rng, seed=seed, device_index=device_index)
@@ -195,6 +245,8 @@ class _EngineAgent:
         self._metric_cache: dict[int, list[float]] = {}
         self._live = collections.deque()      # (ticket, n) of returned tuples, oldest first
         self._lazy: dict[int, list] = {}      # ticket -> weak references to its unresolved LazyScalars
+        self._per_call = 0                    # per_draw="device": number of the last update call (owner of the td history buffer)
+        self._per_rows = min(128, max(1, self.gradient_step))   # steps the history buffer holds (the engine's steps per call)
 
         self.noise_std = config.noise_std
         self.noise_clamp = config.noise_clamp
@@ -324,6 +376,8 @@ class _EngineAgent:
         inputs, keep = self._inject(batch, noise, eps_next, eps_cur)
         her = None
         per = isinstance(self.buffer, PERBuffer) and batch is None
+        if per and self.buffer.draw_mode == "device":
+            return self._update_per_device(step, 1, inputs)[0]
         if per:   # src/agent.py:1380-1387: the prioritised draw (host, numpy-exact), weights into the critic losses
             indices, weights = self.buffer.draw(self.batch_size, self.beta)
             if inputs is None:
@@ -355,9 +409,51 @@ class _EngineAgent:
             out = out[:i] + (td,) + out[i + 1:]
         return out
 
+    def _update_per_device(self, step0: int, n: int, inputs):
+        """per_draw="device": n steps as ONE native call; per step the engine refreshes the pushed rows' priorities, draws, weighs,
+        gathers, steps and updates the priorities on the device (csrc/agent.hip run_per_device).  No read-back: td_error is lazy.
+        Step i uses the beta the schedule left after step i - 1, as update() does."""
+        her = self.buffer.handle
+        assert her is not None and len(self.buffer) >= self.batch_size, "[ERROR] Not enough in buffer to sample"
+        betas = np.empty(n, np.float32)
+        for i in range(n):
+            betas[i] = self.beta
+            self.beta_scheduler(step0 + i)
+        _ffi.check(lib.gcrl_per_set_betas(her, betas.ctypes.data, n))
+        tickets = (C.c_int64 * n)()
+        lens = (C.c_int32 * n)()
+        if n == 1:
+            t1 = C.c_int64(-1)
+            lens[0] = _ffi.check(lib.gcrl_agent_update(self._h, her, int(step0), C.byref(inputs) if inputs is not None else None,
+                                                       C.byref(t1), _ffi.stream_handle()))
+            tickets[0] = t1.value
+        else:
+            _ffi.check(lib.gcrl_agent_update_n(self._h, her, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
+        self._per_call += 1
+        if self._sac:
+            self.actor.num_batches_tracked += sum(1 + (1 if l == 9 else 0) for l in lens)
+        # the history buffer holds the last chunk of the call (the engine runs at most _per_rows steps per chunk)
+        last0 = ((n - 1) // self._per_rows) * self._per_rows
+        outs = []
+        for i, (t, l) in enumerate(zip(tickets, lens)):
+            out = self._tuple(int(t), int(l))
+            k = self.TD_INDEX[int(l)]
+            outs.append(out[:k] + (LazyTdError(self, self._per_call, i - last0),) + out[k + 1:])
+        return outs
+
+    def drawn_indices(self, n: int = 1) -> np.ndarray:
+        """per_draw="device": the logical row indices the last update call drew, [n, B] (reads back; for tests and logging)."""
+        B = self.batch_size
+        raw = np.empty(self._per_rows * B, np.float32)
+        _ffi.check(lib.gcrl_agent_get(self._h, b"per_idx_hist", raw.ctypes.data, raw.size))
+        return raw.view(np.uint32).reshape(-1, B)[:n].copy()
+
     def update_many(self, step0: int, n: int):
         """The trainer's `for _ in range(gradient_step): update(step)` loop (src/env.py:384-385) as
         one call: all n batches are drawn (same RNG stream order) and gathered by one launch."""
+        if isinstance(self.buffer, PERBuffer) and self.buffer.draw_mode == "device":
+            self.set_train()
+            return self._update_per_device(step0, n, None)
         if isinstance(self.buffer, PERBuffer):   # the priorities change after every step: one draw per step (src/agent.py:1380-1387)
             return [self.update(step0 + i) for i in range(n)]
         self.set_train()

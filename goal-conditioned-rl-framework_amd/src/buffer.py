@@ -478,26 +478,120 @@ class ReplayBuffer(_RingState):
         return s, a, ns, r, d
 
 
-class PERBuffer(ReplayBuffer):
-    """Drop-in for the reference's proportional PERBuffer (src/buffer.py:38-89).  Rows live in the HBM ring; the
-    priorities and the draw stay on the host in numpy, operation for operation as the reference writes them
-    (`np.random.choice(N, B, p=P)` consumes numpy's global stream; float32 priorities / weights), because the
-    priority update needs the per-sample |td| on the host anyway (one read-back per step, as in the reference)."""
+class TdHistoryOverwritten(RuntimeError):
+    """A lazily fetched td_error was read after a later update call reused the device history buffer."""
 
-    def __init__(self, max_len: int, alpha: float, **kw):
+
+class PERBuffer(ReplayBuffer):
+    """Drop-in for the reference's proportional PERBuffer (src/buffer.py:38-89).  Rows live in the HBM ring.
+
+    draw="host" (default, the parity mode): the priorities and the draw stay on the host in numpy, operation for operation as
+    the reference writes them (`np.random.choice(N, B, p=P)` consumes numpy's global stream; float32 priorities / weights),
+    with one |td| read-back per step, as in the reference.
+
+    draw="device": priorities, draw, importance-sampling weights and the priority update are device state and HIP kernels on a
+    priority tree beside the ring (csrc/per_tree.hip).  NOT the reference's index stream: the draw is defined by the restatement
+    tests/per_tree_ref.py (a counter hash keyed by the buffer's seed and a draw counter).  `sample` returns weights and indices
+    as CUDA tensors, `update_priorities` takes device tensors, and nothing synchronises with the host."""
+
+    def __init__(self, max_len: int, alpha: float, draw: str = "host", **kw):
+        if draw not in ("host", "device"):
+            raise ValueError(f"PERBuffer: draw must be 'host' or 'device', got {draw!r}")
         super().__init__(max_len, **kw)
-        from collections import deque
-        self.priorities = deque(maxlen=int(max_len))
+        self.draw_mode = draw
         self.alpha = alpha
         self.epsilon = 1e-6
+        if draw == "host":
+            from collections import deque
+            self.priorities = deque(maxlen=int(max_len))
 
+    # ------------------------------------------------------------------ device mode
+    def _ensure(self, S: int, A: int):
+        fresh = self._h is None
+        super()._ensure(S, A)
+        if fresh and self.draw_mode == "device":
+            _ffi.check(lib.gcrl_per_attach(self._h, float(self.alpha), float(self.epsilon)))
+
+    def _need_device(self, what: str):
+        if self.draw_mode != "device":
+            raise _ffi.GcrlError(f"PERBuffer.{what} needs draw='device' (this buffer keeps its priorities on the host)")
+        if self._h is None:
+            raise _ffi.GcrlError(f"PERBuffer.{what}: nothing has been pushed yet")
+
+    def get_priorities(self) -> np.ndarray:
+        """Priorities in logical order (0 = oldest row), float32; device mode reads them back (synchronises)."""
+        if self.draw_mode == "host":
+            return np.array(self.priorities, dtype=np.float32)
+        self._need_device("get_priorities")
+        out = np.empty(len(self), np.float32)
+        _ffi.check(lib.gcrl_per_get_priorities(self._h, out.ctypes.data, out.size))
+        return out
+
+    def set_priorities(self, values):
+        """Replace every stored row's priority (logical order); device mode rebuilds the tree, one launch per level."""
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if self.draw_mode == "host":
+            assert v.size == len(self.priorities)
+            self.priorities.clear()
+            self.priorities.extend(np.float32(p) for p in v)
+            return
+        self._need_device("set_priorities")
+        _ffi.check(lib.gcrl_per_set_priorities(self._h, v.ctypes.data, v.size))
+
+    def tree_levels(self):
+        """Test helper (device mode): every level of the priority tree as stored, leaves first."""
+        self._need_device("tree_levels")
+        out = []
+        for k in range(int(lib.gcrl_per_levels(self._h))):
+            a = np.empty(int(lib.gcrl_per_level_size(self._h, k)), np.float32)
+            _ffi.check(lib.gcrl_per_read_level(self._h, k, a.ctypes.data, a.size))
+            out.append(a)
+        return out
+
+    @property
+    def draw_counter(self) -> int:
+        self._need_device("draw_counter")
+        return int(lib.gcrl_per_get_draw_counter(self._h))
+
+    @draw_counter.setter
+    def draw_counter(self, v: int):
+        self._need_device("draw_counter")
+        _ffi.check(lib.gcrl_per_set_draw_counter(self._h, int(v)))
+
+    def save_state(self, path: str) -> dict:
+        meta = super().save_state(path)
+        meta["per_draw"] = self.draw_mode
+        if self.draw_mode == "device" and self._h is not None:
+            meta["priorities"] = [float(p) for p in self.get_priorities()]
+            meta["per_draw_counter"] = self.draw_counter
+            meta["per_head"] = int(lib.gcrl_her_head(self._h))    # the tree's sums depend on where the leaves lie
+        return meta
+
+    def load_state(self, path: str, meta: dict):
+        if meta.get("per_draw", "host") != self.draw_mode:
+            raise ValueError(f"PERBuffer.load_state: the state was saved with draw={meta.get('per_draw', 'host')!r}, this buffer has draw={self.draw_mode!r}")
+        super().load_state(path, meta)
+        if self.draw_mode == "device" and self._h is not None and "priorities" in meta:
+            _ffi.check(lib.gcrl_her_set_head(self._h, int(meta.get("per_head", 0))))
+            self.set_priorities(np.asarray(meta["priorities"], dtype=np.float32))
+            self.draw_counter = int(meta.get("per_draw_counter", 0))
+
+    # ------------------------------------------------------------------ reference surface
     def push(self, state, action, reward, next_state, done):
         super().push(state, action, reward, next_state, done)
-        self.priorities.append(1.0)
+        if self.draw_mode == "host":
+            self.priorities.append(1.0)      # (device mode: the tree gives a pushed row's slot 1.0 at its next refresh)
 
     def draw(self, batch_size: int, beta: float):
-        """-> (indices, weights float32 [B]) exactly as src/buffer.py:50-65."""
+        """host mode -> (indices, weights float32 [B]) exactly as src/buffer.py:50-65; device mode -> (indices int32 [B],
+        weights float32 [B]) as CUDA tensors, drawn by the priority tree in stream order."""
         assert len(self) >= batch_size, "Not enough in buffer to sample"
+        if self.draw_mode == "device":
+            dev = torch.device("cuda", self.device_index)
+            idx = torch.empty(batch_size, dtype=torch.int32, device=dev)
+            w = torch.empty(batch_size, dtype=torch.float32, device=dev)
+            _ffi.check(lib.gcrl_per_draw(self._h, int(batch_size), float(beta), idx.data_ptr(), w.data_ptr(), _ffi.stream_handle()))
+            return idx, w
         N = len(self)
         P = np.array(self.priorities, dtype=np.float32)
         P_sum = P.sum()
@@ -510,13 +604,32 @@ class PERBuffer(ReplayBuffer):
         weights /= weights.max()
         return indices, weights
 
+    def _gather_dev(self, idx: torch.Tensor):
+        S, A = self._dims
+        n, dev = idx.numel(), idx.device
+        out = (torch.empty((n, S), dtype=torch.float32, device=dev), torch.empty((n, A), dtype=torch.float32, device=dev),
+               torch.empty((n, 1), dtype=torch.float32, device=dev), torch.empty((n, S), dtype=torch.float32, device=dev),
+               torch.empty((n, 1), dtype=torch.float32, device=dev))
+        _ffi.check(lib.gcrl_her_sample_dev(self._h, n, idx.data_ptr(), out[0].data_ptr(), S, out[1].data_ptr(), A, out[2].data_ptr(),
+                                           out[3].data_ptr(), S, out[4].data_ptr(), _ffi.stream_handle()))
+        return out
+
     def sample(self, batch_size: int, beta: float):
         indices, weights = self.draw(batch_size, beta)
+        if self.draw_mode == "device":
+            return self._gather_dev(indices) + (weights.unsqueeze(-1), indices)
         batch = self._gather(batch_size, indices)
         w = torch.as_tensor(weights, dtype=torch.float32).unsqueeze(-1).to(batch[0].device)
         return batch + (w, indices)
 
     def update_priorities(self, indices, priorities):
+        if self.draw_mode == "device":
+            dev = torch.device("cuda", self.device_index)
+            idx = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+            td = torch.as_tensor(priorities).to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+            assert idx.numel() == td.numel()
+            _ffi.check(lib.gcrl_per_update(self._h, idx.data_ptr(), td.data_ptr(), idx.numel(), _ffi.stream_handle()))
+            return
         priorities = np.asarray(priorities).squeeze(-1)
         for index, priority in zip(indices, priorities):
             self.priorities[index] = (abs(priority) + self.epsilon) ** self.alpha

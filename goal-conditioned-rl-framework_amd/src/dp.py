@@ -98,6 +98,9 @@ class DataParallelUpdater:
         instead of each rank's own rows — G ranks x B rows then equal 1 rank x G*B rows for these agents too, at the price of
         one small exchange per BatchNorm layer and pass on the step's critical path."""
         from .. import _ffi
+        if getattr(agent, "per_draw", "host") == "device":   # refused before any collective or device work
+            raise _ffi.GcrlError("gcrl_amd.dp: per_draw: an agent with per_draw='device' draws its batches from its own priority tree inside "
+                                 "the update call; DataParallelUpdater does not drive it (use per_draw='host')")
         self._ffi = _ffi
         self.agent = agent
         self.group = group

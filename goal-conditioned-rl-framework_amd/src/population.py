@@ -73,11 +73,14 @@ class _Population:
     MERGE_GATHER_FROM = MAX_MEMBERS + 1
 
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
-                 seeds=None, device_index: int = 0, shared_ring: bool = False):
+                 seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host"):
         configs = list(configs)
         P = len(configs)
         self.shared_ring = bool(shared_ring)
         # every refusal before any device work
+        if per_draw != "host":
+            self._refuse("per_draw", f"populations train from HER rings; the device-resident prioritised draw (per_draw={per_draw!r}) is a "
+                                     "single-agent mode")
         if not 1 <= P <= MAX_MEMBERS:
             self._refuse("members", f"a population has 1..{MAX_MEMBERS} members, got {P}")
         seeds = [None] * P if seeds is None else list(seeds)

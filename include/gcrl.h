@@ -802,6 +802,47 @@ int gcrl_td3_smooth_f32(float* act_dev, int ld, int B, int A, const float* eps_d
  * update is not given injected noise.  Not torch's stream; restated in oracle/device_rng_oracle.py and tested against it. */
 int gcrl_hash_normal_fill(uint64_t seed, uint64_t ctr0, int64_t n, float* out_dev, void* stream);
 
+/* ---- Device-resident prioritised replay (csrc/per_tree.hip; DESIGN.md "Device-resident prioritised replay").
+ * A tree of fp32 sums over one priority per PHYSICAL ring slot lives in HBM beside the ring: the proportional draw, the
+ * importance-sampling weights and the priority update of the reference's PERBuffer (src/buffer.py:38-89) are HIP kernels on
+ * it.  NOT the reference's index stream (np.random.choice): a device mode beside the host-drawn parity mode, defined by the
+ * restatement tests/per_tree_ref.py.  A pushed row's slot gets priority 1.0; never-filled slots hold 0 and are never drawn.
+ *
+ * attach: build the (all-zero) tree for the ring's capacity; rows already in the ring count as pushed (priority 1.0).
+ * alpha, eps: p = (|td| + eps)^alpha of the update. */
+int gcrl_per_attach(gcrl_her* h, float alpha, float eps);
+int gcrl_per_attached(const gcrl_her* h);
+/* number of levels (leaves = level 0) and the padded entry count of one (a multiple of 64; -1: no such level) */
+int gcrl_per_levels(const gcrl_her* h);
+int64_t gcrl_per_level_size(const gcrl_her* h, int level);
+/* In stream order: priority 1.0 for the rows pushed since the last draw (at most one launch), B proportional draws ->
+ * idx_dev[B] (logical indices, what the gather reads), their weights (N p / total)^(-beta) / max -> w_dev[B] (may be null).
+ * Advances the draw counter by one.  No host synchronisation.  GCRL_ERR_NOT_ENOUGH when the ring holds fewer than B rows. */
+int gcrl_per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, void* stream);
+/* leaf of idx_dev[b] <- (|td_dev[b]| + eps)^alpha, the LAST occurrence of a duplicated index wins (src/buffer.py:86-89), the
+ * touched ancestors recomputed; one launch, no host synchronisation. */
+int gcrl_per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B, void* stream);
+/* The beta values of the update engine's next steps on this ring, one per step, consumed in order by the device-drawn path
+ * of the agent update entries below (they travel as kernel arguments). */
+int gcrl_per_set_betas(gcrl_her* h, const float* betas_host, int n);
+/* priorities in logical order (0 = oldest row) on host arrays of exactly the ring's length; both synchronise.  set rebuilds
+ * the whole tree (one launch per level), refuses negative / non-finite values and an all-zero array. */
+int gcrl_per_get_priorities(gcrl_her* h, float* out_host, int64_t n);
+int gcrl_per_set_priorities(gcrl_her* h, const float* in_host, int64_t n);
+/* one level as stored (n = its padded size), pending pushes applied first; for tests and state */
+int gcrl_per_read_level(gcrl_her* h, int level, float* out_host, int64_t n);
+/* gcrl_her_sample's gather over n logical indices that are already on the device (each < capacity; what gcrl_per_draw wrote) */
+int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* out_s, int ld_s, float* out_a, int ld_a,
+                        float* out_r, float* out_ns, int ld_ns, float* out_d, void* stream);
+/* Move a FULL ring's rows so that logical row 0 lies at slot `head` (gcrl_her_load_state leaves it at 0).  The tree's sums depend
+ * on where the leaves lie: a bitwise resume restores the saved head before gcrl_per_set_priorities.  Synchronises. */
+int gcrl_her_set_head(gcrl_her* h, int64_t head);
+/* the draw counter: number of the next draw (-1: no tree) */
+int64_t gcrl_per_get_draw_counter(const gcrl_her* h);
+int gcrl_per_set_draw_counter(gcrl_her* h, int64_t counter);
+/* kernel launches the tree has issued so far (-1: no tree) */
+int64_t gcrl_per_launches(const gcrl_her* h);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);
