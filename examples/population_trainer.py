@@ -31,7 +31,7 @@ from trainer_standin import PointReachVecEnv  # noqa: E402
 
 
 def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
-          seed=0, verbose=True, pbt=0, shared_ring=False):
+          seed=0, verbose=True, pbt=0, shared_ring=False, relabel="push"):
     import gcrl_amd
     from gcrl_amd.src.synthetic import agent_config as make_config
     from gcrl_amd.src.utils import DeviceRunningNormalizer
@@ -44,9 +44,12 @@ def train(agent_name="DDPG", members=4, num_envs=8, cycles=40, max_episode=8, gr
                         tau=0.05, grad_clip=10.0, actor_lr=1e-3 * (1 + 0.25 * i), critic_lr=1e-3 * (1 + 0.25 * i),
                         ac_update_freq=1 if agent_name == "DDPG" else 2, policy_noise=0.2 if agent_name == "TD3" else 0.0)
             for i in range(members)]
+    if relabel == "sample":   # the rings then count real transitions: the same episodes resident in 1 / (1 + k_future) of the rows
+        for c in cfgs:
+            c.max_len //= 1 + c.k_future
     cls = dict(DDPG=gcrl_amd.DDPGPopulation, TD3=gcrl_amd.TD3Population, SAC=gcrl_amd.SACPopulation, TQC=gcrl_amd.TQCPopulation)[agent_name]
     pop = cls(e0.obs_dim + e0.goal_dim, e0.ac_dim, cfgs, num_envs, gradient_step, rng="engine", seeds=[seed + i for i in range(members)],
-              shared_ring=shared_ring)
+              shared_ring=shared_ring, relabel=relabel)
     # (shared_ring: every member's .buffer is the one ring: its normalisers and reward are set once)
     for m, env in zip(pop.members[:1] if shared_ring else pop.members, envs):   # what GoalEnvHER.__init__ injects (src/env.py:93-105), device normalisers
         m.buffer.obs_normalizer = DeviceRunningNormalizer(env.obs_dim)
@@ -117,9 +120,11 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--pbt", type=int, default=0, metavar="N", help="every N cycles the bottom quarter exploits the top quarter and explores (0: off)")
     ap.add_argument("--shared-ring", action="store_true", help="all members learn from one replay ring that all their envs fill")
+    ap.add_argument("--relabel", default="push", choices=["push", "sample"],
+                    help="push: relabelled copies stored at every flush (the reference's form); sample: rows stored once, relabelled when a batch is drawn")
     args = ap.parse_args()
     out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, pbt=args.pbt,
-                shared_ring=args.shared_ring)
+                shared_ring=args.shared_ring, relabel=args.relabel)
     print(f"{args.agent} x {args.members}: success over the last 10 cycles " + " ".join(f"{s:.2f}" for s in out["success"]) +
           f"; {out['env_steps']} env steps in aggregate ({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} "
           f"gradient steps in aggregate ({out['gradient_steps_per_s']:.0f}/s in the update phase), {out['wall_s']:.1f} s; "

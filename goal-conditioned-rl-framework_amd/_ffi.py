@@ -99,6 +99,12 @@ PROTOTYPES = {
     "gcrl_cosine_lr_next": (_f64, [_f64, _f64, _f64, _i64, _i64]),
     "gcrl_ringbook_sim": (C.c_int, [_i64, _i64, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "gcrl_her_create": (_vp, [C.POINTER(HerConfig), _vp]),
+    "gcrl_her_create_relabel": (_vp, [C.POINTER(HerConfig), _vp, C.c_int]),
+    "gcrl_her_relabel_mode": (C.c_int, [_vp]),
+    "gcrl_her_get_relabel_counter": (_u64, [_vp]),
+    "gcrl_her_set_relabel_counter": (C.c_int, [_vp, _u64]),
+    "gcrl_her_gather_update": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gcrl_her_read_tails": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "gcrl_her_destroy": (None, [_vp]),
     "gcrl_her_len": (_i64, [_vp]),
     "gcrl_her_head": (_i64, [_vp]),

@@ -1237,6 +1237,10 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   g.h = her;
   if (!injected) g.gen = her->last_gen;   // (device-RNG mode: this member's draws, also when other members share the ring)
   g.n = rows_now;
+  if (!injected && !per_dev && her->relabel_mode == GCRL_RELABEL_SAMPLE) {   // the relabel stream's counter as of this member's turn (her_ring.h)
+    g.ctr = her->relabel_ctr;
+    her->relabel_ctr += (uint64_t)rows_now;
+  }
   g.sa = a->sa; g.nsa = a->nsa; g.spa = a->rowchain ? nullptr : a->spa; g.ldx = a->ldx; g.r = a->rbuf; g.d = a->dbuf;
   return GCRL_OK;
 }
@@ -1254,12 +1258,12 @@ int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
   const GatherCall& g = cg->g;
   call_gather_form(a, cg, cg->head_form);
   if (cg->head_form) {
-    TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes));
+    TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
   } else {
     GCRL_HIP(hipMemcpyAsync(a->upload_dev, cg->ub, cg->bytes, hipMemcpyHostToDevice, st));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
-    if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st));
+    if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, nullptr, nullptr, 0, &g.ctr));
   }
   return GCRL_OK;
 }

@@ -740,6 +740,8 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
   GCRL_CHECK_ARG(s->expr == d->expr, "gcrl_pop_clone: %s: member %d's ring has %lld, member %d's %lld", field, src[k], (long long)s->expr, dst[k], (long long)d->expr)
       GCRL_RING_SAME(cfg.capacity, "capacity");
       GCRL_RING_SAME(S, "state_dim"); GCRL_RING_SAME(A, "action_dim"); GCRL_RING_SAME(G, "goal_dim");
+      if (s->relabel_mode != d->relabel_mode)   // (sample-time relabelling: the records carry tails the other mode's do not)
+        return fail(GCRL_ERR_STATE, "gcrl_pop_clone: relabel: member %d's ring has relabel mode %d, member %d's %d", src[k], s->relabel_mode, dst[k], d->relabel_mode);
       GCRL_RING_SAME(RS, "record_floats"); GCRL_RING_SAME(RG, "staged_record_floats");
       GCRL_RING_SAME(cfg.nenvs, "nenvs"); GCRL_RING_SAME(cfg.flush_len, "flush_len"); GCRL_RING_SAME(cfg.k_future, "k_future");
 #undef GCRL_RING_SAME
@@ -795,6 +797,7 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
       hd->staged = hs->staged;
       hd->head = 0; hd->len = hs->len;
       hd->episodes_flushed = hs->episodes_flushed; hd->draws_done = hs->draws_done; hd->mutation_epoch = hs->mutation_epoch + 1;
+      hd->relabel_ctr = hs->relabel_ctr;
     }
   }
   // the launch closes the work so far of every member involved: a destination's next update, acting or metrics call, and a source's

@@ -12,6 +12,23 @@
 //
 // Staging: per env, up to flush_len records of RG = roundup(RW+G, 16) floats: the ring record's
 // RW = SA4+S4+2 leading floats, then ag (G)          (the dg column is the goal slot of s itself)
+//
+// Sample-time relabelling (relabel_mode == GCRL_RELABEL_SAMPLE; kernels in her_relabel.hip).  The ring stores an episode's T
+// ORIGINAL rows only; a record carries a tail behind its RW leading floats — ag (G floats, the staged achieved goal) and
+// `remaining` (one float holding the integer T-1-i) — so RS = roundup(RW+G+1, 16).  The leading RW floats keep the layout above:
+// whatever reads only them (read_rows, the clone kernels, save / load by whole records) is unchanged.
+// INVARIANT the relabelling gathers rest on: an episode's rows are appended by ONE flush, contiguously and in step order, and
+// eviction is FIFO.  So if row i of an episode is alive, rows i+1 .. T-1 of that episode are alive, at physical slots
+// (phys_i + 1 .. phys_i + remaining) mod cap.  Eviction of an episode's OLDEST rows is therefore harmless, and so is load_state's
+// re-laying of the rows at head 0 (it keeps the logical order).  Every address a gather forms stays inside the ring whatever a
+// tail holds: `remaining` is clamped to [0, min(flush_len, cap) - 1] after the load and the future slot phys + f is brought back
+// into range by compare-and-subtract.  A flush in this mode draws nothing: the MT stream is not consumed by it.
+// The relabel rule, for the c-th row ever gathered from the ring in this mode (relabel_ctr, a 64-bit counter the host advances by
+// n when it issues a launch of n rows; it travels as a kernel argument, as IdxGen does), K = kRelabelStream:
+//     relabel = rem > 0 && hash_below(seed, K, 2c, k_future + 1) != 0        (share k/(k+1): the reference's 1 original : k copies)
+//     f       = 1 + hash_below(seed, K, 2c + 1, rem);   fut = phys + f (mod cap)
+// a relabelled row takes record fut's tail ag as the goal of s and of ns, its reward by her_flush_kernel's arithmetic from the two
+// tails, done = 0.  Restated in tests/her_relabel_ref.py, which is the definition.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +53,8 @@ __host__ __device__ inline uint32_t hash_below(uint64_t seed, uint64_t stream, u
   uint64_t h = mix64(mix64(seed ^ (stream * 0xd1342543de82ef95ull)) + ctr);
   return (uint32_t)(((h >> 32) * (uint64_t)n) >> 32);  // multiply-high range reduction
 }
+
+constexpr uint64_t kRelabelStream = 0x52454c4142454c21ull;   // stream id of the sample-time relabel draws ("RELABEL!")
 
 // device-RNG batch draw: batch element t of draw d is pi_{seed,d}(t), pi a keyed permutation of [0, n)
 // (a 4-round balanced Feistel network over the next even power of two, cycle-walked back into range).
@@ -84,6 +103,8 @@ struct gcrl_per_tree;
 struct gcrl_her {
   gcrl_her_config cfg;
   int S, A, G, SA4, S4, RW, RS, RG;   // o_ns = SA4, o_r = SA4+S4, o_d = o_r+1, o_ag = RW
+  int relabel_mode = 0;               // GCRL_RELABEL_*
+  uint64_t relabel_ctr = 0;           // sample mode: rows ever gathered from this ring (the relabel stream's counter)
   gcrl_mt* rng = nullptr;
   bool own_rng = false;
   hipStream_t stream = nullptr;
@@ -180,14 +201,28 @@ int her_upload_indices(gcrl_her* h, int B, int M, const uint32_t* idx_host, hipS
 // (pinned host) to cp_dst (device) — the call's control block travels with its first gather instead of as copies before it.
 int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa, float* nsa,
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src = nullptr,
-                      void* cp_dst = nullptr, size_t cp_bytes = 0);
+                      void* cp_dst = nullptr, size_t cp_bytes = 0, const uint64_t* relabel_ctr = nullptr);
+// A ring in sample-time relabelling mode takes her_gather_relabel_kernel instead (her_relabel.hip).  relabel_ctr == null: the
+// launch's first row is the ring's relabel_ctr, which advances by n; otherwise *relabel_ctr, and the ring's counter is left
+// alone (the planner of the call advanced it: GatherCall::ctr).
+
+// sample-time relabelling mode (her_relabel.hip): the flush of `nep` staged episodes (T rows each, bookkeeping included), the
+// update engine's gather and the public sample's, each starting at relabel counter `ctr`; the indices are idx or, when null,
+// h->last_gen's
+int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipStream_t st, int64_t* rows_out);
+int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, int64_t n, float* sa, float* nsa, float* spa, int ldx,
+                              float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
+int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
+                       float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
 
 // One her_gather_update call stated before it is issued (the update engine's begin_call plans it, gcrl_pop_update_n issues the
 // members' calls together).  `gen` is the ring's IdxGen as of the member's turn: members that share a ring each keep their own.
+// `ctr` likewise is the ring's relabel counter as of the member's turn (sample-time relabelling mode).
 struct GatherCall {
   gcrl_her* h = nullptr;
   const uint32_t* idx = nullptr;
   IdxGen gen{};
+  uint64_t ctr = 0;
   int64_t n = 0;
   float *sa = nullptr, *nsa = nullptr, *spa = nullptr;
   int ldx = 0;
@@ -199,7 +234,8 @@ constexpr int kGatherPopMax = 16;   // members of one population gather launch (
 // The gathers of P members as ONE her_gather_update_pop_kernel launch (grid (ceil(rows / 64), P), member = blockIdx.y; the head
 // form when any member carries a side copy); given the same indices, bit for bit the members' own her_gather_update launches.
 // *merged says whether that launch was issued: with P == 1, unequal record layouts, a ring with gather timing on or the
-// development gather variants, the members' own launches run in member order instead.
+// development gather variants, the members' own launches run in member order instead.  So they do when any ring is in
+// sample-time relabelling mode (no merged launch for that mode).
 int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merged);
 
 // gcrl_pop_process_step (her_ring.hip): one vector-env step of `members` rings as ONE her_process_step_pop_kernel launch (workgroup m =

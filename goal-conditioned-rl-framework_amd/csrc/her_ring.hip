@@ -588,6 +588,7 @@ int ensure_index_capacity(gcrl_her* h, size_t rows) {
 int launch_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, const uint8_t* const* futs,
                  hipStream_t st, int64_t* rows_out) {
   const gcrl_her_config& c = h->cfg;
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE) return gcrl::her_relabel_flush(h, nep, envs, Ts, st, rows_out);   // T rows per episode, no picks drawn
   FlushArgs fa;
   std::memset(&fa, 0, sizeof(fa));
   fa.ring = h->ring;
@@ -737,10 +738,18 @@ int her_upload_indices(gcrl_her* h, int B, int M, const uint32_t* idx_host, hipS
 }
 
 int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa, float* nsa,
-                      float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes) {
+                      float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes,
+                      const uint64_t* relabel_ctr) {
   if (cp_bytes % 16 != 0 || (cp_bytes && (!cp_src || !cp_dst))) return fail(GCRL_ERR_ARG, "her_gather_update: bad side copy (%zu bytes)", cp_bytes);
   if (ldx != h->SA4) return fail(GCRL_ERR_ARG, "her_gather_update: batch row stride %d != roundup(S+A,4) = %d", ldx, h->SA4);
   if (int rc = prof_begin(h, st)) return rc;
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
+    uint64_t ctr = h->relabel_ctr;
+    if (relabel_ctr) ctr = *relabel_ctr;
+    else h->relabel_ctr += (uint64_t)n;
+    if (int rc = her_relabel_gather_update(h, idx_dev, ctr, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
+    return prof_end(h, st, n);
+  }
   GatherUpdArgs ga{h->ring, idx_dev, h->last_gen, n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, ldx, sa, nsa, spa, r, d,
                    (const uint4*)cp_src, (uint4*)cp_dst, (int)(cp_bytes / 16)};
   const int blocks = (int)((n + 63) / 64);                                              // 16 rows per wave, 4 waves per block
@@ -765,12 +774,13 @@ int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merg
     if (g.ldx != g.h->SA4) return fail(GCRL_ERR_ARG, "her_gather_update_pop: member %d: batch row stride %d != roundup(S+A,4) = %d", i, g.ldx, g.h->SA4);
     // one x extent and one LDS tile for all: equal record layouts; a ring that times its gather launches keeps its own launch
     one = one && !g.h->prof && g.h->SA4 == c[0].h->SA4 && g.h->S4 == c[0].h->S4 && g.h->RS == c[0].h->RS;
+    one = one && g.h->relabel_mode != GCRL_RELABEL_SAMPLE;   // sample-time relabelling has no merged launch
   }
   if (!one) {
     for (int i = 0; i < P; ++i) {
       const GatherCall& g = c[i];
       g.h->last_gen = g.gen;   // (members sharing a ring: each launch computes its own member's draws)
-      if (int rc = her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes)) return rc;
+      if (int rc = her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr)) return rc;
     }
     return GCRL_OK;
   }
@@ -806,9 +816,15 @@ int gcrl_device_count(void) {
   return n;
 }
 
-gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng) {
+gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng) { return gcrl_her_create_relabel(cfg, rng, GCRL_RELABEL_PUSH); }
+
+gcrl_her* gcrl_her_create_relabel(const gcrl_her_config* cfg, gcrl_mt* rng, int mode) {
   auto bad = [](const char* m) -> gcrl_her* { gcrl::fail(GCRL_ERR_ARG, "gcrl_her_create: %s", m); return nullptr; };
   if (!cfg) return bad("null config");
+  if (mode != GCRL_RELABEL_PUSH && mode != GCRL_RELABEL_SAMPLE) return bad("mode: GCRL_RELABEL_PUSH or GCRL_RELABEL_SAMPLE required");
+  if (mode == GCRL_RELABEL_SAMPLE && cfg->reward_kind != GCRL_REWARD_SPARSE && cfg->reward_kind != GCRL_REWARD_DENSE)
+    return bad("compute_reward: sample-time relabelling (GCRL_RELABEL_SAMPLE) computes the relabel rewards in the gather kernel and takes the "
+               "built-in sparse or dense reward only, not a host callback (GCRL_REWARD_HOST)");
   if (cfg->state_dim < 1 || cfg->action_dim < 1 || cfg->action_dim > 16) return bad("state_dim >= 1 and 1 <= action_dim <= 16 required");
   if (cfg->goal_dim < 1 || cfg->goal_dim > kMaxG || cfg->goal_dim > cfg->state_dim) return bad("goal_dim must be 1..8 and <= state_dim");
   if (cfg->capacity < 1 || cfg->capacity >= (1ll << 32)) return bad("capacity must be in [1, 2^32)");
@@ -826,7 +842,8 @@ gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng) {
   h->SA4 = gcrl::round_up(h->S + h->A, 4);
   h->S4 = gcrl::round_up(h->S, 4);
   h->RW = h->SA4 + h->S4 + 2;
-  h->RS = gcrl::round_up(h->RW, 16);
+  h->relabel_mode = mode;
+  h->RS = gcrl::round_up(mode == GCRL_RELABEL_SAMPLE ? h->RW + h->G + 1 : h->RW, 16);   // sample mode: tail [ag | remaining] (her_ring.h)
   h->RG = gcrl::round_up(h->RW + h->G, 16);
   h->staged.assign(cfg->nenvs, 0);
   h->ag_mirror.assign((size_t)cfg->nenvs * cfg->flush_len * cfg->goal_dim, 0.f);
@@ -984,6 +1001,8 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
   if (!next_on_device) std::memcpy(sa.ns_inl, next_state, sizeof(float) * h->S);
   hipLaunchKernelGGL(her_stage_kernel, dim3(1), dim3(64), 0, st, sa);
   GCRL_HIP(hipGetLastError());
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)    // a lone row has no later row: remaining = 0, never relabelled
+    GCRL_HIP(hipMemsetAsync(h->ring + (size_t)phys * h->RS + h->RW, 0, (size_t)(h->RS - h->RW) * sizeof(float), st));
   book.append(1);                              // deque(maxlen): at capacity the oldest row falls off
   h->head = book.head; h->len = book.len;
   h->rows_pushed += 1;
@@ -1164,6 +1183,13 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
   if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, drawn_idx_host ? &host_copy : nullptr)) return rc;
   if (drawn_idx_host) std::memcpy(drawn_idx_host, host_copy, (size_t)B * M * sizeof(uint32_t));
   const long long n = (long long)B * M;
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
+    if (int rc = prof_begin(h, st)) return rc;
+    const uint64_t ctr = h->relabel_ctr;
+    h->relabel_ctr += (uint64_t)n;
+    if (int rc = gcrl::her_relabel_sample(h, h->idx_on_device ? h->idx_dev : nullptr, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    return prof_end(h, st, n);
+  }
   GatherArgs ga{h->ring, h->idx_on_device ? h->idx_dev : nullptr, h->last_gen, n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
                 out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns};
   if (int rc = prof_begin(h, st)) return rc;
@@ -1186,6 +1212,13 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
   GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample_dev: row stride smaller than the row");
   if (h->len < 1) return gcrl::fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
   hipStream_t st = h->pick(stream);
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
+    if (int rc = prof_begin(h, st)) return rc;
+    const uint64_t ctr = h->relabel_ctr;
+    h->relabel_ctr += (uint64_t)n;
+    if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    return prof_end(h, st, n);
+  }
   GatherArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
                 out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns};
   if (int rc = prof_begin(h, st)) return rc;
@@ -1199,6 +1232,16 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
   }
   GCRL_HIP(hipGetLastError());
   return prof_end(h, st, n);
+}
+
+int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* sa, float* nsa, float* spa, int ldx, float* r, float* d,
+                           const void* side_src, void* side_dst, int64_t side_bytes, void* stream) {
+  GCRL_CHECK_ARG(h && sa && nsa && r && d, "gcrl_her_gather_update: null output");
+  GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_gather_update: B and M must be >= 1");
+  GCRL_CHECK_ARG(side_bytes >= 0, "gcrl_her_gather_update: side_bytes %lld", (long long)side_bytes);
+  hipStream_t st = h->pick(stream);
+  if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, nullptr)) return rc;
+  return gcrl::her_gather_update(h, h->idx_on_device ? h->idx_dev : nullptr, (int64_t)B * M, sa, nsa, spa, ldx, r, d, st, side_src, side_dst, (size_t)side_bytes);
 }
 
 int gcrl_her_profile_enable(gcrl_her* h, int on) {
@@ -1237,8 +1280,12 @@ struct HerStateHeader {
   uint64_t episodes_flushed, draws_done, mutation_epoch;
 };
 constexpr uint32_t kHerMagic = 0x52454847u;   // "GHER"
+// version 1: a ring in the default mode (the blob of before).  version 2: sample-time relabelling — the header is followed by
+// this record, the ring records are whole (tails included)
+struct HerStateRelabel { uint64_t relabel_ctr; int32_t relabel_mode, pad; };
+size_t her_state_extra(int mode) { return mode == GCRL_RELABEL_SAMPLE ? sizeof(HerStateRelabel) : 0; }
 size_t her_state_bytes(const gcrl_her* h) {
-  return sizeof(HerStateHeader) + (size_t)h->cfg.nenvs * sizeof(int32_t) +
+  return sizeof(HerStateHeader) + her_state_extra(h->relabel_mode) + (size_t)h->cfg.nenvs * sizeof(int32_t) +
          ((size_t)h->cfg.nenvs * h->cfg.flush_len * h->RG + (size_t)h->len * h->RS) * sizeof(float);
 }
 }  // namespace
@@ -1248,10 +1295,14 @@ int64_t gcrl_her_state_size(const gcrl_her* h) { return h ? (int64_t)her_state_b
 int gcrl_her_save_state(gcrl_her* h, void* dst_host, int64_t n) {
   GCRL_CHECK_ARG(h && dst_host && n == (int64_t)her_state_bytes(h), "gcrl_her_save_state: buffer must be gcrl_her_state_size() bytes");
   GCRL_HIP(hipDeviceSynchronize());
-  HerStateHeader hd{kHerMagic, 1, h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
+  HerStateHeader hd{kHerMagic, h->relabel_mode == GCRL_RELABEL_SAMPLE ? 2u : 1u, h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
                     h->cfg.capacity, h->len, h->episodes_flushed, h->draws_done, h->mutation_epoch};
   char* o = (char*)dst_host;
   std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
+    const HerStateRelabel x{h->relabel_ctr, h->relabel_mode, 0};
+    std::memcpy(o, &x, sizeof(x)); o += sizeof(x);
+  }
   for (int e = 0; e < h->cfg.nenvs; ++e) { const int32_t v = h->staged[e]; std::memcpy(o, &v, sizeof(v)); o += sizeof(v); }
   const size_t stage_bytes = (size_t)h->cfg.nenvs * h->cfg.flush_len * h->RG * sizeof(float);
   GCRL_HIP(hipMemcpy(o, h->stage, stage_bytes, hipMemcpyDeviceToHost)); o += stage_bytes;
@@ -1267,16 +1318,26 @@ int gcrl_her_load_state(gcrl_her* h, const void* src_host, int64_t n) {
   GCRL_CHECK_ARG(h && src_host && n >= (int64_t)sizeof(HerStateHeader), "gcrl_her_load_state: null / short blob");
   HerStateHeader hd;
   std::memcpy(&hd, src_host, sizeof(hd));
-  GCRL_CHECK_ARG(hd.magic == kHerMagic && hd.version == 1, "gcrl_her_load_state: not a replay-ring state blob");
+  GCRL_CHECK_ARG(hd.magic == kHerMagic && (hd.version == 1 || hd.version == 2), "gcrl_her_load_state: not a replay-ring state blob");
+  const int blob_mode = hd.version == 2 ? GCRL_RELABEL_SAMPLE : GCRL_RELABEL_PUSH;
+  if (blob_mode != h->relabel_mode)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_load_state: relabel: the state was saved by a ring with relabel=\"%s\", this ring has relabel=\"%s\"",
+                      blob_mode == GCRL_RELABEL_SAMPLE ? "sample" : "push", h->relabel_mode == GCRL_RELABEL_SAMPLE ? "sample" : "push");
+  const size_t extra = her_state_extra(blob_mode);
   GCRL_CHECK_ARG(hd.S == h->S && hd.A == h->A && hd.G == h->G && hd.nenvs == h->cfg.nenvs && hd.flush_len == h->cfg.flush_len &&
                      hd.RS == h->RS && hd.RG == h->RG && hd.k_future == h->cfg.k_future,
                  "gcrl_her_load_state: the blob was saved by a ring of another shape");
   GCRL_CHECK_ARG(hd.len >= 0 && hd.len <= h->cfg.capacity, "gcrl_her_load_state: %lld saved rows do not fit capacity %lld", (long long)hd.len, (long long)h->cfg.capacity);
   const size_t stage_bytes = (size_t)h->cfg.nenvs * h->cfg.flush_len * h->RG * sizeof(float);
-  const size_t want = sizeof(hd) + (size_t)h->cfg.nenvs * sizeof(int32_t) + stage_bytes + (size_t)hd.len * h->RS * sizeof(float);
+  const size_t want = sizeof(hd) + extra + (size_t)h->cfg.nenvs * sizeof(int32_t) + stage_bytes + (size_t)hd.len * h->RS * sizeof(float);
   GCRL_CHECK_ARG((size_t)n == want, "gcrl_her_load_state: blob size %lld, expected %zu", (long long)n, want);
   GCRL_HIP(hipDeviceSynchronize());
   const char* o = (const char*)src_host + sizeof(hd);
+  if (extra) {
+    HerStateRelabel x;
+    std::memcpy(&x, o, sizeof(x)); o += sizeof(x);
+    h->relabel_ctr = x.relabel_ctr;
+  }
   for (int e = 0; e < h->cfg.nenvs; ++e) { int32_t v; std::memcpy(&v, o, sizeof(v)); o += sizeof(v); h->staged[e] = v; }
   GCRL_HIP(hipMemcpy(h->stage, o, stage_bytes, hipMemcpyHostToDevice)); o += stage_bytes;
   GCRL_HIP(hipMemcpy(h->ring, o, (size_t)hd.len * h->RS * sizeof(float), hipMemcpyHostToDevice));
@@ -1338,6 +1399,41 @@ int gcrl_her_read_rows(gcrl_her* h, int64_t first, int64_t n, float* s, float* a
     if (ns) std::memcpy(ns + (size_t)i * h->S, rec + h->SA4, sizeof(float) * h->S);
     if (r) r[i] = rec[h->SA4 + h->S4];
     if (d) d[i] = rec[h->SA4 + h->S4 + 1];
+  }
+  return GCRL_OK;
+}
+
+int gcrl_her_relabel_mode(const gcrl_her* h) { return h ? h->relabel_mode : -1; }
+uint64_t gcrl_her_get_relabel_counter(const gcrl_her* h) { return h ? h->relabel_ctr : 0; }
+int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter) {
+  GCRL_CHECK_ARG(h, "gcrl_her_set_relabel_counter: null handle");
+  if (h->relabel_mode != GCRL_RELABEL_SAMPLE)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_set_relabel_counter: relabel: the ring was created with GCRL_RELABEL_PUSH and has no relabel stream");
+  h->relabel_ctr = counter;
+  return GCRL_OK;
+}
+
+int gcrl_her_read_tails(gcrl_her* h, int64_t first, int64_t n, float* ag, float* remaining) {
+  GCRL_CHECK_ARG(h, "gcrl_her_read_tails: null handle");
+  if (h->relabel_mode != GCRL_RELABEL_SAMPLE)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_read_tails: relabel: the ring was created with GCRL_RELABEL_PUSH and its records have no tails");
+  GCRL_CHECK_ARG(first >= 0 && n >= 0 && first + n <= h->len, "gcrl_her_read_tails: range [%lld,+%lld) outside len %lld", (long long)first, (long long)n, (long long)h->len);
+  if (n == 0) return GCRL_OK;
+  GCRL_HIP(hipDeviceSynchronize());
+  float* tmp = nullptr;
+  GCRL_HIP(hipMalloc((void**)&tmp, (size_t)n * h->RS * sizeof(float)));
+  long long total = n * h->RS;
+  hipLaunchKernelGGL(her_copy_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
+                     h->ring, (long long)h->head, (long long)h->cfg.capacity, h->RS, (long long)first, (long long)n, tmp);
+  std::vector<float> host((size_t)total);
+  hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(tmp);
+  GCRL_HIP(e);
+  for (int64_t i = 0; i < n; ++i) {
+    const float* rec = host.data() + (size_t)i * h->RS;
+    if (ag) std::memcpy(ag + (size_t)i * h->G, rec + h->RW, sizeof(float) * h->G);
+    if (remaining) remaining[i] = rec[h->RW + h->G];
   }
   return GCRL_OK;
 }

@@ -302,6 +302,8 @@ extern "C" {
 int gcrl_per_attach(gcrl_her* h, float alpha, float eps) {
   GCRL_CHECK_ARG(h, "gcrl_per_attach: null ring");
   GCRL_CHECK_ARG(!h->per, "gcrl_per_attach: the ring already has a priority tree");
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)   // a property of the ring, not of this call's arguments
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_per_attach: relabel: a ring with sample-time relabelling (GCRL_RELABEL_SAMPLE) takes no priority tree");
   GCRL_CHECK_ARG(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(eps) && eps > 0.0f, "gcrl_per_attach: alpha %g (>= 0) / eps %g (> 0)", (double)alpha, (double)eps);
   gcrl::PerLayout L;
   GCRL_CHECK_ARG(gcrl::per_layout(h->cfg.capacity, &L), "gcrl_per_attach: capacity %lld has no tree layout", (long long)h->cfg.capacity);

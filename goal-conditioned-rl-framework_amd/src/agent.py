@@ -186,7 +186,14 @@ class _EngineAgent:
     def __init__(self, obs_dim: int, ac_dim: int, config, weights, nenvs: int, gradient_step: int, *,
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
-                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", _member=None):
+                 top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
+                 _member=None):
+        # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
+        if relabel not in ("push", "sample"):
+            raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
+        if relabel == "sample" and config.buffer_type != "HER":
+            raise _ffi.GcrlError(f"{type(self).__name__}: relabel: 'sample' needs buffer_type 'HER', got {config.buffer_type!r}")
+        self.relabel = relabel
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -220,7 +227,7 @@ class _EngineAgent:
             self.buffer = ReplayBuffer(config.max_len, rng=rng, seed=seed, device_index=device_index)
         elif config.buffer_type == "HER":
             self.buffer = HERBuffer(config.max_len, config.max_eps_len, nenvs, k_future=config.k_future,
-                                    rng=rng, seed=seed, device_index=device_index)
+                                    rng=rng, seed=seed, device_index=device_index, relabel=relabel)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 

@@ -134,6 +134,9 @@ def _classify_reward_probe(fn, goal_dim: int, default_threshold: float):
     return 2, float(default_threshold)
 
 
+RELABEL_MODES = {"push": 0, "sample": 1}    # include/gcrl.h GCRL_RELABEL_*
+
+
 class _RingState:
     """save_state / load_state shared by the three buffers (extension of SURVEY.md §8f-2)."""
 
@@ -141,6 +144,7 @@ class _RingState:
         """Ring rows (logical order), staged partial episodes and the MT19937 stream -> `path`; returns the metadata
         load_state needs.  An untouched buffer (no transition pushed yet) saves as empty."""
         meta = dict(dims=self._dims, rng_mode=self.rng.mode, py_random=None, mt=None, bytes=0)
+        meta["relabel"] = getattr(self, "relabel", "push")
         if self.rng.mode == "python":
             st = _pyrandom.getstate()
             meta["py_random"] = [st[0], list(st[1]), st[2]]
@@ -158,6 +162,9 @@ class _RingState:
         return meta
 
     def load_state(self, path: str, meta: dict):
+        if meta.get("relabel", "push") != getattr(self, "relabel", "push"):    # refused before any device work
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: relabel: the state was saved with relabel={meta.get('relabel', 'push')!r}, "
+                                 f"this buffer has relabel={getattr(self, 'relabel', 'push')!r}")
         if meta["bytes"]:
             self._ensure(*meta["dims"])
             blob = np.fromfile(path, dtype=np.uint8)
@@ -176,7 +183,14 @@ class _RingState:
 class HERBuffer(_RingState):
     def __init__(self, max_mem_len: int, max_eps_len: int, nenvs: int, threshold: float = 0.05,
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
-                 device_index: int = 0):
+                 device_index: int = 0, relabel: str = "push"):
+        # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
+        # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
+        # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
+        # resident as in push mode, divide it by about 1 + k_future.
+        if relabel not in RELABEL_MODES:
+            raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
+        self.relabel = relabel
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError("HERBuffer needs a HIP device: the replay ring lives in HBM and "
                                  "there is no CPU fallback")
@@ -238,12 +252,15 @@ class HERBuffer(_RingState):
                 raise ValueError(f"transition dims {(S, A, G)} differ from the ring's {self._dims}")
             return
         kind, thr = _classify_reward(self.compute_reward, G, self.threshold)
+        if self.relabel == "sample" and kind == 2:    # refused before any device work
+            raise _ffi.GcrlError("HERBuffer: compute_reward: relabel='sample' computes the relabel rewards in the gather kernel and takes the "
+                                 "built-in sparse or dense reward only; this callable is neither (use relabel='push')")
         self._reward_cfg = (kind, thr)
         cfg = _ffi.HerConfig(state_dim=S, action_dim=A, goal_dim=G, capacity=self.max_mem_len,
                              nenvs=self.nenvs, k_future=self.k_future, flush_len=FLUSH_LEN,
                              reward_kind=kind, reward_threshold=thr, device=self.device_index,
                              rng_mode=1 if self.rng.mode == "device" else 0, seed=self.rng.seed_value)
-        self._h = _ffi.check_ptr(lib.gcrl_her_create(C.byref(cfg), self.rng.handle), "gcrl_her_create")
+        self._h = _ffi.check_ptr(lib.gcrl_her_create_relabel(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel]), "gcrl_her_create")
         self._dims = (S, A, G)
         if kind == 2:
             self._install_reward_callback()
@@ -397,6 +414,56 @@ class HERBuffer(_RingState):
         _ffi.check(lib.gcrl_her_read_rows(self._h, first, n, s.ctypes.data, a.ctypes.data,
                                           ns.ctypes.data, r.ctypes.data, d.ctypes.data))
         return s, a, ns, r, d
+
+    def gather_update(self, batch_size: int, num_batches: int = 1, indices=None, spa: bool = False, side=None):
+        """The update engine's batch gather on its own (tests, tools): -> (sa, nsa, spa or None, r, d) cuda tensors, sa / nsa / spa of
+        row stride roundup(S + A, 4) (spa pre-filled with NaN: the launch writes its roundup(S, 4) leading columns only).  `side`: a
+        cuda uint8 tensor (a multiple of 16 bytes) the launch also copies — the engine's call-start form; its copy is returned last."""
+        assert len(self) >= batch_size, "[ERROR] Not enough in buffer to sample"
+        S, A, _ = self._dims
+        n, ldx = batch_size * num_batches, (S + A + 3) // 4 * 4
+        dev = torch.device("cuda", self.device_index)
+        sa = torch.empty((n, ldx), dtype=torch.float32, device=dev)
+        nsa = torch.empty((n, ldx), dtype=torch.float32, device=dev)
+        sp = torch.full((n, ldx), float("nan"), dtype=torch.float32, device=dev) if spa else None
+        r = torch.empty(n, dtype=torch.float32, device=dev)
+        d = torch.empty(n, dtype=torch.float32, device=dev)
+        idx_in = None
+        if indices is not None:
+            idx_in = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+            assert idx_in.size == n
+        side_out = torch.zeros_like(side) if side is not None else None
+        if idx_in is None:
+            self.rng.pull()
+        _ffi.check(lib.gcrl_her_gather_update(
+            self._h, batch_size, num_batches, idx_in.ctypes.data if idx_in is not None else None, sa.data_ptr(), nsa.data_ptr(),
+            sp.data_ptr() if spa else None, ldx, r.data_ptr(), d.data_ptr(), side.data_ptr() if side is not None else None,
+            side_out.data_ptr() if side is not None else None, side.numel() if side is not None else 0, _ffi.stream_handle()))
+        if idx_in is None:
+            self.rng.push_back()
+        out = (sa, nsa, sp, r, d)
+        return out + (side_out,) if side is not None else out
+
+    def tails(self, first: int = 0, count: int | None = None):
+        """relabel="sample": the tails of ring rows in logical order — (ag [n, G], remaining [n]) — for tests and state."""
+        if self._h is None:
+            raise _ffi.GcrlError("HERBuffer.tails: the ring has no rows yet")
+        n = len(self) - first if count is None else count
+        G = self._dims[2]
+        ag = np.empty((n, G), np.float32); rem = np.empty(n, np.float32)
+        _ffi.check(lib.gcrl_her_read_tails(self._h, first, n, ag.ctypes.data, rem.ctypes.data))
+        return ag, rem
+
+    @property
+    def relabel_counter(self) -> int:
+        """relabel="sample": rows gathered from the ring so far, the counter of its relabel stream (0 before the ring exists)."""
+        return 0 if self._h is None else int(lib.gcrl_her_get_relabel_counter(self._h))
+
+    @relabel_counter.setter
+    def relabel_counter(self, v: int):
+        if self._h is None:
+            raise _ffi.GcrlError("HERBuffer.relabel_counter: the ring is created by the first push")
+        _ffi.check(lib.gcrl_her_set_relabel_counter(self._h, int(v)))
 
     def compute_termination(self, dg, ag):
         return np.linalg.norm(dg - ag, axis=-1) < self.threshold

@@ -73,7 +73,13 @@ class _Population:
     MERGE_GATHER_FROM = MAX_MEMBERS + 1
 
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
-                 seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host"):
+                 seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
+                 relabel: str = "push"):
+        # relabel="sample": every member's ring (or the shared one) relabels at gather time (buffer.HERBuffer); such gathers have no
+        # population launch, so merge_gather = True then reports no merged launch (gather_counts()).
+        if relabel not in ("push", "sample"):
+            raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
+        self.relabel = relabel
         configs = list(configs)
         P = len(configs)
         self.shared_ring = bool(shared_ring)
@@ -104,7 +110,7 @@ class _Population:
         pop = self._pop
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
-            self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index,
+            self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index, relabel=relabel,
                                            _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
         self._merge_gather = False
@@ -116,7 +122,7 @@ class _Population:
             c0 = configs[0]
             self.nenvs = int(nenvs)
             self.buffer = HERBuffer(c0.max_len, c0.max_eps_len, int(nenvs) * P, k_future=c0.k_future, rng=rng, seed=seeds[0],
-                                    device_index=device_index)
+                                    device_index=device_index, relabel=relabel)
             for m in self.members:
                 m.buffer = self.buffer
         if rng == "python":
@@ -399,6 +405,10 @@ class _Population:
             for s, d in pairs:
                 if ms[s].buffer.handle is None:
                     self._refuse("copy_ring", f"member {s} has no replay ring yet (nothing was pushed)")
+                ra, rb = getattr(ms[s].buffer, "relabel", "push"), getattr(ms[d].buffer, "relabel", "push")
+                if ra != rb:
+                    self._refuse("relabel", f"member {s}'s ring has relabel={ra!r}, member {d}'s relabel={rb!r}: records of one mode do not "
+                                            "fit a ring of the other (copy_ring=True)")
                 ms[d].buffer._ensure(*ms[s].buffer._dims)
             rings = (C.c_void_p * P)(*[m.buffer.handle for m in ms])
         src = (C.c_int32 * n)(*[s for s, _ in pairs])

@@ -119,6 +119,20 @@ typedef struct gcrl_her_config {
 /* rng: shared CPython-exact generator (may be NULL: the handle creates one seeded with
  * cfg->seed).  The ring never frees a shared rng. */
 gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng);
+/* Relabelling mode of a ring.  GCRL_RELABEL_PUSH (what gcrl_her_create makes): the reference's form — a flush stores every step's
+ * original row and its k_future relabelled copies, `capacity` counts copies.  GCRL_RELABEL_SAMPLE: a flush stores an episode's T
+ * original rows once (no future pick is drawn: the CPython-MT stream is not consumed by a flush), each record with a tail
+ * [achieved goal | steps remaining in its episode]; `capacity` counts real transitions.  A row is relabelled when it is gathered:
+ * with probability k_future / (k_future + 1), against a uniformly chosen later row of its episode, by a counter hash of the number
+ * of rows gathered from the ring so far (gcrl_her_get_relabel_counter) — also when the indices come from the CPython-MT stream.
+ * Refused: reward_kind GCRL_REWARD_HOST (the relabel rewards are computed in the gather kernel), gcrl_per_attach on such a ring,
+ * gcrl_her_load_state of a blob saved in the other mode. */
+enum { GCRL_RELABEL_PUSH = 0, GCRL_RELABEL_SAMPLE = 1 };
+gcrl_her* gcrl_her_create_relabel(const gcrl_her_config* cfg, gcrl_mt* rng, int mode);
+int gcrl_her_relabel_mode(const gcrl_her* h);
+/* rows ever gathered from a GCRL_RELABEL_SAMPLE ring: the counter of its relabel stream (saved and loaded with the ring's state) */
+uint64_t gcrl_her_get_relabel_counter(const gcrl_her* h);
+int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter);
 void gcrl_her_destroy(gcrl_her* h);
 /* compute_reward for GCRL_REWARD_HOST rings: out[i] = compute_reward(achieved[i], goal[i], {}) for n pairs of goal_dim floats
  * (row-major), in the reference's call order (src/buffer.py:151-166: step-major, relabel-minor).  Returns 0, or non-zero to
@@ -203,6 +217,16 @@ int gcrl_her_load_state(gcrl_her* h, const void* src_host, int64_t nbytes);
  * (any may be NULL).  Synchronises the handle's stream. */
 int gcrl_her_read_rows(gcrl_her* h, int64_t first, int64_t n, float* s_host, float* a_host,
                        float* ns_host, float* r_host, float* d_host);
+/* The update engine's batch gather on its own (tests, tools): M batches of B rows drawn as gcrl_her_sample draws them (idx_host,
+ * the CPython-MT stream or the device RNG) into the engine's GEMM-ready device matrices of row stride ldx = roundup(S + A, 4):
+ * sa = [s | a], nsa = [ns | 0 ..], spa (may be NULL) = [s | ..] in its roundup(S, 4) leading columns, r[B * M], d[B * M].
+ * side_bytes > 0 (a multiple of 16): the launch also copies side_bytes from side_src to side_dst (both readable / writable by the
+ * device) — the engine's call-start form.  A GCRL_RELABEL_SAMPLE ring relabels the rows and advances its counter by B * M. */
+int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* sa_dev, float* nsa_dev, float* spa_dev, int ldx,
+                           float* r_dev, float* d_dev, const void* side_src, void* side_dst, int64_t side_bytes, void* stream);
+/* Test/state: the tails of `n` rows of a GCRL_RELABEL_SAMPLE ring from logical index `first`: ag_host[n][goal_dim],
+ * remaining_host[n] (either may be NULL).  Synchronises the device. */
+int gcrl_her_read_tails(gcrl_her* h, int64_t first, int64_t n, float* ag_host, float* remaining_host);
 
 /* ------------------------------------------------------------------------------------------
  * Update engine.  Replaces DDPG / TD3Agent / SACAgent / TQCAgent .update() and what it calls

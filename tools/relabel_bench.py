@@ -1,0 +1,92 @@
+"""Sample-time relabelling against the default mode, by the profiler's clock.
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/relabel_bench.py --run
+    python tools/relabel_bench.py --parse DIR
+
+--run fills two rings of 1e6 records at PickAndPlace dims (S 23, A 4, G 3; k_future 4, rng="device": no host draw, no index
+upload) — one per relabel mode — and then, alternating the modes, issues the update engine's gather (HERBuffer.gather_update) at
+9 216 and 77 824 rows, and the flush of one T = 50 episode (push_episode).  Nothing is timed here: the kernel trace is.
+--parse reads the trace and prints, per kernel and launch size, the number of launches, the median and the range of the kernel
+durations — the launches after the warm-up ones.  No GPU: --run fails; it does not fall back."""
+import argparse
+import csv
+import glob
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+S, A, G, K = 23, 4, 3, 4
+CAP = 1_000_000
+SIZES = ((256, 36), (256, 304))      # 9 216 and 77 824 rows: a trainer cycle's head-sized and main gather
+WARM, ITERS = 10, 60
+
+
+def run():
+    import numpy as np
+    import gcrl_amd
+    from oracle import her_oracle
+    gen = np.random.default_rng(0)
+    st = her_oracle.synthetic_episode(gen, 50, S, A, G)
+    ep = [np.stack([x[j] for x in st]).astype(np.float32) for j in (0, 1, 2)] + \
+         [np.array([x[3] for x in st], np.float32), np.zeros(50, np.float32), np.stack([x[6] for x in st])]
+    rings = {}
+    for mode in ("push", "sample"):
+        buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel=mode)
+        buf.compute_reward = her_oracle.sparse_reward
+        per = 50 if mode == "sample" else 50 + K * 49
+        for _ in range(CAP // per + 2):                      # the same episode again and again: the gathers' addresses are what matters
+            buf.push_episode(0, *ep)
+        assert len(buf) == CAP
+        rings[mode] = buf
+    import torch
+    torch.cuda.synchronize()
+    for B, M in SIZES:
+        for _ in range(WARM + ITERS):
+            for mode in ("push", "sample"):
+                rings[mode].gather_update(B, M)
+    for _ in range(WARM + ITERS):
+        for mode in ("push", "sample"):
+            rings[mode].push_episode(1, *ep)
+    torch.cuda.synchronize()
+    print("relabel_bench: done")
+
+
+NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_flush_kernel", "her_flush_sample_kernel")
+
+
+def parse(d):
+    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        sys.exit(f"no kernel trace under {d}")
+    rows = {}
+    for f in files:
+        for r in csv.DictReader(open(f)):
+            name = r["Kernel_Name"]
+            key = next((n for n in NAMES if n in name), None)
+            if key is None:
+                continue
+            grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r.get("Grid_Size_X", 0))
+            rows.setdefault((key, grid), []).append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
+    for (key, grid), v in sorted(rows.items()):
+        v.sort()
+        if len(v) < ITERS:           # the fill's flushes have their own grid sizes only in push mode; keep the timed tail of each
+            continue
+        dur = [x[1] / 1e3 for x in v[-ITERS:]]
+        print(f"{key:28s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
+              f"range {min(dur):7.2f} .. {max(dur):7.2f} us")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--run", action="store_true")
+    ap.add_argument("--parse", metavar="DIR")
+    a = ap.parse_args()
+    if a.parse:
+        parse(a.parse)
+    elif a.run:
+        run()
+    else:
+        ap.error("--run or --parse DIR")
