@@ -243,6 +243,7 @@ struct gcrl_agent {
   // draws ~2 us per batch from the MT stream: with all n batches up front the GPU idled ~40 us at the start of a cycle)
   struct { gcrl_her* her = nullptr; int n = 0; int slot = 0; int next = 0; } deferred;   // batches [next, n) not yet drawn
   int head_batches = 2;       // batches drawn and gathered before a call's first launch (the rest: behind that many queued steps)
+  bool main_idx_staged = false;   // the main gather's indices as a staged copy (round 5's form) instead of read from the pinned block
   std::vector<StepPlan> dp_plans;  // steps of the data-parallel cycle begun by gcrl_agent_dp_begin
   std::vector<DpSeg> dp_segs;      // ... as segments separated by gradient exchanges
   size_t dp_pos = 0;
@@ -1139,12 +1140,22 @@ int finish_deferred_draw(gcrl_agent* a, hipStream_t st) {
   const int n = a->deferred.n, B = a->B, first = a->deferred.next;
   uint32_t* idx = (uint32_t*)(a->upload_pinned[a->deferred.slot] + sizeof(UploadBlock));
   for (int i = first; i < n; ++i) TRY(gcrl_mt_sample_indices(her->rng, (uint32_t)her->len, (uint32_t)B, idx + (size_t)i * B));
-  GCRL_HIP(hipMemcpyAsync(a->idx_dev() + (size_t)first * B, idx + (size_t)first * B, (size_t)(n - first) * B * sizeof(uint32_t),
-                          hipMemcpyHostToDevice, st));
-  GCRL_HIP(hipEventRecord(a->upload_ev[a->deferred.slot], st));
-  return her_gather_update(her, a->idx_dev() + (size_t)first * B, (int64_t)(n - first) * B, a->sa + first * a->slot_x,
-                           a->nsa + first * a->slot_x, a->rowchain ? nullptr : a->spa + first * a->slot_x, a->ldx,
-                           a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st);
+  // The main gather reads its indices straight from the pinned block, like the head gather.  Behind a staged copy of the
+  // 36 x 256 indices of a 40-step call (36 KB; up to 16 KB the runtime copies with a kernel on the same queue) the gather
+  // started 22-25 us after the step before it had ended, with the host not late: 0.6 us/step on the headline
+  // (profiles/r17_trace_gaps_ddpg_parent.txt, r17_ab_main_gather_indices.txt).  GCRL_MAIN_IDX_STAGED=1: the copy.
+  const bool staged = a->main_idx_staged;
+  const uint32_t* src = idx + (size_t)first * B;
+  if (staged) {
+    GCRL_HIP(hipMemcpyAsync(a->idx_dev() + (size_t)first * B, src, (size_t)(n - first) * B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipEventRecord(a->upload_ev[a->deferred.slot], st));
+    src = a->idx_dev() + (size_t)first * B;
+  }
+  TRY(her_gather_update(her, src, (int64_t)(n - first) * B, a->sa + first * a->slot_x,
+                        a->nsa + first * a->slot_x, a->rowchain ? nullptr : a->spa + first * a->slot_x, a->ldx,
+                        a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st));
+  if (!staged) GCRL_HIP(hipEventRecord(a->upload_ev[a->deferred.slot], st));   // the pinned block is free once the gather has read it
+  return GCRL_OK;
 }
 
 // begin_call in two parts.  begin_call_plan consumes the tickets and the upload slot, plans the steps, draws the indices into the
@@ -1556,9 +1567,11 @@ int build(gcrl_agent* a) {
     a->head_batches = 3;   // (TD3 at batch 2048: the host draws 38 x 2048 indices in ~390 us, more than two 170 us steps)
     // round 5, DDPG's overlapped step at 50 us: three steps of queued work no longer cover the host's six launches + the draw (a 20-step call showed
     // 23 us of idle GPU before the main gather); four do: 57.0 -> 55.9 us/step on the 20-step line, the steady state unchanged
-    // (profiles/r05_ab_head_batches.txt; reading the indices straight from the pinned block instead of the staged copy: no gain)
+    // (profiles/r05_ab_head_batches.txt; reading the indices straight from the pinned block instead of the staged copy: no gain on that line —
+    // the 40-step call's larger copy is another matter, round 17, finish_deferred_draw)
     if (c.kind == GCRL_AGENT_DDPG && c.pipeline_steps != 0) a->head_batches = 4;
     if (const char* e = std::getenv("GCRL_HEAD_BATCHES")) a->head_batches = std::max(1, std::min(8, std::atoi(e)));   // experiment knob
+    a->main_idx_staged = std::getenv("GCRL_MAIN_IDX_STAGED") != nullptr;   // A/B knob (finish_deferred_draw)
     a->dw_batch_off = std::getenv("GCRL_NO_DW_BATCH") != nullptr;
     a->bn_fused_tiled = std::getenv("GCRL_NO_BN_TILED_STATS") == nullptr;
     a->layer_adv_off = std::getenv("GCRL_NO_LAYER_ADV") != nullptr;

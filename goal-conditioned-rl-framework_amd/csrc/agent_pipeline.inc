@@ -25,6 +25,13 @@
 // = 3L+7 launches (16 at L=3) instead of 6L+13 (31) for the two phases run back to back.  The
 // arithmetic of each step is untouched (same kernels, same operands, same order inside a chain),
 // so update_many stays bitwise equal to repeated update() — tests/test_gpu_parity.py checks it.
+//
+// How a call's steps reach the GPU (run_steps_ddpg): at the default use_graph = 1 the row-block path issues PLAIN launches
+// (graph_on(), agent.hip) — two per overlapped step, no graph launch anywhere in the call.  Measured (round 17,
+// profiles/r17_trace_gaps_ddpg_parent.txt): with the host ahead, plain launches follow each other with 0.0 us of idle GPU, the
+// same as kernels inside a graph, while every graph launch idles the GPU for 8.3-8.8 us; the graph pieces below (use_graph = 2)
+// therefore cannot beat the plain form, however few they are.  The call's idle time sat in front of the main gather instead
+// (finish_deferred_draw, agent.hip).
 
 // forward launches of K: [TA l | C l] at l = 0..L, [TC l] at L+1..2L+1
 void pipe_add_K_fwd(gcrl_agent* a, Launches& f, const PipeCtx& k) {
