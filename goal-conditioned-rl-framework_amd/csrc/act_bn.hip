@@ -5,8 +5,8 @@
 // partial sums of all 4 rows; a three-step exchange inside the eight lanes finishes the sums, and lanes 0..3 of the group apply the
 // bias, the BatchNorm-eval formula and the ReLU (sac_select.h: the arithmetic of bn_relu_eval) for row 0..3 and store to LDS.  Four
 // columns per lane group are in flight at once: with 8 waves that is the ~64 vector-memory instructions a CU keeps in flight
-// (DESIGN.md 4e).  GCRL_ACT_BN_WARM=1 makes each pass first touch one float of every 128-byte line of the NEXT pass's weights
-// (warm_lines); measured, that is slower at both benchmark shapes (52 vs 58 us per call at H = 512), so it is off by default.
+// (DESIGN.md 4e).  ActBnArgs::warm makes each pass first touch one float of every 128-byte line of the NEXT pass's weights
+// (warm_lines); measured, that is slower at both benchmark shapes (52 vs 58 us per call at H = 512), so the host never sets it.
 #include "act_bn.h"
 #include "common.h"
 #include "norm_math.h"

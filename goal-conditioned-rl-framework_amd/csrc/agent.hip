@@ -155,7 +155,6 @@ struct gcrl_agent {
   float *dw_part = nullptr, *dw_tick = nullptr;
   std::vector<long long> dwp_off_c, dwp_off_a, dwt_off_c, dwt_off_a;
   long long dwp_cstride = 0, dwt_cstride = 0, dwp_actor = 0, dwt_actor = 0;
-  bool dw_batch_off = false;  // GCRL_NO_DW_BATCH=1: a large ensemble's dW problems stay with their layers' dX launches (A/B knob)
   // [Linear -> BatchNorm -> ReLU] of the SAC / TQC actor as one launch per layer and direction (bn_slab.hip): B <= 512, no
   // SyncBN (GCRL_NO_BN_SLAB=1: the GEMM + BatchNorm launches).  bn_bstat: batch statistics [input][L][2][H]
   bool bn_slab = false;
@@ -177,7 +176,6 @@ struct gcrl_agent {
   bool red_off = false;       // GCRL_NO_MB_REDUCE=1: single-workgroup td_loss / actor_select_alpha at every batch size
   bool layer_adv_off = false; // GCRL_NO_LAYER_ADV=1: begin_step launches on the layer-per-launch path as in rounds 1-3
   bool bn_fused_tiled = true; // GCRL_NO_BN_TILED_STATS=1 turns it off: the LDS-tiled GEMM's epilogue leaves the 64-row BatchNorm partials (no bn_stats launch)
-  bool bn_fused = false;      // GCRL_BN_FUSED=1: BatchNorm statistics out of the producing GEMM's epilogue instead of bn_stats launches
   bool split_k = false;       // TD3: critic phase as role-parallel launches (agent_rowchain.inc)
   bool split_roles = false;   // twin-critic phases as role-parallel launches (rowchain.h launch_rowchain_split)
   int n_cus = 0;              // compute units of the device (residency checks of the launches whose workgroups meet)
@@ -192,11 +190,6 @@ struct gcrl_agent {
   long long of_stride = 0;
   float* rc_bar = nullptr;    // meeting counters of the row blocks [2][nblk][32 words]
   long long rc_bar_words = 0;
-  // weight-slice form of the DDPG launch (rowtile.hip): a 16 x 16 tile of every layer per workgroup, hand-offs inside the launch
-  bool rowtile = false, rowtile_can = false;
-  float *rt_xb = nullptr, *rt_qpart = nullptr, *rt_ctr = nullptr, *rt_xid = nullptr;
-  long long rt_xb_floats = 0, rt_part_floats = 0;
-  long long rt_ctr_words = 0;   // 64-bit words
   // host-visible status word of the launches whose workgroups wait for each other (meet.h): a timed-out wait sets a bit, the
   // next host synchronisation of this handle returns GCRL_ERR_STATE, zeroes the counters and clears it (meet_check below)
   unsigned int *status_host = nullptr, *status_dev = nullptr;
@@ -205,7 +198,6 @@ struct gcrl_agent {
   gcrl_xchg* xchg = nullptr;
   bool xchg_sep_norm = false;   // GCRL_XCHG_SEPARATE_NORM=1 (A/B and the bitwise test against the RCCL / gloo exchange): the clip norm from a sum-of-squares launch over the reduced gradients instead of the exchange kernel's partials
   float xchg_scale() const { return xchg ? 1.0f / (float)gcrl_xchg_world(xchg) : 1.0f; }
-  int split_rg[4] = {1, 1, 1, 1};
   int row_rg = 1, row_ldl = 0;
   float *wt = nullptr, *rc_gC = nullptr, *rc_gA = nullptr, *ybuf = nullptr;
   long long wt_net[4] = {};   // offsets of actor | target actor | critic 0 | target critic 0 inside wt
@@ -458,16 +450,15 @@ int sac_actor_forward_multi(gcrl_agent* a, hipStream_t st, const ActorFwd* f, in
   }
   for (int l = 0; l < net.L && !slab; ++l) {
     std::vector<GemmDesc> v;
-    bool fused_stats = false, fused_tiled = false;
+    bool fused_tiled = false;
     for (int i = 0; i < nf; ++i) {
       const float* X = l == 0 ? f[i].X0 : hbuf(f[i], l - 1);
       GemmDesc d = fwd(X, l == 0 ? a->ldx : H, P, net.lin[l], f[i].z, H, B, EPI_NONE);
       if (l == 0 && f[i].x_slot) { d.slot = a->slot_ptr(); d.a_slot = f[i].x_slot; }
-      // BatchNorm statistics out of this GEMM's epilogue when its form allows (16-row partials, at most 32 of them)
-      if (i == 0) fused_stats = a->bn_fused && a->bn_sync.world <= 1 && gemm_shape_of(d) == 1 && (B + kBnFusedRows - 1) / kBnFusedRows <= kBnFusedMaxParts;
-      // ... or of the LDS-tiled form's (64-row partials: what bn_stats_kernel would compute from z; TQC's B = 2048, H = 512)
-      if (i == 0) fused_tiled = !fused_stats && a->bn_fused_tiled && a->bn_sync.world <= 1 && gemm_shape_of(d) == 4 && H % 4 == 0;
-      if (fused_stats || fused_tiled) d.bn_part = f[i].bn_part;
+      // BatchNorm statistics out of the LDS-tiled form's epilogue (64-row partials: what bn_stats_kernel would compute from z; TQC's
+      // B = 2048, H = 512).  The k-split 16x16 form's 16-row partials measured equal at cfg 5 (204.6 vs 203.6 us/step): never asked for
+      if (i == 0) fused_tiled = a->bn_fused_tiled && a->bn_sync.world <= 1 && gemm_shape_of(d) == 4 && H % 4 == 0;
+      if (fused_tiled) d.bn_part = f[i].bn_part;
       v.push_back(d);
     }
     if (extra && (size_t)l < extra->steps.size()) v.insert(v.end(), extra->steps[l].begin(), extra->steps[l].end());
@@ -477,7 +468,7 @@ int sac_actor_forward_multi(gcrl_agent* a, hipStream_t st, const ActorFwd* f, in
       pb[i] = BnFwdProb{f[i].z, hbuf(f[i], l), f[i].save ? a->xhatA + (long long)l * BH : nullptr,
                         f[i].save ? a->invstdA + (long long)l * H : nullptr, f[i].bn_part};
     TRY(launch_bn_relu_fwd_multi(st, pb, nf, B, H, P + net.bn_g[l], P + net.bn_b[l], a->bn_rmean + (long long)l * H,
-                                 a->bn_rvar + (long long)l * H, fused_stats ? kBnFusedRows : 64, a->bn_sync.world > 1 ? &a->bn_sync : nullptr, fused_tiled));
+                                 a->bn_rvar + (long long)l * H, 64, a->bn_sync.world > 1 ? &a->bn_sync : nullptr, fused_tiled));
   }
   const int ldh = 2 * a->Apad;
   std::vector<GemmDesc> v;
@@ -584,12 +575,11 @@ int row_rg_of(int kind, int B) {
   const int phases = kind == GCRL_AGENT_DDPG ? 2 : 1;
   int rg = 1;
   while (rg < 4 && phases * ((B + 4 * rg - 1) / (4 * rg)) > 256) rg *= 2;
-  if (const char* e = std::getenv("GCRL_ROW_RG")) rg = std::max(1, std::min(4, std::atoi(e)));   // experiment knob
   return rg;
 }
 // TD3's critic phase as role-parallel launches once the batch fills the chip (cfg 3: 183.5 -> 178.4 us/step; below that the fused
 // launch is the shorter chain)
-bool td3_split_k_rule(int B, int rg) { return (B + 4 * rg - 1) / (4 * rg) >= 256 && !std::getenv("GCRL_NO_SPLIT_TD3"); }
+bool td3_split_k_rule(int B, int rg) { return (B + 4 * rg - 1) / (4 * rg) >= 256; }
 // SAC: the BatchNorm actor's slab launches (bn_slab.hip), the twin critics' role-split chain launches while the fused form leaves CUs idle, and the
 // actor's heads folded into them — the path a SAC population needs
 bool sac_slab_rule(int B, int H) { return bn_slab_ok(B, H) && !std::getenv("GCRL_NO_BN_SLAB"); }
@@ -680,7 +670,7 @@ int enqueue_phase0(gcrl_agent* a, hipStream_t st, int variant) {
   // (K = batch) into a mid-sized output: it wants the k-split 16x16 form, which re-reads its operands from L2 for every
   // 16x16 tile (4 flop per byte) and runs the 16x16x4 instruction — 13 such launches were 30 % of TQC's step.
   const long long dw_tiles = (long long)((H + 63) / 64) * ((H + 1 + 63) / 64);
-  const bool dw_batch = !a->dw_batch_off && L >= 2 && B >= 1024 && B % 16 == 0 && (long long)C * (L - 1) * dw_tiles >= 512;
+  const bool dw_batch = L >= 2 && B >= 1024 && B % 16 == 0 && (long long)C * (L - 1) * dw_tiles >= 512;
   auto Gbuf = [&](int c, int l) -> float* {            // gradient w.r.t. the output of hidden layer l (l < L)
     return dw_batch ? a->rc_gC + ((long long)c * L + l) * B * H : a->gC_at(c, (l + 1) & 1);
   };
@@ -1347,7 +1337,6 @@ int end_call(gcrl_agent* a, hipStream_t st) {
 // Called after every host synchronisation of the handle: the error surfaces ONCE, the meeting counters are zeroed (a
 // timed-out round may have left them off a multiple of the arrival count) and the next launch works again.  The reference
 // raises on any failed step (src/agent.py:659-699).
-int rowtile_reset(gcrl_agent* a);
 int optfuse_reset(gcrl_agent* a);
 int meet_check(gcrl_agent* a) {
   if (!a->status_host) return GCRL_OK;
@@ -1356,7 +1345,6 @@ int meet_check(gcrl_agent* a) {
   (void)hipDeviceSynchronize();
   if (a->bn_bar && a->bn_xchg) (void)bn_slab_scratch_reset(a->bn_xchg, reinterpret_cast<unsigned int*>(a->bn_bar), a->H, nullptr);
   if (a->rc_bar && a->rc_bar_words) (void)hipMemset(a->rc_bar, 0, (size_t)a->rc_bar_words * sizeof(unsigned int));
-  (void)rowtile_reset(a);
   (void)optfuse_reset(a);
   if (bits & (MEET_ERR_XCHG_READY | MEET_ERR_XCHG_DONE)) {
     (void)hipDeviceSynchronize();
@@ -1382,25 +1370,10 @@ int optfuse_reset(gcrl_agent* a) {
   return GCRL_OK;
 }
 
-// the weight-slice launch's hand-off words: "not written yet" everywhere, counters at zero (creation; after a timed-out wait)
-int rowtile_reset(gcrl_agent* a) {
-  if (a->rt_ctr && a->rt_ctr_words) GCRL_HIP(hipMemset(a->rt_ctr, 0, (size_t)a->rt_ctr_words * sizeof(unsigned long long)));
-  if (a->rt_xb && a->rt_xb_floats) GCRL_HIP(hipMemset(a->rt_xb, 0xFF, (size_t)a->rt_xb_floats * sizeof(float)));
-  if (a->rt_qpart && a->rt_part_floats) GCRL_HIP(hipMemset(a->rt_qpart, 0xFF, (size_t)a->rt_part_floats * sizeof(float)));
-  return GCRL_OK;
-}
-
 int bytes_alloc(float** p, long long n) {
   GCRL_HIP(hipMalloc((void**)p, (size_t)n * sizeof(float)));
   GCRL_HIP(hipMemset(*p, 0, (size_t)n * sizeof(float)));
   return GCRL_OK;
-}
-
-// the weight-slice DDPG launch (rowtile.hip): GCRL_ROWTILE=1 turns it on, GCRL_NO_ROWTILE=1 off (the default until its full-size
-// parity and speed are recorded)
-bool rowtile_enabled() {
-  if (std::getenv("GCRL_NO_ROWTILE")) return false;
-  return std::getenv("GCRL_ROWTILE") != nullptr;
 }
 
 int build(gcrl_agent* a) {
@@ -1500,12 +1473,11 @@ int build(gcrl_agent* a) {
     // SAC (the BatchNorm actor runs outside the chain kernels, both phases are critic-only): split by roles while the
     // fused form leaves CUs idle, i.e. up to ~one workgroup per CU per role pair
     a->split_roles = a->rowchain && c.kind == GCRL_AGENT_SAC && sac_split_roles_rule(C, B, a->row_rg);
-    for (int i = 0; i < 4; ++i) a->split_rg[i] = a->row_rg;
     {
       const long long nblk = (B + 4 * a->row_rg - 1) / (4 * a->row_rg);
       // (workgroups that wait for each other inside a launch must all be resident at once: rowchain_merge_ok asks the kernel's
       // occupancy at this LDS size and refuses on a shared device)
-      a->rc_merge = a->split_roles && !std::getenv("GCRL_NO_RC_MERGE") && !std::getenv("GCRL_SPLIT_RG") &&
+      a->rc_merge = a->split_roles && !std::getenv("GCRL_NO_RC_MERGE") &&
                     rowchain_merge_ok(a->row_rg, a->row_ldl, A, H, C, B);
       if (a->rc_merge) { a->rc_bar_words = 2 * nblk * 32; wants.push_back({&a->rc_bar, a->rc_bar_words}); }
     }
@@ -1518,22 +1490,11 @@ int build(gcrl_agent* a) {
       a->rc_bar_words = 2 * nblk * 32;
       wants.push_back({&a->rc_bar, a->rc_bar_words});
     }
-    // DDPG, one critic: the weight-slice launch (rowtile.hip) when all its 3 * (B/16) * (H/16) workgroups are resident at once
-    a->rowtile_can = a->rowchain && c.kind == GCRL_AGENT_DDPG && C == 1 && rowtile_shape_ok(B, H, L, S, A, C);
-    a->rowtile = a->rowtile_can && rowtile_enabled() && rowtile_ok(B, H, L, S, A, C);
-    if (a->rowtile_can) {
-      a->rt_ctr_words = rowtile_ctr_words(B, L);
-      a->rt_xb_floats = rowtile_xb_floats(B, H, L); a->rt_part_floats = rowtile_part_floats(B, H);
-      wants.push_back({&a->rt_xb, a->rt_xb_floats});
-      wants.push_back({&a->rt_qpart, a->rt_part_floats}); wants.push_back({&a->rt_ctr, 2 * a->rt_ctr_words});
-      wants.push_back({&a->rt_xid, 3LL * (B / 16) * 32});
-    }
     // DDPG: target chain and online critic of the critic phase in their own workgroups of the fused launch while all three roles'
     // workgroups fit the chip at once (one per CU)
     {
       const long long nblk = (B + 4 * a->row_rg - 1) / (4 * a->row_rg);
-      static const int per_cu = std::getenv("GCRL_DDPG_KSPLIT_PER_CU") ? std::atoi(std::getenv("GCRL_DDPG_KSPLIT_PER_CU")) : 1;   // experiment knob
-      a->ddpg_ksplit_can = a->rowchain && c.kind == GCRL_AGENT_DDPG && C == 1 && 3 * nblk <= per_cu * std::max(a->n_cus, 1);
+      a->ddpg_ksplit_can = a->rowchain && c.kind == GCRL_AGENT_DDPG && C == 1 && 3 * nblk <= std::max(a->n_cus, 1);
       a->ddpg_ksplit = a->ddpg_ksplit_can && !meet_device_shared() && !std::getenv("GCRL_NO_DDPG_KSPLIT");
       if (a->ddpg_ksplit_can && !a->rc_bar_words) { a->rc_bar_words = 2 * nblk * 32; wants.push_back({&a->rc_bar, a->rc_bar_words}); }
     }
@@ -1572,14 +1533,10 @@ int build(gcrl_agent* a) {
     if (c.kind == GCRL_AGENT_DDPG && c.pipeline_steps != 0) a->head_batches = 4;
     if (const char* e = std::getenv("GCRL_HEAD_BATCHES")) a->head_batches = std::max(1, std::min(8, std::atoi(e)));   // experiment knob
     a->main_idx_staged = std::getenv("GCRL_MAIN_IDX_STAGED") != nullptr;   // A/B knob (finish_deferred_draw)
-    a->dw_batch_off = std::getenv("GCRL_NO_DW_BATCH") != nullptr;
     a->bn_fused_tiled = std::getenv("GCRL_NO_BN_TILED_STATS") == nullptr;
     a->layer_adv_off = std::getenv("GCRL_NO_LAYER_ADV") != nullptr;
     a->red_off = std::getenv("GCRL_NO_MB_REDUCE") != nullptr;
     a->heads_fused_off = std::getenv("GCRL_NO_HEADS_FUSED") != nullptr;
-    a->bn_fused = std::getenv("GCRL_BN_FUSED") != nullptr;   // measured equal at cfg 5 (204.6 vs 203.6 us/step): off by default
-    if (const char* e = std::getenv("GCRL_SPLIT_RG"))   // experiment knob: four digits, rows/4 per workgroup of the four launches
-      for (int i = 0; i < 4 && e[i]; ++i) a->split_rg[i] = e[i] - '0';
   }
   // split dW reductions (gemm_tiled.h): at batch >= 1024 a dW problem is a long reduction into few 64x64 tiles; S workgroups
   // per tile, S = the power of two (<= 8) that brings the phase's launch to about five workgroups per CU (1280)
@@ -1600,28 +1557,22 @@ int build(gcrl_agent* a) {
       while (S < 8 && phase_tiles * (S * 2) <= 1280 && B / (16 * S * 2) >= 8) S *= 2;
       return S;
     };
-    // experiment knob: the split LDS-tiled dW form at any batch size.  Round 4, headline (B = 256), same box: 57.8 us/step with the
-    // 16x16 k-split form, 66.5 (S = 2) / 65.8 (S = 4) with the split tiled form, 74.1 with the unsplit one (GCRL_DW_TILED): stays off
-    const bool anyb = std::getenv("GCRL_DW_SPLIT_ANYB") != nullptr;
-    const bool on = (B >= 1024 || anyb) && B % 32 == 0 && !std::getenv("GCRL_NO_DW_SPLIT");
+    // Not below batch 1024.  Round 4, headline (B = 256), same box: 57.8 us/step with the 16x16 k-split form, 66.5 (S = 2) / 65.8 (S = 4)
+    // with the split tiled form, 74.1 with the unsplit one
+    const bool on = B >= 1024 && B % 32 == 0;
     // rc_add_dw (DDPG / TD3 on the row-block path: every dW problem of a phase in one launch) at batch >= 2048: TD3 cfg 3
     // 173.8 -> 168.7 us/step (the launch 31.2 -> 27.0 us by rocprofv3 at S = 8, 25.5 at S = 16; element-wise operands — the
     // head's M = 1, the first layer's 27 columns — go through the pipelined k-loop too, in the plain loop they set the launch's
     // length at one memory round trip per k-step).  Not at batch 1024 (DDPG cfg 2: 61.8 -> 67.8 us/step, 8 k-steps per split).
-    const bool chain_dw = a->rowchain && (c.kind == GCRL_AGENT_DDPG || c.kind == GCRL_AGENT_TD3) && (B >= 2048 || anyb);
+    const bool chain_dw = a->rowchain && (c.kind == GCRL_AGENT_DDPG || c.kind == GCRL_AGENT_TD3) && B >= 2048;
     long long tc = 0, ta = 0, big_c = 0;
     for (const Lin& ln : a->critic.lin) { tc += tiles_of(ln); if (ln.out >= 64 && ln.in >= 64) big_c += tiles_of(ln); }
     for (const Lin& ln : a->actor.lin) ta += tiles_of(ln);
-    const bool ens = !a->dw_batch_off && L >= 2 && (long long)C * (L - 1) * ((H + 63) / 64) * ((H + 1 + 63) / 64) >= 512;   // enqueue_critic's dw_batch
+    const bool ens = L >= 2 && (long long)C * (L - 1) * ((H + 63) / 64) * ((H + 1 + 63) / 64) >= 512;   // enqueue_critic's dw_batch
     if (on && chain_dw) { a->dw_split_c = pick(C * tc); a->dw_split_a = pick(ta); }
     else if (on && ens) a->dw_split_c = pick(C * big_c);
     // the BatchNorm actor at batch >= 2048 (TQC cfg 4): a hidden layer's dW joins its dX problem's LDS-tiled launch
-    if (on && a->sac && B >= 2048 && !a->rowchain && !std::getenv("GCRL_NO_DW_SPLIT_ACTOR")) a->dw_split_a = pick((long long)((H + 63) / 64) * ((H + 63) / 64));
-    if (const char* e = std::getenv("GCRL_DW_SPLIT")) {   // experiment knob
-      const int S = std::max(1, std::min(16, std::atoi(e)));
-      if (a->dw_split_c > 1) a->dw_split_c = S;
-      if (a->dw_split_a > 1) a->dw_split_a = S;
-    }
+    if (on && a->sac && B >= 2048 && !a->rowchain) a->dw_split_a = pick((long long)((H + 63) / 64) * ((H + 63) / 64));
     long long pc = 0, tcn = 0, pa = 0, tan = 0;
     layout(a->critic, a->dw_split_c, a->dwp_off_c, a->dwt_off_c, &pc, &tcn);
     layout(a->actor, a->dw_split_a, a->dwp_off_a, a->dwt_off_a, &pa, &tan);
@@ -1637,7 +1588,6 @@ int build(gcrl_agent* a) {
   TRY(bytes_alloc(&a->work, total));
   long long used = 0;
   for (auto& w : wants) { *w.first = a->work + used; used += align_up(w.second, 64); }
-  TRY(rowtile_reset(a));
   TRY(optfuse_reset(a));
   if (a->bn_xchg && a->bn_bar) { TRY(bn_slab_scratch_reset(a->bn_xchg, reinterpret_cast<unsigned int*>(a->bn_bar), H, nullptr)); GCRL_HIP(hipDeviceSynchronize()); }
 
@@ -2275,13 +2225,12 @@ int gcrl_agent_set_meetings(gcrl_agent* a, int on) {
   const gcrl_agent_config& c = a->cfg;
   const bool want = on != 0 && !meet_device_shared();
   a->bn_rsplit = (want && a->bn_slab && a->B > 128 && !std::getenv("GCRL_NO_BN_RSPLIT") && bn_slab_row_split(a->B, a->H, 2) > 1) ? 4 : 1;
-  a->rc_merge = want && a->rc_bar && a->split_roles && !std::getenv("GCRL_NO_RC_MERGE") && !std::getenv("GCRL_SPLIT_RG") &&
+  a->rc_merge = want && a->rc_bar && a->split_roles && !std::getenv("GCRL_NO_RC_MERGE") &&
                 rowchain_merge_ok(a->row_rg, a->row_ldl, c.ac_dim, a->H, a->C, a->B);
   a->rc_merge_k = want && a->rc_bar && a->split_k && !std::getenv("GCRL_NO_RC_MERGE");
   a->ddpg_ksplit = want && a->ddpg_ksplit_can && a->rc_bar && !std::getenv("GCRL_NO_DDPG_KSPLIT");
-  a->rowtile = want && a->rowtile_can && rowtile_enabled() && rowtile_ok(a->B, a->H, a->L, a->S, a->A, a->C);
   a->opt_fuse = want && a->opt_fuse_can && !std::getenv("GCRL_NO_OPT_FUSE");
-  return (a->bn_rsplit > 1 ? 1 : 0) | ((a->rc_merge || a->rc_merge_k || a->ddpg_ksplit) ? 2 : 0) | (a->rowtile ? 4 : 0) | (a->opt_fuse ? 8 : 0);
+  return (a->bn_rsplit > 1 ? 1 : 0) | ((a->rc_merge || a->rc_merge_k || a->ddpg_ksplit) ? 2 : 0) | (a->opt_fuse ? 8 : 0);
 }
 
 int gcrl_agent_get_meetings(gcrl_agent* a) {
@@ -2290,7 +2239,7 @@ int gcrl_agent_get_meetings(gcrl_agent* a) {
     const int rc = gcrl_agent_set_meetings(a, 0);
     if (rc < 0) return rc;
   }
-  return (a->bn_rsplit > 1 ? 1 : 0) | ((a->rc_merge || a->rc_merge_k || a->ddpg_ksplit) ? 2 : 0) | (a->rowtile ? 4 : 0) | (a->opt_fuse ? 8 : 0);
+  return (a->bn_rsplit > 1 ? 1 : 0) | ((a->rc_merge || a->rc_merge_k || a->ddpg_ksplit) ? 2 : 0) | (a->opt_fuse ? 8 : 0);
 }
 
 int gcrl_agent_debug_meet_fault(gcrl_agent* a) {
@@ -2301,11 +2250,7 @@ int gcrl_agent_debug_meet_fault(gcrl_agent* a) {
   // kept off the chip would cause
   const unsigned long long one = 7;
   float* words = a->rc_merge ? a->rc_bar : (a->bn_rsplit > 1 ? a->bn_bar : nullptr);
-  if (a->rowtile) {   // the first-arrival counter of the actor-phase role's row block 0: +7 of its H / 16 arrivals
-    GCRL_HIP(hipMemcpy(a->rt_ctr, &one, sizeof(one), hipMemcpyHostToDevice));
-    return GCRL_OK;
-  }
-  if (a->rc_merge_k || (a->ddpg_ksplit && !a->rowtile)) {   // producers / consumers: a consumer's own launch count far ahead of its producers' counter
+  if (a->rc_merge_k || a->ddpg_ksplit) {   // producers / consumers: a consumer's own launch count far ahead of its producers' counter
     const unsigned long long far = 1ull << 40;
     GCRL_HIP(hipMemcpy(a->rc_bar + 4, &far, sizeof(far), hipMemcpyHostToDevice));    // (64-bit word 2 of row block 0's line: critic 0's consumer)
     return GCRL_OK;
@@ -2536,7 +2481,7 @@ int gcrl_agent_observe_act(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normaliz
     ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
     ba.S = a->S; ba.H = a->H; ba.L = a->L; ba.A = A; ba.n = n; ba.D = D;
     ba.ldl = (std::max(a->S, a->H) + 3) / 4 * 4;
-    ba.warm = std::getenv("GCRL_ACT_BN_WARM") ? 1 : 0;   // (measured slower at both shapes, profiles/r09_sac_acting.jsonl: off unless asked for)
+    ba.warm = 0;   // (warming the weights measured slower at both shapes, profiles/r09_sac_acting.jsonl)
     gcrl::normalizer_view(nz_obs, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
     gcrl::normalizer_view(nz_dg, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
     if (fits_inline) {

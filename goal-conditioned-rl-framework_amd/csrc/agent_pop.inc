@@ -385,16 +385,16 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
   const bool tqc = a0->cfg.kind == GCRL_AGENT_TQC;
   const bool sac = a0->cfg.kind == GCRL_AGENT_SAC || tqc;   // (the BatchNorm actors: their slab launches have the row-split form)
   const bool ksplit = !sac && (forms & 2) != 0, ofuse = (forms & 8) != 0, rsplit = (forms & 1) != 0, merge = sac && (forms & 2) != 0;
-  struct Forms { bool ksplit, ofuse, rowtile, rc_merge; int bn_rsplit; };
+  struct Forms { bool ksplit, ofuse, rc_merge; int bn_rsplit; };
   std::vector<Forms> saved(P);
   for (int i = 0; i < P; ++i) {
     gcrl_agent* a = p->m[i];
-    saved[i] = Forms{a->ddpg_ksplit, a->opt_fuse, a->rowtile, a->rc_merge, a->bn_rsplit};
+    saved[i] = Forms{a->ddpg_ksplit, a->opt_fuse, a->rc_merge, a->bn_rsplit};
   }
   auto restore = [&]() {
     for (int i = 0; i < P; ++i) {
       gcrl_agent* a = p->m[i];
-      a->ddpg_ksplit = saved[i].ksplit; a->opt_fuse = saved[i].ofuse; a->rowtile = saved[i].rowtile; a->rc_merge = saved[i].rc_merge; a->bn_rsplit = saved[i].bn_rsplit;
+      a->ddpg_ksplit = saved[i].ksplit; a->opt_fuse = saved[i].ofuse; a->rc_merge = saved[i].rc_merge; a->bn_rsplit = saved[i].bn_rsplit;
     }
   };
   const int chunk = std::min(kMaxStepsPerCall, a0->Mmax);
@@ -419,7 +419,7 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
     int rc = GCRL_OK;
     for (int i = 0; i < P && !rc; ++i) {
       gcrl_agent* a = p->m[i];
-      a->ddpg_ksplit = ksplit; a->opt_fuse = ofuse; a->rowtile = false;
+      a->ddpg_ksplit = ksplit; a->opt_fuse = ofuse;
       if (sac) { a->rc_merge = merge; if (!rsplit) a->bn_rsplit = 1; }
       rc = pop_record_steps(a, a0->cap_stream, plans[i], &p->rec[i]);
     }
@@ -611,7 +611,6 @@ int gcrl_pop_observe_act_bn(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_no
   }
   // the members' table: what belongs to the member, filled as gcrl_agent_observe_act fills its own arguments
   ActBnArgs tab[kMaxPopMembers];
-  const int warm = std::getenv("GCRL_ACT_BN_WARM") ? 1 : 0;
   for (int i = 0; i < P; ++i) {
     gcrl_agent* a = p->m[i];
     ActBnArgs& ba = tab[i];
@@ -619,7 +618,7 @@ int gcrl_pop_observe_act_bn(gcrl_pop* p, gcrl_normalizer* const* nz_obs, gcrl_no
     ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
     ba.S = S; ba.H = a->H; ba.L = a->L; ba.A = A; ba.n = n; ba.D = D;
     ba.ldl = (std::max(S, a->H) + 3) / 4 * 4;
-    ba.warm = warm;
+    ba.warm = 0;   // (as gcrl_agent_observe_act: measured slower)
     gcrl::normalizer_view(nz_obs ? nz_obs[i] : nullptr, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
     gcrl::normalizer_view(nz_dg ? nz_dg[i] : nullptr, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
   }

@@ -86,11 +86,7 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
   rc.slot_x = a->slot_x; rc.slot_rd = a->slot_rd;
   rc.ldx = a->ldx; rc.ldl = a->row_ldl; rc.B = a->B; rc.S = a->S; rc.A = a->A; rc.Apad = a->Apad;
   const int nblk = (a->B + 4 * a->row_rg - 1) / (4 * a->row_rg);
-  // roles by XCD (K on XCDs 0-3, P on 4-7): measured in round 4 — HBM-side traffic of the launch 32.3 -> 23.4 MB (PMC), but the step
-  // 56.03 -> 56.53 us (same box, 3 rounds each): the launch is latency-bound, not traffic-bound, and 16 lock-stepped workgroups of
-  // one role per XCD collide on the same L2 lines more than 8 + 8 of two roles do.  Off unless GCRL_ROW_XCD_ROLES=1.
-  static const bool xcd_roles = std::getenv("GCRL_ROW_XCD_ROLES") != nullptr;
-  rc.linear_roles = xcd_roles ? 0 : 1;
+  rc.linear_roles = 1;   // (roles by XCD, K on XCDs 0-3 and P on 4-7: HBM-side traffic 32.3 -> 23.4 MB but the step 56.03 -> 56.53 us, round 4)
   rc.nblk_k = (what & 1) ? nblk : 0;
   rc.nblk_p = (what & 2) ? nblk : 0;
   rc.hC = a->hC; rc.gC = a->rc_gC; rc.q = a->q; rc.y = a->ybuf; rc.dq = a->dq;
@@ -100,8 +96,6 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
   rc.qt = a->qt;
   if (a->split_roles) {
     // twin critics at a latency-bound batch size: each network's chain in its own workgroups (rowchain.h)
-    // rows per workgroup of each of the four launches (K forward has 2C roles, the others C)
-    const int* rg = a->split_rg;
     HeadsFold hfold;
     std::memset(&hfold, 0, sizeof(hfold));
     if (heads_fold_on(a)) {
@@ -128,12 +122,12 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
     const HeadsFold* hfp_p = (hfold.on && !hfold.cur_in_k) ? &hfold : nullptr;   // phase 1 runs on the stored pi otherwise
     if (a->rc_merge) {   // forward and backward parts of a phase in ONE launch: the role workgroups of a row block meet inside it (rowchain.h)
       rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev;
-      if (what & 1) TRY(launch_rowchain_split(st, rc, rg[0], 0, 3, hfp));
-      if (what & 2) TRY(launch_rowchain_split(st, rc, rg[2], 1, 3, hfp_p));
+      if (what & 1) TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 3, hfp));
+      if (what & 2) TRY(launch_rowchain_split(st, rc, a->row_rg, 1, 3, hfp_p));
       return GCRL_OK;
     }
-    if (what & 1) { TRY(launch_rowchain_split(st, rc, rg[0], 0, 1, hfp)); TRY(launch_rowchain_split(st, rc, rg[1], 0, 2)); }
-    if (what & 2) { TRY(launch_rowchain_split(st, rc, rg[2], 1, 1, hfp_p)); TRY(launch_rowchain_split(st, rc, rg[3], 1, 2)); }
+    if (what & 1) { TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 1, hfp)); TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 2)); }
+    if (what & 2) { TRY(launch_rowchain_split(st, rc, a->row_rg, 1, 1, hfp_p)); TRY(launch_rowchain_split(st, rc, a->row_rg, 1, 2)); }
     return GCRL_OK;
   }
   if (a->split_k) {
@@ -151,27 +145,14 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
     rc.k_split = 1; rc.producers_first = 1;
     rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev;
   }
-  auto chain = [&]() -> int {
-    if (!a->rowtile) return launch_rowchain_ddpg(st, rc, a->row_rg);
-    // weight-slice form (rowtile.hip): 16 x 16 tiles of every layer per workgroup, the row block's workgroups hand each other the layers
-    RowTileArgs rt;
-    std::memset(&rt, 0, sizeof(rt));
-    rt.rc = rc;
-    rt.xb = a->rt_xb; rt.qpart = a->rt_qpart;
-    rt.ctr = reinterpret_cast<unsigned long long*>(a->rt_ctr); rt.xid = reinterpret_cast<unsigned int*>(a->rt_xid);
-    rt.status = a->status_dev;
-    static const bool sc1 = std::getenv("GCRL_ROWTILE_SC1") != nullptr;   // A/B knob: never the plain-store (same-XCD) form
-    rt.force_sc1 = sc1 ? 1 : 0;
-    return launch_rowtile_ddpg(st, rt);
-  };
-  if (!a->prof || what != 3) return chain();
+  if (!a->prof || what != 3) return launch_rowchain_ddpg(st, rc, a->row_rg);
   // measurement mode (never inside a graph capture): the overlapped launch, bracketed
   if (a->prof_used == gcrl_agent::kProfPairs) TRY(prof_drain(a));
   const unsigned long long init[2] = {~0ull, 0ull};
   rc.clk = a->prof_clk + 2 * a->prof_used;
   GCRL_HIP(hipMemcpyAsync(rc.clk, init, sizeof(init), hipMemcpyHostToDevice, st));
   GCRL_HIP(hipEventRecord(a->prof_a[a->prof_used], st));
-  TRY(chain());
+  TRY(launch_rowchain_ddpg(st, rc, a->row_rg));
   GCRL_HIP(hipEventRecord(a->prof_b[a->prof_used], st));
   a->prof_used++;
   a->prof_launches++;
@@ -195,8 +176,6 @@ void rc_add_dw(gcrl_agent* a, Launches& ls, const PipeCtx& c, bool critic, bool 
       if (l == 0) { dw.slot = c.slot; dw.b_slot = a->slot_x; }
       if (fused) dw.sumsq_out = critic ? a->parts_c + (long long)k * a->nparts_c + a->part_off_c[l] : a->parts_a + a->part_off_a[l];
       dw_split_form(a, dw, critic ? k : -1, l);
-      static const bool tiled = std::getenv("GCRL_DW_TILED") != nullptr;   // experiment knob: the (unsplit) LDS-tiled form for the big dW problems
-      if (tiled && dw.M >= 64 && dw.N >= 64) dw.shape_hint = 4;
       ls.add(0, dw);
     }
   }
@@ -294,11 +273,7 @@ void of_common(gcrl_agent* a, DwAdamArgs& da) {
   da.tau = (float)a->cfg.tau; da.one_m_tau = (float)(1.0 - a->cfg.tau);
   da.metrics = a->metrics_dev;
   da.status = a->status_dev;
-  static const int first_sleep = std::getenv("GCRL_OF_SLEEP_FIRST") ? std::atoi(std::getenv("GCRL_OF_SLEEP_FIRST")) : 0;   // experiment knobs
-  static const int poll_sleep = std::getenv("GCRL_OF_SLEEP_POLL") ? std::atoi(std::getenv("GCRL_OF_SLEEP_POLL")) : 2;
-  static const int gate = std::getenv("GCRL_OF_GATE") ? std::atoi(std::getenv("GCRL_OF_GATE")) : 0;
-  static const bool flat = std::getenv("GCRL_OF_FLAT") != nullptr;
-  da.poll_first_sleep = first_sleep; da.poll_sleep = poll_sleep; da.poll_gate = gate; da.leaders = flat ? 0 : 1;
+  da.poll_first_sleep = 0; da.poll_sleep = 2; da.poll_gate = 0; da.leaders = 1;
 }
 
 // TD3 / SAC on the row-chain path (per-step phases, agent.hip): every critic's dW | db + clip + AdamW (+ Polyak) in ONE launch at the

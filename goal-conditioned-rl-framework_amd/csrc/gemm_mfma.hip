@@ -133,15 +133,6 @@ int prep_outer(GemmBatch& gb) {
 }
 
 int prep_tiled(GemmBatch& gb) {
-  static const bool trace = std::getenv("GCRL_GEMM_TRACE") != nullptr;
-  if (trace) {
-    std::fprintf(stderr, "[tiled] %d problems:", gb.n);
-    for (int i = 0; i < gb.n; ++i) {
-      const GemmDesc& d = gb.d[i];
-      std::fprintf(stderr, " (M=%d N=%d K=%d a:%d%d b:%d%d ones=%d)", d.M, d.N, d.K, d.a_vec, d.a_rvec, d.b_vec, d.b_rvec, d.ones_col);
-    }
-    std::fprintf(stderr, "\n");
-  }
   int tiles = 0;
   for (int i = 0; i < gb.n; ++i) {
     GemmDesc& d = gb.d[i];

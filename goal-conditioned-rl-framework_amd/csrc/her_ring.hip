@@ -482,49 +482,6 @@ __global__ __launch_bounds__(256) void her_gather_update_pop_kernel(GatherUpdPop
 #include "her_gather_update_body.inc"
 }
 
-// round 2's form of the same gather (per-lane index loads, stores straight from the load lanes), kept for same-box A/B runs:
-// GCRL_GATHER_R2=1
-template <int kUnroll>
-__global__ __launch_bounds__(256) void her_gather_update_r2_kernel(GatherUpdArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane >> 4, v4 = lane & 15;
-  const long long wave_id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long long nwaves = (long long)gridDim.x * 4;
-  const int o_r = p.SA4 + p.S4;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < p.cp_n16; i += gridDim.x * 256) p.cp_dst[i] = p.cp_src[i];
-  // records wider than 64 floats (state dims above ~28) take further 64-float column passes
-  for (int cc = 0; cc < p.RS; cc += 64) {
-    const int c0 = cc + v4 * 4;
-    for (long long r0 = wave_id * (4 * kUnroll); r0 < p.n; r0 += nwaves * (4 * kUnroll)) {
-      float4 val[kUnroll];
-      long long row[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        row[u] = r0 + u * 4 + sub;
-        val[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row[u] < p.n && c0 < p.RS) {
-          const long long phys = (p.head + (long long)(p.idx ? p.idx[row[u]] : gcrl::idxgen_at(p.gen, row[u]))) % p.cap;
-          val[u] = *reinterpret_cast<const float4*>(p.ring + phys * p.RS + c0);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        if (row[u] >= p.n) continue;
-        const long long ro = row[u] * p.ldx;
-        if (c0 < p.SA4) {
-          *reinterpret_cast<float4*>(p.sa + ro + c0) = val[u];
-          if (p.spa && c0 < p.S4) *reinterpret_cast<float4*>(p.spa + ro + c0) = val[u];
-        } else if (c0 < o_r) {
-          *reinterpret_cast<float4*>(p.nsa + ro + (c0 - p.SA4)) = val[u];
-        } else if (c0 == o_r) {
-          p.r[row[u]] = val[u].x;
-          p.d[row[u]] = val[u].y;
-        }
-      }
-    }
-  }
-}
-
 // rows [first, first+n) in logical order -> contiguous records (read_rows)
 __global__ void her_copy_rows_kernel(const float* ring, long long head, long long cap, int RS,
                                      long long first, long long n, float* out) {
@@ -754,10 +711,7 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
                    (const uint4*)cp_src, (uint4*)cp_dst, (int)(cp_bytes / 16)};
   const int blocks = (int)((n + 63) / 64);                                              // 16 rows per wave, 4 waves per block
   const size_t lds = 4 * ((size_t)32 * h->SA4 + 32) * sizeof(float);                    // <= 54 KB (record <= 160 floats)
-  static const int dev_variant = std::getenv("GCRL_GATHER_R2") ? 2 : (std::getenv("GCRL_GATHER_PLAIN") ? 1 : 0);   // development A/B knobs
-  if (dev_variant == 2) hipLaunchKernelGGL(her_gather_update_r2_kernel<4>, dim3((int)std::min<int64_t>((n + 63) / 64, 8192)), dim3(256), 0, st, ga);
-  else if (cp_bytes) hipLaunchKernelGGL(her_gather_update_kernel<true>, dim3(blocks), dim3(256), lds, st, ga);
-  else if (dev_variant == 1) hipLaunchKernelGGL((her_gather_update_kernel<false, false>), dim3(blocks), dim3(256), lds, st, ga);
+  if (cp_bytes) hipLaunchKernelGGL(her_gather_update_kernel<true>, dim3(blocks), dim3(256), lds, st, ga);
   else hipLaunchKernelGGL(her_gather_update_kernel<false>, dim3(blocks), dim3(256), lds, st, ga);
   GCRL_HIP(hipGetLastError());
   return prof_end(h, st, n);
@@ -766,8 +720,7 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
 int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merged) {
   if (merged) *merged = false;
   if (P < 1 || P > kGatherPopMax) return fail(GCRL_ERR_ARG, "her_gather_update_pop: %d members (1..%d)", P, kGatherPopMax);
-  static const bool dev_variant = std::getenv("GCRL_GATHER_R2") || std::getenv("GCRL_GATHER_PLAIN");   // development A/B knobs: the members' own launches
-  bool one = P >= 2 && !dev_variant;
+  bool one = P >= 2;
   for (int i = 0; i < P; ++i) {
     const GatherCall& g = c[i];
     if (g.cp_bytes % 16 != 0 || (g.cp_bytes && (!g.cp_src || !g.cp_dst))) return fail(GCRL_ERR_ARG, "her_gather_update_pop: member %d: bad side copy (%zu bytes)", i, g.cp_bytes);
@@ -1071,7 +1024,7 @@ int64_t gcrl_her_process_step_g(gcrl_her* h, gcrl_normalizer* nz_obs, int update
   // ONE upload: raw rows [obs(n*D) | next_obs(n*D) | dg(n*G) | next_dg(n*G)], then the per-env payload [t | r | d | a | ag]
   const size_t raw = (size_t)n * (2 * D + (nz_dg ? 4 : 2) * G), need = raw + (size_t)n * kPayW;
   static_assert(sizeof(ProcArgsInline) <= 4096, "kernel arguments are limited to 4 KB");
-  const bool inl = need <= (size_t)kProcInlineFloats && !std::getenv("GCRL_PROC_STAGED");
+  const bool inl = need <= (size_t)kProcInlineFloats;
   if (!inl && need > h->ps_floats) {
     GCRL_HIP(hipDeviceSynchronize());
     if (h->ps_dev) GCRL_HIP(hipFree(h->ps_dev));

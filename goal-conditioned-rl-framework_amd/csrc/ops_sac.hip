@@ -704,7 +704,7 @@ int launch_quantile_actor(hipStream_t st, const QuantileActorArgs& a) {
 }
 
 static inline unsigned reduce_threads(long long n) { return (unsigned)std::min<long long>(1024, std::max<long long>(256, (n + 63) / 64 * 64)); }
-static inline int bn_slabs(int B) { static const char* e = getenv("GCRL_BN_SLABS"); if (e) return atoi(e); return std::min(kBnSlabMax, std::max(1, B / 1024)); }
+static inline int bn_slabs(int B) { return std::min(kBnSlabMax, std::max(1, B / 1024)); }
 static inline bool bn_aligned(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
 
 int launch_bn_relu_fwd(hipStream_t st, const float* z, int B, int H, const float* gamma,

@@ -262,7 +262,7 @@ struct RowChainArgs {
   long long slot_x, slot_rd;
   int ldx, ldl, B, S, A, Apad;
   int nblk_k, nblk_p;
-  int linear_roles;           // 1 (default): roles in launch order (K's workgroups first); 0: by XCD (GCRL_ROW_XCD_ROLES=1: A/B knob, agent_rowchain.inc)
+  int linear_roles;           // 1 (default): roles in launch order (K's workgroups first); 0: by XCD (never asked for: agent_rowchain.inc)
   float *hC, *gC, *q, *y, *dq;      // K: activations / pre-activation gradients [C][L][B][H], q / dq [C][B], y [B]
   float *hA, *gA, *hC2, *q2, *dz;   // P: ..., critic activations (scratch) [C][L][B][H], Q(s, pi(s)) [C][B], d(pre-tanh) [C][B][Apad]
   float gamma, clamp_lo;
@@ -368,26 +368,6 @@ struct RowActPop {
   int stride_n;
 };
 int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int n, int ldl, int A, int H);
-
-// Weight-slice form of the DDPG launch (rowtile.hip): a workgroup owns the 16 x 16 tile (row block, column block) of every
-// layer of its role's chain; the H / 16 workgroups of a row block hand the layer outputs to each other inside the launch.
-struct RowTileArgs {
-  RowChainArgs rc;            // networks, batch arrays, outputs (nblk_k / nblk_p != 0: which phases run)
-  float* xb;                  // hand-off tile stages [2 roles][4L][B][H], every word 0xFFFFFFFF ("not written yet") between launches
-  float* qpart;               // scalar-head partials [3][B/16][H/16][16]: Q' (target chain), q (online critic), Q(s, pi(s)); same convention
-  unsigned long long* ctr;    // first-arrival counters [2 roles][B/16][16 words]: one 128-byte line each, zero-initialised, monotonic
-  unsigned int* xid;          // [2 roles][B/16][32]: the XCD of each workgroup of a row block (+1)
-  unsigned int* status;       // host-visible word: MEET_ERR_ROWCHAIN on a timed-out wait
-  int force_sc1;              // never the plain-store form (GCRL_ROWTILE_SC1=1)
-  // filled by the launcher
-  int roles[3], nroles, nstage, w16, ldsx, kperx, force_linear, role_mask, sleep_first, sleep_poll;
-};
-bool rowtile_shape_ok(int B, int H, int L, int S, int A, int C);
-bool rowtile_ok(int B, int H, int L, int S, int A, int C);   // ... and all 3 * (B/16) * (H/16) workgroups resident at once, device not shared
-long long rowtile_ctr_words(int B, int L);                   // 64-bit words
-long long rowtile_xb_floats(int B, int H, int L);
-long long rowtile_part_floats(int B, int H);
-int launch_rowtile_ddpg(hipStream_t st, RowTileArgs t);
 
 // rows per workgroup = 4*rg, rg in {1, 2, 4}
 int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg);

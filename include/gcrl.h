@@ -619,7 +619,7 @@ int gcrl_agent_dp_sync_bn_xchg(gcrl_agent* a, int world, int rank, gcrl_xchg* bx
  *                               library's collectives) — handles created afterwards use the launch forms without waits;
  *   gcrl_agent_set_meetings     switches an existing handle (0: off; 1: on where admissible); captured graphs are dropped;
  *                               returns a bit mask of the forms now active (1 slab row groups, 2 row-chain roles: merged phases,
- *                               DDPG's two-role critic phase; 4 the opt-in weight-slice DDPG launch, GCRL_ROWTILE=1; 8 the
+ *                               DDPG's two-role critic phase; 4 reserved, always 0 (a launch form deleted in round 18); 8 the
  *                               fused dW | db + clip + optimiser launch of the row-chain agents, csrc/dw_adam.hip — the reference's
  *                               backward -> clip_grad_norm_ -> optimizer.step(), src/agent.py:1326-1333, :1288-1300, :199-222);
  *   gcrl_agent_get_meetings     the same mask, changing nothing;

@@ -22,7 +22,6 @@ pytestmark = pytest.mark.gpu
 
 
 def _agent(gcrl, monkeypatch, fused, H, L, B, **kw):
-    monkeypatch.delenv("GCRL_ROWTILE", raising=False)
     if fused:
         monkeypatch.delenv("GCRL_NO_OPT_FUSE", raising=False)
     else:
@@ -249,3 +248,21 @@ def test_two_agents_queued_back_to_back_do_not_wait_on_each_other(gcrl, monkeypa
             ref[who] += [tuple(float(x) for x in t) for t in ag.update_many(1 + 40 * c, 40)]
     assert got == ref
     assert np.all(np.isfinite(np.array(got)))
+
+
+@pytest.mark.parametrize("H,L,B", [(64, 3, 64), (256, 3, 256)])
+def test_two_role_critic_phase_is_bitwise_the_one_role_launch(gcrl, monkeypatch, H, L, B):
+    """DDPG's critic phase as two roles of the fused row-chain launch (target chain | online critic, producers / consumers:
+    csrc/rowchain.hip k_split, the default) against the launch that walks a row block through both (GCRL_NO_DDPG_KSPLIT=1): the
+    same per-row arithmetic in the same order — 90 pipelined steps, every tuple and every parameter bitwise equal."""
+    monkeypatch.setenv("GCRL_NO_DDPG_KSPLIT", "1")
+    a_one = _ddpg_for_schedules(gcrl, H, L, 2, B=B)
+    assert not (a_one.meetings() & 2)
+    one = _run_many(a_one)
+    monkeypatch.delenv("GCRL_NO_DDPG_KSPLIT")
+    a_two = _ddpg_for_schedules(gcrl, H, L, 2, B=B)
+    if not (a_two.meetings() & 2):
+        pytest.skip("launch forms with in-kernel waits are not admissible on this device")
+    assert _run_many(a_two) == one
+    for v1, v2 in [(a_one.actor, a_two.actor), (a_one.critic, a_two.critic), (a_one.target_critic, a_two.target_critic)]:
+        assert np.array_equal(v1.flat(), v2.flat())

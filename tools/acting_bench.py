@@ -9,9 +9,8 @@ on every 50th step.  Legs, alternated over `--rounds` rounds, each in a fresh ch
 
 usage: tools/acting_bench.py [--rounds 5] [--steps 3000] [--parent-tree DIR] [--out FILE.jsonl]
        tools/acting_bench.py --child KIND H L [--tree DIR] [--steps N]      (one leg; prints one JSON line)
-Writes one JSON line per shape with the median and min-max of every leg (default profiles/r09_sac_acting.jsonl); --warm adds the
-leg `warm` (GCRL_ACT_BN_WARM=1: the kernel with its L2 warm-up loads).  Kernel durations come from a run of one leg under the
-profiler, on its own:
+Writes one JSON line per shape with the median and min-max of every leg (default profiles/r09_sac_acting.jsonl).  Kernel durations
+come from a run of one leg under the profiler, on its own:
   rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- python tools/acting_bench.py --child SAC 256 3 --steps 1000
 (DIR/**/run_kernel_stats.csv; the two shapes' files are concatenated into profiles/r09_sac_acting_kernel_stats.csv)."""
 import argparse
@@ -68,7 +67,6 @@ def child(kind, H, L, tree, steps):
 def run_leg(shape, tree, steps, knob):
     env = dict(os.environ)
     env.pop("GCRL_ACT_STAGED", None)
-    env.pop("GCRL_ACT_BN_WARM", None)
     if knob:
         env[knob] = "1"
     cmd = [sys.executable, os.path.abspath(__file__), "--child", shape["kind"], str(shape["H"]), str(shape["L"]), "--tree", tree, "--steps", str(steps)]
@@ -85,14 +83,11 @@ def main():
     ap.add_argument("--parent-tree")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=3000)
-    ap.add_argument("--warm", action="store_true")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "r09_sac_acting.jsonl"))
     a = ap.parse_args()
     if a.child:
         return child(a.child[0], int(a.child[1]), int(a.child[2]), os.path.abspath(a.tree), a.steps)
     legs = [("new", HERE, None)] + ([("parent", os.path.abspath(a.parent_tree), None)] if a.parent_tree else []) + [("staged", HERE, "GCRL_ACT_STAGED")]
-    if a.warm:
-        legs.append(("warm", HERE, "GCRL_ACT_BN_WARM"))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         for shape in SHAPES:

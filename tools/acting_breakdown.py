@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where one vector-env step of the stand-in trainer spends its HOST time (wall clock per call, 8 envs), split into the Python
 wrapper (array marshalling, RNG draws, ctypes argument conversion) and the native call (staging, launches, the wait for the
-actions).  GCRL_ACT_STAGED=1 / GCRL_PROC_STAGED=1 select the round-3 forms (staged copies + stream synchronisation) for an A/B.
+actions).  GCRL_ACT_STAGED=1 selects observe_act's round-3 form (staged copies + stream synchronisation) for an A/B.
 Writes gpurun_out/acting_breakdown.json."""
 import json
 import os
@@ -73,7 +73,7 @@ def run(kind, n=8, N=3000):
                                        "includes the flush launch on the steps that end an episode"),
                 env_step_us=us(t["env"]),
                 env_steps_per_s_acting_only=round(n * N / (t["act"] + t["env"] + t["proc"]), 1),
-                forms=dict(act="staged" if os.environ.get("GCRL_ACT_STAGED") else "inline", proc="staged" if os.environ.get("GCRL_PROC_STAGED") else "inline"))
+                forms=dict(act="staged" if os.environ.get("GCRL_ACT_STAGED") else "inline", proc="inline"))
 
 
 if __name__ == "__main__":

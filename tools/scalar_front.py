@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S"]
-UNITS = sys.argv[1:] or ["rowchain.hip", "gemm_mfma.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "dw_adam.hip", "her_ring.hip", "rowtile.hip", "xchg_ipc.hip", "normalizer.hip"]
+UNITS = sys.argv[1:] or ["rowchain.hip", "gemm_mfma.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "dw_adam.hip", "her_ring.hip", "xchg_ipc.hip", "normalizer.hip"]
 
 
 def kernels(text):
