@@ -273,7 +273,6 @@ void of_common(gcrl_agent* a, DwAdamArgs& da) {
   da.tau = (float)a->cfg.tau; da.one_m_tau = (float)(1.0 - a->cfg.tau);
   da.metrics = a->metrics_dev;
   da.status = a->status_dev;
-  da.poll_first_sleep = 0; da.poll_sleep = 2; da.poll_gate = 0; da.leaders = 1;
 }
 
 // TD3 / SAC on the row-chain path (per-step phases, agent.hip): every critic's dW | db + clip + AdamW (+ Polyak) in ONE launch at the

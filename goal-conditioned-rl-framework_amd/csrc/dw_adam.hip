@@ -15,6 +15,8 @@ namespace {
 
 constexpr unsigned long long kSlotEmpty = ~0ull;
 constexpr int kLeaderMinTiles = 64;
+constexpr int kSc1 = 16;      // cache-policy bit of the raw buffer builtins on gfx94x / gfx950: written through to the memory side
+constexpr int kImgLd = 20;    // row stride of a regular tile's LDS images: rows stay 16-byte aligned
 static_assert(kFusedMaxLayers == 5, "DwNetHead::tile0 holds the first tiles of problems 1..4");   // a negative quiet NaN with every payload bit set: never a sum of squares
 
 // development build (-DGCRL_OF_STAMPS, tools/of_stamps.sh): thread 0 of every workgroup leaves the constant-rate clock (100 MHz) at
@@ -42,6 +44,12 @@ __device__ __forceinline__ T load_uniform(const T* p) {
 typedef float __attribute__((address_space(1))) gfloat;
 typedef unsigned long long __attribute__((address_space(1))) gu64;
 typedef unsigned int __attribute__((address_space(1))) gu32;
+
+// between two polls of a norm slot or result word (s_sleep counts 64 clocks)
+__device__ __forceinline__ void poll_pause() {
+  __builtin_amdgcn_s_sleep(1);
+  __builtin_amdgcn_s_sleep(1);
+}
 
 // a POD record copied HERE, every dword of it in a scalar register: the loads of its fields cannot sink to their uses (left to
 // itself the compiler fetched every field where it was first needed: a dozen dependent scalar round trips in front of the GEMM)
@@ -82,7 +90,6 @@ struct DwNetK {
 };
 struct DwAdamK {
   float beta2, w1, w2, eps, tau, one_m_tau;
-  int leaders, poll_gate, poll_first_sleep, poll_sleep;
   float* metrics; CtrlBlock* advance; unsigned int* status;
 #ifdef GCRL_OF_STAMPS
   unsigned long long* stamps;
@@ -112,7 +119,6 @@ int launch_dw_adam(hipStream_t st, DwAdamArgs& a) {
   DwAdamK k;
   std::memset(&k, 0, sizeof(k));
   k.beta2 = a.beta2; k.w1 = a.w1; k.w2 = a.w2; k.eps = a.eps; k.tau = a.tau; k.one_m_tau = a.one_m_tau;
-  k.leaders = a.leaders; k.poll_gate = a.poll_gate; k.poll_first_sleep = a.poll_first_sleep; k.poll_sleep = a.poll_sleep;
   k.metrics = a.metrics; k.advance = a.advance; k.status = a.status;
 #ifdef GCRL_OF_STAMPS
   k.stamps = a.stamps;

@@ -9,6 +9,7 @@
   __shared__ double dred[4];
   __shared__ float s_coef;
   __shared__ float tile_p[16][17], tile_t[16][17];
+  __shared__ __attribute__((aligned(16))) float img[4][16][kImgLd];   // a regular tile's p / m / v / target: in as loaded, out as stepped
   const DwNetK& on = a.net[by];
   DwNetHead o = on.h;          // first round trip: 16 dwords
   pin(o);
@@ -16,7 +17,6 @@
   // XCD-aware workgroup -> tile order (gemm_mfma.h xcd_tile_of, here for the 2-D grid: workgroup (x, y) runs on XCD
   // (x + y * gridDim.x) % 8): an XCD takes a contiguous range of the net's tiles — whole tile rows of a layer, i.e. that layer's
   // activations enter ONE L2 instead of eight.  A wrong guess about the placement costs speed, never correctness.
-  const unsigned long long t_start = wall_clock64();
   int bid = (int)bx;
   {
     const int per = o.ntiles >> 3;
@@ -86,11 +86,31 @@
     __hip_atomic_store(mine + slot, (unsigned long long)__double_as_longlong(dt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
     gslots[(long long)((seq & 1u) ^ 1u) * o.slot_stride + slot] = kSlotEmpty;   // nobody reads the other array in this launch; the kernel boundary publishes it
   }
+  // A regular tile — all 16 x 16 elements are weights of a layer whose rows are whole 16-byte runs — moves its parameter traffic as
+  // ONE 16-byte access per lane and array: wave w takes array w (p, m, v; target on a Polyak step), lane -> row lane >> 2, columns
+  // 4 * (lane & 3) ..+3, through an LDS image, and the new values leave written through (sc1): nothing of them stays dirty in this
+  // XCD's L2 for the kernel boundary to write back.  (16-byte sc1 stores cost what plain ones do; 4-byte ones six times that.)
+  // Every other tile — first layers with odd rows, the bias column, head rows, partial tiles — keeps the element-per-lane path.
+  // (Worked out HERE, behind the tile body, from operands the compiler cannot see through: in front of it the operand requests
+  // left 0.4 us later.  And the 16-byte pre-load stands in front of the other path's loads, not in an else branch: laid out behind
+  // them, its zero-initialised registers were those loads' destinations and the compiler drained every access in flight —
+  // s_waitcnt vmcnt(0), the gradient tile's stores included — before requesting it.)
+  int in_q = in, out_q = out;
+  asm volatile("" : "+s"(in_q), "+s"(out_q) :: "memory");
+  const bool wt_wide = lay.wt_dst < 0 || ((out_q & 3) == 0 && (lay.wt_dst & 3) == 0 &&
+                                          (((unsigned long long)ptr.wt | (pk ? (unsigned long long)ptr.wt_target : 0ull)) & 15) == 0);
+  const bool regular = (in_q & 3) == 0 && n0 + 16 <= in_q && m0 + 16 <= out_q && (lay.pw & 3) == 0 && wt_wide &&
+                       (((unsigned long long)ptr.p | (unsigned long long)ptr.m | (unsigned long long)ptr.v | (pk ? (unsigned long long)ptr.target : 0ull)) & 15) == 0;
+  const bool mover = wave < 3 || pk;              // (uniform per wave) this wave has an array to move
+  const int r4 = lane >> 2, c4 = (lane & 3) << 2;
+  const float* const my_arr = wave == 0 ? ptr.p : wave == 1 ? ptr.m : wave == 2 ? ptr.v : ptr.target;
   // this lane's parameter, moments and target: requested now, they arrive while the slots are awaited.  (In front of the tile body
   // they cost it a round trip: its k-loop's header waits for every load in flight — the registers its loads return in are reused
   // per iteration — and so the operand requests went out only after these had landed.)
   float pre_p = 0.f, pre_m = 0.f, pre_v = 0.f, pre_t = 0.f;
-  if (my_i >= 0) {
+  v4u pre4 = {0u, 0u, 0u, 0u};
+  if (regular && mover) pre4 = __builtin_amdgcn_raw_buffer_load_b128(wave_uniform_rsrc_n(my_arr + lay.pw + (long long)m0 * in + n0, 15LL * in + 16), (r4 * in + c4) * 4, 0, 0);
+  if (!regular && my_i >= 0) {
     pre_p = gp[my_i]; pre_m = gm[my_i]; pre_v = gv[my_i];
     if (pk) pre_t = gt[my_i];
   }
@@ -108,7 +128,7 @@
   // flight in front of the operand loads of the workgroups still working (measured: the last tile done at 10-15 us instead of
   // 7.5); a leader's sweep is 37 lines.  Smaller nets: every workgroup sweeps (a few KB in all).
   {
-    const bool lead_mode = a.leaders && o.ntiles >= kLeaderMinTiles;
+    const bool lead_mode = o.ntiles >= kLeaderMinTiles;
     const bool sweeper = !lead_mode || bx < 8;
     const int xc = ((int)bx + (int)by * o.grid_x) & 7;
     gu64* res = mine + (o.slot_stride - 8);
@@ -118,8 +138,6 @@
       // a lane re-loads only the slots it has not seen yet
       unsigned long long w[kFusedMaxSlotsPerThread];
       int spins = 0;
-      for (int i = 0; i < a.poll_first_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-      for (int i = 0; i < 4096 && (long long)(wall_clock64() - t_start) < (long long)a.poll_gate; ++i) __builtin_amdgcn_s_sleep(2);
 #pragma unroll
       for (int u = 0; u < kFusedMaxSlotsPerThread; ++u) {
         const int i = (int)threadIdx.x + 256 * u;
@@ -131,7 +149,7 @@
         for (int u = 0; u < kFusedMaxSlotsPerThread; ++u) all = all && w[u] != kSlotEmpty;
         if (all) break;
         if (++spins >= kMeetSpinMax) { ok = false; break; }
-        for (int i = 0; i < a.poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
+        poll_pause();
 #pragma unroll
         for (int u = 0; u < kFusedMaxSlotsPerThread; ++u)
           if (w[u] == kSlotEmpty) w[u] = __hip_atomic_load(mine + (int)threadIdx.x + 256 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -156,7 +174,7 @@
       unsigned long long w = __hip_atomic_load(res + xc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int spins = 0; w == kSlotEmpty; ) {
         if (++spins >= kMeetSpinMax) { ok = false; w = 0x7ff8000000000000ull; break; }
-        for (int i = 0; i < a.poll_sleep; ++i) __builtin_amdgcn_s_sleep(1);
+        poll_pause();
         w = __hip_atomic_load(res + xc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       s = __longlong_as_double((long long)w);
@@ -168,17 +186,35 @@
       if (bid == 0 && a.metrics) met[on.metric_index] = post;
     }
   }
+  if (regular && mover) *reinterpret_cast<v4u*>(&img[wave][r4][c4]) = pre4;
   __syncthreads();
   OF_STAMP(3);
   const float gmul = c.grad_scale * s_coef;
   float p_new = 0.f, t_new = 0.f;
-  if (my_i >= 0) {
+  if (regular) {
+    const int r = 4 * lg + wave;
+    const AdamElem e = adam_elem(x, img[0][r][li], img[1][r][li], img[2][r][li], gmul, sc, a.beta2, a.w1, a.w2, a.eps);
+    if (pk) img[3][r][li] = polyak_elem(a.tau, e.p, a.one_m_tau, img[3][r][li]);
+    img[0][r][li] = e.p; img[1][r][li] = e.m; img[2][r][li] = e.v;   // (each lane overwrites what it alone read)
+    __syncthreads();
+    if (mover)
+      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const v4u*>(&img[wave][r4][c4]), wave_uniform_rsrc_n(my_arr + lay.pw + (long long)m0 * in + n0, 15LL * in + 16),
+                                             (r4 * in + c4) * 4, 0, kSc1);
+    // the [in][out] copies: 16 x 16 again, a lane's run is four consecutive outputs of input n0 + r4 — wave 3 the online copy, wave 2 the target's
+    const bool cp_t = wave == 2 && pk && ptr.wt_target;
+    if (lay.wt_dst >= 0 && (wave == 3 || cp_t)) {
+      const float (*src)[kImgLd] = cp_t ? img[3] : img[0];
+      const v4u run = {__float_as_uint(src[c4][r4]), __float_as_uint(src[c4 + 1][r4]), __float_as_uint(src[c4 + 2][r4]), __float_as_uint(src[c4 + 3][r4])};
+      __builtin_amdgcn_raw_buffer_store_b128(run, wave_uniform_rsrc_n((cp_t ? ptr.wt_target : ptr.wt) + lay.wt_dst + (long long)n0 * out + m0, 15LL * out + 16),
+                                             (r4 * out + c4) * 4, 0, kSc1);
+    }
+  } else if (my_i >= 0) {
     const AdamElem e = adam_elem(x, pre_p, pre_m, pre_v, gmul, sc, a.beta2, a.w1, a.w2, a.eps);
     gp[my_i] = e.p; gm[my_i] = e.m; gv[my_i] = e.v;
     p_new = e.p;
     if (pk) { t_new = polyak_elem(a.tau, e.p, a.one_m_tau, pre_t); gt[my_i] = t_new; }
   }
-  if (lay.wt_dst >= 0) {   // (uniform per workgroup) the [in][out] copy of a hidden layer's weight: 16 consecutive outputs per run
+  if (!regular && lay.wt_dst >= 0) {   // (uniform per workgroup) the [in][out] copy of a hidden layer's weight: 16 consecutive outputs per run
     tile_p[4 * lg + wave][li] = p_new;
     tile_t[4 * lg + wave][li] = t_new;
     __syncthreads();
