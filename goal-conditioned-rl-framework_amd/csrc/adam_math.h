@@ -3,6 +3,9 @@
 // clip norm and the riding metrics are the same bits whichever launch computed them.
 // Reference: torch.optim.Adam / AdamW single-tensor path (lerp, addcmul, addcdiv order), torch.nn.utils.clip_grad_norm_,
 // Polyak src/agent.py:1260-1271, metrics src/agent.py:1296-1300, :1334-1343.
+// The ORDER of operations is torch's; the bits are not where torch fuses a multiply-add (its CPU lerp_ / addcmul_ do): every
+// product here is rounded before it is added, so a moment word may differ from torch's in its last place
+// (tests/adam_ref.py states the bound, tests/test_gpu_optimiser_audit.py holds every launch form to it).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -111,10 +111,11 @@ __device__ inline float hash_normal(unsigned long long seed, unsigned long long 
 constexpr int kNormBlocks = 64;
 constexpr int kMaxTransposed = 8;
 constexpr int kMaxAdamSeg = 2 * kMaxTransposed + 2;
-// A net's parameter vector cut into block-sized work items: FLAT segments (256 consecutive elements per
-// block) and TILED [rows][cols] weight matrices (one 16x16 tile per block) whose updated values are also
-// written, through an LDS transpose, to an [cols][rows] copy (rowchain.h streams those): 64-byte runs
-// instead of 4-byte scattered stores (the scattered form cost 3.2 us of a 10.8 us launch).
+// A net's parameter vector cut into block-sized work items: FLAT segments (kAdamPerThread * 256 = 1 024 consecutive
+// elements per block) and TILED [rows][cols] weight matrices (one kAdamTile x kAdamTile = 32 x 32 tile per block, as four
+// 16 x 16 sub-tiles) whose updated values are also written, through an LDS transpose, to an [cols][rows] copy
+// (rowchain.h streams those): 64-byte runs instead of 4-byte scattered stores (the scattered form cost 3.2 us of a
+// 10.8 us launch).
 struct AdamSeg { long long beg, dst; int rows, cols; int blk0, nblk; int tiled, pad; };
 // a block of the segmented launch: kAdamPerThread elements per thread — 1 024 consecutive elements of a flat segment, or a
 // kAdamTile x kAdamTile tile of a hidden layer's weight as four 16 x 16 sub-tiles (the launchers count `nblk` accordingly)

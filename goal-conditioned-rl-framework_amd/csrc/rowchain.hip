@@ -852,6 +852,8 @@ void rowchain_pop_merge_terms(int rg, int ldl, int A, int H, int C, int B, int m
 }
 
 int launch_wt_rebuild(hipStream_t st, const RowNet& net, float* Wt) {
+  // a population step is being recorded (pop.h): no population form, issued member by member
+  if (PopRec* r = pop_recording()) return pop_defer(r, [net, Wt](hipStream_t s) { return launch_wt_rebuild(s, net, Wt); });
   hipLaunchKernelGGL(wt_rebuild_kernel, dim3(64, net.L), dim3(256), 0, st, net, Wt);
   GCRL_HIP(hipGetLastError());
   return GCRL_OK;

@@ -93,6 +93,15 @@ def test_full_shapes_bitwise(gcrl, S, A, H, P):
     _run_and_compare(pop, solo, [(1, gstep), (gstep + 1, gstep)])
 
 
+def test_calls_that_start_on_a_polyak_step_bitwise(gcrl):
+    """A call whose FIRST step is a Polyak step (step % 40 == 0) takes the per-step path, which rebuilds the target actor's
+    [in][out] copy in a launch of its own: that launch has to go through the population's recorder like the Polyak launch in
+    front of it (it did not: gcrl_pop_update_n refused such a call, `pop.update(40)` included)."""
+    pop, solo = _pair(gcrl, 10, 3, _cfgs(3, 64, 64), 8, [91, 92, 93])
+    _run_and_compare(pop, solo, [(38, 2), (40, 1), (41, 3), (80, 4)])
+    assert len(pop.update(120)) == 3
+
+
 def test_single_member_is_standalone(gcrl):
     pop, solo = _pair(gcrl, 10, 3, _cfgs(1, 64, 64), 8, [5])
     _run_and_compare(pop, solo, [(1, 8), (9, 8)])
