@@ -103,6 +103,8 @@ PROTOTYPES = {
     "gcrl_her_relabel_mode": (C.c_int, [_vp]),
     "gcrl_her_get_relabel_counter": (_u64, [_vp]),
     "gcrl_her_set_relabel_counter": (C.c_int, [_vp, _u64]),
+    "gcrl_her_set_nstep": (C.c_int, [_vp, C.c_int, _f64]),
+    "gcrl_her_get_nstep": (C.c_int, [_vp, C.POINTER(_f64)]),
     "gcrl_her_gather_update": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gcrl_her_read_tails": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "gcrl_her_destroy": (None, [_vp]),

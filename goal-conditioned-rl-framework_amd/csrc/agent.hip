@@ -1143,7 +1143,7 @@ int finish_deferred_draw(gcrl_agent* a, hipStream_t st) {
   }
   TRY(her_gather_update(her, src, (int64_t)(n - first) * B, a->sa + first * a->slot_x,
                         a->nsa + first * a->slot_x, a->rowchain ? nullptr : a->spa + first * a->slot_x, a->ldx,
-                        a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st));
+                        a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st, nullptr, nullptr, 0, nullptr, &a->cfg.gamma));   // (n-step returns: the head gather's gamma)
   if (!staged) GCRL_HIP(hipEventRecord(a->upload_ev[a->deferred.slot], st));   // the pinned block is free once the gather has read it
   return GCRL_OK;
 }
@@ -1238,6 +1238,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   g.h = her;
   if (!injected) g.gen = her->last_gen;   // (device-RNG mode: this member's draws, also when other members share the ring)
   g.n = rows_now;
+  g.gamma = a->cfg.gamma;                 // read at plan time: a set_hparams of gamma holds from the next call on (n-step returns, her_nstep.hip)
   if (!injected && !per_dev && her->relabel_mode == GCRL_RELABEL_SAMPLE) {   // the relabel stream's counter as of this member's turn (her_ring.h)
     g.ctr = her->relabel_ctr;
     her->relabel_ctr += (uint64_t)rows_now;
@@ -1259,12 +1260,12 @@ int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
   const GatherCall& g = cg->g;
   call_gather_form(a, cg, cg->head_form);
   if (cg->head_form) {
-    TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr));
+    TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr, &g.gamma));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
   } else {
     GCRL_HIP(hipMemcpyAsync(a->upload_dev, cg->ub, cg->bytes, hipMemcpyHostToDevice, st));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
-    if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, nullptr, nullptr, 0, &g.ctr));
+    if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, nullptr, nullptr, 0, &g.ctr, &g.gamma));
   }
   return GCRL_OK;
 }

@@ -105,6 +105,8 @@ struct gcrl_her {
   int S, A, G, SA4, S4, RW, RS, RG;   // o_ns = SA4, o_r = SA4+S4, o_d = o_r+1, o_ag = RW
   int relabel_mode = 0;               // GCRL_RELABEL_*
   uint64_t relabel_ctr = 0;           // sample mode: rows ever gathered from this ring (the relabel stream's counter)
+  int n_step = 1;                     // sample mode: rows folded into a gathered row's reward and done flag (her_nstep.hip); configuration, not state
+  double nstep_gamma = 0.0;           // the discount of the ring's own gathers (gcrl_her_sample, gcrl_her_gather_update); the update engine passes the agent's
   gcrl_mt* rng = nullptr;
   bool own_rng = false;
   hipStream_t stream = nullptr;
@@ -201,10 +203,11 @@ int her_upload_indices(gcrl_her* h, int B, int M, const uint32_t* idx_host, hipS
 // (pinned host) to cp_dst (device) — the call's control block travels with its first gather instead of as copies before it.
 int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa, float* nsa,
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src = nullptr,
-                      void* cp_dst = nullptr, size_t cp_bytes = 0, const uint64_t* relabel_ctr = nullptr);
+                      void* cp_dst = nullptr, size_t cp_bytes = 0, const uint64_t* relabel_ctr = nullptr, const double* gamma = nullptr);
 // A ring in sample-time relabelling mode takes her_gather_relabel_kernel instead (her_relabel.hip).  relabel_ctr == null: the
 // launch's first row is the ring's relabel_ctr, which advances by n; otherwise *relabel_ctr, and the ring's counter is left
-// alone (the planner of the call advanced it: GatherCall::ctr).
+// alone (the planner of the call advanced it: GatherCall::ctr).  With n_step > 1 such a ring takes her_gather_nstep_kernel
+// (her_nstep.hip), which discounts by float(*gamma) — the caller's, as its TD kernels cast it — or, gamma == null, by the ring's own.
 
 // sample-time relabelling mode (her_relabel.hip): the flush of `nep` staged episodes (T rows each, bookkeeping included), the
 // update engine's gather and the public sample's, each starting at relabel counter `ctr`; the indices are idx or, when null,
@@ -214,15 +217,22 @@ int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, in
                               float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
 int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                        float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
+// the same two gathers for a ring with n_step in 2..8 (her_nstep.hip), discounting by g32
+int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
+                            float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
+int her_nstep_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
+                     float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
 
 // One her_gather_update call stated before it is issued (the update engine's begin_call plans it, gcrl_pop_update_n issues the
 // members' calls together).  `gen` is the ring's IdxGen as of the member's turn: members that share a ring each keep their own.
-// `ctr` likewise is the ring's relabel counter as of the member's turn (sample-time relabelling mode).
+// `ctr` likewise is the ring's relabel counter as of the member's turn (sample-time relabelling mode), `gamma` the member's discount
+// as of plan time (n-step returns: members that share a ring each gather with their own).
 struct GatherCall {
   gcrl_her* h = nullptr;
   const uint32_t* idx = nullptr;
   IdxGen gen{};
   uint64_t ctr = 0;
+  double gamma = 0.0;
   int64_t n = 0;
   float *sa = nullptr, *nsa = nullptr, *spa = nullptr;
   int ldx = 0;

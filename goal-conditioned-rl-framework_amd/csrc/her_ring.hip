@@ -696,7 +696,7 @@ int her_upload_indices(gcrl_her* h, int B, int M, const uint32_t* idx_host, hipS
 
 int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa, float* nsa,
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes,
-                      const uint64_t* relabel_ctr) {
+                      const uint64_t* relabel_ctr, const double* gamma) {
   if (cp_bytes % 16 != 0 || (cp_bytes && (!cp_src || !cp_dst))) return fail(GCRL_ERR_ARG, "her_gather_update: bad side copy (%zu bytes)", cp_bytes);
   if (ldx != h->SA4) return fail(GCRL_ERR_ARG, "her_gather_update: batch row stride %d != roundup(S+A,4) = %d", ldx, h->SA4);
   if (int rc = prof_begin(h, st)) return rc;
@@ -704,7 +704,10 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
     uint64_t ctr = h->relabel_ctr;
     if (relabel_ctr) ctr = *relabel_ctr;
     else h->relabel_ctr += (uint64_t)n;
-    if (int rc = her_relabel_gather_update(h, idx_dev, ctr, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
+    if (h->n_step > 1) {
+      const float g32 = (float)(gamma ? *gamma : h->nstep_gamma);
+      if (int rc = her_nstep_gather_update(h, idx_dev, ctr, g32, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
+    } else if (int rc = her_relabel_gather_update(h, idx_dev, ctr, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
     return prof_end(h, st, n);
   }
   GatherUpdArgs ga{h->ring, idx_dev, h->last_gen, n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, ldx, sa, nsa, spa, r, d,
@@ -733,7 +736,7 @@ int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merg
     for (int i = 0; i < P; ++i) {
       const GatherCall& g = c[i];
       g.h->last_gen = g.gen;   // (members sharing a ring: each launch computes its own member's draws)
-      if (int rc = her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr)) return rc;
+      if (int rc = her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr, &g.gamma)) return rc;
     }
     return GCRL_OK;
   }
@@ -1140,7 +1143,10 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
     if (int rc = prof_begin(h, st)) return rc;
     const uint64_t ctr = h->relabel_ctr;
     h->relabel_ctr += (uint64_t)n;
-    if (int rc = gcrl::her_relabel_sample(h, h->idx_on_device ? h->idx_dev : nullptr, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    const uint32_t* idx = h->idx_on_device ? h->idx_dev : nullptr;
+    if (h->n_step > 1) {
+      if (int rc = gcrl::her_nstep_sample(h, idx, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    } else if (int rc = gcrl::her_relabel_sample(h, idx, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     return prof_end(h, st, n);
   }
   GatherArgs ga{h->ring, h->idx_on_device ? h->idx_dev : nullptr, h->last_gen, n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
@@ -1169,7 +1175,9 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
     if (int rc = prof_begin(h, st)) return rc;
     const uint64_t ctr = h->relabel_ctr;
     h->relabel_ctr += (uint64_t)n;
-    if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    if (h->n_step > 1) {
+      if (int rc = gcrl::her_nstep_sample(h, idx_dev, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    } else if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     return prof_end(h, st, n);
   }
   GatherArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,

@@ -22,7 +22,7 @@ import torch
 
 from .. import _ffi
 from .._ffi import lib
-from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten
+from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_nstep
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -187,13 +187,18 @@ class _EngineAgent:
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
-                 _member=None):
+                 n_step: int = 1, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
         if relabel == "sample" and config.buffer_type != "HER":
             raise _ffi.GcrlError(f"{type(self).__name__}: relabel: 'sample' needs buffer_type 'HER', got {config.buffer_type!r}")
         self.relabel = relabel
+        # n_step=N (2..8, relabel="sample"): the ring's gathers hand the engine n-step windows (buffer.HERBuffer); gamma is the config's.
+        if n_step != 1 and config.buffer_type != "HER":
+            raise _ffi.GcrlError(f"{type(self).__name__}: n_step: n_step={n_step!r} needs buffer_type 'HER' with relabel='sample', "
+                                 f"got {config.buffer_type!r}")
+        self.n_step = _check_nstep(type(self).__name__, n_step, config.gamma, relabel)[0]
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -227,7 +232,8 @@ class _EngineAgent:
             self.buffer = ReplayBuffer(config.max_len, rng=rng, seed=seed, device_index=device_index)
         elif config.buffer_type == "HER":
             self.buffer = HERBuffer(config.max_len, config.max_eps_len, nenvs, k_future=config.k_future,
-                                    rng=rng, seed=seed, device_index=device_index, relabel=relabel)
+                                    rng=rng, seed=seed, device_index=device_index, relabel=relabel,
+                                    n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 

@@ -135,6 +135,20 @@ def _classify_reward_probe(fn, goal_dim: int, default_threshold: float):
 
 
 RELABEL_MODES = {"push": 0, "sample": 1}    # include/gcrl.h GCRL_RELABEL_*
+NSTEP_MAX = 8                               # n_step of a relabel="sample" ring: 1..8 (gcrl_her_set_nstep)
+
+
+def _check_nstep(who: str, n_step, gamma, relabel: str):
+    """-> (n_step, gamma) as the ring takes them, or a GcrlError that names n_step"""
+    if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= int(n_step) <= NSTEP_MAX:
+        raise _ffi.GcrlError(f"{who}: n_step: must be an integer in 1..{NSTEP_MAX}, got {n_step!r}")
+    n_step = int(n_step)
+    if n_step > 1 and relabel != "sample":
+        raise _ffi.GcrlError(f"{who}: n_step: n_step={n_step} needs relabel='sample' (the window's rewards are recomputed by the relabelling "
+                             f"gather), got relabel={relabel!r}")
+    if n_step > 1 and gamma is None:
+        raise _ffi.GcrlError(f"{who}: n_step: n_step={n_step} needs a discount: pass gamma=")
+    return n_step, (None if gamma is None else float(gamma))
 
 
 class _RingState:
@@ -183,7 +197,7 @@ class _RingState:
 class HERBuffer(_RingState):
     def __init__(self, max_mem_len: int, max_eps_len: int, nenvs: int, threshold: float = 0.05,
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
-                 device_index: int = 0, relabel: str = "push"):
+                 device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None):
         # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
         # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
         # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
@@ -191,6 +205,12 @@ class HERBuffer(_RingState):
         if relabel not in RELABEL_MODES:
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
         self.relabel = relabel
+        # n_step = N in 2..8 (relabel="sample" only): a gathered row becomes a window of up to N rows of its episode — r the
+        # discounted sum of the window's rewards (recomputed against the new goal when the row is relabelled), ns the window's last
+        # next state, d folded so that r + gamma (1 - d) q' is the n-step target (tests/her_nstep_ref.py is the definition).  `gamma`
+        # discounts this buffer's own sample() / gather_update(); an agent's update calls discount by the agent's gamma.  The values
+        # are held here until the first push creates the ring.  Every refusal before any device work.
+        self.n_step, self.gamma = _check_nstep("HERBuffer", n_step, gamma, relabel)
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError("HERBuffer needs a HIP device: the replay ring lives in HBM and "
                                  "there is no CPU fallback")
@@ -262,6 +282,8 @@ class HERBuffer(_RingState):
                              rng_mode=1 if self.rng.mode == "device" else 0, seed=self.rng.seed_value)
         self._h = _ffi.check_ptr(lib.gcrl_her_create_relabel(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel]), "gcrl_her_create")
         self._dims = (S, A, G)
+        if self.n_step > 1:
+            _ffi.check(lib.gcrl_her_set_nstep(self._h, self.n_step, self.gamma))
         if kind == 2:
             self._install_reward_callback()
 

@@ -21,7 +21,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import lib
 from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
-from .buffer import HERBuffer, MTStream
+from .buffer import HERBuffer, MTStream, _check_nstep
 
 MAX_MEMBERS = 16
 MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
@@ -74,13 +74,19 @@ class _Population:
 
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
-                 relabel: str = "push"):
+                 relabel: str = "push", n_step: int = 1):
         # relabel="sample": every member's ring (or the shared one) relabels at gather time (buffer.HERBuffer); such gathers have no
         # population launch, so merge_gather = True then reports no merged launch (gather_counts()).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
         self.relabel = relabel
         configs = list(configs)
+        # n_step=N: every member's ring (or the shared one) gathers n-step windows; each member's update calls discount by its own gamma
+        if n_step != 1:
+            for i, c in enumerate(configs):
+                if getattr(c, "buffer_type", "HER") != "HER":
+                    self._refuse("n_step", f"member {i}: n_step={n_step!r} needs buffer_type 'HER' with relabel='sample', got {c.buffer_type!r}")
+        self.n_step = _check_nstep(type(self).__name__, n_step, configs[0].gamma if configs else 0.0, relabel)[0]
         P = len(configs)
         self.shared_ring = bool(shared_ring)
         # every refusal before any device work
@@ -111,7 +117,7 @@ class _Population:
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
             self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index, relabel=relabel,
-                                           _member=lambda cfg, i=i: (pop, pop.member(i))))
+                                           n_step=self.n_step, _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
         self._merge_gather = False
         if P >= self.MERGE_GATHER_FROM:
@@ -122,7 +128,8 @@ class _Population:
             c0 = configs[0]
             self.nenvs = int(nenvs)
             self.buffer = HERBuffer(c0.max_len, c0.max_eps_len, int(nenvs) * P, k_future=c0.k_future, rng=rng, seed=seeds[0],
-                                    device_index=device_index, relabel=relabel)
+                                    device_index=device_index, relabel=relabel, n_step=self.n_step,
+                                    gamma=c0.gamma if self.n_step > 1 else None)   # (the ring's own gathers; a member's calls use the member's gamma)
             for m in self.members:
                 m.buffer = self.buffer
         if rng == "python":

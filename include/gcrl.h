@@ -133,6 +133,17 @@ int gcrl_her_relabel_mode(const gcrl_her* h);
 /* rows ever gathered from a GCRL_RELABEL_SAMPLE ring: the counter of its relabel stream (saved and loaded with the ring's state) */
 uint64_t gcrl_her_get_relabel_counter(const gcrl_her* h);
 int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter);
+/* n-step returns on a GCRL_RELABEL_SAMPLE ring: n_step = N in 1..8 (1, the default: one-step rows, the kernels of before).  With
+ * N > 1 a gathered row p becomes a window of m = min(N, remaining + 1) rows of its episode: s, a of row p, ns of row p + m - 1,
+ * r <- sum_j gamma^j r_j (each r_j recomputed against the new goal when the row is relabelled, otherwise as stored) and
+ * d <- 1 - gamma^(m-1) (1 - d_last), so that the engine's r + gamma (1 - d) q' is the n-step target.  The relabel decision and the
+ * counter are consumed as for N = 1.  `gamma` is the discount of the ring's own gathers (gcrl_her_sample, gcrl_her_sample_dev,
+ * gcrl_her_gather_update), applied as a float; an agent's update calls discount by the agent's gamma as of the call.
+ * Configuration, not state: gcrl_her_save_state / gcrl_her_load_state do not carry it.  Refused, naming n_step: a value outside
+ * 1..8 (GCRL_ERR_ARG), N > 1 on a GCRL_RELABEL_PUSH ring (GCRL_ERR_STATE).  gcrl_her_get_nstep returns N (gamma through *gamma,
+ * which may be NULL), -1 for a null handle. */
+int gcrl_her_set_nstep(gcrl_her* h, int n_step, double gamma);
+int gcrl_her_get_nstep(const gcrl_her* h, double* gamma);
 void gcrl_her_destroy(gcrl_her* h);
 /* compute_reward for GCRL_REWARD_HOST rings: out[i] = compute_reward(achieved[i], goal[i], {}) for n pairs of goal_dim floats
  * (row-major), in the reference's call order (src/buffer.py:151-166: step-major, relabel-minor).  Returns 0, or non-zero to

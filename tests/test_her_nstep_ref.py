@@ -1,0 +1,243 @@
+"""Host tests (no GPU) of tests/her_nstep_ref.py, the numpy definition of n-step returns on a sample-mode HER ring
+(HERBuffer(relabel="sample", n_step=N, gamma=g); csrc/her_nstep.hip): N = 1 is the mode of before, the two folded outputs give the
+TD sites the n-step target exactly, a second restatement written the other way round agrees with the definition while each of
+eight plausible mistakes in it is caught on a named table — and the new kernels use no scratch memory."""
+import os
+import re
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import her_nstep_ref as NS
+import her_relabel_ref as R
+import test_her_relabel_ref as host
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F32 = np.float32
+
+
+def bits(x):
+    return np.ascontiguousarray(np.asarray(x, F32)).view(np.uint32)
+
+
+# ---------------------------------------------------------------- rings
+def make_ring(cap, episodes, dims=(6, 2, 2), seed=0, dense=False, d_end=1.0, step=0.03):
+    """A ring of `cap` slots after flushing episodes of the given lengths, by physical slot, FIFO-evicted as the device ring is:
+    global row g lies at slot g mod cap.  An episode's last row carries d = d_end, every other row 0.  Achieved goals walk with
+    `step`; stored rewards are -1.0 / -0.0 (sparse) or -uniform (dense).  -> (s, a, ns, r, d, ag, rem, head, cap, len)"""
+    S, A, G = dims
+    gen = np.random.default_rng(seed)
+    total = sum(episodes)
+    s = np.zeros((cap, S), F32); a = np.zeros((cap, A), F32); ns = np.zeros((cap, S), F32)
+    r = np.zeros(cap, F32); d = np.zeros(cap, F32); ag = np.zeros((cap, G), F32); rem = np.zeros(cap, F32)
+    g = 0
+    for T in episodes:
+        goal = gen.standard_normal(G).astype(F32)
+        pos = gen.standard_normal(G).astype(F32)
+        for i in range(T):
+            p = g % cap
+            pos = (pos + step * gen.standard_normal(G)).astype(F32)
+            s[p] = np.concatenate([gen.standard_normal(S - G).astype(F32), goal])
+            ns[p] = np.concatenate([gen.standard_normal(S - G).astype(F32), goal])
+            a[p] = gen.standard_normal(A).astype(F32)
+            r[p] = -F32(gen.random()) if dense else (F32(-1.0) if gen.random() < 0.7 else F32(-0.0))
+            d[p] = d_end if i == T - 1 else 0.0
+            ag[p] = pos
+            rem[p] = T - 1 - i
+            g += 1
+    length = min(cap, total)
+    head = total % cap if total > cap else 0
+    return s, a, ns, r, d, ag, rem, head, cap, length
+
+
+def test_n1_is_the_mode_of_before():
+    """N = 1: every output bit for bit her_relabel_ref.gather, on the hand-built ring of its host test and on a wrapped one"""
+    for kind in (R.SPARSE, R.DENSE):
+        for ctr in (0, 5):
+            want = R.gather(*host._ring(), host.HEAD, host.CAP, host.IDX, ctr, host.SEED, host.KF, kind, host.THR)
+            got = NS.gather(*host._ring(), host.HEAD, host.CAP, host.IDX, ctr, host.SEED, host.KF, kind, host.THR, 1, 0.98)
+            for key in ("s", "a", "r", "ns", "d", "f", "fut"):
+                assert np.array_equal(bits(got[key]) if key in "s a r ns d".split() else got[key],
+                                      bits(want[key]) if key in "s a r ns d".split() else want[key]), (kind, ctr, key)
+            assert (got["m"] == 1).all()
+    ring = make_ring(60, [50, 50], seed=3, dense=True)
+    idx = np.random.default_rng(4).integers(0, 60, 512)
+    for k in (0, 4):
+        want = R.gather(*ring[:7], ring[7], 60, idx, 11, 21, k, R.DENSE, 0.05)
+        got = NS.gather(*ring[:7], ring[7], 60, idx, 11, 21, k, R.DENSE, 0.05, 1, 0.98)
+        for key in ("s", "a", "r", "ns", "d"):
+            assert np.array_equal(bits(got[key]), bits(want[key])), (k, key)
+
+
+def test_offsets_do_not_depend_on_n_and_rem0_rows_are_todays():
+    ring = make_ring(60, [50, 50], seed=5)
+    idx = np.random.default_rng(6).integers(0, 60, 4096)
+    for k in (0, 4):
+        one = R.gather(*ring[:7], ring[7], 60, idx, 0, 9, k, R.SPARSE, 0.05)
+        cut = {}
+        for N in (2, 3, 8):
+            got = NS.gather(*ring[:7], ring[7], 60, idx, 0, 9, k, R.SPARSE, 0.05, N, 0.98)
+            assert np.array_equal(got["f"], one["f"]) and np.array_equal(got["fut"], one["fut"]), (k, N)
+            cut[N] = int((got["m"] < N).sum())
+            lone = np.flatnonzero(got["m"] == 1)
+            assert lone.size > 0
+            for key in ("s", "a", "r", "ns", "d"):
+                assert np.array_equal(bits(got[key][lone]), bits(one[key][lone])), (k, N, key)     # rem = 0: the row of before
+        assert 0 < cut[2] < cut[3] < cut[8], cut
+
+
+# ---------------------------------------------------------------- the folded target
+def test_folded_outputs_give_the_n_step_target_exactly():
+    """gamma = 0.5, rewards in {-1, -0} and small-integer q: every fp32 operation is exact, so what a TD site computes from the two
+    folded outputs, r' + g32 (1 - d') q, IS sum_j gamma^j r_j + gamma^m (1 - d_last) q — checked against rational arithmetic"""
+    ring = make_ring(60, [50, 50], seed=7)
+    s, a, ns, r, d, ag, rem, head, cap, length = ring
+    idx = np.random.default_rng(8).integers(0, length, 1024)
+    q = np.random.default_rng(9).integers(-8, 9, idx.size).astype(F32)
+    g32 = F32(0.5)
+    ended = 0
+    for N in range(1, 9):
+        for k in (0, 4):
+            got = NS.gather(*ring[:7], head, cap, idx, 0, 13, k, R.SPARSE, 0.05, N, 0.5)
+            for t in range(idx.size):
+                p, m, f = (head + int(idx[t])) % cap, int(got["m"][t]), int(got["f"][t])
+                if f:
+                    rs = [R.reward(ag[(p + j) % cap], ag[(p + f) % cap], R.SPARSE, 0.05) for j in range(m)]
+                    d_last = 0.0
+                else:
+                    rs = [r[(p + j) % cap] for j in range(m)]
+                    d_last = float(d[(p + m - 1) % cap])
+                    ended += d_last == 1.0
+                want = sum(Fraction(1, 2 ** j) * Fraction(float(x)) for j, x in enumerate(rs)) + Fraction(1, 2 ** m) * Fraction(1 - d_last) * Fraction(float(q[t]))
+                y = F32(got["r"][t] + F32(g32 * F32(F32(F32(1.0) - got["d"][t]) * q[t])))
+                assert Fraction(float(y)) == want, (N, k, t, y, want)
+    assert ended > 0                                             # windows that end on the d = 1 row: the bootstrap term vanishes
+
+
+# ---------------------------------------------------------------- a second restatement, and the mistakes it could hold
+MUTANTS = ["window_not_cut_at_episode_end", "stored_rewards_for_a_relabelled_row", "ns_from_p", "goal_not_patched_into_ns_of_last",
+           "d_left_as_d_last", "gamma_power_off_by_one", "horner_from_the_front", "m1_through_one_minus_one_minus_d"]
+# name -> (ring, k, kind, N, gamma): the table on which each mistake must be caught (others may catch it too)
+TABLES = {
+    "two_episodes_original_rows_n3": (dict(cap=60, episodes=[50, 50], seed=21), 0, R.SPARSE, 3, 0.98),
+    "two_episodes_relabelled_dense_n3": (dict(cap=60, episodes=[50, 50], seed=22, dense=True), 4, R.DENSE, 3, 0.98),
+    "wrapped_dense_n8": (dict(cap=130, episodes=[50, 50, 50], seed=23, dense=True), 1, R.DENSE, 8, 0.98),
+    "soft_done_original_rows_n2": (dict(cap=40, episodes=[7, 1, 9, 1], seed=24, d_end=0.1), 0, R.SPARSE, 2, 0.5),
+}
+CAUGHT_ON = {
+    "window_not_cut_at_episode_end": "two_episodes_original_rows_n3",
+    "stored_rewards_for_a_relabelled_row": "two_episodes_relabelled_dense_n3",
+    "ns_from_p": "two_episodes_original_rows_n3",
+    "goal_not_patched_into_ns_of_last": "two_episodes_relabelled_dense_n3",
+    "d_left_as_d_last": "two_episodes_original_rows_n3",
+    "gamma_power_off_by_one": "two_episodes_original_rows_n3",
+    "horner_from_the_front": "wrapped_dense_n8",
+    "m1_through_one_minus_one_minus_d": "soft_done_original_rows_n2",
+}
+THR, SEED, CTR = 0.05, 77, 3
+
+
+def _case(name):
+    spec, k, kind, N, gamma = TABLES[name]
+    ring = make_ring(**spec)
+    idx = np.random.default_rng(31).integers(0, ring[9], 777)
+    return ring, idx, k, kind, N, gamma
+
+
+def restate(name, mutant=None):
+    """The rule once more, written from the window outwards (collect the window's slots, then read everything off them)."""
+    (s, a, ns, r, d, ag, rem, head, cap, _), idx, k, kind, N, gamma = _case(name)
+    g = F32(gamma)
+    S, G = s.shape[1], ag.shape[1]
+    out = dict(s=[], a=[], r=[], ns=[], d=[])
+    for t, j in enumerate(idx):
+        p = (head + int(j)) % cap
+        left = int(min(max(float(rem[p]), 0.0), min(R.FLUSH_LEN, cap) - 1))
+        f = R.decide(SEED, k, CTR + t, left)
+        m = N if mutant == "window_not_cut_at_episode_end" else min(N, left + 1)
+        window = [(p + i) % cap for i in range(m)]
+        row_s, row_ns = s[p].copy(), ns[p if mutant == "ns_from_p" else window[-1]].copy()
+        if f:
+            goal = ag[(p + f) % cap]
+            row_s[S - G:] = goal
+            if mutant != "goal_not_patched_into_ns_of_last" or m == 1:
+                row_ns[S - G:] = goal
+            rs = [r[w] for w in window] if mutant == "stored_rewards_for_a_relabelled_row" else [R.reward(ag[w], goal, kind, THR) for w in window]
+            d_last = F32(0.0)
+        else:
+            rs, d_last = [r[w] for w in window], d[window[-1]]
+        if mutant == "horner_from_the_front":
+            acc, gp = F32(rs[0]), F32(1.0)
+            for x in rs[1:]:
+                gp = F32(gp * g)
+                acc = F32(acc + F32(gp * F32(x)))
+        else:
+            acc = F32(rs[-1])
+            for x in rs[-2::-1]:
+                acc = F32(F32(x) + F32(g * acc))
+        power = m if mutant == "gamma_power_off_by_one" else m - 1
+        if mutant == "d_left_as_d_last" or (m == 1 and mutant != "m1_through_one_minus_one_minus_d"):
+            dn = F32(d_last)
+        else:
+            gp = F32(1.0)
+            for _ in range(power):
+                gp = F32(gp * g)
+            dn = F32(F32(1.0) - F32(gp * F32(F32(1.0) - F32(d_last))))
+        for key, v in zip(("s", "a", "r", "ns", "d"), (row_s, a[p], acc, row_ns, dn)):
+            out[key].append(v)
+    return {key: np.asarray(v, F32) for key, v in out.items()}
+
+
+def differing(name, got):
+    """the outputs in which `got` is not bit for bit the definition's"""
+    ring, idx, k, kind, N, gamma = _case(name)
+    want = NS.gather(*ring[:7], ring[7], ring[8], idx, CTR, SEED, k, kind, THR, N, gamma)
+    return [key for key in ("s", "a", "r", "ns", "d") if not np.array_equal(bits(got[key]), bits(want[key]))], want
+
+
+def test_tables_are_what_they_claim():
+    for name in TABLES:
+        (s, a, ns, r, d, ag, rem, head, cap, length), idx, k, kind, N, gamma = _case(name)
+        _, want = differing(name, restate(name))
+        assert (want["m"] < N).any() and (want["m"] == N).any(), name          # windows cut by the episode end, and whole ones
+        assert ((want["f"] > 0).any()) == (k > 0), name
+        if k > 0:
+            assert ((want["f"] > 0) & (want["f"] < want["m"])).any(), name       # a goal reached inside the window
+        live = [(head + j) % cap for j in range(length)]
+        assert all(d[p] == 0 for p in live if rem[p] > 0), name                  # the invariant: only an episode's last row is done
+    (s, a, ns, r, d, ag, rem, head, cap, length), *_ = _case("soft_done_original_rows_n2")
+    x = F32(0.1)
+    assert F32(F32(1.0) - F32(F32(1.0) - x)) != x                                # why m == 1 must leave d alone
+    (_, _, _, _, _, _, rem, head, cap, length), *_ = _case("wrapped_dense_n8")
+    assert head != 0 and length == cap                                           # windows cross the physical end
+
+
+@pytest.mark.parametrize("name", TABLES)
+def test_checker_accepts_the_right_restatement(name):
+    bad, _ = differing(name, restate(name))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("mutant", MUTANTS)
+def test_checker_rejects_the_mutant(mutant):
+    name = CAUGHT_ON[mutant]
+    bad, _ = differing(name, restate(name, mutant))
+    print(f"{mutant} on {name}: rejected by {bad}")
+    assert bad, f"{mutant} passes on {name}"
+
+
+# ---------------------------------------------------------------- no scratch in the new kernels
+def test_new_kernels_use_no_scratch(tmp_path):
+    """her_nstep.hip compiled to gfx950 assembly with the Makefile's flags: .private_segment_fixed_size is 0 for each new kernel"""
+    csrc = os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", re.search(r"^ARCH\s*\?=\s*(\S+)", mk, re.M).group(1)).split()
+    hipcc = os.environ.get("HIPCC", re.search(r"^HIPCC\s*\?=\s*(\S+)", mk, re.M).group(1))
+    asm = tmp_path / "her_nstep.s"
+    subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, "her_nstep.hip"), "-o", str(asm)], check=True, cwd=csrc)
+    found = re.findall(r"\.name:\s+(\S*her_gather_nstep\S*)\n((?:(?!\.name:).)*?)\.private_segment_fixed_size:\s+(\d+)", asm.read_text(), re.S)
+    sizes = {n: int(sz) for n, _, sz in found}
+    assert len(sizes) == 3 and sum("pub_kernel" in n for n in sizes) == 1, sizes      # <false>, <true> and the public form
+    assert all(v == 0 for v in sizes.values()), sizes

@@ -3,11 +3,14 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/relabel_bench.py --run
     python tools/relabel_bench.py --parse DIR
 
---run fills two rings of 1e6 records at PickAndPlace dims (S 23, A 4, G 3; k_future 4, rng="device": no host draw, no index
-upload) — one per relabel mode — and then, alternating the modes, issues the update engine's gather (HERBuffer.gather_update) at
-9 216 and 77 824 rows, and the flush of one T = 50 episode (push_episode).  Nothing is timed here: the kernel trace is.
+--run fills rings of 1e6 records at PickAndPlace dims (S 23, A 4, G 3; k_future 4, rng="device": no host draw, no index
+upload) — one per relabel mode, and for the sample mode one more per n_step in NSTEPS (gamma 0.98; n_step = 1 is the sample-mode
+ring itself) — and then, alternating the rings, issues the update engine's gather (HERBuffer.gather_update) at 9 216 and 77 824
+rows, and the flush of one T = 50 episode (push_episode; the two modes only: n_step does not reach the flush).  Nothing is timed
+here: the kernel trace is.
 --parse reads the trace and prints, per kernel and launch size, the number of launches, the median and the range of the kernel
-durations — the launches after the warm-up ones.  No GPU: --run fails; it does not fall back."""
+durations — the launches after the warm-up ones.  The n-step rings launch one kernel at one grid size: their launches alternate in
+NSTEPS order and are told apart by that.  No GPU: --run fails; it does not fall back."""
 import argparse
 import csv
 import glob
@@ -22,6 +25,7 @@ S, A, G, K = 23, 4, 3, 4
 CAP = 1_000_000
 SIZES = ((256, 36), (256, 304))      # 9 216 and 77 824 rows: a trainer cycle's head-sized and main gather
 WARM, ITERS = 10, 60
+NSTEPS = (3, 8)
 
 
 def run():
@@ -41,11 +45,18 @@ def run():
             buf.push_episode(0, *ep)
         assert len(buf) == CAP
         rings[mode] = buf
+    for N in NSTEPS:
+        buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel="sample", n_step=N, gamma=0.98)
+        buf.compute_reward = her_oracle.sparse_reward
+        for _ in range(CAP // 50 + 2):
+            buf.push_episode(0, *ep)
+        assert len(buf) == CAP
+        rings[f"sample_n{N}"] = buf
     import torch
     torch.cuda.synchronize()
     for B, M in SIZES:
         for _ in range(WARM + ITERS):
-            for mode in ("push", "sample"):
+            for mode in rings:                              # push, sample (N = 1), then the n-step rings in NSTEPS order
                 rings[mode].gather_update(B, M)
     for _ in range(WARM + ITERS):
         for mode in ("push", "sample"):
@@ -54,7 +65,7 @@ def run():
     print("relabel_bench: done")
 
 
-NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_flush_kernel", "her_flush_sample_kernel")
+NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_gather_nstep_kernel", "her_flush_kernel", "her_flush_sample_kernel")
 
 
 def parse(d):
@@ -70,12 +81,18 @@ def parse(d):
                 continue
             grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r.get("Grid_Size_X", 0))
             rows.setdefault((key, grid), []).append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
+    for (key, grid), v in list(rows.items()):
+        if key == "her_gather_nstep_kernel":                 # launches alternate between the n-step rings
+            v.sort()
+            del rows[key, grid]
+            for i, N in enumerate(NSTEPS):
+                rows[f"{key} N={N}", grid] = v[i::len(NSTEPS)]
     for (key, grid), v in sorted(rows.items()):
         v.sort()
         if len(v) < ITERS:           # the fill's flushes have their own grid sizes only in push mode; keep the timed tail of each
             continue
         dur = [x[1] / 1e3 for x in v[-ITERS:]]
-        print(f"{key:28s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
+        print(f"{key:30s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
               f"range {min(dur):7.2f} .. {max(dur):7.2f} us")
 
 
