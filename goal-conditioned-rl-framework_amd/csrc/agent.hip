@@ -181,6 +181,7 @@ struct gcrl_agent {
   int n_cus = 0;              // compute units of the device (residency checks of the launches whose workgroups meet)
   bool rc_merge = false;      // ... forward and backward part in ONE launch each (part 3; GCRL_NO_RC_MERGE=1: two launches)
   bool rc_merge_k = false;    // TD3 (split_k): the critic phase's two launches as one, producers / consumers form (meet.h)
+  bool rc_global_mul = false;   // GCRL_RC_GLOBAL_MUL=1 (A/B switch): the fused DDPG launch keeps its act' multipliers in the global saves (rowchain.h)
   bool ddpg_ksplit = false, ddpg_ksplit_can = false;   // DDPG: the critic phase as two roles of the fused launch (rowchain.hip, k_split)
   // the dW | db GEMMs, the clip and the optimiser step of the row-chain DDPG step as ONE launch (dw_adam.hip; GCRL_NO_OPT_FUSE=1: the
   // two launches): per net [critic 0 | actor] two arrays of of_stride 64-bit norm slots and a launch count on its own line
@@ -1534,6 +1535,8 @@ int build(gcrl_agent* a) {
     if (c.kind == GCRL_AGENT_DDPG && c.pipeline_steps != 0) a->head_batches = 4;
     if (const char* e = std::getenv("GCRL_HEAD_BATCHES")) a->head_batches = std::max(1, std::min(8, std::atoi(e)));   // experiment knob
     a->main_idx_staged = std::getenv("GCRL_MAIN_IDX_STAGED") != nullptr;   // A/B knob (finish_deferred_draw)
+    a->rc_global_mul = std::getenv("GCRL_RC_GLOBAL_MUL") != nullptr;       // A/B knob (rowchain.h: rowchain_lds_mul_ok)
+    (void)rc_lds_mul_forms(a);   // (asks the device about both forms' residency now, not at the first launch)
     a->bn_fused_tiled = std::getenv("GCRL_NO_BN_TILED_STATS") == nullptr;
     a->layer_adv_off = std::getenv("GCRL_NO_LAYER_ADV") != nullptr;
     a->red_off = std::getenv("GCRL_NO_MB_REDUCE") != nullptr;
@@ -2241,6 +2244,11 @@ int gcrl_agent_get_meetings(gcrl_agent* a) {
     if (rc < 0) return rc;
   }
   return (a->bn_rsplit > 1 ? 1 : 0) | ((a->rc_merge || a->rc_merge_k || a->ddpg_ksplit) ? 2 : 0) | (a->opt_fuse ? 8 : 0);
+}
+
+int gcrl_agent_rowchain_form(gcrl_agent* a) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_rowchain_form: null handle");
+  return rc_lds_mul_forms(a);
 }
 
 int gcrl_agent_debug_meet_fault(gcrl_agent* a) {

@@ -56,6 +56,16 @@ int prof_drain(gcrl_agent* a) {
   return GCRL_OK;
 }
 
+// which of the agent's fused DDPG launches (rowchain_ddpg_kernel) take the LDS-multiplier form (rowchain.h): bit 0 a launch of critic-phase
+// workgroups only, bit 1 of actor-phase workgroups only, bit 2 the overlapped launch of both; 0: none, or no launch goes through that kernel
+int rc_lds_mul_forms(const gcrl_agent* a) {
+  if (!a->rowchain || a->sac || a->split_roles || a->rc_global_mul) return 0;
+  const long long nblk = (a->B + 4 * a->row_rg - 1) / (4 * a->row_rg), nk = (a->ddpg_ksplit ? 2 : 1) * nblk;
+  auto ok = [&](bool actor_phase, long long wgs) { return rowchain_lds_mul_ok(a->row_rg, a->row_ldl, a->A, a->H, a->C, a->L, actor_phase, wgs); };
+  const bool k_fused = !a->split_k;   // (TD3's split critic phase runs in the role-parallel kernels)
+  return ((k_fused && ok(false, nk)) ? 1 : 0) | (ok(true, nblk) ? 2 : 0) | ((k_fused && ok(true, nk + nblk)) ? 4 : 0);
+}
+
 // SAC on the role-parallel row-chain launches: the BatchNorm actor's heads and its sampling run inside them (rowchain.h HeadsFold)
 bool heads_fold_on(const gcrl_agent* a) {
   return a->rowchain && a->cfg.kind == GCRL_AGENT_SAC && a->split_roles && a->slab_on() && !a->heads_fold_off && a->A <= 16 && a->bn_sync.world <= 1;
@@ -86,7 +96,7 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
   rc.slot_x = a->slot_x; rc.slot_rd = a->slot_rd;
   rc.ldx = a->ldx; rc.ldl = a->row_ldl; rc.B = a->B; rc.S = a->S; rc.A = a->A; rc.Apad = a->Apad;
   const int nblk = (a->B + 4 * a->row_rg - 1) / (4 * a->row_rg);
-  rc.linear_roles = 1;   // (roles by XCD, K on XCDs 0-3 and P on 4-7: HBM-side traffic 32.3 -> 23.4 MB but the step 56.03 -> 56.53 us, round 4)
+  // (roles in launch order.  By XCD, K on XCDs 0-3 and P on 4-7: HBM-side traffic 32.3 -> 23.4 MB but the step 56.03 -> 56.53 us, round 4)
   rc.nblk_k = (what & 1) ? nblk : 0;
   rc.nblk_p = (what & 2) ? nblk : 0;
   rc.hC = a->hC; rc.gC = a->rc_gC; rc.q = a->q; rc.y = a->ybuf; rc.dq = a->dq;
@@ -138,21 +148,21 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
       rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev; rc.producers_first = 1;
       TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 3));
     } else if (what & 1) { TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 1)); TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 2)); }
-    if (what & 2) { rc.nblk_k = 0; TRY(launch_rowchain_ddpg(st, rc, a->row_rg)); }
+    if (what & 2) { rc.nblk_k = 0; TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul)); }
     return GCRL_OK;
   }
   if (a->ddpg_ksplit && (what & 1)) {   // the critic phase as two roles of the fused launch (rowchain.hip: k_split)
     rc.k_split = 1; rc.producers_first = 1;
     rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev;
   }
-  if (!a->prof || what != 3) return launch_rowchain_ddpg(st, rc, a->row_rg);
+  if (!a->prof || what != 3) return launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul);
   // measurement mode (never inside a graph capture): the overlapped launch, bracketed
   if (a->prof_used == gcrl_agent::kProfPairs) TRY(prof_drain(a));
   const unsigned long long init[2] = {~0ull, 0ull};
   rc.clk = a->prof_clk + 2 * a->prof_used;
   GCRL_HIP(hipMemcpyAsync(rc.clk, init, sizeof(init), hipMemcpyHostToDevice, st));
   GCRL_HIP(hipEventRecord(a->prof_a[a->prof_used], st));
-  TRY(launch_rowchain_ddpg(st, rc, a->row_rg));
+  TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul));
   GCRL_HIP(hipEventRecord(a->prof_b[a->prof_used], st));
   a->prof_used++;
   a->prof_launches++;

@@ -21,7 +21,7 @@ namespace gcrl {
 
 enum PopKind {
   POP_ALONE = 0,       // no population form: each member's own launch, in member order
-  POP_ROWCHAIN = 1,    // rowchain_ddpg_kernel<sub> (sub = rows per block / 4)
+  POP_ROWCHAIN = 1,    // rowchain_ddpg_kernel<sub & 15, sub & 16> (rows per block / 4; + 16: the LDS-multiplier form)
   POP_DW_ADAM = 2,     // dw_adam_kernel
   POP_BEGIN_STEP = 3,  // begin_step_kernel
   POP_GEMM_BATCH = 4,  // one form's launch of launch_gemm_batch (sub = the form, 1..5; only form 1, gemm_batch_kernel<1, 1, 4>, merges)
@@ -106,7 +106,7 @@ struct PopTabCache {
 };
 
 // population launches: `tab` is a device array of `members` argument structs
-int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int rg, dim3 grid, size_t lds);
+int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid, size_t lds);
 int launch_dw_adam_pop(hipStream_t st, const void* tab, int members, dim3 grid);
 int launch_begin_step_pop(hipStream_t st, const void* tab, int members);
 int launch_gemm_batch_pop(hipStream_t st, const void* tab, int members, int shape, dim3 grid);

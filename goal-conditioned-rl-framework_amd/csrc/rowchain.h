@@ -262,7 +262,7 @@ struct RowChainArgs {
   long long slot_x, slot_rd;
   int ldx, ldl, B, S, A, Apad;
   int nblk_k, nblk_p;
-  int linear_roles;           // 1 (default): roles in launch order (K's workgroups first); 0: by XCD (never asked for: agent_rowchain.inc)
+  int reserved0;              // (was linear_roles: the by-XCD role placement, measured and never asked for — the slot stays so that no later field moves)
   float *hC, *gC, *q, *y, *dq;      // K: activations / pre-activation gradients [C][L][B][H], q / dq [C][B], y [B]
   float *hA, *gA, *hC2, *q2, *dz;   // P: ..., critic activations (scratch) [C][L][B][H], Q(s, pi(s)) [C][B], d(pre-tanh) [C][B][Apad]
   float gamma, clamp_lo;
@@ -370,8 +370,16 @@ struct RowActPop {
 int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int n, int ldl, int A, int H);
 
 // rows per workgroup = 4*rg, rg in {1, 2, 4}
-int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg);
+// lds_mul: the LDS-multiplier form (below) where the launch's shape admits it; false: the global-multiplier form
+int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul);
 size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C);
+// LDS-multiplier form of the fused DDPG launch (rowchain.hip): every hidden layer's output of a net with a backward chain keeps LDS rows of
+// its own and the chain's act' multipliers are read from there, not from the global saves — L - 1 more [R][ldl] buffers for a launch of
+// critic-phase roles only, 2 (L - 1) once it carries actor-phase workgroups (actor and critic live at once).  rowchain_lds_mul_ok: the
+// form a launch of this shape takes — it fits the 160 KB, leaves as many of the launch's `wgs` workgroups resident at once as the global-multiplier form does.
+// (GCRL_RC_GLOBAL_MUL=1, read when an agent is created, is the A/B switch: the global-multiplier form everywhere.)
+size_t rowchain_lds_bytes_mul(int rg, int ldl, int A, int H, int C, int L, bool actor_phase);
+bool rowchain_lds_mul_ok(int rg, int ldl, int A, int H, int C, int L, bool actor_phase, long long wgs);
 
 // (re)build the [in][out] copies of one net's hidden-layer weights from its parameter block
 int launch_wt_rebuild(hipStream_t st, const RowNet& net, float* Wt);

@@ -15,6 +15,10 @@
 #include "pop.h"
 
 #include <algorithm>
+#include <array>
+#include <cstdlib>
+#include <map>
+#include <mutex>
 
 namespace gcrl {
 namespace {
@@ -96,6 +100,45 @@ __device__ inline float* grad_chain(const RowNet& net, float* G, float* X1, floa
   return in;
 }
 
+// LDS-multiplier form (rowchain.h rowchain_lds_bytes_mul) of the two walks above, for a net whose backward chain runs in the same workgroup:
+// layer l < L-1 leaves its output in rows of its own, keep + l * R * ldl, layer L-1 in `last`, and the chain multiplies by act' of the kept
+// rows instead of loading the global save back.  Same passes, same operands, same order: act_deriv sees the fp32 value the save holds.
+// Chained passes need no barrier for it: in both directions N = H, so a wave's (row, column) items of the epilogue are the same
+// (rows_linear: cb, q4) and it reads back as multiplier exactly what it wrote as output; the unchained form ends every pass with a barrier.
+// Rows >= rv hold finite values (biases walked through zero inputs) that nothing reads: rows_linear takes a multiplier for valid rows only.
+template <int RG>
+__device__ inline float* mlp_hidden_keep(const RowNet& net, const float* X0, float* keep, float* last, int ldl, float* part,
+                                         float* save, long long BH, long long row0, int rv) {
+  constexpr int R = 4 * RG;
+  const float* in = X0;
+  const bool chained = RG == 1 && net.H <= kRowChunk;
+  for (int l = 0; l < net.L; ++l) {
+    float* out = l == net.L - 1 ? last : keep + l * R * ldl;
+    rows_linear<RG>(in, ldl, l == 0 ? net.jpad0 : net.H, net.Wt + net.wt[l], net.H, net.H, net.P + net.b[l], EPI_LEAKY,
+                    part, out, ldl, save ? save + l * BH + row0 * net.H : nullptr, net.H, rv, nullptr, 0, MUL_NONE,
+                    chained, l & 1);
+    in = out;
+  }
+  if (chained) __syncthreads();
+  return last;
+}
+template <int RG>
+__device__ inline float* grad_chain_keep(const RowNet& net, float* G, float* X1, float* X2, int ldl, float* part,
+                                         const float* keep, float* gsave, long long BH, long long row0, int rv) {
+  constexpr int R = 4 * RG;
+  float* in = G;
+  const bool chained = RG == 1 && net.H <= kRowChunk;
+  for (int l = net.L - 1; l >= 1; --l) {
+    float* out = (in == X1) ? X2 : X1;
+    rows_linear<RG>(in, ldl, net.H, net.P + net.w[l], net.H, net.H, nullptr, EPI_NONE, part, out, ldl,
+                    gsave ? gsave + (l - 1) * BH + row0 * net.H : nullptr, net.H, rv,
+                    keep + (l - 1) * R * ldl, ldl, MUL_DLEAKY, chained, l & 1);
+    in = out;
+  }
+  if (chained) __syncthreads();
+  return in;
+}
+
 // stage `n` floats of global memory into LDS (all threads)
 // Prologue staging in two phases — every global load of the block's inputs is requested (into registers)
 // before the first LDS store waits for any of them: the phases used to alternate per region and the
@@ -146,10 +189,12 @@ __device__ inline void stage(float* dst, const float* src, int n) {
   }
 }
 
-template <int RG, bool HF = false>
+// LM: the LDS-multiplier form (mlp_hidden_keep; only the fused DDPG launch's two-role critic phase asks for it: phase 0, part 3)
+template <int RG, bool HF = false, bool LM = false>
 __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int phase, int part, int bid, const HeadsFold& hfr = HeadsFold{});
 
-template <int RG>
+// LM = false: the global-multiplier form (the chain's act' multipliers are loaded back from the global saves); true: from LDS
+template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {
   kernarg_warm<sizeof(RowChainArgs)>();
 #include "rowchain_ddpg_body.inc"
@@ -157,7 +202,7 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs
 
 // population form (agent.hip gcrl_pop_*): member blockIdx.y runs its own arguments tab[blockIdx.y] on the workgroups blockIdx.x of
 // its single-agent launch; every pointer of a member's arguments is that member's own
-template <int RG>
+template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_pop_kernel(const RowChainArgs* __restrict__ tab) {
   const RowChainArgs& a = tab[blockIdx.y];
 #include "rowchain_ddpg_body.inc"
@@ -259,7 +304,7 @@ __device__ __forceinline__ void heads_write_cur(const HeadsFold& f, const float*
 
 // HF: the instantiation of rowchain_split_heads_kernel (the record is a kernel argument: read in place, never through a pointer that could be null —
 // with `const HeadsFold*` and run-time null checks hipcc copied the 192-byte record to per-thread scratch once a third use site appeared)
-template <int RG, bool HF>
+template <int RG, bool HF, bool LM>
 __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int phase, int part, int bid, const HeadsFold& hfr) {
   const HeadsFold* const hf = &hfr;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -275,6 +320,7 @@ __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int p
   float* sm3 = sm2 + R * 16;
   float* hw = sm3 + R * 16;
   float* hb = hw + max(max(2 * A + 1, A + 2 * C), C * (A + 1)) * H;
+  [[maybe_unused]] float* KP = hb + 96;   // LM: the online critic's kept layers, [L - 1][R][ldl]
   const int nblk = (B + R - 1) / R;
   const int role = bid / nblk;
   const int blk = bid - role * nblk;
@@ -360,11 +406,13 @@ __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int p
     // ---- online critic `role - C` on [s | a]: forward, activations saved
     const int k = role - C;
     const float* sa_rows = a.sa + (long long)c.batch_slot * a.slot_x + row0 * a.ldx;
-    load_rows<RG>(XS, ldl, sa_rows, a.ldx, S + A, a.critic[0].jpad0, rv);
+    load_rows<RG>(LM ? X0 : XS, ldl, sa_rows, a.ldx, S + A, a.critic[0].jpad0, rv);   // (LM: XS takes the last layer's output)
     stage(hw, a.critic[k].P + a.critic[k].w[a.critic[k].L], H);
     if (tid == 0) hb[18] = a.critic[k].P[a.critic[k].b[a.critic[k].L]];
     __syncthreads();
-    float* h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
+    float* h;
+    if constexpr (LM) h = mlp_hidden_keep<RG>(a.critic[k], X0, KP, XS, ldl, part_ + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
+    else h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
     rows_head<RG>(h, ldl, H, hw, H, hb + 18, 1, EPI_NONE, sm);
     __syncthreads();
     if (tid < rv) a.q[(long long)k * B + row0 + tid] = sm[tid * 16];
@@ -382,10 +430,11 @@ __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int p
     const float* hs = a.hC + (long long)k * L * BH;
     const float* hsrc = hs + (L - 1) * BH + row0 * H;
     stage(hw, a.critic[k].P + a.critic[k].w[L], H);
-    for (int i = tid; i < R * H; i += kRowThreads) {
-      const int r = i / H, kk = i - r * H;
-      XS[r * ldl + kk] = r < rv ? hsrc[(long long)r * H + kk] : 0.f;
-    }
+    if constexpr (!LM)   // (LM: the forward part of this launch left the activation in XS)
+      for (int i = tid; i < R * H; i += kRowThreads) {
+        const int r = i / H, kk = i - r * H;
+        XS[r * ldl + kk] = r < rv ? hsrc[(long long)r * H + kk] : 0.f;
+      }
     if (tid < R) {
       const int r = tid;
       float g = 0.f;
@@ -410,7 +459,8 @@ __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int p
     float* gsave = a.gC + (long long)k * L * BH;
     head_backward<RG>(XS, ldl, H, hw, 1, sm2, gsave + (L - 1) * BH + row0 * H, rv);
     __syncthreads();
-    grad_chain<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, hs, gsave, BH, row0, rv);
+    if constexpr (LM) grad_chain_keep<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, KP, gsave, BH, row0, rv);
+    else grad_chain<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, hs, gsave, BH, row0, rv);
     return;
   }
   if (part != 2) {
@@ -653,6 +703,49 @@ size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C) {
   return (size_t)(4 * R * ldl + (rg == 1 ? 2 : 1) * 4 * R * kRowChunk + 4 * R * 16 + std::max(std::max(2 * A + 1, A + 2 * C), C * (A + 1)) * H + 96) * sizeof(float);   // (the trailing floats: head biases — hb[0 .. 64))
 }
 
+size_t rowchain_lds_bytes_mul(int rg, int ldl, int A, int H, int C, int L, bool actor_phase) {
+  return rowchain_lds_bytes(rg, ldl, A, H, C) + (size_t)(actor_phase ? 2 : 1) * std::max(L - 1, 0) * 4 * rg * ldl * sizeof(float);
+}
+
+namespace {
+// workgroups of `kernel` a CU holds at this much dynamic LDS (meet_capacity's count, abi_misc.hip: the occupancy query, then LDS in 1 KB
+// granules with one held back); 0 when the query fails
+int rc_resident_per_cu(const void* kernel, size_t lds) {
+  int per_cu = 0;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRowThreads, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, kernel) == hipSuccess) {
+    const size_t g = ((fa.sharedSizeBytes + lds + 1023) / 1024) * 1024;
+    if (g > 0) per_cu = (int)std::min<long long>(per_cu, (long long)((160 * 1024 - 1024) / g));
+  }
+  return std::max(per_cu, 0);
+}
+}  // namespace
+
+bool rowchain_lds_mul_ok(int rg, int ldl, int A, int H, int C, int L, bool actor_phase, long long wgs) {
+  if (L < 2 || wgs < 1 || !(rg == 1 || rg == 2 || rg == 4)) return false;
+  const size_t lds_old = rowchain_lds_bytes(rg, ldl, A, H, C), lds_new = rowchain_lds_bytes_mul(rg, ldl, A, H, C, L, actor_phase);
+  if (lds_new > 160 * 1024) return false;
+  // (the device is asked once per shape — agent creation does it, gcrl_agent_rowchain_form's rule —: the occupancy queries are host work a
+  // launch should not repeat, least of all inside a stream capture)
+  static std::mutex mu;
+  static std::map<std::array<long long, 3>, std::array<long long, 2>> known;   // -> workgroups the device holds at once: old form, new form
+  const std::array<long long, 3> key = {(long long)rg, (long long)lds_old, (long long)lds_new};
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find(key);
+  // never fewer of the launch's workgroups resident at once than it has today (a launch smaller than the chip has all of them either way)
+  auto rule = [&](const std::array<long long, 2>& cap) { return std::min(wgs, cap[1]) >= 1 && std::min(wgs, cap[1]) >= std::min(wgs, cap[0]); };
+  if (it != known.end()) return rule(it->second);
+  const void* k_old = rg == 1 ? (const void*)rowchain_ddpg_kernel<1, false> : (rg == 2 ? (const void*)rowchain_ddpg_kernel<2, false> : (const void*)rowchain_ddpg_kernel<4, false>);
+  const void* k_new = rg == 1 ? (const void*)rowchain_ddpg_kernel<1, true> : (rg == 2 ? (const void*)rowchain_ddpg_kernel<2, true> : (const void*)rowchain_ddpg_kernel<4, true>);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
+  const std::array<long long, 2> cap = {(long long)cus * rc_resident_per_cu(k_old, lds_old), (long long)cus * rc_resident_per_cu(k_new, lds_new)};
+  known.emplace(key, cap);
+  return rule(cap);
+}
+
 // the merged (part 3) launches wait inside the kernel: all 2C x nblk workgroups of the larger one must be resident at once
 bool rowchain_merge_ok(int rg, int ldl, int A, int H, int C, int B) {
   const size_t lds = rowchain_lds_bytes(rg, ldl, A, H, C);
@@ -667,19 +760,22 @@ bool rowchain_merge_ok(int rg, int ldl, int A, int H, int C, int B) {
   return 2LL * C * nblk <= meet_capacity(k, kRowThreads, lds) && 2LL * C * nblk <= meet_capacity(kh, kRowThreads, lds);
 }
 
-int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg) {
+int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul) {
   GCRL_CHECK_ARG(rg == 1 || rg == 2 || rg == 4, "rowchain: rows per block must be 4, 8 or 16");
   GCRL_CHECK_ARG(a.critic[0].H % 4 == 0 && a.ldl % 4 == 0 && a.A <= 16 && a.C >= 1 && a.C <= 2,
                  "rowchain: unsupported shape (H=%d, A=%d, C=%d)", a.critic[0].H, a.A, a.C);
-  const size_t lds = rowchain_lds_bytes(rg, a.ldl, a.A, a.critic[0].H, a.C);
+  // the form: multipliers from LDS where that fits and costs no resident workgroup (rowchain.h); the SAC form keeps the global saves
+  const int L = std::max(a.actor.L, a.critic[0].L);
+  const int grid = (a.k_split ? 2 : 1) * a.nblk_k + a.nblk_p;
+  const bool lm = lds_mul && !a.p_critic_only && a.actor.L == a.critic[0].L && rowchain_lds_mul_ok(rg, a.ldl, a.A, a.critic[0].H, a.C, L, a.nblk_p > 0, grid);
+  const size_t lds = lm ? rowchain_lds_bytes_mul(rg, a.ldl, a.A, a.critic[0].H, a.C, L, a.nblk_p > 0) : rowchain_lds_bytes(rg, a.ldl, a.A, a.critic[0].H, a.C);
   GCRL_CHECK_ARG(lds <= 160 * 1024, "rowchain: %zu bytes of LDS needed", lds);
   GCRL_CHECK_ARG(!a.k_split || (a.bar && a.qt && a.producers_first && a.C == 1), "rowchain: the two-role critic phase needs its meeting counters");
-  const int grid = (a.k_split ? 2 : 1) * a.nblk_k + a.nblk_p;
   if (grid < 1) return GCRL_OK;
   if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
-    return pop_record(r, POP_ROWCHAIN, rg, dim3(grid), lds, &a, sizeof(a), [ac = a, rg](hipStream_t s) { return launch_rowchain_ddpg(s, ac, rg); });
+    return pop_record(r, POP_ROWCHAIN, rg | (lm ? 16 : 0), dim3(grid), lds, &a, sizeof(a), [ac = a, rg, lds_mul](hipStream_t s) { return launch_rowchain_ddpg(s, ac, rg, lds_mul); });
   auto go = [&](auto kern) -> int {
-    static thread_local size_t raised = 0;
+    static thread_local size_t raised = 0;   // (per kernel: a generic lambda's statics belong to its instantiation)
     if (lds > 64 * 1024 && lds > raised) {
       GCRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       raised = lds;
@@ -688,9 +784,14 @@ int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg) {
     GCRL_HIP(hipGetLastError());
     return GCRL_OK;
   };
-  if (rg == 1) return go(rowchain_ddpg_kernel<1>);
-  if (rg == 2) return go(rowchain_ddpg_kernel<2>);
-  return go(rowchain_ddpg_kernel<4>);
+  if (lm) {
+    if (rg == 1) return go(rowchain_ddpg_kernel<1, true>);
+    if (rg == 2) return go(rowchain_ddpg_kernel<2, true>);
+    return go(rowchain_ddpg_kernel<4, true>);
+  }
+  if (rg == 1) return go(rowchain_ddpg_kernel<1, false>);
+  if (rg == 2) return go(rowchain_ddpg_kernel<2, false>);
+  return go(rowchain_ddpg_kernel<4, false>);
 }
 
 int launch_rowchain_split(hipStream_t st, const RowChainArgs& a, int rg, int phase, int part, const HeadsFold* hf) {
@@ -797,18 +898,28 @@ int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int
   return GCRL_OK;
 }
 
-int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int rg, dim3 grid, size_t lds) {
+// sub: rows per block / 4, + 16 for the LDS-multiplier form (the members' own launches chose it: launch_rowchain_ddpg, same shape, same LDS)
+int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid, size_t lds) {
+  const int rg = sub & 15;
+  const bool lm = (sub & 16) != 0;
   GCRL_CHECK_ARG(rg == 1 || rg == 2 || rg == 4, "rowchain population: rows per block must be 4, 8 or 16");
   GCRL_CHECK_ARG(members >= 1 && members <= 65535 && grid.y == 1 && grid.z == 1 && lds <= 160 * 1024, "rowchain population: bad launch");
-  const void* kern = rg == 1 ? (const void*)rowchain_ddpg_pop_kernel<1> : (rg == 2 ? (const void*)rowchain_ddpg_pop_kernel<2> : (const void*)rowchain_ddpg_pop_kernel<4>);
-  if (lds > 64 * 1024) GCRL_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const RowChainArgs* t = static_cast<const RowChainArgs*>(tab);
   const dim3 g(grid.x, (unsigned)members);
-  if (rg == 1) hipLaunchKernelGGL(rowchain_ddpg_pop_kernel<1>, g, dim3(kRowThreads), lds, st, t);
-  else if (rg == 2) hipLaunchKernelGGL(rowchain_ddpg_pop_kernel<2>, g, dim3(kRowThreads), lds, st, t);
-  else hipLaunchKernelGGL(rowchain_ddpg_pop_kernel<4>, g, dim3(kRowThreads), lds, st, t);
-  GCRL_HIP(hipGetLastError());
-  return GCRL_OK;
+  auto go = [&](auto kern) -> int {
+    if (lds > 64 * 1024) GCRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, g, dim3(kRowThreads), lds, st, t);
+    GCRL_HIP(hipGetLastError());
+    return GCRL_OK;
+  };
+  if (lm) {
+    if (rg == 1) return go(rowchain_ddpg_pop_kernel<1, true>);
+    if (rg == 2) return go(rowchain_ddpg_pop_kernel<2, true>);
+    return go(rowchain_ddpg_pop_kernel<4, true>);
+  }
+  if (rg == 1) return go(rowchain_ddpg_pop_kernel<1, false>);
+  if (rg == 2) return go(rowchain_ddpg_pop_kernel<2, false>);
+  return go(rowchain_ddpg_pop_kernel<4, false>);
 }
 
 int launch_rowchain_split_pop(hipStream_t st, const void* tab, int members, int sub, bool heads, dim3 grid, size_t lds) {

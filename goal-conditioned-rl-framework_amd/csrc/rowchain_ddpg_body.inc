@@ -1,6 +1,9 @@
 // rowchain_ddpg_body.inc — body of the fused DDPG row-chain launch, included by rowchain.hip into rowchain_ddpg_kernel (the
 // single-agent launch) and rowchain_ddpg_pop_kernel (the population launch).  In scope: template <int RG>, `a` (the launch's
-// RowChainArgs) and blockIdx.x (the workgroup's index in the member's launch).
+// RowChainArgs) and blockIdx.x (the workgroup's index in the member's launch); template <bool LM>: the LDS-multiplier form (rowchain.h
+// rowchain_lds_bytes_mul) — the hidden activations of every net with a backward chain keep LDS rows of their own behind the head biases,
+// KP = [L - 1][R][ldl] per net, and the chains read their multipliers there.  hA / gA / hC / gC still leave for the dW launch; hC2, which
+// only this launch read, is neither written nor read.  The SAC form (p_critic_only) is never launched with LM (launch_rowchain_ddpg).
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // k_split (round 4, DDPG): the critic phase K as TWO roles in this launch — its target chain (target actor -> target critic -> Q')
   // and its online critic's forward are independent, so K's critical path shrinks from 11 layer passes to 6 + 2 (the split kernel's
@@ -9,7 +12,7 @@
   if (a.k_split && a.nblk_k) {
     if ((int)blockIdx.x < 2 * a.nblk_k) {
       if (a.clk && threadIdx.x == 0 && blockIdx.x == 0) atomicMin(&a.clk[0], (unsigned long long)wall_clock64());
-      rowchain_split_body<RG>(a, 0, 3, (int)blockIdx.x);
+      rowchain_split_body<RG, false, LM>(a, 0, 3, (int)blockIdx.x);
       if (a.clk && threadIdx.x == 0) atomicMax(&a.clk[1], (unsigned long long)wall_clock64());
       return;
     }
@@ -27,17 +30,11 @@
   float* sm3 = sm2 + R * 16;              // [R][16] reward / done
   float* hw = sm3 + R * 16;               // head weights of the role: [A*H | H | max(A*H, H)], then head biases [16 | 16]
   float* hb = hw + max(max(2 * A + 1, A + 2 * a.C), a.C * (A + 1)) * H;
-  // Which role, which row block.  Workgroup w runs on XCD w % 8 and every XCD has its own L2: with the roles in launch order every
-  // XCD streamed BOTH roles' weights (PMC: 32 MB HBM-side per launch for 3.3 MB of distinct weights).  When both roles have the
-  // same number of row blocks (a multiple of 4) the critic phase K takes XCDs 0-3 and the actor phase P XCDs 4-7: an XCD fetches
-  // one role's networks only.  (A wrong guess about the placement costs speed, never correctness.)
-  bool role_k = (int)blockIdx.x < kblocks;
-  int blk = role_k ? (int)blockIdx.x : (int)blockIdx.x - kblocks;
-  if (a.nblk_k == a.nblk_p && (a.nblk_k & 3) == 0 && !a.linear_roles && !a.k_split) {
-    const int xcd = (int)blockIdx.x & 7;
-    role_k = xcd < 4;
-    blk = ((int)blockIdx.x >> 3) * 4 + (xcd & 3);
-  }
+  [[maybe_unused]] float* KP = hb + 96;                                // LM: kept layers of the role's first chained net (K: critic k, P: actor)
+  [[maybe_unused]] float* KPC = KP + max(a.actor.L - 1, 0) * R * ldl;  // LM, P: the critic's, behind the actor's
+  // Which role, which row block: the roles in launch order, K's workgroups first
+  const bool role_k = (int)blockIdx.x < kblocks;
+  const int blk = role_k ? (int)blockIdx.x : (int)blockIdx.x - kblocks;
   const long long row0 = (long long)blk * R;
   const int rv = min(R, B - (int)row0);
   const long long BH = (long long)B * H;
@@ -132,7 +129,8 @@
     }
     // online critic(s) on [s | a]: forward (activations saved), loss gradient, input-gradient chain
     for (int k = 0; k < C; ++k) {
-      h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
+      if constexpr (LM) h = mlp_hidden_keep<RG>(a.critic[k], XS, KP, X1, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
+      else h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);
       rows_head<RG>(h, ldl, H, hw_c + k * H, H, hb + 18 + k, 1, EPI_NONE, sm);
       __syncthreads();
       if (tid < R) {
@@ -150,7 +148,8 @@
       float* gsave = a.gC + (long long)k * a.critic[k].L * BH;
       head_backward<RG>(h, ldl, H, hw_c + k * H, 1, sm2, gsave + (a.critic[k].L - 1) * BH + row0 * H, rv);
       __syncthreads();
-      grad_chain<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, gsave, BH, row0, rv);
+      if constexpr (LM) grad_chain_keep<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, KP, gsave, BH, row0, rv);
+      else grad_chain<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, gsave, BH, row0, rv);
     }
   } else if (a.p_critic_only) {
     const StepCtrl c = *a.cur_p;
@@ -238,13 +237,16 @@
     if (fuse_q && tid < R) sm2[tid * 16] = (tid < rv) ? -1.0f / (float)B : 0.f;   // d(-mean Q)/dq, constant
     __syncthreads();
     // the last actor activation lands in XS and stays there: the critic chain reuses X1 / X2
-    float* h = mlp_hidden<RG>(a.actor, X0, X1, X2, ldl, part + R * 16, a.hA, BH, row0, rv, XS);
+    float* h;
+    if constexpr (LM) h = mlp_hidden_keep<RG>(a.actor, X0, KP, XS, ldl, part + R * 16, a.hA, BH, row0, rv);
+    else h = mlp_hidden<RG>(a.actor, X0, X1, X2, ldl, part + R * 16, a.hA, BH, row0, rv, XS);
     rows_head<RG>(h, ldl, H, hw_a, H, hb, A, EPI_TANH, sm);
     __syncthreads();
     if (tid < R * A) { const int r = tid / A, o = tid - r * A; X0[r * ldl + S + o] = sm[r * 16 + o]; }
     __syncthreads();
     // critic on [s | pi(s)]
-    h = mlp_hidden<RG>(a.critic[0], X0, X1, X2, ldl, part + R * 16, a.hC2, BH, row0, rv);
+    if constexpr (LM) h = mlp_hidden_keep<RG>(a.critic[0], X0, KPC, X1, ldl, part + R * 16, nullptr, BH, row0, rv);
+    else h = mlp_hidden<RG>(a.critic[0], X0, X1, X2, ldl, part + R * 16, a.hC2, BH, row0, rv);
     if (fuse_q) {
       head_backward<RG>(h, ldl, H, hw_c, 1, sm2, nullptr, rv, sm3, hb[16]);
       __syncthreads();
@@ -260,7 +262,9 @@
       head_backward<RG>(h, ldl, H, hw_c, 1, sm2, nullptr, rv);
       __syncthreads();
     }
-    float* g0 = grad_chain<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv);
+    float* g0;
+    if constexpr (LM) g0 = grad_chain_keep<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, KPC, nullptr, BH, row0, rv);
+    else g0 = grad_chain<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv);
     // da[r][j] = g0[r][:] . W0[:, S+j]  (row S+j of the [in][out] copy), then through the tanh
     rows_head<RG>(g0, ldl, H, hw_da, H, nullptr, A, EPI_NONE, sm2);
     __syncthreads();
@@ -274,6 +278,7 @@
     __syncthreads();
     head_backward<RG>(XS, ldl, H, hw_a, A, sm2, a.gA + (a.actor.L - 1) * BH + row0 * H, rv);
     __syncthreads();
-    grad_chain<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv);
+    if constexpr (LM) grad_chain_keep<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, KP, a.gA, BH, row0, rv);
+    else grad_chain<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv);
   }
   if (a.clk && tid == 0) atomicMax(&a.clk[1], (unsigned long long)wall_clock64());

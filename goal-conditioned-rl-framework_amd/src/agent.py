@@ -323,6 +323,12 @@ class _EngineAgent:
         roles, 4 reserved (always 0), 8 the fused dW + optimiser launch of the row-chain DDPG step); changes nothing."""
         return _ffi.check(lib.gcrl_agent_get_meetings(self._h))
 
+    def rowchain_form(self) -> int:
+        """Bit mask of the fused DDPG row-chain launches of this handle that read the backward chains' multipliers from LDS
+        (csrc/rowchain.h): 1 critic-phase launches, 2 actor-phase launches, 4 the overlapped launch; 0: the global-multiplier form
+        everywhere (GCRL_RC_GLOBAL_MUL=1, a shape the LDS rule refuses, or an agent without that launch).  Changes nothing."""
+        return _ffi.check(lib.gcrl_agent_rowchain_form(self._h))
+
     # ------------------------------------------------------------------ update
     def _metrics(self, ticket: int, n: int):
         vals = self._metric_cache.get(ticket)

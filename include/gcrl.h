@@ -642,6 +642,12 @@ int gcrl_set_shared_device(int shared);
 int gcrl_agent_set_meetings(gcrl_agent* a, int on);
 int gcrl_agent_get_meetings(gcrl_agent* a);
 int gcrl_agent_debug_meet_fault(gcrl_agent* a);
+/* Which of the handle's fused DDPG row-chain launches read the backward chains' act' multipliers from LDS instead of the global
+ * saves (csrc/rowchain.h rowchain_lds_mul_ok: the form fits the LDS and costs no resident workgroup; GCRL_RC_GLOBAL_MUL=1 at
+ * creation: none).  Bits: 1 a launch of critic-phase workgroups only, 2 of actor-phase workgroups only, 4 the overlapped launch of
+ * both; 0 also when no launch of the handle goes through that kernel (SAC, TQC).  Same results either way; changes nothing.
+ * New design (the reference is eager PyTorch: no such forms). */
+int gcrl_agent_rowchain_form(gcrl_agent* a);
 /* device pointer of a named vector (parameters / grads), for zero-copy interop */
 int gcrl_agent_dev_ptr(gcrl_agent* a, const char* name, float** ptr_dev_out, int64_t* numel_out);
 

@@ -1,6 +1,8 @@
 """Section timeline of rowchain_ddpg_kernel (development tool): needs a library built with -DGCRL_RC_STAMPS
 (GCRL_HIP_LIB=<that .so>); prints the device-clock stamps (10 ns ticks) the first K-role and the first P-role workgroup
-left at their section boundaries during the LAST launch of a run of headline steps."""
+left at their section boundaries during the LAST launch of a run of headline steps.  The K role's stamps are those of the one-role
+critic phase (GCRL_NO_DDPG_KSPLIT=1): the two roles of the default form run rowchain_split_body, which carries no stamps.
+GCRL_RC_GLOBAL_MUL=1 stamps the global-multiplier form of the kernel, the default its LDS-multiplier form."""
 import argparse
 import ctypes as C
 import os

@@ -11,6 +11,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "csrc")
 src = open(os.path.join(CSRC, "rowchain.hip")).read()
+# the kernel's body lives in rowchain_ddpg_body.inc (shared with the population kernel): inlined into the single-agent kernel, which is
+# the first to include it, so that the stamps below land in that kernel only
+INC = '#include "rowchain_ddpg_body.inc"\n'
+assert src.count(INC) == 2, "rowchain.hip no longer includes the DDPG body twice: follow it here"
+src = src.replace(INC, open(os.path.join(CSRC, "rowchain_ddpg_body.inc")).read(), 1)
 
 
 def after(anchor, stamp, nth=0):
@@ -22,19 +27,21 @@ def after(anchor, stamp, nth=0):
     src = src[:end] + f"\n    RC_STAMP({stamp});" + src[end:]
 
 
-src = src.replace("template <int RG>\n__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {",
+HEAD = "template <int RG, bool LM>\n__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {"
+assert src.count(HEAD) == 1, "rowchain_ddpg_kernel's head moved: follow it here"
+src = src.replace(HEAD,
                   "__device__ unsigned long long g_rc_stamps[2][32];\n"
-                  "#define RC_STAMP(i) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == a.nblk_k)) g_rc_stamps[blockIdx.x == 0 ? 0 : 1][i] = wall_clock64(); } while (0)\n"
-                  "template <int RG>\n__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {", 1)
+                  "#define RC_STAMP(i) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == (a.k_split ? 2 : 1) * a.nblk_k)) g_rc_stamps[blockIdx.x == 0 ? 0 : 1][i] = wall_clock64(); } while (0)\n"
+                  + HEAD, 1)
 # P role (the plain DDPG branch)
 marks_p = [
     ("    const float* src_da = a.critic[0].Wt + a.critic[0].wt[0] + (long long)S * H;   // rows S..S+A-1 of W0^T", 0, "start"),
-    ("    float* h = mlp_hidden<RG>(a.actor, X0, X1, X2, ldl, part + R * 16, a.hA, BH, row0, rv, XS);", 2, "actor hidden"),
+    ("    else h = mlp_hidden<RG>(a.actor, X0, X1, X2, ldl, part + R * 16, a.hA, BH, row0, rv, XS);", 2, "actor hidden"),
     ("    if (tid < R * A) { const int r = tid / A, o = tid - r * A; X0[r * ldl + S + o] = sm[r * 16 + o]; }\n    __syncthreads();", 3, "actor head + act"),
-    ("    h = mlp_hidden<RG>(a.critic[0], X0, X1, X2, ldl, part + R * 16, a.hC2, BH, row0, rv);", 4, "critic hidden"),
-    ("    float* g0 = grad_chain<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv);", 7, "critic dX chain"),
+    ("    else h = mlp_hidden<RG>(a.critic[0], X0, X1, X2, ldl, part + R * 16, a.hC2, BH, row0, rv);", 4, "critic hidden"),
+    ("    else g0 = grad_chain<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv);", 7, "critic dX chain"),
     ("    head_backward<RG>(XS, ldl, H, hw_a, A, sm2, a.gA + (a.actor.L - 1) * BH + row0 * H, rv);\n    __syncthreads();", 9, "da head, tanh', actor head bwd"),
-    ("    grad_chain<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv);", 10, "actor dX chain"),
+    ("    else grad_chain<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv);", 10, "actor dX chain"),
 ]
 names_p = {}
 for anchor, i, name in marks_p:
@@ -50,9 +57,9 @@ after("      h = mlp_hidden<RG>(a.tactor, X0, X1, X2, ldl, part + R * 16, nullpt
 after("        X0[r * ldl + S + o] = act;\n      }\n      __syncthreads();\n    }", 3)
 after("      h = mlp_hidden<RG>(a.tcritic[k], X0, X1, X2, ldl, part + R * 16, nullptr, BH, row0, rv);", 4)
 after("      if (r < rv) a.y[row0 + r] = y;\n    }", 5)
-after("      h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);", 6)
+after("      else h = mlp_hidden<RG>(a.critic[k], XS, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, BH, row0, rv);", 6)
 after("      head_backward<RG>(h, ldl, H, hw_c + k * H, 1, sm2, gsave + (a.critic[k].L - 1) * BH + row0 * H, rv);\n      __syncthreads();", 7)
-after("      grad_chain<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, gsave, BH, row0, rv);", 8)
+after("      else grad_chain<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, a.hC + (long long)k * a.critic[k].L * BH, gsave, BH, row0, rv);", 8)
 src = src.replace("size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C) {",
                   'extern "C" int gcrl_debug_rc_stamps(unsigned long long* out64) {\n'
                   "  return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_rc_stamps), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;\n}\n"
