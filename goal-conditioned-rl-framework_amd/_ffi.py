@@ -203,6 +203,8 @@ PROTOTYPES = {
     "gcrl_tanh_gauss_bwd_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _f32, C.c_int, C.c_int, _vp, _vp,
                                           C.c_int, _vp]),
     "gcrl_actor_select_f32": (C.c_int, [_vp, _vp, _f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _f32, C.c_int, _vp, _vp, _vp, _vp]),
+    "gcrl_quantile_td_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gcrl_quantile_actor_f32": (C.c_int, [_vp, _vp, _f32, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gcrl_td3_smooth_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _f32, _f32, _vp]),
     "gcrl_her_set_reward_callback": (C.c_int, [_vp, _vp, _vp]),
     "gcrl_agent_dp_sync_bn": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),

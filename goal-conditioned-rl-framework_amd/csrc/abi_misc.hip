@@ -384,6 +384,32 @@ int gcrl_actor_select_f32(const float* q, const float* logp, float alpha, int B,
   return rc;
 }
 
+int gcrl_quantile_td_f32(const float* r, const float* d, const float* zt, const float* z, const float* logp_next, float alpha, int B, int C,
+                         int Q, int drop, float gamma, float* y, float* dz, float* row_loss, float* row_td, float* metrics, void* stream) {
+  GCRL_CHECK_ARG(r && d && zt && z && logp_next && y && dz && row_loss && row_td && metrics && B >= 1 && B <= (1 << 24),
+                 "gcrl_quantile_td_f32: bad arguments (B=%d)", B);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, alpha, 0)) return rc;
+  gcrl::QuantileArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cur = s.ctrl();
+  a.r = r; a.d = d; a.zt = zt; a.z = z; a.logp_next = logp_next; a.alpha_dev = s.alpha();
+  a.y = y; a.dz = dz; a.row_loss = row_loss; a.row_td = row_td; a.metrics = metrics;
+  a.B = B; a.C = C; a.Q = Q; a.drop = drop; a.gamma = gamma;
+  return gcrl::launch_quantile_td(st, a);   // (C, Q, drop: the launcher's own refusal)
+}
+
+int gcrl_quantile_actor_f32(const float* z, const float* logp, float alpha, int B, int C, int Q, float* dz, float* metrics, void* stream) {
+  GCRL_CHECK_ARG(z && logp && dz && metrics && B >= 1 && B <= (1 << 24) && C >= 1 && C <= gcrl::kMaxCritics && Q >= 1 && C * Q <= 64,
+                 "gcrl_quantile_actor_f32: bad arguments (B=%d C=%d Q=%d)", B, C, Q);
+  hipStream_t st = as_stream(stream);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, alpha, 0)) return rc;
+  gcrl::QuantileActorArgs a{s.ctrl(), z, logp, s.alpha(), dz, metrics, B, C, Q};
+  return gcrl::launch_quantile_actor(st, a);
+}
+
 int gcrl_td3_smooth_f32(float* act, int ld, int B, int A, const float* eps, float policy_noise, float noise_clip, void* stream) {
   GCRL_CHECK_ARG(act && eps && B >= 1 && A >= 1 && ld >= A && (long long)B * ld < (1ll << 31) && noise_clip >= 0.f,
                  "gcrl_td3_smooth_f32: bad arguments (B=%d A=%d ld=%d)", B, A, ld);

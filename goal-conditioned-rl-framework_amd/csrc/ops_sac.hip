@@ -690,7 +690,8 @@ __global__ __launch_bounds__(256) void quantile_actor_kernel(QuantileActorArgs a
 }  // namespace
 
 int launch_quantile_td(hipStream_t st, const QuantileArgs& a) {
-  GCRL_CHECK_ARG(a.C >= 1 && a.Q >= 1 && a.C * a.Q <= 64 && a.drop >= 0 && a.drop < a.Q, "quantile_td: need C*Q <= 64 and 0 <= drop < Q (C=%d, Q=%d, drop=%d)", a.C, a.Q, a.drop);
+  GCRL_CHECK_ARG(a.C >= 1 && a.C <= kMaxCritics && a.Q >= 1 && a.Q <= 64 && a.C * a.Q <= 64 && a.drop >= 0 && a.drop < a.Q,   // (one loss slot per critic)
+                 "quantile_td: need C <= %d, C*Q <= 64 and 0 <= drop < Q (C=%d, Q=%d, drop=%d)", kMaxCritics, a.C, a.Q, a.drop);
   hipLaunchKernelGGL(quantile_td_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
   hipLaunchKernelGGL(quantile_metrics_kernel, dim3(1), dim3(256), 0, st, a);
   GCRL_HIP(hipGetLastError());

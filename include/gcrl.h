@@ -833,6 +833,23 @@ int gcrl_actor_select_f32(const float* q_dev, const float* logp_dev, float alpha
                           int do_alpha, float target_entropy, float log_alpha, int form, float* dq_dev, float* metrics_dev,
                           float* grad_log_alpha_dev, void* stream);
 
+/* The distributional TQC variant's loss kernels (gcrl_agent_config.n_quantiles > 1; no reference counterpart: the
+ * specification is oracle/quantile_tqc_oracle.py).  r, d, logp_next [B]; zt, z [C][B][Q]: the target and online critics' atoms.
+ * One wavefront sorts a row's C*Q pooled target atoms and keeps the lowest K = C*(Q - drop):
+ *   y [B][64]: y_j = r + gamma (1 - d) (zt_(j) - alpha logp_next) for j < K, +0 for K <= j < 64 (all 64 words written)
+ *   dz [C][B][Q] = d loss_c / d z_c, loss_c = mean over (B, Q, K) of |tau_i - 1(u < 0)| huber_1(u), u = y_j - z_c,i,
+ *                  tau_i = (2i + 1) / (2Q)
+ *   row_loss [C][B], row_td [B]: the per-row sums the metrics pass reduces; metrics[c] = loss_c for c < C,
+ *                  metrics[16] = mean_b max_c |mean_j y_j - mean_i z_c,i|.
+ * The launcher itself refuses C > 8, C*Q > 64 and drop outside [0, Q) (GCRL_ERR_ARG, "quantile_td: ..."), launching nothing. */
+int gcrl_quantile_td_f32(const float* r_dev, const float* d_dev, const float* zt_dev, const float* z_dev,
+                         const float* logp_next_dev, float alpha, int B, int C, int Q, int drop, float gamma, float* y_dev,
+                         float* dz_dev, float* row_loss_dev, float* row_td_dev, float* metrics_dev, void* stream);
+/* Its actor objective: loss = mean_b(alpha logp_b - mean over all C*Q atoms of z_c(s_b, pi(s_b))).  z [C][B][Q], logp [B]
+ * -> dz [C][B][Q] = -1 / (B*C*Q) in every word, metrics[18] = loss. */
+int gcrl_quantile_actor_f32(const float* z_dev, const float* logp_dev, float alpha, int B, int C, int Q, float* dz_dev,
+                            float* metrics_dev, void* stream);
+
 /* TD3 target-policy smoothing (src/agent.py:174-179), in place: act [B, ld] (first A columns) <- clamp(act +
  * clamp(eps * policy_noise, -noise_clip, noise_clip), -1, 1), eps [B, A]. */
 int gcrl_td3_smooth_f32(float* act_dev, int ld, int B, int A, const float* eps_dev, float policy_noise, float noise_clip,

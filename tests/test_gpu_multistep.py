@@ -70,12 +70,23 @@ def _state(ag):
     return out
 
 
+# the distributional TQC variant (Q-wide critic heads; what bench.py's "TQC Push, 25 quantiles x 2 critics" line times through
+# update_many): the benchmark's 25 x 2 with the top 2 dropped, and a full wavefront of pooled atoms (32 x 2) with nothing dropped
+DISTRIBUTIONAL = {"TQC-25x2-drop2": dict(n_quantiles=25, num_critics=2, top_quantiles_to_drop=2),
+                  "TQC-32x2-drop0": dict(n_quantiles=32, num_critics=2, top_quantiles_to_drop=0)}
+
+
 @pytest.mark.parametrize("use_graph", [True, 2])
-@pytest.mark.parametrize("kind,H,L,B", [("TD3", 32, 2, 32), ("SAC", 32, 2, 32), ("TQC", 32, 2, 32), ("TD3", 64, 3, 300), ("SAC", 64, 3, 130)])
+@pytest.mark.parametrize("kind,H,L,B", [("TD3", 32, 2, 32), ("SAC", 32, 2, 32), ("TQC", 32, 2, 32), ("TD3", 64, 3, 300), ("SAC", 64, 3, 130),
+                                        ("TQC-25x2-drop2", 32, 2, 32), ("TQC-32x2-drop0", 32, 2, 30)])
 def test_update_many_is_bitwise_repeated_update(gcrl, kind, H, L, B, use_graph):
     gstep = 5                      # SAC: Polyak on steps 5, 10, ... (src/agent.py:681); chunks below cross it and the 8-step graph runs
+    kw = DISTRIBUTIONAL.get(kind, {})
+    kind = kind.split("-")[0]
     cfg = _cfg(kind, H, L, B)
-    one, many = _build(gcrl, kind, cfg, gstep, use_graph=use_graph), _build(gcrl, kind, cfg, gstep, use_graph=use_graph)
+    one, many = _build(gcrl, kind, cfg, gstep, use_graph=use_graph, **kw), _build(gcrl, kind, cfg, gstep, use_graph=use_graph, **kw)
+    if kw:
+        assert (many.n_quantiles, len(many.critics)) == (kw["n_quantiles"], kw["num_critics"])
     chunks = [(1, 19), (20, 1), (21, 8), (29, 11)]          # 19 = 8 + 8 + 3 steps of graph runs; 39 steps in all
     t_many, t_one = [], []
     for s0, n in chunks:

@@ -822,16 +822,35 @@ def test_large_k_future_flush_bit_exact(gcrl):
 
 
 # ------------------------------------------------------------------ distributional TQC (BASELINE.json configs[3]; no reference parity)
-@pytest.mark.parametrize("H,L,B,Q,C,drop", [(32, 2, 64, 25, 2, 2), (64, 3, 130, 8, 3, 1), (512, 3, 2048, 25, 2, 2)])
+# the small-net cases: Q-wide head GEMM, its backward and the [C][B][Q] stores at Q = 2, 13, 21 (rows not 16-byte aligned) and
+# Q = 32, a full wavefront of pooled atoms (C*Q = 64) and one padding lane (63), drop = 0 and Q - 1, ragged last row groups
+@pytest.mark.parametrize("H,L,B,Q,C,drop", [(32, 2, 64, 25, 2, 2), (64, 3, 130, 8, 3, 1), (512, 3, 2048, 25, 2, 2),
+                                            (32, 2, 7, 32, 2, 0), (32, 2, 66, 8, 8, 7), (32, 2, 30, 21, 3, 5), (32, 2, 5, 2, 2, 1), (32, 2, 33, 13, 4, 12)])
 def test_quantile_tqc_matches_its_oracle(gcrl, H, L, B, Q, C, drop):
     """The 25-quantile x 2-critic TQC variant (n_quantiles > 1: pooled-atom wavefront sort, truncation, quantile-Huber
     loss) against oracle/quantile_tqc_oracle.py — the reference has no quantile critic, so the oracle is the specification
     (built from the reference's own networks / optimiser / cadence).  Two steps from identical parameters: returned tuples,
     pre-clip gradients of every network, including the full BASELINE shape (H=512, B=2048)."""
+    _quantile_tqc_against_its_oracle(gcrl, H, L, B, Q, C, drop, steps=(1, 2))
+
+
+def test_quantile_tqc_matches_its_oracle_across_the_actor_cadence(gcrl):
+    """The same with ac_update_freq = 2 and the log-alpha branch switching on inside the run (alpha_min_steps as in
+    tests/test_gpu_multistep.py): critic-only steps (6-tuples), actor steps (9-tuples) with alpha frozen, then live."""
+    lens, alpha_losses = _quantile_tqc_against_its_oracle(gcrl, 32, 2, 64, 25, 2, 2, steps=range(1, 11), ac_update_freq=2, alpha_min_steps=6.0,
+                                                          alpha_lr=1e-2)
+    assert lens == [6, 9] * 5
+    # steps 2, 4, 6: off; step 8 > alpha_min_steps: the first live update, whose loss -(log_alpha * ...).mean() is 0 at log_alpha = 0
+    # and whose step moves log_alpha; step 10: the loss of the moved log_alpha
+    assert alpha_losses[:4] == [0.0] * 4 and alpha_losses[4] != 0.0
+
+
+def _quantile_tqc_against_its_oracle(gcrl, H, L, B, Q, C, drop, steps, ac_update_freq=1, **over):
     from oracle.quantile_tqc_oracle import QuantileTQCOracle
     S, A = 22, 3
-    cfg = make_config("TQC", hidden_dim=H, layer_count=L, batch_size=B, max_len=5000, grad_clip=5.0, gamma=0.95, tau=0.05,
-                      alpha_min_steps=0.0)
+    cfg = make_config("TQC", **dict(dict(hidden_dim=H, layer_count=L, batch_size=B, max_len=5000, grad_clip=5.0, gamma=0.95, tau=0.05,
+                                         alpha_min_steps=0.0, ac_update_freq=ac_update_freq), **over))
+    lens, alpha_losses = [], []
     torch.manual_seed(3)
     torch.set_num_threads(4)
     orc = QuantileTQCOracle(S, A, cfg, n_quantiles=Q, num_critics=C, top_drop=drop)
@@ -848,7 +867,7 @@ def test_quantile_tqc_matches_its_oracle(gcrl, H, L, B, Q, C, drop):
     for v, c in zip(ag.critics, orc.critics):
         v.set_flat(orc.flat_params(c))
     ag.update_target_network()
-    for step in (1, 2):
+    for step in steps:
         batch = (gen.standard_normal((B, S)).astype(np.float32), gen.uniform(-1, 1, (B, A)).astype(np.float32),
                  -(gen.uniform(size=(B, 1)) > 0.3).astype(np.float32), gen.standard_normal((B, S)).astype(np.float32),
                  (gen.uniform(size=(B, 1)) > 0.9).astype(np.float32))
@@ -857,11 +876,15 @@ def test_quantile_tqc_matches_its_oracle(gcrl, H, L, B, Q, C, drop):
         got = ag.update(step, batch=tuple(torch.from_numpy(x).cuda() for x in batch), eps_next=torch.from_numpy(e1),
                         eps_cur=torch.from_numpy(e2))
         g = np.array([float(x) for x in got]); w = np.array([float(x) for x in want])
-        assert g.shape == w.shape == (9,)
+        actor_step = step % ac_update_freq == 0
+        assert g.shape == w.shape == ((9,) if actor_step else (6,))
         assert np.allclose(g, w, rtol=5e-5, atol=2e-6), (step, g, w)
         for v, pre in zip(ag.critics, orc.last["critic_grads_pre"]):
             assert vec_close(v.grad_flat(), pre, rtol=5e-5), (step, v.name, float(np.abs(v.grad_flat() - pre).max()), float(np.abs(pre).max()))
-        assert vec_close(ag.actor.grad_flat(), orc.last["actor_grads_pre"], rtol=5e-5), step
+        if actor_step:
+            assert vec_close(ag.actor.grad_flat(), orc.last["actor_grads_pre"], rtol=5e-5), step
+            alpha_losses.append(float(g[-1]))
+        lens.append(len(g))
         # continue both from the oracle's state
         ag.actor.set_flat(orc.flat_params(orc.actor))
         for v, t, c, tc in zip(ag.critics, ag.target_critics, orc.critics, orc.target_critics):
@@ -870,3 +893,4 @@ def test_quantile_tqc_matches_its_oracle(gcrl, H, L, B, Q, C, drop):
         ag.actor._set("bn_running_mean", np.concatenate([m.running_mean.numpy() for m in bns]))
         ag.actor._set("bn_running_var", np.concatenate([m.running_var.numpy() for m in bns]))
         ag.actor._set("log_alpha", orc.log_alpha.detach().numpy())
+    return lens, alpha_losses

@@ -22,13 +22,23 @@ def fill(agent, n_eps=2, seed=0):
             agent.push_her(0, *st)
 
 
-@pytest.mark.parametrize("kind", ["DDPG", "TD3", "SAC", "TQC"])
+# "TQC-25x2": the distributional variant (n_quantiles = 25, 2 critics, top 2 dropped): Q-wide critic heads in every checkpoint
+DISTRIBUTIONAL = dict(n_quantiles=25, num_critics=2, top_quantiles_to_drop=2)
+
+
+def variant(kind):
+    """(agent kind, extra constructor arguments) of a parametrised kind."""
+    return ("TQC", DISTRIBUTIONAL) if kind == "TQC-25x2" else (kind, {})
+
+
+@pytest.mark.parametrize("kind", ["DDPG", "TD3", "SAC", "TQC", "TQC-25x2"])
 def test_checkpoints_round_trip_through_torch_modules(gcrl, tmp_path, kind):
     """save_weights() files load with strict=True into torch modules laid out like the reference's
     (src/model.py key names / shapes), and weights saved by those modules load back."""
+    kind, kw = variant(kind)
     cfg = make_config(kind, hidden_dim=H, layer_count=L, batch_size=16)
     cls = dict(DDPG=gcrl.DDPG, TD3=gcrl.TD3Agent, SAC=gcrl.SACAgent, TQC=gcrl.TQCAgent)[kind]
-    ag = cls(S, A, cfg, None, nenvs=1, gradient_step=2, rng="engine", seed=3)
+    ag = cls(S, A, cfg, None, nenvs=1, gradient_step=2, rng="engine", seed=3, **kw)
     fill(ag)
     for step in (1, 2):
         ag.update(step)          # moves weights, BN statistics, log_alpha away from their init
@@ -36,9 +46,14 @@ def test_checkpoints_round_trip_through_torch_modules(gcrl, tmp_path, kind):
     actor_mod = (GaussActor if kind in ("SAC", "TQC") else DetActor)(S, H, A, L)
     actor_mod.load_state_dict(torch.load(tmp_path / "actor.pth"), strict=True)
     names = {"DDPG": ["critic.pth"], "TD3": ["critic_1.pth", "critic_2.pth"], "SAC": ["critic_1.pth", "critic_2.pth"],
-             "TQC": [f"critic_{i}.pth" for i in range(5)]}[kind]
+             "TQC": [f"critic_{i}.pth" for i in range(kw.get("num_critics", 5))]}[kind]
+    assert len(names) == len(ag.critics)
     for i, fn in enumerate(names):
-        q = QNet(S + A, H, L)
+        if kw:      # the reference's Critic with a Q-wide head (oracle/quantile_tqc_oracle.py): same keys, the head [Q, H]
+            from oracle.quantile_tqc_oracle import QuantileNet
+            q = QuantileNet(S + A, H, L, kw["n_quantiles"])
+        else:
+            q = QNet(S + A, H, L)
         q.load_state_dict(torch.load(tmp_path / fn), strict=True)
         flat = np.concatenate([p.detach().numpy().reshape(-1) for p in q.parameters()])
         assert np.array_equal(flat, ag.critics[i].flat())
@@ -49,7 +64,9 @@ def test_checkpoints_round_trip_through_torch_modules(gcrl, tmp_path, kind):
         bn = [m for m in actor_mod.base_net if isinstance(m, torch.nn.BatchNorm1d)]
         assert not torch.equal(bn[0].running_mean, torch.zeros(H))     # statistics travelled
     # and back: a fresh engine agent constructed with weights=dir reproduces the actor's outputs
-    ag2 = cls(S, A, cfg, str(tmp_path), nenvs=1, gradient_step=2, rng="engine", seed=99)
+    ag2 = cls(S, A, cfg, str(tmp_path), nenvs=1, gradient_step=2, rng="engine", seed=99, **kw)
+    for c, c2 in zip(ag.critics, ag2.critics):
+        assert np.array_equal(c.flat(), c2.flat())
     obs = np.random.default_rng(1).standard_normal((7, S)).astype(np.float32)
     assert np.array_equal(ag.select_action(obs, eval_action=True), ag2.select_action(obs, eval_action=True))
     with torch.no_grad():
@@ -278,13 +295,14 @@ def test_push_batch_equals_per_env_pushes_and_oracle(gcrl, k, nenvs):
 # ------------------------------------------------------------------ full resume state (SURVEY.md §8f-2 extension)
 def resume_agent(gcrl, kind, nenvs=2):
     from oracle.agent_oracle import make_config
+    kind, kw = variant(kind)
     cfg = make_config(kind, hidden_dim=32, layer_count=2, batch_size=32, max_len=1000, ac_update_freq=2 if kind == "TD3" else 1,
                       policy_noise=0.2, actor_lr_min=1e-4, ac_scheduler_steps=25, critic_lr_min=2e-4, cr_scheduler_steps=30)
     cls = dict(DDPG=gcrl.DDPG, TD3=gcrl.TD3Agent, SAC=gcrl.SACAgent, TQC=gcrl.TQCAgent)[kind]
-    return cls(10, 3, cfg, None, nenvs=nenvs, gradient_step=10, rng="engine", seed=5)
+    return cls(10, 3, cfg, None, nenvs=nenvs, gradient_step=10, rng="engine", seed=5, **kw)
 
 
-@pytest.mark.parametrize("kind", ["DDPG", "TD3", "SAC", "TQC"])
+@pytest.mark.parametrize("kind", ["DDPG", "TD3", "SAC", "TQC", "TQC-25x2"])
 def test_full_state_resume_in_a_new_process(gcrl, tmp_path, kind):
     """save_state after 30 steps (ring wrapped, one episode half staged, cosine schedules mid-way, device-noise counter
     advanced), load into a fresh agent in a NEW process, continue 20 steps there and here: tuples, parameters, targets
