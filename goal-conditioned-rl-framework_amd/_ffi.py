@@ -35,6 +35,11 @@ class HerConfig(C.Structure):
     ]
 
 
+class EnergyConfig(C.Structure):
+    _fields_ = [("potential", C.c_float), ("kinetic", C.c_float), ("axis", C.c_int32), ("clip", C.c_float), ("alpha", C.c_float),
+                ("eps", C.c_float)]
+
+
 class AgentConfig(C.Structure):
     _fields_ = [
         ("kind", C.c_int32), ("obs_dim", C.c_int32), ("ac_dim", C.c_int32),
@@ -243,6 +248,11 @@ PROTOTYPES = {
     "gcrl_per_get_draw_counter": (_i64, [_vp]),
     "gcrl_per_set_draw_counter": (C.c_int, [_vp, _i64]),
     "gcrl_per_launches": (_i64, [_vp]),
+    "gcrl_her_prio_attach": (C.c_int, [_vp, C.POINTER(EnergyConfig)]),
+    "gcrl_her_prio_mode": (C.c_int, [_vp]),
+    "gcrl_her_prio_draw": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "gcrl_her_get_prio_counter": (_u64, [_vp]),
+    "gcrl_her_set_prio_counter": (C.c_int, [_vp, _u64]),
     "gcrl_event_create": (_vp, []),
     "gcrl_event_destroy": (None, [_vp]),
     "gcrl_event_record": (C.c_int, [_vp, _vp]),

@@ -1158,6 +1158,8 @@ struct CallGather {
   bool per_dev = false;        // no gather with the call's upload: every step draws and gathers its own rows
   bool head_form = false;      // the gather reads its indices from the pinned block and carries the control block as a side copy
   bool host_idx = false;
+  bool prio = false;           // the ring's energy tree draws the call's rows into idx_dev() ahead of the gather (her_prio.hip)
+  uint64_t prio_c0 = 0;        // ... from this row of the ring's draw stream on (snapshotted and advanced at plan time, like g.ctr)
   int slot = 0;
   UploadBlock* ub = nullptr;
   const uint32_t* idx_pinned = nullptr;
@@ -1179,7 +1181,12 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     GCRL_CHECK_ARG(her->S == a->S && her->A == a->A, "update: ring dims (S=%d,A=%d) differ from the agent's (S=%d,A=%d)", her->S, her->A, a->S, a->A);
     if (her->len < a->B) return fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
   }
-  GCRL_CHECK_ARG(injected || (in && in->idx_host) || !her->per || a->per_call,
+  const bool prio = !injected && !(in && in->idx_host) && her_prio_on(her);   // a third index source beside the MT upload and the in-kernel IdxGen
+  if (prio) {   // refused before a ticket, slot or plan is consumed
+    if (a->xchg) return fail(GCRL_ERR_STATE, "update: prioritise: a ring with an energy tree does not feed an agent under a gradient exchange");
+    TRY(her_prio_check(her, "update"));
+  }
+  GCRL_CHECK_ARG(injected || (in && in->idx_host) || !per_is_td(her->per) || a->per_call,
                  "update: this entry does not draw from a ring's priority tree (per_draw=\"device\"): use gcrl_agent_update / gcrl_agent_update_n");
   if (!injected && in && in->idx_host)     // every argument is checked before a ticket, slot or plan is consumed
     for (int i = 0; i < a->B; ++i)
@@ -1202,12 +1209,12 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   ub->cb.cur = table[0];
   size_t bytes = sizeof(UploadBlock);
   const bool explicit_idx = !injected && in && in->idx_host;
-  const bool per_dev = !injected && !explicit_idx && her->per;   // the priority tree draws every step's rows on the device (run_per_device)
-  const bool device_rng = !injected && !per_dev && her->cfg.rng_mode != GCRL_RNG_CPYTHON_MT;
+  const bool per_dev = !injected && !explicit_idx && per_is_td(her->per);   // the priority tree draws every step's rows on the device (run_per_device)
+  const bool device_rng = !injected && !per_dev && !prio && her->cfg.rng_mode != GCRL_RNG_CPYTHON_MT;
   if (explicit_idx) {   // prioritised replay: the caller drew the rows
     for (int i = 0; i < a->B; ++i) idx[i] = in->idx_host[i];
     bytes += (size_t)a->B * sizeof(uint32_t);
-  } else if (!injected && !device_rng && !per_dev) {
+  } else if (!injected && !device_rng && !per_dev && !prio) {
     const int head = a->head_batches;
     defer_rest = defer_rest && n > head;
     const int now = defer_rest ? head : n;   // same MT stream order either way: the head's batches now, the rest once that many steps are issued
@@ -1225,6 +1232,8 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   cg->injected = injected;
   cg->per_dev = per_dev;
   cg->host_idx = host_idx;
+  cg->prio = prio;
+  if (prio) cg->prio_c0 = her_prio_take(her, rows_now);   // all n * B rows of the call: one draw launch, nothing deferred, the MT stream untouched
   cg->slot = slot;
   cg->ub = ub;
   cg->idx_pinned = idx;
@@ -1232,7 +1241,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   // One launch starts the call: the gather reads its (<= 2 B) indices straight from the pinned block and carries the
   // control block to the device (header + the n table entries in use) — before, two staged copies and their launch
   // gaps (19 us) preceded the first gather.
-  cg->head_form = !injected && !per_dev && (!host_idx || rows_now <= (int64_t)a->head_batches * a->B);
+  cg->head_form = !injected && !per_dev && (!host_idx || prio || rows_now <= (int64_t)a->head_batches * a->B);   // (prio: the indices are on the device already)
   cg->cb_bytes = (offsetof(UploadBlock, cb) + offsetof(CtrlBlock, table) + (size_t)n * sizeof(StepCtrl) + 15) & ~(size_t)15;
   GatherCall& g = cg->g;
   g = GatherCall{};
@@ -1251,7 +1260,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
 // the form a planned gather takes: head (indices in the pinned block, control block as a side copy) or main (both uploaded before)
 void call_gather_form(gcrl_agent* a, CallGather* cg, bool head) {
   GatherCall& g = cg->g;
-  g.idx = !cg->host_idx ? nullptr : (head ? cg->idx_pinned : a->idx_dev());
+  g.idx = !cg->host_idx ? nullptr : (head && !cg->prio ? cg->idx_pinned : a->idx_dev());
   g.cp_src = head ? cg->ub : nullptr;
   g.cp_dst = head ? a->upload_dev : nullptr;
   g.cp_bytes = head ? cg->cb_bytes : 0;
@@ -1260,6 +1269,7 @@ void call_gather_form(gcrl_agent* a, CallGather* cg, bool head) {
 int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
   const GatherCall& g = cg->g;
   call_gather_form(a, cg, cg->head_form);
+  if (cg->prio) TRY(her_prio_draw_at(g.h, cg->prio_c0, g.n, a->idx_dev(), st));   // draw + gather: the call's only launches ahead of its steps
   if (cg->head_form) {
     TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, g.cp_src, g.cp_dst, g.cp_bytes, &g.ctr, &g.gamma));
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
@@ -1982,7 +1992,7 @@ int run_per_device(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcr
 int gcrl_agent_update(gcrl_agent* a, gcrl_her* her, int64_t step, const gcrl_update_inputs* in, int64_t* ticket_out, void* stream) {
   GCRL_CHECK_ARG(a, "gcrl_agent_update: null handle");
   hipStream_t st = a->pick(stream);
-  if (her && her->per && !(in && (in->s_dev || in->idx_host))) {
+  if (her && per_is_td(her->per) && !(in && (in->s_dev || in->idx_host))) {
     int32_t plen = 0;
     TRY(run_per_device(a, her, step, 1, in, ticket_out, &plen, st));
     return plen;
@@ -2008,7 +2018,7 @@ int gcrl_agent_update_n(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, int6
   // a process that arrived on this device after the handle was built: its kernels hold CUs, so no more waits inside launches
   if ((a->calls & 31) == 0 && !meet_device_shared()) { const int rc = gcrl_agent_get_meetings(a); if (rc < 0) return rc; }   // (probes, and switches the forms off)
   hipStream_t st = a->pick(stream);
-  if (her->per) return run_per_device(a, her, step0, n, nullptr, tickets_out, lens_out, st);
+  if (per_is_td(her->per)) return run_per_device(a, her, step0, n, nullptr, tickets_out, lens_out, st);
   const int chunk = std::min(kMaxStepsPerCall, a->Mmax);
   for (int done = 0; done < n; done += chunk) {
     const int m = std::min(chunk, n - done);

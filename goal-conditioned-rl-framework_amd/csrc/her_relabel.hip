@@ -332,7 +332,8 @@ int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipS
   h->episodes_flushed += nep;
   h->mutation_epoch++;
   *rows_out = total;
-  return GCRL_OK;
+  // a ring with an energy tree: the leaves of the rows just written, from the same staged records, in stream order behind the flush
+  return her_prio_flush(h, nep, fa.stage, fa.T, fa.tail, fa.skip, total, st);
 }
 
 int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, int64_t n, float* sa, float* nsa, float* spa, int ldx,

@@ -121,7 +121,7 @@ struct gcrl_her {
   bool idx_on_device = true;      // false: no index array was uploaded (device-RNG mode)
   uint64_t mutation_epoch = 0;    // bumped by every flush
   uint64_t rows_pushed = 0;       // rows ever appended (>= len): what the priority tree measures its pending pushes against
-  gcrl_per_tree* per = nullptr;   // device-resident prioritised replay (per_tree.h), or null
+  gcrl_per_tree* per = nullptr;   // the ring's priority tree (per_tree.h), or null: TD priorities (per_tree.hip) or episode energies (her_prio.hip), by its source tag
 
   // index upload: pinned host slots -> idx_dev
   static constexpr int kSlots = 8;
@@ -217,6 +217,17 @@ int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, in
                               float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
 int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                        float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
+// energy-prioritised draw of such a ring (her_prio.hip; a no-op / refusal unless gcrl_her_prio_attach gave it an energy tree).
+// her_prio_flush: ONE launch behind a flush launch — the leaves of the rows it wrote (stage / Ts / tail / skip: that launch's own
+// arguments; `total` its rows; the ring's head / len already advanced) and their ancestors.  her_prio_check: GCRL_ERR_STATE without a
+// fresh energy tree.  her_prio_draw_at: rows c0 .. c0 + rows - 1 of the ring's draw stream -> idx_dev (logical indices), one launch;
+// the ring's counter is the caller's to advance (the planner of an update call does, as with GatherCall::ctr).
+int her_prio_flush(gcrl_her* h, int nep, const float* const* stage, const int* Ts, int64_t tail, int64_t skip, int64_t total, hipStream_t st);
+// her_prio_on: the ring has an energy tree.  her_prio_take: the counter as of now, advanced by `rows`.
+bool her_prio_on(const gcrl_her* h);
+uint64_t her_prio_take(gcrl_her* h, int64_t rows);
+int her_prio_check(const gcrl_her* h, const char* who);
+int her_prio_draw_at(gcrl_her* h, uint64_t c0, int64_t rows, uint32_t* idx_dev, hipStream_t st);
 // the same two gathers for a ring with n_step in 2..8 (her_nstep.hip), discounting by g32
 int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
                             float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);

@@ -694,6 +694,22 @@ int her_upload_indices(gcrl_her* h, int B, int M, const uint32_t* idx_host, hipS
   return GCRL_OK;
 }
 
+// The B * M rows of a public sample / gather of a ring with an energy tree (her_prio.hip): ONE draw launch into h->idx_dev at the
+// ring's draw counter, which advances; the MT stream is not consumed.  drawn_host: the indices copied back (synchronises).
+int her_prio_indices(gcrl_her* h, int B, int M, hipStream_t st, uint32_t* drawn_host) {
+  const size_t rows = (size_t)B * M;
+  if (int rc = her_prio_check(h, "sample")) return rc;
+  if (h->len < B) return fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
+  if (int rc = ensure_index_capacity(h, rows)) return rc;
+  if (int rc = her_prio_draw_at(h, her_prio_take(h, (int64_t)rows), (int64_t)rows, h->idx_dev, st)) return rc;
+  h->idx_on_device = true;
+  if (drawn_host) {
+    GCRL_HIP(hipMemcpyAsync(drawn_host, h->idx_dev, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipStreamSynchronize(st));
+  }
+  return GCRL_OK;
+}
+
 int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa, float* nsa,
                       float* spa, int ldx, float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes,
                       const uint64_t* relabel_ctr, const double* gamma) {
@@ -942,6 +958,8 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
   GCRL_CHECK_ARG(h && state && action_host && next_state, "gcrl_her_append: null argument");
   if ((!state_on_device || !next_on_device) && h->S > kMaxInline)
     return gcrl::fail(GCRL_ERR_ARG, "gcrl_her_append: host-pointer states support state_dim <= %d", kMaxInline);
+  if (gcrl::her_prio_on(h))
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_append: prioritise: a ring with an energy tree takes whole episodes (a lone row has no trajectory)");
   hipStream_t st = h->pick(stream);
   gcrl::RingBook book{h->cfg.capacity, h->head, h->len};
   const int64_t phys = book.tail();
@@ -1136,8 +1154,12 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
   GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample: row stride smaller than the row");
   hipStream_t st = h->pick(stream);
   const uint32_t* host_copy = nullptr;
-  if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, drawn_idx_host ? &host_copy : nullptr)) return rc;
-  if (drawn_idx_host) std::memcpy(drawn_idx_host, host_copy, (size_t)B * M * sizeof(uint32_t));
+  if (!idx_host && gcrl::her_prio_on(h)) {   // prioritise = "energy": the tree draws the rows
+    if (int rc = gcrl::her_prio_indices(h, B, M, st, drawn_idx_host)) return rc;
+  } else {
+    if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, drawn_idx_host ? &host_copy : nullptr)) return rc;
+    if (drawn_idx_host) std::memcpy(drawn_idx_host, host_copy, (size_t)B * M * sizeof(uint32_t));
+  }
   const long long n = (long long)B * M;
   if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
     if (int rc = prof_begin(h, st)) return rc;
@@ -1201,7 +1223,9 @@ int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, 
   GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_gather_update: B and M must be >= 1");
   GCRL_CHECK_ARG(side_bytes >= 0, "gcrl_her_gather_update: side_bytes %lld", (long long)side_bytes);
   hipStream_t st = h->pick(stream);
-  if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, nullptr)) return rc;
+  if (!idx_host && gcrl::her_prio_on(h)) {
+    if (int rc = gcrl::her_prio_indices(h, B, M, st, nullptr)) return rc;
+  } else if (int rc = gcrl::her_upload_indices(h, B, M, idx_host, st, nullptr)) return rc;
   return gcrl::her_gather_update(h, h->idx_on_device ? h->idx_dev : nullptr, (int64_t)B * M, sa, nsa, spa, ldx, r, d, st, side_src, side_dst, (size_t)side_bytes);
 }
 

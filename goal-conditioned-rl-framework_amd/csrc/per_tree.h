@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "../../include/gcrl.h"
 #include "per_host.h"
 
 struct gcrl_her;
@@ -21,13 +22,25 @@ struct gcrl_per_tree {
   std::vector<float> betas;     // per-step beta values queued for the engine's next steps (gcrl_per_set_betas)
   size_t beta_pos = 0;
   int64_t launches = 0;         // kernel launches issued by this tree
+  int source = 0;               // gcrl::kPerSourceTd (leaves = (|td| + eps)^alpha, fed back by the update engine) or kPerSourceEnergy
+  gcrl_energy_config energy{};  // kPerSourceEnergy (her_prio.hip): leaves written once, by the ring's flush
+  uint64_t prio_ctr = 0;        // kPerSourceEnergy: rows ever drawn (the draw stream's counter)
 };
 
 namespace gcrl {
 
 constexpr uint64_t kPerKey = 0x5045525f54524545ull;   // "PER_TREE": key of the draw's uniform stream
 
+constexpr int kPerSourceTd = 0, kPerSourceEnergy = 1;
+inline bool per_is_td(const gcrl_per_tree* t) { return t && t->source == kPerSourceTd; }
+inline bool per_is_energy(const gcrl_per_tree* t) { return t && t->source == kPerSourceEnergy; }
+
 void per_release(gcrl_her* h);
+// a zeroed tree for the ring's capacity, not yet attached (*out; freed by the caller on a later failure: per_tree_free)
+int per_tree_alloc(gcrl_her* h, const char* who, gcrl_per_tree** out);
+void per_tree_free(gcrl_per_tree* t);
+// every level above the leaves recomputed, one launch per level
+int per_rebuild(gcrl_per_tree* t, hipStream_t st);
 // priority 1.0 for the rows pushed since the last refresh, their ancestors recomputed: at most one launch up to kPerRefreshOne
 // pending rows (beyond that: one fill launch and a rebuild)
 int per_refresh(gcrl_her* h, hipStream_t st);

@@ -203,8 +203,11 @@ int rebuild(gcrl_per_tree* t, hipStream_t st) {
   return GCRL_OK;
 }
 
-int need_tree(const gcrl_her* h, const char* who, bool fresh = true) {
+int need_tree(const gcrl_her* h, const char* who, bool fresh = true, bool td_only = false) {
   if (!h || !h->per) return gcrl::fail(GCRL_ERR_STATE, "%s: no priority tree is attached to this ring (gcrl_per_attach)", who);
+  if (td_only && !gcrl::per_is_td(h->per))
+    return gcrl::fail(GCRL_ERR_STATE, "%s: prioritise: the ring's tree holds episode energies (gcrl_her_prio_attach): it is drawn by gcrl_her_prio_draw, "
+                      "takes no weights and no priority update", who);
   if (fresh && h->per->stale)
     return gcrl::fail(GCRL_ERR_STATE, "%s: the ring was reloaded after the tree was built: set its priorities first (gcrl_per_set_priorities)", who);
   return GCRL_OK;
@@ -214,14 +217,35 @@ int need_tree(const gcrl_her* h, const char* who, bool fresh = true) {
 
 namespace gcrl {
 
-void per_release(gcrl_her* h) {
-  gcrl_per_tree* t = h->per;
+void per_tree_free(gcrl_per_tree* t) {
   if (!t) return;
-  h->per = nullptr;
   if (t->tree) (void)hipFree(t->tree);
   if (t->p_drawn) (void)hipFree(t->p_drawn);
   delete t;
 }
+
+void per_release(gcrl_her* h) {
+  gcrl_per_tree* t = h->per;
+  h->per = nullptr;
+  per_tree_free(t);
+}
+
+int per_tree_alloc(gcrl_her* h, const char* who, gcrl_per_tree** out) {
+  PerLayout L;
+  GCRL_CHECK_ARG(per_layout(h->cfg.capacity, &L), "%s: capacity %lld has no tree layout", who, (long long)h->cfg.capacity);
+  GCRL_HIP(hipSetDevice(h->cfg.device));
+  float* tree = nullptr;
+  GCRL_HIP(hipMalloc((void**)&tree, (size_t)L.total * sizeof(float)));
+  hipError_t e = hipMemset(tree, 0, (size_t)L.total * sizeof(float));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(tree); GCRL_HIP(e); }
+  gcrl_per_tree* t = new gcrl_per_tree;
+  t->L = L; t->tree = tree;
+  *out = t;
+  return GCRL_OK;
+}
+
+int per_rebuild(gcrl_per_tree* t, hipStream_t st) { return rebuild(t, st); }
 
 void per_mark_stale(gcrl_her* h) {
   if (h->per) h->per->stale = true;
@@ -229,7 +253,7 @@ void per_mark_stale(gcrl_her* h) {
 
 int per_refresh(gcrl_her* h, hipStream_t st) {
   gcrl_per_tree* t = h->per;
-  const int64_t pending = (int64_t)(h->rows_pushed - t->synced_rows);
+  const int64_t pending = per_is_td(t) ? (int64_t)(h->rows_pushed - t->synced_rows) : 0;   // an energy tree's leaves are the flush's: never 1.0
   t->synced_rows = h->rows_pushed;
   const PerSegs s = per_pending_segments(h->head, h->len, h->cfg.capacity, pending);
   const int64_t n = (s.a1 - s.a0) + (s.b1 - s.b0);
@@ -249,7 +273,7 @@ int per_refresh(gcrl_her* h, hipStream_t st) {
 }
 
 int per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, hipStream_t st) {
-  if (int rc = need_tree(h, "per_draw")) return rc;
+  if (int rc = need_tree(h, "per_draw", true, true)) return rc;
   gcrl_per_tree* t = h->per;
   GCRL_CHECK_ARG(idx_dev && B >= 1 && B <= (1 << 20), "per_draw: batch size %d (1..2^20) / null index buffer", B);
   if (h->len < B) return fail(GCRL_ERR_NOT_ENOUGH, "Not enough in buffer to sample");
@@ -275,7 +299,7 @@ int per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, hi
 }
 
 int per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B, float* hist_dev, hipStream_t st) {
-  if (int rc = need_tree(h, "per_update")) return rc;
+  if (int rc = need_tree(h, "per_update", true, true)) return rc;
   gcrl_per_tree* t = h->per;
   GCRL_CHECK_ARG(idx_dev && td_dev && B >= 1, "per_update: null buffer / batch size %d", B);
   if (int rc = per_refresh(h, st)) return rc;   // (rows pushed between the draw and this update: their 1.0 first, as in the reference's order)
@@ -290,7 +314,7 @@ int per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B,
 
 bool per_next_beta(gcrl_her* h, float* beta) {
   gcrl_per_tree* t = h->per;
-  if (!t || t->beta_pos >= t->betas.size()) return false;
+  if (!per_is_td(t) || t->beta_pos >= t->betas.size()) return false;
   *beta = t->betas[t->beta_pos++];
   return true;
 }
@@ -301,20 +325,13 @@ extern "C" {
 
 int gcrl_per_attach(gcrl_her* h, float alpha, float eps) {
   GCRL_CHECK_ARG(h, "gcrl_per_attach: null ring");
-  GCRL_CHECK_ARG(!h->per, "gcrl_per_attach: the ring already has a priority tree");
-  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)   // a property of the ring, not of this call's arguments
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)   // a property of the ring, not of this call's arguments (whether or not it has an energy tree)
     return gcrl::fail(GCRL_ERR_STATE, "gcrl_per_attach: relabel: a ring with sample-time relabelling (GCRL_RELABEL_SAMPLE) takes no priority tree");
+  GCRL_CHECK_ARG(!h->per, "gcrl_per_attach: the ring already has a priority tree");
   GCRL_CHECK_ARG(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(eps) && eps > 0.0f, "gcrl_per_attach: alpha %g (>= 0) / eps %g (> 0)", (double)alpha, (double)eps);
-  gcrl::PerLayout L;
-  GCRL_CHECK_ARG(gcrl::per_layout(h->cfg.capacity, &L), "gcrl_per_attach: capacity %lld has no tree layout", (long long)h->cfg.capacity);
-  GCRL_HIP(hipSetDevice(h->cfg.device));
-  float* tree = nullptr;
-  GCRL_HIP(hipMalloc((void**)&tree, (size_t)L.total * sizeof(float)));
-  hipError_t e = hipMemset(tree, 0, (size_t)L.total * sizeof(float));
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { (void)hipFree(tree); GCRL_HIP(e); }
-  gcrl_per_tree* t = new gcrl_per_tree;
-  t->L = L; t->tree = tree; t->alpha = alpha; t->eps = eps;
+  gcrl_per_tree* t = nullptr;
+  if (int rc = gcrl::per_tree_alloc(h, "gcrl_per_attach", &t)) return rc;
+  t->alpha = alpha; t->eps = eps;
   t->synced_rows = h->rows_pushed - (uint64_t)h->len;   // rows already in the ring: priority 1.0 at the first refresh
   h->per = t;
   return GCRL_OK;
@@ -339,7 +356,7 @@ int gcrl_per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, i
 }
 
 int gcrl_per_set_betas(gcrl_her* h, const float* betas_host, int n) {
-  if (int rc = need_tree(h, "gcrl_per_set_betas", false)) return rc;
+  if (int rc = need_tree(h, "gcrl_per_set_betas", false, true)) return rc;
   GCRL_CHECK_ARG(n >= 0 && (betas_host || n == 0), "gcrl_per_set_betas: null array");
   h->per->betas.assign(betas_host, betas_host + n);
   h->per->beta_pos = 0;
@@ -396,7 +413,7 @@ int gcrl_per_read_level(gcrl_her* h, int level, float* out_host, int64_t n) {
 int64_t gcrl_per_get_draw_counter(const gcrl_her* h) { return h && h->per ? (int64_t)h->per->draws : -1; }
 
 int gcrl_per_set_draw_counter(gcrl_her* h, int64_t counter) {
-  if (int rc = need_tree(h, "gcrl_per_set_draw_counter", false)) return rc;
+  if (int rc = need_tree(h, "gcrl_per_set_draw_counter", false, true)) return rc;
   GCRL_CHECK_ARG(counter >= 0, "gcrl_per_set_draw_counter: counter %lld", (long long)counter);
   h->per->draws = (uint64_t)counter;
   return GCRL_OK;

@@ -22,7 +22,7 @@ import torch
 
 from .. import _ffi
 from .._ffi import lib
-from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_nstep
+from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_nstep
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -187,7 +187,7 @@ class _EngineAgent:
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
-                 n_step: int = 1, _member=None):
+                 n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -213,6 +213,12 @@ class _EngineAgent:
                 raise _ffi.GcrlError(f"{who}: per_draw: the distributional TQC variant (n_quantiles > 1) has no importance-weighted loss; "
                                      "per_draw='device' needs scalar critics")
         self.per_draw = per_draw
+        # prioritise="energy" (relabel="sample"): the HER ring draws every batch from its energy tree (buffer.HERBuffer); every agent
+        # kind and launch form runs as without it, only the row indices the call's gather reads change.  Refused before any device work.
+        _check_energy(type(self).__name__, prioritise, energy, relabel, per_draw, config.buffer_type)
+        if prioritise is not None and _member is not None:
+            raise _ffi.GcrlError(f"{type(self).__name__}: prioritise: populations do not draw from an energy tree")
+        self.prioritise = prioritise
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
         self.device = "cuda"
@@ -233,7 +239,8 @@ class _EngineAgent:
         elif config.buffer_type == "HER":
             self.buffer = HERBuffer(config.max_len, config.max_eps_len, nenvs, k_future=config.k_future,
                                     rng=rng, seed=seed, device_index=device_index, relabel=relabel,
-                                    n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None)
+                                    n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None,
+                                    prioritise=prioritise, energy=energy)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 

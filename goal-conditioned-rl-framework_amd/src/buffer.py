@@ -151,6 +151,62 @@ def _check_nstep(who: str, n_step, gamma, relabel: str):
     return n_step, (None if gamma is None else float(gamma))
 
 
+PRIORITISE_MODES = (None, "energy")
+# prioritise="energy": the constants of the episode energy (tests/her_energy_ref.py is the definition).  The defaults are this
+# project's choice — m = 1: potential = m g = 9.81, kinetic = m / (2 dt^2) with dt = 0.04, axis 2 = the height of a 3-component goal
+# position (-1, no potential term, for goals with fewer components) — not a claim about anybody's published settings.
+ENERGY_DEFAULTS = dict(potential=9.81, kinetic=312.5, axis=None, clip=0.5, alpha=1.0, eps=1e-3)
+
+
+def _check_energy(who: str, prioritise, energy, relabel: str, per_draw: str = "host", buffer_type: str = "HER"):
+    """-> the energy settings as a dict (axis None until the goal width is known), or None for prioritise=None; every refusal names
+    `prioritise` or the `energy` key at fault and comes before any device work"""
+    if prioritise not in PRIORITISE_MODES:
+        raise _ffi.GcrlError(f"{who}: prioritise: must be None or 'energy', got {prioritise!r}")
+    if prioritise is None:
+        if energy is not None:
+            raise _ffi.GcrlError(f"{who}: prioritise: energy= was given without prioritise='energy'")
+        return None
+    if per_draw != "host":       # (asked first: per_draw='device' implies a PER buffer, which the next check would name instead)
+        raise _ffi.GcrlError(f"{who}: prioritise: 'energy' and per_draw={per_draw!r} are two trees for one ring; a ring takes one")
+    if buffer_type != "HER":
+        raise _ffi.GcrlError(f"{who}: prioritise: 'energy' needs buffer_type 'HER' with relabel='sample', got {buffer_type!r}")
+    if relabel != "sample":
+        raise _ffi.GcrlError(f"{who}: prioritise: 'energy' reads an episode's achieved goals from the tails of a relabel='sample' ring, "
+                             f"got relabel={relabel!r}")
+    cfg = dict(ENERGY_DEFAULTS)
+    for k, v in dict(energy or {}).items():
+        if k not in cfg:
+            raise _ffi.GcrlError(f"{who}: energy: unknown key {k!r} (one of {sorted(cfg)})")
+        cfg[k] = v
+    for k in ("potential", "kinetic", "clip", "alpha", "eps"):
+        v = cfg[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(v)):
+            raise _ffi.GcrlError(f"{who}: energy: {k}: must be a finite number, got {v!r}")
+        cfg[k] = float(np.float32(v))
+    if cfg["clip"] <= 0:
+        raise _ffi.GcrlError(f"{who}: energy: clip: must be > 0, got {cfg['clip']!r}")
+    if cfg["eps"] <= 0:
+        raise _ffi.GcrlError(f"{who}: energy: eps: must be > 0, got {cfg['eps']!r}")
+    if cfg["alpha"] < 0:
+        raise _ffi.GcrlError(f"{who}: energy: alpha: must be >= 0, got {cfg['alpha']!r}")
+    ax = cfg["axis"]
+    if ax is not None and (isinstance(ax, bool) or not isinstance(ax, (int, np.integer))):
+        raise _ffi.GcrlError(f"{who}: energy: axis: must be an integer (negative: no potential term) or None, got {ax!r}")
+    if ax is not None:
+        cfg["axis"] = max(int(ax), -1)     # every negative axis is the one setting "no potential term": held, saved and compared as -1
+    return cfg
+
+
+def _energy_axis(who: str, cfg: dict, G: int) -> int:
+    ax = cfg["axis"]
+    if ax is None:
+        return 2 if G >= 3 else -1
+    if int(ax) >= G:
+        raise _ffi.GcrlError(f"{who}: energy: axis: {int(ax)} of a goal with {G} components")
+    return max(int(ax), -1)
+
+
 class _RingState:
     """save_state / load_state shared by the three buffers (extension of SURVEY.md §8f-2)."""
 
@@ -159,6 +215,7 @@ class _RingState:
         load_state needs.  An untouched buffer (no transition pushed yet) saves as empty."""
         meta = dict(dims=self._dims, rng_mode=self.rng.mode, py_random=None, mt=None, bytes=0)
         meta["relabel"] = getattr(self, "relabel", "push")
+        meta["prioritise"] = getattr(self, "prioritise", None)
         if self.rng.mode == "python":
             st = _pyrandom.getstate()
             meta["py_random"] = [st[0], list(st[1]), st[2]]
@@ -173,12 +230,27 @@ class _RingState:
             meta["bytes"] = n
         if hasattr(self, "priorities"):
             meta["priorities"] = [float(p) for p in self.priorities]
+        if meta["prioritise"] is not None:
+            meta["energy"] = dict(self.energy)
+            if self._h is not None:    # the leaves (logical order), the draw counter, and the head the tree's sums depend on
+                meta["prio_leaves"] = self.get_priorities().view(np.uint32).tolist()
+                meta["prio_counter"] = self.prio_counter
+                meta["prio_head"] = int(lib.gcrl_her_head(self._h))
         return meta
 
     def load_state(self, path: str, meta: dict):
         if meta.get("relabel", "push") != getattr(self, "relabel", "push"):    # refused before any device work
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: relabel: the state was saved with relabel={meta.get('relabel', 'push')!r}, "
                                  f"this buffer has relabel={getattr(self, 'relabel', 'push')!r}")
+        if meta.get("prioritise") != getattr(self, "prioritise", None):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with prioritise={meta.get('prioritise')!r}, "
+                                 f"this buffer has prioritise={getattr(self, 'prioritise', None)!r}")
+        mine = dict(self.energy) if getattr(self, "prioritise", None) is not None else None
+        if mine is not None and mine["axis"] is None and meta.get("dims"):     # (the default axis follows the goal width: known once a ring exists)
+            mine["axis"] = _energy_axis(type(self).__name__, mine, int(meta["dims"][2]))
+        if meta.get("prioritise") is not None and meta.get("energy") != mine:
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with energy={meta.get('energy')!r}, "
+                                 f"this buffer has energy={mine!r}")
         if meta["bytes"]:
             self._ensure(*meta["dims"])
             blob = np.fromfile(path, dtype=np.uint8)
@@ -192,12 +264,18 @@ class _RingState:
         if hasattr(self, "priorities") and "priorities" in meta:
             self.priorities.clear()
             self.priorities.extend(np.float32(p) for p in meta["priorities"])
+        if meta.get("prioritise") is not None and "prio_leaves" in meta and self._h is not None:
+            _ffi.check(lib.gcrl_her_set_head(self._h, int(meta["prio_head"])))     # the rows back at their slots, then the leaves
+            leaves = np.asarray(meta["prio_leaves"], dtype=np.uint32).view(np.float32)
+            _ffi.check(lib.gcrl_per_set_priorities(self._h, leaves.ctypes.data, leaves.size))
+            self.prio_counter = int(meta["prio_counter"])
 
 
 class HERBuffer(_RingState):
     def __init__(self, max_mem_len: int, max_eps_len: int, nenvs: int, threshold: float = 0.05,
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
-                 device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None):
+                 device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None,
+                 prioritise: str | None = None, energy: dict | None = None):
         # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
         # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
         # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
@@ -211,6 +289,12 @@ class HERBuffer(_RingState):
         # discounts this buffer's own sample() / gather_update(); an agent's update calls discount by the agent's gamma.  The values
         # are held here until the first push creates the ring.  Every refusal before any device work.
         self.n_step, self.gamma = _check_nstep("HERBuffer", n_step, gamma, relabel)
+        # prioritise="energy" (relabel="sample" only): an episode is drawn in proportion to the energy its achieved-goal trajectory
+        # gained, a row uniformly inside it (csrc/her_prio.hip; tests/her_energy_ref.py is the definition).  The leaves of a priority
+        # tree beside the ring are written once, by the flush; sample() / gather_update() without indices= and the update engine draw
+        # their rows from it.  A deliberate sampling bias with no importance correction.  None (default): nothing changes.
+        self.energy = _check_energy("HERBuffer", prioritise, energy, relabel)
+        self.prioritise = prioritise
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError("HERBuffer needs a HIP device: the replay ring lives in HBM and "
                                  "there is no CPU fallback")
@@ -271,6 +355,8 @@ class HERBuffer(_RingState):
             if self._dims != (S, A, G):
                 raise ValueError(f"transition dims {(S, A, G)} differ from the ring's {self._dims}")
             return
+        if self.prioritise is not None:               # refused before any device work
+            self.energy["axis"] = _energy_axis("HERBuffer", self.energy, G)
         kind, thr = _classify_reward(self.compute_reward, G, self.threshold)
         if self.relabel == "sample" and kind == 2:    # refused before any device work
             raise _ffi.GcrlError("HERBuffer: compute_reward: relabel='sample' computes the relabel rewards in the gather kernel and takes the "
@@ -284,6 +370,10 @@ class HERBuffer(_RingState):
         self._dims = (S, A, G)
         if self.n_step > 1:
             _ffi.check(lib.gcrl_her_set_nstep(self._h, self.n_step, self.gamma))
+        if self.prioritise is not None:
+            e = self.energy
+            ecfg = _ffi.EnergyConfig(potential=e["potential"], kinetic=e["kinetic"], axis=e["axis"], clip=e["clip"], alpha=e["alpha"], eps=e["eps"])
+            _ffi.check(lib.gcrl_her_prio_attach(self._h, C.byref(ecfg)))
         if kind == 2:
             self._install_reward_callback()
 
@@ -475,6 +565,41 @@ class HERBuffer(_RingState):
         ag = np.empty((n, G), np.float32); rem = np.empty(n, np.float32)
         _ffi.check(lib.gcrl_her_read_tails(self._h, first, n, ag.ctypes.data, rem.ctypes.data))
         return ag, rem
+
+    # ------------------------------------------------------------------ prioritise="energy": test and logging helpers
+    def _need_prio(self, what: str):
+        if self.prioritise is None:
+            raise _ffi.GcrlError(f"HERBuffer.{what}: prioritise: this buffer was built with prioritise=None and has no tree")
+        if self._h is None:
+            raise _ffi.GcrlError(f"HERBuffer.{what}: the ring is created by the first push")
+
+    def get_priorities(self) -> np.ndarray:
+        """The leaves in logical order (0 = oldest row), float32: p_ep / T of each row's episode (synchronises)."""
+        self._need_prio("get_priorities")
+        out = np.empty(len(self), np.float32)
+        if out.size:
+            _ffi.check(lib.gcrl_per_get_priorities(self._h, out.ctypes.data, out.size))
+        return out
+
+    def tree_levels(self):
+        """Every level of the tree as stored, leaves (by physical slot) first."""
+        self._need_prio("tree_levels")
+        out = []
+        for k in range(int(lib.gcrl_per_levels(self._h))):
+            a = np.empty(int(lib.gcrl_per_level_size(self._h, k)), np.float32)
+            _ffi.check(lib.gcrl_per_read_level(self._h, k, a.ctypes.data, a.size))
+            out.append(a)
+        return out
+
+    @property
+    def prio_counter(self) -> int:
+        """Rows drawn from the tree so far: the counter of its draw stream (0 before the ring exists)."""
+        return 0 if self._h is None else int(lib.gcrl_her_get_prio_counter(self._h))
+
+    @prio_counter.setter
+    def prio_counter(self, v: int):
+        self._need_prio("prio_counter")
+        _ffi.check(lib.gcrl_her_set_prio_counter(self._h, int(v)))
 
     @property
     def relabel_counter(self) -> int:

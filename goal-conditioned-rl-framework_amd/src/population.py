@@ -74,7 +74,10 @@ class _Population:
 
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
-                 relabel: str = "push", n_step: int = 1):
+                 relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None):
+        # prioritise: accepted only to be refused by name — the energy-prioritised draw (buffer.HERBuffer) is a single-agent mode
+        if prioritise is not None or energy is not None:
+            self._refuse("prioritise", f"populations (and their shared ring) do not draw from an energy tree, got prioritise={prioritise!r}")
         # relabel="sample": every member's ring (or the shared one) relabels at gather time (buffer.HERBuffer); such gathers have no
         # population launch, so merge_gather = True then reports no merged launch (gather_counts()).
         if relabel not in ("push", "sample"):

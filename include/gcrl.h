@@ -901,6 +901,39 @@ int gcrl_per_set_draw_counter(gcrl_her* h, int64_t counter);
 /* kernel launches the tree has issued so far (-1: no tree) */
 int64_t gcrl_per_launches(const gcrl_her* h);
 
+/* ---- Energy-prioritised replay draw of a GCRL_RELABEL_SAMPLE ring (csrc/her_prio.hip).
+ * The ring gets a priority tree of the layout above whose leaves are written ONCE, by the flush: every row of a flushed episode
+ * gets (E_traj + eps)^alpha / T, E_traj the clipped energy gains of the episode's achieved-goal trajectory (potential * ag[axis]
+ * + kinetic * |ag_i - ag_{i-1}|^2 per step, one fp32 rounding per operation).  An episode is thereby drawn in proportion to its
+ * energy and a row uniformly inside it.  Nothing feeds back from the loss, there are no importance-sampling weights: only the row
+ * indices a gather reads change.  Definition: tests/her_energy_ref.py, held bit for bit (alpha == 1; otherwise 1e-6 relative).
+ * The default constants (9.81, 312.5 = 0.5 / 0.04^2, axis 2, clip 0.5, alpha 1, eps 1e-3) are this project's choice.
+ * gcrl_her_prio_attach: GCRL_RELABEL_SAMPLE rings only (GCRL_ERR_STATE otherwise), before or after rows exist — rows already in
+ * the ring get the floor leaf eps^alpha (a zero-energy episode of one row, evaluated on the host) and the tree is rebuilt.
+ * Refused: a ring that already has a tree of either kind (GCRL_ERR_STATE), axis >= goal_dim, clip <= 0, eps <= 0, alpha < 0,
+ * a non-finite value, flush_len > 64 (GCRL_ERR_ARG).  gcrl_per_attach on such a ring stays refused; gcrl_per_draw / _update /
+ * _set_betas refuse an energy tree; gcrl_per_get / set_priorities, gcrl_per_read_level and gcrl_per_launches serve both kinds.
+ * With the tree attached, gcrl_her_sample and gcrl_her_gather_update called without indices draw their rows from it (the MT
+ * stream is not consumed), and so does the update engine for every agent kind and launch form; gcrl_her_append is refused. */
+typedef struct gcrl_energy_config {
+  float potential;   /* m * g */
+  float kinetic;     /* m / (2 dt^2) */
+  int32_t axis;      /* component of the achieved goal that is a height; < 0: no potential term */
+  float clip;        /* upper bound of one step's energy gain, > 0 */
+  float alpha;       /* >= 0 */
+  float eps;         /* > 0 */
+} gcrl_energy_config;
+enum { GCRL_PRIO_NONE = 0, GCRL_PRIO_ENERGY = 1 };
+int gcrl_her_prio_attach(gcrl_her* h, const gcrl_energy_config* cfg);
+int gcrl_her_prio_mode(const gcrl_her* h);
+/* `rows` draws (with replacement) -> idx_dev[rows], logical indices; row t is the ring's (prio counter + t)-th draw and the
+ * counter advances by `rows`: one call of n * B rows equals n calls of B.  One launch.  GCRL_ERR_STATE: no energy tree, or the
+ * ring was reloaded and its leaves not yet set (gcrl_per_set_priorities). */
+int gcrl_her_prio_draw(gcrl_her* h, int64_t rows, uint32_t* idx_dev, void* stream);
+/* rows ever drawn from the ring's energy tree (0: no such tree); saved and restored by the caller for a bitwise resume */
+uint64_t gcrl_her_get_prio_counter(const gcrl_her* h);
+int gcrl_her_set_prio_counter(gcrl_her* h, uint64_t counter);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);
