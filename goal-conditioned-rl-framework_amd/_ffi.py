@@ -112,6 +112,9 @@ PROTOTYPES = {
     "gcrl_her_get_nstep": (C.c_int, [_vp, C.POINTER(_f64)]),
     "gcrl_her_gather_update": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gcrl_her_read_tails": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "gcrl_her_create_goal": (_vp, [C.POINTER(HerConfig), _vp, C.c_int, C.c_int]),
+    "gcrl_her_goal_strategy": (C.c_int, [_vp]),
+    "gcrl_her_read_elapsed": (C.c_int, [_vp, _i64, _i64, _vp]),
     "gcrl_her_destroy": (None, [_vp]),
     "gcrl_her_len": (_i64, [_vp]),
     "gcrl_her_head": (_i64, [_vp]),

@@ -745,6 +745,8 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
       GCRL_RING_SAME(S, "state_dim"); GCRL_RING_SAME(A, "action_dim"); GCRL_RING_SAME(G, "goal_dim");
       if (s->relabel_mode != d->relabel_mode)   // (sample-time relabelling: the records carry tails the other mode's do not)
         return fail(GCRL_ERR_STATE, "gcrl_pop_clone: relabel: member %d's ring has relabel mode %d, member %d's %d", src[k], s->relabel_mode, dst[k], d->relabel_mode);
+      if (s->goal_strategy != d->goal_strategy)   // (the record widths differ, and a goal pick of one strategy reads tails the other's lack)
+        return fail(GCRL_ERR_STATE, "gcrl_pop_clone: goal_strategy: member %d's ring has goal strategy %d, member %d's %d", src[k], s->goal_strategy, dst[k], d->goal_strategy);
       GCRL_RING_SAME(RS, "record_floats"); GCRL_RING_SAME(RG, "staged_record_floats");
       GCRL_RING_SAME(cfg.nenvs, "nenvs"); GCRL_RING_SAME(cfg.flush_len, "flush_len"); GCRL_RING_SAME(cfg.k_future, "k_future");
 #undef GCRL_RING_SAME

@@ -336,6 +336,8 @@ namespace gcrl {
 
 int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
                             float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes) {
+  if (h->goal_strategy != GCRL_GOAL_FUTURE)   // final / episode: her_strategy.hip
+    return her_goal_gather_update(h, idx, ctr, g32, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes);
   if (h->n_step < 2 || h->n_step > kMaxN) return fail(GCRL_ERR_STATE, "her_gather_update: n_step: %d outside 2..%d for the n-step gather", h->n_step, kMaxN);
   GatherNstepArgs ga{h->ring, idx, h->last_gen, n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, ldx, sa, nsa, spa, r, d,
                      (const uint4*)cp_src, (uint4*)cp_dst, (int)(cp_bytes / 16), h->S, h->G, make_rule(h, ctr, g32)};
@@ -351,6 +353,7 @@ int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, floa
 
 int her_nstep_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                      float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st) {
+  if (h->goal_strategy != GCRL_GOAL_FUTURE) return her_goal_sample(h, idx_dev, ctr, g32, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st);
   if (h->n_step < 2 || h->n_step > kMaxN) return fail(GCRL_ERR_STATE, "gcrl_her_sample: n_step: %d outside 2..%d for the n-step gather", h->n_step, kMaxN);
   GatherNstepPubArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->G, h->SA4, h->S4, h->RS,
                         out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns, make_rule(h, ctr, g32)};

@@ -305,6 +305,7 @@ RelabelRule make_rule(const gcrl_her* h, uint64_t ctr) {
 namespace gcrl {
 
 int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipStream_t st, int64_t* rows_out) {
+  if (h->goal_strategy == GCRL_GOAL_EPISODE) return her_goal_flush(h, nep, envs, Ts, st, rows_out);   // records with `elapsed` (her_strategy.hip)
   const gcrl_her_config& c = h->cfg;
   if (nep < 1 || nep > kMaxEp) return fail(GCRL_ERR_ARG, "flush: %d episodes in one launch (1..%d)", nep, kMaxEp);
   FlushSampleArgs fa;
@@ -338,6 +339,8 @@ int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipS
 
 int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, int64_t n, float* sa, float* nsa, float* spa, int ldx,
                               float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes) {
+  if (h->goal_strategy != GCRL_GOAL_FUTURE)   // final / episode: her_strategy.hip
+    return her_goal_gather_update(h, idx, ctr, 0.f, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes);
   GatherRelArgs ga{h->ring, idx, h->last_gen, n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, ldx, sa, nsa, spa, r, d,
                    (const uint4*)cp_src, (uint4*)cp_dst, (int)(cp_bytes / 16), h->S, h->G, make_rule(h, ctr)};
   const int blocks = (int)((n + 63) / 64);
@@ -351,6 +354,7 @@ int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, in
 
 int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                        float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st) {
+  if (h->goal_strategy != GCRL_GOAL_FUTURE) return her_goal_sample(h, idx_dev, ctr, 0.f, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st);
   GatherRelPubArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->G, h->SA4, h->S4, h->RS,
                       out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns, make_rule(h, ctr)};
   const int blocks = (int)std::min<long long>((n + 15) / 16, 8192);

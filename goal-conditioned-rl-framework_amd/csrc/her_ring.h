@@ -29,6 +29,16 @@
 //     f       = 1 + hash_below(seed, K, 2c + 1, rem);   fut = phys + f (mod cap)
 // a relabelled row takes record fut's tail ag as the goal of s and of ns, its reward by her_flush_kernel's arithmetic from the two
 // tails, done = 0.  Restated in tests/her_relabel_ref.py, which is the definition.
+// Goal selection (goal_strategy; kernels in her_strategy.hip, definition tests/her_strategy_ref.py).  The rule above is
+// GCRL_GOAL_FUTURE.  A ring created with GCRL_GOAL_EPISODE carries a second tail word, [ag (G) | remaining | elapsed]: `elapsed`, one
+// float holding the integer i, so RS = roundup(RW+G+2, 16); it sits at tail index 2 + G + 1 <= 11 of the record from o_r on, so
+// the gathers' 12-float tails hold it for G <= 8.  A lone appended row has elapsed = 0.  Rings of the other strategies keep the
+// records above.  The INVARIANT, extended backwards: logical index 0 is the oldest live row and eviction is FIFO, so of the i rows
+// of its episode that precede a row of logical index j, exactly min(i, j) are alive, at physical slots
+// (phys - 1 .. phys - min(i, j)) mod cap — after a wrap, after load_state's re-laying at head 0, on a ring smaller than a flush.
+// The gathers clamp `elapsed` to [0, min(min(flush_len, cap) - 1, j)] before any address is formed and bring phys + o, o signed,
+// back into the ring by compare-and-subtract (o > 0) or compare-and-add (o < 0): every address stays inside the live ring
+// whatever a tail holds.  GCRL_GOAL_FINAL takes o = remaining; GCRL_GOAL_EPISODE draws o uniformly from [-back, rem] \ {0}.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -104,6 +114,7 @@ struct gcrl_her {
   gcrl_her_config cfg;
   int S, A, G, SA4, S4, RW, RS, RG;   // o_ns = SA4, o_r = SA4+S4, o_d = o_r+1, o_ag = RW
   int relabel_mode = 0;               // GCRL_RELABEL_*
+  int goal_strategy = 0;              // GCRL_GOAL_*: fixed at creation (GCRL_GOAL_EPISODE widens the record's tail)
   uint64_t relabel_ctr = 0;           // sample mode: rows ever gathered from this ring (the relabel stream's counter)
   int n_step = 1;                     // sample mode: rows folded into a gathered row's reward and done flag (her_nstep.hip); configuration, not state
   double nstep_gamma = 0.0;           // the discount of the ring's own gathers (gcrl_her_sample, gcrl_her_gather_update); the update engine passes the agent's
@@ -233,6 +244,15 @@ int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, floa
                             float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
 int her_nstep_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                      float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
+
+// a ring whose goal_strategy is GCRL_GOAL_FINAL or GCRL_GOAL_EPISODE (her_strategy.hip): the four entry points above hand over to
+// these — her_goal_flush for an EPISODE ring (a FINAL ring keeps her_flush_sample_kernel), the gathers for both, at every n_step
+// (g32 is not read at n_step == 1)
+int her_goal_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipStream_t st, int64_t* rows_out);
+int her_goal_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
+                           float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
+int her_goal_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
+                    float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
 
 // One her_gather_update call stated before it is issued (the update engine's begin_call plans it, gcrl_pop_update_n issues the
 // members' calls together).  `gen` is the ring's IdxGen as of the member's turn: members that share a ring each keep their own.

@@ -790,10 +790,17 @@ int gcrl_device_count(void) {
 
 gcrl_her* gcrl_her_create(const gcrl_her_config* cfg, gcrl_mt* rng) { return gcrl_her_create_relabel(cfg, rng, GCRL_RELABEL_PUSH); }
 
-gcrl_her* gcrl_her_create_relabel(const gcrl_her_config* cfg, gcrl_mt* rng, int mode) {
+gcrl_her* gcrl_her_create_relabel(const gcrl_her_config* cfg, gcrl_mt* rng, int mode) { return gcrl_her_create_goal(cfg, rng, mode, GCRL_GOAL_FUTURE); }
+
+gcrl_her* gcrl_her_create_goal(const gcrl_her_config* cfg, gcrl_mt* rng, int mode, int strategy) {
   auto bad = [](const char* m) -> gcrl_her* { gcrl::fail(GCRL_ERR_ARG, "gcrl_her_create: %s", m); return nullptr; };
   if (!cfg) return bad("null config");
   if (mode != GCRL_RELABEL_PUSH && mode != GCRL_RELABEL_SAMPLE) return bad("mode: GCRL_RELABEL_PUSH or GCRL_RELABEL_SAMPLE required");
+  if (strategy != GCRL_GOAL_FUTURE && strategy != GCRL_GOAL_FINAL && strategy != GCRL_GOAL_EPISODE)
+    return bad("goal_strategy: GCRL_GOAL_FUTURE, GCRL_GOAL_FINAL or GCRL_GOAL_EPISODE required");
+  if (strategy != GCRL_GOAL_FUTURE && mode != GCRL_RELABEL_SAMPLE)
+    return bad("goal_strategy: GCRL_GOAL_FINAL and GCRL_GOAL_EPISODE select the goal in the sample-time relabelling gather; a "
+               "GCRL_RELABEL_PUSH ring takes GCRL_GOAL_FUTURE only");
   if (mode == GCRL_RELABEL_SAMPLE && cfg->reward_kind != GCRL_REWARD_SPARSE && cfg->reward_kind != GCRL_REWARD_DENSE)
     return bad("compute_reward: sample-time relabelling (GCRL_RELABEL_SAMPLE) computes the relabel rewards in the gather kernel and takes the "
                "built-in sparse or dense reward only, not a host callback (GCRL_REWARD_HOST)");
@@ -815,7 +822,9 @@ gcrl_her* gcrl_her_create_relabel(const gcrl_her_config* cfg, gcrl_mt* rng, int 
   h->S4 = gcrl::round_up(h->S, 4);
   h->RW = h->SA4 + h->S4 + 2;
   h->relabel_mode = mode;
-  h->RS = gcrl::round_up(mode == GCRL_RELABEL_SAMPLE ? h->RW + h->G + 1 : h->RW, 16);   // sample mode: tail [ag | remaining] (her_ring.h)
+  h->goal_strategy = strategy;
+  // sample mode: tail [ag | remaining], and [ag | remaining | elapsed] on a GCRL_GOAL_EPISODE ring (her_ring.h)
+  h->RS = gcrl::round_up(mode == GCRL_RELABEL_SAMPLE ? h->RW + h->G + (strategy == GCRL_GOAL_EPISODE ? 2 : 1) : h->RW, 16);
   h->RG = gcrl::round_up(h->RW + h->G, 16);
   h->staged.assign(cfg->nenvs, 0);
   h->ag_mirror.assign((size_t)cfg->nenvs * cfg->flush_len * cfg->goal_dim, 0.f);
@@ -975,7 +984,7 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
   if (!next_on_device) std::memcpy(sa.ns_inl, next_state, sizeof(float) * h->S);
   hipLaunchKernelGGL(her_stage_kernel, dim3(1), dim3(64), 0, st, sa);
   GCRL_HIP(hipGetLastError());
-  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)    // a lone row has no later row: remaining = 0, never relabelled
+  if (h->relabel_mode == GCRL_RELABEL_SAMPLE)    // a lone row has no later or earlier row: remaining = 0 (and elapsed = 0), never relabelled
     GCRL_HIP(hipMemsetAsync(h->ring + (size_t)phys * h->RS + h->RW, 0, (size_t)(h->RS - h->RW) * sizeof(float), st));
   book.append(1);                              // deque(maxlen): at capacity the oldest row falls off
   h->head = book.head; h->len = book.len;
@@ -1267,8 +1276,11 @@ struct HerStateHeader {
 constexpr uint32_t kHerMagic = 0x52454847u;   // "GHER"
 // version 1: a ring in the default mode (the blob of before).  version 2: sample-time relabelling — the header is followed by
 // this record, the ring records are whole (tails included)
-struct HerStateRelabel { uint64_t relabel_ctr; int32_t relabel_mode, pad; };
+// version 3: sample-time relabelling with a goal strategy other than GCRL_GOAL_FUTURE — version 2's layout, the strategy in the
+// record's last word (a GCRL_GOAL_FUTURE ring keeps writing version 2, bit for bit)
+struct HerStateRelabel { uint64_t relabel_ctr; int32_t relabel_mode, goal_strategy; };
 size_t her_state_extra(int mode) { return mode == GCRL_RELABEL_SAMPLE ? sizeof(HerStateRelabel) : 0; }
+const char* goal_name(int s) { return s == GCRL_GOAL_FINAL ? "final" : s == GCRL_GOAL_EPISODE ? "episode" : "future"; }
 size_t her_state_bytes(const gcrl_her* h) {
   return sizeof(HerStateHeader) + her_state_extra(h->relabel_mode) + (size_t)h->cfg.nenvs * sizeof(int32_t) +
          ((size_t)h->cfg.nenvs * h->cfg.flush_len * h->RG + (size_t)h->len * h->RS) * sizeof(float);
@@ -1280,12 +1292,12 @@ int64_t gcrl_her_state_size(const gcrl_her* h) { return h ? (int64_t)her_state_b
 int gcrl_her_save_state(gcrl_her* h, void* dst_host, int64_t n) {
   GCRL_CHECK_ARG(h && dst_host && n == (int64_t)her_state_bytes(h), "gcrl_her_save_state: buffer must be gcrl_her_state_size() bytes");
   GCRL_HIP(hipDeviceSynchronize());
-  HerStateHeader hd{kHerMagic, h->relabel_mode == GCRL_RELABEL_SAMPLE ? 2u : 1u, h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
+  HerStateHeader hd{kHerMagic, h->relabel_mode == GCRL_RELABEL_SAMPLE ? (h->goal_strategy != GCRL_GOAL_FUTURE ? 3u : 2u) : 1u, h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
                     h->cfg.capacity, h->len, h->episodes_flushed, h->draws_done, h->mutation_epoch};
   char* o = (char*)dst_host;
   std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
   if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
-    const HerStateRelabel x{h->relabel_ctr, h->relabel_mode, 0};
+    const HerStateRelabel x{h->relabel_ctr, h->relabel_mode, h->goal_strategy};   // (GCRL_GOAL_FUTURE == 0: version 2's pad word)
     std::memcpy(o, &x, sizeof(x)); o += sizeof(x);
   }
   for (int e = 0; e < h->cfg.nenvs; ++e) { const int32_t v = h->staged[e]; std::memcpy(o, &v, sizeof(v)); o += sizeof(v); }
@@ -1303,12 +1315,22 @@ int gcrl_her_load_state(gcrl_her* h, const void* src_host, int64_t n) {
   GCRL_CHECK_ARG(h && src_host && n >= (int64_t)sizeof(HerStateHeader), "gcrl_her_load_state: null / short blob");
   HerStateHeader hd;
   std::memcpy(&hd, src_host, sizeof(hd));
-  GCRL_CHECK_ARG(hd.magic == kHerMagic && (hd.version == 1 || hd.version == 2), "gcrl_her_load_state: not a replay-ring state blob");
-  const int blob_mode = hd.version == 2 ? GCRL_RELABEL_SAMPLE : GCRL_RELABEL_PUSH;
+  GCRL_CHECK_ARG(hd.magic == kHerMagic && hd.version >= 1 && hd.version <= 3, "gcrl_her_load_state: not a replay-ring state blob");
+  const int blob_mode = hd.version >= 2 ? GCRL_RELABEL_SAMPLE : GCRL_RELABEL_PUSH;
   if (blob_mode != h->relabel_mode)
     return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_load_state: relabel: the state was saved by a ring with relabel=\"%s\", this ring has relabel=\"%s\"",
                       blob_mode == GCRL_RELABEL_SAMPLE ? "sample" : "push", h->relabel_mode == GCRL_RELABEL_SAMPLE ? "sample" : "push");
   const size_t extra = her_state_extra(blob_mode);
+  int blob_goal = GCRL_GOAL_FUTURE;
+  if (hd.version == 3) {
+    GCRL_CHECK_ARG(n >= (int64_t)(sizeof(hd) + sizeof(HerStateRelabel)), "gcrl_her_load_state: null / short blob");
+    HerStateRelabel x;
+    std::memcpy(&x, (const char*)src_host + sizeof(hd), sizeof(x));
+    blob_goal = x.goal_strategy;
+  }
+  if (blob_goal != h->goal_strategy)   // (before the shape test: the record widths of differing strategies differ)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_load_state: goal_strategy: the state was saved by a ring with goal_strategy=\"%s\", this ring has "
+                                      "goal_strategy=\"%s\"", goal_name(blob_goal), goal_name(h->goal_strategy));
   GCRL_CHECK_ARG(hd.S == h->S && hd.A == h->A && hd.G == h->G && hd.nenvs == h->cfg.nenvs && hd.flush_len == h->cfg.flush_len &&
                      hd.RS == h->RS && hd.RG == h->RG && hd.k_future == h->cfg.k_future,
                  "gcrl_her_load_state: the blob was saved by a ring of another shape");
@@ -1420,6 +1442,29 @@ int gcrl_her_read_tails(gcrl_her* h, int64_t first, int64_t n, float* ag, float*
     if (ag) std::memcpy(ag + (size_t)i * h->G, rec + h->RW, sizeof(float) * h->G);
     if (remaining) remaining[i] = rec[h->RW + h->G];
   }
+  return GCRL_OK;
+}
+
+int gcrl_her_goal_strategy(const gcrl_her* h) { return h ? h->goal_strategy : -1; }
+
+int gcrl_her_read_elapsed(gcrl_her* h, int64_t first, int64_t n, float* elapsed) {
+  GCRL_CHECK_ARG(h && elapsed, "gcrl_her_read_elapsed: null argument");
+  if (h->goal_strategy != GCRL_GOAL_EPISODE)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_read_elapsed: goal_strategy: only a ring created with GCRL_GOAL_EPISODE stores `elapsed`");
+  GCRL_CHECK_ARG(first >= 0 && n >= 0 && first + n <= h->len, "gcrl_her_read_elapsed: range [%lld,+%lld) outside len %lld", (long long)first, (long long)n, (long long)h->len);
+  if (n == 0) return GCRL_OK;
+  GCRL_HIP(hipDeviceSynchronize());
+  float* tmp = nullptr;
+  GCRL_HIP(hipMalloc((void**)&tmp, (size_t)n * h->RS * sizeof(float)));
+  long long total = n * h->RS;
+  hipLaunchKernelGGL(her_copy_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
+                     h->ring, (long long)h->head, (long long)h->cfg.capacity, h->RS, (long long)first, (long long)n, tmp);
+  std::vector<float> host((size_t)total);
+  hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(tmp);
+  GCRL_HIP(e);
+  for (int64_t i = 0; i < n; ++i) elapsed[i] = host[(size_t)i * h->RS + h->RW + h->G + 1];
   return GCRL_OK;
 }
 

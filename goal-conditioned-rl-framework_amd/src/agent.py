@@ -22,7 +22,7 @@ import torch
 
 from .. import _ffi
 from .._ffi import lib
-from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_nstep
+from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_goal_strategy, _check_nstep
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -187,7 +187,8 @@ class _EngineAgent:
                  use_graph: bool = True, pipeline: bool = True, sync_metrics: bool = False, rng: str = "python",
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
-                 n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, _member=None):
+                 n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
+                 _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -199,6 +200,9 @@ class _EngineAgent:
             raise _ffi.GcrlError(f"{type(self).__name__}: n_step: n_step={n_step!r} needs buffer_type 'HER' with relabel='sample', "
                                  f"got {config.buffer_type!r}")
         self.n_step = _check_nstep(type(self).__name__, n_step, config.gamma, relabel)[0]
+        # goal_strategy="final" | "episode" (relabel="sample"): which row of its episode a relabelled row takes its goal from
+        # (buffer.HERBuffer); "future", the default, changes nothing.
+        self.goal_strategy = _check_goal_strategy(type(self).__name__, goal_strategy, relabel, config.buffer_type)
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -240,7 +244,7 @@ class _EngineAgent:
             self.buffer = HERBuffer(config.max_len, config.max_eps_len, nenvs, k_future=config.k_future,
                                     rng=rng, seed=seed, device_index=device_index, relabel=relabel,
                                     n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None,
-                                    prioritise=prioritise, energy=energy)
+                                    prioritise=prioritise, energy=energy, goal_strategy=self.goal_strategy)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 

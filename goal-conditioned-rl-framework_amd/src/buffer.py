@@ -151,6 +151,21 @@ def _check_nstep(who: str, n_step, gamma, relabel: str):
     return n_step, (None if gamma is None else float(gamma))
 
 
+GOAL_STRATEGIES = {"future": 0, "final": 1, "episode": 2}    # include/gcrl.h GCRL_GOAL_*
+
+
+def _check_goal_strategy(who: str, goal_strategy, relabel: str, buffer_type: str = "HER") -> str:
+    """-> the strategy as the ring takes it, or a GcrlError that names goal_strategy; before any device work"""
+    if not isinstance(goal_strategy, str) or goal_strategy not in GOAL_STRATEGIES:
+        raise _ffi.GcrlError(f"{who}: goal_strategy: must be one of {sorted(GOAL_STRATEGIES)}, got {goal_strategy!r}")
+    if goal_strategy != "future" and buffer_type != "HER":
+        raise _ffi.GcrlError(f"{who}: goal_strategy: {goal_strategy!r} needs buffer_type 'HER' with relabel='sample', got {buffer_type!r}")
+    if goal_strategy != "future" and relabel != "sample":
+        raise _ffi.GcrlError(f"{who}: goal_strategy: {goal_strategy!r} needs relabel='sample' (the goal is selected by the relabelling gather), "
+                             f"got relabel={relabel!r}")
+    return goal_strategy
+
+
 PRIORITISE_MODES = (None, "energy")
 # prioritise="energy": the constants of the episode energy (tests/her_energy_ref.py is the definition).  The defaults are this
 # project's choice — m = 1: potential = m g = 9.81, kinetic = m / (2 dt^2) with dt = 0.04, axis 2 = the height of a 3-component goal
@@ -216,6 +231,7 @@ class _RingState:
         meta = dict(dims=self._dims, rng_mode=self.rng.mode, py_random=None, mt=None, bytes=0)
         meta["relabel"] = getattr(self, "relabel", "push")
         meta["prioritise"] = getattr(self, "prioritise", None)
+        meta["goal_strategy"] = getattr(self, "goal_strategy", "future")
         if self.rng.mode == "python":
             st = _pyrandom.getstate()
             meta["py_random"] = [st[0], list(st[1]), st[2]]
@@ -242,6 +258,10 @@ class _RingState:
         if meta.get("relabel", "push") != getattr(self, "relabel", "push"):    # refused before any device work
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: relabel: the state was saved with relabel={meta.get('relabel', 'push')!r}, "
                                  f"this buffer has relabel={getattr(self, 'relabel', 'push')!r}")
+        if meta.get("goal_strategy", "future") != getattr(self, "goal_strategy", "future"):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: goal_strategy: the state was saved with "
+                                 f"goal_strategy={meta.get('goal_strategy', 'future')!r}, this buffer has "
+                                 f"goal_strategy={getattr(self, 'goal_strategy', 'future')!r}")
         if meta.get("prioritise") != getattr(self, "prioritise", None):
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with prioritise={meta.get('prioritise')!r}, "
                                  f"this buffer has prioritise={getattr(self, 'prioritise', None)!r}")
@@ -275,7 +295,7 @@ class HERBuffer(_RingState):
     def __init__(self, max_mem_len: int, max_eps_len: int, nenvs: int, threshold: float = 0.05,
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
                  device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None,
-                 prioritise: str | None = None, energy: dict | None = None):
+                 prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future"):
         # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
         # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
         # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
@@ -295,6 +315,11 @@ class HERBuffer(_RingState):
         # their rows from it.  A deliberate sampling bias with no importance correction.  None (default): nothing changes.
         self.energy = _check_energy("HERBuffer", prioritise, energy, relabel)
         self.prioritise = prioritise
+        # goal_strategy (relabel="sample" only): which row of its episode a relabelled row takes its goal from — "future" (default:
+        # a later row, nothing changes), "final" (the episode's last row) or "episode" (any other live row of the episode, earlier ones
+        # included; the ring's records then carry `elapsed` beside `remaining`).  csrc/her_strategy.hip; tests/her_strategy_ref.py is
+        # the definition.  Fixed when the ring is created.
+        self.goal_strategy = _check_goal_strategy("HERBuffer", goal_strategy, relabel)
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError("HERBuffer needs a HIP device: the replay ring lives in HBM and "
                                  "there is no CPU fallback")
@@ -366,7 +391,11 @@ class HERBuffer(_RingState):
                              nenvs=self.nenvs, k_future=self.k_future, flush_len=FLUSH_LEN,
                              reward_kind=kind, reward_threshold=thr, device=self.device_index,
                              rng_mode=1 if self.rng.mode == "device" else 0, seed=self.rng.seed_value)
-        self._h = _ffi.check_ptr(lib.gcrl_her_create_relabel(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel]), "gcrl_her_create")
+        if self.goal_strategy == "future":
+            self._h = _ffi.check_ptr(lib.gcrl_her_create_relabel(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel]), "gcrl_her_create")
+        else:
+            self._h = _ffi.check_ptr(lib.gcrl_her_create_goal(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel],
+                                                              GOAL_STRATEGIES[self.goal_strategy]), "gcrl_her_create")
         self._dims = (S, A, G)
         if self.n_step > 1:
             _ffi.check(lib.gcrl_her_set_nstep(self._h, self.n_step, self.gamma))
@@ -565,6 +594,17 @@ class HERBuffer(_RingState):
         ag = np.empty((n, G), np.float32); rem = np.empty(n, np.float32)
         _ffi.check(lib.gcrl_her_read_tails(self._h, first, n, ag.ctypes.data, rem.ctypes.data))
         return ag, rem
+
+    def elapsed(self, first: int = 0, count: int | None = None):
+        """goal_strategy="episode": the `elapsed` word of ring rows in logical order — [n], the rows of its episode before each row."""
+        if self.goal_strategy != "episode":
+            raise _ffi.GcrlError(f"HERBuffer.elapsed: goal_strategy: only an 'episode' ring stores it, this buffer has {self.goal_strategy!r}")
+        if self._h is None:
+            raise _ffi.GcrlError("HERBuffer.elapsed: the ring has no rows yet")
+        n = len(self) - first if count is None else count
+        el = np.empty(n, np.float32)
+        _ffi.check(lib.gcrl_her_read_elapsed(self._h, first, n, el.ctypes.data))
+        return el
 
     # ------------------------------------------------------------------ prioritise="energy": test and logging helpers
     def _need_prio(self, what: str):

@@ -21,7 +21,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import lib
 from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
-from .buffer import HERBuffer, MTStream, _check_nstep
+from .buffer import HERBuffer, MTStream, _check_goal_strategy, _check_nstep
 
 MAX_MEMBERS = 16
 MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
@@ -74,7 +74,8 @@ class _Population:
 
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
-                 relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None):
+                 relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None,
+                 goal_strategy: str = "future"):
         # prioritise: accepted only to be refused by name — the energy-prioritised draw (buffer.HERBuffer) is a single-agent mode
         if prioritise is not None or energy is not None:
             self._refuse("prioritise", f"populations (and their shared ring) do not draw from an energy tree, got prioritise={prioritise!r}")
@@ -84,6 +85,9 @@ class _Population:
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
         self.relabel = relabel
         configs = list(configs)
+        # goal_strategy: passed through to every member's ring (or the shared one); their sample-mode gathers stay member by member
+        for c in configs or [None]:
+            self.goal_strategy = _check_goal_strategy(type(self).__name__, goal_strategy, relabel, getattr(c, "buffer_type", "HER"))
         # n_step=N: every member's ring (or the shared one) gathers n-step windows; each member's update calls discount by its own gamma
         if n_step != 1:
             for i, c in enumerate(configs):
@@ -120,7 +124,7 @@ class _Population:
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
             self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index, relabel=relabel,
-                                           n_step=self.n_step, _member=lambda cfg, i=i: (pop, pop.member(i))))
+                                           n_step=self.n_step, goal_strategy=self.goal_strategy, _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
         self._merge_gather = False
         if P >= self.MERGE_GATHER_FROM:
@@ -132,6 +136,7 @@ class _Population:
             self.nenvs = int(nenvs)
             self.buffer = HERBuffer(c0.max_len, c0.max_eps_len, int(nenvs) * P, k_future=c0.k_future, rng=rng, seed=seeds[0],
                                     device_index=device_index, relabel=relabel, n_step=self.n_step,
+                                    goal_strategy=self.goal_strategy,
                                     gamma=c0.gamma if self.n_step > 1 else None)   # (the ring's own gathers; a member's calls use the member's gamma)
             for m in self.members:
                 m.buffer = self.buffer
@@ -419,6 +424,10 @@ class _Population:
                 if ra != rb:
                     self._refuse("relabel", f"member {s}'s ring has relabel={ra!r}, member {d}'s relabel={rb!r}: records of one mode do not "
                                             "fit a ring of the other (copy_ring=True)")
+                ga, gb = getattr(ms[s].buffer, "goal_strategy", "future"), getattr(ms[d].buffer, "goal_strategy", "future")
+                if ga != gb:
+                    self._refuse("goal_strategy", f"member {s}'s ring has goal_strategy={ga!r}, member {d}'s goal_strategy={gb!r}: their "
+                                                  "record widths differ (copy_ring=True)")
                 ms[d].buffer._ensure(*ms[s].buffer._dims)
             rings = (C.c_void_p * P)(*[m.buffer.handle for m in ms])
         src = (C.c_int32 * n)(*[s for s, _ in pairs])

@@ -144,6 +144,18 @@ int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter);
  * which may be NULL), -1 for a null handle. */
 int gcrl_her_set_nstep(gcrl_her* h, int n_step, double gamma);
 int gcrl_her_get_nstep(const gcrl_her* h, double* gamma);
+/* Goal selection of a GCRL_RELABEL_SAMPLE ring (csrc/her_strategy.hip; tests/her_strategy_ref.py is the definition):
+ * WHICH row of its episode a relabelled row takes its goal from.  GCRL_GOAL_FUTURE (what gcrl_her_create_relabel makes): a uniformly
+ * chosen later row.  GCRL_GOAL_FINAL: the episode's last row (an episode's last row itself is never relabelled).  GCRL_GOAL_EPISODE:
+ * a uniformly chosen OTHER live row of the episode, earlier ones included; its records carry a second tail word,
+ * [achieved goal | remaining | elapsed], so the record width differs and the strategy is fixed at creation.  The relabel decision
+ * (share k_future / (k_future + 1)), the counter and n-step windows are those of GCRL_GOAL_FUTURE for every strategy.
+ * Refused with GCRL_ERR_ARG, naming goal_strategy: an unknown strategy; FINAL or EPISODE on a GCRL_RELABEL_PUSH ring.  A FUTURE ring
+ * writes the state blobs of before; another strategy's blob carries the strategy, and gcrl_her_load_state across differing
+ * strategies is refused by that name, as is gcrl_pop_clone between such rings. */
+enum { GCRL_GOAL_FUTURE = 0, GCRL_GOAL_FINAL = 1, GCRL_GOAL_EPISODE = 2 };
+gcrl_her* gcrl_her_create_goal(const gcrl_her_config* cfg, gcrl_mt* rng, int mode, int strategy);
+int gcrl_her_goal_strategy(const gcrl_her* h);   /* -1 for a null handle */
 void gcrl_her_destroy(gcrl_her* h);
 /* compute_reward for GCRL_REWARD_HOST rings: out[i] = compute_reward(achieved[i], goal[i], {}) for n pairs of goal_dim floats
  * (row-major), in the reference's call order (src/buffer.py:151-166: step-major, relabel-minor).  Returns 0, or non-zero to
@@ -238,6 +250,9 @@ int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, 
 /* Test/state: the tails of `n` rows of a GCRL_RELABEL_SAMPLE ring from logical index `first`: ag_host[n][goal_dim],
  * remaining_host[n] (either may be NULL).  Synchronises the device. */
 int gcrl_her_read_tails(gcrl_her* h, int64_t first, int64_t n, float* ag_host, float* remaining_host);
+/* The same for the `elapsed` word of a GCRL_GOAL_EPISODE ring: elapsed_host[n], the number of rows of its episode that precede each
+ * row.  GCRL_ERR_STATE, naming goal_strategy, on a ring whose records have no such word. */
+int gcrl_her_read_elapsed(gcrl_her* h, int64_t first, int64_t n, float* elapsed_host);
 
 /* ------------------------------------------------------------------------------------------
  * Update engine.  Replaces DDPG / TD3Agent / SACAgent / TQCAgent .update() and what it calls

@@ -5,12 +5,13 @@
 
 --run fills rings of 1e6 records at PickAndPlace dims (S 23, A 4, G 3; k_future 4, rng="device": no host draw, no index
 upload) — one per relabel mode, and for the sample mode one more per n_step in NSTEPS (gamma 0.98; n_step = 1 is the sample-mode
-ring itself) — and then, alternating the rings, issues the update engine's gather (HERBuffer.gather_update) at 9 216 and 77 824
-rows, and the flush of one T = 50 episode (push_episode; the two modes only: n_step does not reach the flush).  Nothing is timed
+ring itself), and one per goal strategy in GOALS at n_step 1 and at GOAL_NSTEP (csrc/her_strategy.hip) — and then, alternating the rings, issues the update engine's gather (HERBuffer.gather_update) at 9 216 and 77 824
+rows, and the flush of one T = 50 episode (push_episode; the two modes and the `episode` ring, whose flush stamps `elapsed`:
+n_step does not reach the flush, and a `final` ring launches the sample mode's).  Nothing is timed
 here: the kernel trace is.
 --parse reads the trace and prints, per kernel and launch size, the number of launches, the median and the range of the kernel
 durations — the launches after the warm-up ones.  The n-step rings launch one kernel at one grid size: their launches alternate in
-NSTEPS order and are told apart by that.  No GPU: --run fails; it does not fall back."""
+NSTEPS order and are told apart by that; so do the rings of the goal strategies, in GOALS order.  No GPU: --run fails; it does not fall back."""
 import argparse
 import csv
 import glob
@@ -26,6 +27,8 @@ CAP = 1_000_000
 SIZES = ((256, 36), (256, 304))      # 9 216 and 77 824 rows: a trainer cycle's head-sized and main gather
 WARM, ITERS = 10, 60
 NSTEPS = (3, 8)
+GOALS = ("final", "episode")
+GOAL_NSTEP = 3
 
 
 def run():
@@ -52,20 +55,30 @@ def run():
             buf.push_episode(0, *ep)
         assert len(buf) == CAP
         rings[f"sample_n{N}"] = buf
+    for N in (1, GOAL_NSTEP):
+        for goal in GOALS:
+            kw = dict(n_step=N, gamma=0.98) if N > 1 else {}
+            buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel="sample", goal_strategy=goal, **kw)
+            buf.compute_reward = her_oracle.sparse_reward
+            for _ in range(CAP // 50 + 2):
+                buf.push_episode(0, *ep)
+            assert len(buf) == CAP
+            rings[goal if N == 1 else f"{goal}_n{N}"] = buf
     import torch
     torch.cuda.synchronize()
     for B, M in SIZES:
         for _ in range(WARM + ITERS):
-            for mode in rings:                              # push, sample (N = 1), then the n-step rings in NSTEPS order
+            for mode in rings:                              # push, sample (N = 1), the n-step rings in NSTEPS order, the goal rings in GOALS order
                 rings[mode].gather_update(B, M)
     for _ in range(WARM + ITERS):
-        for mode in ("push", "sample"):
+        for mode in ("push", "sample", "episode"):
             rings[mode].push_episode(1, *ep)
     torch.cuda.synchronize()
     print("relabel_bench: done")
 
 
-NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_gather_nstep_kernel", "her_flush_kernel", "her_flush_sample_kernel")
+NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_gather_nstep_kernel", "her_gather_goal_kernel", "her_gather_goal_nstep_kernel",
+         "her_flush_kernel", "her_flush_sample_kernel", "her_flush_episode_kernel")
 
 
 def parse(d):
@@ -87,12 +100,17 @@ def parse(d):
             del rows[key, grid]
             for i, N in enumerate(NSTEPS):
                 rows[f"{key} N={N}", grid] = v[i::len(NSTEPS)]
+        if key in ("her_gather_goal_kernel", "her_gather_goal_nstep_kernel"):     # launches alternate between the strategies' rings
+            v.sort()
+            del rows[key, grid]
+            for i, goal in enumerate(GOALS):
+                rows[f"{key} {goal}" + (f" N={GOAL_NSTEP}" if "nstep" in key else ""), grid] = v[i::len(GOALS)]
     for (key, grid), v in sorted(rows.items()):
         v.sort()
         if len(v) < ITERS:           # the fill's flushes have their own grid sizes only in push mode; keep the timed tail of each
             continue
         dur = [x[1] / 1e3 for x in v[-ITERS:]]
-        print(f"{key:30s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
+        print(f"{key:42s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
               f"range {min(dur):7.2f} .. {max(dur):7.2f} us")
 
 
