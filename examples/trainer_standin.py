@@ -69,11 +69,13 @@ class PointReachVecEnv:
 
 def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
           seed=0, verbose=True, per_env_push=False, fused=False, relabel="push", n_step=1, prioritise=None,
-          goal_strategy="future"):
+          goal_strategy="future", normalize="push"):
     import gcrl_amd
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
         RunningNormalizer = DeviceRunningNormalizer
+    if normalize == "sample" and not fused:
+        raise SystemExit("--normalize sample stores raw rows through the fused process_step and needs --fused (device normalisers)")
     from gcrl_amd.src.synthetic import agent_config as make_config   # hyper-parameter container with the YAML field names
 
     np.random.seed(seed)
@@ -85,7 +87,8 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
         cfg.max_len //= 1 + cfg.k_future
     cls = dict(DDPG=gcrl_amd.DDPG, TD3=gcrl_amd.TD3Agent, SAC=gcrl_amd.SACAgent, TQC=gcrl_amd.TQCAgent)[agent_name]
     agent = cls(env.obs_dim + env.goal_dim, env.ac_dim, cfg, None, nenvs=num_envs, gradient_step=gradient_step,
-                rng="engine", seed=seed, relabel=relabel, n_step=n_step, prioritise=prioritise, goal_strategy=goal_strategy)
+                rng="engine", seed=seed, relabel=relabel, n_step=n_step, prioritise=prioritise, goal_strategy=goal_strategy,
+                normalize=normalize)
     # what GoalEnvHER.__init__ injects (src/env.py:93-105)
     agent.buffer.obs_normalizer = RunningNormalizer(env.obs_dim)
     agent.buffer.dg_normalizer = RunningNormalizer(env.goal_dim)
@@ -173,9 +176,13 @@ if __name__ == "__main__":
                     help="with --relabel sample: draw episodes in proportion to the energy their achieved-goal trajectory gained")
     ap.add_argument("--goal-strategy", default="future", choices=["future", "final", "episode"],
                     help="with --relabel sample: a relabelled row's goal comes from a later row of its episode, its last row, or any other row of it")
+    ap.add_argument("--normalize", default="push", choices=["push", "sample"],
+                    help="push: rows are stored normalised with the statistics of the moment of the push (the reference's form); sample (with "
+                         "--fused): rows are stored raw and every gathered batch is normalised with the statistics of that moment")
     args = ap.parse_args()
     out = train(args.agent, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, per_env_push=args.per_env_push, fused=args.fused,
-                relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy)
+                relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy,
+                normalize=args.normalize)
     tail = out["success_per_cycle"][-10:]
     print(f"{args.agent}: success over the last 10 cycles {np.mean(tail):.2f}; {out['env_steps']} env steps "
           f"({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} gradient steps "

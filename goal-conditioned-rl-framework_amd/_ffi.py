@@ -115,6 +115,10 @@ PROTOTYPES = {
     "gcrl_her_create_goal": (_vp, [C.POINTER(HerConfig), _vp, C.c_int, C.c_int]),
     "gcrl_her_goal_strategy": (C.c_int, [_vp]),
     "gcrl_her_read_elapsed": (C.c_int, [_vp, _i64, _i64, _vp]),
+    "gcrl_her_set_normalize": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+    "gcrl_her_require_normalize": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "gcrl_her_normalize_mode": (C.c_int, [_vp]),
+    "gcrl_normalizer_normalize_states": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "gcrl_her_destroy": (None, [_vp]),
     "gcrl_her_len": (_i64, [_vp]),
     "gcrl_her_head": (_i64, [_vp]),

@@ -1181,6 +1181,10 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     GCRL_CHECK_ARG(her->S == a->S && her->A == a->A, "update: ring dims (S=%d,A=%d) differ from the agent's (S=%d,A=%d)", her->S, her->A, a->S, a->A);
     if (her->len < a->B) return fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
   }
+  if (!injected && her_norm_on(her)) {   // normalize = "sample": refused before a ticket, slot or plan is consumed
+    if (a->xchg) return fail(GCRL_ERR_STATE, "update: normalize: a ring that stores raw rows (normalize=\"sample\") does not feed an agent under a gradient exchange");
+    TRY(her_norm_check(her, "update"));
+  }
   const bool prio = !injected && !(in && in->idx_host) && her_prio_on(her);   // a third index source beside the MT upload and the in-kernel IdxGen
   if (prio) {   // refused before a ticket, slot or plan is consumed
     if (a->xchg) return fail(GCRL_ERR_STATE, "update: prioritise: a ring with an energy tree does not feed an agent under a gradient exchange");

@@ -747,6 +747,8 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
         return fail(GCRL_ERR_STATE, "gcrl_pop_clone: relabel: member %d's ring has relabel mode %d, member %d's %d", src[k], s->relabel_mode, dst[k], d->relabel_mode);
       if (s->goal_strategy != d->goal_strategy)   // (the record widths differ, and a goal pick of one strategy reads tails the other's lack)
         return fail(GCRL_ERR_STATE, "gcrl_pop_clone: goal_strategy: member %d's ring has goal strategy %d, member %d's %d", src[k], s->goal_strategy, dst[k], d->goal_strategy);
+      if (s->normalize_mode != d->normalize_mode)   // (raw rows in a ring whose gathers do not normalise, or the reverse)
+        return fail(GCRL_ERR_STATE, "gcrl_pop_clone: normalize: member %d's ring has normalize mode %d, member %d's %d", src[k], s->normalize_mode, dst[k], d->normalize_mode);
       GCRL_RING_SAME(RS, "record_floats"); GCRL_RING_SAME(RG, "staged_record_floats");
       GCRL_RING_SAME(cfg.nenvs, "nenvs"); GCRL_RING_SAME(cfg.flush_len, "flush_len"); GCRL_RING_SAME(cfg.k_future, "k_future");
 #undef GCRL_RING_SAME

@@ -109,6 +109,7 @@ __host__ __device__ inline uint32_t idxgen_at(const IdxGen& g, long long row) {
 }  // namespace gcrl
 
 struct gcrl_per_tree;
+struct gcrl_normalizer;
 
 struct gcrl_her {
   gcrl_her_config cfg;
@@ -132,6 +133,11 @@ struct gcrl_her {
   bool idx_on_device = true;      // false: no index array was uploaded (device-RNG mode)
   uint64_t mutation_epoch = 0;    // bumped by every flush
   uint64_t rows_pushed = 0;       // rows ever appended (>= len): what the priority tree measures its pending pushes against
+  int normalize_mode = 0;         // GCRL_NORMALIZE_*: SAMPLE = the records are raw, the gathers' batches are normalised behind the gather (her_norm.hip)
+  gcrl_normalizer* nz_obs = nullptr;   // borrowed: the observation normaliser of columns [0, norm_D) of a state (null: left raw)
+  gcrl_normalizer* nz_dg = nullptr;    // borrowed: the goal normaliser of columns [norm_D, S) (null: left raw)
+  int norm_D = 0;
+  int norm_need = 0;              // bit 0 / 1: a gather needs nz_obs / nz_dg bound (gcrl_her_require_normalize)
   gcrl_per_tree* per = nullptr;   // the ring's priority tree (per_tree.h), or null: TD priorities (per_tree.hip) or episode energies (her_prio.hip), by its source tag
 
   // index upload: pinned host slots -> idx_dev
@@ -253,6 +259,29 @@ int her_goal_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float
                            float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
 int her_goal_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                     float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
+
+// sample-time normalisation (her_norm.hip).  her_norm_on: the ring is raw.  her_norm_check: GCRL_ERR_STATE naming `normalize` when a
+// normaliser the ring's gathers need is not bound — callers ask before a ticket or a counter is consumed.  her_norm_rows: the
+// in-place pass over one gather's sa / nsa / spa (spa may be null; n rows of stride ldx), one launch.  her_norm_dense: the same for
+// the public sample()'s out_s / out_ns.  Both are no-ops on a ring in the default mode.
+bool her_norm_on(const gcrl_her* h);
+int her_norm_check(const gcrl_her* h, const char* who);
+int her_norm_rows(const gcrl_her* h, int64_t n, float* sa, float* nsa, float* spa, int ldx, hipStream_t st);
+int her_norm_dense(const gcrl_her* h, int64_t n, float* out_s, int ld_s, float* out_ns, int ld_ns, hipStream_t st);
+// the raw-store form of the fused process_step launch (her_norm.hip): her_process_step_kernel's two statistics updates, then the
+// step's rows and achieved goals staged as they came.  ProcRawArgs is her_ring.hip's ProcArgs, field for field.
+struct ProcRawArgs {
+  float* stage; const float* raw; const float* pay;
+  double* mean; double* var; double* count; double clip;
+  double* gmean; double* gvar; double* gcount; double gclip;
+  int update, gupdate, n, env0, flush_len, D, S, A, G, SA4, S4, RG;
+  int mode, gmode;
+};
+constexpr int kProcRawInlineFloats = 896;
+// data != null: the rows and the payload travel inside the kernel arguments (floats <= kProcRawInlineFloats of them, the payload
+// from data[raw_floats] on); otherwise p.raw / p.pay
+int her_process_step_raw(const ProcRawArgs& p, const float* data, int raw_floats, int floats, hipStream_t st);
+int her_process_step_raw_pop(const ProcRawArgs* tab_dev, const float* data_dev, int stride, int raw_floats, int members, hipStream_t st);
 
 // One her_gather_update call stated before it is issued (the update engine's begin_call plans it, gcrl_pop_update_n issues the
 // members' calls together).  `gen` is the ring's IdxGen as of the member's turn: members that share a ring each keep their own.

@@ -715,6 +715,7 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
                       const uint64_t* relabel_ctr, const double* gamma) {
   if (cp_bytes % 16 != 0 || (cp_bytes && (!cp_src || !cp_dst))) return fail(GCRL_ERR_ARG, "her_gather_update: bad side copy (%zu bytes)", cp_bytes);
   if (ldx != h->SA4) return fail(GCRL_ERR_ARG, "her_gather_update: batch row stride %d != roundup(S+A,4) = %d", ldx, h->SA4);
+  if (int rc = her_norm_check(h, "her_gather_update")) return rc;   // (a raw ring without its normalisers: before the counter moves)
   if (int rc = prof_begin(h, st)) return rc;
   if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
     uint64_t ctr = h->relabel_ctr;
@@ -724,7 +725,8 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
       const float g32 = (float)(gamma ? *gamma : h->nstep_gamma);
       if (int rc = her_nstep_gather_update(h, idx_dev, ctr, g32, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
     } else if (int rc = her_relabel_gather_update(h, idx_dev, ctr, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
-    return prof_end(h, st, n);
+    if (int rc = prof_end(h, st, n)) return rc;
+    return her_norm_rows(h, n, sa, nsa, spa, ldx, st);   // normalize = "sample": the in-place pass behind the gather (her_norm.hip)
   }
   GatherUpdArgs ga{h->ring, idx_dev, h->last_gen, n, h->head, h->cfg.capacity, h->SA4, h->S4, h->RS, ldx, sa, nsa, spa, r, d,
                    (const uint4*)cp_src, (uint4*)cp_dst, (int)(cp_bytes / 16)};
@@ -733,7 +735,8 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
   if (cp_bytes) hipLaunchKernelGGL(her_gather_update_kernel<true>, dim3(blocks), dim3(256), lds, st, ga);
   else hipLaunchKernelGGL(her_gather_update_kernel<false>, dim3(blocks), dim3(256), lds, st, ga);
   GCRL_HIP(hipGetLastError());
-  return prof_end(h, st, n);
+  if (int rc = prof_end(h, st, n)) return rc;
+  return her_norm_rows(h, n, sa, nsa, spa, ldx, st);
 }
 
 int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merged) {
@@ -747,6 +750,7 @@ int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merg
     // one x extent and one LDS tile for all: equal record layouts; a ring that times its gather launches keeps its own launch
     one = one && !g.h->prof && g.h->SA4 == c[0].h->SA4 && g.h->S4 == c[0].h->S4 && g.h->RS == c[0].h->RS;
     one = one && g.h->relabel_mode != GCRL_RELABEL_SAMPLE;   // sample-time relabelling has no merged launch
+    if (int rc = her_norm_check(g.h, "her_gather_update_pop")) return rc;
   }
   if (!one) {
     for (int i = 0; i < P; ++i) {
@@ -775,6 +779,8 @@ int her_gather_update_pop(const GatherCall* c, int P, hipStream_t st, bool* merg
   else hipLaunchKernelGGL(her_gather_update_pop_kernel<false>, grid, dim3(256), lds, st, pa);
   GCRL_HIP(hipGetLastError());
   if (merged) *merged = true;
+  for (int i = 0; i < P; ++i)   // raw rings: one pass per member behind the merged launch, in member order (members sharing a ring share its normalisers)
+    if (int rc = her_norm_rows(c[i].h, c[i].n, c[i].sa, c[i].nsa, c[i].spa, c[i].ldx, st)) return rc;
   return GCRL_OK;
 }
 
@@ -967,6 +973,8 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
   GCRL_CHECK_ARG(h && state && action_host && next_state, "gcrl_her_append: null argument");
   if ((!state_on_device || !next_on_device) && h->S > kMaxInline)
     return gcrl::fail(GCRL_ERR_ARG, "gcrl_her_append: host-pointer states support state_dim <= %d", kMaxInline);
+  if (gcrl::her_norm_on(h))
+    return gcrl::fail(GCRL_ERR_ARG, "gcrl_her_append: normalize: a ring marked raw (normalize=\"sample\") takes episodes through the HER entries, not lone rows");
   if (gcrl::her_prio_on(h))
     return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_append: prioritise: a ring with an energy tree takes whole episodes (a lone row has no trajectory)");
   hipStream_t st = h->pick(stream);
@@ -1115,7 +1123,12 @@ int64_t gcrl_her_process_step_g(gcrl_her* h, gcrl_normalizer* nz_obs, int update
   }
   pa.n = n; pa.env0 = env0; pa.flush_len = h->cfg.flush_len; pa.D = D; pa.S = h->S; pa.A = h->A; pa.G = G;
   pa.SA4 = h->SA4; pa.S4 = h->S4; pa.RG = h->RG;
-  if (inl) hipLaunchKernelGGL(her_process_step_inline_kernel, dim3(1), dim3(256), 0, st, qi);
+  if (gcrl::her_norm_on(h)) {   // normalize = "sample": the raw-store form (her_norm.hip) — the same two updates, the rows staged as they came
+    gcrl::ProcRawArgs ra;
+    static_assert(sizeof(ra) == sizeof(pa), "ProcRawArgs is ProcArgs field for field");
+    std::memcpy(&ra, &pa, sizeof(ra));
+    if (int rc = gcrl::her_process_step_raw(ra, inl ? qi.data : nullptr, (int)raw, (int)need, st)) return rc;
+  } else if (inl) hipLaunchKernelGGL(her_process_step_inline_kernel, dim3(1), dim3(256), 0, st, qi);
   else hipLaunchKernelGGL(her_process_step_kernel, dim3(1), dim3(256), 0, st, pa);
   GCRL_HIP(hipGetLastError());
   if (pa.update) gcrl::normalizer_updated(nz_obs);
@@ -1161,6 +1174,7 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
   GCRL_CHECK_ARG(h && out_s && out_a && out_r && out_ns && out_d, "gcrl_her_sample: null output");
   GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_sample: B and M must be >= 1");
   GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample: row stride smaller than the row");
+  if (int rc = gcrl::her_norm_check(h, "gcrl_her_sample")) return rc;
   hipStream_t st = h->pick(stream);
   const uint32_t* host_copy = nullptr;
   if (!idx_host && gcrl::her_prio_on(h)) {   // prioritise = "energy": the tree draws the rows
@@ -1178,7 +1192,8 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
     if (h->n_step > 1) {
       if (int rc = gcrl::her_nstep_sample(h, idx, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     } else if (int rc = gcrl::her_relabel_sample(h, idx, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
-    return prof_end(h, st, n);
+    if (int rc = prof_end(h, st, n)) return rc;
+    return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
   }
   GatherArgs ga{h->ring, h->idx_on_device ? h->idx_dev : nullptr, h->last_gen, n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
                 out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns};
@@ -1192,7 +1207,8 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
     hipLaunchKernelGGL(her_gather_wide_kernel<kUnroll>, dim3(blocks), dim3(256), 0, st, ga);
   }
   GCRL_HIP(hipGetLastError());
-  return prof_end(h, st, n);
+  if (int rc = prof_end(h, st, n)) return rc;
+  return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
 }
 
 int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* out_s, int ld_s, float* out_a, int ld_a, float* out_r,
@@ -1201,6 +1217,7 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
   GCRL_CHECK_ARG(n >= 1, "gcrl_her_sample_dev: n must be >= 1");
   GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample_dev: row stride smaller than the row");
   if (h->len < 1) return gcrl::fail(GCRL_ERR_NOT_ENOUGH, "[ERROR] Not enough in buffer to sample");
+  if (int rc = gcrl::her_norm_check(h, "gcrl_her_sample_dev")) return rc;
   hipStream_t st = h->pick(stream);
   if (h->relabel_mode == GCRL_RELABEL_SAMPLE) {
     if (int rc = prof_begin(h, st)) return rc;
@@ -1209,7 +1226,8 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
     if (h->n_step > 1) {
       if (int rc = gcrl::her_nstep_sample(h, idx_dev, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     } else if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
-    return prof_end(h, st, n);
+    if (int rc = prof_end(h, st, n)) return rc;
+    return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
   }
   GatherArgs ga{h->ring, idx_dev, h->last_gen, (long long)n, h->head, h->cfg.capacity, h->S, h->A, h->SA4, h->S4, h->RS,
                 out_s, out_a, out_r, out_ns, out_d, ld_s, ld_a, ld_ns};
@@ -1223,7 +1241,8 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
     hipLaunchKernelGGL(her_gather_wide_kernel<kUnroll>, dim3(blocks), dim3(256), 0, st, ga);
   }
   GCRL_HIP(hipGetLastError());
-  return prof_end(h, st, n);
+  if (int rc = prof_end(h, st, n)) return rc;
+  return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
 }
 
 int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* sa, float* nsa, float* spa, int ldx, float* r, float* d,
@@ -1231,6 +1250,7 @@ int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, 
   GCRL_CHECK_ARG(h && sa && nsa && r && d, "gcrl_her_gather_update: null output");
   GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_gather_update: B and M must be >= 1");
   GCRL_CHECK_ARG(side_bytes >= 0, "gcrl_her_gather_update: side_bytes %lld", (long long)side_bytes);
+  if (int rc = gcrl::her_norm_check(h, "gcrl_her_gather_update")) return rc;   // before an index is drawn
   hipStream_t st = h->pick(stream);
   if (!idx_host && gcrl::her_prio_on(h)) {
     if (int rc = gcrl::her_prio_indices(h, B, M, st, nullptr)) return rc;
@@ -1274,6 +1294,7 @@ struct HerStateHeader {
   uint64_t episodes_flushed, draws_done, mutation_epoch;
 };
 constexpr uint32_t kHerMagic = 0x52454847u;   // "GHER"
+constexpr uint32_t kHerRawFlag = 0x100u;      // in the version word: the rows are raw (normalize = "sample"); the layout is the version's
 // version 1: a ring in the default mode (the blob of before).  version 2: sample-time relabelling — the header is followed by
 // this record, the ring records are whole (tails included)
 // version 3: sample-time relabelling with a goal strategy other than GCRL_GOAL_FUTURE — version 2's layout, the strategy in the
@@ -1292,7 +1313,7 @@ int64_t gcrl_her_state_size(const gcrl_her* h) { return h ? (int64_t)her_state_b
 int gcrl_her_save_state(gcrl_her* h, void* dst_host, int64_t n) {
   GCRL_CHECK_ARG(h && dst_host && n == (int64_t)her_state_bytes(h), "gcrl_her_save_state: buffer must be gcrl_her_state_size() bytes");
   GCRL_HIP(hipDeviceSynchronize());
-  HerStateHeader hd{kHerMagic, h->relabel_mode == GCRL_RELABEL_SAMPLE ? (h->goal_strategy != GCRL_GOAL_FUTURE ? 3u : 2u) : 1u, h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
+  HerStateHeader hd{kHerMagic, (h->relabel_mode == GCRL_RELABEL_SAMPLE ? (h->goal_strategy != GCRL_GOAL_FUTURE ? 3u : 2u) : 1u) | (gcrl::her_norm_on(h) ? kHerRawFlag : 0u), h->S, h->A, h->G, h->cfg.nenvs, h->cfg.k_future, h->cfg.flush_len, h->RS, h->RG,
                     h->cfg.capacity, h->len, h->episodes_flushed, h->draws_done, h->mutation_epoch};
   char* o = (char*)dst_host;
   std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
@@ -1315,7 +1336,12 @@ int gcrl_her_load_state(gcrl_her* h, const void* src_host, int64_t n) {
   GCRL_CHECK_ARG(h && src_host && n >= (int64_t)sizeof(HerStateHeader), "gcrl_her_load_state: null / short blob");
   HerStateHeader hd;
   std::memcpy(&hd, src_host, sizeof(hd));
+  const bool blob_raw = (hd.version & kHerRawFlag) != 0;
+  hd.version &= ~kHerRawFlag;
   GCRL_CHECK_ARG(hd.magic == kHerMagic && hd.version >= 1 && hd.version <= 3, "gcrl_her_load_state: not a replay-ring state blob");
+  if (blob_raw != gcrl::her_norm_on(h))
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_load_state: normalize: the state was saved by a ring with normalize=\"%s\", this ring has normalize=\"%s\"",
+                      blob_raw ? "sample" : "push", gcrl::her_norm_on(h) ? "sample" : "push");
   const int blob_mode = hd.version >= 2 ? GCRL_RELABEL_SAMPLE : GCRL_RELABEL_PUSH;
   if (blob_mode != h->relabel_mode)
     return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_load_state: relabel: the state was saved by a ring with relabel=\"%s\", this ring has relabel=\"%s\"",
@@ -1500,6 +1526,8 @@ int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, g
     GCRL_CHECK_ARG(!(zg && h->cfg.reward_kind == GCRL_REWARD_HOST), "gcrl_pop_process_step: nz_dg: a goal normaliser together with a host-callback "
                    "compute_reward is not supported by the fused entry (member %d): use the separate calls", i);
     any_g = any_g || zg;
+    GCRL_CHECK_ARG(h->normalize_mode == h0->normalize_mode, "gcrl_pop_process_step: normalize: member %d's ring has normalize mode %d, member 0's %d", i,
+                   h->normalize_mode, h0->normalize_mode);
   }
   ps->calls++;
   const size_t oD = (size_t)n * D, oG = (size_t)n * G, oA = (size_t)n * A;
@@ -1577,7 +1605,10 @@ int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, g
   void* tab_dev = nullptr;
   if (static_cast<PopTabCache*>(ps->tabs)->get(tab, sizeof(ProcArgs) * P, st, &tab_dev)) return gcrl::fail(GCRL_ERR_HIP, "gcrl_pop_process_step: argument table upload failed");
   const float* data_dev = reinterpret_cast<const float*>(ps->blk_dev) + (size_t)slot * ps->slot_floats;
-  hipLaunchKernelGGL(her_process_step_pop_kernel, dim3(P), dim3(256), 0, st, static_cast<const ProcArgs*>(tab_dev), data_dev, (int)stride, (int)raw);
+  static_assert(sizeof(ProcArgs) == sizeof(ProcRawArgs), "ProcRawArgs is ProcArgs field for field");
+  if (her_norm_on(h0)) {   // raw rings: the raw-store form of the launch (her_norm.hip)
+    if (int rc = her_process_step_raw_pop(static_cast<const ProcRawArgs*>(tab_dev), data_dev, (int)stride, (int)raw, P, st)) return rc;
+  } else hipLaunchKernelGGL(her_process_step_pop_kernel, dim3(P), dim3(256), 0, st, static_cast<const ProcArgs*>(tab_dev), data_dev, (int)stride, (int)raw);
   GCRL_HIP(hipGetLastError());
   GCRL_HIP(hipEventRecord(ps->ev[slot], st));
   ps->launches++;

@@ -22,7 +22,8 @@ import torch
 
 from .. import _ffi
 from .._ffi import lib
-from .buffer import HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_goal_strategy, _check_nstep
+from .buffer import (HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_goal_strategy, _check_normalize,
+                     _check_nstep)
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -188,7 +189,7 @@ class _EngineAgent:
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
                  n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
-                 _member=None):
+                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -203,6 +204,10 @@ class _EngineAgent:
         # goal_strategy="final" | "episode" (relabel="sample"): which row of its episode a relabelled row takes its goal from
         # (buffer.HERBuffer); "future", the default, changes nothing.
         self.goal_strategy = _check_goal_strategy(type(self).__name__, goal_strategy, relabel, config.buffer_type)
+        # normalize="sample": the HER ring stores raw rows and every gathered batch is normalised with the statistics of that moment
+        # (buffer.HERBuffer); `obs_normalize` / `g_normalize` are then the flags `observe_act` and `process_step` must be called with.
+        self.normalize = _check_normalize(type(self).__name__, normalize, obs_normalize, g_normalize, config.buffer_type)
+        self.obs_normalize, self.g_normalize = bool(obs_normalize), bool(g_normalize)
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -244,7 +249,8 @@ class _EngineAgent:
             self.buffer = HERBuffer(config.max_len, config.max_eps_len, nenvs, k_future=config.k_future,
                                     rng=rng, seed=seed, device_index=device_index, relabel=relabel,
                                     n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None,
-                                    prioritise=prioritise, energy=energy, goal_strategy=self.goal_strategy)
+                                    prioritise=prioritise, energy=energy, goal_strategy=self.goal_strategy,
+                                    normalize=self.normalize, obs_normalize=self.obs_normalize, g_normalize=self.g_normalize)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 
@@ -531,6 +537,22 @@ class _EngineAgent:
             return None
         return (on.handle if obs_normalize else None, gn.handle if g_normalize else None)
 
+    def _check_normalize_call(self, what: str, obs_normalize: bool, g_normalize: bool, need_device: bool = False):
+        """normalize="sample": the ring's gathers normalise with the constructor's flags, so a step that acts or pushes with other
+        flags is refused by the flag's name; `need_device`: and so is a step whose normalisers are not on the device."""
+        if getattr(self, "normalize", "push") != "sample":
+            return
+        who = f"{type(self).__name__}.{what}"
+        if bool(obs_normalize) != self.obs_normalize:
+            raise _ffi.GcrlError(f"{who}: obs_normalize: {bool(obs_normalize)!r} differs from the constructor's {self.obs_normalize!r} "
+                                 "(normalize='sample' normalises every gathered batch with the constructor's flags)")
+        if bool(g_normalize) != self.g_normalize:
+            raise _ffi.GcrlError(f"{who}: g_normalize: {bool(g_normalize)!r} differs from the constructor's {self.g_normalize!r} "
+                                 "(normalize='sample' normalises every gathered batch with the constructor's flags)")
+        if need_device and self._device_normalizers(obs_normalize, g_normalize) is None:
+            raise _ffi.GcrlError(f"{who}: normalize: normalize='sample' stores raw rows through the fused device entry and needs "
+                                 "DeviceRunningNormalizer objects assigned to buffer.obs_normalizer / buffer.dg_normalizer")
+
     def _rows_dtypes(self, obs_dtype, goal_dtype, obs_normalize: bool, g_normalize: bool):
         """numpy's type rules decide the reference normaliser's arithmetic: tell the device normalisers which dtype the rows
         have on the caller's side (the trainer's observation batches are float64 arrays, its goal batches float32)."""
@@ -559,6 +581,7 @@ class _EngineAgent:
         generators are consumed exactly as in the reference (`random.random()` for DDPG's epsilon branch, `np.random`
         for the Gaussian noise, torch's for SAC / TQC eps).  Falls back to the two separate calls when the normalisers
         are host objects."""
+        self._check_normalize_call("observe_act", obs_normalize, g_normalize)
         nz = self._device_normalizers(obs_normalize, g_normalize)
         obs_in = observation if isinstance(observation, np.ndarray) else np.asarray(observation)
         dg_in = desired_goal if isinstance(desired_goal, np.ndarray) else np.asarray(desired_goal)
@@ -606,12 +629,16 @@ class _EngineAgent:
         :222-223).  Falls back to the separate calls when a normaliser this step needs is a host object (or, with
         g_normalize, when compute_reward runs through the host callback).  `env0`: the ring's episode slot of this call's first
         env (agents that share one ring each push into their own slots)."""
+        self._check_normalize_call("process_step", obs_normalize, g_normalize, need_device=True)
         nz = self._device_normalizers(obs_normalize, g_normalize)
         buf = self.buffer
         if nz is not None and g_normalize:   # (the ring — and with it the reward kind — exists from here on)
             buf._ensure(np.shape(state["observation"])[1] + np.shape(state["desired_goal"])[1], np.shape(actions)[1],
                         np.shape(next_obs_raw["achieved_goal"])[1])
         if nz is None or (g_normalize and buf._reward_cfg[0] == 2):
+            if self.normalize == "sample":
+                raise _ffi.GcrlError(f"{type(self).__name__}.process_step: normalize: normalize='sample' with g_normalize and a host-callback "
+                                     "compute_reward has no fused entry to store raw rows through")
             self.update_normalizers([state["observation"], next_obs_raw["observation"]],
                                     [state["desired_goal"], next_obs_raw["desired_goal"], state["achieved_goal"],
                                      next_obs_raw["achieved_goal"]], obs_normalize, g_normalize)
@@ -717,7 +744,8 @@ class _EngineAgent:
             if nz is not None:
                 meta[name] = dict(mean=np.asarray(nz.mean, np.float64).tolist(), var=np.asarray(nz.var, np.float64).tolist(),
                                   count=float(nz.count), clip_range=float(nz.clip_range),
-                                  float32=bool(np.asarray(nz.mean).dtype == np.float32))   # (the regime after RunningNormalizer.load)
+                                  float32=bool(np.asarray(nz.mean).dtype == np.float32),   # (the regime after RunningNormalizer.load)
+                                  rows64=bool(getattr(nz, "_rows64", 0)))   # (a device normaliser: the dtype its rows have on the trainer's side)
         with open(os.path.join(path, "meta.json"), "w") as f:
             json.dump(meta, f)
 
@@ -738,6 +766,8 @@ class _EngineAgent:
                 d = meta[name]
                 if hasattr(nz, "set_state"):     # DeviceRunningNormalizer: its statistics live on the device
                     nz.set_state(np.array(d["mean"]), np.array(d["var"]), d["count"], d["clip_range"], float32=bool(d.get("float32", False)))
+                    if "rows64" in d:     # (normalize="sample" normalises a gathered batch before the next acting call says it again)
+                        nz.rows_dtype(np.float64 if d["rows64"] else np.float32)
                 else:
                     dt = np.float32 if d.get("float32", False) else np.float64
                     nz.mean, nz.var = np.array(d["mean"], dtype=dt), np.array(d["var"], dtype=dt)

@@ -166,6 +166,21 @@ def _check_goal_strategy(who: str, goal_strategy, relabel: str, buffer_type: str
     return goal_strategy
 
 
+NORMALIZE_MODES = {"push": 0, "sample": 1}    # include/gcrl.h GCRL_NORMALIZE_*
+
+
+def _check_normalize(who: str, normalize, obs_normalize, g_normalize, buffer_type: str = "HER") -> str:
+    """-> the mode as the ring takes it, or a GcrlError that names normalize; before any device work"""
+    if not isinstance(normalize, str) or normalize not in NORMALIZE_MODES:
+        raise _ffi.GcrlError(f"{who}: normalize: must be one of {sorted(NORMALIZE_MODES)}, got {normalize!r}")
+    if normalize == "sample" and buffer_type != "HER":
+        raise _ffi.GcrlError(f"{who}: normalize: 'sample' needs buffer_type 'HER' (the REPLAY and PER buffers store what they are given), "
+                             f"got {buffer_type!r}")
+    if normalize == "sample" and not (obs_normalize or g_normalize):
+        raise _ffi.GcrlError(f"{who}: normalize: 'sample' with obs_normalize=False and g_normalize=False leaves nothing to normalise")
+    return normalize
+
+
 PRIORITISE_MODES = (None, "energy")
 # prioritise="energy": the constants of the episode energy (tests/her_energy_ref.py is the definition).  The defaults are this
 # project's choice — m = 1: potential = m g = 9.81, kinetic = m / (2 dt^2) with dt = 0.04, axis 2 = the height of a 3-component goal
@@ -232,6 +247,9 @@ class _RingState:
         meta["relabel"] = getattr(self, "relabel", "push")
         meta["prioritise"] = getattr(self, "prioritise", None)
         meta["goal_strategy"] = getattr(self, "goal_strategy", "future")
+        meta["normalize"] = getattr(self, "normalize", "push")
+        if meta["normalize"] == "sample":
+            meta["obs_normalize"], meta["g_normalize"] = bool(self.obs_normalize), bool(self.g_normalize)
         if self.rng.mode == "python":
             st = _pyrandom.getstate()
             meta["py_random"] = [st[0], list(st[1]), st[2]]
@@ -262,6 +280,15 @@ class _RingState:
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: goal_strategy: the state was saved with "
                                  f"goal_strategy={meta.get('goal_strategy', 'future')!r}, this buffer has "
                                  f"goal_strategy={getattr(self, 'goal_strategy', 'future')!r}")
+        mine_n = getattr(self, "normalize", "push")
+        if meta.get("normalize", "push") != mine_n:
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: normalize: the state was saved with normalize={meta.get('normalize', 'push')!r}, "
+                                 f"this buffer has normalize={mine_n!r}")
+        if mine_n == "sample":
+            for flag in ("obs_normalize", "g_normalize"):
+                if bool(meta.get(flag)) != bool(getattr(self, flag)):
+                    raise _ffi.GcrlError(f"{type(self).__name__}.load_state: normalize: the state was saved with {flag}={bool(meta.get(flag))!r}, "
+                                         f"this buffer has {flag}={bool(getattr(self, flag))!r}")
         if meta.get("prioritise") != getattr(self, "prioritise", None):
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with prioritise={meta.get('prioritise')!r}, "
                                  f"this buffer has prioritise={getattr(self, 'prioritise', None)!r}")
@@ -295,7 +322,8 @@ class HERBuffer(_RingState):
     def __init__(self, max_mem_len: int, max_eps_len: int, nenvs: int, threshold: float = 0.05,
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
                  device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None,
-                 prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future"):
+                 prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
+                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False):
         # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
         # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
         # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
@@ -320,6 +348,14 @@ class HERBuffer(_RingState):
         # included; the ring's records then carry `elapsed` beside `remaining`).  csrc/her_strategy.hip; tests/her_strategy_ref.py is
         # the definition.  Fixed when the ring is created.
         self.goal_strategy = _check_goal_strategy("HERBuffer", goal_strategy, relabel)
+        # normalize="sample" (either relabel mode): the ring stores RAW [obs | dg] states, next states and achieved goals, and every
+        # batch that leaves it — sample(), gather_update(), an agent's update calls — is normalised on the device with the statistics
+        # of `obs_normalizer` (obs_normalize) and `dg_normalizer` (g_normalize) as they stand when the batch is gathered; rewards the
+        # gathers recompute compare raw achieved goals (csrc/her_norm.hip; tests/her_normalize_ref.py is the definition).  The two must be
+        # DeviceRunningNormalizer objects; they are bound to the ring whenever they are assigned.  Rows handed to push / push_batch /
+        # push_episode are stored as given: hand them over raw.  "push" (default): nothing changes.
+        self.normalize = _check_normalize("HERBuffer", normalize, obs_normalize, g_normalize)
+        self.obs_normalize, self.g_normalize = bool(obs_normalize), bool(g_normalize)
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError("HERBuffer needs a HIP device: the replay ring lives in HBM and "
                                  "there is no CPU fallback")
@@ -337,11 +373,53 @@ class HERBuffer(_RingState):
         self._threshold = threshold
         self.k_future = int(k_future)
         self._compute_reward = None
-        self.obs_normalizer = None
-        self.dg_normalizer = None
+        self._obs_normalizer = None
+        self._dg_normalizer = None
         self.rng = MTStream(rng, seed)
         self._dims = None
         self._reward_cfg = None
+
+    # the trainer assigns the normalisers after construction (src/env.py:93-98); a normalize="sample" ring is told at once
+    @property
+    def obs_normalizer(self):
+        return self._obs_normalizer
+
+    @obs_normalizer.setter
+    def obs_normalizer(self, nz):
+        self._assign_normalizer("_obs_normalizer", "obs_normalizer", self.obs_normalize, nz)
+
+    @property
+    def dg_normalizer(self):
+        return self._dg_normalizer
+
+    @dg_normalizer.setter
+    def dg_normalizer(self, nz):
+        self._assign_normalizer("_dg_normalizer", "dg_normalizer", self.g_normalize, nz)
+
+    def _assign_normalizer(self, slot: str, name: str, needed: bool, nz):
+        if self.normalize == "sample" and needed and nz is not None:
+            from .utils import DeviceRunningNormalizer
+            if not isinstance(nz, DeviceRunningNormalizer):    # refused before any device work
+                raise _ffi.GcrlError(f"HERBuffer.{name}: normalize: normalize='sample' normalises the gathered batch on the device and needs a "
+                                     f"DeviceRunningNormalizer, got a {type(nz).__name__}")
+        old = getattr(self, slot)
+        setattr(self, slot, nz)
+        try:
+            self._bind_normalizers()
+        except (_ffi.GcrlError, ValueError):
+            setattr(self, slot, old)
+            self._bind_normalizers()
+            raise
+
+    def _bind_normalizers(self):
+        """normalize="sample": (re-)bind the device normalisers to the ring (borrowed handles) and say which ones its gathers need."""
+        if self.normalize != "sample" or self._h is None:
+            return
+        S, _, G = self._dims
+        on = self._obs_normalizer.handle if (self.obs_normalize and self._obs_normalizer is not None) else None
+        gn = self._dg_normalizer.handle if (self.g_normalize and self._dg_normalizer is not None) else None
+        _ffi.check(lib.gcrl_her_set_normalize(self._h, on, gn, S - G))
+        _ffi.check(lib.gcrl_her_require_normalize(self._h, 1 if self.obs_normalize else 0, 1 if self.g_normalize else 0))
 
     # the trainer assigns compute_reward after construction (src/env.py:105); classification into a built-in reward
     # kind happens when the ring is created — a later reassignment that changes the kind / threshold is refused
@@ -397,6 +475,12 @@ class HERBuffer(_RingState):
             self._h = _ffi.check_ptr(lib.gcrl_her_create_goal(C.byref(cfg), self.rng.handle, RELABEL_MODES[self.relabel],
                                                               GOAL_STRATEGIES[self.goal_strategy]), "gcrl_her_create")
         self._dims = (S, A, G)
+        try:
+            self._bind_normalizers()
+        except (_ffi.GcrlError, ValueError):     # (a normaliser of another size: no ring is left behind in the other mode)
+            h, self._h, self._dims = self._h, None, None
+            lib.gcrl_her_destroy(h)
+            raise
         if self.n_step > 1:
             _ffi.check(lib.gcrl_her_set_nstep(self._h, self.n_step, self.gamma))
         if self.prioritise is not None:

@@ -21,7 +21,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import lib
 from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
-from .buffer import HERBuffer, MTStream, _check_goal_strategy, _check_nstep
+from .buffer import HERBuffer, MTStream, _check_goal_strategy, _check_normalize, _check_nstep
 
 MAX_MEMBERS = 16
 MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
@@ -75,7 +75,7 @@ class _Population:
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
                  relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None,
-                 goal_strategy: str = "future"):
+                 goal_strategy: str = "future", normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False):
         # prioritise: accepted only to be refused by name — the energy-prioritised draw (buffer.HERBuffer) is a single-agent mode
         if prioritise is not None or energy is not None:
             self._refuse("prioritise", f"populations (and their shared ring) do not draw from an energy tree, got prioritise={prioritise!r}")
@@ -88,6 +88,11 @@ class _Population:
         # goal_strategy: passed through to every member's ring (or the shared one); their sample-mode gathers stay member by member
         for c in configs or [None]:
             self.goal_strategy = _check_goal_strategy(type(self).__name__, goal_strategy, relabel, getattr(c, "buffer_type", "HER"))
+        # normalize="sample": every member's ring (or the shared one, whose normalisers the members share) stores raw rows and
+        # normalises what it gathers — one pass per member behind the population's gather launch, merged or not (buffer.HERBuffer)
+        for c in configs or [None]:
+            self.normalize = _check_normalize(type(self).__name__, normalize, obs_normalize, g_normalize, getattr(c, "buffer_type", "HER"))
+        self.obs_normalize, self.g_normalize = bool(obs_normalize), bool(g_normalize)
         # n_step=N: every member's ring (or the shared one) gathers n-step windows; each member's update calls discount by its own gamma
         if n_step != 1:
             for i, c in enumerate(configs):
@@ -124,7 +129,8 @@ class _Population:
         self.members = []
         for i, (c, s) in enumerate(zip(configs, seeds)):
             self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index, relabel=relabel,
-                                           n_step=self.n_step, goal_strategy=self.goal_strategy, _member=lambda cfg, i=i: (pop, pop.member(i))))
+                                           n_step=self.n_step, goal_strategy=self.goal_strategy, normalize=self.normalize, obs_normalize=self.obs_normalize,
+                                           g_normalize=self.g_normalize, _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
         self._merge_gather = False
         if P >= self.MERGE_GATHER_FROM:
@@ -136,7 +142,8 @@ class _Population:
             self.nenvs = int(nenvs)
             self.buffer = HERBuffer(c0.max_len, c0.max_eps_len, int(nenvs) * P, k_future=c0.k_future, rng=rng, seed=seeds[0],
                                     device_index=device_index, relabel=relabel, n_step=self.n_step,
-                                    goal_strategy=self.goal_strategy,
+                                    goal_strategy=self.goal_strategy, normalize=self.normalize, obs_normalize=self.obs_normalize,
+                                    g_normalize=self.g_normalize,
                                     gamma=c0.gamma if self.n_step > 1 else None)   # (the ring's own gathers; a member's calls use the member's gamma)
             for m in self.members:
                 m.buffer = self.buffer
@@ -237,6 +244,8 @@ class _Population:
         self._per_member("desired_goals", desired_goals)
         ms = self.members
         P = len(ms)
+        if getattr(self, "normalize", "push") == "sample":    # the constructor's flags (the members share them)
+            ms[0]._check_normalize_call("observe_act", obs_normalize, g_normalize)
         obs = [x if isinstance(x, np.ndarray) else np.asarray(x) for x in observations]
         dgs = [x if isinstance(x, np.ndarray) else np.asarray(x) for x in desired_goals]
         nzs = [m._device_normalizers(obs_normalize, g_normalize) for m in ms]
@@ -285,6 +294,9 @@ class _Population:
             self._per_member(name, seq)
         ms = self.members
         P = len(ms)
+        if getattr(self, "normalize", "push") == "sample":    # the constructor's flags and device normalisers, before any member has pushed
+            for m in ms:
+                m._check_normalize_call("process_step", obs_normalize, g_normalize, need_device=True)
         if getattr(self, "shared_ring", False):
             # one ring and one pair of normalisers: the merged staging launch would update them from P members at once, so the members
             # push one after another, each into its own episode slots
@@ -424,6 +436,10 @@ class _Population:
                 if ra != rb:
                     self._refuse("relabel", f"member {s}'s ring has relabel={ra!r}, member {d}'s relabel={rb!r}: records of one mode do not "
                                             "fit a ring of the other (copy_ring=True)")
+                na, nb = getattr(ms[s].buffer, "normalize", "push"), getattr(ms[d].buffer, "normalize", "push")
+                if na != nb:
+                    self._refuse("normalize", f"member {s}'s ring has normalize={na!r}, member {d}'s normalize={nb!r}: raw rows do not belong "
+                                              "in a ring whose gathers do not normalise, nor the reverse (copy_ring=True)")
                 ga, gb = getattr(ms[s].buffer, "goal_strategy", "future"), getattr(ms[d].buffer, "goal_strategy", "future")
                 if ga != gb:
                     self._refuse("goal_strategy", f"member {s}'s ring has goal_strategy={ga!r}, member {d}'s goal_strategy={gb!r}: their "

@@ -156,6 +156,35 @@ int gcrl_her_get_nstep(const gcrl_her* h, double* gamma);
 enum { GCRL_GOAL_FUTURE = 0, GCRL_GOAL_FINAL = 1, GCRL_GOAL_EPISODE = 2 };
 gcrl_her* gcrl_her_create_goal(const gcrl_her_config* cfg, gcrl_mt* rng, int mode, int strategy);
 int gcrl_her_goal_strategy(const gcrl_her* h);   /* -1 for a null handle */
+/* Sample-time normalisation (csrc/her_norm.hip; tests/her_normalize_ref.py is the definition).  A ring is created
+ * in GCRL_NORMALIZE_PUSH: its records hold whatever the caller pushed, which for the trainer is rows normalised with the statistics
+ * of the moment of the push.  gcrl_her_set_normalize marks it GCRL_NORMALIZE_SAMPLE ("raw") and binds the two device normalisers —
+ * borrowed, never freed by the ring; either may be NULL (those columns stay raw); a later call re-binds.  On a raw ring
+ *   - gcrl_her_process_step_g / gcrl_pop_process_step update the statistics as before and stage the rows and achieved goals RAW;
+ *   - every reward a gather recomputes (relabelled rows, n-step windows) and the energy tree read raw achieved goals;
+ *   - one in-place launch behind every gather (gcrl_her_sample, gcrl_her_sample_dev, gcrl_her_gather_update, the update engine's
+ *     and the populations' gathers) normalises columns [0, obs_dim) of s and ns with nz_obs and [obs_dim, state_dim) with nz_dg:
+ *     bit for bit gcrl_normalizer_normalize of those columns with the statistics as they stand in stream order at that launch.
+ *     Actions, rewards, done flags and padding columns are not touched.
+ * Refused with GCRL_ERR_ARG, naming normalize: a normaliser of another size than its columns; obs_dim + goal_dim != state_dim or
+ * obs_dim > 128; a ring that already holds or stages rows pushed in the other mode; a ring with a TD priority tree or rows appended
+ * one by one (gcrl_her_append: the REPLAY and PER buffers), and gcrl_her_append on a raw ring likewise.
+ * gcrl_her_require_normalize says which normalisers a gather must find bound (bit 0: nz_obs, bit 1: nz_dg); a raw ring with neither
+ * bound, or without a required one, refuses to gather with GCRL_ERR_STATE naming normalize before a ticket or a counter is
+ * consumed.  Also refused by that name: an update call of an agent under a gradient exchange from a raw ring; gcrl_pop_clone
+ * between rings of differing modes; gcrl_her_load_state of a blob saved in the other mode (a raw ring's blob carries the flag 0x100 in its version word). */
+enum { GCRL_NORMALIZE_PUSH = 0, GCRL_NORMALIZE_SAMPLE = 1 };
+struct gcrl_normalizer;   /* (the device RunningNormalizer, declared below) */
+int gcrl_her_set_normalize(gcrl_her* h, struct gcrl_normalizer* nz_obs, struct gcrl_normalizer* nz_dg, int obs_dim);
+int gcrl_her_require_normalize(gcrl_her* h, int need_obs, int need_dg);
+int gcrl_her_normalize_mode(const gcrl_her* h);   /* -1 for a null handle */
+/* The pass on its own, for a batch the caller formed (an injected batch of raw states): IN PLACE, columns [0, obs_dim) of every row of
+ * the device matrices x0 / x1 / x2 (n rows each, row strides ld0 / ld1 / ld2 floats; NULL matrices are skipped) are normalised with
+ * nz_obs and columns [obs_dim, state_dim) with nz_dg (a NULL normaliser leaves its columns as they are); every other column keeps its
+ * bits.  One launch: 16-byte accesses when every matrix is 16-byte aligned with a stride that is a multiple of 4 floats and holds
+ * roundup(state_dim, 4) columns, element accesses otherwise.  Bit for bit gcrl_normalizer_normalize of those columns. */
+int gcrl_normalizer_normalize_states(struct gcrl_normalizer* nz_obs, struct gcrl_normalizer* nz_dg, int obs_dim, int state_dim, int64_t n,
+                                     float* x0, int ld0, float* x1, int ld1, float* x2, int ld2, void* stream);
 void gcrl_her_destroy(gcrl_her* h);
 /* compute_reward for GCRL_REWARD_HOST rings: out[i] = compute_reward(achieved[i], goal[i], {}) for n pairs of goal_dim floats
  * (row-major), in the reference's call order (src/buffer.py:151-166: step-major, relabel-minor).  Returns 0, or non-zero to

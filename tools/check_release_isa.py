@@ -88,7 +88,7 @@ def check_kernel(body):
 # by-value argument struct made hipcc copy the whole 3.7 KB struct to every thread's private memory — a 3 us kernel took 36 us
 # (rowchain_act_inline_kernel, round 4).  `.amdhsa_private_segment_fixed_size` says it all.
 SCRATCH_UNITS = ["her_ring.hip", "her_relabel.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "rowchain.hip", "agent.hip", "normalizer.hip", "abi_misc.hip",
-                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip", "act_bn.hip", "pop_clone.hip", "her_prio.hip", "her_strategy.hip"]
+                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip", "act_bn.hip", "pop_clone.hip", "her_prio.hip", "her_strategy.hip", "her_norm.hip"]
 SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
     "rowchain_split_kernelILi4E": 64,   # 16 rows per workgroup: register spills; row_rg_of picks it only past one wave of 8-row blocks
     "gemm_tiled_kernel": 16,                                                   # three spilled dwords outside the k-loop
@@ -104,6 +104,8 @@ SCRATCH_NAMED = {"pop_clone.hip": ["pop_clone_kernel"], "her_prio.hip": ["her_en
                  "her_relabel.hip": ["her_flush_sample_kernel", "her_gather_relabel_kernel", "her_gather_relabel_pub_kernel"],
                  "her_strategy.hip": ["her_flush_episode_kernel", "her_gather_goal_kernel", "her_gather_goal_nstep_kernel",
                                       "her_gather_goal_pub_kernel", "her_gather_goal_nstep_pub_kernel"],
+                 "her_norm.hip": ["her_norm_rows_kernel", "her_norm_dense_kernel", "her_process_step_raw_kernel", "her_process_step_raw_inline_kernel",
+                                  "her_process_step_raw_pop_kernel"],
                  "ops_sac.hip": ["tanh_gauss_fwd_pop_kernel", "tanh_gauss_fwd2_pop_kernel", "tanh_gauss_bwd_pop_kernel"],
                  "act_bn.hip": ["act_bn_kernel", "act_bn_inline_kernel", "act_bn_pop_kernel", "act_bn_pop_staged_kernel"]}
 

@@ -11,7 +11,10 @@ n_step does not reach the flush, and a `final` ring launches the sample mode's).
 here: the kernel trace is.
 --parse reads the trace and prints, per kernel and launch size, the number of launches, the median and the range of the kernel
 durations — the launches after the warm-up ones.  The n-step rings launch one kernel at one grid size: their launches alternate in
-NSTEPS order and are told apart by that; so do the rings of the goal strategies, in GOALS order.  No GPU: --run fails; it does not fall back."""
+NSTEPS order and are told apart by that; so do the rings of the goal strategies, in GOALS order.  No GPU: --run fails; it does not fall back.
+--rings NAME[,NAME ...] builds and times only those rings (push, sample, sample_n3, final, episode_n3, ...).  `sample_norm` is the
+sample-mode ring with normalize="sample" (csrc/her_norm.hip; observation and goal normalisers bound): behind each of its gathers runs
+her_norm_rows_kernel, whose launches are listed beside the her_gather_relabel_kernel ones they follow."""
 import argparse
 import csv
 import glob
@@ -31,7 +34,7 @@ GOALS = ("final", "episode")
 GOAL_NSTEP = 3
 
 
-def run():
+def run(only=None):
     import numpy as np
     import gcrl_amd
     from oracle import her_oracle
@@ -40,7 +43,10 @@ def run():
     ep = [np.stack([x[j] for x in st]).astype(np.float32) for j in (0, 1, 2)] + \
          [np.array([x[3] for x in st], np.float32), np.zeros(50, np.float32), np.stack([x[6] for x in st])]
     rings = {}
+    want = lambda name: only is None or name in only     # (a ring that is not asked for is not built: the fill is most of the run)
     for mode in ("push", "sample"):
+        if not want(mode):
+            continue
         buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel=mode)
         buf.compute_reward = her_oracle.sparse_reward
         per = 50 if mode == "sample" else 50 + K * 49
@@ -49,6 +55,8 @@ def run():
         assert len(buf) == CAP
         rings[mode] = buf
     for N in NSTEPS:
+        if not want(f"sample_n{N}"):
+            continue
         buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel="sample", n_step=N, gamma=0.98)
         buf.compute_reward = her_oracle.sparse_reward
         for _ in range(CAP // 50 + 2):
@@ -58,12 +66,29 @@ def run():
     for N in (1, GOAL_NSTEP):
         for goal in GOALS:
             kw = dict(n_step=N, gamma=0.98) if N > 1 else {}
+            if not want(goal if N == 1 else f"{goal}_n{N}"):
+                continue
             buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel="sample", goal_strategy=goal, **kw)
             buf.compute_reward = her_oracle.sparse_reward
             for _ in range(CAP // 50 + 2):
                 buf.push_episode(0, *ep)
             assert len(buf) == CAP
             rings[goal if N == 1 else f"{goal}_n{N}"] = buf
+    if want("sample_norm"):
+        from gcrl_amd.src.utils import DeviceRunningNormalizer
+        buf = gcrl_amd.HERBuffer(CAP, 50, 2, k_future=K, rng="device", seed=1, relabel="sample", normalize="sample", g_normalize=True)
+        buf.compute_reward = her_oracle.sparse_reward
+        buf.obs_normalizer, buf.dg_normalizer = DeviceRunningNormalizer(S - G), DeviceRunningNormalizer(G)
+        buf.obs_normalizer.update(ep[0][:, :S - G])
+        buf.dg_normalizer.update(ep[0][:, S - G:])
+        for _ in range(CAP // 50 + 2):
+            buf.push_episode(0, *ep)
+        assert len(buf) == CAP
+        rings["sample_norm"] = buf
+    if only is not None:
+        unknown = [r for r in only if r not in rings]
+        if unknown:
+            sys.exit(f"--rings: unknown ring(s) {unknown}")
     import torch
     torch.cuda.synchronize()
     for B, M in SIZES:
@@ -72,13 +97,14 @@ def run():
                 rings[mode].gather_update(B, M)
     for _ in range(WARM + ITERS):
         for mode in ("push", "sample", "episode"):
-            rings[mode].push_episode(1, *ep)
+            if mode in rings:
+                rings[mode].push_episode(1, *ep)
     torch.cuda.synchronize()
     print("relabel_bench: done")
 
 
 NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_gather_nstep_kernel", "her_gather_goal_kernel", "her_gather_goal_nstep_kernel",
-         "her_flush_kernel", "her_flush_sample_kernel", "her_flush_episode_kernel")
+         "her_flush_kernel", "her_flush_sample_kernel", "her_flush_episode_kernel", "her_norm_rows_kernel")
 
 
 def parse(d):
@@ -118,10 +144,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--run", action="store_true")
     ap.add_argument("--parse", metavar="DIR")
+    ap.add_argument("--rings", default=None, help="with --run: comma-separated ring names to build and time (default: all)")
     a = ap.parse_args()
     if a.parse:
         parse(a.parse)
     elif a.run:
-        run()
+        run(a.rings.split(",") if a.rings else None)
     else:
         ap.error("--run or --parse DIR")
