@@ -67,9 +67,38 @@ class PointReachVecEnv:
         return obs, rewards, terminated, truncated, {}
 
 
+def fill_prior_ring(agent, prior, episodes, normalize, seed):
+    """`episodes` scripted episodes of the synthetic goal environment into the prior ring: the action closes the distance to the goal,
+    so most of them succeed — a stand-in for demonstrations or logged data.  normalize="push": the rings hold rows normalised at push
+    time, so the scripted observations first update the agent's normalisers and are then stored normalised with those statistics
+    (like the main ring's rows they keep the statistics of that moment).  normalize="sample": stored raw; the agent binds its
+    normalisers to the prior ring and its rows leave normalised with the statistics of the moment of the gather."""
+    env = PointReachVecEnv(1, seed=seed + 4242)
+    eps = []
+    for _ in range(episodes):
+        state, _ = env.reset()
+        rows = []
+        for _ in range(env.T):
+            action = np.clip((state["desired_goal"] - state["achieved_goal"]) / 0.04, -1, 1).astype(np.float32)
+            nxt, reward, _, _, _ = env.step(action)
+            rows.append((state, action, nxt, reward))
+            state = nxt
+        eps.append(rows)
+    if normalize == "push":
+        agent.update_normalizers([x[0]["observation"] for rows in eps for x in rows] + [x[2]["observation"] for rows in eps for x in rows],
+                                 [], True, False)
+        enc = lambda st: agent.normalize_state_batch(st["observation"], st["desired_goal"], True, False)
+    else:
+        enc = lambda st: np.concatenate([st["observation"], st["desired_goal"]], axis=-1)
+    for rows in eps:
+        prior.push_episode(0, np.concatenate([enc(x[0]) for x in rows]), np.concatenate([x[1] for x in rows]),
+                           np.concatenate([enc(x[2]) for x in rows]), np.concatenate([x[3] for x in rows]), np.zeros(len(rows), np.float32),
+                           np.concatenate([x[2]["achieved_goal"] for x in rows]))
+
+
 def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
           seed=0, verbose=True, per_env_push=False, fused=False, relabel="push", n_step=1, prioritise=None,
-          goal_strategy="future", normalize="push"):
+          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0):
     import gcrl_amd
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
@@ -86,13 +115,23 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     if relabel == "sample":   # the ring then counts real transitions: the same episodes resident in 1 / (1 + k_future) of the rows
         cfg.max_len //= 1 + cfg.k_future
     cls = dict(DDPG=gcrl_amd.DDPG, TD3=gcrl_amd.TD3Agent, SAC=gcrl_amd.SACAgent, TQC=gcrl_amd.TQCAgent)[agent_name]
+    prior_kw, prior = {}, None
+    if prior_episodes or prior_rows:   # prior-data replay: prior_rows of every batch come from a second ring the agent never pushes into
+        if not (prior_episodes and prior_rows):
+            raise SystemExit("--prior-episodes and --prior-rows go together")
+        prior = gcrl_amd.HERBuffer(50 * prior_episodes, 50, 1, threshold=env.thr, k_future=cfg.k_future, rng="device", seed=seed,
+                                   relabel="sample", normalize=normalize)
+        prior.compute_reward = env.compute_reward
+        prior_kw = dict(prior_buffer=prior, prior_rows=prior_rows)
     agent = cls(env.obs_dim + env.goal_dim, env.ac_dim, cfg, None, nenvs=num_envs, gradient_step=gradient_step,
                 rng="engine", seed=seed, relabel=relabel, n_step=n_step, prioritise=prioritise, goal_strategy=goal_strategy,
-                normalize=normalize)
+                normalize=normalize, **prior_kw)
     # what GoalEnvHER.__init__ injects (src/env.py:93-105)
     agent.buffer.obs_normalizer = RunningNormalizer(env.obs_dim)
     agent.buffer.dg_normalizer = RunningNormalizer(env.goal_dim)
     agent.buffer.compute_reward = env.compute_reward
+    if prior is not None:
+        fill_prior_ring(agent, prior, prior_episodes, normalize, seed)
 
     state, _ = env.reset()
     grad_counter, env_steps = 1, 0
@@ -179,10 +218,14 @@ if __name__ == "__main__":
     ap.add_argument("--normalize", default="push", choices=["push", "sample"],
                     help="push: rows are stored normalised with the statistics of the moment of the push (the reference's form); sample (with "
                          "--fused): rows are stored raw and every gathered batch is normalised with the statistics of that moment")
+    ap.add_argument("--prior-episodes", type=int, default=0,
+                    help="fill a prior ring with this many scripted episodes of the synthetic goal environment (with --prior-rows)")
+    ap.add_argument("--prior-rows", type=int, default=0,
+                    help="rows of every batch that come from the prior ring, 1 .. batch - 1 (prior-data replay; the batch is 256)")
     args = ap.parse_args()
     out = train(args.agent, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, per_env_push=args.per_env_push, fused=args.fused,
                 relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy,
-                normalize=args.normalize)
+                normalize=args.normalize, prior_episodes=args.prior_episodes, prior_rows=args.prior_rows)
     tail = out["success_per_cycle"][-10:]
     print(f"{args.agent}: success over the last 10 cycles {np.mean(tail):.2f}; {out['env_steps']} env steps "
           f"({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} gradient steps "

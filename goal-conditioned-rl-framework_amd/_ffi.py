@@ -260,6 +260,11 @@ PROTOTYPES = {
     "gcrl_her_prio_draw": (C.c_int, [_vp, _i64, _vp, _vp]),
     "gcrl_her_get_prio_counter": (_u64, [_vp]),
     "gcrl_her_set_prio_counter": (C.c_int, [_vp, _u64]),
+    "gcrl_agent_set_prior": (C.c_int, [_vp, _vp, C.c_int]),
+    "gcrl_agent_get_prior": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
+    "gcrl_agent_prior_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_agent_read_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "gcrl_her_gather_update_mixed": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gcrl_event_create": (_vp, []),
     "gcrl_event_destroy": (None, [_vp]),
     "gcrl_event_record": (C.c_int, [_vp, _vp]),

@@ -32,6 +32,7 @@
 #include "dw_adam.h"
 #include "gemm_mfma.h"
 #include "her_ring.h"
+#include "her_prior.h"
 #include "per_tree.h"
 #include "meet.h"
 #include "ops.h"
@@ -235,6 +236,16 @@ struct gcrl_agent {
   // update_n: batches 1..n-1 are drawn / uploaded / gathered AFTER the first step's launches have been issued (the host
   // draws ~2 us per batch from the MT stream: with all n batches up front the GPU idled ~40 us at the start of a cycle)
   struct { gcrl_her* her = nullptr; int n = 0; int slot = 0; int next = 0; } deferred;   // batches [next, n) not yet drawn
+  // prior-data replay (her_prior.hip; gcrl_agent_set_prior): rows [B - prior_rows, B) of every gathered batch come from this ring
+  // (borrowed), through the scratch batch [Mmax * prior_rows] rows.  prior_deferred: its counters of the call whose rest is deferred.
+  gcrl_her* prior = nullptr;
+  int prior_rows = 0;
+  float* prior_block = nullptr;
+  PriorScratch prior_sc;
+  PriorSnap prior_deferred;
+  bool prior_deferred_on = false;
+  int64_t prior_gathers = 0, prior_places = 0;
+  PriorPlace prior_place() const { return PriorPlace{B, prior_rows, ldx, slot_x, slot_rd}; }
   int head_batches = 2;       // batches drawn and gathered before a call's first launch (the rest: behind that many queued steps)
   bool main_idx_staged = false;   // the main gather's indices as a staged copy (round 5's form) instead of read from the pinned block
   std::vector<StepPlan> dp_plans;  // steps of the data-parallel cycle begun by gcrl_agent_dp_begin
@@ -1116,6 +1127,24 @@ int stage_injected(gcrl_agent* a, const gcrl_update_inputs* in, hipStream_t st, 
   return GCRL_OK;
 }
 
+// prior-data replay: batches [b0, b0 + nb) of the call whose prior-ring counters `snap` holds — the prior ring's gather into the
+// scratch and the placement over the tail rows of those batch slots (her_prior.hip): two launches behind the main gather's
+int prior_issue(gcrl_agent* a, const PriorSnap& snap, int b0, int nb, double gamma, hipStream_t st) {
+  if (b0 < 0 || nb < 1 || b0 + nb > a->Mmax) return fail(GCRL_ERR_STATE, "update: prior_rows: batches [%d, %d) outside the %d batch slots", b0, b0 + nb, a->Mmax);
+  TRY(her_prior_gather_place(a->prior, snap, b0, nb, gamma, a->prior_sc, a->sa, a->nsa, a->rowchain ? nullptr : a->spa, a->rbuf, a->dbuf,
+                             a->prior_place(), st));
+  a->prior_gathers++;
+  a->prior_places++;
+  return GCRL_OK;
+}
+
+// what an update call asks of the agent's prior ring against the ring it gathers from: before a ticket, slot or counter is consumed
+int prior_precheck(const gcrl_agent* a, const gcrl_her* her, const char* who) {
+  if (!a->prior) return GCRL_OK;
+  if (a->xchg) return fail(GCRL_ERR_STATE, "%s: prior_buffer: an agent with a prior ring does not run under a gradient exchange", who);
+  return her_prior_check_call(her, a->prior, a->prior_rows, who);
+}
+
 // phase-0 entry of `n` steps: control table + indices upload, batch gather / pack
 // Draw and gather the batches a call left for later ([deferred.next, n); same MT stream order as drawing them all up
 // front).  Called once the head's steps have been issued, so that the GPU has more work queued than the host needs for the
@@ -1146,6 +1175,10 @@ int finish_deferred_draw(gcrl_agent* a, hipStream_t st) {
                         a->nsa + first * a->slot_x, a->rowchain ? nullptr : a->spa + first * a->slot_x, a->ldx,
                         a->rbuf + first * a->slot_rd, a->dbuf + first * a->slot_rd, st, nullptr, nullptr, 0, nullptr, &a->cfg.gamma));   // (n-step returns: the head gather's gamma)
   if (!staged) GCRL_HIP(hipEventRecord(a->upload_ev[a->deferred.slot], st));   // the pinned block is free once the gather has read it
+  if (a->prior_deferred_on) {   // prior-data replay: the same batches' tail rows, behind the main gather
+    a->prior_deferred_on = false;
+    TRY(prior_issue(a, a->prior_deferred, first, n - first, a->cfg.gamma, st));
+  }
   return GCRL_OK;
 }
 
@@ -1160,6 +1193,9 @@ struct CallGather {
   bool host_idx = false;
   bool prio = false;           // the ring's energy tree draws the call's rows into idx_dev() ahead of the gather (her_prio.hip)
   uint64_t prio_c0 = 0;        // ... from this row of the ring's draw stream on (snapshotted and advanced at plan time, like g.ctr)
+  bool prior = false;          // prior-data replay: the tail rows of batches [0, prior_nb) follow the gather (her_prior.hip)
+  int prior_nb = 0;
+  PriorSnap prior_snap;        // the prior ring's counters as of this member's turn (snapshotted and advanced at plan time, after the main ring's)
   int slot = 0;
   UploadBlock* ub = nullptr;
   const uint32_t* idx_pinned = nullptr;
@@ -1185,6 +1221,8 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     if (a->xchg) return fail(GCRL_ERR_STATE, "update: normalize: a ring that stores raw rows (normalize=\"sample\") does not feed an agent under a gradient exchange");
     TRY(her_norm_check(her, "update"));
   }
+  const bool use_prior = a->prior && !injected && !(in && in->idx_host);   // injected batches and caller-given rows bypass the prior part
+  if (use_prior) TRY(prior_precheck(a, her, "update"));   // refused before a ticket, slot or plan is consumed
   const bool prio = !injected && !(in && in->idx_host) && her_prio_on(her);   // a third index source beside the MT upload and the in-kernel IdxGen
   if (prio) {   // refused before a ticket, slot or plan is consumed
     if (a->xchg) return fail(GCRL_ERR_STATE, "update: prioritise: a ring with an energy tree does not feed an agent under a gradient exchange");
@@ -1258,6 +1296,13 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     her->relabel_ctr += (uint64_t)rows_now;
   }
   g.sa = a->sa; g.nsa = a->nsa; g.spa = a->rowchain ? nullptr : a->spa; g.ldx = a->ldx; g.r = a->rbuf; g.d = a->dbuf;
+  cg->prior = use_prior;
+  a->prior_deferred_on = use_prior && a->deferred.her != nullptr;
+  if (use_prior) {   // after the main ring's counters: rings shared between agents or members are consumed in call order
+    cg->prior_snap = her_prior_take(a->prior, n, a->prior_rows);
+    cg->prior_nb = a->deferred.her ? a->deferred.next : n;
+    if (a->prior_deferred_on) a->prior_deferred = cg->prior_snap;
+  }
   return GCRL_OK;
 }
 
@@ -1282,6 +1327,7 @@ int begin_call_issue(gcrl_agent* a, CallGather* cg, hipStream_t st) {
     GCRL_HIP(hipEventRecord(a->upload_ev[cg->slot], st));
     if (!cg->injected && !cg->per_dev) TRY(her_gather_update(g.h, g.idx, g.n, g.sa, g.nsa, g.spa, g.ldx, g.r, g.d, st, nullptr, nullptr, 0, &g.ctr, &g.gamma));
   }
+  if (cg->prior) TRY(prior_issue(a, cg->prior_snap, 0, cg->prior_nb, g.gamma, st));
   return GCRL_OK;
 }
 
@@ -1319,6 +1365,8 @@ int begin_call_issue_pop(gcrl_agent* const* m, CallGather* cg, int P, bool merge
   TRY(her_gather_update_pop(calls, P, st, merged));
   if (head)
     for (int i = 0; i < P; ++i) GCRL_HIP(hipEventRecord(m[i]->upload_ev[cg[i].slot], st));
+  for (int i = 0; i < P; ++i)   // prior-data replay: member by member behind the merged main launch, each with the counters of its turn
+    if (cg[i].prior) TRY(prior_issue(m[i], cg[i].prior_snap, 0, cg[i].prior_nb, cg[i].g.gamma, st));
   return GCRL_OK;
 }
 
@@ -1748,6 +1796,7 @@ void gcrl_agent_destroy(gcrl_agent* a) {
   if (a->metrics_host) (void)hipHostFree(a->metrics_host);
   if (a->metrics_dev) (void)hipFree(a->metrics_dev);
   if (a->prof_clk) (void)hipFree(a->prof_clk);
+  if (a->prior_block) (void)hipFree(a->prior_block);
   if (a->bn_sync_buf) (void)hipFree(a->bn_sync_buf);
   if (a->act_pinned) (void)hipHostFree(a->act_pinned);
   if (a->oa_pinned) (void)hipHostFree(a->oa_pinned);
@@ -2223,6 +2272,56 @@ gcrl_xchg* gcrl_agent_xchg_create(gcrl_agent* a, int rank, int world) {
   gcrl_xchg* x = gcrl_xchg_create(a->grads, a->n_grads, off.data(), n.data(), (int)off.size(), rank, world, a->cfg.device);
   if (x) gcrl_xchg_set_status(x, a->status_dev);
   return x;
+}
+
+int gcrl_agent_set_prior(gcrl_agent* a, gcrl_her* prior, int rows) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_set_prior: null handle");
+  if (!prior) {
+    GCRL_CHECK_ARG(rows == 0, "gcrl_agent_set_prior: prior_rows: %d rows without a prior_buffer", rows);
+    a->prior = nullptr; a->prior_rows = 0; a->prior_deferred_on = false;
+    return GCRL_OK;
+  }
+  TRY(her_prior_check_ring(prior, a->S, a->A, a->B, rows, "gcrl_agent_set_prior"));
+  if (!a->prior_block || rows != a->prior_rows) {   // the scratch batch, once per row count: [Mmax * rows] rows of sa, nsa, spa, r, d
+    GCRL_HIP(hipDeviceSynchronize());
+    if (a->prior_block) { (void)hipFree(a->prior_block); a->prior_block = nullptr; }
+    const size_t n = (size_t)a->Mmax * rows, xf = n * (size_t)a->ldx;
+    const int nx = a->rowchain ? 2 : 3;
+    const size_t bytes = (nx * xf + 2 * n) * sizeof(float);
+    GCRL_HIP(hipMalloc((void**)&a->prior_block, bytes));
+    GCRL_HIP(hipMemset(a->prior_block, 0, bytes));
+    PriorScratch& sc = a->prior_sc;
+    sc.sa = a->prior_block; sc.nsa = sc.sa + xf; sc.spa = a->rowchain ? nullptr : sc.nsa + xf;
+    sc.r = a->prior_block + nx * xf; sc.d = sc.r + n;
+  }
+  a->prior = prior; a->prior_rows = rows; a->prior_deferred_on = false;
+  return GCRL_OK;
+}
+
+int gcrl_agent_get_prior(const gcrl_agent* a, gcrl_her** prior_out, int* rows_out) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_get_prior: null handle");
+  if (prior_out) *prior_out = a->prior;
+  if (rows_out) *rows_out = a->prior_rows;
+  return GCRL_OK;
+}
+
+int gcrl_agent_prior_counts(const gcrl_agent* a, int64_t* prior_gathers, int64_t* placements) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_prior_counts: null handle");
+  if (prior_gathers) *prior_gathers = a->prior_gathers;
+  if (placements) *placements = a->prior_places;
+  return GCRL_OK;
+}
+
+int gcrl_agent_read_batch(gcrl_agent* a, int slot, float* sa, float* nsa, float* r, float* d) {
+  GCRL_CHECK_ARG(a && sa && nsa && r && d, "gcrl_agent_read_batch: null argument");
+  GCRL_CHECK_ARG(slot >= 0 && slot < a->Mmax, "gcrl_agent_read_batch: slot %d of %d", slot, a->Mmax);
+  GCRL_HIP(hipDeviceSynchronize());
+  const size_t xb = (size_t)a->B * a->ldx * sizeof(float), rb = (size_t)a->B * sizeof(float);
+  GCRL_HIP(hipMemcpy(sa, a->sa + slot * a->slot_x, xb, hipMemcpyDeviceToHost));
+  GCRL_HIP(hipMemcpy(nsa, a->nsa + slot * a->slot_x, xb, hipMemcpyDeviceToHost));
+  GCRL_HIP(hipMemcpy(r, a->rbuf + slot * a->slot_rd, rb, hipMemcpyDeviceToHost));
+  GCRL_HIP(hipMemcpy(d, a->dbuf + slot * a->slot_rd, rb, hipMemcpyDeviceToHost));
+  return GCRL_OK;
 }
 
 int gcrl_agent_set_exchange(gcrl_agent* a, gcrl_xchg* x) {

@@ -375,6 +375,7 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
       return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: prioritise: member %d's ring has an energy tree; populations do not draw from one", i);
     GCRL_CHECK_ARG(!a->xchg && a->bn_sync.world <= 1, "gcrl_pop_update_n: member %d is in a data-parallel group", i);
     GCRL_CHECK_ARG(!a->prof, "gcrl_pop_update_n: member %d has launch profiling on", i);
+    TRY(prior_precheck(a, rings[i], "gcrl_pop_update_n"));   // prior-data replay: every member's prior ring, before any member's ticket
     // (members may share a ring: its index stream — the ring's generator, or draws_done in device-RNG mode — is then consumed in
     // member order, as by standalone agents that share the ring and are called in that order)
     // a process that arrived on this device after the handle was built: the forms with waits go off (as gcrl_agent_update_n)

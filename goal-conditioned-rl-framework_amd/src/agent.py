@@ -23,7 +23,7 @@ import torch
 from .. import _ffi
 from .._ffi import lib
 from .buffer import (HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_goal_strategy, _check_normalize,
-                     _check_nstep)
+                     _check_nstep, _check_prior)
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -189,7 +189,8 @@ class _EngineAgent:
                  seed: int | None = None, device_index: int = 0, num_critics: int = 5,
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
                  n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
-                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, _member=None):
+                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, prior_buffer=None,
+                 prior_rows: int | None = None, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -208,6 +209,17 @@ class _EngineAgent:
         # (buffer.HERBuffer); `obs_normalize` / `g_normalize` are then the flags `observe_act` and `process_step` must be called with.
         self.normalize = _check_normalize(type(self).__name__, normalize, obs_normalize, g_normalize, config.buffer_type)
         self.obs_normalize, self.g_normalize = bool(obs_normalize), bool(g_normalize)
+        # prior_buffer=<HERBuffer, rng="device">, prior_rows=Bd (1..batch_size - 1): prior-data replay.  Rows [B - Bd, B) of every batch
+        # the engine gathers from the agent's ring are the prior ring's own gather of Bd rows per batch, the other rows exactly those
+        # of an agent without the keywords (csrc/her_prior.hip; tests/her_prior_ref.py is the definition).  The agent never pushes into
+        # the prior ring: fill it with push_episode / push, at any time between calls.  Every refusal here before any device work.
+        self.prior_rows = _check_prior(type(self).__name__, prior_buffer, prior_rows, config.batch_size, config.buffer_type, self.normalize)
+        if prior_buffer is not None and self.normalize == "sample" and (
+                bool(prior_buffer.obs_normalize), bool(prior_buffer.g_normalize)) != (self.obs_normalize, self.g_normalize):
+            raise _ffi.GcrlError(f"{type(self).__name__}: prior_buffer: normalize='sample' normalises the prior ring's rows with this agent's "
+                                 f"statistics: its obs_normalize / g_normalize must be {self.obs_normalize!r} / {self.g_normalize!r}")
+        self.prior_buffer = prior_buffer
+        self._prior_bound = None              # (prior ring handle, rows) the engine holds
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -346,6 +358,45 @@ class _EngineAgent:
         everywhere (GCRL_RC_GLOBAL_MUL=1, a shape the LDS rule refuses, or an agent without that launch).  Changes nothing."""
         return _ffi.check(lib.gcrl_agent_rowchain_form(self._h))
 
+    # ------------------------------------------------------------------ prior-data replay
+    def _bind_prior(self):
+        """Tell the engine which ring the tail rows of the next call's batches come from (gcrl_agent_set_prior); called by every update
+        entry before anything is consumed.  The prior ring exists once it holds rows; with normalize="sample" it is given this agent's
+        normalisers, so that its rows leave through its own pass with the same statistics."""
+        pb = self.prior_buffer
+        if pb is None:
+            if self._prior_bound is not None:
+                _ffi.check(lib.gcrl_agent_set_prior(self._h, None, 0))
+                self._prior_bound = None
+            return
+        if pb.handle is None or len(pb) < self.prior_rows:
+            raise _ffi.NotEnoughSamples(f"[ERROR] Not enough in buffer to sample (prior_buffer holds {len(pb)} rows, prior_rows = {self.prior_rows})")
+        if self.normalize == "sample":
+            for name in ("obs_normalizer", "dg_normalizer"):
+                mine = getattr(self.buffer, name, None)
+                if mine is not None and getattr(pb, name) is not mine:
+                    setattr(pb, name, mine)
+        key = (pb.handle, self.prior_rows)
+        if self._prior_bound != key:
+            _ffi.check(lib.gcrl_agent_set_prior(self._h, pb.handle, self.prior_rows))
+            self._prior_bound = key
+
+    def prior_counts(self):
+        """(prior_gathers, placements): gathers of the prior ring and placement launches issued since the agent was created — one of
+        each per gather part, at most two parts per call (include/gcrl.h gcrl_agent_prior_counts); (0, 0) without a prior ring."""
+        g, p = C.c_int64(0), C.c_int64(0)
+        _ffi.check(lib.gcrl_agent_prior_counts(self._h, C.byref(g), C.byref(p)))
+        return int(g.value), int(p.value)
+
+    def read_batch(self, slot: int):
+        """Batch slot `slot` of the last update call as numpy arrays (sa, nsa, r, d) (include/gcrl.h gcrl_agent_read_batch; synchronises;
+        for tests and tools).  nsa's columns from the state width on hold what the steps left there."""
+        B, ldx = int(self.batch_size), (self.obs_dim + self.ac_dim + 3) // 4 * 4
+        sa, nsa = np.empty((B, ldx), np.float32), np.empty((B, ldx), np.float32)
+        r, d = np.empty(B, np.float32), np.empty(B, np.float32)
+        _ffi.check(lib.gcrl_agent_read_batch(self._h, int(slot), sa.ctypes.data, nsa.ctypes.data, r.ctypes.data, d.ctypes.data))
+        return sa, nsa, r, d
+
     # ------------------------------------------------------------------ update
     def _metrics(self, ticket: int, n: int):
         vals = self._metric_cache.get(ticket)
@@ -425,6 +476,7 @@ class _EngineAgent:
         if batch is None:
             her = self.buffer.handle
             assert her is not None and len(self.buffer) >= self.batch_size, "[ERROR] Not enough in buffer to sample"
+            self._bind_prior()
             self.buffer.rng.pull()
         ticket = C.c_int64(-1)
         n = _ffi.check(lib.gcrl_agent_update(self._h, her, int(step), C.byref(inputs) if inputs is not None else None,
@@ -497,9 +549,12 @@ class _EngineAgent:
         assert her is not None and len(self.buffer) >= self.batch_size, "[ERROR] Not enough in buffer to sample"
         tickets = (C.c_int64 * n)()
         lens = (C.c_int32 * n)()
+        self._bind_prior()
         self.buffer.rng.pull()
-        _ffi.check(lib.gcrl_agent_update_n(self._h, her, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
-        self.buffer.rng.push_back()
+        try:
+            _ffi.check(lib.gcrl_agent_update_n(self._h, her, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
+        finally:
+            self.buffer.rng.push_back()
         self.beta_scheduler(step0 + n - 1)
         if self._sac:
             self.actor.num_batches_tracked += sum(1 + (1 if l == 9 else 0) for l in lens)
@@ -739,6 +794,8 @@ class _EngineAgent:
         blob.tofile(os.path.join(path, "agent.bin"))
         meta = dict(kind=self.KIND_NAME, beta=self.beta, num_batches_tracked=int(self.actor.num_batches_tracked),
                     ring=self.buffer.save_state(os.path.join(path, "ring.bin")))
+        if self.prior_buffer is not None:     # prior-data replay: the prior ring next to the main ring, through the same path
+            meta["prior"] = dict(rows=int(self.prior_rows), ring=self.prior_buffer.save_state(os.path.join(path, "prior_ring.bin")))
         for name in ("obs_normalizer", "dg_normalizer"):
             nz = getattr(self.buffer, name, None)
             if nz is not None:
@@ -755,11 +812,21 @@ class _EngineAgent:
             meta = json.load(f)
         if meta["kind"] != self.KIND_NAME:      # checked before anything of this agent is overwritten
             raise ValueError(f"state of a {meta['kind']} agent loaded into a {self.KIND_NAME}")
+        saved_prior = meta.get("prior")
+        if (saved_prior is None) != (self.prior_buffer is None):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prior_buffer: the state was saved "
+                                 f"{'with' if saved_prior is not None else 'without'} a prior ring, this agent was built "
+                                 f"{'with' if self.prior_buffer is not None else 'without'} one")
+        if saved_prior is not None and int(saved_prior["rows"]) != int(self.prior_rows):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prior_rows: the state was saved with prior_rows={saved_prior['rows']}, "
+                                 f"this agent has prior_rows={self.prior_rows}")
         blob = np.fromfile(os.path.join(path, "agent.bin"), dtype=np.uint8)
         _ffi.check(lib.gcrl_agent_load_state(self._h, blob.ctypes.data, blob.size))
         self.beta = meta["beta"]
         self.actor.num_batches_tracked = meta["num_batches_tracked"]
         self.buffer.load_state(os.path.join(path, "ring.bin"), meta["ring"])
+        if saved_prior is not None:
+            self.prior_buffer.load_state(os.path.join(path, "prior_ring.bin"), saved_prior["ring"])
         for name in ("obs_normalizer", "dg_normalizer"):
             nz = getattr(self.buffer, name, None)
             if name in meta and nz is not None:

@@ -181,6 +181,33 @@ def _check_normalize(who: str, normalize, obs_normalize, g_normalize, buffer_typ
     return normalize
 
 
+def _check_prior(who: str, prior_buffer, prior_rows, batch_size: int, buffer_type: str = "HER", normalize: str = "push"):
+    """-> prior_rows as the engine takes it (0 without a prior ring), or a GcrlError that names prior_buffer or prior_rows; before any
+    device work.  The ring's dims and length are known only once it holds rows: the update call asks for them (include/gcrl.h)."""
+    if prior_buffer is None and prior_rows is None:
+        return 0
+    if prior_buffer is None:
+        raise _ffi.GcrlError(f"{who}: prior_buffer: prior_rows={prior_rows!r} was given without a prior_buffer")
+    if prior_rows is None:
+        raise _ffi.GcrlError(f"{who}: prior_rows: a prior_buffer was given without prior_rows (1..batch_size - 1)")
+    if not isinstance(prior_buffer, HERBuffer):
+        raise _ffi.GcrlError(f"{who}: prior_buffer: must be a HERBuffer, got a {type(prior_buffer).__name__}")
+    if isinstance(prior_rows, bool) or not isinstance(prior_rows, (int, np.integer)) or not 1 <= int(prior_rows) <= int(batch_size) - 1:
+        raise _ffi.GcrlError(f"{who}: prior_rows: must be an integer in 1..batch_size - 1 = {int(batch_size) - 1}, got {prior_rows!r}")
+    if buffer_type != "HER":
+        raise _ffi.GcrlError(f"{who}: prior_buffer: prior rows are mixed into batches gathered from a HER ring; buffer_type is {buffer_type!r}")
+    if prior_buffer.rng.mode != "device":
+        raise _ffi.GcrlError(f"{who}: prior_buffer: the prior ring's gather computes its own row indices and needs rng='device', "
+                             f"got rng={prior_buffer.rng.mode!r}")
+    if getattr(prior_buffer, "prioritise", None) is not None:
+        raise _ffi.GcrlError(f"{who}: prior_buffer: the prior ring carries a priority tree (prioritise={prior_buffer.prioritise!r}); it is "
+                             "drawn uniformly")
+    if getattr(prior_buffer, "normalize", "push") != normalize:
+        raise _ffi.GcrlError(f"{who}: prior_buffer: normalize={normalize!r} here but the prior ring has "
+                             f"normalize={getattr(prior_buffer, 'normalize', 'push')!r}: raw and normalised rows would share a batch")
+    return int(prior_rows)
+
+
 PRIORITISE_MODES = (None, "energy")
 # prioritise="energy": the constants of the episode energy (tests/her_energy_ref.py is the definition).  The defaults are this
 # project's choice — m = 1: potential = m g = 9.81, kinetic = m / (2 dt^2) with dt = 0.04, axis 2 = the height of a 3-component goal
@@ -668,6 +695,31 @@ class HERBuffer(_RingState):
             self.rng.push_back()
         out = (sa, nsa, sp, r, d)
         return out + (side_out,) if side is not None else out
+
+    def gather_update_mixed(self, prior, prior_rows: int, batch_size: int, num_batches: int = 1, spa: bool = False):
+        """`gather_update(batch_size, num_batches)` of this ring with rows [batch_size - prior_rows, batch_size) of every batch
+        replaced by the `prior` ring's own `gather_update(prior_rows, num_batches)` (include/gcrl.h gcrl_her_gather_update_mixed;
+        tests/her_prior_ref.py is the definition): what an agent built with `prior_buffer=` / `prior_rows=` trains on, without the
+        agent.  -> (sa, nsa, spa or None, r, d) as `gather_update`.  Both rings' counters advance as by their own gathers."""
+        prior_rows = _check_prior("HERBuffer.gather_update_mixed", prior, prior_rows, batch_size, "HER", self.normalize)
+        assert len(self) >= batch_size, "[ERROR] Not enough in buffer to sample"
+        if prior.handle is None:
+            raise _ffi.NotEnoughSamples("[ERROR] Not enough in buffer to sample (prior_buffer holds no rows yet)")
+        S, A, _ = self._dims
+        n, ldx = batch_size * num_batches, (S + A + 3) // 4 * 4
+        dev = torch.device("cuda", self.device_index)
+        sa = torch.empty((n, ldx), dtype=torch.float32, device=dev)
+        nsa = torch.empty((n, ldx), dtype=torch.float32, device=dev)
+        sp = torch.full((n, ldx), float("nan"), dtype=torch.float32, device=dev) if spa else None
+        r = torch.empty(n, dtype=torch.float32, device=dev)
+        d = torch.empty(n, dtype=torch.float32, device=dev)
+        self.rng.pull()
+        try:
+            _ffi.check(lib.gcrl_her_gather_update_mixed(self._h, prior.handle, batch_size, prior_rows, num_batches, sa.data_ptr(), nsa.data_ptr(),
+                                                        sp.data_ptr() if spa else None, ldx, r.data_ptr(), d.data_ptr(), _ffi.stream_handle()))
+        finally:
+            self.rng.push_back()
+        return sa, nsa, sp, r, d
 
     def tails(self, first: int = 0, count: int | None = None):
         """relabel="sample": the tails of ring rows in logical order — (ag [n, G], remaining [n]) — for tests and state."""

@@ -21,7 +21,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import lib
 from .agent import DDPG, KIND, SACAgent, TD3Agent, TQCAgent, check_hyperparameters, native_config
-from .buffer import HERBuffer, MTStream, _check_goal_strategy, _check_normalize, _check_nstep
+from .buffer import HERBuffer, MTStream, _check_goal_strategy, _check_normalize, _check_nstep, _check_prior
 
 MAX_MEMBERS = 16
 MAX_PAIRS = 16          # (source, destination) pairs of one `exploit` call
@@ -32,6 +32,27 @@ MANIFEST = "population.json"
 SHARED = ("hidden_dim", "layer_count", "batch_size", "ac_update_freq")
 # the replay ring's own settings: with `shared_ring` there is one ring, built from member 0's, so these must agree too
 RING_FIELDS = ("max_len", "max_eps_len", "k_future")
+
+
+def check_shared_prior_normalizers(who: str, members):
+    """normalize="sample": a prior ring normalises what it gathers with the normalisers bound to IT, and a population binds every
+    member's prior ring before the one native call that issues all members' prior parts.  Members that share a prior ring must
+    therefore share the normaliser objects their flags need (`shared_ring=True` does; so does assigning one pair to every member):
+    otherwise all but the last member's prior rows would leave with another member's statistics.  Refused naming prior_buffer,
+    before anything is bound or consumed.  Standalone agents that share a prior ring are not concerned: each rebinds before its
+    own call."""
+    first = {}
+    for i, m in enumerate(members):
+        pb = getattr(m, "prior_buffer", None)
+        if pb is None or getattr(m, "normalize", "push") != "sample":
+            continue
+        mine = (getattr(m.buffer, "obs_normalizer", None) if m.obs_normalize else None,
+                getattr(m.buffer, "dg_normalizer", None) if m.g_normalize else None)
+        j, theirs = first.setdefault(id(pb), (i, mine))
+        if any(a is not b for a, b in zip(theirs, mine)):
+            raise _ffi.GcrlError(f"{who}: prior_buffer: members {j} and {i} share one prior ring but not their normalisers; with "
+                                 "normalize='sample' the ring's rows leave with the statistics bound to it, so members that share it "
+                                 "must share the same obs_normalizer / dg_normalizer objects (shared_ring=True, or one prior ring per member)")
 
 
 class _PopHandle:
@@ -75,7 +96,8 @@ class _Population:
     def __init__(self, obs_dim: int, ac_dim: int, configs, nenvs: int, gradient_step: int, *, rng: str = "python",
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
                  relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None,
-                 goal_strategy: str = "future", normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False):
+                 goal_strategy: str = "future", normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False,
+                 prior_buffer=None, prior_rows: int | None = None):
         # prioritise: accepted only to be refused by name — the energy-prioritised draw (buffer.HERBuffer) is a single-agent mode
         if prioritise is not None or energy is not None:
             self._refuse("prioritise", f"populations (and their shared ring) do not draw from an energy tree, got prioritise={prioritise!r}")
@@ -93,6 +115,16 @@ class _Population:
         for c in configs or [None]:
             self.normalize = _check_normalize(type(self).__name__, normalize, obs_normalize, g_normalize, getattr(c, "buffer_type", "HER"))
         self.obs_normalize, self.g_normalize = bool(obs_normalize), bool(g_normalize)
+        # prior_buffer / prior_rows: prior-data replay for every member (agent._EngineAgent) — ONE prior ring shared by all members
+        # (read only, consumed in member order) or a list of one ring per member.  The main gathers keep merging as before; the
+        # members' prior parts follow them member by member.  `exploit(copy_ring=True)` leaves prior rings alone.
+        priors = list(prior_buffer) if isinstance(prior_buffer, (list, tuple)) else [prior_buffer] * max(1, len(configs))
+        if isinstance(prior_buffer, (list, tuple)) and len(priors) != len(configs):
+            self._refuse("prior_buffer", f"{len(priors)} prior rings for {len(configs)} members (one shared ring, or one per member)")
+        for c, pb in zip(configs or [None], priors):
+            self.prior_rows = _check_prior(type(self).__name__, pb, prior_rows, getattr(c, "batch_size", 2), getattr(c, "buffer_type", "HER"),
+                                           self.normalize)
+        self.prior_buffers = priors if prior_buffer is not None else None
         # n_step=N: every member's ring (or the shared one) gathers n-step windows; each member's update calls discount by its own gamma
         if n_step != 1:
             for i, c in enumerate(configs):
@@ -130,7 +162,9 @@ class _Population:
         for i, (c, s) in enumerate(zip(configs, seeds)):
             self.members.append(self.AGENT(obs_dim, ac_dim, c, None, nenvs, gradient_step, rng=rng, seed=s, device_index=device_index, relabel=relabel,
                                            n_step=self.n_step, goal_strategy=self.goal_strategy, normalize=self.normalize, obs_normalize=self.obs_normalize,
-                                           g_normalize=self.g_normalize, _member=lambda cfg, i=i: (pop, pop.member(i))))
+                                           g_normalize=self.g_normalize, prior_buffer=priors[i] if prior_buffer is not None else None,
+                                           prior_rows=prior_rows if prior_buffer is not None else None,
+                                           _member=lambda cfg, i=i: (pop, pop.member(i))))
         self.rng_mode = rng
         self._merge_gather = False
         if P >= self.MERGE_GATHER_FROM:
@@ -169,13 +203,18 @@ class _Population:
             her = m.buffer.handle
             assert her is not None and len(m.buffer) >= m.batch_size, f"[ERROR] Not enough in buffer to sample (member {i})"
             rings[i] = her
+        check_shared_prior_normalizers(type(self).__name__, self.members)
+        for m in self.members:     # prior-data replay: every member's prior ring is bound before any member's call is planned
+            m._bind_prior()
         tickets = (C.c_int64 * (P * n))()
         lens = (C.c_int32 * (P * n))()
         if self._shared_rng is not None:
             self._shared_rng.pull()
-        _ffi.check(lib.gcrl_pop_update_n(self._pop.h, rings, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
-        if self._shared_rng is not None:
-            self._shared_rng.push_back()
+        try:
+            _ffi.check(lib.gcrl_pop_update_n(self._pop.h, rings, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
+        finally:
+            if self._shared_rng is not None:
+                self._shared_rng.push_back()
         out = []
         for i, m in enumerate(self.members):
             m.beta_scheduler(step0 + n - 1)
@@ -569,6 +608,9 @@ class _Population:
         import os
         if getattr(self, "shared_ring", False):
             self._refuse("shared_ring", "save_state of a population with one shared replay ring is not supported yet")
+        pbs = getattr(self, "prior_buffers", None)
+        if pbs is not None and len({id(b) for b in pbs}) < len(pbs):
+            self._refuse("prior_buffer", "save_state of a population whose members share a prior ring is not supported yet")
         os.makedirs(path, exist_ok=True)
         for i, m in enumerate(self.members):
             m.save_state(os.path.join(path, f"member_{i:02d}"))

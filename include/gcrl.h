@@ -978,6 +978,43 @@ int gcrl_her_prio_draw(gcrl_her* h, int64_t rows, uint32_t* idx_dev, void* strea
 uint64_t gcrl_her_get_prio_counter(const gcrl_her* h);
 int gcrl_her_set_prio_counter(gcrl_her* h, uint64_t counter);
 
+/* ---- Prior-data replay: a fixed share of every batch from a second ring (csrc/her_prior.hip; DESIGN.md §4n;
+ * tests/her_prior_ref.py is the definition).  An agent with a prior ring bound assembles every batch of B rows it gathers from its
+ * own ring (gcrl_agent_update, gcrl_agent_update_n, gcrl_pop_update_n) so that
+ *   - rows [0, B - rows) are bit for bit the rows the same call gathers without a prior ring: the main ring still draws B rows
+ *     per batch, and its index stream, relabel counter and draw counter advance exactly as without one;
+ *   - rows [B - rows, B) of batch j are batch j of the prior ring's own gather of `rows` rows per batch: bit for bit what
+ *     gcrl_her_gather_update(prior, rows, n, NULL, ...) writes on a ring in the same state, with the agent's gamma as the discount
+ *     of n-step windows.  The prior ring relabels, selects goals and normalises as IT is configured; its relabel counter advances
+ *     by n * rows and its batch-draw counter by n, both snapshotted and advanced when the call is planned, after the main ring's.
+ * The prior ring's existing gather writes the rows of a gather part into a scratch batch of the agent and ONE launch of
+ * her_place_rows_kernel copies them over the tail rows of the batch slots: at most two extra launches per gather part, at most
+ * four per call (a GCRL_NORMALIZE_SAMPLE prior ring adds its own normalise pass over the scratch to each part: three and six;
+ * gcrl_agent_prior_counts counts the gathers and the placements).  Injected batches and caller-given row indices bypass the prior part.  The agent never pushes into the prior
+ * ring; the caller fills it, between calls.  Without a prior ring nothing changes and no new kernel is launched.  This is the
+ * symmetric sampling of RLPD and the replay half of "HER with demonstrations"; it is NOT the reference's sampling.
+ * gcrl_agent_set_prior binds (prior != NULL, 1 <= rows <= batch_size - 1) or unbinds (NULL, 0); the ring is borrowed.  Refused,
+ * naming prior_buffer or prior_rows — by gcrl_agent_set_prior (GCRL_ERR_ARG): rows outside 1..batch_size - 1; a ring whose rng
+ * mode is not GCRL_RNG_DEVICE (its gather computes its own indices: no second index upload); a ring with a priority tree of
+ * either kind; state or action widths other than the agent's — and by the update entries, before a ticket, an upload slot or a
+ * row of any stream is consumed: fewer than `rows` rows in the prior ring (GCRL_ERR_NOT_ENOUGH); a goal width or a normalize mode
+ * other than the main ring's, the main ring itself as its own prior, a main ring with a TD priority tree, an agent under a
+ * gradient exchange (GCRL_ERR_STATE; the last is caution, not a measured limit). */
+int gcrl_agent_set_prior(gcrl_agent* a, gcrl_her* prior, int rows);
+int gcrl_agent_get_prior(const gcrl_agent* a, gcrl_her** prior_out, int* rows_out);
+/* gathers of the prior ring and placement launches the agent has issued since creation (both 0 without a prior ring) */
+int gcrl_agent_prior_counts(const gcrl_agent* a, int64_t* prior_gathers, int64_t* placements);
+/* Batch slot `slot` (step `slot` of the last update call, 0 <= slot < min(gradient_step, 128)) as the call left it, to host arrays:
+ * sa, nsa [batch_size][roundup(S + A, 4)], r, d [batch_size]; for tests and tools.  Synchronises the device.  The steps overwrite
+ * nsa's columns from S on (the target policy's action); sa, nsa's state columns, r and d are the gathered batch. */
+int gcrl_agent_read_batch(gcrl_agent* a, int slot, float* sa, float* nsa, float* r, float* d);
+/* The same composition on two rings without an agent: gcrl_her_gather_update(main, B, M, NULL, outputs) followed by the prior ring's
+ * gather of Bd rows per batch and the placement over rows [B - Bd, B) of each of the M batches (sa / nsa / spa [M * B][ldx], spa may
+ * be NULL; r, d [M * B]).  Both rings' counters advance as by their own gathers.  The prior ring is held to the refusals above.
+ * Allocates and frees its scratch and synchronises the stream: for tests and tools. */
+int gcrl_her_gather_update_mixed(gcrl_her* main_ring, gcrl_her* prior, int B, int Bd, int M, float* sa, float* nsa, float* spa, int ldx,
+                                 float* r, float* d, void* stream);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);
