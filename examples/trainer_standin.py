@@ -98,7 +98,7 @@ def fill_prior_ring(agent, prior, episodes, normalize, seed):
 
 def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
           seed=0, verbose=True, per_env_push=False, fused=False, relabel="push", n_step=1, prioritise=None,
-          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0):
+          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0, bc_weight=None, q_filter=True):
     import gcrl_amd
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
@@ -123,6 +123,10 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
                                    relabel="sample", normalize=normalize)
         prior.compute_reward = env.compute_reward
         prior_kw = dict(prior_buffer=prior, prior_rows=prior_rows)
+    if bc_weight is not None:   # Q-filtered behaviour cloning on the prior rows (DDPG / TD3): the weight is the caller's; the library has no default
+        if prior is None:
+            raise SystemExit("--bc-weight acts on the prior rows: it needs --prior-episodes and --prior-rows")
+        prior_kw.update(bc_weight=bc_weight, q_filter=q_filter)
     agent = cls(env.obs_dim + env.goal_dim, env.ac_dim, cfg, None, nenvs=num_envs, gradient_step=gradient_step,
                 rng="engine", seed=seed, relabel=relabel, n_step=n_step, prioritise=prioritise, goal_strategy=goal_strategy,
                 normalize=normalize, **prior_kw)
@@ -194,6 +198,8 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
         success_per_cycle.append(float(np.mean(recent)))
         if verbose and cycle % 10 == 0:
             print(f"cycle {cycle:4d}  success(last {len(recent)} episodes) {success_per_cycle[-1]:.2f}  buffer {len(agent.buffer)}")
+            if bc_weight is not None and grad_counter > 1:
+                print("            bc_loss %.4g  accepted share of the prior rows %.2f" % agent.bc_metrics())
     wall = time.perf_counter() - t0
     return dict(success_per_cycle=success_per_cycle, env_steps=env_steps, gradient_steps=grad_counter - 1, wall_s=wall,
                 env_steps_per_s=env_steps / max(t_env, 1e-9), gradient_steps_per_s=(grad_counter - 1) / max(t_upd, 1e-9))
@@ -222,10 +228,16 @@ if __name__ == "__main__":
                     help="fill a prior ring with this many scripted episodes of the synthetic goal environment (with --prior-rows)")
     ap.add_argument("--prior-rows", type=int, default=0,
                     help="rows of every batch that come from the prior ring, 1 .. batch - 1 (prior-data replay; the batch is 256)")
+    ap.add_argument("--bc-weight", type=float, default=None,
+                    help="DDPG / TD3 with --prior-rows: weight of the behaviour-cloning term on the prior rows of every batch (> 0).  No default: "
+                         "the library has none, and any value used here is this example's choice, not a published setting")
+    ap.add_argument("--no-q-filter", action="store_true",
+                    help="with --bc-weight: clone every prior row, not only those whose stored action the critic rates above the actor's")
     args = ap.parse_args()
     out = train(args.agent, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, per_env_push=args.per_env_push, fused=args.fused,
                 relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy,
-                normalize=args.normalize, prior_episodes=args.prior_episodes, prior_rows=args.prior_rows)
+                normalize=args.normalize, prior_episodes=args.prior_episodes, prior_rows=args.prior_rows,
+                bc_weight=args.bc_weight, q_filter=not args.no_q_filter)
     tail = out["success_per_cycle"][-10:]
     print(f"{args.agent}: success over the last 10 cycles {np.mean(tail):.2f}; {out['env_steps']} env steps "
           f"({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} gradient steps "

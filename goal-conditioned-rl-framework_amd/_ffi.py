@@ -265,6 +265,11 @@ PROTOTYPES = {
     "gcrl_agent_prior_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_agent_read_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "gcrl_her_gather_update_mixed": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "gcrl_agent_set_bc": (C.c_int, [_vp, _f64, C.c_int, C.c_int]),
+    "gcrl_agent_get_bc": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
+    "gcrl_agent_bc_metrics": (C.c_int, [_vp, _i64, _vp]),
+    "gcrl_bc_qfilter_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _f64, _vp, C.c_int,
+                                      _vp, _vp, _vp]),
     "gcrl_event_create": (_vp, []),
     "gcrl_event_destroy": (None, [_vp]),
     "gcrl_event_record": (C.c_int, [_vp, _vp]),

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <string>
 
@@ -15,6 +16,7 @@
 
 #include "common.h"
 #include "gemm_mfma.h"
+#include "her_bc.h"
 #include "meet.h"
 #include "ops.h"
 
@@ -245,7 +247,7 @@ struct StageScratch {
     (void)hipStreamSynchronize(st);
     (void)hipFree(base);
   }
-  int init(hipStream_t stream, int do_alpha, float log_alpha, float alpha, size_t part_floats) {
+  int init(hipStream_t stream, int do_alpha, float log_alpha, float alpha, size_t part_floats, int batch_slot = 0) {
     st = stream;
     GCRL_HIP(hipMalloc((void**)&base, kPart + part_floats * sizeof(float)));
     char img[kPart];
@@ -253,6 +255,7 @@ struct StageScratch {
     gcrl::StepCtrl c;
     std::memset(&c, 0, sizeof(c));
     c.do_alpha = do_alpha;
+    c.batch_slot = batch_slot;
     std::memcpy(img, &c, sizeof(c));
     const float sc[2] = {log_alpha, alpha};
     std::memcpy(img + kScalars, sc, sizeof(sc));
@@ -306,6 +309,26 @@ int gcrl_td_loss_f32(const float* r, const float* d, const float* qt, const floa
     rc = gcrl::launch_td_loss(st, a);
   }
   return rc;
+}
+
+int gcrl_bc_qfilter_f32(const float* spa, const float* sa, int ldx, int col0, int slots, int slot, const float* q_pi, const float* q_a, int B, int Bd,
+                        int A, double bc_weight, float* dact, int ld_dact, float* mask, float* metrics, void* stream) {
+  GCRL_CHECK_ARG(spa && sa && q_pi && dact && metrics, "gcrl_bc_qfilter_f32: null argument");
+  GCRL_CHECK_ARG(slots >= 1 && slot >= 0 && slot < slots, "gcrl_bc_qfilter_f32: batch slot %d of %d", slot, slots);
+  GCRL_CHECK_ARG(std::isfinite(bc_weight) && bc_weight > 0.0, "gcrl_bc_qfilter_f32: bc_weight: %g is not a finite weight > 0", bc_weight);
+  hipStream_t st = as_stream(stream);
+  gcrl::BcArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.spa = spa; a.sa = sa; a.slot_x = (long long)B * ldx; a.ldx = ldx; a.col0 = col0;
+  a.q_pi = q_pi; a.q_a = q_a; a.dact = dact; a.ld_dact = ld_dact; a.mask = mask; a.metrics = metrics;
+  a.B = B; a.Bd = Bd; a.A = A;
+  a.c = (float)((2.0 * bc_weight) / (double)Bd); a.w_bd = (float)(bc_weight / (double)Bd);
+  a.cur = reinterpret_cast<const gcrl::StepCtrl*>(metrics);   // (any non-null value: checked below, replaced once the scratch exists)
+  GCRL_CHECK_ARG(gcrl::bc_args_ok(a), "gcrl_bc_qfilter_f32: bad arguments (B=%d Bd=%d A=%d ldx=%d col0=%d ld_dact=%d)", B, Bd, A, ldx, col0, ld_dact);
+  StageScratch s;
+  if (int rc = s.init(st, 0, 0.f, 0.f, 0, slot)) return rc;
+  a.cur = s.ctrl();
+  return gcrl::launch_bc_qfilter(st, a);
 }
 
 int gcrl_tanh_gauss_fwd_f32(const float* mu, const float* ls_raw, int ld_head, const float* eps, int B, int A, int deterministic,

@@ -33,6 +33,7 @@
 #include "gemm_mfma.h"
 #include "her_ring.h"
 #include "her_prior.h"
+#include "her_bc.h"
 #include "per_tree.h"
 #include "meet.h"
 #include "ops.h"
@@ -246,6 +247,13 @@ struct gcrl_agent {
   bool prior_deferred_on = false;
   int64_t prior_gathers = 0, prior_places = 0;
   PriorPlace prior_place() const { return PriorPlace{B, prior_rows, ldx, slot_x, slot_rd}; }
+  // Q-filtered behaviour cloning on the batch's last bc_rows rows (her_bc.hip; gcrl_agent_set_bc): bc_weight > 0 is "on".  bc_q: Q0(s, a)
+  // of those rows [B] (q_filter), bc_mask: the rows the filter accepted [B], hBC: the extra critic forward's own hidden activations
+  double bc_weight = 0.0;
+  bool bc_filter = false;
+  int bc_rows = 0;
+  float *bc_q = nullptr, *bc_mask = nullptr, *hBC[2] = {};
+  int64_t bc_launches = 0;    // bc_qfilter_kernel launches issued or replayed since creation
   int head_batches = 2;       // batches drawn and gathered before a call's first launch (the rest: behind that many queued steps)
   bool main_idx_staged = false;   // the main gather's indices as a staged copy (round 5's form) instead of read from the pinned block
   std::vector<StepPlan> dp_plans;  // steps of the data-parallel cycle begun by gcrl_agent_dp_begin
@@ -399,6 +407,7 @@ float* hid_C(gcrl_agent* a, int c, int l) { return a->hC_at(c, l); }
 float* hid_TC(gcrl_agent* a, int c, int l) { return a->hTC_at(c, l & 1); }
 float* hid_ACT(gcrl_agent* a, int, int l) { return a->act_tmp[l & 1]; }
 float* hid_C2(gcrl_agent* a, int, int l) { return a->hC2_at(l); }
+float* hid_BC(gcrl_agent* a, int, int l) { return a->hBC[l & 1]; }
 
 // plain MLP chain (Actor / Critic of src/model.py): layer l goes to launch at+l.
 // x_slot / out_slot: per-batch-slot strides when input / output live in the batch array.
@@ -544,9 +553,12 @@ int sac_actor_forwards(gcrl_agent* a, hipStream_t st, int variant, bool with_cur
 // backward and after the actor backward — and the exchange kernel leaves the sum-of-squares partials of the REDUCED gradients:
 // no dW-epilogue partials (they would be the local gradients'), no sumsq launch
 enum { V_ACTOR = 1, V_POLYAK_C = 2, V_POLYAK_A = 4, V_NOISE = 8, V_EPSN = 16, V_EPSC = 32, V_FUSED_NORM = 64, V_WEIGHTS = 128,
-       V_PRE = 256, V_ADV = 512, V_XCHG = 1024 };
+       V_PRE = 256, V_ADV = 512, V_XCHG = 1024, V_BC = 2048 };
 // how the clip norm reaches the optimiser launches of a step issued by the update entry points
 int norm_bits(const gcrl_agent* a) { return a->xchg ? V_XCHG : V_FUSED_NORM; }
+// V_BC (her_bc.hip): an actor step of the layer-per-launch DDPG / TD3 schedule with the behaviour-cloning term on the batch's last
+// bc_rows rows: (q_filter) a second forward of the stepped critic 0 over those rows of [s | a] inside the launches of the one over
+// [s | pi(s)], and one bc_qfilter_kernel launch between the critic's input-gradient chain and the actor's backward
 // exchange of the critic gradients (which = 1), the actor's (+ log_alpha) (2), or both blocks at once (3: overlapped DDPG step)
 int xchg_launch(gcrl_agent* a, hipStream_t st, int which) {
   const int C = a->C, na = a->sac ? 2 : 1;
@@ -809,6 +821,23 @@ int enqueue_phase1_body(gcrl_agent* a, hipStream_t st, int variant) {
   if (re_merged)
     for (size_t i = 0; i < re.steps.size(); ++i)
       for (const GemmDesc& d : re.steps[i]) c2.add(i, d);
+  const bool bc = (variant & V_BC) != 0;
+  if (bc && (a->sac || a->rowchain || a->bc_rows < 1 || a->bc_rows > B || !(a->bc_weight > 0.0)))
+    return fail(GCRL_ERR_STATE, "update: bc_weight: the behaviour-cloning step needs a layer-per-launch DDPG / TD3 agent with gcrl_agent_set_bc in force");
+  if (bc && a->bc_filter) {
+    // Q-filter: the stepped critic 0 on the demonstration rows of [s | a], layer l in the launch of layer l above (the form of that
+    // launch's [s | pi(s)] problem, so that no second launch appears), hidden activations in scratch of its own: hid_C stays what the
+    // input-gradient chain below reads
+    const int Bd = a->bc_rows, row0 = B - Bd;
+    Launches qa;
+    chain_mlp(a, qa, 0, a->critic, a->P_critic(0), a->sa + (long long)row0 * a->ldx, a->ldx, a->slot_x, hid_BC, 0, a->bc_q + row0, 1, 0, EPI_NONE, Bd);
+    for (size_t i = 0; i < qa.steps.size(); ++i)
+      for (GemmDesc d : qa.steps[i]) {
+        const int form = (i < c2.steps.size() && !c2.steps[i].empty()) ? gemm_shape_of(c2.steps[i][0]) : 0;
+        if (form >= 1 && form <= 4) d.shape_hint = form;
+        c2.add(i, d);
+      }
+  }
   TRY(c2.run(st));
   const bool met_rider = re_merged && a->sac && a->Q == 1 && !a->rowchain;   // then the mean rides on the selection launch below
   if (re_merged && !met_rider) TRY(launch_mean_metric(st, a->cur(), a->qt, C * B * a->Q, 1.0f, a->metrics_dev, MET_Q));
@@ -860,6 +889,17 @@ int enqueue_phase1_body(gcrl_agent* a, hipStream_t st, int variant) {
     cb.add((size_t)L, d0);
   }
   TRY(cb.run(st));
+  if (bc) {   // the behaviour-cloning term's gradient on top of dact, mask and metric words (her_bc.hip): one launch
+    BcArgs ba;
+    std::memset(&ba, 0, sizeof(ba));
+    ba.cur = a->cur();
+    ba.spa = a->spa; ba.sa = a->sa; ba.slot_x = a->slot_x; ba.ldx = a->ldx; ba.col0 = S;
+    ba.q_pi = a->q2; ba.q_a = a->bc_filter ? a->bc_q : nullptr;
+    ba.dact = a->dact; ba.ld_dact = a->Apad; ba.mask = a->bc_mask; ba.metrics = a->metrics_dev;
+    ba.B = B; ba.Bd = a->bc_rows; ba.A = A;
+    ba.c = (float)((2.0 * a->bc_weight) / (double)a->bc_rows); ba.w_bd = (float)(a->bc_weight / (double)a->bc_rows);
+    TRY(launch_bc_qfilter(st, ba));
+  }
 
   float* Ga = a->G_actor();
   const float* Pa = a->P_actor();
@@ -1020,11 +1060,12 @@ int enqueue_phases(gcrl_agent* a, hipStream_t st, int variant, int mask) {
 // identical steps is replayed with a single launch
 int run_step(gcrl_agent* a, hipStream_t st, int variant, int mask, int count = 1) {
   if (a->rowchain && a->wt_dirty) TRY(rc_rebuild_wt(a, st));
+  if ((variant & V_BC) && (mask & 2)) a->bc_launches += count;
   if (!graph_on(a) || pop_recording()) {
     for (int c = 0; c < count; ++c) TRY(enqueue_phases(a, st, variant, mask));
     return GCRL_OK;
   }
-  static_assert(2 * V_XCHG <= (1 << 12), "graph key: the variant flags must stay below the phase-mask bits");
+  static_assert(2 * V_BC <= (1 << 12), "graph key: the variant flags must stay below the phase-mask bits");
   const int key = variant | (mask << 12) | (count > 1 ? (0x40000000 | (count << 16)) : 0);
   auto it = a->graphs.find(key);
   if (it == a->graphs.end()) {
@@ -1053,6 +1094,7 @@ StepPlan plan_step(gcrl_agent* a, int64_t step, float grad_scale, int batch_slot
   StepPlan p{0, 0};
   const bool do_actor = (step % c.ac_update_freq) == 0;
   if (do_actor) p.variant |= V_ACTOR;
+  if (do_actor && a->bc_weight > 0.0) p.variant |= V_BC;
   switch (c.kind) {
     case GCRL_AGENT_DDPG:
       if (step % c.polyak_every == 0) p.variant |= V_POLYAK_C | V_POLYAK_A;
@@ -1145,6 +1187,18 @@ int prior_precheck(const gcrl_agent* a, const gcrl_her* her, const char* who) {
   return her_prior_check_call(her, a->prior, a->prior_rows, who);
 }
 
+// what an update call asks of an agent with the behaviour-cloning term on (gcrl_agent_set_bc): before a ticket, slot or counter is consumed
+int bc_precheck(const gcrl_agent* a, const gcrl_her* her, const gcrl_update_inputs* in, const char* who) {
+  if (!(a->bc_weight > 0.0)) return GCRL_OK;
+  if (a->rowchain || a->cfg.pipeline_steps != 0)
+    return fail(GCRL_ERR_STATE, "%s: bc_weight: the behaviour-cloning term runs on the layer-per-launch schedule (pipeline_steps = 0)", who);
+  if (a->sac) return fail(GCRL_ERR_STATE, "%s: bc_weight: the behaviour-cloning term is for the deterministic actors (DDPG / TD3)", who);
+  if (a->xchg) return fail(GCRL_ERR_STATE, "%s: bc_weight: an agent with the behaviour-cloning term does not run under a gradient exchange", who);
+  if ((in && in->weights_host) || a->per_call || (her && !(in && in->s_dev) && per_is_td(her->per)))
+    return fail(GCRL_ERR_STATE, "%s: bc_weight: the behaviour-cloning term does not combine with importance-sampling weights (prioritised replay)", who);
+  return GCRL_OK;
+}
+
 // phase-0 entry of `n` steps: control table + indices upload, batch gather / pack
 // Draw and gather the batches a call left for later ([deferred.next, n); same MT stream order as drawing them all up
 // front).  Called once the head's steps have been issued, so that the GPU has more work queued than the host needs for the
@@ -1221,6 +1275,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     if (a->xchg) return fail(GCRL_ERR_STATE, "update: normalize: a ring that stores raw rows (normalize=\"sample\") does not feed an agent under a gradient exchange");
     TRY(her_norm_check(her, "update"));
   }
+  if (a->bc_weight > 0.0) TRY(bc_precheck(a, her, in, "update"));   // refused before a ticket, slot or plan is consumed
   const bool use_prior = a->prior && !injected && !(in && in->idx_host);   // injected batches and caller-given rows bypass the prior part
   if (use_prior) TRY(prior_precheck(a, her, "update"));   // refused before a ticket, slot or plan is consumed
   const bool prio = !injected && !(in && in->idx_host) && her_prio_on(her);   // a third index source beside the MT upload and the in-kernel IdxGen
@@ -1649,6 +1704,9 @@ int build(gcrl_agent* a) {
       wants.push_back({&a->dw_tick, (long long)C * tcn + tan});     // (unsigned int tickets; the arena is zero-filled)
     }
   }
+  // behaviour cloning (her_bc.hip), behind every earlier buffer: Q0(s, a) and the mask per row, the extra forward's two hidden buffers
+  wants.push_back({&a->bc_q, B}); wants.push_back({&a->bc_mask, B});
+  wants.push_back({&a->hBC[0], BH}); wants.push_back({&a->hBC[1], BH});
   long long total = 0;
   for (auto& w : wants) total += align_up(w.second, 64);
   TRY(bytes_alloc(&a->work, total));
@@ -1703,6 +1761,10 @@ int build(gcrl_agent* a) {
   }
   reg("td_abs", a->td_abs, B);
   reg("w_in", a->w_in, B);
+  reg("bc_q", a->bc_q, B);
+  reg("bc_mask", a->bc_mask, B);
+  reg("bc_q_pi", a->q2, B);                                   // Q0(s, pi(s)) of the last actor step: the other side of the filter
+  reg("batch_spa", a->spa, (long long)a->Mmax * a->slot_x);   // [s | pi(s)] rows of every batch slot, as the last actor steps left them
   reg("per_td_hist", a->per_hist, (long long)a->Mmax * B);                         // rows = the steps of the last device-drawn call
   reg("per_idx_hist", reinterpret_cast<float*>(a->idx_dev()), (long long)a->Mmax * B);   // their drawn indices (uint32 bit patterns)
   if (a->sac) {
@@ -2134,6 +2196,7 @@ int gcrl_agent_dp_begin(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, floa
                         int32_t* lens_out, void* stream) {
   GCRL_CHECK_ARG(a && her, "gcrl_agent_dp_begin: null handle");
   if (a->xchg) return fail(GCRL_ERR_STATE, "gcrl_agent_dp_begin: an in-engine exchange is attached (gcrl_agent_set_exchange): the update entry points exchange by themselves");
+  if (a->bc_weight > 0.0) return fail(GCRL_ERR_STATE, "gcrl_agent_dp_begin: bc_weight: an agent with the behaviour-cloning term does not run under a gradient exchange");
   hipStream_t st = a->pick(stream);
   a->dp_plans.clear();
   TRY(begin_call(a, her, step0, n, nullptr, grad_scale, st, a->dp_plans, tickets_out, lens_out));
@@ -2298,6 +2361,35 @@ int gcrl_agent_set_prior(gcrl_agent* a, gcrl_her* prior, int rows) {
   return GCRL_OK;
 }
 
+int gcrl_agent_set_bc(gcrl_agent* a, double bc_weight, int q_filter, int rows) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_set_bc: null handle");
+  GCRL_CHECK_ARG(std::isfinite(bc_weight) && bc_weight >= 0.0, "gcrl_agent_set_bc: bc_weight: %g is not a finite weight >= 0 (0: off)", bc_weight);
+  if (bc_weight > 0.0) {
+    GCRL_CHECK_ARG(rows >= 1 && rows <= a->B, "gcrl_agent_set_bc: bc_weight: %d demonstration rows of a batch of %d (1..%d)", rows, a->B, a->B);
+    if (a->sac) return fail(GCRL_ERR_ARG, "gcrl_agent_set_bc: bc_weight: the behaviour-cloning term is for the deterministic actors (DDPG / TD3)");
+    if (a->rowchain || a->cfg.pipeline_steps != 0)
+      return fail(GCRL_ERR_ARG, "gcrl_agent_set_bc: bc_weight: the behaviour-cloning term runs on the layer-per-launch schedule (pipeline_steps = 0)");
+    if (a->xchg) return fail(GCRL_ERR_STATE, "gcrl_agent_set_bc: bc_weight: an agent under a gradient exchange does not take the behaviour-cloning term");
+  }
+  GCRL_HIP(hipDeviceSynchronize());
+  for (auto& kv : a->graphs) (void)hipGraphExecDestroy(kv.second);   // captured steps hold the other launch sequence and its arguments
+  a->graphs.clear();
+  GCRL_HIP(hipMemset(a->bc_q, 0, (size_t)a->B * sizeof(float)));
+  GCRL_HIP(hipMemset(a->bc_mask, 0, (size_t)a->B * sizeof(float)));
+  const bool on = bc_weight > 0.0;
+  a->bc_weight = on ? bc_weight : 0.0; a->bc_filter = on && q_filter != 0; a->bc_rows = on ? rows : 0;
+  return GCRL_OK;
+}
+
+int gcrl_agent_get_bc(const gcrl_agent* a, double* bc_weight_out, int* q_filter_out, int* rows_out, int64_t* launches_out) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_get_bc: null handle");
+  if (bc_weight_out) *bc_weight_out = a->bc_weight;
+  if (q_filter_out) *q_filter_out = a->bc_filter ? 1 : 0;
+  if (rows_out) *rows_out = a->bc_rows;
+  if (launches_out) *launches_out = a->bc_launches;
+  return GCRL_OK;
+}
+
 int gcrl_agent_get_prior(const gcrl_agent* a, gcrl_her** prior_out, int* rows_out) {
   GCRL_CHECK_ARG(a, "gcrl_agent_get_prior: null handle");
   if (prior_out) *prior_out = a->prior;
@@ -2458,6 +2550,17 @@ int gcrl_agent_metrics(gcrl_agent* a, int64_t ticket, double* out, int n) {
       break;
     }
   }
+  return GCRL_OK;
+}
+
+int gcrl_agent_bc_metrics(gcrl_agent* a, int64_t ticket, double* out2) {
+  GCRL_CHECK_ARG(a && out2, "gcrl_agent_bc_metrics: null argument");
+  GCRL_CHECK_ARG(ticket >= 0 && ticket < a->next_ticket && ticket >= a->next_ticket - kMetricSlots, "gcrl_agent_bc_metrics: ticket %lld is not live", (long long)ticket);
+  double tuple[16];
+  TRY(gcrl_agent_metrics(a, ticket, tuple, a->ticket_len[ticket % kMetricSlots]));   // (waits for the ticket's call and refreshes the host mirror)
+  const float* m = a->metrics_host + (ticket % kMetricSlots) * kMetricFloats;
+  out2[0] = m[MET_BC_LOSS];
+  out2[1] = m[MET_BC_PASS];
   return GCRL_OK;
 }
 

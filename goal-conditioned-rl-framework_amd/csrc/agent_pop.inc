@@ -375,6 +375,7 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
       return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: prioritise: member %d's ring has an energy tree; populations do not draw from one", i);
     GCRL_CHECK_ARG(!a->xchg && a->bn_sync.world <= 1, "gcrl_pop_update_n: member %d is in a data-parallel group", i);
     GCRL_CHECK_ARG(!a->prof, "gcrl_pop_update_n: member %d has launch profiling on", i);
+    if (a->bc_weight > 0.0) return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: bc_weight: member %d has the behaviour-cloning term on; populations do not step it", i);
     TRY(prior_precheck(a, rings[i], "gcrl_pop_update_n"));   // prior-data replay: every member's prior ring, before any member's ticket
     // (members may share a ring: its index stream — the ring's generator, or draws_done in device-RNG mode — is then consumed in
     // member order, as by standalone agents that share the ring and are called in that order)
@@ -730,6 +731,9 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
   char why[256];
   if (!pop_clone_check(P, src, dst, pairs, what, why, sizeof(why))) return fail(GCRL_ERR_ARG, "gcrl_pop_clone: %s", why);
   const bool with_agent = (what & GCRL_CLONE_AGENT) != 0, with_ring = (what & GCRL_CLONE_RING) != 0;
+  for (int k = 0; k < pairs; ++k)
+    for (const int i : {src[k], dst[k]})
+      if (p->m[i]->bc_weight > 0.0) return fail(GCRL_ERR_STATE, "gcrl_pop_clone: bc_weight: member %d has the behaviour-cloning term on; populations do not carry it", i);
   if (with_ring) {
     GCRL_CHECK_ARG(rings, "gcrl_pop_clone: rings: null array with GCRL_CLONE_RING");
     for (int k = 0; k < pairs; ++k) {

@@ -19,7 +19,9 @@ enum {
   MET_ACTOR_LOSS = 18,
   MET_ACTOR_GRAD = 19,
   MET_ALPHA_LOSS = 20,
-  MET_ALPHA = 21
+  MET_ALPHA = 21,
+  MET_BC_LOSS = 22,      // behaviour-cloning term of the actor loss, bc_weight included (her_bc.hip)
+  MET_BC_PASS = 23       // ... and the share of the demonstration rows its Q-filter accepted
 };
 
 // Per-step scalars.  The host uploads a table of these (one per step of an update_n call); the

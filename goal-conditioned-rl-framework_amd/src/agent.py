@@ -180,6 +180,30 @@ def check_hyperparameters(who: str, sac: bool, hparams: dict):
             refuse(k, f"{v!r}: a scheduler length is an integer")
 
 
+def _check_bc(who: str, kind_name: str, bc_weight, q_filter, prior_buffer, buffer_type: str = "HER", per_draw: str = "host",
+              member: bool = False):
+    """-> bc_weight as a float, or None when the term is off; or a GcrlError that names bc_weight (q_filter for its own type); before
+    any device work."""
+    import math
+    if not isinstance(q_filter, (bool, np.bool_)):
+        raise _ffi.GcrlError(f"{who}: q_filter: must be True or False, got {q_filter!r}")
+    if bc_weight is None:
+        return None
+    if kind_name in ("SAC", "TQC"):
+        raise _ffi.GcrlError(f"{who}: bc_weight: the behaviour-cloning term is for the deterministic actors (DDPG / TD3); the "
+                             "tanh-Gaussian actors have none yet")
+    if member:
+        raise _ffi.GcrlError(f"{who}: bc_weight: populations do not step the behaviour-cloning term")
+    if isinstance(bc_weight, bool) or not isinstance(bc_weight, (int, float, np.integer, np.floating)) or not math.isfinite(bc_weight) \
+            or not bc_weight > 0:
+        raise _ffi.GcrlError(f"{who}: bc_weight: must be a finite number > 0 (None: off), got {bc_weight!r}")
+    if prior_buffer is None:
+        raise _ffi.GcrlError(f"{who}: bc_weight: the term acts on the prior rows of a batch and needs prior_buffer / prior_rows")
+    if buffer_type == "PER" or per_draw == "device":
+        raise _ffi.GcrlError(f"{who}: bc_weight: the term does not combine with importance-sampling weights (prioritised replay)")
+    return float(bc_weight)
+
+
 class _EngineAgent:
     KIND_NAME = "DDPG"
     TD_INDEX = {6: 2, 4: 1}  # position of td_error in the tuple, by tuple length
@@ -190,7 +214,7 @@ class _EngineAgent:
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
                  n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
                  normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, prior_buffer=None,
-                 prior_rows: int | None = None, _member=None):
+                 prior_rows: int | None = None, bc_weight: float | None = None, q_filter: bool = True, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -220,6 +244,16 @@ class _EngineAgent:
                                  f"statistics: its obs_normalize / g_normalize must be {self.obs_normalize!r} / {self.g_normalize!r}")
         self.prior_buffer = prior_buffer
         self._prior_bound = None              # (prior ring handle, rows) the engine holds
+        # bc_weight=W (> 0; None: off), q_filter=True: Q-filtered behaviour cloning on the prior rows (DDPG / TD3; csrc/her_bc.hip;
+        # tests/her_bc_ref.py is the definition).  The actor loss gains W / prior_rows * sum over the accepted prior rows of
+        # |pi(s) - a|^2; with q_filter a row is accepted where the stepped critic rates the stored action above the actor's.  The term
+        # runs on the layer-per-launch schedule, so pipeline becomes 0 below.  Every refusal here before any device work.
+        self.bc_weight = _check_bc(type(self).__name__, self.KIND_NAME, bc_weight, q_filter, prior_buffer, config.buffer_type,
+                                   per_draw, _member is not None)
+        self.q_filter = bool(q_filter)
+        self._bc_ticket = None                # ticket of the last actor step (bc_metrics)
+        if self.bc_weight is not None:
+            pipeline = 0
         # per_draw="device": the prioritised draw, weights and priority update on the device (buffer.PERBuffer draw="device").
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
@@ -284,6 +318,8 @@ class _EngineAgent:
             self._h = _ffi.check_ptr(lib.gcrl_agent_create(C.byref(cfg)), "gcrl_agent_create")
         else:   # a population member (src/population.py): the population made the handle and owns it
             self._owner, self._h = _member(cfg)
+        if self.bc_weight is not None:
+            _ffi.check(lib.gcrl_agent_set_bc(self._h, float(self.bc_weight), 1 if self.q_filter else 0, int(self.prior_rows)))
         self._metric_cache: dict[int, list[float]] = {}
         self._live = collections.deque()      # (ticket, n) of returned tuples, oldest first
         self._lazy: dict[int, list] = {}      # ticket -> weak references to its unresolved LazyScalars
@@ -409,6 +445,24 @@ class _EngineAgent:
             self._metric_cache[ticket] = vals
         return vals
 
+    def bc_metrics(self):
+        """(bc_loss, pass_fraction) of the last actor step: the behaviour-cloning term of its actor loss, bc_weight included, and the
+        share of the prior rows its Q-filter accepted (1.0 with q_filter=False).  Fetched on call (waits for that step)."""
+        if self.bc_weight is None:
+            raise _ffi.GcrlError(f"{type(self).__name__}.bc_metrics: bc_weight: the agent was built without the behaviour-cloning term")
+        if self._bc_ticket is None:
+            raise _ffi.GcrlError(f"{type(self).__name__}.bc_metrics: bc_weight: no actor step has run yet")
+        out = (C.c_double * 2)()
+        _ffi.check(lib.gcrl_agent_bc_metrics(self._h, int(self._bc_ticket), out))
+        return float(out[0]), float(out[1])
+
+    def _note_bc(self, tickets, lens):
+        """remember the ticket of a call's last actor step (the longer tuple) for bc_metrics"""
+        full = max(self.TD_INDEX)
+        for t, l in zip(tickets, lens):
+            if int(l) == full:
+                self._bc_ticket = int(t)
+
     def _tuple(self, ticket: int, n: int):
         td = self.TD_INDEX[n]
         self._live.append((ticket, n))
@@ -491,6 +545,8 @@ class _EngineAgent:
         self.beta_scheduler(step)
         if self._sac:
             self.actor.num_batches_tracked += 1 + (1 if n == 9 else 0)
+        if self.bc_weight is not None:
+            self._note_bc((ticket.value,), (n,))
         out = self._tuple(ticket.value, n)
         if per:
             i = self.TD_INDEX[n]
@@ -558,6 +614,8 @@ class _EngineAgent:
         self.beta_scheduler(step0 + n - 1)
         if self._sac:
             self.actor.num_batches_tracked += sum(1 + (1 if l == 9 else 0) for l in lens)
+        if self.bc_weight is not None:
+            self._note_bc(tickets, lens)
         return [self._tuple(int(t), int(l)) for t, l in zip(tickets, lens)]
 
     # ------------------------------------------------------------------ acting
@@ -796,6 +854,8 @@ class _EngineAgent:
                     ring=self.buffer.save_state(os.path.join(path, "ring.bin")))
         if self.prior_buffer is not None:     # prior-data replay: the prior ring next to the main ring, through the same path
             meta["prior"] = dict(rows=int(self.prior_rows), ring=self.prior_buffer.save_state(os.path.join(path, "prior_ring.bin")))
+        if self.bc_weight is not None:        # the behaviour-cloning term's settings: a resume under other settings is refused
+            meta["bc"] = dict(bc_weight=float(self.bc_weight), q_filter=bool(self.q_filter))
         for name in ("obs_normalizer", "dg_normalizer"):
             nz = getattr(self.buffer, name, None)
             if nz is not None:
@@ -820,8 +880,16 @@ class _EngineAgent:
         if saved_prior is not None and int(saved_prior["rows"]) != int(self.prior_rows):
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prior_rows: the state was saved with prior_rows={saved_prior['rows']}, "
                                  f"this agent has prior_rows={self.prior_rows}")
+        saved_bc = meta.get("bc")
+        if (saved_bc is None) != (self.bc_weight is None) or (saved_bc is not None and float(saved_bc["bc_weight"]) != float(self.bc_weight)):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: bc_weight: the state was saved with bc_weight="
+                                 f"{None if saved_bc is None else saved_bc['bc_weight']!r}, this agent has bc_weight={self.bc_weight!r}")
+        if saved_bc is not None and bool(saved_bc["q_filter"]) != bool(self.q_filter):
+            raise _ffi.GcrlError(f"{type(self).__name__}.load_state: q_filter: the state was saved with q_filter={bool(saved_bc['q_filter'])!r}, "
+                                 f"this agent has q_filter={self.q_filter!r}")
         blob = np.fromfile(os.path.join(path, "agent.bin"), dtype=np.uint8)
         _ffi.check(lib.gcrl_agent_load_state(self._h, blob.ctypes.data, blob.size))
+        self._bc_ticket = None
         self.beta = meta["beta"]
         self.actor.num_batches_tracked = meta["num_batches_tracked"]
         self.buffer.load_state(os.path.join(path, "ring.bin"), meta["ring"])

@@ -97,7 +97,10 @@ class _Population:
                  seeds=None, device_index: int = 0, shared_ring: bool = False, per_draw: str = "host",
                  relabel: str = "push", n_step: int = 1, prioritise: str | None = None, energy: dict | None = None,
                  goal_strategy: str = "future", normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False,
-                 prior_buffer=None, prior_rows: int | None = None):
+                 prior_buffer=None, prior_rows: int | None = None, bc_weight: float | None = None, q_filter: bool = True):
+        # bc_weight: accepted only to be refused by name — the behaviour-cloning term (agent._EngineAgent) is a single-agent mode
+        if bc_weight is not None:
+            self._refuse("bc_weight", f"populations do not step the behaviour-cloning term, got bc_weight={bc_weight!r}")
         # prioritise: accepted only to be refused by name — the energy-prioritised draw (buffer.HERBuffer) is a single-agent mode
         if prioritise is not None or energy is not None:
             self._refuse("prioritise", f"populations (and their shared ring) do not draw from an energy tree, got prioritise={prioritise!r}")

@@ -1015,6 +1015,42 @@ int gcrl_agent_read_batch(gcrl_agent* a, int slot, float* sa, float* nsa, float*
 int gcrl_her_gather_update_mixed(gcrl_her* main_ring, gcrl_her* prior, int B, int Bd, int M, float* sa, float* nsa, float* spa, int ldx,
                                  float* r, float* d, void* stream);
 
+/* ---- Q-filtered behaviour cloning on the prior-data rows, DDPG and TD3 (csrc/her_bc.hip; tests/her_bc_ref.py is the
+ * definition).  With the term on, an actor step on a batch of B rows whose last `rows` rows are demonstrations minimises
+ *   L_actor = -mean_B Q0(s, pi(s)) + bc_weight * (1 / rows) * sum_{b >= B - rows} mask_b * sum_j (pi_bj - a_bj)^2
+ * with Q0 the first critic as this step's critic update left it.  mask_b = 1 without the Q-filter; with it, mask_b = 1 where
+ * Q0(s_b, a_b) > Q0(s_b, pi_b), strictly (a NaN on either side: 0).  The denominator is always `rows`.  The mask is a constant of the
+ * step: no gradient flows through the comparison.  This is the loss of Nair et al. (ICRA 2018) in the form of OpenAI Baselines'
+ * her/ddpg.py; it is NOT the reference's loss.
+ * On the device: (q_filter) the stepped critic 0 runs a second forward over rows [B - rows, B) of [s | a] inside the launches of its
+ * forward over [s | pi(s)] (no extra launch, hidden activations in scratch of its own), and ONE launch of bc_qfilter_kernel, between
+ * the critic's input-gradient chain and the actor's backward, adds  (c * (pi - a)) * (1 - pi * pi), c = fp32(2 * bc_weight / rows), to
+ * the accepted rows of the pre-tanh action gradient — rejected rows and rows below B - rows are not touched — and writes two words of
+ * the step's metrics record: the term's value, bc_weight included, and the accepted share of the `rows` rows.  One extra launch per
+ * actor step, none on critic-only TD3 steps, none at all without the term.  The update's result tuple does not change (its actor
+ * loss stays -mean Q).  Named vectors "bc_q" and "bc_mask" [batch_size] (gcrl_agent_get): Q0(s, a) and the mask of the last actor
+ * step, rows [B - rows, B); the other rows stay 0.  "bc_q_pi" [batch_size]: Q0(s, pi(s)) of that step; "batch_spa"
+ * [min(gradient_step, 128)][batch_size][roundup(S + A, 4)]: the [s | pi(s)] rows of every batch slot as the actor steps left them.
+ * gcrl_agent_set_bc: bc_weight > 0 and finite turns the term on for the last `rows` (1..batch_size) rows of every batch — the caller's
+ * business that those rows are demonstrations (gcrl_agent_set_prior with the same count, or injected batches); bc_weight = 0 turns
+ * it off.  Drops the captured step graphs.  Refused, naming bc_weight — by gcrl_agent_set_bc (GCRL_ERR_ARG): a weight that is
+ * negative or not finite, rows outside 1..batch_size, SAC / TQC agents, agents on the row-chain or pipelined schedules
+ * (pipeline_steps != 0) — and by the update entries, before a ticket, an upload slot or a row of any stream is consumed
+ * (GCRL_ERR_STATE): an agent under a gradient exchange (gcrl_agent_set_exchange, gcrl_agent_dp_begin), steps with importance-sampling
+ * weights (weights_host, a ring with a TD priority tree), population entries (gcrl_pop_update_n, gcrl_pop_clone). */
+int gcrl_agent_set_bc(gcrl_agent* a, double bc_weight, int q_filter, int rows);
+/* the settings in force (bc_weight 0: off) and the bc_qfilter_kernel launches issued or replayed since creation; any pointer may be NULL */
+int gcrl_agent_get_bc(const gcrl_agent* a, double* bc_weight_out, int* q_filter_out, int* rows_out, int64_t* launches_out);
+/* out2[0] = the behaviour-cloning term of the actor step with this (live) ticket, out2[1] = the accepted share of its demonstration
+ * rows; waits for the ticket's call like gcrl_agent_metrics.  A ticket of a step without the term reads what its record slot held. */
+int gcrl_agent_bc_metrics(gcrl_agent* a, int64_t ticket, double* out2);
+/* The kernel alone, on raw device arrays, for tests: spa / sa [slots][B][ldx] with pi / the stored action in columns
+ * [col0, col0 + A) of batch slot `slot`; q_pi [B]; q_a [B] or NULL (no filter); dact [B][ld_dact] updated in place; mask [B] (rows
+ * [B - Bd, B) written) or NULL; metrics: one record of 32 floats, words [22] (term) and [23] (accepted share) written. */
+int gcrl_bc_qfilter_f32(const float* spa_dev, const float* sa_dev, int ldx, int col0, int slots, int slot, const float* q_pi_dev,
+                        const float* q_a_dev, int B, int Bd, int A, double bc_weight, float* dact_dev, int ld_dact, float* mask_dev,
+                        float* metrics_dev, void* stream);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);
