@@ -100,14 +100,14 @@ __device__ inline void process_step_raw_body(const gcrl::ProcRawArgs& p, const f
     const int j = threadIdx.x - 128;
     double m = p.gmean[j], v = p.gvar[j];
     int md = p.gmode;
-    gcrl::norm_update_col(m, v, 4 * n, *p.gcount, md, [&](int i) { return dg[(size_t)i * G + j]; });   // [dg ; next_dg ; ag ; next_ag] lie in this order
+    gcrl::norm_update_col(m, v, 4 * n, G, *p.gcount, md, [&](int i) { return dg[(size_t)i * G + j]; });   // [dg ; next_dg ; ag ; next_ag] lie in this order
     p.gmean[j] = m; p.gvar[j] = v;
   }
   if (p.mean && p.update) {
     for (int j = threadIdx.x; j < D; j += 256) {
       double m = p.mean[j], v = p.var[j];
       int md = p.mode;
-      gcrl::norm_update_col(m, v, 2 * n, *p.count, md, [&](int i) { return obs[(size_t)i * D + j]; });
+      gcrl::norm_update_col(m, v, 2 * n, D, *p.count, md, [&](int i) { return obs[(size_t)i * D + j]; });
       p.mean[j] = m; p.var[j] = v;
     }
   }

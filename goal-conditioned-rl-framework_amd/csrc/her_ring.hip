@@ -97,7 +97,7 @@ __device__ inline void her_process_step_body(const ProcArgs& p, const float* raw
     double m = p.gmean[j], v = p.gvar[j];
     if (p.gupdate) {
       int md = p.gmode;
-      gcrl::norm_update_col(m, v, 4 * n, *p.gcount, md, [&](int i) { return dg[(size_t)i * G + j]; });   // [dg ; next_dg ; ag ; next_ag] lie in this order
+      gcrl::norm_update_col(m, v, 4 * n, G, *p.gcount, md, [&](int i) { return dg[(size_t)i * G + j]; });   // [dg ; next_dg ; ag ; next_ag] lie in this order
       p.gmean[j] = m; p.gvar[j] = v;
     }
     s_gmean[j] = m; s_gden[j] = gcrl::norm_den(v, (gmode & gcrl::NORM_F32) != 0);
@@ -107,7 +107,7 @@ __device__ inline void her_process_step_body(const ProcArgs& p, const float* raw
       double m = p.mean[j], v = p.var[j];
       if (p.update) {
         int md = p.mode;
-        gcrl::norm_update_col(m, v, 2 * n, *p.count, md, [&](int i) { return obs[(size_t)i * D + j]; });   // np.concatenate([obs, next_obs]) is how the two blocks lie
+        gcrl::norm_update_col(m, v, 2 * n, D, *p.count, md, [&](int i) { return obs[(size_t)i * D + j]; });   // np.concatenate([obs, next_obs]) is how the two blocks lie
         p.mean[j] = m; p.var[j] = v;
       }
       s_mean[j] = m; s_den[j] = gcrl::norm_den(v, (mode & gcrl::NORM_F32) != 0);

@@ -8,8 +8,8 @@
 //                batches with the observation space's dtype, which TimeFeatureWrapper declares float64 (src/utils.py:156),
 //                while the goal spaces stay float32.  (The values are float32-valued either way — panda-gym produces float32
 //                — so float32 rows carry them exactly across the ABI.)
-// float32 rows (round 2-3, goldens normalizer.npz / normalizer_loaded.npz): batch moments in float32 (numpy's sequential axis-0
-//   sums); a created normaliser merges and normalises in float64, a loaded one does EVERYTHING in float32 from then on (Python
+// float32 rows (round 2-3, goldens normalizer.npz / normalizer_loaded.npz): batch moments in float32 (numpy's axis-0 sums:
+//   sequential for two features or more, pairwise for a one-feature normaliser — see norm_pairwise_sum below); a created normaliser merges and normalises in float64, a loaded one does EVERYTHING in float32 from then on (Python
 //   scalars are weak; only the count stays a double).
 // float64 rows (round 4, golden normalizer_f64.npz): batch moments and the merge in float64 whatever the statistics' type — only
 //   `self.var * self.count` of a loaded normaliser is still a float32 product — so the first update after a load puts the
@@ -54,24 +54,128 @@ __device__ inline void norm_merge64(double& m, double& v, double bm, double bv, 
   m = nm; v = M2 / total;
 }
 
-// RunningNormalizer.update (:75-93) for one feature of rows x(0) .. x(rows - 1); `mode` comes back as the statistics' type
-// AFTER the update (float64 rows turn float32 statistics into float64 ones)
+// ---- the order of the batch sums.  np.mean / np.var reduce axis 0 of an (n, D) array.  For D >= 2 the reduction's inner loop runs
+// ACROSS the features and every feature's sum is sequential in the rows.  A ONE-feature array is different: numpy coalesces the
+// contiguous (n, 1) array into one inner reduce of n elements, and that loop is its pairwise sum (tests/numpy_pairwise_ref.py
+// restates it and pins it against numpy):
+//   n < 8     sequential;
+//   n <= 128  eight running sums r[k] over the elements k, k + 8, k + 16, .. of the first n - n % 8, combined as
+//             ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the n % 8 tail elements added one by one;
+//   n > 128   sum(first n2) + sum(rest), n2 = n / 2 rounded down to a multiple of 8, each half by the same rule;
+//   n > 8192  chunks of 8192 elements, each by the rule above, added to the result one after another.
+// Both the sum of the rows and the sum of the squared deviations take that order, for float32 and for float64 rows.
+__device__ inline float norm_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ inline double norm_add(double a, double b) { return __dadd_rn(a, b); }
+
+// one leaf of the rule above: elements [off, off + n), n <= 128
+template <typename T, typename Term>
+__device__ inline T norm_pairwise_block(int off, int n, Term t) {
+  if (n < 8) {
+    T res = (T)0;
+    for (int i = 0; i < n; ++i) res = norm_add(res, t(off + i));
+    return res;
+  }
+  T r0 = t(off), r1 = t(off + 1), r2 = t(off + 2), r3 = t(off + 3), r4 = t(off + 4), r5 = t(off + 5), r6 = t(off + 6), r7 = t(off + 7);
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+    r0 = norm_add(r0, t(off + i));     r1 = norm_add(r1, t(off + i + 1)); r2 = norm_add(r2, t(off + i + 2)); r3 = norm_add(r3, t(off + i + 3));
+    r4 = norm_add(r4, t(off + i + 4)); r5 = norm_add(r5, t(off + i + 5)); r6 = norm_add(r6, t(off + i + 6)); r7 = norm_add(r7, t(off + i + 7));
+  }
+  T res = norm_add(norm_add(norm_add(r0, r1), norm_add(r2, r3)), norm_add(norm_add(r4, r5), norm_add(r6, r7)));
+  for (; i < n; ++i) res = norm_add(res, t(off + i));
+  return res;
+}
+
+// One chunk (n <= 8192, see below) by the whole rule, without recursion and without an indexed array (so: no call stack, no
+// per-thread scratch).  The split tree is walked in post-order; where the walk stands is (depth d, one bit per level: 0 = in the left
+// half, 1 = in the right half), and the node's [off, off + len) is re-derived from the chunk's start whenever it is needed.  left[k]
+// holds the finished left half of the level-k node while its right half is being summed; it is read and written by fully unrolled
+// compares, which keeps it in registers.  A level takes the length to at most len / 2 + 4, so 8192 elements need at most 7 levels.
+constexpr int kNormPairLevels = 8;
+constexpr int kNormPairChunk = 8192;
+template <typename T, typename Term>
+__device__ inline T norm_pairwise_chunk(int base, int n, Term t) {
+  if (n <= 128) return norm_pairwise_block<T>(base, n, t);
+  T left[kNormPairLevels];
+#pragma unroll
+  for (int k = 0; k < kNormPairLevels; ++k) left[k] = (T)0;
+  unsigned path = 0;
+  int d = 0;
+  for (;;) {
+    int off = base, len = n;                               // the node at (d, path)
+    for (int k = 0; k < d; ++k) {
+      int n2 = len / 2; n2 -= n2 % 8;
+      if ((path >> k) & 1u) { off += n2; len -= n2; } else len = n2;
+    }
+    while (len > 128 && d < kNormPairLevels) {             // down its left spine to a leaf
+      int n2 = len / 2; n2 -= n2 % 8;
+      path &= ~(1u << d); ++d; len = n2;
+    }
+    T ret = norm_pairwise_block<T>(off, len, t);
+    bool turned = false;
+    while (d > 0) {                                        // up again: a finished left half waits, a finished right half is added to it
+      const int k = d - 1;
+      if (!((path >> k) & 1u)) {
+#pragma unroll
+        for (int q = 0; q < kNormPairLevels; ++q) if (q == k) left[q] = ret;
+        path |= 1u << k; turned = true;
+        break;
+      }
+      T lv = (T)0;
+#pragma unroll
+      for (int q = 0; q < kNormPairLevels; ++q) if (q == k) lv = left[q];
+      ret = norm_add(lv, ret);
+      path &= ~(1u << k); d = k;
+    }
+    if (!turned) return ret;
+  }
+}
+// numpy hands its inner loop at most 8192 elements at a time (the ufunc buffer size, which also bounds an unbuffered reduce's inner
+// loop) and adds the chunks' sums to the result one after another: ((0 + chunk0) + chunk1) + ...
+template <typename T, typename Term>
+__device__ inline T norm_pairwise_sum(int n, Term t) {
+  T res = (T)0;
+  for (int base = 0; base < n; base += kNormPairChunk)
+    res = norm_add(res, norm_pairwise_chunk<T>(base, n - base < kNormPairChunk ? n - base : kNormPairChunk, t));
+  return res;
+}
+
+// RunningNormalizer.update (:75-93) for one feature of rows x(0) .. x(rows - 1) of a normaliser of `width` features; `mode` comes
+// back as the statistics' type AFTER the update (float64 rows turn float32 statistics into float64 ones).  width >= 2: the sums run
+// sequentially over the rows; width == 1: in numpy's pairwise order (above).  The pairwise sum of the rows and that of the squared
+// deviations are two rounds of ONE not-unrolled loop: a second inlined copy of the walk made the process_step kernels a seventh
+// longer and their launches 0.8 us slower for every width (instruction fetch), so the rare case keeps its code small.
 template <typename Row>
-__device__ inline void norm_update_col(double& m, double& v, int rows, double c0, int& mode, Row x) {
+__device__ inline void norm_update_col(double& m, double& v, int rows, int width, double c0, int& mode, Row x) {
+  const bool pair = __builtin_expect(width == 1, 0);
   if (mode & NORM_ROWS64) {
-    double s = 0.0;
-    for (int i = 0; i < rows; ++i) s = __dadd_rn(s, (double)x(i));
-    const double bm = __ddiv_rn(s, (double)rows);
-    double q = 0.0;
-    for (int i = 0; i < rows; ++i) { const double d = __dsub_rn((double)x(i), bm); q = __dadd_rn(q, __dmul_rn(d, d)); }
+    double s = 0.0, bm = 0.0, q = 0.0;
+    if (pair) {
+#pragma nounroll
+      for (int pass = 0; pass < 2; ++pass) {     // pass 0: the sum of the rows; pass 1: of the squared deviations (one copy of the walk)
+        const double r = norm_pairwise_sum<double>(rows, [&](int i) { const double xi = (double)x(i); if (pass == 0) return xi; const double d = __dsub_rn(xi, bm); return __dmul_rn(d, d); });
+        if (pass == 0) bm = __ddiv_rn(r, (double)rows); else q = r;
+      }
+    } else {
+      for (int i = 0; i < rows; ++i) s = __dadd_rn(s, (double)x(i));
+      bm = __ddiv_rn(s, (double)rows);
+      for (int i = 0; i < rows; ++i) { const double d = __dsub_rn((double)x(i), bm); q = __dadd_rn(q, __dmul_rn(d, d)); }
+    }
     norm_merge64(m, v, bm, __ddiv_rn(q, (double)rows), rows, c0, (mode & NORM_F32) != 0);
     mode &= ~NORM_F32;
   } else {
-    float s = 0.f;
-    for (int i = 0; i < rows; ++i) s = __fadd_rn(s, x(i));
-    const float bm = __fdiv_rn(s, (float)rows);
-    float q = 0.f;
-    for (int i = 0; i < rows; ++i) { const float d = __fsub_rn(x(i), bm); q = __fadd_rn(q, __fmul_rn(d, d)); }
+    float s = 0.f, bm = 0.f, q = 0.f;
+    if (pair) {
+#pragma nounroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const float r = norm_pairwise_sum<float>(rows, [&](int i) { const float xi = x(i); if (pass == 0) return xi; const float d = __fsub_rn(xi, bm); return __fmul_rn(d, d); });
+        if (pass == 0) bm = __fdiv_rn(r, (float)rows); else q = r;
+      }
+    } else {
+      for (int i = 0; i < rows; ++i) s = __fadd_rn(s, x(i));
+      bm = __fdiv_rn(s, (float)rows);
+      for (int i = 0; i < rows; ++i) { const float d = __fsub_rn(x(i), bm); q = __fadd_rn(q, __fmul_rn(d, d)); }
+    }
     norm_merge(m, v, bm, __fdiv_rn(q, (float)rows), rows, c0, (mode & NORM_F32) != 0);
   }
 }

@@ -5,7 +5,8 @@
 //
 // Arithmetic restated exactly (bit-for-bit against numpy, tests/golden/normalizer.npz):
 //   update(x)        batch_mean = np.mean(x, axis=0), batch_var = np.var(x, axis=0) on float32 rows: numpy
-//                    reduces the row axis SEQUENTIALLY in float32 (sum, / n; (x - mean)^2 sum, / n);
+//                    reduces the row axis SEQUENTIALLY in float32 (sum, / n; (x - mean)^2 sum, / n) when there are
+//                    two features or more, and PAIRWISE for a one-feature normaliser (norm_math.h);
 //                    then the parallel-variance merge in float64, operation by operation as written in
 //                    _update_from_moments (src/utils.py:83-93)
 //   normalize(x)     (x - mean) / (sqrt(var) + 1e-8) in float64, clipped to +-clip_range; the trainer casts the
@@ -40,7 +41,7 @@ __global__ void norm_update_kernel(const float* __restrict__ x, int n, int ld, i
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= D) return;
   double m = mean[j], v = var[j];
-  gcrl::norm_update_col(m, v, n, *count, mode, [&](int i) { return x[(long long)i * ld + j]; });
+  gcrl::norm_update_col(m, v, n, D, *count, mode, [&](int i) { return x[(long long)i * ld + j]; });
   mean[j] = m;
   var[j] = v;
 }

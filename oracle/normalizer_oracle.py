@@ -1,9 +1,10 @@
 """ORACLE — TEST INFRASTRUCTURE ONLY.  Never imported by the product.
 
 CPU restatement of the reference's RunningNormalizer (src/utils.py:68-98), with the batch moments written out as
-the explicit float32 sequential sums numpy's axis-0 reductions perform — the order the device kernel
-(csrc/normalizer.hip) follows.  Pinned by tests/golden/normalizer.npz, normalizer_loaded.npz (the float32 regime after
-`load`) and normalizer_f64.npz (float64 rows, created and loaded), all captured from the reference's own class.
+the explicit sequential sums numpy's axis-0 reductions perform at two features or more, and numpy's pairwise order at one
+feature (tests/numpy_pairwise_ref.py) — the orders the device kernel (csrc/norm_math.h) follows.  Pinned by
+tests/golden/normalizer.npz, normalizer_loaded.npz (the float32 regime after `load`), normalizer_f64.npz (float64 rows, created
+and loaded) and normalizer_widths.npz (1, 2 and 3 features), all captured from the reference's own class.
 """
 from __future__ import annotations
 
@@ -26,6 +27,9 @@ class RunningNormalizerOracle:
         ft = np.float64 if x.dtype == np.float64 else np.float32
         x = np.asarray(x, ft)
         n, D = x.shape
+        if D == 1:      # a contiguous (n, 1) batch is one inner reduce for numpy: summed pairwise, not row after row
+            from numpy_pairwise_ref import mean_var_one_feature      # (tests/: the order's definition, pinned against numpy there)
+            return (*mean_var_one_feature(np.ascontiguousarray(x)), n)
         s = np.zeros(D, ft)
         for i in range(n):
             s = s + x[i]

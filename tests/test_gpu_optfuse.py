@@ -196,21 +196,39 @@ def test_a_second_process_on_the_device_switches_the_waiting_forms_off(gcrl, mon
     assert first.set_meetings(True) != 0
 
 
-@pytest.mark.parametrize("kind,H,L,B", [("SAC", 256, 3, 512), ("SAC", 64, 3, 130), ("TQC", 32, 2, 40)])
-def test_heads_and_sampling_as_one_launch_are_bitwise_the_two_launches(gcrl, monkeypatch, kind, H, L, B):
+# A > 8 (2A > 16): heads_sample_rows' two-pass branch and the wide side of csrc/sac_heads.h; the other cases run the suite's A = 3
+WIDE_HEADS = [pytest.param("SAC", 64, 2, 40, 9, id="SAC-64-2-40-A9"), pytest.param("SAC", 64, 2, 40, 16, id="SAC-64-2-40-A16"),
+              pytest.param("TQC", 32, 2, 40, 9, id="TQC-32-2-40-A9"), pytest.param("TQC", 32, 2, 40, 16, id="TQC-32-2-40-A16")]
+
+
+@pytest.mark.parametrize("kind,H,L,B,A", [pytest.param("SAC", 256, 3, 512, None, id="SAC-256-3-512"), pytest.param("SAC", 64, 3, 130, None, id="SAC-64-3-130"),
+                                          pytest.param("TQC", 32, 2, 40, None, id="TQC-32-2-40")] + WIDE_HEADS)
+def test_heads_and_sampling_as_one_launch_are_bitwise_the_two_launches(gcrl, monkeypatch, kind, H, L, B, A):
     """SACActorModel's mean / log_std heads (src/model.py:114-115) and sample() (:125-141) as one launch (csrc/sac_heads.h: the
     heads' tiles by the batched GEMM's own tile body, one thread per (row, action) for the sampling arithmetic, the log-prob summed
     in action order) against the GEMM launch + sampling launch of rounds 1-4 (GCRL_NO_HEADS_FUSED=1): 24 steps with device noise,
     every tuple, parameter, BatchNorm statistic and alpha bitwise."""
+    _heads_one_launch_vs_two(gcrl, monkeypatch, kind, H, L, B, A)
+
+
+@pytest.mark.parametrize("kind,H,L,B,A", WIDE_HEADS)
+def test_heads_and_sampling_without_the_heads_fold_are_bitwise_the_two_launches(gcrl, monkeypatch, kind, H, L, B, A):
+    """The wide-action cases once more with the heads not folded into the row-block launch (GCRL_NO_HEADS_FOLD=1): the stand-alone
+    heads launch of csrc/sac_heads.h at 2A > 16 against the two launches, bitwise."""
+    monkeypatch.setenv("GCRL_NO_HEADS_FOLD", "1")
+    _heads_one_launch_vs_two(gcrl, monkeypatch, kind, H, L, B, A)
+
+
+def _heads_one_launch_vs_two(gcrl, monkeypatch, kind, H, L, B, A=None):
     import test_gpu_multistep as ms
     cfg = ms._cfg(kind, H, L, B, max_len=20000 if B > 200 else 4000)
 
-    def build():
-        ag = ms._cls(gcrl, kind)(ms.S, ms.A, cfg, None, nenvs=2, gradient_step=5, rng="engine", seed=21)
+    def build(A=ms.A if A is None else A):
+        ag = ms._cls(gcrl, kind)(ms.S, A, cfg, None, nenvs=2, gradient_step=5, rng="engine", seed=21)
         gen = np.random.default_rng(3)
         ep = 0
         while len(ag.buffer) < B + 300:
-            for st in ms.her_oracle.synthetic_episode(gen, 50, ms.S, ms.A):
+            for st in ms.her_oracle.synthetic_episode(gen, 50, ms.S, A):
                 ag.push_her(ep % 2, *st)
             ep += 1
         return ag

@@ -695,7 +695,9 @@ def test_row_block_ddpg_tracks_the_layer_per_launch_path(gcrl, H, L, B):
 
 @pytest.mark.parametrize("kind,H,L,B,S,A", [("TD3", 32, 2, 32, 10, 3), ("TD3", 128, 3, 1030, 23, 4), ("TD3", 64, 1, 7, 5, 16),
                                               ("DDPG", 4, 2, 3, 3, 1), ("DDPG", 128, 8, 17, 30, 6), ("DDPG", 520, 2, 40, 12, 2),
-                                              ("TD3-devnoise", 64, 2, 50, 9, 3), ("SAC", 64, 2, 40, 11, 3), ("SAC", 256, 3, 130, 22, 4)])
+                                              ("TD3-devnoise", 64, 2, 50, 9, 3), ("SAC", 64, 2, 40, 11, 3), ("SAC", 256, 3, 130, 22, 4),
+                                              # 2A > 16: heads_sample_rows' two-pass branch and the wide side of sac_heads.h
+                                              ("SAC", 64, 2, 40, 11, 9), ("SAC", 64, 2, 40, 11, 16)])
 def test_row_block_path_against_the_layer_per_launch_path_one_step(gcrl, kind, H, L, B, S, A):
     """Shape sweep of the row-block kernels (ragged last row block, 1..8 hidden layers, 1..16
     action dims, hidden width below / across the 256-column chunk, 4-/8-/16-row blocks): one update
@@ -740,6 +742,45 @@ def test_row_block_path_against_the_layer_per_launch_path_one_step(gcrl, kind, H
     for v0, v1 in pairs:
         d = np.abs(v0.flat() - v1.flat())
         assert float(np.mean(d > 2e-5)) < 0.02 and float(d.max()) < 3e-3      # Adam turns ~0 gradients into +-lr
+
+
+@pytest.mark.parametrize("A", [9, 16])
+def test_sac_first_update_with_wide_actions_matches_the_oracle(gcrl, A):
+    """SAC with more than 8 actions (2A > 16: the two-pass branch of heads_sample_rows, the wide side of csrc/sac_heads.h), which no
+    other test of the suite reaches: the first update() against OracleAgent from identical parameters, batch and injected eps -
+    returned tuple and pre-clip gradients of the actor and both critics at RTOL / ATOL."""
+    H, L, B, S = 64, 2, 40, 11
+    cfg = make_config("SAC", hidden_dim=H, layer_count=L, batch_size=B, max_len=2000, grad_clip=0.7, ac_update_freq=1)
+    torch.manual_seed(40 + A)
+    orc = OracleAgent("SAC", S, A, cfg, nenvs=1, gradient_step=40, rng=random.Random(1))
+    ag = gcrl.SACAgent(S, A, cfg, None, nenvs=1, gradient_step=40, rng="engine", seed=3)
+    gen = np.random.default_rng(100 + A)
+    with torch.no_grad():   # moderate tanh-Gaussian heads (see tests/detdata.py), asymmetric everything else
+        for net in [orc.actor] + orc.critics:
+            for p in net.parameters():
+                p.add_(torch.from_numpy((0.02 * gen.standard_normal(tuple(p.shape))).astype(np.float32)))
+        orc.actor.log_std_head.weight.mul_(0.25); orc.actor.log_std_head.bias.fill_(-1.0); orc.actor.mean_head.weight.mul_(0.5)
+    orc.hard_update()
+    ag.actor.set_flat(orc.flat_params(orc.actor))
+    for v, c in zip(ag.critics, orc.critics):
+        v.set_flat(orc.flat_params(c))
+    ag.update_target_network()
+    batch = (gen.standard_normal((B, S)).astype(np.float32), gen.uniform(-1, 1, (B, A)).astype(np.float32),
+             -(gen.uniform(size=(B, 1)) > 0.3).astype(np.float32), gen.standard_normal((B, S)).astype(np.float32),
+             (gen.uniform(size=(B, 1)) > 0.9).astype(np.float32))
+    e1, e2 = gen.standard_normal((B, A)).astype(np.float32), gen.standard_normal((B, A)).astype(np.float32)
+    want = orc.update(1, tuple(torch.from_numpy(x) for x in batch), eps_next=torch.from_numpy(e1), eps_cur=torch.from_numpy(e2))
+    got = ag.update(1, batch=tuple(torch.from_numpy(x).cuda() for x in batch), eps_next=torch.from_numpy(e1), eps_cur=torch.from_numpy(e2))
+    g = np.array([float(x) for x in got]); w = np.array([float(np.asarray(x)) for x in want])
+    assert g.shape == w.shape == (9,)
+    print(f"SAC A={A}: tuple worst |diff| {np.abs(g - w).max():.3e} of scale {np.abs(w).max():.3e}")
+    assert vec_close(g, w), (g, w)
+    for v, pre in zip(ag.critics, orc.last["critic_grads_pre"]):
+        print(f"SAC A={A}: {v.name} pre-clip gradient worst |diff| {np.abs(v.grad_flat() - pre).max():.3e} of scale {np.abs(pre).max():.3e}")
+        assert vec_close(v.grad_flat(), pre), (v.name, float(np.abs(v.grad_flat() - pre).max()), float(np.abs(pre).max()))
+    pre = orc.last["actor_grads_pre"]
+    print(f"SAC A={A}: actor pre-clip gradient worst |diff| {np.abs(ag.actor.grad_flat() - pre).max():.3e} of scale {np.abs(pre).max():.3e}")
+    assert vec_close(ag.actor.grad_flat(), pre), (float(np.abs(ag.actor.grad_flat() - pre).max()), float(np.abs(pre).max()))
 
 
 def test_tuple_contract_and_td_error_array(gcrl):

@@ -212,22 +212,42 @@ def test_mixed_branches(gcrl):
 
 
 def test_normaliser_regimes(gcrl):
+    _normaliser_regimes(gcrl, CFG1)
+
+
+def test_normaliser_regimes_with_a_one_feature_goal(gcrl):
+    """The same with a 1-D goal: the goal normaliser is one feature wide and gets 4 * 8 = 32 rows per step, which numpy sums pairwise
+    (tests/numpy_pairwise_ref.py).  Besides population == members, every member's goal statistics equal a host numpy normaliser fed
+    the same [dg ; next_dg ; ag ; next_ag] batches, bit for bit."""
+    _normaliser_regimes(gcrl, dict(D=9, G=1, A=3, H=64, B=64), host_goal=True)
+
+
+def _normaliser_regimes(gcrl, sh, host_goal=False):
+    from gcrl_amd.src.utils import RunningNormalizer
     P = 4
-    pop, solo = _twins(gcrl, "DDPG", P, CFG1)
+    pop, solo = _twins(gcrl, "DDPG", P, sh)
     # member 2's observation normaliser was loaded: float32 statistics, float32 arithmetic (the regime bits are per member)
     gen = np.random.default_rng(3)
-    mean, var = gen.standard_normal(CFG1["D"]).astype(np.float32), (0.5 + gen.random(CFG1["D"])).astype(np.float32)
+    mean, var = gen.standard_normal(sh["D"]).astype(np.float32), (0.5 + gen.random(sh["D"])).astype(np.float32)
     for ag in (pop.members[2], solo[2]):
         ag.buffer.obs_normalizer.set_state(mean, var, 40.0)
     assert pop.members[2].buffer.obs_normalizer.float32 and not pop.members[1].buffer.obs_normalizer.float32
+    host = [RunningNormalizer(sh["G"]) for _ in range(P)]
     step = 0
     for obs_dtype, kw in [(np.float32, {}), (np.float64, {}), (np.float64, dict(g_normalize=True)), (np.float32, dict(g_normalize=True)),
                           (np.float32, dict(obs_normalize=False)), (np.float64, dict(obs_normalize=False, g_normalize=True)), (np.float32, {})]:
         for _ in range(3):
-            rows, acts = _act(pop, solo, step, CFG1, obs_dtype=obs_dtype, **kw)
+            rows, acts = _act(pop, solo, step, sh, obs_dtype=obs_dtype, **kw)
             _proc(pop, solo, step, rows, acts, _dones(step), **kw)
+            if kw.get("g_normalize"):
+                for nz, (state, nxt, _) in zip(host, rows):
+                    nz.update(np.concatenate([state["desired_goal"], nxt["desired_goal"], state["achieved_goal"], nxt["achieved_goal"]]))
             step += 1
     _compare_members(pop, solo, goal_nz=True)
+    if host_goal:
+        for i, (m, nz) in enumerate(zip(pop.members, host)):
+            got = m.buffer.dg_normalizer
+            assert nz.count > 9 * 4 * NENVS and np.array_equal(got.mean, nz.mean) and np.array_equal(got.var, nz.var) and got.count == nz.count, i
     counts = pop.acting_counts()
     assert counts[0] == counts[2] == step and counts[3] == step
 

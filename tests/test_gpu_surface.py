@@ -293,13 +293,13 @@ def test_push_batch_equals_per_env_pushes_and_oracle(gcrl, k, nenvs):
 
 
 # ------------------------------------------------------------------ full resume state (SURVEY.md §8f-2 extension)
-def resume_agent(gcrl, kind, nenvs=2):
+def resume_agent(gcrl, kind, nenvs=2, state_dim=10, action_dim=3):
     from oracle.agent_oracle import make_config
     kind, kw = variant(kind)
     cfg = make_config(kind, hidden_dim=32, layer_count=2, batch_size=32, max_len=1000, ac_update_freq=2 if kind == "TD3" else 1,
                       policy_noise=0.2, actor_lr_min=1e-4, ac_scheduler_steps=25, critic_lr_min=2e-4, cr_scheduler_steps=30)
     cls = dict(DDPG=gcrl.DDPG, TD3=gcrl.TD3Agent, SAC=gcrl.SACAgent, TQC=gcrl.TQCAgent)[kind]
-    return cls(10, 3, cfg, None, nenvs=nenvs, gradient_step=10, rng="engine", seed=5, **kw)
+    return cls(state_dim, action_dim, cfg, None, nenvs=nenvs, gradient_step=10, rng="engine", seed=5, **kw)
 
 
 @pytest.mark.parametrize("kind", ["DDPG", "TD3", "SAC", "TQC", "TQC-25x2"])
@@ -494,19 +494,19 @@ def test_fused_acting_entries_with_float64_observation_rows(gcrl, loaded, tmp_pa
     _fused_vs_separate(gcrl, "DDPG", True, loaded, tmp_path, obs64=True)
 
 
-def _fused_vs_separate(gcrl, kind, g_norm, loaded, tmp_path=None, obs64=False):
+def _fused_vs_separate(gcrl, kind, g_norm, loaded, tmp_path=None, obs64=False, D=7, G=3, A=3, n=8, mt=False):
     """observe_act / process_step (one native call each per vector-env step, device normalisers) against the reference's
     call sequence made of the separate calls with host normalisers: same actions (same host RNG draws), same normaliser
     statistics, same ring rows bit for bit — including the episode flushes (HER relabel) inside the steps.  g_norm: goals
-    normalised as well (g_normalize = True, src/env.py:167-175, :222-223: the goal normaliser sees [dg ; next_dg ; ag ; next_ag])."""
+    normalised as well (g_normalize = True, src/env.py:167-175, :222-223: the goal normaliser sees [dg ; next_dg ; ag ; next_ag]).
+    mt: the ring's Mersenne Twister ends in the same state as well."""
     import random
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     from oracle import her_oracle
-    D, G, A, n = 7, 3, 3, 8
     gen = np.random.default_rng(4)
 
     def build(device):
-        ag = resume_agent(gcrl, kind, nenvs=n)
+        ag = resume_agent(gcrl, kind, nenvs=n, state_dim=D + G, action_dim=A)
         Nz = DeviceRunningNormalizer if device else RunningNormalizer
         ag.buffer.obs_normalizer, ag.buffer.dg_normalizer = Nz(D), Nz(G)
         ag.buffer.compute_reward = her_oracle.sparse_reward
@@ -561,6 +561,64 @@ def _fused_vs_separate(gcrl, kind, g_norm, loaded, tmp_path=None, obs64=False):
     assert len(host.buffer) == len(dev.buffer) == min(1000, n * 246)      # 1000-row ring: wrapped
     for a, b in zip(host.buffer.rows(), dev.buffer.rows()):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    if mt:
+        import ctypes
+        from gcrl_amd._ffi import check, lib
+        states = []
+        for ag in (host, dev):
+            buf = (ctypes.c_uint32 * 625)()
+            check(lib.gcrl_mt_get_state(ag.buffer.rng.handle, buf))
+            states.append(np.array(buf[:], np.uint32))
+        assert np.array_equal(states[0], states[1]), "Mersenne Twister state differs"
+
+
+@pytest.mark.parametrize("regime", ["created", "loaded", "obs64"])
+@pytest.mark.parametrize("nenvs", [2, 5])
+def test_fused_acting_entries_with_a_one_feature_goal(gcrl, nenvs, regime, tmp_path):
+    """A 1-D goal under g_normalize: the goal normaliser is ONE feature wide and sees 4 * nenvs rows per step.  numpy reduces a
+    contiguous (n, 1) array pairwise from 8 rows on (tests/numpy_pairwise_ref.py) - 2 envs are the first size at which that differs
+    from the sequential sum a column of a wider normaliser gets; 5 envs give 20 rows, a ragged tail after two rounds of eight.  Fused
+    process_step / observe_act against the separate host calls: statistics, ring rows and the ring's generator, bit for bit."""
+    _fused_vs_separate(gcrl, "DDPG", True, regime == "loaded", tmp_path, obs64=regime == "obs64", D=9, G=1, A=3, n=nenvs, mt=True)
+
+
+WIDTH_REGIMES = ["c32", "l32", "c64"]
+
+
+@pytest.mark.parametrize("regime", WIDTH_REGIMES)
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_device_normalizer_at_one_two_and_three_features_bit_exact_vs_reference(gcrl, tmp_path, D, regime):
+    """csrc/normalizer.hip against tests/golden/normalizer_widths.npz (make_golden_norm_widths.py): the reference's RunningNormalizer
+    at 1, 2 and 3 features over batches of 1 .. 1000 rows - a one-feature batch is summed in numpy's pairwise order, a wider one
+    row after row - created with float32 rows, loaded (float32 statistics), created with float64 rows.  Statistics after every
+    update and the normalised probe (one row of it clipped), bit for bit."""
+    from conftest import load_golden
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    g = load_golden("normalizer_widths.npz")
+    sizes, k = [int(v) for v in g["sizes"]], f"d{D}_{regime}_"
+    assert sizes == [1, 2, 7, 8, 9, 16, 33, 128, 129, 136, 1000]
+    cast = np.float64 if regime == "c64" else np.float32
+    r32 = lambda z: np.asarray(z, np.float64).astype(np.float32)      # what the trainer keeps of a normalised row (src/env.py:189-190)
+    nz = DeviceRunningNormalizer(D)
+    if regime == "l32":
+        path = tmp_path / "n.yaml"
+        path.write_text(str(g[f"d{D}_yaml_text"]))
+        nz.load(str(path))
+        assert nz.float32 and np.array_equal(nz.mean, g[f"d{D}_load_mean"]) and np.array_equal(nz.var, g[f"d{D}_load_var"])
+    probe, x, at = g[f"d{D}_probe"].astype(cast), g[f"d{D}_x"], 0
+    assert x.shape == (sum(sizes), D) and x.dtype == np.float32
+    bad = []
+    for i, n in enumerate(sizes):
+        nz.update(np.ascontiguousarray(x[at:at + n].astype(cast)))
+        at += n
+        mean, var, z = nz.mean, nz.var, nz.normalize(probe)
+        assert mean.dtype == g[k + "mean"].dtype and z.dtype == g[k + "norm"].dtype, (n, mean.dtype, z.dtype)
+        ok = (np.array_equal(mean, g[k + "mean"][i]) and np.array_equal(var, g[k + "var"][i]) and nz.count == g[k + "count"][i]
+              and np.array_equal(r32(z), r32(g[k + "norm"][i])))
+        if not ok:
+            bad.append(n)
+    assert np.abs(r32(g[k + "norm"][-1])).max() == 5.0      # the clip engaged in the probe
+    assert not bad, f"D = {D}, {regime}: differs from the reference from the batch of {bad[0]} rows on (batches {bad})"
 
 
 def test_resume_with_device_normalizers(gcrl, tmp_path):

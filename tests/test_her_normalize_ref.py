@@ -172,8 +172,10 @@ def test_abi_declares_the_new_entries(gcrl):
 
 
 # what DESIGN.md §4m states for the unit: kernel -> (VGPRs, bytes of static LDS)
-KERNELS = {"her_norm_rows_kernel": (36, 2176), "her_norm_dense_kernel": (32, 2176), "her_process_step_raw_kernel": (42, 0),
-           "her_process_step_raw_inline_kernel": (42, 0), "her_process_step_raw_pop_kernel": (44, 0)}
+# (the process_step kernels: 42 / 42 / 44 VGPRs before norm_update_col's pairwise order for one-feature normalisers, whose running
+# sums and waiting left halves are kept in registers; still 0 bytes of scratch and LDS)
+KERNELS = {"her_norm_rows_kernel": (36, 2176), "her_norm_dense_kernel": (32, 2176), "her_process_step_raw_kernel": (72, 0),
+           "her_process_step_raw_inline_kernel": (90, 0), "her_process_step_raw_pop_kernel": (90, 0)}
 
 
 def test_new_kernels_use_no_scratch_and_the_stated_registers(tmp_path):
