@@ -1345,7 +1345,7 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
   g.h = her;
   if (!injected) g.gen = her->last_gen;   // (device-RNG mode: this member's draws, also when other members share the ring)
   g.n = rows_now;
-  g.gamma = a->cfg.gamma;                 // read at plan time: a set_hparams of gamma holds from the next call on (n-step returns, her_nstep.hip)
+  g.gamma = a->cfg.gamma;                 // read at plan time: a set_hparams of gamma holds from the next call on (n-step returns, her_relabel.hip)
   if (!injected && !per_dev && her->relabel_mode == GCRL_RELABEL_SAMPLE) {   // the relabel stream's counter as of this member's turn (her_ring.h)
     g.ctr = her->relabel_ctr;
     her->relabel_ctr += (uint64_t)rows_now;

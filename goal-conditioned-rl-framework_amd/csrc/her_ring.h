@@ -29,7 +29,7 @@
 //     f       = 1 + hash_below(seed, K, 2c + 1, rem);   fut = phys + f (mod cap)
 // a relabelled row takes record fut's tail ag as the goal of s and of ns, its reward by her_flush_kernel's arithmetic from the two
 // tails, done = 0.  Restated in tests/her_relabel_ref.py, which is the definition.
-// Goal selection (goal_strategy; kernels in her_strategy.hip, definition tests/her_strategy_ref.py).  The rule above is
+// Goal selection (goal_strategy; the same kernels, definition tests/her_strategy_ref.py).  The rule above is
 // GCRL_GOAL_FUTURE.  A ring created with GCRL_GOAL_EPISODE carries a second tail word, [ag (G) | remaining | elapsed]: `elapsed`, one
 // float holding the integer i, so RS = roundup(RW+G+2, 16); it sits at tail index 2 + G + 1 <= 11 of the record from o_r on, so
 // the gathers' 12-float tails hold it for G <= 8.  A lone appended row has elapsed = 0.  Rings of the other strategies keep the
@@ -117,7 +117,7 @@ struct gcrl_her {
   int relabel_mode = 0;               // GCRL_RELABEL_*
   int goal_strategy = 0;              // GCRL_GOAL_*: fixed at creation (GCRL_GOAL_EPISODE widens the record's tail)
   uint64_t relabel_ctr = 0;           // sample mode: rows ever gathered from this ring (the relabel stream's counter)
-  int n_step = 1;                     // sample mode: rows folded into a gathered row's reward and done flag (her_nstep.hip); configuration, not state
+  int n_step = 1;                     // sample mode: rows folded into a gathered row's reward and done flag (her_relabel.hip); configuration, not state
   double nstep_gamma = 0.0;           // the discount of the ring's own gathers (gcrl_her_sample, gcrl_her_gather_update); the update engine passes the agent's
   gcrl_mt* rng = nullptr;
   bool own_rng = false;
@@ -223,16 +223,17 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
                       void* cp_dst = nullptr, size_t cp_bytes = 0, const uint64_t* relabel_ctr = nullptr, const double* gamma = nullptr);
 // A ring in sample-time relabelling mode takes her_gather_relabel_kernel instead (her_relabel.hip).  relabel_ctr == null: the
 // launch's first row is the ring's relabel_ctr, which advances by n; otherwise *relabel_ctr, and the ring's counter is left
-// alone (the planner of the call advanced it: GatherCall::ctr).  With n_step > 1 such a ring takes her_gather_nstep_kernel
-// (her_nstep.hip), which discounts by float(*gamma) — the caller's, as its TD kernels cast it — or, gamma == null, by the ring's own.
+// alone (the planner of the call advanced it: GatherCall::ctr).  With n_step > 1 such a ring takes her_gather_nstep_kernel, which
+// discounts by float(*gamma) — the caller's, as its TD kernels cast it — or, gamma == null, by the ring's own.
 
 // sample-time relabelling mode (her_relabel.hip): the flush of `nep` staged episodes (T rows each, bookkeeping included), the
 // update engine's gather and the public sample's, each starting at relabel counter `ctr`; the indices are idx or, when null,
-// h->last_gen's
+// h->last_gen's.  Every goal_strategy and every n_step of the ring: the gathers pick the one-step or the n-step kernel by
+// h->n_step and discount by g32 (not read at n_step == 1).
 int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipStream_t st, int64_t* rows_out);
-int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, int64_t n, float* sa, float* nsa, float* spa, int ldx,
+int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
                               float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
-int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
+int her_relabel_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
                        float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
 // energy-prioritised draw of such a ring (her_prio.hip; a no-op / refusal unless gcrl_her_prio_attach gave it an energy tree).
 // her_prio_flush: ONE launch behind a flush launch — the leaves of the rows it wrote (stage / Ts / tail / skip: that launch's own
@@ -245,21 +246,6 @@ bool her_prio_on(const gcrl_her* h);
 uint64_t her_prio_take(gcrl_her* h, int64_t rows);
 int her_prio_check(const gcrl_her* h, const char* who);
 int her_prio_draw_at(gcrl_her* h, uint64_t c0, int64_t rows, uint32_t* idx_dev, hipStream_t st);
-// the same two gathers for a ring with n_step in 2..8 (her_nstep.hip), discounting by g32
-int her_nstep_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
-                            float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
-int her_nstep_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
-                     float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
-
-// a ring whose goal_strategy is GCRL_GOAL_FINAL or GCRL_GOAL_EPISODE (her_strategy.hip): the four entry points above hand over to
-// these — her_goal_flush for an EPISODE ring (a FINAL ring keeps her_flush_sample_kernel), the gathers for both, at every n_step
-// (g32 is not read at n_step == 1)
-int her_goal_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipStream_t st, int64_t* rows_out);
-int her_goal_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,
-                           float* r, float* d, hipStream_t st, const void* cp_src, void* cp_dst, size_t cp_bytes);
-int her_goal_sample(gcrl_her* h, const uint32_t* idx_dev, uint64_t ctr, float g32, int64_t n, float* out_s, int ld_s, float* out_a, int ld_a,
-                    float* out_r, float* out_ns, int ld_ns, float* out_d, hipStream_t st);
-
 // sample-time normalisation (her_norm.hip).  her_norm_on: the ring is raw.  her_norm_check: GCRL_ERR_STATE naming `normalize` when a
 // normaliser the ring's gathers need is not bound — callers ask before a ticket or a counter is consumed.  her_norm_rows: the
 // in-place pass over one gather's sa / nsa / spa (spa may be null; n rows of stride ldx), one launch.  her_norm_dense: the same for

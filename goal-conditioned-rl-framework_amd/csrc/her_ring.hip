@@ -721,10 +721,8 @@ int her_gather_update(gcrl_her* h, const uint32_t* idx_dev, int64_t n, float* sa
     uint64_t ctr = h->relabel_ctr;
     if (relabel_ctr) ctr = *relabel_ctr;
     else h->relabel_ctr += (uint64_t)n;
-    if (h->n_step > 1) {
-      const float g32 = (float)(gamma ? *gamma : h->nstep_gamma);
-      if (int rc = her_nstep_gather_update(h, idx_dev, ctr, g32, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
-    } else if (int rc = her_relabel_gather_update(h, idx_dev, ctr, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
+    const float g32 = (float)(gamma ? *gamma : h->nstep_gamma);
+    if (int rc = her_relabel_gather_update(h, idx_dev, ctr, g32, n, sa, nsa, spa, ldx, r, d, st, cp_src, cp_dst, cp_bytes)) return rc;
     if (int rc = prof_end(h, st, n)) return rc;
     return her_norm_rows(h, n, sa, nsa, spa, ldx, st);   // normalize = "sample": the in-place pass behind the gather (her_norm.hip)
   }
@@ -1189,9 +1187,7 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
     const uint64_t ctr = h->relabel_ctr;
     h->relabel_ctr += (uint64_t)n;
     const uint32_t* idx = h->idx_on_device ? h->idx_dev : nullptr;
-    if (h->n_step > 1) {
-      if (int rc = gcrl::her_nstep_sample(h, idx, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
-    } else if (int rc = gcrl::her_relabel_sample(h, idx, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    if (int rc = gcrl::her_relabel_sample(h, idx, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     if (int rc = prof_end(h, st, n)) return rc;
     return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
   }
@@ -1223,9 +1219,7 @@ int gcrl_her_sample_dev(gcrl_her* h, int64_t n, const uint32_t* idx_dev, float* 
     if (int rc = prof_begin(h, st)) return rc;
     const uint64_t ctr = h->relabel_ctr;
     h->relabel_ctr += (uint64_t)n;
-    if (h->n_step > 1) {
-      if (int rc = gcrl::her_nstep_sample(h, idx_dev, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
-    } else if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
+    if (int rc = gcrl::her_relabel_sample(h, idx_dev, ctr, (float)h->nstep_gamma, n, out_s, ld_s, out_a, ld_a, out_r, out_ns, ld_ns, out_d, st)) return rc;
     if (int rc = prof_end(h, st, n)) return rc;
     return gcrl::her_norm_dense(h, n, out_s, ld_s, out_ns, ld_ns, st);
   }

@@ -372,7 +372,7 @@ class HERBuffer(_RingState):
         self.prioritise = prioritise
         # goal_strategy (relabel="sample" only): which row of its episode a relabelled row takes its goal from — "future" (default:
         # a later row, nothing changes), "final" (the episode's last row) or "episode" (any other live row of the episode, earlier ones
-        # included; the ring's records then carry `elapsed` beside `remaining`).  csrc/her_strategy.hip; tests/her_strategy_ref.py is
+        # included; the ring's records then carry `elapsed` beside `remaining`).  csrc/her_relabel.hip; tests/her_strategy_ref.py is
         # the definition.  Fixed when the ring is created.
         self.goal_strategy = _check_goal_strategy("HERBuffer", goal_strategy, relabel)
         # normalize="sample" (either relabel mode): the ring stores RAW [obs | dg] states, next states and achieved goals, and every

@@ -133,7 +133,7 @@ int gcrl_her_relabel_mode(const gcrl_her* h);
 /* rows ever gathered from a GCRL_RELABEL_SAMPLE ring: the counter of its relabel stream (saved and loaded with the ring's state) */
 uint64_t gcrl_her_get_relabel_counter(const gcrl_her* h);
 int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter);
-/* n-step returns on a GCRL_RELABEL_SAMPLE ring: n_step = N in 1..8 (1, the default: one-step rows, the kernels of before).  With
+/* n-step returns on a GCRL_RELABEL_SAMPLE ring: n_step = N in 1..8 (1, the default: one-step rows).  With
  * N > 1 a gathered row p becomes a window of m = min(N, remaining + 1) rows of its episode: s, a of row p, ns of row p + m - 1,
  * r <- sum_j gamma^j r_j (each r_j recomputed against the new goal when the row is relabelled, otherwise as stored) and
  * d <- 1 - gamma^(m-1) (1 - d_last), so that the engine's r + gamma (1 - d) q' is the n-step target.  The relabel decision and the
@@ -144,7 +144,7 @@ int gcrl_her_set_relabel_counter(gcrl_her* h, uint64_t counter);
  * which may be NULL), -1 for a null handle. */
 int gcrl_her_set_nstep(gcrl_her* h, int n_step, double gamma);
 int gcrl_her_get_nstep(const gcrl_her* h, double* gamma);
-/* Goal selection of a GCRL_RELABEL_SAMPLE ring (csrc/her_strategy.hip; tests/her_strategy_ref.py is the definition):
+/* Goal selection of a GCRL_RELABEL_SAMPLE ring (csrc/her_relabel.hip; tests/her_strategy_ref.py is the definition):
  * WHICH row of its episode a relabelled row takes its goal from.  GCRL_GOAL_FUTURE (what gcrl_her_create_relabel makes): a uniformly
  * chosen later row.  GCRL_GOAL_FINAL: the episode's last row (an episode's last row itself is never relabelled).  GCRL_GOAL_EPISODE:
  * a uniformly chosen OTHER live row of the episode, earlier ones included; its records carry a second tail word,

@@ -1,4 +1,4 @@
-"""n-step returns on a sample-mode HER ring (HERBuffer(relabel="sample", n_step=N, gamma=g); csrc/her_nstep.hip) restated in numpy.
+"""n-step returns on a sample-mode HER ring (HERBuffer(relabel="sample", n_step=N, gamma=g); csrc/her_relabel.hip) restated in numpy.
 This file is the DEFINITION of the feature and builds on tests/her_relabel_ref.py, the definition of the mode: the kernels are held
 to it bit for bit.
 

@@ -1,4 +1,4 @@
-"""Goal selection of sample-time HER relabelling (HERBuffer(relabel="sample", goal_strategy=...); csrc/her_strategy.hip) restated in
+"""Goal selection of sample-time HER relabelling (HERBuffer(relabel="sample", goal_strategy=...); csrc/her_relabel.hip) restated in
 numpy.  This file is the DEFINITION of the `final` and `episode` strategies and builds on tests/her_relabel_ref.py (the mode) and
 tests/her_nstep_ref.py (n-step windows): the kernels are held to it bit for bit.  `future` here is those two files' rule, bit for bit.
 

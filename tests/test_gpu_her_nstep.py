@@ -1,4 +1,4 @@
-"""GPU (-m gpu): n-step returns on a sample-mode HER ring (HERBuffer(relabel="sample", n_step=N, gamma=g); csrc/her_nstep.hip) held
+"""GPU (-m gpu): n-step returns on a sample-mode HER ring (HERBuffer(relabel="sample", n_step=N, gamma=g); csrc/her_relabel.hip) held
 bit for bit to the numpy definition tests/her_nstep_ref.py: both gathers, n_step=1 against the keyword left out, the four agents
 and a population on top of them (each member with its own gamma), resume and refusals.  Helpers and shapes are those of
 tests/test_gpu_her_relabel.py."""

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the `final` and `episode` goal-selection strategies of a sample-mode HER ring (HERBuffer(relabel="sample",
-goal_strategy=...); csrc/her_strategy.hip) held bit for bit to the numpy definition tests/her_strategy_ref.py: the flush that
+goal_strategy=...); csrc/her_relabel.hip) held bit for bit to the numpy definition tests/her_strategy_ref.py: the flush that
 stamps `elapsed`, both gathers one-step and with n-step windows, `future` against the keyword left out, the four agents and a
 population on top of them, resume and refusals.  Helpers and shapes are those of tests/test_gpu_her_relabel.py."""
 import random

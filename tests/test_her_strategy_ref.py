@@ -1,8 +1,8 @@
 """Host tests (no GPU) of tests/her_strategy_ref.py, the numpy definition of the goal-selection strategies of a sample-mode HER
-ring (HERBuffer(relabel="sample", goal_strategy="future" | "final" | "episode"); csrc/her_strategy.hip): `future` is the rule of
+ring (HERBuffer(relabel="sample", goal_strategy="future" | "final" | "episode"); csrc/her_relabel.hip): `future` is the rule of
 before bit for bit, `episode` is uniform over the other live rows of the episode and never leaves it, `final` picks the last row,
-no tail — however dishonest — takes a slot out of the ring, the keyword's refusals come before any device work, and the new
-kernels use no scratch memory."""
+no tail — however dishonest — takes a slot out of the ring, the keyword's refusals come before any device work, and the
+unit's kernels use no scratch memory."""
 import math
 import os
 import re
@@ -204,15 +204,20 @@ def test_abi_declares_the_new_entries(gcrl):
 
 
 def test_new_kernels_use_no_scratch(tmp_path):
-    """her_strategy.hip compiled to gfx950 assembly with the Makefile's flags: .private_segment_fixed_size is 0 for each new kernel"""
+    """her_relabel.hip compiled to gfx950 assembly with the Makefile's flags: the unit has its six kernels and no others, and
+    .private_segment_fixed_size is 0 for each"""
     csrc = os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     flags = re.search(r"^CXXFLAGS\s*=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", re.search(r"^ARCH\s*\?=\s*(\S+)", mk, re.M).group(1)).split()
     hipcc = os.environ.get("HIPCC", re.search(r"^HIPCC\s*\?=\s*(\S+)", mk, re.M).group(1))
-    asm = tmp_path / "her_strategy.s"
-    subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, "her_strategy.hip"), "-o", str(asm)], check=True, cwd=csrc)
-    found = re.findall(r"\.name:\s+(\S*her_(?:gather_goal|flush_episode)\S*)\n((?:(?!\.name:).)*?)\.private_segment_fixed_size:\s+(\d+)", asm.read_text(), re.S)
+    asm = tmp_path / "her_relabel.s"
+    subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, "her_relabel.hip"), "-o", str(asm)], check=True, cwd=csrc)
+    text = asm.read_text()
+    found = re.findall(r"\.name:\s+(\S*_kernel\S*)\n((?:(?!\.name:).)*?)\.private_segment_fixed_size:\s+(\d+)", text, re.S)
     sizes = {n: int(sz) for n, _, sz in found}
-    # the flush, the one-step and n-step gathers <false> and <true>, the two public forms
-    assert len(sizes) == 7 and sum("pub_kernel" in n for n in sizes) == 2 and sum("flush_episode" in n for n in sizes) == 1, sizes
+    assert len(sizes) == len(re.findall(r"^\s*\.amdhsa_kernel\s", text, re.M)) == 6, sizes         # every kernel of the unit was found
+    # one flush, the one-step and n-step gathers <false> and <true>, one public form
+    count = lambda part: sum(part in n for n in sizes)
+    assert count("her_flush_sample_kernel") == 1 and count("her_gather_relabel_pub_kernel") == 1, sizes
+    assert count("her_gather_relabel_kernelILb") == 2 and count("her_gather_nstep_kernelILb") == 2, sizes
     assert all(v == 0 for v in sizes.values()), sizes

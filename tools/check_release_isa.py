@@ -88,7 +88,7 @@ def check_kernel(body):
 # by-value argument struct made hipcc copy the whole 3.7 KB struct to every thread's private memory — a 3 us kernel took 36 us
 # (rowchain_act_inline_kernel, round 4).  `.amdhsa_private_segment_fixed_size` says it all.
 SCRATCH_UNITS = ["her_ring.hip", "her_relabel.hip", "ops.hip", "ops_sac.hip", "bn_slab.hip", "rowchain.hip", "agent.hip", "normalizer.hip", "abi_misc.hip",
-                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip", "act_bn.hip", "pop_clone.hip", "her_prio.hip", "her_strategy.hip", "her_norm.hip",
+                 "gemm_mfma.hip", "xchg_ipc.hip", "dw_adam.hip", "adam_pop.hip", "act_bn.hip", "pop_clone.hip", "her_prio.hip", "her_norm.hip",
                  "her_bc.hip"]
 SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
     "rowchain_split_kernelILi4E": 64,   # 16 rows per workgroup: register spills; row_rg_of picks it only past one wave of 8-row blocks
@@ -102,9 +102,8 @@ SCRATCH_ALLOWED = {   # kernel-name substring -> bytes tolerated
 # ... and the one-launch device copy of gcrl_pop_clone (pop_clone.hip)
 SCRATCH_NAMED = {"pop_clone.hip": ["pop_clone_kernel"], "her_bc.hip": ["bc_qfilter_kernel"], "her_prio.hip": ["her_energy_kernel", "her_prio_draw_kernel"],
                  "rowchain.hip": ["rowchain_act_pop_kernel"], "her_ring.hip": ["her_process_step_pop_kernel", "her_gather_update_pop_kernel"],
-                 "her_relabel.hip": ["her_flush_sample_kernel", "her_gather_relabel_kernel", "her_gather_relabel_pub_kernel"],
-                 "her_strategy.hip": ["her_flush_episode_kernel", "her_gather_goal_kernel", "her_gather_goal_nstep_kernel",
-                                      "her_gather_goal_pub_kernel", "her_gather_goal_nstep_pub_kernel"],
+                 "her_relabel.hip": ["her_flush_sample_kernel", "her_gather_relabel_kernelILb0E", "her_gather_relabel_kernelILb1E",
+                                     "her_gather_nstep_kernelILb0E", "her_gather_nstep_kernelILb1E", "her_gather_relabel_pub_kernel"],
                  "her_norm.hip": ["her_norm_rows_kernel", "her_norm_dense_kernel", "her_process_step_raw_kernel", "her_process_step_raw_inline_kernel",
                                   "her_process_step_raw_pop_kernel"],
                  "ops_sac.hip": ["tanh_gauss_fwd_pop_kernel", "tanh_gauss_fwd2_pop_kernel", "tanh_gauss_bwd_pop_kernel"],

@@ -4,17 +4,20 @@
     python tools/relabel_bench.py --parse DIR
 
 --run fills rings of 1e6 records at PickAndPlace dims (S 23, A 4, G 3; k_future 4, rng="device": no host draw, no index
-upload) — one per relabel mode, and for the sample mode one more per n_step in NSTEPS (gamma 0.98; n_step = 1 is the sample-mode
-ring itself), and one per goal strategy in GOALS at n_step 1 and at GOAL_NSTEP (csrc/her_strategy.hip) — and then, alternating the rings, issues the update engine's gather (HERBuffer.gather_update) at 9 216 and 77 824
-rows, and the flush of one T = 50 episode (push_episode; the two modes and the `episode` ring, whose flush stamps `elapsed`:
-n_step does not reach the flush, and a `final` ring launches the sample mode's).  Nothing is timed
-here: the kernel trace is.
---parse reads the trace and prints, per kernel and launch size, the number of launches, the median and the range of the kernel
-durations — the launches after the warm-up ones.  The n-step rings launch one kernel at one grid size: their launches alternate in
-NSTEPS order and are told apart by that; so do the rings of the goal strategies, in GOALS order.  No GPU: --run fails; it does not fall back.
---rings NAME[,NAME ...] builds and times only those rings (push, sample, sample_n3, final, episode_n3, ...).  `sample_norm` is the
-sample-mode ring with normalize="sample" (csrc/her_norm.hip; observation and goal normalisers bound): behind each of its gathers runs
-her_norm_rows_kernel, whose launches are listed beside the her_gather_relabel_kernel ones they follow."""
+upload) in this order: `push` and `sample`, one per relabel mode; `sample_n3`, `sample_n8`, the sample mode with n_step in NSTEPS
+(gamma 0.98); `final`, `episode`, one per goal strategy in GOALS, then `final_n3`, `episode_n3`, the same at n_step GOAL_NSTEP; and
+`sample_norm` (below).  Then, the rings alternating IN THAT ORDER inside every iteration, it issues the update engine's gather
+(HERBuffer.gather_update) at 9 216 and 77 824 rows, then the public sample (HERBuffer.sample) at 9 216 rows on the sample-mode rings,
+then the flush of one T = 50 episode (push_episode) on `push`, `sample` and `episode` (n_step does not reach the flush; only an
+`episode` ring's flush stamps `elapsed`).  Nothing is timed here: the kernel trace is.
+--parse reads the trace and prints, per kernel, ring and launch size, the number of launches, the median and the range of the
+kernel durations — the launches after the warm-up ones.  All sample-mode rings launch the same kernels (csrc/her_relabel.hip) at the
+same grids — her_gather_relabel_kernel at n_step 1, her_gather_nstep_kernel above it, her_gather_relabel_pub_kernel for the public
+sample, her_flush_sample_kernel — so a kernel's launches are told apart by the order above alone: launch i of a kernel at a grid
+belongs to ring i mod R of the R rings that launch it.  No GPU: --run fails; it does not fall back.
+--rings NAME[,NAME ...] builds and times only those rings; give --parse the same list.  `sample_norm` is the sample-mode ring with
+normalize="sample" (csrc/her_norm.hip; observation and goal normalisers bound): behind each of its gathers runs
+her_norm_rows_kernel (her_norm_dense_kernel behind its public sample), listed beside the gathers they follow."""
 import argparse
 import csv
 import glob
@@ -93,21 +96,31 @@ def run(only=None):
     torch.cuda.synchronize()
     for B, M in SIZES:
         for _ in range(WARM + ITERS):
-            for mode in rings:                              # push, sample (N = 1), the n-step rings in NSTEPS order, the goal rings in GOALS order
+            for mode in rings:                              # in ORDER
                 rings[mode].gather_update(B, M)
     for _ in range(WARM + ITERS):
-        for mode in ("push", "sample", "episode"):
+        for mode in rings:
+            if mode != "push":
+                rings[mode].sample(*SIZES[0])
+    for _ in range(WARM + ITERS):
+        for mode in FLUSHED:
             if mode in rings:
                 rings[mode].push_episode(1, *ep)
     torch.cuda.synchronize()
     print("relabel_bench: done")
 
 
-NAMES = ("her_gather_update_kernel", "her_gather_relabel_kernel", "her_gather_nstep_kernel", "her_gather_goal_kernel", "her_gather_goal_nstep_kernel",
-         "her_flush_kernel", "her_flush_sample_kernel", "her_flush_episode_kernel", "her_norm_rows_kernel")
+# the rings in the order --run builds and alternates them, and which of them launch a kernel (a kernel that is not listed has one ring)
+ORDER = ("push", "sample") + tuple(f"sample_n{N}" for N in NSTEPS) + GOALS + tuple(f"{g}_n{GOAL_NSTEP}" for g in GOALS) + ("sample_norm",)
+FLUSHED = ("push", "sample", "episode")
+ONE_STEP = ("sample",) + GOALS + ("sample_norm",)
+RINGS_OF = {"her_gather_update_kernel": ("push",), "her_flush_kernel": ("push",),
+            "her_gather_relabel_kernel": ONE_STEP, "her_gather_nstep_kernel": tuple(r for r in ORDER[1:] if r not in ONE_STEP),
+            "her_gather_relabel_pub_kernel": ORDER[1:], "her_flush_sample_kernel": FLUSHED[1:],
+            "her_norm_rows_kernel": ("sample_norm",), "her_norm_dense_kernel": ("sample_norm",)}
 
 
-def parse(d):
+def parse(d, only=None):
     files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
         sys.exit(f"no kernel trace under {d}")
@@ -115,39 +128,31 @@ def parse(d):
     for f in files:
         for r in csv.DictReader(open(f)):
             name = r["Kernel_Name"]
-            key = next((n for n in NAMES if n in name), None)
+            key = next((n for n in RINGS_OF if n in name), None)
             if key is None:
                 continue
             grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r.get("Grid_Size_X", 0))
             rows.setdefault((key, grid), []).append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
-    for (key, grid), v in list(rows.items()):
-        if key == "her_gather_nstep_kernel":                 # launches alternate between the n-step rings
-            v.sort()
-            del rows[key, grid]
-            for i, N in enumerate(NSTEPS):
-                rows[f"{key} N={N}", grid] = v[i::len(NSTEPS)]
-        if key in ("her_gather_goal_kernel", "her_gather_goal_nstep_kernel"):     # launches alternate between the strategies' rings
-            v.sort()
-            del rows[key, grid]
-            for i, goal in enumerate(GOALS):
-                rows[f"{key} {goal}" + (f" N={GOAL_NSTEP}" if "nstep" in key else ""), grid] = v[i::len(GOALS)]
     for (key, grid), v in sorted(rows.items()):
         v.sort()
-        if len(v) < ITERS:           # the fill's flushes have their own grid sizes only in push mode; keep the timed tail of each
+        rings = [r for r in RINGS_OF[key] if only is None or r in only]
+        v = v[-len(rings) * ITERS:]  # the timed tail: the fill's flushes and the warm-up launches come first
+        if not rings or len(v) < len(rings) * ITERS:
             continue
-        dur = [x[1] / 1e3 for x in v[-ITERS:]]
-        print(f"{key:42s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
-              f"range {min(dur):7.2f} .. {max(dur):7.2f} us")
+        for i, ring in enumerate(rings):
+            dur = [x[1] / 1e3 for x in v[i::len(rings)]]
+            print(f"{key:30s} {ring:12s} grid {grid:8d} threads: {len(dur)} launches, median {statistics.median(dur):7.2f} us, "
+                  f"range {min(dur):7.2f} .. {max(dur):7.2f} us")
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--run", action="store_true")
     ap.add_argument("--parse", metavar="DIR")
-    ap.add_argument("--rings", default=None, help="with --run: comma-separated ring names to build and time (default: all)")
+    ap.add_argument("--rings", default=None, help="comma-separated ring names to build and time, or to parse (default: all)")
     a = ap.parse_args()
     if a.parse:
-        parse(a.parse)
+        parse(a.parse, a.rings.split(",") if a.rings else None)
     elif a.run:
         run(a.rings.split(",") if a.rings else None)
     else:
