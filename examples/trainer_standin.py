@@ -217,8 +217,10 @@ if __name__ == "__main__":
                     help="push: relabelled copies stored at every flush (the reference's form); sample: rows stored once, relabelled when a batch is drawn")
     ap.add_argument("--n-step", type=int, default=1,
                     help="with --relabel sample: n-step returns, 1..8 (the gather folds the next N - 1 rows of the episode into reward and done)")
-    ap.add_argument("--prioritise", default=None, choices=["energy"],
-                    help="with --relabel sample: draw episodes in proportion to the energy their achieved-goal trajectory gained")
+    ap.add_argument("--prioritise", default=None, choices=["energy", "td_error"],
+                    help="with --relabel sample: 'energy' draws episodes in proportion to the energy their achieved-goal trajectory gained; "
+                         "'td_error' is TD-error prioritised replay on the HER ring (HER + PER: the priorities follow the loss, new rows "
+                         "enter at the largest priority seen so far, the critic losses carry importance-sampling weights)")
     ap.add_argument("--goal-strategy", default="future", choices=["future", "final", "episode"],
                     help="with --relabel sample: a relabelled row's goal comes from a later row of its episode, its last row, or any other row of it")
     ap.add_argument("--normalize", default="push", choices=["push", "sample"],

@@ -260,6 +260,9 @@ PROTOTYPES = {
     "gcrl_her_prio_draw": (C.c_int, [_vp, _i64, _vp, _vp]),
     "gcrl_her_get_prio_counter": (_u64, [_vp]),
     "gcrl_her_set_prio_counter": (C.c_int, [_vp, _u64]),
+    "gcrl_her_td_attach": (C.c_int, [_vp, _f32, _f32]),
+    "gcrl_her_td_get_pmax": (C.c_int, [_vp, _vp]),
+    "gcrl_her_td_set_pmax": (C.c_int, [_vp, _f32]),
     "gcrl_agent_set_prior": (C.c_int, [_vp, _vp, C.c_int]),
     "gcrl_agent_get_prior": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
     "gcrl_agent_prior_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

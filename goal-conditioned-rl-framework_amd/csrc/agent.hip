@@ -1283,8 +1283,12 @@ int begin_call_plan(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gc
     if (a->xchg) return fail(GCRL_ERR_STATE, "update: prioritise: a ring with an energy tree does not feed an agent under a gradient exchange");
     TRY(her_prio_check(her, "update"));
   }
-  GCRL_CHECK_ARG(injected || (in && in->idx_host) || !per_is_td(her->per) || a->per_call,
-                 "update: this entry does not draw from a ring's priority tree (per_draw=\"device\"): use gcrl_agent_update / gcrl_agent_update_n");
+  if (!(injected || (in && in->idx_host) || !per_is_td(her->per) || a->per_call)) {
+    if (her_td_on(her))
+      return fail(GCRL_ERR_ARG, "update: prioritise: this entry does not draw from a ring's TD-error tree (prioritise=\"td_error\"): use "
+                                "gcrl_agent_update / gcrl_agent_update_n");
+    return fail(GCRL_ERR_ARG, "update: this entry does not draw from a ring's priority tree (per_draw=\"device\"): use gcrl_agent_update / gcrl_agent_update_n");
+  }
   if (!injected && in && in->idx_host)     // every argument is checked before a ticket, slot or plan is consumed
     for (int i = 0; i < a->B; ++i)
       GCRL_CHECK_ARG((int64_t)in->idx_host[i] < her->len, "update: row index %u outside the ring (len %lld)", in->idx_host[i], (long long)her->len);
@@ -2070,13 +2074,22 @@ int gcrl_agent_profile_read(gcrl_agent* a, int64_t* launches_out, double* total_
 // freeze beta, head, len and the draw counter); the step itself replays its graph as on the host-drawn path.
 int run_per_device(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcrl_update_inputs* in, int64_t* tickets_out, int32_t* lens_out,
                    hipStream_t st) {
+  // a sample-mode HER ring's TD-error tree (her_td.hip) runs the same loop: its refusals name `prioritise`
+  const bool her_td = her_td_on(her);
+  const char* mode = her_td ? "prioritise: prioritise=\"td_error\"" : "per_draw=\"device\"";
   GCRL_CHECK_ARG(!a->rowchain && a->Q == 1 && a->cfg.pipeline_steps == 0,
-                 "update: per_draw=\"device\" (a ring with a priority tree) needs the layer-per-launch schedule (pipeline_steps = 0) and scalar critics");
-  GCRL_CHECK_ARG(!a->xchg, "update: per_draw=\"device\" does not run under a gradient exchange");
-  GCRL_CHECK_ARG(!in || (n == 1 && !in->weights_host), "update: per_draw=\"device\": injected noise drives one step; weights come from the tree");
+                 "update: %s (a ring with a priority tree) needs the layer-per-launch schedule (pipeline_steps = 0) and scalar critics", mode);
+  if (a->xchg && her_td)   // (a state of the handle, not an argument: GCRL_ERR_STATE, as the energy tree's refusal)
+    return fail(GCRL_ERR_STATE, "update: %s does not run under a gradient exchange", mode);
+  GCRL_CHECK_ARG(!a->xchg, "update: %s does not run under a gradient exchange", mode);
+  GCRL_CHECK_ARG(!in || (n == 1 && !in->weights_host), "update: %s: injected noise drives one step; weights come from the tree", mode);
   GCRL_CHECK_ARG(n >= 1, "update: n must be >= 1");
+  if (her_td && a->prior)      // every refusal before a ticket, slot, draw or relabel counter is consumed
+    return fail(GCRL_ERR_STATE, "update: prioritise: an agent with a prior ring does not train from a ring with a TD-error tree (prior rows have no leaf)");
+  if (her_td && a->bc_weight > 0.0)
+    return fail(GCRL_ERR_STATE, "update: prioritise: the behaviour-cloning term (bc_weight) does not combine with the tree's importance-sampling weights");
   if (her->per->betas.size() - her->per->beta_pos < (size_t)n)    // checked before a ticket, slot or plan is consumed
-    return fail(GCRL_ERR_STATE, "update: per_draw=\"device\": %zu beta values queued for %d steps from step %lld (gcrl_per_set_betas)",
+    return fail(GCRL_ERR_STATE, "update: %s: %zu beta values queued for %d steps from step %lld (gcrl_per_set_betas)", mode,
                 her->per->betas.size() - her->per->beta_pos, n, (long long)step0);
   const int B = a->B, chunk = std::min(kMaxStepsPerCall, a->Mmax);
   int extra = V_WEIGHTS;
@@ -2089,13 +2102,20 @@ int run_per_device(gcrl_agent* a, gcrl_her* her, int64_t step0, int n, const gcr
     a->per_call = false;
     if (rc) return rc;
     if (in) TRY(stage_injected(a, in, st, &extra));   // (injected noise / eps: device-to-device copies)
+    // a sample-mode ring relabels what it gathers: the relabel stream's counter as of this call, B rows per step (begin_call_plan
+    // leaves it alone on this path), and the agent's gamma for the n-step returns, as on the host-drawn path
+    const bool relabels = her->relabel_mode == GCRL_RELABEL_SAMPLE;
+    const uint64_t ctr0 = her->relabel_ctr;
+    if (relabels) her->relabel_ctr += (uint64_t)m * B;
+    const double gamma = a->cfg.gamma;
     for (int i = 0; i < m; ++i) {
       float beta = 0.0f;
       (void)per_next_beta(her, &beta);
       uint32_t* idx = a->idx_dev() + (size_t)i * B;
       TRY(per_draw(her, B, beta, idx, a->w_in, st));
+      const uint64_t ctr = ctr0 + (uint64_t)i * B;
       TRY(her_gather_update(her, idx, B, a->sa + i * a->slot_x, a->nsa + i * a->slot_x, a->spa + i * a->slot_x, a->ldx, a->rbuf + i * a->slot_rd,
-                            a->dbuf + i * a->slot_rd, st));
+                            a->dbuf + i * a->slot_rd, st, nullptr, nullptr, 0, relabels ? &ctr : nullptr, relabels ? &gamma : nullptr));
       TRY(run_step(a, st, plans[i].variant | norm_bits(a) | extra, 7));
       TRY(per_update(her, idx, a->td_abs, B, a->per_hist + (size_t)i * B, st));
     }

@@ -373,6 +373,8 @@ int gcrl_pop_update_n(gcrl_pop* p, gcrl_her* const* rings, int64_t step0, int32_
     GCRL_CHECK_ARG(rings[i], "gcrl_pop_update_n: member %d has no replay ring", i);
     if (her_prio_on(rings[i]))
       return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: prioritise: member %d's ring has an energy tree; populations do not draw from one", i);
+    if (her_td_on(rings[i]))
+      return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: prioritise: member %d's ring has a TD-error tree; populations do not draw from one", i);
     GCRL_CHECK_ARG(!a->xchg && a->bn_sync.world <= 1, "gcrl_pop_update_n: member %d is in a data-parallel group", i);
     GCRL_CHECK_ARG(!a->prof, "gcrl_pop_update_n: member %d has launch profiling on", i);
     if (a->bc_weight > 0.0) return fail(GCRL_ERR_STATE, "gcrl_pop_update_n: bc_weight: member %d has the behaviour-cloning term on; populations do not step it", i);
@@ -744,6 +746,8 @@ int gcrl_pop_clone(gcrl_pop* p, gcrl_her* const* rings, const int32_t* src, cons
       GCRL_CHECK_ARG(s != d, "gcrl_pop_clone: rings: members %d and %d share a replay ring", src[k], dst[k]);
       if (her_prio_on(s) || her_prio_on(d))
         return fail(GCRL_ERR_STATE, "gcrl_pop_clone: prioritise: a ring with an energy tree is not cloned (members %d, %d)", src[k], dst[k]);
+      if (her_td_on(s) || her_td_on(d))
+        return fail(GCRL_ERR_STATE, "gcrl_pop_clone: prioritise: a ring with a TD-error tree is not cloned (members %d, %d)", src[k], dst[k]);
 #define GCRL_RING_SAME(expr, field) \
   GCRL_CHECK_ARG(s->expr == d->expr, "gcrl_pop_clone: %s: member %d's ring has %lld, member %d's %lld", field, src[k], (long long)s->expr, dst[k], (long long)d->expr)
       GCRL_RING_SAME(cfg.capacity, "capacity");

@@ -238,7 +238,7 @@ int gcrl_her_set_normalize(gcrl_her* h, gcrl_normalizer* nz_obs, gcrl_normalizer
                  "gcrl_her_set_normalize: normalize: observation normaliser of size %d for obs_dim %d", gcrl_normalizer_size(nz_obs), obs_dim);
   GCRL_CHECK_ARG(!nz_dg || gcrl_normalizer_size(nz_dg) == h->G,
                  "gcrl_her_set_normalize: normalize: goal normaliser of size %d for goal_dim %d", gcrl_normalizer_size(nz_dg), h->G);
-  GCRL_CHECK_ARG(!gcrl::per_is_td(h->per), "gcrl_her_set_normalize: normalize: a ring with a TD priority tree (PER) stores what it is given; "
+  GCRL_CHECK_ARG(!gcrl::per_is_td(h->per) || gcrl::per_is_her_td(h->per), "gcrl_her_set_normalize: normalize: a ring with a TD priority tree (PER) stores what it is given; "
                                            "sample-time normalisation is a HER ring's");
   if (h->normalize_mode != GCRL_NORMALIZE_SAMPLE) {
     bool staged = false;

@@ -253,7 +253,10 @@ int gcrl_her_prio_attach(gcrl_her* h, const gcrl_energy_config* cfg) {
   return GCRL_OK;
 }
 
-int gcrl_her_prio_mode(const gcrl_her* h) { return h && gcrl::per_is_energy(h->per) ? GCRL_PRIO_ENERGY : GCRL_PRIO_NONE; }
+int gcrl_her_prio_mode(const gcrl_her* h) {
+  if (h && gcrl::per_is_her_td(h->per)) return GCRL_PRIO_TD;
+  return h && gcrl::per_is_energy(h->per) ? GCRL_PRIO_ENERGY : GCRL_PRIO_NONE;
+}
 
 int gcrl_her_prio_draw(gcrl_her* h, int64_t rows, uint32_t* idx_dev, void* stream) {
   GCRL_CHECK_ARG(h, "gcrl_her_prio_draw: null ring");

@@ -77,6 +77,8 @@ int her_prior_check_call(const gcrl_her* main_ring, const gcrl_her* prior, int B
   if (prior->S != main_ring->S || prior->A != main_ring->A || prior->G != main_ring->G)
     return fail(GCRL_ERR_STATE, "%s: prior_buffer: the prior ring's dims (S=%d,A=%d,G=%d) differ from the main ring's (S=%d,A=%d,G=%d)", who,
                 prior->S, prior->A, prior->G, main_ring->S, main_ring->A, main_ring->G);
+  if (per_is_her_td(main_ring->per))
+    return fail(GCRL_ERR_STATE, "%s: prioritise: a main ring with a TD-error tree weighs and re-prioritises every row it draws; prior rows have no leaf", who);
   if (per_is_td(main_ring->per))
     return fail(GCRL_ERR_STATE, "%s: prior_buffer: a main ring with a TD priority tree weighs and re-prioritises every row it draws; prior rows have no leaf", who);
   if (her_norm_on(prior) != her_norm_on(main_ring))

@@ -542,7 +542,8 @@ int her_relabel_flush(gcrl_her* h, int nep, const int* envs, const int* Ts, hipS
   h->mutation_epoch++;
   *rows_out = total;
   // a ring with an energy tree: the leaves of the rows just written, from the same staged records, in stream order behind the flush
-  return her_prio_flush(h, nep, fa.stage, fa.T, fa.tail, fa.skip, total, st);
+  if (int rc = her_prio_flush(h, nep, fa.stage, fa.T, fa.tail, fa.skip, total, st)) return rc;
+  return her_td_flush(h, total, st);   // a ring with a TD-error tree: the rows just written enter at p_max (her_td.hip)
 }
 
 int her_relabel_gather_update(gcrl_her* h, const uint32_t* idx, uint64_t ctr, float g32, int64_t n, float* sa, float* nsa, float* spa, int ldx,

@@ -246,6 +246,11 @@ bool her_prio_on(const gcrl_her* h);
 uint64_t her_prio_take(gcrl_her* h, int64_t rows);
 int her_prio_check(const gcrl_her* h, const char* who);
 int her_prio_draw_at(gcrl_her* h, uint64_t c0, int64_t rows, uint32_t* idx_dev, hipStream_t st);
+// TD-error tree of such a ring (her_td.hip; a no-op unless gcrl_her_td_attach gave it one).  her_td_flush: ONE launch behind a flush
+// launch of `total` rows (the ring's head / len already advanced) — their leaves <- p_max as that device word stands in stream
+// order, their ancestors recomputed.  her_td_on: the ring has such a tree.
+int her_td_flush(gcrl_her* h, int64_t total, hipStream_t st);
+bool her_td_on(const gcrl_her* h);
 // sample-time normalisation (her_norm.hip).  her_norm_on: the ring is raw.  her_norm_check: GCRL_ERR_STATE naming `normalize` when a
 // normaliser the ring's gathers need is not bound — callers ask before a ticket or a counter is consumed.  her_norm_rows: the
 // in-place pass over one gather's sa / nsa / spa (spa may be null; n rows of stride ldx), one launch.  her_norm_dense: the same for

@@ -975,6 +975,8 @@ int64_t gcrl_her_append(gcrl_her* h, const float* state, int state_on_device, co
     return gcrl::fail(GCRL_ERR_ARG, "gcrl_her_append: normalize: a ring marked raw (normalize=\"sample\") takes episodes through the HER entries, not lone rows");
   if (gcrl::her_prio_on(h))
     return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_append: prioritise: a ring with an energy tree takes whole episodes (a lone row has no trajectory)");
+  if (gcrl::her_td_on(h))
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_append: prioritise: a ring with a TD-error tree seeds the rows of its flushes; a lone row would get no leaf");
   hipStream_t st = h->pick(stream);
   gcrl::RingBook book{h->cfg.capacity, h->head, h->len};
   const int64_t phys = book.tail();
@@ -1173,6 +1175,9 @@ int gcrl_her_sample(gcrl_her* h, int B, int M, const uint32_t* idx_host, float* 
   GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_sample: B and M must be >= 1");
   GCRL_CHECK_ARG(ld_s >= h->S && ld_ns >= h->S && ld_a >= h->A, "gcrl_her_sample: row stride smaller than the row");
   if (int rc = gcrl::her_norm_check(h, "gcrl_her_sample")) return rc;
+  if (!idx_host && gcrl::her_td_on(h))   // (a uniform draw here would pass for a prioritised one)
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_sample: prioritise: a ring with a TD-error tree draws through gcrl_per_draw (weights, counter) and "
+                      "gathers through gcrl_her_sample_dev; give indices, or use those");
   hipStream_t st = h->pick(stream);
   const uint32_t* host_copy = nullptr;
   if (!idx_host && gcrl::her_prio_on(h)) {   // prioritise = "energy": the tree draws the rows
@@ -1245,6 +1250,9 @@ int gcrl_her_gather_update(gcrl_her* h, int B, int M, const uint32_t* idx_host, 
   GCRL_CHECK_ARG(B >= 1 && M >= 1, "gcrl_her_gather_update: B and M must be >= 1");
   GCRL_CHECK_ARG(side_bytes >= 0, "gcrl_her_gather_update: side_bytes %lld", (long long)side_bytes);
   if (int rc = gcrl::her_norm_check(h, "gcrl_her_gather_update")) return rc;   // before an index is drawn
+  if (!idx_host && gcrl::her_td_on(h))
+    return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_gather_update: prioritise: a ring with a TD-error tree draws through gcrl_per_draw; give indices "
+                      "(the update engine draws and gathers per step itself)");
   hipStream_t st = h->pick(stream);
   if (!idx_host && gcrl::her_prio_on(h)) {
     if (int rc = gcrl::her_prio_indices(h, B, M, st, nullptr)) return rc;

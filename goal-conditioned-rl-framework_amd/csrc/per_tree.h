@@ -25,6 +25,8 @@ struct gcrl_per_tree {
   int source = 0;               // gcrl::kPerSourceTd (leaves = (|td| + eps)^alpha, fed back by the update engine) or kPerSourceEnergy
   gcrl_energy_config energy{};  // kPerSourceEnergy (her_prio.hip): leaves written once, by the ring's flush
   uint64_t prio_ctr = 0;        // kPerSourceEnergy: rows ever drawn (the draw stream's counter)
+  bool her_td = false;          // kPerSourceTd on a sample-mode HER ring (her_td.hip): new rows enter at p_max, seeded by the flush
+  float* p_max = nullptr;       // her_td: ONE fp32 word on the device, the largest finite priority an update has written (initially 1.0f)
 };
 
 namespace gcrl {
@@ -34,6 +36,7 @@ constexpr uint64_t kPerKey = 0x5045525f54524545ull;   // "PER_TREE": key of the 
 constexpr int kPerSourceTd = 0, kPerSourceEnergy = 1;
 inline bool per_is_td(const gcrl_per_tree* t) { return t && t->source == kPerSourceTd; }
 inline bool per_is_energy(const gcrl_per_tree* t) { return t && t->source == kPerSourceEnergy; }
+inline bool per_is_her_td(const gcrl_per_tree* t) { return per_is_td(t) && t->her_td; }   // a TD tree all the same: per_is_td routes it
 
 void per_release(gcrl_her* h);
 // a zeroed tree for the ring's capacity, not yet attached (*out; freed by the caller on a later failure: per_tree_free)
@@ -48,6 +51,8 @@ int per_refresh(gcrl_her* h, hipStream_t st);
 int per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, hipStream_t st);
 // leaves of idx_dev[B] <- (|td| + eps)^alpha, last occurrence wins, ancestors recomputed; hist_dev (may be null) <- td
 int per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B, float* hist_dev, hipStream_t st);
+// her_td.hip: per_update's launch for the TD tree of a sample-mode HER ring (her_td == true), which also raises p_max
+int her_td_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B, float* hist_dev, hipStream_t st);
 // next queued beta of the engine's steps; false: none queued
 bool per_next_beta(gcrl_her* h, float* beta);
 

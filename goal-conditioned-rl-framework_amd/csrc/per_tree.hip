@@ -22,17 +22,7 @@ constexpr int kWaves = 4;               // waves per workgroup of the multi-work
 constexpr int kOneWgThreads = 1024;     // the single-workgroup kernels (levels separated by barriers)
 constexpr int64_t kPerRefreshOne = 65536;
 
-struct TreeView {
-  float* tree;
-  long long off[kPerMaxLevels];
-  int levels;
-};
-
-__device__ inline float wave_sum64(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;   // the same bits in every lane (a + b == b + a)
-}
+#include "per_tree_dev.inc"   // TreeView, wave_sum64, reduce_range, view_of: shared with her_td.hip
 
 // level k+1 <- the reduction of level k, one wave per node
 __global__ __launch_bounds__(64 * kWaves) void per_level_kernel(const float* __restrict__ child, float* __restrict__ parent, long long nodes) {
@@ -47,16 +37,6 @@ __global__ __launch_bounds__(256) void per_fill_kernel(float* __restrict__ leave
   const long long na = a1 - a0, n = na + (b1 - b0);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     leaves[i < na ? a0 + i : b0 + (i - na)] = value;
-}
-
-// the entries [x0, x1) of level k - 1 changed: recompute their parents on level k; one wave per node
-__device__ inline void reduce_range(const TreeView& t, int k, long long p0, long long p1, int wave, int nwaves, int lane) {
-  const float* child = t.tree + t.off[k - 1];
-  float* parent = t.tree + t.off[k];
-  for (long long node = p0 + wave; node < p1; node += nwaves) {
-    const float s = wave_sum64(child[node * kPerFan + lane]);
-    if (lane == 0) parent[node] = s;
-  }
 }
 
 // pushes since the last refresh: leaves of two slot segments <- value, then their ancestors level by level (one workgroup,
@@ -184,14 +164,6 @@ __global__ __launch_bounds__(kOneWgThreads) void per_update_kernel(UpdArgs a) {
   }
 }
 
-TreeView view_of(const gcrl_per_tree* t) {
-  TreeView v;
-  v.tree = t->tree;
-  for (int k = 0; k < kPerMaxLevels; ++k) v.off[k] = t->L.off[k];
-  v.levels = t->L.levels;
-  return v;
-}
-
 int rebuild(gcrl_per_tree* t, hipStream_t st) {
   for (int k = 1; k < t->L.levels; ++k) {
     const long long nodes = t->L.padded[k - 1] / kPerFan;
@@ -221,6 +193,7 @@ void per_tree_free(gcrl_per_tree* t) {
   if (!t) return;
   if (t->tree) (void)hipFree(t->tree);
   if (t->p_drawn) (void)hipFree(t->p_drawn);
+  if (t->p_max) (void)hipFree(t->p_max);
   delete t;
 }
 
@@ -253,7 +226,8 @@ void per_mark_stale(gcrl_her* h) {
 
 int per_refresh(gcrl_her* h, hipStream_t st) {
   gcrl_per_tree* t = h->per;
-  const int64_t pending = per_is_td(t) ? (int64_t)(h->rows_pushed - t->synced_rows) : 0;   // an energy tree's leaves are the flush's: never 1.0
+  // an energy tree's leaves are the flush's, and so are a HER ring's TD tree's (p_max, her_td.hip): never 1.0
+  const int64_t pending = per_is_td(t) && !t->her_td ? (int64_t)(h->rows_pushed - t->synced_rows) : 0;
   t->synced_rows = h->rows_pushed;
   const PerSegs s = per_pending_segments(h->head, h->len, h->cfg.capacity, pending);
   const int64_t n = (s.a1 - s.a0) + (s.b1 - s.b0);
@@ -276,7 +250,8 @@ int per_draw(gcrl_her* h, int B, float beta, uint32_t* idx_dev, float* w_dev, hi
   if (int rc = need_tree(h, "per_draw", true, true)) return rc;
   gcrl_per_tree* t = h->per;
   GCRL_CHECK_ARG(idx_dev && B >= 1 && B <= (1 << 20), "per_draw: batch size %d (1..2^20) / null index buffer", B);
-  if (h->len < B) return fail(GCRL_ERR_NOT_ENOUGH, "Not enough in buffer to sample");
+  // (a HER ring's TD tree draws with replacement from whatever rows there are; the callers that need B rows ask for them themselves)
+  if (t->her_td ? h->len < 1 : h->len < B) return fail(GCRL_ERR_NOT_ENOUGH, "Not enough in buffer to sample");
   if (B > t->p_cap) {
     if (t->p_drawn) { GCRL_HIP(hipStreamSynchronize(st)); GCRL_HIP(hipFree(t->p_drawn)); t->p_drawn = nullptr; t->p_cap = 0; }
     GCRL_HIP(hipMalloc((void**)&t->p_drawn, (size_t)B * sizeof(float)));
@@ -302,6 +277,7 @@ int per_update(gcrl_her* h, const uint32_t* idx_dev, const float* td_dev, int B,
   if (int rc = need_tree(h, "per_update", true, true)) return rc;
   gcrl_per_tree* t = h->per;
   GCRL_CHECK_ARG(idx_dev && td_dev && B >= 1, "per_update: null buffer / batch size %d", B);
+  if (t->her_td) return her_td_update(h, idx_dev, td_dev, B, hist_dev, st);   // a HER ring's TD tree: the update that also raises p_max (her_td.hip)
   if (int rc = per_refresh(h, st)) return rc;   // (rows pushed between the draw and this update: their 1.0 first, as in the reference's order)
   UpdArgs a;
   a.t = view_of(t);

@@ -23,7 +23,7 @@ import torch
 from .. import _ffi
 from .._ffi import lib
 from .buffer import (HERBuffer, PERBuffer, ReplayBuffer, TdHistoryOverwritten, _check_energy, _check_goal_strategy, _check_normalize,
-                     _check_nstep, _check_prior)
+                     _check_nstep, _check_prior, _check_td)
 from .model import Actor, Critic, SACActorModel
 
 KIND = {"DDPG": 0, "TD3": 1, "SAC": 2, "TQC": 3}
@@ -214,7 +214,7 @@ class _EngineAgent:
                  top_quantiles_to_drop: int = 2, n_quantiles: int = 1, per_draw: str = "host", relabel: str = "push",
                  n_step: int = 1, prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
                  normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, prior_buffer=None,
-                 prior_rows: int | None = None, bc_weight: float | None = None, q_filter: bool = True, _member=None):
+                 prior_rows: int | None = None, bc_weight: float | None = None, q_filter: bool = True, td: dict | None = None, _member=None):
         # relabel="sample": the HER ring stores original rows only and relabels when a batch is gathered (buffer.HERBuffer).
         if relabel not in ("push", "sample"):
             raise ValueError(f"relabel must be 'push' or 'sample', got {relabel!r}")
@@ -258,6 +258,8 @@ class _EngineAgent:
         # Every refusal before any device work.
         if per_draw not in ("host", "device"):
             raise ValueError(f"per_draw must be 'host' or 'device', got {per_draw!r}")
+        if per_draw == "device" and prioritise == "td_error":     # (asked first: the per_draw checks below would name the buffer type instead)
+            raise _ffi.GcrlError(f"{type(self).__name__}: prioritise: 'td_error' and per_draw='device' are two trees for one ring; a ring takes one")
         if per_draw == "device":
             who = type(self).__name__
             if config.buffer_type != "PER":
@@ -274,6 +276,21 @@ class _EngineAgent:
         if prioritise is not None and _member is not None:
             raise _ffi.GcrlError(f"{type(self).__name__}: prioritise: populations do not draw from an energy tree")
         self.prioritise = prioritise
+        # prioritise="td_error" (relabel="sample"): TD-error prioritised replay on the HER ring, "HER + PER" (buffer.HERBuffer;
+        # csrc/her_td.hip).  Every update step draws its batch from the ring's tree, weighs the critic losses with the importance-sampling
+        # weights (beta follows beta_scheduler, as for PER agents) and feeds |td| back into the drawn rows' leaves, all on the device in
+        # one native call per update() / update_many(); td_error is lazy.  td=dict(alpha=config.alpha, eps=1e-6) at most.  The weights
+        # enter the loss on the layer-per-launch schedule, so pipeline becomes 0.  Every refusal here before any device work.
+        self.td = _check_td(type(self).__name__, prioritise, td, relabel, per_draw, config.buffer_type, default_alpha=config.alpha)
+        if self.td is not None:
+            who = type(self).__name__
+            if self.KIND_NAME == "TQC" and int(n_quantiles) > 1:
+                raise _ffi.GcrlError(f"{who}: prioritise: the distributional TQC variant (n_quantiles > 1) has no importance-weighted loss; "
+                                     "'td_error' needs scalar critics")
+            if prior_buffer is not None or bc_weight is not None:
+                raise _ffi.GcrlError(f"{who}: prioritise: 'td_error' weighs and re-prioritises every row of a batch; prior_buffer / bc_weight "
+                                     "rows have no leaf in the ring's tree")
+            pipeline = 0
         if not torch.cuda.is_available() or lib.gcrl_device_count() <= 0:
             raise _ffi.GcrlError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
         self.device = "cuda"
@@ -296,7 +313,7 @@ class _EngineAgent:
                                     rng=rng, seed=seed, device_index=device_index, relabel=relabel,
                                     n_step=self.n_step, gamma=config.gamma if self.n_step > 1 else None,
                                     prioritise=prioritise, energy=energy, goal_strategy=self.goal_strategy,
-                                    normalize=self.normalize, obs_normalize=self.obs_normalize, g_normalize=self.g_normalize)
+                                    normalize=self.normalize, obs_normalize=self.obs_normalize, g_normalize=self.g_normalize, td=self.td)
         else:
             raise ValueError(f"[ERROR] Invalid Buffer type. Received {config.buffer_type}.")
 
@@ -519,6 +536,8 @@ class _EngineAgent:
         per = isinstance(self.buffer, PERBuffer) and batch is None
         if per and self.buffer.draw_mode == "device":
             return self._update_per_device(step, 1, inputs)[0]
+        if self.prioritise == "td_error" and batch is None:     # the HER ring's TD-error tree: the same per-step loop in the engine
+            return self._update_per_device(step, 1, inputs)[0]
         if per:   # src/agent.py:1380-1387: the prioritised draw (host, numpy-exact), weights into the critic losses
             indices, weights = self.buffer.draw(self.batch_size, self.beta)
             if inputs is None:
@@ -560,19 +579,25 @@ class _EngineAgent:
         her = self.buffer.handle
         assert her is not None and len(self.buffer) >= self.batch_size, "[ERROR] Not enough in buffer to sample"
         betas = np.empty(n, np.float32)
+        beta0 = self.beta
         for i in range(n):
             betas[i] = self.beta
             self.beta_scheduler(step0 + i)
-        _ffi.check(lib.gcrl_per_set_betas(her, betas.ctypes.data, n))
         tickets = (C.c_int64 * n)()
         lens = (C.c_int32 * n)()
-        if n == 1:
-            t1 = C.c_int64(-1)
-            lens[0] = _ffi.check(lib.gcrl_agent_update(self._h, her, int(step0), C.byref(inputs) if inputs is not None else None,
-                                                       C.byref(t1), _ffi.stream_handle()))
-            tickets[0] = t1.value
-        else:
-            _ffi.check(lib.gcrl_agent_update_n(self._h, her, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
+        try:
+            _ffi.check(lib.gcrl_per_set_betas(her, betas.ctypes.data, n))
+            if n == 1:
+                t1 = C.c_int64(-1)
+                lens[0] = _ffi.check(lib.gcrl_agent_update(self._h, her, int(step0), C.byref(inputs) if inputs is not None else None,
+                                                           C.byref(t1), _ffi.stream_handle()))
+                tickets[0] = t1.value
+            else:
+                _ffi.check(lib.gcrl_agent_update_n(self._h, her, int(step0), int(n), tickets, lens, _ffi.stream_handle()))
+        except (_ffi.GcrlError, ValueError):
+            if self.prioritise == "td_error":
+                self.beta = beta0   # a refused call consumed nothing: the schedule neither
+            raise
         self._per_call += 1
         if self._sac:
             self.actor.num_batches_tracked += sum(1 + (1 if l == 9 else 0) for l in lens)
@@ -595,7 +620,7 @@ class _EngineAgent:
     def update_many(self, step0: int, n: int):
         """The trainer's `for _ in range(gradient_step): update(step)` loop (src/env.py:384-385) as
         one call: all n batches are drawn (same RNG stream order) and gathered by one launch."""
-        if isinstance(self.buffer, PERBuffer) and self.buffer.draw_mode == "device":
+        if (isinstance(self.buffer, PERBuffer) and self.buffer.draw_mode == "device") or self.prioritise == "td_error":
             self.set_train()
             return self._update_per_device(step0, n, None)
         if isinstance(self.buffer, PERBuffer):   # the priorities change after every step: one draw per step (src/agent.py:1380-1387)
@@ -887,6 +912,7 @@ class _EngineAgent:
         if saved_bc is not None and bool(saved_bc["q_filter"]) != bool(self.q_filter):
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: q_filter: the state was saved with q_filter={bool(saved_bc['q_filter'])!r}, "
                                  f"this agent has q_filter={self.q_filter!r}")
+        self.buffer._check_td_state(meta["ring"])     # prioritise="td_error" on either side: refused before anything is overwritten
         blob = np.fromfile(os.path.join(path, "agent.bin"), dtype=np.uint8)
         _ffi.check(lib.gcrl_agent_load_state(self._h, blob.ctypes.data, blob.size))
         self._bc_ticket = None

@@ -208,7 +208,9 @@ def _check_prior(who: str, prior_buffer, prior_rows, batch_size: int, buffer_typ
     return int(prior_rows)
 
 
-PRIORITISE_MODES = (None, "energy")
+PRIORITISE_MODES = (None, "energy", "td_error")
+# prioritise="td_error": the exponent and the offset of a leaf (|td| + eps)^alpha — the PER buffer's (csrc/per_tree.hip)
+TD_DEFAULTS = dict(alpha=0.6, eps=1e-6)
 # prioritise="energy": the constants of the episode energy (tests/her_energy_ref.py is the definition).  The defaults are this
 # project's choice — m = 1: potential = m g = 9.81, kinetic = m / (2 dt^2) with dt = 0.04, axis 2 = the height of a 3-component goal
 # position (-1, no potential term, for goals with fewer components) — not a claim about anybody's published settings.
@@ -219,10 +221,14 @@ def _check_energy(who: str, prioritise, energy, relabel: str, per_draw: str = "h
     """-> the energy settings as a dict (axis None until the goal width is known), or None for prioritise=None; every refusal names
     `prioritise` or the `energy` key at fault and comes before any device work"""
     if prioritise not in PRIORITISE_MODES:
-        raise _ffi.GcrlError(f"{who}: prioritise: must be None or 'energy', got {prioritise!r}")
+        raise _ffi.GcrlError(f"{who}: prioritise: must be None, 'energy' or 'td_error', got {prioritise!r}")
     if prioritise is None:
         if energy is not None:
             raise _ffi.GcrlError(f"{who}: prioritise: energy= was given without prioritise='energy'")
+        return None
+    if prioritise == "td_error":     # the TD-error tree has settings of its own (_check_td)
+        if energy is not None:
+            raise _ffi.GcrlError(f"{who}: prioritise: energy= belongs to prioritise='energy'; 'td_error' takes td=dict(alpha=, eps=)")
         return None
     if per_draw != "host":       # (asked first: per_draw='device' implies a PER buffer, which the next check would name instead)
         raise _ffi.GcrlError(f"{who}: prioritise: 'energy' and per_draw={per_draw!r} are two trees for one ring; a ring takes one")
@@ -252,6 +258,41 @@ def _check_energy(who: str, prioritise, energy, relabel: str, per_draw: str = "h
         raise _ffi.GcrlError(f"{who}: energy: axis: must be an integer (negative: no potential term) or None, got {ax!r}")
     if ax is not None:
         cfg["axis"] = max(int(ax), -1)     # every negative axis is the one setting "no potential term": held, saved and compared as -1
+    return cfg
+
+
+def _check_td(who: str, prioritise, td, relabel: str, per_draw: str = "host", buffer_type: str = "HER", default_alpha: float | None = None):
+    """-> the settings of prioritise="td_error" as a dict(alpha, eps) of float32-exact floats, or None for every other mode; every
+    refusal names `prioritise` and comes before any device work (the mode itself is judged by _check_energy)"""
+    if prioritise != "td_error":
+        if td is not None:
+            raise _ffi.GcrlError(f"{who}: prioritise: td= was given without prioritise='td_error'")
+        return None
+    if per_draw != "host":
+        raise _ffi.GcrlError(f"{who}: prioritise: 'td_error' and per_draw={per_draw!r} are two trees for one ring; a ring takes one")
+    if buffer_type != "HER":
+        raise _ffi.GcrlError(f"{who}: prioritise: 'td_error' needs buffer_type 'HER' with relabel='sample', got {buffer_type!r}")
+    if relabel != "sample":
+        raise _ffi.GcrlError(f"{who}: prioritise: 'td_error' keeps one leaf per stored transition and needs a relabel='sample' ring, "
+                             f"got relabel={relabel!r}")
+    cfg = dict(TD_DEFAULTS)
+    if default_alpha is not None:
+        cfg["alpha"] = default_alpha
+    if td is not None and not isinstance(td, dict):
+        raise _ffi.GcrlError(f"{who}: prioritise: td must be a dict with at most the keys {sorted(cfg)}, got {td!r}")
+    for k, v in dict(td or {}).items():
+        if k not in cfg:
+            raise _ffi.GcrlError(f"{who}: prioritise: td: unknown key {k!r} (one of {sorted(cfg)})")
+        cfg[k] = v
+    for k in ("alpha", "eps"):
+        v = cfg[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(v)):
+            raise _ffi.GcrlError(f"{who}: prioritise: td: {k}: must be a finite number, got {v!r}")
+        cfg[k] = float(np.float32(v))
+    if cfg["alpha"] < 0:
+        raise _ffi.GcrlError(f"{who}: prioritise: td: alpha: must be >= 0, got {cfg['alpha']!r}")
+    if cfg["eps"] <= 0:
+        raise _ffi.GcrlError(f"{who}: prioritise: td: eps: must be > 0, got {cfg['eps']!r}")
     return cfg
 
 
@@ -291,13 +332,36 @@ class _RingState:
             meta["bytes"] = n
         if hasattr(self, "priorities"):
             meta["priorities"] = [float(p) for p in self.priorities]
-        if meta["prioritise"] is not None:
+        if meta["prioritise"] == "td_error":
+            meta["td"] = dict(self.td)
+            if self._h is not None:    # the leaves (logical order) and p_max as bit patterns, the draw counter, the head the sums depend on
+                meta["prio_leaves"] = self.get_priorities().view(np.uint32).tolist()
+                meta["td_pmax"] = int(np.float32(self.p_max).view(np.uint32))
+                meta["td_draw_counter"] = self.draw_counter
+                meta["prio_head"] = int(lib.gcrl_her_head(self._h))
+        elif meta["prioritise"] is not None:
             meta["energy"] = dict(self.energy)
             if self._h is not None:    # the leaves (logical order), the draw counter, and the head the tree's sums depend on
                 meta["prio_leaves"] = self.get_priorities().view(np.uint32).tolist()
                 meta["prio_counter"] = self.prio_counter
                 meta["prio_head"] = int(lib.gcrl_her_head(self._h))
         return meta
+
+    def _check_td_state(self, meta: dict, mode: bool = True):
+        """prioritise="td_error" on either side: a state saved under another `prioritise` (`mode`), alpha or eps is refused naming the
+        field — asked by an agent's load_state before anything of the agent is overwritten, and (the settings: load_state has compared
+        the modes itself) by load_state"""
+        mine = getattr(self, "prioritise", None)
+        if "td_error" not in (mine, meta.get("prioritise")):
+            return
+        who = f"{type(self).__name__}.load_state"
+        if mode and meta.get("prioritise") != mine:
+            raise _ffi.GcrlError(f"{who}: prioritise: the state was saved with prioritise={meta.get('prioritise')!r}, this buffer has "
+                                 f"prioritise={mine!r}")
+        for k in ("alpha", "eps"):
+            saved = (meta.get("td") or {}).get(k)
+            if saved != self.td[k]:
+                raise _ffi.GcrlError(f"{who}: prioritise: td: {k}: the state was saved with {k}={saved!r}, this buffer has {k}={self.td[k]!r}")
 
     def load_state(self, path: str, meta: dict):
         if meta.get("relabel", "push") != getattr(self, "relabel", "push"):    # refused before any device work
@@ -319,10 +383,12 @@ class _RingState:
         if meta.get("prioritise") != getattr(self, "prioritise", None):
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with prioritise={meta.get('prioritise')!r}, "
                                  f"this buffer has prioritise={getattr(self, 'prioritise', None)!r}")
-        mine = dict(self.energy) if getattr(self, "prioritise", None) is not None else None
+        is_td = getattr(self, "prioritise", None) == "td_error"
+        self._check_td_state(meta, mode=False)
+        mine = dict(self.energy) if getattr(self, "prioritise", None) is not None and not is_td else None
         if mine is not None and mine["axis"] is None and meta.get("dims"):     # (the default axis follows the goal width: known once a ring exists)
             mine["axis"] = _energy_axis(type(self).__name__, mine, int(meta["dims"][2]))
-        if meta.get("prioritise") is not None and meta.get("energy") != mine:
+        if meta.get("prioritise") is not None and not is_td and meta.get("energy") != mine:
             raise _ffi.GcrlError(f"{type(self).__name__}.load_state: prioritise: the state was saved with energy={meta.get('energy')!r}, "
                                  f"this buffer has energy={mine!r}")
         if meta["bytes"]:
@@ -342,7 +408,11 @@ class _RingState:
             _ffi.check(lib.gcrl_her_set_head(self._h, int(meta["prio_head"])))     # the rows back at their slots, then the leaves
             leaves = np.asarray(meta["prio_leaves"], dtype=np.uint32).view(np.float32)
             _ffi.check(lib.gcrl_per_set_priorities(self._h, leaves.ctypes.data, leaves.size))
-            self.prio_counter = int(meta["prio_counter"])
+            if meta["prioritise"] == "td_error":
+                self.p_max = np.asarray([meta["td_pmax"]], dtype=np.uint32).view(np.float32)[0]
+                self.draw_counter = int(meta["td_draw_counter"])
+            else:
+                self.prio_counter = int(meta["prio_counter"])
 
 
 class HERBuffer(_RingState):
@@ -350,7 +420,7 @@ class HERBuffer(_RingState):
                  k_future: int = 4, *, rng: str = "python", seed: int | None = None,
                  device_index: int = 0, relabel: str = "push", n_step: int = 1, gamma: float | None = None,
                  prioritise: str | None = None, energy: dict | None = None, goal_strategy: str = "future",
-                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False):
+                 normalize: str = "push", obs_normalize: bool = True, g_normalize: bool = False, td: dict | None = None):
         # relabel="push" (default): the reference's form, a flush stores every step's k_future relabelled copies and max_mem_len
         # counts copies.  relabel="sample": a flush stores the T original rows once and a row is relabelled when a batch is drawn
         # (the original paper's and SB3's form); max_mem_len then counts REAL transitions — for the same number of episodes
@@ -369,6 +439,12 @@ class HERBuffer(_RingState):
         # tree beside the ring are written once, by the flush; sample() / gather_update() without indices= and the update engine draw
         # their rows from it.  A deliberate sampling bias with no importance correction.  None (default): nothing changes.
         self.energy = _check_energy("HERBuffer", prioritise, energy, relabel)
+        # prioritise="td_error" (relabel="sample" only): TD-error prioritised replay, "HER + PER" (csrc/her_td.hip; tests/her_td_ref.py
+        # is the definition).  The tree beside the ring has one leaf per stored transition; a drawn row's leaf becomes
+        # (|td| + eps)^alpha through update_priorities() or an agent's update calls, and a NEW row enters at p_max, the largest
+        # priority seen so far (the PER paper's rule), seeded by the flush on the device.  sample() without indices= draws from the
+        # tree and, given beta=, returns the importance-sampling weights.  td=dict(alpha=0.6, eps=1e-6) at most.
+        self.td = _check_td("HERBuffer", prioritise, td, relabel)
         self.prioritise = prioritise
         # goal_strategy (relabel="sample" only): which row of its episode a relabelled row takes its goal from — "future" (default:
         # a later row, nothing changes), "final" (the episode's last row) or "episode" (any other live row of the episode, earlier ones
@@ -485,7 +561,7 @@ class HERBuffer(_RingState):
             if self._dims != (S, A, G):
                 raise ValueError(f"transition dims {(S, A, G)} differ from the ring's {self._dims}")
             return
-        if self.prioritise is not None:               # refused before any device work
+        if self.prioritise == "energy":               # refused before any device work
             self.energy["axis"] = _energy_axis("HERBuffer", self.energy, G)
         kind, thr = _classify_reward(self.compute_reward, G, self.threshold)
         if self.relabel == "sample" and kind == 2:    # refused before any device work
@@ -510,7 +586,9 @@ class HERBuffer(_RingState):
             raise
         if self.n_step > 1:
             _ffi.check(lib.gcrl_her_set_nstep(self._h, self.n_step, self.gamma))
-        if self.prioritise is not None:
+        if self.prioritise == "td_error":
+            _ffi.check(lib.gcrl_her_td_attach(self._h, self.td["alpha"], self.td["eps"]))
+        elif self.prioritise is not None:
             e = self.energy
             ecfg = _ffi.EnergyConfig(potential=e["potential"], kinetic=e["kinetic"], axis=e["axis"], clip=e["clip"], alpha=e["alpha"], eps=e["eps"])
             _ffi.check(lib.gcrl_her_prio_attach(self._h, C.byref(ecfg)))
@@ -631,11 +709,29 @@ class HERBuffer(_RingState):
         self.rng.push_back()
         return int(rows)
 
-    def sample(self, batch_size: int, num_batches: int = 1, indices=None, return_indices: bool = False):
+    def sample(self, batch_size: int, num_batches: int = 1, indices=None, return_indices: bool = False, beta: float | None = None):
         assert len(self) >= batch_size, "[ERROR] Not enough in buffer to sample"
         S, A, _ = self._dims
         n = batch_size * num_batches
         dev = torch.device("cuda", self.device_index)
+        if beta is not None and (self.prioritise != "td_error" or indices is not None):
+            raise _ffi.GcrlError("HERBuffer.sample: prioritise: beta= asks for the importance-sampling weights of a draw from a "
+                                 "prioritise='td_error' tree (no indices= given)")
+        if self.prioritise == "td_error" and indices is None:
+            # num_batches draws of batch_size rows from the tree (with replacement), weights normalised per batch, then the ring's own
+            # relabelling gather of those rows; everything in stream order on the device
+            idx = torch.empty(n, dtype=torch.int32, device=dev)
+            w = torch.empty(n, dtype=torch.float32, device=dev) if beta is not None else None
+            for m in range(num_batches):
+                o = m * batch_size
+                _ffi.check(lib.gcrl_per_draw(self._h, int(batch_size), float(beta or 0.0), idx[o:].data_ptr(),
+                                             w[o:].data_ptr() if w is not None else None, _ffi.stream_handle()))
+            out = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((n, S), (n, A), (n, 1), (n, S), (n, 1)))
+            _ffi.check(lib.gcrl_her_sample_dev(self._h, n, idx.data_ptr(), out[0].data_ptr(), S, out[1].data_ptr(), A, out[2].data_ptr(),
+                                               out[3].data_ptr(), S, out[4].data_ptr(), _ffi.stream_handle()))
+            if return_indices:
+                out += (idx.cpu().numpy().view(np.uint32),)
+            return out + (w,) if w is not None else out
         states = torch.empty((n, S), dtype=torch.float32, device=dev)
         actions = torch.empty((n, A), dtype=torch.float32, device=dev)
         rewards = torch.empty((n, 1), dtype=torch.float32, device=dev)
@@ -756,6 +852,53 @@ class HERBuffer(_RingState):
         if out.size:
             _ffi.check(lib.gcrl_per_get_priorities(self._h, out.ctypes.data, out.size))
         return out
+
+    # ------------------------------------------------------------------ prioritise="td_error"
+    def _need_td(self, what: str):
+        if self.prioritise != "td_error":
+            raise _ffi.GcrlError(f"HERBuffer.{what}: prioritise: needs prioritise='td_error', this buffer has {self.prioritise!r}")
+        if self._h is None:
+            raise _ffi.GcrlError(f"HERBuffer.{what}: the ring is created by the first push")
+
+    def update_priorities(self, indices, td_abs):
+        """Leaves of the logical rows `indices` <- (|td_abs| + eps)^alpha, last occurrence wins, and p_max raised; device tensors, one
+        launch in stream order, no host synchronisation."""
+        self._need_td("update_priorities")
+        dev = torch.device("cuda", self.device_index)
+        idx = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+        td = torch.as_tensor(td_abs).to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+        assert idx.numel() == td.numel()
+        _ffi.check(lib.gcrl_per_update(self._h, idx.data_ptr(), td.data_ptr(), idx.numel(), _ffi.stream_handle()))
+
+    def set_priorities(self, values):
+        """Replace every stored row's leaf (logical order) and rebuild the tree, one launch per level (synchronises)."""
+        self._need_td("set_priorities")
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        _ffi.check(lib.gcrl_per_set_priorities(self._h, v.ctypes.data, v.size))
+
+    @property
+    def p_max(self) -> float:
+        """The device word new rows are seeded with: the largest finite priority an update has written, 1.0 before any (synchronises)."""
+        self._need_td("p_max")
+        out = np.empty(1, np.float32)
+        _ffi.check(lib.gcrl_her_td_get_pmax(self._h, out.ctypes.data))
+        return np.float32(out[0])
+
+    @p_max.setter
+    def p_max(self, v):
+        self._need_td("p_max")
+        _ffi.check(lib.gcrl_her_td_set_pmax(self._h, float(np.float32(v))))
+
+    @property
+    def draw_counter(self) -> int:
+        """Number of the tree's next draw of a batch (the key of its uniform stream beside the buffer's seed)."""
+        self._need_td("draw_counter")
+        return int(lib.gcrl_per_get_draw_counter(self._h))
+
+    @draw_counter.setter
+    def draw_counter(self, v: int):
+        self._need_td("draw_counter")
+        _ffi.check(lib.gcrl_per_set_draw_counter(self._h, int(v)))
 
     def tree_levels(self):
         """Every level of the tree as stored, leaves (by physical slot) first."""

@@ -101,6 +101,9 @@ class DataParallelUpdater:
         if getattr(agent, "per_draw", "host") == "device":   # refused before any collective or device work
             raise _ffi.GcrlError("gcrl_amd.dp: per_draw: an agent with per_draw='device' draws its batches from its own priority tree inside "
                                  "the update call; DataParallelUpdater does not drive it (use per_draw='host')")
+        if getattr(agent, "prioritise", None) == "td_error":
+            raise _ffi.GcrlError("gcrl_amd.dp: prioritise: an agent with prioritise='td_error' draws its batches from its ring's priority tree "
+                                 "inside the update call; DataParallelUpdater does not drive it")
         if getattr(agent, "bc_weight", None) is not None:   # (the engine refuses the same under its exchange)
             raise _ffi.GcrlError("gcrl_amd.dp: bc_weight: an agent with the behaviour-cloning term (bc_weight=) does not run under a gradient "
                                  "exchange; DataParallelUpdater does not drive it")

@@ -967,7 +967,7 @@ typedef struct gcrl_energy_config {
   float alpha;       /* >= 0 */
   float eps;         /* > 0 */
 } gcrl_energy_config;
-enum { GCRL_PRIO_NONE = 0, GCRL_PRIO_ENERGY = 1 };
+enum { GCRL_PRIO_NONE = 0, GCRL_PRIO_ENERGY = 1, GCRL_PRIO_TD = 2 };
 int gcrl_her_prio_attach(gcrl_her* h, const gcrl_energy_config* cfg);
 int gcrl_her_prio_mode(const gcrl_her* h);
 /* `rows` draws (with replacement) -> idx_dev[rows], logical indices; row t is the ring's (prio counter + t)-th draw and the
@@ -977,6 +977,29 @@ int gcrl_her_prio_draw(gcrl_her* h, int64_t rows, uint32_t* idx_dev, void* strea
 /* rows ever drawn from the ring's energy tree (0: no such tree); saved and restored by the caller for a bitwise resume */
 uint64_t gcrl_her_get_prio_counter(const gcrl_her* h);
 int gcrl_her_set_prio_counter(gcrl_her* h, uint64_t counter);
+
+/* ---- TD-error prioritised replay of a GCRL_RELABEL_SAMPLE ring (csrc/her_td.hip; tests/her_td_ref.py is the
+ * definition).  The ring gets a priority tree of the layout above, one leaf per stored transition, whose leaves follow the loss as
+ * those of gcrl_per_attach do: a drawn row's leaf becomes (|td| + eps)^alpha (last occurrence of an index wins; alpha == 1: the
+ * single fp32 add).  What differs is a NEW row's priority: one fp32 word p_max on the device, initially 1.0f, holds the largest
+ * finite leaf value an update has produced; every row a flush launch writes gets the leaf p_max as that word stands in stream
+ * order (one launch behind the flush, no host synchronisation), and rows present at attach time get its initial value.  p_max never
+ * decreases; a NaN or infinite leaf value is written to its leaf and never raises it.
+ * gcrl_her_td_attach: GCRL_RELABEL_SAMPLE rings only.  Refused, each naming `prioritise`: a GCRL_RELABEL_PUSH ring, a ring that has a
+ * tree of any kind (GCRL_ERR_STATE), alpha not finite or < 0, eps not finite or not > 0 (GCRL_ERR_ARG).  gcrl_per_attach on such a
+ * ring stays refused.  With the tree attached: gcrl_per_draw (draw + weights, N = the ring's length), gcrl_per_update (the update
+ * above), gcrl_per_set_betas, gcrl_per_get / set_priorities, gcrl_per_read_level, gcrl_per_get / set_draw_counter and
+ * gcrl_per_launches serve it; gcrl_her_prio_mode returns GCRL_PRIO_TD; gcrl_agent_update / gcrl_agent_update_n run the per-step loop
+ * of a ring with a TD tree (draw, weights, the ring's own relabelling gather of those rows, the layer-per-launch step with the
+ * weights, the update; scalar critics, pipeline_steps = 0, no gradient exchange, no prior ring, no behaviour-cloning term);
+ * gcrl_pop_update_n and gcrl_pop_clone refuse such a ring, and so do gcrl_her_sample and gcrl_her_gather_update called without
+ * indices (a uniform draw would pass for a prioritised one: draw with gcrl_per_draw, gather with gcrl_her_sample_dev) and
+ * gcrl_her_append.  The TD error of whatever the gather produced for a drawn row, relabelled
+ * or not, updates the stored row's one leaf.
+ * gcrl_her_td_get_pmax (synchronises) / gcrl_her_td_set_pmax (finite, > 0): state and tests, never the loop. */
+int gcrl_her_td_attach(gcrl_her* h, float alpha, float eps);
+int gcrl_her_td_get_pmax(gcrl_her* h, float* out_host);
+int gcrl_her_td_set_pmax(gcrl_her* h, float value);
 
 /* ---- Prior-data replay: a fixed share of every batch from a second ring (csrc/her_prior.hip; DESIGN.md §4n;
  * tests/her_prior_ref.py is the definition).  An agent with a prior ring bound assembles every batch of B rows it gathers from its
