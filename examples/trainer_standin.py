@@ -11,6 +11,9 @@ trainer itself is outside the hot path.  What it exercises en
 and what it reports: success rate per cycle (does it learn?), env steps/s, gradient steps/s.
 
     python examples/trainer_standin.py --agent DDPG --cycles 60
+
+--device-env reach|push runs the same cycle with the environment on the device (gcrl_amd.DeviceGoalEnv) and `agent.collect` in place
+of the Python loop: acting, the env's step and _process_step are three launches per vector step and nothing crosses to the host.
 """
 import argparse
 import os
@@ -98,9 +101,13 @@ def fill_prior_ring(agent, prior, episodes, normalize, seed):
 
 def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
           seed=0, verbose=True, per_env_push=False, fused=False, relabel="push", n_step=1, prioritise=None,
-          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0, bc_weight=None, q_filter=True):
+          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0, bc_weight=None, q_filter=True, device_env=None):
     import gcrl_amd
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
+    if device_env is not None:
+        fused = True          # collect needs the normalisers on the device
+        if prior_episodes or prior_rows:
+            raise SystemExit("--device-env: the scripted prior episodes come from the host point-mass environment; not combined here")
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
         RunningNormalizer = DeviceRunningNormalizer
     if normalize == "sample" and not fused:
@@ -109,6 +116,10 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
 
     np.random.seed(seed)
     env = PointReachVecEnv(num_envs, seed=seed)
+    host_env = env
+    if device_env is not None:   # the env's state, its step blocks and its counters live on the device; the host env only lends its compute_reward
+        env = gcrl_amd.DeviceGoalEnv(device_env, num_envs, seed=seed, max_steps=host_env.T, threshold=host_env.thr)
+        env.thr = env.threshold
     cfg = make_config(agent_name, hidden_dim=hidden, layer_count=layers, batch_size=batch, max_len=200_000, k_future=4,
                       gamma=0.95, tau=0.05, grad_clip=10.0, ac_update_freq=2 if agent_name == "TD3" else 1,
                       policy_noise=0.2 if agent_name == "TD3" else 0.0)
@@ -133,11 +144,12 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     # what GoalEnvHER.__init__ injects (src/env.py:93-105)
     agent.buffer.obs_normalizer = RunningNormalizer(env.obs_dim)
     agent.buffer.dg_normalizer = RunningNormalizer(env.goal_dim)
-    agent.buffer.compute_reward = env.compute_reward
+    agent.buffer.compute_reward = host_env.compute_reward
     if prior is not None:
         fill_prior_ring(agent, prior, prior_episodes, normalize, seed)
 
-    state, _ = env.reset()
+    if device_env is None:
+        state, _ = env.reset()
     grad_counter, env_steps = 1, 0
     success_per_cycle, final_success = [], []
     t_env = t_upd = 0.0
@@ -145,6 +157,15 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     for cycle in range(1, cycles + 1):
         episode_count = 0
         tc = time.perf_counter()
+        if device_env is not None:   # the envs run in lockstep: every `max_steps` vector steps all of them finish an episode
+            rounds = -(-max_episode // num_envs)
+            before = env.stats()
+            agent.collect(env, rounds * env.max_steps)
+            after = env.stats()       # (synchronises: the cycle's collection is over)
+            done_eps = after["episodes"] - before["episodes"]
+            final_success.extend([True] * (after["successes"] - before["successes"]) + [False] * (done_eps - (after["successes"] - before["successes"])))
+            env_steps += rounds * env.max_steps * num_envs
+            episode_count = max_episode
         while episode_count < max_episode:
             if fused:
                 actions = np.asarray(agent.observe_act(state["observation"], state["desired_goal"]), dtype=np.float32)
@@ -194,7 +215,7 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
             grad_counter += gradient_step
             float(infos[-1][0])   # reads one metric: waits for the cycle's updates
         t_upd += time.perf_counter() - tu
-        recent = final_success[-max_episode:]
+        recent = final_success[-(max_episode if device_env is None else done_eps):]
         success_per_cycle.append(float(np.mean(recent)))
         if verbose and cycle % 10 == 0:
             print(f"cycle {cycle:4d}  success(last {len(recent)} episodes) {success_per_cycle[-1]:.2f}  buffer {len(agent.buffer)}")
@@ -211,6 +232,8 @@ if __name__ == "__main__":
     ap.add_argument("--cycles", type=int, default=60)
     ap.add_argument("--nenv", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device-env", default=None, choices=["reach", "push"],
+                    help="run the environment on the device (gcrl_amd.DeviceGoalEnv) and collect with agent.collect: no host in the acting loop")
     ap.add_argument("--per-env-push", action="store_true", help="push one env at a time, exactly as the reference's trainer does")
     ap.add_argument("--fused", action="store_true", help="device normalisers + one native call for acting and one for _process_step")
     ap.add_argument("--relabel", default="push", choices=["push", "sample"],
@@ -239,7 +262,7 @@ if __name__ == "__main__":
     out = train(args.agent, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, per_env_push=args.per_env_push, fused=args.fused,
                 relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy,
                 normalize=args.normalize, prior_episodes=args.prior_episodes, prior_rows=args.prior_rows,
-                bc_weight=args.bc_weight, q_filter=not args.no_q_filter)
+                bc_weight=args.bc_weight, q_filter=not args.no_q_filter, device_env=args.device_env)
     tail = out["success_per_cycle"][-10:]
     print(f"{args.agent}: success over the last 10 cycles {np.mean(tail):.2f}; {out['env_steps']} env steps "
           f"({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} gradient steps "

@@ -200,6 +200,25 @@ PROTOTYPES = {
     "gcrl_normalizer_set_rows_float64": (C.c_int, [_vp, C.c_int]),
     "gcrl_agent_observe_act": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "gcrl_agent_acting_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_env_create": (_vp, [C.c_int, C.c_int, _u64, C.c_int, _f32, C.c_int]),
+    "gcrl_env_destroy": (None, [_vp]),
+    "gcrl_env_dims": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                C.POINTER(C.c_int), C.POINTER(_f32), C.POINTER(_u64)]),
+    "gcrl_env_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "gcrl_env_reset": (C.c_int, [_vp, _vp, _vp]),
+    "gcrl_env_step": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "gcrl_env_stats": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64), _vp]),
+    "gcrl_env_state_bytes": (_i64, [_vp]),
+    "gcrl_env_save_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_env_load_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_proc_pack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "gcrl_agent_observe_act_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "gcrl_her_process_step_dev": (_i64, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "gcrl_her_flush_calls": (_i64, [_vp]),
+    "gcrl_agent_collect_set": (C.c_int, [_vp, _u64, _f64, _f64, _u64]),
+    "gcrl_agent_collect_get": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_u64)]),
+    "gcrl_agent_collect": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp]),
+    "gcrl_agent_collect_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gcrl_her_process_step": (_i64, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "gcrl_her_process_step_g": (_i64, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "gcrl_sort_truncate_mean": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp]),

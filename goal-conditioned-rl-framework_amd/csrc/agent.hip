@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "act_bn.h"
+#include "dev_env.h"
 #include "dw_adam.h"
 #include "gemm_mfma.h"
 #include "her_ring.h"
@@ -141,6 +142,15 @@ struct gcrl_agent {
   // what gcrl_agent_observe_act has issued since creation (gcrl_agent_acting_counts): calls, kernel launches, copies, stream synchronisations
   long long oa_calls = 0, oa_launches = 0, oa_copies = 0, oa_syncs = 0;
   size_t oa_bytes = 0;
+  // device-row acting (gcrl_agent_observe_act_dev) and the collect loop (gcrl_agent_collect): float64 actions [B][A] | float64 noise [B][A] |
+  // float32 actions or eps [B][A]; the exploration stream's seed, scale and vector-step counter; which env's noise of which step the
+  // noise block holds (written by the previous step's env launch); what the loop has issued (gcrl_agent_collect_counts)
+  char* col_dev = nullptr;
+  unsigned long long col_seed = 0, col_ctr = 0;
+  double col_noise_std = 0.0, col_epsilon = 0.0;
+  const void* col_noise_env = nullptr; unsigned long long col_noise_ctr = 0; bool col_noise_valid = false;
+  long long col_calls = 0, col_steps = 0, col_launches = 0, col_copies = 0, col_syncs = 0;
+  std::vector<int32_t> col_t;
   // row-block DDPG path (rowchain.h): [in][out] weight copies of actor | target actor | critic 0 |
   // target critic 0, per-layer gradient buffers, TD targets
   bool rowchain = false, wt_dirty = true;
@@ -1868,6 +1878,7 @@ void gcrl_agent_destroy(gcrl_agent* a) {
   if (a->oa_pinned) (void)hipHostFree(a->oa_pinned);
   if (a->act_fl_host) (void)hipHostFree(a->act_fl_host);
   if (a->oa_dev) (void)hipFree(a->oa_dev);
+  if (a->col_dev) (void)hipFree(a->col_dev);
   for (int i = 0; i < gcrl_agent::kProfPairs; ++i) {
     if (a->prof_a[i]) (void)hipEventDestroy(a->prof_a[i]);
     if (a->prof_b[i]) (void)hipEventDestroy(a->prof_b[i]);
@@ -2841,6 +2852,195 @@ int gcrl_agent_acting_counts(const gcrl_agent* a, int64_t* calls, int64_t* launc
   if (launches) *launches = a->oa_launches;
   if (copies) *copies = a->oa_copies;
   if (syncs) *syncs = a->oa_syncs;
+  return GCRL_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- device-row acting and the collect loop (dev_env.h)
+namespace {
+
+constexpr unsigned long long kEpsStream = 0x455053494c4f4e21ull;   // "EPSILON!": DDPG's epsilon uniform and its random actions
+
+struct ColBufs { double* out64; double* noise64; float* f32; };
+int col_bufs(gcrl_agent* a, ColBufs* b) {
+  const size_t cnt = (size_t)a->B * a->A;
+  if (!a->col_dev) GCRL_HIP(hipMalloc((void**)&a->col_dev, cnt * (2 * sizeof(double) + sizeof(float))));
+  b->out64 = reinterpret_cast<double*>(a->col_dev); b->noise64 = b->out64 + cnt; b->f32 = reinterpret_cast<float*>(b->noise64 + cnt);
+  return GCRL_OK;
+}
+
+// The launch gcrl_agent_observe_act issues for staged rows, on the caller's device rows [n][S]: float64 actions to out64.  noise64: the
+// exploration noise of the tanh actors (mode 1) or null; eps32: the eps of the BatchNorm actors or null (the deterministic action).
+int act_dev_launch(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, const float* rows, int D, int n, const double* noise64,
+                   const float* eps32, int mode, double* out64, hipStream_t st, long long* launches) {
+  if (a->sac) {
+    ActBnArgs ba;
+    std::memset(&ba, 0, sizeof(ba));
+    ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
+    ba.S = a->S; ba.H = a->H; ba.L = a->L; ba.A = a->A; ba.n = n; ba.D = D;
+    ba.ldl = (std::max(a->S, a->H) + 3) / 4 * 4;
+    gcrl::normalizer_view(nz_obs, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
+    gcrl::normalizer_view(nz_dg, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
+    ba.rows = rows; ba.eps = eps32; ba.out64 = out64;
+    TRY(launch_act_bn(st, ba));
+    *launches += 1;
+    return GCRL_OK;
+  }
+  if (a->wt_dirty) {   // (the [in][out] weight copies after a parameter write, as gcrl_agent_observe_act rebuilds them)
+    *launches += 1 + (a->has_target_actor ? 1 : 0) + 2 * a->C;
+    TRY(rc_rebuild_wt(a, st));
+  }
+  RowActArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  ra.actor = make_rownet(a, a->actor, a->P_actor(), 0);
+  ra.obs = rows; ra.ld_obs = a->S; ra.out = a->dact; ra.ld_out = a->Apad;
+  ra.n = n; ra.S = a->S; ra.A = a->A; ra.ldl = a->row_ldl;
+  ra.D = D;
+  gcrl::normalizer_view(nz_obs, &ra.nz_mean, &ra.nz_var, nullptr, &ra.nz_clip, &ra.nz_mode);
+  gcrl::normalizer_view(nz_dg, &ra.nzg_mean, &ra.nzg_var, nullptr, &ra.nzg_clip, &ra.nzg_mode);
+  ra.post = mode == 1 ? 1 : (mode == 0 ? 2 : 3);
+  ra.noise = mode == 1 ? noise64 : nullptr; ra.out64 = out64;
+  TRY(launch_rowchain_act(st, ra));
+  *launches += 1;
+  return GCRL_OK;
+}
+
+int act_dev_check(const gcrl_agent* a, const gcrl_normalizer* nz_obs, const gcrl_normalizer* nz_dg, int obs_dim, int n, int mode, const char* who) {
+  GCRL_CHECK_ARG(n >= 1 && n <= a->B, "%s: n: %d rows (1..batch_size = %d)", who, n, a->B);
+  GCRL_CHECK_ARG(obs_dim >= 1 && obs_dim <= a->S, "%s: obs_dim %d for state_dim %d", who, obs_dim, a->S);
+  GCRL_CHECK_ARG(mode >= 0 && mode <= 2, "%s: mode must be 0, 1 or 2", who);
+  GCRL_CHECK_ARG(!nz_obs || gcrl_normalizer_size(nz_obs) == obs_dim, "%s: nz_obs: observation normaliser of size %d for obs_dim %d", who, gcrl_normalizer_size(nz_obs), obs_dim);
+  GCRL_CHECK_ARG(!nz_dg || gcrl_normalizer_size(nz_dg) == a->S - obs_dim, "%s: nz_dg: goal normaliser of size %d for goal_dim %d", who, gcrl_normalizer_size(nz_dg), a->S - obs_dim);
+  GCRL_CHECK_ARG(a->sac || a->rowchain, "%s: this agent's shape has no one-launch acting kernel, which the device-row entries are built on", who);
+  return GCRL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcrl_agent_observe_act_dev(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, const float* rows_dev, int obs_dim, int n,
+                               const double* noise_dev, int mode, float* out_f32_dev, void* stream) {
+  GCRL_CHECK_ARG(a && rows_dev && out_f32_dev, "gcrl_agent_observe_act_dev: null argument");
+  TRY(act_dev_check(a, nz_obs, nz_dg, obs_dim, n, mode, "gcrl_agent_observe_act_dev"));
+  hipStream_t st = a->pick(stream);
+  ColBufs cb;
+  TRY(col_bufs(a, &cb));
+  a->col_noise_valid = false;   // (the float32 block below is shared with the collect loop's eps)
+  const float* eps32 = nullptr;
+  if (a->sac && noise_dev) {    // the BatchNorm actors take their eps as float32, as the host entry stages it
+    TRY(gcrl::round_to_f32(noise_dev, cb.f32, n * a->A, st));
+    a->col_launches += 1;
+    eps32 = cb.f32;
+  }
+  TRY(act_dev_launch(a, nz_obs, nz_dg, rows_dev, obs_dim, n, noise_dev, eps32, mode, cb.out64, st, &a->col_launches));
+  TRY(gcrl::round_to_f32(cb.out64, out_f32_dev, n * a->A, st));
+  a->col_launches += 1;
+  return GCRL_OK;
+}
+
+int gcrl_agent_collect_set(gcrl_agent* a, uint64_t seed, double noise_std, double epsilon, uint64_t counter) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_collect_set: null handle");
+  GCRL_CHECK_ARG(noise_std >= 0.0 && epsilon >= 0.0 && epsilon <= 1.0, "gcrl_agent_collect_set: noise_std >= 0 and 0 <= epsilon <= 1 required");
+  a->col_seed = seed; a->col_noise_std = noise_std; a->col_epsilon = epsilon; a->col_ctr = counter;
+  a->col_noise_valid = false;
+  return GCRL_OK;
+}
+
+int gcrl_agent_collect_get(const gcrl_agent* a, uint64_t* seed, double* noise_std, double* epsilon, uint64_t* counter) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_collect_get: null handle");
+  if (seed) *seed = a->col_seed;
+  if (noise_std) *noise_std = a->col_noise_std;
+  if (epsilon) *epsilon = a->col_epsilon;
+  if (counter) *counter = a->col_ctr;
+  return GCRL_OK;
+}
+
+int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                       int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
+  const char* who = "gcrl_agent_collect";
+  GCRL_CHECK_ARG(a && env && ring && rows_out, "%s: null argument", who);
+  // every refusal comes before a counter, a ring slot or a draw of the exploration stream is consumed
+  GCRL_CHECK_ARG(steps >= 1, "%s: steps: %d (>= 1 required)", who, steps);
+  GCRL_CHECK_ARG(env->device == a->cfg.device, "%s: env: it lives on device %d, the agent on device %d", who, env->device, a->cfg.device);
+  GCRL_CHECK_ARG(env->N <= ring->cfg.nenvs, "%s: env: %d envs for a ring of %d episode slots", who, env->N, ring->cfg.nenvs);
+  GCRL_CHECK_ARG(env->N <= a->B, "%s: env: %d envs exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, env->N, a->B);
+  GCRL_CHECK_ARG(env->N <= kEnvMaxN, "%s: env: %d envs (at most %d)", who, env->N, kEnvMaxN);
+  GCRL_CHECK_ARG(env->D + kEnvG == a->S && a->S == ring->S, "%s: env: obs_dim %d + goal_dim %d != state_dim %d (ring: %d)", who, env->D, kEnvG, a->S, ring->S);
+  GCRL_CHECK_ARG(kEnvA == a->A && kEnvA == ring->A && kEnvG == ring->G, "%s: env: action_dim %d / goal_dim %d, the agent has action_dim %d, the ring %d / %d", who,
+                 kEnvA, kEnvG, a->A, ring->A, ring->G);
+  GCRL_CHECK_ARG(env->T == ring->cfg.flush_len, "%s: max_steps: the env's horizon %d differs from the ring's flush length %d", who, env->T, ring->cfg.flush_len);
+  GCRL_CHECK_ARG(ring->cfg.reward_kind == GCRL_REWARD_SPARSE, "%s: compute_reward: the ring's reward kind is %s; the env's reward is the built-in sparse kind%s", who,
+                 ring->cfg.reward_kind == GCRL_REWARD_HOST ? "a host callback" : "dense",
+                 ring->cfg.reward_kind == GCRL_REWARD_HOST ? ", and a host-callback flush needs the host mirror of the achieved goals, which device rows do not fill" : "");
+  GCRL_CHECK_ARG(std::memcmp(&env->thr, &ring->cfg.reward_threshold, sizeof(float)) == 0, "%s: threshold: the env's %g differs from the ring's %g", who, env->thr,
+                 ring->cfg.reward_threshold);
+  GCRL_CHECK_ARG(!update_stats || nz_obs, "%s: nz_obs: update_stats without an observation normaliser", who);
+  GCRL_CHECK_ARG(!update_goal_stats || nz_dg, "%s: nz_dg: update_goal_stats without a goal normaliser", who);
+  TRY(act_dev_check(a, nz_obs, nz_dg, env->D, env->N, eval_mode, who));
+  const int N = env->N;
+  for (int i = 0; i < N; ++i)
+    if (env->t_host[i] != ring->staged[i])
+      return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d is at step %d of its episode, the ring has %d transitions staged for it", who, i, env->t_host[i], ring->staged[i]);
+  hipStream_t st = a->pick(stream);
+  void* sarg = stream ? stream : (void*)a->stream;   // one stream for the three handles: the loop is stream-ordered
+  ColBufs cb;
+  TRY(col_bufs(a, &cb));
+  a->col_calls += 1;
+  const bool ddpg = a->cfg.kind == GCRL_AGENT_DDPG;
+  const double scale = a->sac ? 1.0 : a->col_noise_std;
+  void* noise_buf = a->sac ? (void*)cb.f32 : (void*)cb.noise64;
+  const unsigned long long per_step = (unsigned long long)N * kEnvA;
+  const int flush_mul = 1 + (gcrl::her_prio_on(ring) ? 1 : 0) + (gcrl::her_td_on(ring) ? 1 : 0);
+  int64_t total = 0;
+  for (int s = 0; s < steps; ++s) {
+    const unsigned long long c = a->col_ctr;
+    const void* act = cb.out64; int act_f64 = 1;
+    const bool eps_step = explore && ddpg && a->col_epsilon > 0.0 &&
+                          (double)gcrl::hash_below(a->col_seed, kEpsStream, c, 1u << 24) * (1.0 / 16777216.0) < a->col_epsilon;
+    if (eps_step) {   // every env takes clip(randn): no network involved
+      TRY(gcrl::clipped_normal_fill(cb.f32, (int)per_step, a->col_seed ^ kEpsStream, c * per_step, st));
+      a->col_launches += 1;
+      act = cb.f32; act_f64 = 0;
+    } else {
+      if (explore && !(a->col_noise_valid && a->col_noise_env == env && a->col_noise_ctr == c)) {   // (a first call, or after the stream was set)
+        TRY(gcrl::normal_fill(noise_buf, a->sac ? 0 : 1, (int)per_step, a->col_seed, c * per_step, scale, st));
+        a->col_launches += 1;
+      }
+      TRY(act_dev_launch(a, nz_obs, nz_dg, env->rows, env->D, N, explore ? cb.noise64 : nullptr, explore ? cb.f32 : nullptr, explore ? 1 : eval_mode, cb.out64,
+                         st, &a->col_launches));
+    }
+    // the env's step; its threads also leave the NEXT vector step's noise, so that a step stays three launches
+    // (an epsilon step's float32 actions and the BatchNorm actors' float32 eps share a block, but only DDPG has epsilon steps and its
+    // noise is the float64 block: the rider never writes what this launch reads)
+    a->col_t.assign(env->t_host.begin(), env->t_host.end());   // the payload's t words: the envs' step counts BEFORE the step
+    if (explore) {
+      TRY(gcrl::env_step_launch_noise(env, act, act_f64, noise_buf, a->sac ? 0 : 1, a->col_seed, (c + 1) * per_step, scale, st));
+      a->col_noise_valid = true; a->col_noise_env = env; a->col_noise_ctr = c + 1;
+    } else {
+      TRY(gcrl::env_step_launch(env, act, act_f64, st));
+    }
+    a->col_launches += 1;
+    a->col_ctr = c + 1;
+    a->col_steps += 1;
+    const int64_t f0 = ring->flush_calls;
+    const int64_t r = gcrl_her_process_step_dev(ring, nz_obs, update_stats, nz_dg, update_goal_stats, env->raw, env->pay, env->D, a->col_t.data(), nullptr, 0, N, sarg);
+    if (r < 0) return (int)r;
+    a->col_launches += 1 + (ring->flush_calls - f0) * flush_mul;
+    total += r;
+  }
+  *rows_out = total;
+  return GCRL_OK;
+}
+
+int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_collect_counts: null handle");
+  if (calls) *calls = a->col_calls;
+  if (steps) *steps = a->col_steps;
+  if (launches) *launches = a->col_launches;
+  if (copies) *copies = a->col_copies;
+  if (syncs) *syncs = a->col_syncs;
   return GCRL_OK;
 }
 

@@ -1,0 +1,66 @@
+// dev_env.h — device-resident goal environments (dev_env.hip): N independent envs of one built-in kind whose state, counters and the
+// blocks of a vector step live in device memory.  One env_step_kernel launch writes a step's `raw` and `pay` blocks in the layout
+// her_ring.hip's her_process_step_body reads and the next step's acting rows [obs | goal] in the layout the acting kernels read,
+// so an agent's collect loop (agent.hip) is act -> step -> process-step with nothing crossing to the host.
+// The rule is restated in numpy in tests/dev_env_ref.py, which is its definition.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "common.h"
+
+constexpr int kEnvG = 3, kEnvA = 3;      // goal and action width of both kinds
+constexpr int kEnvPayW = 32;             // floats per env of the payload block (her_ring.hip kPayW)
+constexpr int kEnvMaxN = 1024;
+constexpr int kEnvStateW = 12;           // floats per env: p(3) q(3) vel(3) goal(3)
+
+struct gcrl_env {
+  int kind = 0, N = 0, T = 0, D = 0, device = 0;
+  float thr = 0.f;
+  uint64_t seed = 0;
+  hipStream_t stream = nullptr;
+  // device state: everything a resume needs
+  float* state = nullptr;                // [N][kEnvStateW]
+  int* t = nullptr;                      // [N] steps taken in the running episode
+  unsigned long long* cnt = nullptr;     // [N][3]: episode index (the RNG key), episodes finished, successes
+  double* rsum = nullptr;                // [N] reward sum
+  // blocks of a step
+  float* rows = nullptr;                 // [N][D + G] acting rows of the NEXT step
+  float* raw = nullptr;                  // [obs N*D | next_obs N*D | dg N*G | next_dg N*G | ag N*G | next_ag N*G]
+  float* pay = nullptr;                  // [N][kEnvPayW]: t | r | done = 0 | action(A) | next_ag(G)
+  int64_t steps = 0, launches = 0;       // vector steps taken / kernel launches issued since creation
+  std::vector<int32_t> t_host;           // host mirror of t: the step kernel's rule (t + 1, 0 at the horizon) needs no read-back
+
+  hipStream_t pick(void* s) const {
+    if (!s) return stream;
+    if (s == GCRL_STREAM_LEGACY) return (hipStream_t) nullptr;
+    return (hipStream_t)s;
+  }
+};
+
+namespace gcrl {
+
+// env_step_kernel on `st`: actions [N][A] as float32 (f64 == 0) or as the float64 the acting kernels write (rounded to float32 first)
+int env_step_launch(gcrl_env* e, const void* actions_dev, int f64, hipStream_t st);
+// the same with the collect loop's rider: the env's thread also writes the NEXT vector step's exploration noise, A elements per env —
+// noise[i * A + c] = hash_normal(noise_seed, noise_ctr0 + i * A + c) (as double) * noise_scale, stored as float64 or rounded to float32
+int env_step_launch_noise(gcrl_env* e, const void* actions_dev, int f64, void* noise, int noise_f64, unsigned long long noise_seed,
+                          unsigned long long noise_ctr0, double noise_scale, hipStream_t st);
+// proc_pack_kernel: raw | pay from separate contiguous [n][.] float32 device tensors (the payload's t word: t[i] from device words, or t0 for every
+// env when t == null).  ag may be null (then that block and next_ag's are left as they are: no goal normaliser reads them).
+struct ProcPack {
+  const float *obs, *nobs, *dg, *ndg, *ag, *nag, *act, *rew;
+  const int* t;      // [n] device words, or null: t0 for every env
+  float* raw; float* pay;
+  int n, D, G, A, t0;
+};
+int proc_pack_launch(const ProcPack& p, hipStream_t st);
+// out[i] = clamp(hash_normal(seed, ctr0 + i), -1, 1) for i < n  (the epsilon step of a DDPG collect)
+int clipped_normal_fill(float* out, int n, unsigned long long seed, unsigned long long ctr0, hipStream_t st);
+// out[i] = double(hash_normal(seed, ctr0 + i)) * scale for i < n, stored as float64 (f64 != 0) or rounded to float32
+int normal_fill(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale, hipStream_t st);
+// out32[i] = float(in64[i]) for i < n
+int round_to_f32(const double* in64, float* out32, int n, hipStream_t st);
+
+}  // namespace gcrl

@@ -1,0 +1,469 @@
+// dev_env.hip — two built-in goal environments that live on the device (dev_env.h), and the small launches the device-row acting
+// entries and the collect loop of agent.hip need around them.
+//
+//   reach (D = 7)    a point mass in a box: obs = [pos, vel, t / T], achieved goal = pos
+//   push  (D = 13)   a pusher and a puck on the plane z = 0: obs = [p, q, q - p, vel_p, t / T], achieved goal = q; the puck moves by the
+//                    pusher's planar displacement while the pusher's new position is inside the contact radius
+//
+// G = 3, A = 3, fixed horizon T, sparse reward -(dist > thr) formed as the replay ring's relabelling kernels form it, no termination.
+// All arithmetic is float32, one rounding per operation (the unit is built with -ffp-contract=off): + - * /, comparisons,
+// fminf / fmaxf and the correctly rounded square root of the reward's distance.  The rule — constants, operation order, what a NaN
+// action counts as, the random-number keys — is restated in numpy in tests/dev_env_ref.py, which is its definition.
+//
+// Random numbers: u(env, episode, component) = hash_below(seed, kEnvStream + env, 8 * episode + component, 2^24) * 2^-24.  No state
+// besides the counters, so an env's episode j is the same whatever N is and whenever it is reached.
+//
+// Kernel rules: every address comes from the handle (or, for the pack and fill launches, from the caller's checked arguments);
+// an env index >= N does nothing; no atomics; no waits between workgroups; no per-thread scratch (every loop is over a constant
+// 3 and unrolled); plain vector stores only.
+#include "dev_env.h"
+
+#include <vector>
+
+#include "her_ring.h"   // hash_below
+#include "ops.h"        // hash_normal
+
+namespace {
+
+constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
+constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
+constexpr uint32_t kEnvMagic = 0x564e4547u;   // "GENV"
+
+struct EnvArgs {
+  float* state; int* t; unsigned long long* cnt; double* rsum;
+  float* rows; float* raw; float* pay;
+  const void* act; int act_f64;
+  int restart;
+  int kind, N, T, D;
+  float thr;
+  unsigned long long seed;
+  // rider of the collect loop: the exploration noise of the NEXT vector step, A elements per env, written by the env's thread
+  void* noise; int noise_f64; unsigned long long noise_seed, noise_ctr0; double noise_scale;
+};
+
+__device__ inline float u01(unsigned long long seed, int env, unsigned long long ep, int comp) {
+  return (float)gcrl::hash_below(seed, kEnvStream + (unsigned long long)env, 8ull * ep + (unsigned long long)comp, 1u << 24) * (1.0f / 16777216.0f);
+}
+__device__ inline float spawn(float u) { return (u * 2.0f - 1.0f) * kSpawn; }
+__device__ inline float clamp_box(float x) { return fminf(fmaxf(x, -kBox), kBox); }
+
+struct EnvState { float p[3], q[3], vel[3], goal[3]; };
+
+__device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, EnvState& s) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) s.vel[c] = 0.f;
+  if (a.kind == GCRL_ENV_REACH) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s.p[c] = spawn(u01(a.seed, i, ep, c)); s.q[c] = 0.f; s.goal[c] = spawn(u01(a.seed, i, ep, 3 + c)); }
+  } else {
+    s.q[0] = spawn(u01(a.seed, i, ep, 0)); s.q[1] = spawn(u01(a.seed, i, ep, 1)); s.q[2] = 0.f;
+    s.p[0] = spawn(u01(a.seed, i, ep, 2)); s.p[1] = spawn(u01(a.seed, i, ep, 3)); s.p[2] = kLift;
+    const float two = 2.0f * a.thr;
+    const float m = two + u01(a.seed, i, ep, 4) * (kSpawn - two);
+    s.goal[0] = u01(a.seed, i, ep, 5) < 0.5f ? s.q[0] - m : s.q[0] + m;
+    s.goal[1] = spawn(u01(a.seed, i, ep, 6));
+    s.goal[2] = 0.f;
+  }
+}
+
+__device__ inline void load_state(const EnvArgs& a, int i, EnvState& s) {
+  const float* w = a.state + (size_t)i * kEnvStateW;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { s.p[c] = w[c]; s.q[c] = w[3 + c]; s.vel[c] = w[6 + c]; s.goal[c] = w[9 + c]; }
+}
+__device__ inline void store_state(const EnvArgs& a, int i, const EnvState& s) {
+  float* w = a.state + (size_t)i * kEnvStateW;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { w[c] = s.p[c]; w[3 + c] = s.q[c]; w[6 + c] = s.vel[c]; w[9 + c] = s.goal[c]; }
+}
+// obs of state s at step count t -> o[0 .. D)
+__device__ inline void write_obs(const EnvArgs& a, const EnvState& s, int t, float* o) {
+  const float tt = (float)t / (float)a.T;
+  if (a.kind == GCRL_ENV_REACH) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.vel[c]; }
+    o[6] = tt;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; }
+    o[12] = tt;
+  }
+}
+__device__ inline void write_row(const EnvArgs& a, int i, const EnvState& s, int t) {
+  float* row = a.rows + (size_t)i * (a.D + kEnvG);
+  write_obs(a, s, t, row);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) row[a.D + c] = s.goal[c];
+}
+
+// the selection travels inside the kernel arguments (N <= 1024): one byte per env, ignored on a restart
+struct ResetArgs { EnvArgs a; unsigned char mask[kEnvMaxN]; };
+static_assert(sizeof(ResetArgs) <= 4096, "kernel arguments are limited to 4 KB");
+__global__ __launch_bounds__(64) void env_reset_kernel(ResetArgs q) {
+  const EnvArgs& a = q.a;
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= a.N) return;
+  unsigned long long* cn = a.cnt + (size_t)i * 3;
+  unsigned long long ep;
+  if (a.restart) {
+    ep = 0; cn[1] = 0; cn[2] = 0; a.rsum[i] = 0.0;
+  } else {
+    if (!q.mask[i]) return;
+    ep = cn[0] + 1;
+  }
+  cn[0] = ep;
+  EnvState s;
+  seed_env(a, i, ep, s);
+  store_state(a, i, s);
+  a.t[i] = 0;
+  write_row(a, i, s, 0);
+}
+
+__global__ __launch_bounds__(64) void env_step_kernel(EnvArgs a) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= a.N) return;
+  const int N = a.N, D = a.D;
+  EnvState s;
+  load_state(a, i, s);
+  int t = a.t[i];
+  float* obs = a.raw + (size_t)i * D;
+  float* nobs = a.raw + (size_t)N * D + (size_t)i * D;
+  float* dg = a.raw + (size_t)2 * N * D + (size_t)i * kEnvG;
+  float* ndg = dg + (size_t)N * kEnvG;
+  float* ag = ndg + (size_t)N * kEnvG;
+  float* nag = ag + (size_t)N * kEnvG;
+  float* pw = a.pay + (size_t)i * kEnvPayW;
+  write_obs(a, s, t, obs);
+  float act[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    dg[c] = s.goal[c]; ndg[c] = s.goal[c];
+    ag[c] = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
+    act[c] = a.act_f64 ? (float)static_cast<const double*>(a.act)[(size_t)i * kEnvA + c] : static_cast<const float*>(a.act)[(size_t)i * kEnvA + c];
+  }
+  float pn[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float x = act[c];
+    x = (x == x) ? x : 0.0f;                       // a NaN component counts as 0
+    x = fminf(fmaxf(x, -1.0f), 1.0f);
+    s.vel[c] = kStep * x;
+    pn[c] = clamp_box(s.p[c] + s.vel[c]);
+  }
+  if (a.kind == GCRL_ENV_PUSH) {
+    float d2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { const float df = pn[c] - s.q[c]; d2 = d2 + df * df; }
+    if (d2 < kContact * kContact) {
+      s.q[0] = clamp_box(s.q[0] + (pn[0] - s.p[0]));
+      s.q[1] = clamp_box(s.q[1] + (pn[1] - s.p[1]));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) s.p[c] = pn[c];
+  pw[0] = __int_as_float(t);
+  t += 1;
+  write_obs(a, s, t, nobs);
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float g = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
+    nag[c] = g;
+    pw[3 + c] = act[c];
+    pw[3 + kEnvA + c] = g;
+    const float df = g - s.goal[c];
+    acc = acc + df * df;
+  }
+  const float dist = sqrtf(acc);
+  const float r = dist > a.thr ? -1.0f : -0.0f;
+  pw[1] = r; pw[2] = 0.f;
+  a.rsum[i] = a.rsum[i] + (double)r;
+  if (t == a.T) {
+    unsigned long long* cn = a.cnt + (size_t)i * 3;
+    cn[1] = cn[1] + 1;
+    if (dist < a.thr) cn[2] = cn[2] + 1;
+    const unsigned long long ep = cn[0] + 1;
+    cn[0] = ep;
+    seed_env(a, i, ep, s);
+    t = 0;
+  }
+  store_state(a, i, s);
+  a.t[i] = t;
+  write_row(a, i, s, t);
+  if (a.noise) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float z = gcrl::hash_normal(a.noise_seed, a.noise_ctr0 + (unsigned long long)i * kEnvA + c);
+      if (a.noise_f64) static_cast<double*>(a.noise)[(size_t)i * kEnvA + c] = (double)z * a.noise_scale;
+      else static_cast<float*>(a.noise)[(size_t)i * kEnvA + c] = (float)((double)z * a.noise_scale);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void proc_pack_kernel(gcrl::ProcPack p) {
+  const int n = p.n, D = p.D, G = p.G, A = p.A;
+  const int per = 2 * D + 4 * G + 3 + A + G;      // elements written per env
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)n * per) return;
+  const int i = (int)(e / per); int c = (int)(e - (long long)i * per);
+  float* raw = p.raw; float* pw = p.pay + (size_t)i * kEnvPayW;
+  if (c < D) { raw[(size_t)i * D + c] = p.obs[(size_t)i * D + c]; return; }
+  c -= D;
+  if (c < D) { raw[(size_t)n * D + (size_t)i * D + c] = p.nobs[(size_t)i * D + c]; return; }
+  c -= D;
+  float* g0 = raw + (size_t)2 * n * D;
+  if (c < 4 * G) {
+    const int b = c / G, k = c - b * G;
+    const float* src = b == 0 ? p.dg : b == 1 ? p.ndg : b == 2 ? p.ag : p.nag;
+    if (b >= 2 && !p.ag) return;
+    g0[(size_t)b * n * G + (size_t)i * G + k] = src[(size_t)i * G + k];
+    return;
+  }
+  c -= 4 * G;
+  if (c == 0) pw[0] = __int_as_float(p.t ? p.t[i] : p.t0);
+  else if (c == 1) pw[1] = p.rew[i];
+  else if (c == 2) pw[2] = 0.f;
+  else if (c < 3 + A) pw[c] = p.act[(size_t)i * A + (c - 3)];
+  else pw[c] = p.nag[(size_t)i * G + (c - 3 - A)];
+}
+
+__global__ __launch_bounds__(256) void clipped_normal_fill_kernel(float* out, int n, unsigned long long seed, unsigned long long ctr0) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = fminf(fmaxf(gcrl::hash_normal(seed, ctr0 + (unsigned long long)i), -1.0f), 1.0f);
+}
+__global__ __launch_bounds__(256) void normal_fill_kernel(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double v = (double)gcrl::hash_normal(seed, ctr0 + (unsigned long long)i) * scale;
+  if (f64) static_cast<double*>(out)[i] = v;
+  else static_cast<float*>(out)[i] = (float)v;
+}
+__global__ __launch_bounds__(256) void round_to_f32_kernel(const double* in64, float* out32, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out32[i] = (float)in64[i];
+}
+
+EnvArgs base_args(gcrl_env* e) {
+  EnvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.state = e->state; a.t = e->t; a.cnt = e->cnt; a.rsum = e->rsum;
+  a.rows = e->rows; a.raw = e->raw; a.pay = e->pay;
+  a.kind = e->kind; a.N = e->N; a.T = e->T; a.D = e->D; a.thr = e->thr; a.seed = e->seed;
+  return a;
+}
+
+struct EnvHeader { uint32_t magic; int32_t kind, N, T; float thr; uint32_t pad; uint64_t seed; int64_t steps; };
+
+size_t state_bytes(const gcrl_env* e) {
+  return sizeof(EnvHeader) + (size_t)e->N * (kEnvStateW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
+         (size_t)e->N * (e->D + kEnvG) * sizeof(float);
+}
+
+}  // namespace
+
+namespace gcrl {
+
+int env_step_launch(gcrl_env* e, const void* actions_dev, int f64, hipStream_t st) { return env_step_launch_noise(e, actions_dev, f64, nullptr, 0, 0, 0, 0.0, st); }
+
+int env_step_launch_noise(gcrl_env* e, const void* actions_dev, int f64, void* noise, int noise_f64, unsigned long long noise_seed,
+                          unsigned long long noise_ctr0, double noise_scale, hipStream_t st) {
+  EnvArgs a = base_args(e);
+  a.act = actions_dev; a.act_f64 = f64 ? 1 : 0;
+  a.noise = noise; a.noise_f64 = noise_f64; a.noise_seed = noise_seed; a.noise_ctr0 = noise_ctr0; a.noise_scale = noise_scale;
+  hipLaunchKernelGGL(env_step_kernel, dim3((e->N + 63) / 64), dim3(64), 0, st, a);
+  GCRL_HIP(hipGetLastError());
+  e->steps += 1; e->launches += 1;
+  for (int32_t& t : e->t_host) t = t + 1 == e->T ? 0 : t + 1;   // the kernel's rule for t
+  return GCRL_OK;
+}
+
+int proc_pack_launch(const ProcPack& p, hipStream_t st) {
+  const long long total = (long long)p.n * (2 * p.D + 4 * p.G + 3 + p.A + p.G);
+  hipLaunchKernelGGL(proc_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+int clipped_normal_fill(float* out, int n, unsigned long long seed, unsigned long long ctr0, hipStream_t st) {
+  hipLaunchKernelGGL(clipped_normal_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, n, seed, ctr0);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+int normal_fill(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale, hipStream_t st) {
+  hipLaunchKernelGGL(normal_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, f64, n, seed, ctr0, scale);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+int round_to_f32(const double* in64, float* out32, int n, hipStream_t st) {
+  hipLaunchKernelGGL(round_to_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, in64, out32, n);
+  GCRL_HIP(hipGetLastError());
+  return GCRL_OK;
+}
+
+}  // namespace gcrl
+
+extern "C" {
+
+gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device) {
+  auto bad = [](const char* m) -> gcrl_env* { gcrl::fail(GCRL_ERR_ARG, "gcrl_env_create: %s", m); return nullptr; };
+  if (kind != GCRL_ENV_REACH && kind != GCRL_ENV_PUSH) return bad("kind: GCRL_ENV_REACH or GCRL_ENV_PUSH required");
+  if (num_envs < 1 || num_envs > kEnvMaxN) return bad("num_envs: 1..1024 required");
+  if (max_steps < 1 || max_steps > 64) return bad("max_steps: 1..64 required (the replay ring's flush length limit)");
+  if (!(threshold > 0.f) || !(threshold < kBox)) return bad("threshold: must lie in (0, 0.3)");
+  if (kind == GCRL_ENV_PUSH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push places the goal at least 2 * threshold from the puck and needs 2 * threshold <= 0.15");
+  int ndev = gcrl_device_count();
+  if (ndev <= 0 || device < 0 || device >= ndev) {
+    gcrl::fail(GCRL_ERR_HIP, "gcrl_env_create: no usable HIP device (count=%d, requested %d); there is no CPU fallback", ndev, device);
+    return nullptr;
+  }
+  gcrl_env* e = new gcrl_env;
+  e->kind = kind; e->N = num_envs; e->T = max_steps; e->thr = threshold; e->seed = seed; e->device = device;
+  e->D = kind == GCRL_ENV_REACH ? 7 : 13;
+  const size_t N = (size_t)num_envs, raw_floats = N * (2 * e->D + 4 * kEnvG);
+  auto ok = [&](hipError_t r, const char* what) {
+    if (r == hipSuccess) return true;
+    gcrl::fail(GCRL_ERR_HIP, "gcrl_env_create: %s failed: %s", what, hipGetErrorString(r));
+    return false;
+  };
+  bool good = ok(hipSetDevice(device), "hipSetDevice") && ok(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
+              ok(hipMalloc((void**)&e->state, N * kEnvStateW * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->t, N * sizeof(int)), "hipMalloc") &&
+              ok(hipMalloc((void**)&e->cnt, N * 3 * sizeof(unsigned long long)), "hipMalloc") && ok(hipMalloc((void**)&e->rsum, N * sizeof(double)), "hipMalloc") &&
+              ok(hipMalloc((void**)&e->rows, N * (e->D + kEnvG) * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->raw, raw_floats * sizeof(float)), "hipMalloc") &&
+              ok(hipMalloc((void**)&e->pay, N * kEnvPayW * sizeof(float)), "hipMalloc");
+  if (good) good = ok(hipMemset(e->state, 0, N * kEnvStateW * sizeof(float)), "hipMemset") && ok(hipMemset(e->t, 0, N * sizeof(int)), "hipMemset") &&
+                   ok(hipMemset(e->cnt, 0, N * 3 * sizeof(unsigned long long)), "hipMemset") && ok(hipMemset(e->rsum, 0, N * sizeof(double)), "hipMemset") &&
+                   ok(hipMemset(e->raw, 0, raw_floats * sizeof(float)), "hipMemset") && ok(hipMemset(e->pay, 0, N * kEnvPayW * sizeof(float)), "hipMemset");
+  if (good) {
+    ResetArgs q;
+    std::memset(&q, 0, sizeof(q));
+    q.a = base_args(e);
+    q.a.restart = 1;
+    e->t_host.assign(N, 0);
+    hipLaunchKernelGGL(env_reset_kernel, dim3((e->N + 63) / 64), dim3(64), 0, (hipStream_t) nullptr, q);
+    good = ok(hipGetLastError(), "env_reset_kernel") && ok(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the first step runs on the CALLER's stream
+    e->launches += 1;
+  }
+  if (!good) { gcrl_env_destroy(e); return nullptr; }
+  return e;
+}
+
+void gcrl_env_destroy(gcrl_env* e) {
+  if (!e) return;
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  for (void* p : {(void*)e->state, (void*)e->t, (void*)e->cnt, (void*)e->rsum, (void*)e->rows, (void*)e->raw, (void*)e->pay})
+    if (p) (void)hipFree(p);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+}
+
+int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps, float* threshold, uint64_t* seed) {
+  GCRL_CHECK_ARG(e, "gcrl_env_dims: null handle");
+  if (kind) *kind = e->kind;
+  if (num_envs) *num_envs = e->N;
+  if (obs_dim) *obs_dim = e->D;
+  if (goal_dim) *goal_dim = kEnvG;
+  if (ac_dim) *ac_dim = kEnvA;
+  if (max_steps) *max_steps = e->T;
+  if (threshold) *threshold = e->thr;
+  if (seed) *seed = e->seed;
+  return GCRL_OK;
+}
+
+int gcrl_env_buffers(gcrl_env* e, float** rows, float** raw, float** pay) {
+  GCRL_CHECK_ARG(e, "gcrl_env_buffers: null handle");
+  if (rows) *rows = e->rows;
+  if (raw) *raw = e->raw;
+  if (pay) *pay = e->pay;
+  return GCRL_OK;
+}
+
+int gcrl_env_reset(gcrl_env* e, const uint8_t* mask_host, void* stream) {
+  GCRL_CHECK_ARG(e, "gcrl_env_reset: null handle");
+  ResetArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.a = base_args(e);
+  q.a.restart = mask_host ? 0 : 1;
+  if (mask_host) std::memcpy(q.mask, mask_host, (size_t)e->N);
+  hipLaunchKernelGGL(env_reset_kernel, dim3((e->N + 63) / 64), dim3(64), 0, e->pick(stream), q);
+  GCRL_HIP(hipGetLastError());
+  e->launches += 1;
+  for (int i = 0; i < e->N; ++i) if (!mask_host || mask_host[i]) e->t_host[i] = 0;
+  if (!mask_host) e->steps = 0;
+  return GCRL_OK;
+}
+
+int gcrl_env_step(gcrl_env* e, const void* actions_dev, int actions_f64, void* stream) {
+  GCRL_CHECK_ARG(e && actions_dev, "gcrl_env_step: null argument");
+  return gcrl::env_step_launch(e, actions_dev, actions_f64, e->pick(stream));
+}
+
+int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream) {
+  GCRL_CHECK_ARG(e, "gcrl_env_stats: null handle");
+  std::vector<unsigned long long> cn((size_t)e->N * 3);
+  std::vector<double> rs((size_t)e->N);
+  hipStream_t st = e->pick(stream);
+  GCRL_HIP(hipMemcpyAsync(cn.data(), e->cnt, cn.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipMemcpyAsync(rs.data(), e->rsum, rs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipStreamSynchronize(st));
+  int64_t ep = 0, su = 0; double r = 0.0;
+  for (int i = 0; i < e->N; ++i) { ep += (int64_t)cn[(size_t)i * 3 + 1]; su += (int64_t)cn[(size_t)i * 3 + 2]; r += rs[i]; }
+  if (episodes) *episodes = ep;
+  if (successes) *successes = su;
+  if (reward_sum) *reward_sum = r;
+  return GCRL_OK;
+}
+
+int64_t gcrl_env_state_bytes(const gcrl_env* e) { return e ? (int64_t)state_bytes(e) : 0; }
+
+// blob: header | state [N][12] f32 | t [N] i32 | counters [N][3] u64 | reward sums [N] f64 | acting rows [N][D + G] f32
+int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream) {
+  GCRL_CHECK_ARG(e && dst_host && n == (int64_t)state_bytes(e), "gcrl_env_save_state: the blob is %lld bytes", e ? (long long)state_bytes(e) : 0ll);
+  hipStream_t st = e->pick(stream);
+  EnvHeader hd{kEnvMagic, e->kind, e->N, e->T, e->thr, 0u, e->seed, e->steps};
+  char* o = static_cast<char*>(dst_host);
+  std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
+  const size_t N = (size_t)e->N;
+  const void* src[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
+  const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
+  for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(o, src[k], len[k], hipMemcpyDeviceToHost, st)); o += len[k]; }
+  GCRL_HIP(hipStreamSynchronize(st));
+  return GCRL_OK;
+}
+
+int gcrl_env_load_state(gcrl_env* e, const void* src_host, int64_t n, void* stream) {
+  GCRL_CHECK_ARG(e && src_host && n >= (int64_t)sizeof(EnvHeader), "gcrl_env_load_state: null argument or a blob shorter than its header");
+  EnvHeader hd;
+  std::memcpy(&hd, src_host, sizeof(hd));
+  GCRL_CHECK_ARG(hd.magic == kEnvMagic, "gcrl_env_load_state: not an environment state blob");
+  GCRL_CHECK_ARG(hd.kind == e->kind, "gcrl_env_load_state: kind: the blob holds kind %d, the handle %d", hd.kind, e->kind);
+  GCRL_CHECK_ARG(hd.N == e->N, "gcrl_env_load_state: num_envs: the blob holds %d envs, the handle %d", hd.N, e->N);
+  GCRL_CHECK_ARG(hd.T == e->T, "gcrl_env_load_state: max_steps: the blob holds %d, the handle %d", hd.T, e->T);
+  GCRL_CHECK_ARG(std::memcmp(&hd.thr, &e->thr, sizeof(float)) == 0, "gcrl_env_load_state: threshold: the blob holds %g, the handle %g", hd.thr, e->thr);
+  GCRL_CHECK_ARG(n == (int64_t)state_bytes(e), "gcrl_env_load_state: the blob is %lld bytes, expected %lld", (long long)n, (long long)state_bytes(e));
+  hipStream_t st = e->pick(stream);
+  const char* o = static_cast<const char*>(src_host) + sizeof(hd);
+  const size_t N = (size_t)e->N;
+  void* dst[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
+  const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
+  for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(dst[k], o, len[k], hipMemcpyHostToDevice, st)); o += len[k]; }
+  GCRL_HIP(hipStreamSynchronize(st));   // (the source is the caller's pageable memory)
+  e->seed = hd.seed; e->steps = hd.steps;
+  std::memcpy(e->t_host.data(), static_cast<const char*>(src_host) + sizeof(hd) + len[0], len[1]);
+  return GCRL_OK;
+}
+
+// raw | pay of one vector step from separate contiguous float32 device tensors (for callers that hold the pieces separately)
+int gcrl_proc_pack(const float* obs, const float* next_obs, const float* dg, const float* next_dg, const float* ag, const float* next_ag,
+                   const float* actions, const float* rewards, const int32_t* t_dev, int t0, int n, int obs_dim, int goal_dim, int action_dim, float* raw_out,
+                   float* pay_out, void* stream) {
+  GCRL_CHECK_ARG(obs && next_obs && dg && next_dg && next_ag && actions && rewards && raw_out && pay_out, "gcrl_proc_pack: null argument");
+  GCRL_CHECK_ARG(n >= 1 && obs_dim >= 1 && goal_dim >= 1 && action_dim >= 1 && 3 + action_dim + goal_dim <= kEnvPayW && t0 >= 0,
+                 "gcrl_proc_pack: n, dimensions and t0 must be positive and action_dim + goal_dim fit the payload");
+  gcrl::ProcPack p{obs, next_obs, dg, next_dg, ag, next_ag, actions, rewards, t_dev, raw_out, pay_out, n, obs_dim, goal_dim, action_dim, t0};
+  hipStream_t st = stream == GCRL_STREAM_LEGACY ? (hipStream_t) nullptr : (hipStream_t)stream;
+  return gcrl::proc_pack_launch(p, st);
+}
+
+}  // extern "C"

@@ -170,6 +170,7 @@ struct gcrl_her {
   float* ps_dev = nullptr;
   float* ps_pinned[kSlots] = {};
   size_t ps_floats = 0;
+  int64_t flush_calls = 0;               // flush groups a vector-env step's bookkeeping has issued (gcrl_her_flush_calls)
   // per-env payload of a vector-env step (gcrl_her_push_batch)
   float* pay_dev = nullptr;
   float* pay_pinned[kSlots] = {};

@@ -949,6 +949,7 @@ static int64_t finish_vector_step(gcrl_her* h, int env0, int n, const uint8_t* d
     if (cnt == 0) return GCRL_OK;
     int64_t rows = 0;
     if (int rc = launch_flush(h, cnt, envs, Ts, nullptr, st, &rows)) return rc;
+    h->flush_calls += 1;
     for (int q = 0; q < cnt; ++q) h->staged[envs[q]] = 0;
     total += rows;
     cnt = 0;
@@ -1135,6 +1136,57 @@ int64_t gcrl_her_process_step_g(gcrl_her* h, gcrl_normalizer* nz_obs, int update
   if (pa.gupdate) gcrl::normalizer_updated(nz_dg);
   return finish_vector_step(h, env0, n, dones_host, st);
 }
+
+// The same step from CALLER-OWNED device blocks (a simulator whose state lives on the device, dev_env.hip): the launch of
+// gcrl_her_process_step_g's staged form on raw_dev / pay_dev, then the same host bookkeeping.  Nothing is uploaded and nothing is
+// waited for.  The payload's t word of env i must be the ring's staged count of env0 + i: the caller declares it in t_host[i], and a
+// mismatch is refused before anything is launched — device memory is never read back to check.
+int64_t gcrl_her_process_step_dev(gcrl_her* h, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg, int update_goal_stats,
+                                  const float* raw_dev, const float* pay_dev, int obs_dim, const int32_t* t_host, const uint8_t* dones_host,
+                                  int env0, int n, void* stream) {
+  GCRL_CHECK_ARG(h && raw_dev && pay_dev && t_host, "gcrl_her_process_step_dev: null argument");
+  GCRL_CHECK_ARG(!nz_dg || gcrl_normalizer_size(nz_dg) == h->G, "gcrl_her_process_step_dev: nz_dg: the goal normaliser has size %d for goal_dim %d", nz_dg ? gcrl_normalizer_size(nz_dg) : 0, h->G);
+  GCRL_CHECK_ARG(obs_dim >= 1 && obs_dim <= 128 && obs_dim + h->G == h->S, "gcrl_her_process_step_dev: obs_dim %d + goal_dim %d != state_dim %d (obs_dim <= 128)", obs_dim, h->G, h->S);
+  GCRL_CHECK_ARG(n >= 1 && env0 >= 0 && env0 + n <= h->cfg.nenvs, "gcrl_her_process_step_dev: n: envs [%d, %d) outside [0, %d)", env0, env0 + n, h->cfg.nenvs);
+  GCRL_CHECK_ARG(3 + h->A + h->G <= kPayW, "gcrl_her_process_step_dev: action_dim + goal_dim too large for the payload");
+  GCRL_CHECK_ARG(!nz_obs || gcrl_normalizer_size(nz_obs) == obs_dim, "gcrl_her_process_step_dev: nz_obs: the observation normaliser has size %d for obs_dim %d", nz_obs ? gcrl_normalizer_size(nz_obs) : 0, obs_dim);
+  GCRL_CHECK_ARG(h->cfg.reward_kind != GCRL_REWARD_HOST, "gcrl_her_process_step_dev: compute_reward: a ring with a host-callback reward flushes from the host "
+                 "mirror of the achieved goals, which device rows do not fill");
+  for (int i = 0; i < n; ++i)
+    if (t_host[i] != h->staged[env0 + i])
+      return gcrl::fail(GCRL_ERR_STATE, "gcrl_her_process_step_dev: t: env %d declares step %d of its episode, the ring has %d transitions staged for it",
+                        env0 + i, t_host[i], h->staged[env0 + i]);
+  hipStream_t st = h->pick(stream);
+  ProcArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.stage = h->stage; pa.raw = raw_dev; pa.pay = pay_dev;
+  const double *mean = nullptr, *var = nullptr;
+  gcrl::normalizer_view(nz_obs, &mean, &var, &pa.count, &pa.clip, &pa.mode);
+  pa.mean = const_cast<double*>(mean); pa.var = const_cast<double*>(var);
+  pa.update = (nz_obs && update_stats) ? 1 : 0;
+  if (nz_dg) {
+    const double *gm = nullptr, *gv = nullptr;
+    gcrl::normalizer_view(nz_dg, &gm, &gv, &pa.gcount, &pa.gclip, &pa.gmode);
+    pa.gmean = const_cast<double*>(gm); pa.gvar = const_cast<double*>(gv);
+    pa.gupdate = update_goal_stats ? 1 : 0;
+  }
+  pa.n = n; pa.env0 = env0; pa.flush_len = h->cfg.flush_len; pa.D = obs_dim; pa.S = h->S; pa.A = h->A; pa.G = h->G;
+  pa.SA4 = h->SA4; pa.S4 = h->S4; pa.RG = h->RG;
+  if (gcrl::her_norm_on(h)) {   // normalize = "sample": the raw-store form (her_norm.hip)
+    gcrl::ProcRawArgs ra;
+    std::memcpy(&ra, &pa, sizeof(ra));
+    if (int rc = gcrl::her_process_step_raw(ra, nullptr, 0, 0, st)) return rc;
+  } else hipLaunchKernelGGL(her_process_step_kernel, dim3(1), dim3(256), 0, st, pa);
+  GCRL_HIP(hipGetLastError());
+  if (pa.update) gcrl::normalizer_updated(nz_obs);
+  if (pa.gupdate) gcrl::normalizer_updated(nz_dg);
+  if (dones_host) return finish_vector_step(h, env0, n, dones_host, st);
+  static thread_local std::vector<uint8_t> none;   // (no env terminated: episodes end when flush_len rows are staged)
+  none.assign((size_t)n, 0);
+  return finish_vector_step(h, env0, n, none.data(), st);
+}
+
+int64_t gcrl_her_flush_calls(const gcrl_her* h) { return h ? h->flush_calls : 0; }
 
 int64_t gcrl_her_push_episode(gcrl_her* h, int env, int T, const float* s, const float* a,
                               const float* ns, const float* r, const float* d, const float* ag,

@@ -815,6 +815,174 @@ class _EngineAgent:
         buf.rng.push_back()
         return int(rows)
 
+    # ------------------------------------------------------------------ device rows: acting, process_step and the collect loop
+    COLLECT_EPSILON = 0.0      # DDPG: 0.2, the reference's epsilon-random branch (src/agent.py:1348)
+
+    def _dev_normalizers(self, who: str, obs_normalize: bool, g_normalize: bool):
+        nz = self._device_normalizers(obs_normalize, g_normalize)
+        if nz is None:
+            raise _ffi.GcrlError(f"{type(self).__name__}.{who}: normalize: the device-row entries need DeviceRunningNormalizer objects assigned "
+                                 "to buffer.obs_normalizer / buffer.dg_normalizer for the flags that are on")
+        return nz
+
+    @staticmethod
+    def _dev_f32(who: str, name: str, t, shape=None):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{who}: {name}: a contiguous CUDA float32 tensor{'' if shape is None else ' ' + str(list(shape))} required")
+        return t
+
+    def _collect_stream(self):
+        """(seed, noise_std, epsilon, counter) of the device exploration stream; the seed defaults to the constructor's."""
+        if not self.__dict__.get("_collect_bound"):
+            _ffi.check(lib.gcrl_agent_collect_set(self._h, int(self._collect_seed()) & (2**64 - 1), float(self.noise_std) if not self._sac else 1.0,
+                                                  float(self.COLLECT_EPSILON), 0))
+            self._collect_bound = True
+        sd, ns, ep, ctr = C.c_uint64(), C.c_double(), C.c_double(), C.c_uint64()
+        _ffi.check(lib.gcrl_agent_collect_get(self._h, C.byref(sd), C.byref(ns), C.byref(ep), C.byref(ctr)))
+        return int(sd.value), float(ns.value), float(ep.value), int(ctr.value)
+
+    def _collect_seed(self) -> int:
+        return int(getattr(self.buffer.rng, "seed_value", 0) or 0)
+
+    def set_collect_stream(self, seed: int | None = None, counter: int | None = None):
+        """Re-key the device exploration stream (`collect`, and `observe_act_dev` without `noise`) or move its vector-step counter."""
+        sd, ns, ep, ctr = self._collect_stream()
+        _ffi.check(lib.gcrl_agent_collect_set(self._h, (sd if seed is None else int(seed)) & (2**64 - 1), ns, ep, ctr if counter is None else int(counter)))
+
+    def observe_act_dev(self, observation, desired_goal=None, eval_action: bool = False, noise=None, obs_normalize: bool = True, g_normalize: bool = False,
+                        obs_dim: int | None = None):
+        """`observe_act` for a simulator whose state lives on the GPU: raw rows in, float32 actions out, both CUDA tensors, no copy and no
+        synchronisation.  `observation` [n, obs_dim] and `desired_goal` [n, goal_dim] CUDA float32 tensors — or, with `desired_goal=None`,
+        `observation` is the packed [n, obs_dim + goal_dim] rows (`DeviceGoalEnv.acting_rows()["rows"]`), read in place.  `noise`: CUDA
+        float64 [n, A] (the Gaussian noise of DDPG / TD3, the eps of SAC / TQC); None with `eval_action=False` draws vector step c of the
+        device exploration stream (and advances c).  The result is the float32 rounding of `observe_act`'s float64 action for the same
+        rows and noise, bit for bit.  DDPG's epsilon-random branch is `collect`'s; this entry always runs the actor."""
+        who = f"{type(self).__name__}.observe_act_dev"
+        self._check_normalize_call("observe_act_dev", obs_normalize, g_normalize)
+        nz = self._dev_normalizers("observe_act_dev", obs_normalize, g_normalize)
+        S = self.obs_dim
+        if desired_goal is None:
+            rows = self._dev_f32(who, "observation", observation)
+            if rows.ndim != 2 or rows.shape[1] != S:
+                raise ValueError(f"{who}: observation: packed rows [n, {S}] required")
+            D = obs_dim if obs_dim is not None else getattr(getattr(self.buffer, "obs_normalizer", None), "size", None)
+            if D is None:
+                raise ValueError(f"{who}: obs_dim: packed rows need obs_dim when no observation normaliser tells it")
+            D = int(D)
+        else:
+            o, g = self._dev_f32(who, "observation", observation), self._dev_f32(who, "desired_goal", desired_goal)
+            if o.ndim != 2 or g.ndim != 2 or o.shape[0] != g.shape[0] or o.shape[1] + g.shape[1] != S:
+                raise ValueError(f"{who}: observation / desired_goal: [n, obs_dim] and [n, goal_dim] with obs_dim + goal_dim = {S} required")
+            D = int(o.shape[1])
+            rows = torch.cat([o, g], dim=1)
+        n = int(rows.shape[0])
+        self.set_eval()
+        self._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+        if eval_action:
+            noise, mode = None, (2 if self._sac else self._ACT_MODE_EVAL)
+        else:
+            mode = 2 if self._sac else self._ACT_MODE_EXPLORE
+            if noise is None:
+                sd, ns, _, ctr = self._collect_stream()
+                z = torch.empty((n, self.ac_dim), dtype=torch.float32, device=rows.device)
+                _ffi.check(lib.gcrl_hash_normal_fill(C.c_uint64(sd), C.c_uint64((ctr * n * self.ac_dim) & (2**64 - 1)), n * self.ac_dim, z.data_ptr(),
+                                                     _ffi.stream_handle()))
+                noise = z.double().mul_(ns)
+                self.set_collect_stream(counter=ctr + 1)
+            elif not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.dtype == torch.float64 and noise.is_contiguous()
+                      and tuple(noise.shape) == (n, self.ac_dim)):
+                raise ValueError(f"{who}: noise: a contiguous CUDA float64 tensor [{n}, {self.ac_dim}] required")
+        out = torch.empty((n, self.ac_dim), dtype=torch.float32, device=rows.device)
+        _ffi.check(lib.gcrl_agent_observe_act_dev(self._h, nz[0], nz[1], rows.data_ptr(), D, n, noise.data_ptr() if noise is not None else None,
+                                                  mode, out.data_ptr(), _ffi.stream_handle()))
+        return out
+
+    def process_step_dev(self, state, actions, next_obs_raw, rewards, dones=None, obs_normalize: bool = True, g_normalize: bool = False, env0: int = 0):
+        """`process_step` for CUDA float32 tensors: `state` / `next_obs_raw` are dicts of [n, .] tensors (observation, desired_goal,
+        achieved_goal), `actions` [n, A], `rewards` [n]; `dones`: None (no env terminated) or a host bool array.  One pack launch builds
+        the step's blocks on the device, then the launch and the bookkeeping of `process_step` — nothing crosses to the host."""
+        who = f"{type(self).__name__}.process_step_dev"
+        self._check_normalize_call("process_step_dev", obs_normalize, g_normalize, need_device=True)
+        nz = self._dev_normalizers("process_step_dev", obs_normalize, g_normalize)
+        f = self._dev_f32
+        obs, nobs = f(who, "state['observation']", state["observation"]), f(who, "next_obs_raw['observation']", next_obs_raw["observation"])
+        n, D = int(obs.shape[0]), int(obs.shape[1])
+        dg, ndg = f(who, "state['desired_goal']", state["desired_goal"]), f(who, "next_obs_raw['desired_goal']", next_obs_raw["desired_goal"])
+        G = int(dg.shape[1])
+        nag = f(who, "next_obs_raw['achieved_goal']", next_obs_raw["achieved_goal"], (n, G))
+        ag = f(who, "state['achieved_goal']", state["achieved_goal"], (n, G)) if g_normalize else None
+        act = f(who, "actions", actions)
+        A = int(act.shape[1])
+        rew = f(who, "rewards", rewards.reshape(-1) if isinstance(rewards, torch.Tensor) else rewards, (n,))
+        for name, t, shp in (("next_obs_raw['observation']", nobs, (n, D)), ("state['desired_goal']", dg, (n, G)), ("next_obs_raw['desired_goal']", ndg, (n, G)),
+                             ("actions", act, (n, A))):
+            f(who, name, t, shp)
+        buf = self.buffer
+        buf._ensure(D + G, A, G)
+        self._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+        t_host = np.array([int(lib.gcrl_her_staged(buf.handle, int(env0) + i)) for i in range(n)], np.int32)
+        raw = torch.empty(n * (2 * D + 4 * G), dtype=torch.float32, device=obs.device)
+        pay = torch.zeros((n, 32), dtype=torch.float32, device=obs.device)
+        t_dev = None
+        if n and not np.all(t_host == t_host[0]):
+            t_dev = torch.from_numpy(t_host).to(obs.device)
+        st = _ffi.stream_handle()
+        _ffi.check(lib.gcrl_proc_pack(obs.data_ptr(), nobs.data_ptr(), dg.data_ptr(), ndg.data_ptr(), ag.data_ptr() if ag is not None else None,
+                                      nag.data_ptr(), act.data_ptr(), rew.data_ptr(), t_dev.data_ptr() if t_dev is not None else None,
+                                      int(t_host[0]) if n else 0, n, D, G, A, raw.data_ptr(), pay.data_ptr(), st))
+        dn = None if dones is None else np.ascontiguousarray(np.reshape(dones, -1), np.uint8)
+        if dn is not None and dn.any():   # the done flags are the host's: they reach the payload's done word from there
+            pay[:, 2] = torch.from_numpy(dn.astype(np.float32)).to(obs.device)
+        buf.rng.pull()
+        rows = lib.gcrl_her_process_step_dev(buf.handle, nz[0], 1 if obs_normalize else 0, nz[1], 1 if g_normalize else 0, raw.data_ptr(), pay.data_ptr(),
+                                             D, t_host.ctypes.data, dn.ctypes.data if dn is not None else None, int(env0), n, st)
+        buf._check_rows(rows)
+        buf.rng.push_back()
+        raw.record_stream(torch.cuda.current_stream()); pay.record_stream(torch.cuda.current_stream())
+        return int(rows)
+
+    def collect(self, env, steps: int, explore: bool = True, obs_normalize: bool = True, g_normalize: bool = False) -> int:
+        """`steps` vector steps of a `DeviceGoalEnv` into this agent's ring as ONE native call: per step the acting launch on the env's
+        rows, the env's step and the process-step launch, plus the flush launches of the envs that finish — no host <-> device copy and
+        no synchronisation.  `explore=True`: the device exploration stream (DESIGN.md §4q: counter-hash normals scaled by noise_std;
+        DDPG's epsilon branch from one counter-hash uniform per vector step); False: `observe_act`'s eval action.  Returns the ring rows
+        appended.  Refusals name their field and come before anything is consumed (include/gcrl.h gcrl_agent_collect)."""
+        who = f"{type(self).__name__}.collect"
+        if getattr(self, "_owner", None) is not None:
+            raise _ffi.GcrlError(f"{who}: collect: a population member acts through its population's entries; the population forms of collect are not built")
+        if getattr(self, "_dp_driven", False):
+            raise _ffi.GcrlError(f"{who}: collect: an agent driven by a DataParallelUpdater does not collect (the data-parallel form is not built)")
+        from .device_env import DeviceGoalEnv
+        if not isinstance(env, DeviceGoalEnv):
+            raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnv required")
+        if int(steps) < 1:
+            raise ValueError(f"{who}: steps: {steps} (>= 1 required)")
+        self._check_normalize_call("collect", obs_normalize, g_normalize, need_device=True)
+        nz = self._dev_normalizers("collect", obs_normalize, g_normalize)
+        buf = self.buffer
+        if env.obs_dim + env.goal_dim != self.obs_dim or env.ac_dim != self.ac_dim:
+            raise ValueError(f"{who}: env: obs_dim {env.obs_dim} + goal_dim {env.goal_dim} / ac_dim {env.ac_dim} differ from the agent's "
+                             f"state_dim {self.obs_dim} / ac_dim {self.ac_dim}")
+        buf._ensure(env.obs_dim + env.goal_dim, env.ac_dim, env.goal_dim)
+        self._collect_stream()
+        self.set_eval()
+        self._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+        rows = C.c_int64(0)
+        buf.rng.pull()
+        rc = lib.gcrl_agent_collect(self._h, env.handle, buf.handle, nz[0], 1 if obs_normalize else 0, nz[1], 1 if g_normalize else 0, int(steps),
+                                    1 if explore else 0, 2 if self._sac else self._ACT_MODE_EVAL, C.byref(rows), _ffi.stream_handle())
+        buf.rng.push_back()
+        _ffi.check(rc)
+        buf._check_rows(int(rows.value))
+        return int(rows.value)
+
+    def collect_counts(self) -> dict:
+        """What `collect` (and `observe_act_dev`) have issued since this agent was created: calls and vector steps of `collect`, kernel
+        launches, host <-> device copies and stream synchronisations (include/gcrl.h gcrl_agent_collect_counts)."""
+        v = [C.c_int64(0) for _ in range(5)]
+        _ffi.check(lib.gcrl_agent_collect_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "steps", "launches", "copies", "syncs"), (int(x.value) for x in v)))
+
     def push(self, state, action, reward, next_state, done):
         # (with a HERBuffer the reference passes 5 args to a push that takes 8 -> TypeError there too)
         self.buffer.push(state, action, reward, next_state, done)
@@ -881,6 +1049,9 @@ class _EngineAgent:
             meta["prior"] = dict(rows=int(self.prior_rows), ring=self.prior_buffer.save_state(os.path.join(path, "prior_ring.bin")))
         if self.bc_weight is not None:        # the behaviour-cloning term's settings: a resume under other settings is refused
             meta["bc"] = dict(bc_weight=float(self.bc_weight), q_filter=bool(self.q_filter))
+        if self.__dict__.get("_collect_bound"):   # the device exploration stream of collect: its key and its vector-step counter
+            sd, _, _, ctr = self._collect_stream()
+            meta["collect"] = dict(seed=sd, counter=ctr)
         for name in ("obs_normalizer", "dg_normalizer"):
             nz = getattr(self.buffer, name, None)
             if nz is not None:
@@ -916,6 +1087,8 @@ class _EngineAgent:
         blob = np.fromfile(os.path.join(path, "agent.bin"), dtype=np.uint8)
         _ffi.check(lib.gcrl_agent_load_state(self._h, blob.ctypes.data, blob.size))
         self._bc_ticket = None
+        if "collect" in meta:
+            self.set_collect_stream(seed=int(meta["collect"]["seed"]), counter=int(meta["collect"]["counter"]))
         self.beta = meta["beta"]
         self.actor.num_batches_tracked = meta["num_batches_tracked"]
         self.buffer.load_state(os.path.join(path, "ring.bin"), meta["ring"])
@@ -990,6 +1163,8 @@ class DDPG(_EngineAgent):
             action = torch.tanh(self._actor_forward(obs_tensor)).cpu().numpy()  # double tanh, as the reference
             return np.clip(action + np.random.normal(0, self.noise_std, size=action.shape), -1, 1)
         return np.clip(torch.tanh(self._actor_forward(obs_tensor)).cpu().numpy(), -1, 1)
+
+    COLLECT_EPSILON = 0.2      # src/agent.py:1348, drawn from the device exploration stream's own uniform
 
     def _act_noise(self, n, eval_action):
         if not eval_action and self.buffer.rng.random() < 0.2:      # src/agent.py:1348

@@ -1,0 +1,125 @@
+"""Device-resident goal environments (csrc/dev_env.hip): `num_envs` independent envs of a built-in kind whose state, counters and
+step blocks live in device memory.  `agent.collect(env, steps)` drives them without the host in the loop; `acting_rows()` and
+`step_blocks()` hand out tensor views for callers who drive `observe_act_dev` / `process_step_dev` themselves.
+
+The rule of both kinds — constants, operation order, random-number keys — is restated in numpy in tests/dev_env_ref.py, which
+is its definition.  The envs are not panda-gym: `reach` is the point mass of examples/trainer_standin.py in float32, `push` a
+pusher that carries a puck along while it is inside a contact radius."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _ffi
+from .._ffi import lib
+
+KINDS = {"reach": 0, "push": 1}
+PAY_W = 32
+
+
+class _DevBlock:
+    """Zero-copy torch view of a float32 device block the env handle owns (it lives as long as the handle)."""
+
+    def __init__(self, ptr: int, numel: int):
+        self.__cuda_array_interface__ = {"shape": (int(numel),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class DeviceGoalEnv:
+    def __init__(self, kind: str, num_envs: int, seed: int = 0, max_steps: int = 50, threshold: float = 0.05, device_index: int = 0):
+        if kind not in KINDS:
+            raise ValueError(f"DeviceGoalEnv: kind: {kind!r} (one of {sorted(KINDS)})")
+        self.kind, self.device_index = kind, int(device_index)
+        self._h = _ffi.check_ptr(lib.gcrl_env_create(KINDS[kind], int(num_envs), int(seed) & (2**64 - 1), int(max_steps), float(threshold),
+                                                     self.device_index), "gcrl_env_create")
+        ints = [C.c_int() for _ in range(6)]
+        thr, sd = C.c_float(), C.c_uint64()
+        _ffi.check(lib.gcrl_env_dims(self._h, *[C.byref(x) for x in ints], C.byref(thr), C.byref(sd)))
+        _, self.num_envs, self.obs_dim, self.goal_dim, self.ac_dim, self.max_steps = (int(x.value) for x in ints)
+        self.threshold = float(thr.value)
+        self._views = None
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.gcrl_env_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def seed(self) -> int:
+        sd = C.c_uint64()
+        _ffi.check(lib.gcrl_env_dims(self._h, None, None, None, None, None, None, None, C.byref(sd)))
+        return int(sd.value)
+
+    # ------------------------------------------------------------------ views of the handle's device blocks
+    def _blocks(self):
+        if self._views is None:
+            p = [C.c_void_p() for _ in range(3)]
+            _ffi.check(lib.gcrl_env_buffers(self._h, *[C.byref(x) for x in p]))
+            n, D, G = self.num_envs, self.obs_dim, self.goal_dim
+            dev = f"cuda:{self.device_index}"
+            self._views = (torch.as_tensor(_DevBlock(p[0].value, n * (D + G)), device=dev).view(n, D + G),
+                           torch.as_tensor(_DevBlock(p[1].value, n * (2 * D + 4 * G)), device=dev),
+                           torch.as_tensor(_DevBlock(p[2].value, n * PAY_W), device=dev).view(n, PAY_W))
+        return self._views
+
+    def acting_rows(self):
+        """{"rows": [N, obs_dim + goal_dim] raw [obs | goal] rows of the NEXT step, "observation": ..., "desired_goal": ...}: views of
+        the handle's memory, rewritten by every step."""
+        rows = self._blocks()[0]
+        return {"rows": rows, "observation": rows[:, :self.obs_dim], "desired_goal": rows[:, self.obs_dim:]}
+
+    def step_blocks(self):
+        """(raw, pay) of the LAST step in the layout `process_step_dev` takes: raw = [obs | next_obs | dg | next_dg | ag | next_ag] blocks,
+        pay [N, 32] = t | reward | done | action | next_ag.  `split_raw` cuts raw into its six [N, .] blocks."""
+        return self._blocks()[1], self._blocks()[2]
+
+    def split_raw(self, raw=None):
+        raw = self._blocks()[1] if raw is None else raw
+        n, D, G = self.num_envs, self.obs_dim, self.goal_dim
+        out, o = [], 0
+        for w in (D, D, G, G, G, G):
+            out.append(raw[o:o + n * w].view(n, w))
+            o += n * w
+        return out
+
+    # ------------------------------------------------------------------ stepping by hand
+    def reset(self, mask=None):
+        """No mask: every env back to its episode 0 and the counters to zero.  mask [N] bool (host): those envs go on to their next episode."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1), np.uint8)
+            if m.size != self.num_envs:
+                raise ValueError(f"DeviceGoalEnv.reset: mask: {m.size} entries for {self.num_envs} envs")
+        _ffi.check(lib.gcrl_env_reset(self._h, m.ctypes.data if m is not None else None, _ffi.stream_handle()))
+        return self.acting_rows()
+
+    def step(self, actions):
+        """One vector step from a CUDA float32 or float64 tensor [N, 3]; returns nothing: read `step_blocks()` / `acting_rows()`."""
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.is_contiguous() and actions.dtype in (torch.float32, torch.float64)
+                and tuple(actions.shape) == (self.num_envs, self.ac_dim)):
+            raise ValueError(f"DeviceGoalEnv.step: actions: a contiguous CUDA float32 / float64 tensor [{self.num_envs}, {self.ac_dim}] required")
+        _ffi.check(lib.gcrl_env_step(self._h, actions.data_ptr(), 1 if actions.dtype == torch.float64 else 0, _ffi.stream_handle()))
+
+    def stats(self) -> dict:
+        """Synchronises.  Episodes finished, episodes that ended within the threshold, reward sum — since the last full reset."""
+        ep, su, rs = C.c_int64(), C.c_int64(), C.c_double()
+        _ffi.check(lib.gcrl_env_stats(self._h, C.byref(ep), C.byref(su), C.byref(rs), _ffi.stream_handle()))
+        return dict(episodes=int(ep.value), successes=int(su.value), reward_sum=float(rs.value))
+
+    # ------------------------------------------------------------------ resume
+    def save_state(self) -> np.ndarray:
+        """State arrays, counters, acting rows and the seed as one uint8 array; `load_state` resumes bitwise."""
+        n = int(lib.gcrl_env_state_bytes(self._h))
+        blob = np.empty(n, np.uint8)
+        _ffi.check(lib.gcrl_env_save_state(self._h, blob.ctypes.data, n, _ffi.stream_handle()))
+        return blob
+
+    def load_state(self, blob):
+        """Refuses a state of another kind, num_envs, max_steps or threshold by that field's name before anything is overwritten."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        _ffi.check(lib.gcrl_env_load_state(self._h, blob.ctypes.data, blob.size, _ffi.stream_handle()))

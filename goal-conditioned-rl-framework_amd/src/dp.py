@@ -112,6 +112,7 @@ class DataParallelUpdater:
                                  "gradient exchange; DataParallelUpdater does not drive it")
         self._ffi = _ffi
         self.agent = agent
+        agent._dp_driven = True      # (entries a gradient exchange does not cover refuse such an agent: collect)
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)

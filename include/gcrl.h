@@ -1074,6 +1074,79 @@ int gcrl_bc_qfilter_f32(const float* spa_dev, const float* sa_dev, int ldx, int 
                         const float* q_a_dev, int B, int Bd, int A, double bc_weight, float* dact_dev, int ld_dact, float* mask_dev,
                         float* metrics_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-resident goal environments, device-row acting entries and the collect loop.
+ *
+ * gcrl_env: N independent goal environments of one built-in kind in device memory (csrc/dev_env.hip; the rule is restated in
+ * tests/dev_env_ref.py, which is its definition).  G = 3, A = 3, fixed horizon max_steps, sparse reward -(dist > threshold) as the
+ * replay ring's built-in sparse kind forms it, no termination on success.  GCRL_ENV_REACH: obs = [pos, vel, t/T] (7), achieved goal =
+ * pos.  GCRL_ENV_PUSH: obs = [pusher, puck, puck - pusher, pusher velocity, t/T] (13), achieved goal = puck.  Random numbers are a
+ * counter hash keyed by (seed, episode index of the env, env, component): an env's episode j does not depend on N.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct gcrl_env gcrl_env;
+enum { GCRL_ENV_REACH = 0, GCRL_ENV_PUSH = 1 };
+/* num_envs 1..1024, max_steps 1..64, 0 < threshold < 0.3 (push: 2 * threshold <= 0.15).  Every env starts at its episode 0. */
+gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device);
+void gcrl_env_destroy(gcrl_env* e);
+int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps, float* threshold, uint64_t* seed);
+/* Device addresses of the handle's blocks: rows [N][obs_dim + 3] = the acting rows [obs | goal] of the NEXT step; raw = the last
+ * step's [obs N*D | next_obs N*D | dg N*3 | next_dg N*3 | ag N*3 | next_ag N*3]; pay [N][32] = t | reward | done = 0 | action(3) |
+ * next_ag(3) — the layouts gcrl_agent_observe_act_dev and gcrl_her_process_step_dev read. */
+int gcrl_env_buffers(gcrl_env* e, float** rows, float** raw, float** pay);
+/* mask_host NULL: every env back to its episode 0, the counters to zero.  Else one byte per env: the selected envs go on to their
+ * next episode (not counted as finished). */
+int gcrl_env_reset(gcrl_env* e, const uint8_t* mask_host, void* stream);
+/* One vector step, one launch: actions [N][3] on the device, float32 (actions_f64 == 0) or float64 (rounded to float32 first).  Any
+ * action bits leave a finite state (a NaN component counts as 0).  An env that reaches the horizon is counted and re-seeded. */
+int gcrl_env_step(gcrl_env* e, const void* actions_dev, int actions_f64, void* stream);
+/* Synchronises.  Episodes finished, those that ended with dist < threshold, and the reward sum, over all envs since the last full reset. */
+int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream);
+/* State arrays, counters, acting rows and the seed; resume is bitwise.  Loading refuses another kind, num_envs, max_steps or
+ * threshold by that field's name before anything is overwritten. */
+int64_t gcrl_env_state_bytes(const gcrl_env* e);
+int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream);
+int gcrl_env_load_state(gcrl_env* e, const void* src_host, int64_t n, void* stream);
+/* raw | pay of one vector step (the layout above, general dimensions) from separate contiguous float32 device tensors [n][.], one
+ * launch.  ag_dev may be NULL (the ag and next_ag blocks of raw are then left alone; only a goal normaliser reads them).  The
+ * payload's t word of env i is t_dev[i], or t0 when t_dev is NULL. */
+int gcrl_proc_pack(const float* obs_dev, const float* next_obs_dev, const float* dg_dev, const float* next_dg_dev, const float* ag_dev,
+                   const float* next_ag_dev, const float* actions_dev, const float* rewards_dev, const int32_t* t_dev, int t0, int n,
+                   int obs_dim, int goal_dim, int action_dim, float* raw_out_dev, float* pay_out_dev, void* stream);
+/* gcrl_agent_observe_act on DEVICE rows: rows_dev [n][state_dim] = raw [obs | goal] rows, noise_dev [n][A] float64 or NULL, float32
+ * actions to out_f32_dev [n][A] — the float32 rounding of the float64 action the host entry returns, bit for bit.  It issues the
+ * launch the host entry issues for staged rows (after the weight-copy rebuild where that entry does one), then one launch that rounds
+ * the actions (and, for SAC / TQC with noise, one before it that rounds the eps, as the host entry stages it).  No copy, no
+ * synchronisation.  n = 1..batch_size. */
+int gcrl_agent_observe_act_dev(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, const float* rows_dev, int obs_dim, int n,
+                               const double* noise_dev, int mode, float* out_f32_dev, void* stream);
+/* gcrl_her_process_step_g on CALLER-OWNED device blocks in the layout above (on a normalize = "sample" ring: the raw-store form), with
+ * the same host bookkeeping: staged counts, flushes, normaliser marks.  Nothing is uploaded, nothing is waited for.  dones_host NULL:
+ * no env terminated (episodes end when flush_len rows are staged).  t_host[i]: the t word the caller wrote into env i's payload; it
+ * must equal the ring's staged count of env0 + i, else GCRL_ERR_STATE naming `t` — checked on the host, before any launch.  A ring
+ * with a host-callback reward is refused (compute_reward). */
+int64_t gcrl_her_process_step_dev(gcrl_her* h, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg, int update_goal_stats,
+                                  const float* raw_dev, const float* pay_dev, int obs_dim, const int32_t* t_host, const uint8_t* dones_host,
+                                  int env0, int n, void* stream);
+/* flush groups issued by the vector-step entries' bookkeeping since creation */
+int64_t gcrl_her_flush_calls(const gcrl_her* h);
+/* The exploration stream of gcrl_agent_collect: element (c, i, j) of vector step c is double(hash_normal(seed, (c N + i) A + j)) *
+ * noise_std (SAC / TQC: the eps is that hash value); DDPG: with probability epsilon per vector step (one counter-hash uniform the
+ * host evaluates) every env takes a clipped hash normal instead of the actor's action.  `counter` is c: part of a resume. */
+int gcrl_agent_collect_set(gcrl_agent* a, uint64_t seed, double noise_std, double epsilon, uint64_t counter);
+int gcrl_agent_collect_get(const gcrl_agent* a, uint64_t* seed, double* noise_std, double* epsilon, uint64_t* counter);
+/* `steps` vector steps of env into ring as a native loop, in stream order per step: the acting launch on the env's rows, the env's
+ * step, the process-step launch on the env's blocks, and the flush launches the ring's bookkeeping calls for — no host <-> device
+ * copy and no synchronisation.  explore != 0: the stream above (mode 1 of gcrl_agent_observe_act); else its mode eval_mode.
+ * Refused by field name before anything is consumed: env (more envs than ring slots, than batch_size or than 1024; dimensions that
+ * differ from the agent's or the ring's; another device), max_steps (!= the ring's flush length), compute_reward (a ring whose reward
+ * kind is not the built-in sparse one), threshold, steps (< 1), nz_obs / nz_dg (an update flag without its normaliser), t (the env
+ * is not where the ring's staging area is).  *rows_out: ring rows appended. */
+int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                       int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream);
+/* what gcrl_agent_collect and gcrl_agent_observe_act_dev have issued since creation; counted where issued (flush launches: declared
+ * from the flush's definition — one per flush group, plus one per priority tree it seeds).  Any pointer may be NULL. */
+int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);
