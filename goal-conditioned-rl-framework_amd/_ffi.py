@@ -78,6 +78,25 @@ class UpdateInputs(C.Structure):
     ]
 
 
+class GemmProblem(C.Structure):
+    """gcrl_gemm_problem: one problem of gcrl_gemm_batch_f32 (tests)."""
+    _fields_ = [
+        ("a_dev", C.c_void_p), ("a_rs", C.c_int64), ("a_cs", C.c_int64),
+        ("b_dev", C.c_void_p), ("b_rs", C.c_int64), ("b_cs", C.c_int64),
+        ("c_dev", C.c_void_p), ("c_rs", C.c_int64),
+        ("bias_dev", C.c_void_p),
+        ("h_dev", C.c_void_p), ("h_rs", C.c_int64),
+        ("col_out_dev", C.c_void_p),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("act", C.c_int32), ("mul", C.c_int32), ("ones_col", C.c_int32),
+        ("slot_dev", C.c_void_p),
+        ("a_slot", C.c_int64), ("b_slot", C.c_int64), ("c_slot", C.c_int64), ("h_slot", C.c_int64),
+        ("shape_hint", C.c_int32), ("ksplit", C.c_int32),
+        ("bn_part_dev", C.c_void_p),
+        ("sumsq_dev", C.c_void_p),
+        ("form_out", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _vp, _i32, _i64, _u32, _u64, _f32, _f64 = (C.c_void_p, C.c_int32, C.c_int64, C.c_uint32,
                                            C.c_uint64, C.c_float, C.c_double)
 _cp = C.c_char_p
@@ -223,6 +242,7 @@ PROTOTYPES = {
     "gcrl_her_process_step_g": (_i64, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "gcrl_sort_truncate_mean": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gcrl_gemm_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "gcrl_gemm_batch_f32": (C.c_int, [C.POINTER(GemmProblem), C.c_int, C.c_int, _vp]),
     "gcrl_gemm_dw_split_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gcrl_bn_relu_fwd_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gcrl_bn_relu_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -161,6 +161,100 @@ int gcrl_gemm_dw_split_f32(const float* g, int64_t ldg, const float* x, int64_t 
   return rc;
 }
 
+// The whole problem record, up to kMaxProb problems per call (include/gcrl.h).  Operands are assumed below 2 GiB each: the kernels'
+// 32-bit byte offsets (gemm_mfma.h, gemm_tiled.h) cannot be reached at test sizes and are not checked here.
+int gcrl_gemm_batch_f32(gcrl_gemm_problem* p, int n, int shape, void* stream) {
+  GCRL_CHECK_ARG(shape >= 0 && shape <= 5, "gcrl_gemm_batch_f32: bad shape %d", shape);
+  hipStream_t st = as_stream(stream);
+  if (n < 1 || n > gcrl::kMaxProb) return gcrl::launch_gemm_batch(st, nullptr, n, shape);   // (the launcher's own refusal)
+  GCRL_CHECK_ARG(p, "gcrl_gemm_batch_f32: null problem array");
+  struct Scratch {   // freed, after the stream has drained, when the call returns
+    hipStream_t st;
+    std::vector<void*> mem;
+    ~Scratch() {
+      if (mem.empty()) return;
+      (void)hipStreamSynchronize(st);
+      for (void* m : mem) (void)hipFree(m);
+    }
+    void* zeroed(size_t bytes, bool zero) {
+      void* m = nullptr;
+      if (hipMalloc(&m, bytes) != hipSuccess) return nullptr;
+      mem.push_back(m);
+      if (zero && hipMemsetAsync(m, 0, bytes, st) != hipSuccess) return nullptr;
+      return m;
+    }
+  } sc{st, {}};
+  gcrl::GemmDesc d[gcrl::kMaxProb];
+  int form[gcrl::kMaxProb], nss[gcrl::kMaxProb];
+  bool twice = false;
+  for (int i = 0; i < n; ++i) {
+    const gcrl_gemm_problem& q = p[i];
+    GCRL_CHECK_ARG(q.act >= 0 && q.act <= 3 && q.mul >= 0 && q.mul <= 3 && q.shape_hint >= 0 && q.shape_hint <= 5 && q.ksplit >= 0 && q.ksplit <= 64,
+                   "gcrl_gemm_batch_f32: problem %d: bad act=%d / mul=%d / shape_hint=%d / ksplit=%d", i, q.act, q.mul, q.shape_hint, q.ksplit);
+    GCRL_CHECK_ARG(q.mul == 0 || q.h_dev, "gcrl_gemm_batch_f32: problem %d: mul=%d needs the saved activations", i, q.mul);
+    gcrl::GemmDesc& g = d[i];
+    std::memset(&g, 0, sizeof(g));
+    g.A = q.a_dev; g.a_rs = q.a_rs; g.a_cs = q.a_cs;
+    g.B = q.b_dev; g.b_rs = q.b_rs; g.b_cs = q.b_cs;
+    g.C = q.c_dev; g.c_rs = q.c_rs;
+    g.bias = q.bias_dev;
+    g.H = q.h_dev; g.h_rs = q.h_rs;
+    g.col_out = q.col_out_dev;
+    g.M = q.M; g.N = q.N; g.K = q.K;
+    g.epi = q.act; g.mul = q.mul; g.ones_col = q.ones_col ? 1 : 0;
+    g.slot = q.slot_dev; g.a_slot = q.a_slot; g.b_slot = q.b_slot; g.c_slot = q.c_slot; g.h_slot = q.h_slot;
+    g.shape_hint = q.shape_hint; g.ksplit = q.ksplit;
+    g.bn_part = q.bn_part_dev;
+    g.sumsq_out = q.sumsq_dev;   // (non-null is all the form rule reads; the partial array replaces it below)
+    form[i] = shape ? shape : (g.shape_hint ? g.shape_hint : gcrl::gemm_shape_of(g));
+    p[i].form_out = form[i];
+    nss[i] = 0;
+    if (g.M < 1 || g.N < 1 || g.K < 1) continue;   // (refused by the launcher: nothing to size)
+    if (g.ksplit > 1) {
+      const size_t tiles = (size_t)((g.M + 63) / 64) * (size_t)((g.N - g.ones_col + 63) / 64 > 0 ? (g.N - g.ones_col + 63) / 64 : 1);
+      g.kpart = (float*)sc.zeroed(tiles * g.ksplit * gcrl::kTiledPartStride * sizeof(float), false);
+      g.kticket = (unsigned int*)sc.zeroed(tiles * gcrl::kTicketStride * sizeof(unsigned int), true);
+      if (!g.kpart || !g.kticket) return gcrl::fail(GCRL_ERR_HIP, "gcrl_gemm_batch_f32: problem %d: scratch", i);
+      if (form[i] == 4) twice = true;
+    }
+    if (q.sumsq_dev) {
+      nss[i] = std::max(0, gcrl::gemm_sumsq_partials(g, form[i]));
+      g.sumsq_out = (float*)sc.zeroed((size_t)std::max(nss[i], 1) * sizeof(float), true);
+      if (!g.sumsq_out) return gcrl::fail(GCRL_ERR_HIP, "gcrl_gemm_batch_f32: problem %d: scratch", i);
+    }
+  }
+  if (int rc = gcrl::launch_gemm_batch(st, d, n, shape)) return rc;
+  if (twice) {   // again: the tickets must have come back to zero by themselves; what a split problem wrote is "not written" before
+    for (int i = 0; i < n; ++i) {
+      const gcrl::GemmDesc& g = d[i];
+      if (!(g.ksplit > 1 && form[i] == 4)) continue;
+      int s = 0;
+      if (g.slot) {
+        GCRL_HIP(hipMemcpyAsync(&s, g.slot, sizeof(int), hipMemcpyDeviceToHost, st));
+        GCRL_HIP(hipStreamSynchronize(st));
+      }
+      const int cols = g.N - g.ones_col;
+      if (cols >= 1 && g.c_rs >= cols)
+        GCRL_HIP(hipMemset2DAsync(g.C + (long long)s * g.c_slot, (size_t)g.c_rs * sizeof(float), 0xff, (size_t)cols * sizeof(float), (size_t)g.M, st));
+      if (g.ones_col) GCRL_HIP(hipMemsetAsync(g.col_out, 0xff, (size_t)g.M * sizeof(float), st));
+      if (nss[i]) GCRL_HIP(hipMemsetAsync(g.sumsq_out, 0, (size_t)nss[i] * sizeof(float), st));
+    }
+    if (int rc = gcrl::launch_gemm_batch(st, d, n, shape)) return rc;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!p[i].sumsq_dev) continue;
+    std::vector<float> h((size_t)nss[i]);
+    if (nss[i]) GCRL_HIP(hipMemcpyAsync(h.data(), d[i].sumsq_out, h.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipStreamSynchronize(st));
+    float tot = 0.f;
+    for (float v : h) tot += v;   // index order
+    GCRL_HIP(hipMemcpyAsync(p[i].sumsq_dev, &tot, sizeof(float), hipMemcpyHostToDevice, st));
+    GCRL_HIP(hipStreamSynchronize(st));   // (tot is on this stack)
+  }
+  GCRL_HIP(hipStreamSynchronize(st));
+  return GCRL_OK;
+}
+
 int gcrl_bn_relu_fwd_f32(const float* z, int B, int H, const float* gamma, const float* beta, float* h, float* xhat, float* invstd,
                          float* running_mean, float* running_var, float* scratch, void* stream) {
   GCRL_CHECK_ARG(z && gamma && beta && h && running_mean && running_var && scratch && B >= 1 && H >= 4, "gcrl_bn_relu_fwd_f32: bad arguments");

@@ -484,5 +484,9 @@ int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape = 0);
 // What launch_gemm_batch fills in for a problem of the k-split 16x16 form (vector-load flags, tile bookkeeping with tile0 = 0), for
 // kernels that call gemm_batch_tile<1, 1, 4> themselves (dw_adam.hip, ops_sac.hip heads_sample_kernel).  Returns the tile count.
 int gemm_prepare_ksplit(GemmDesc& d);
+// Floats of sumsq_out a problem writes on form `shape` (1..4), from the launcher's own tile bookkeeping: one per finishing wave at
+// [tile * 4 + wave] on forms 1 and 4 (the split form: per 64x64 tile, not per split), one per wave tile on forms 2 and 3.  0 on
+// form 5 (which takes no sumsq_out), < 0: refused.  For callers that own the partial array (gcrl_gemm_batch_f32).
+int gemm_sumsq_partials(const GemmDesc& d, int shape);
 
 }  // namespace gcrl

@@ -111,7 +111,9 @@ __global__ __launch_bounds__(256) void gemm_outer_kernel(GemmBatch gb) {
     v4f v;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float x = __fmul_rn(av[u], bv[u][r]);
+      // (+ 0: the matrix cores add the product onto an accumulator that starts at +0, so a zero product — 0 * -3 = -0 — comes out as
+      // +0 there; without the bias the bare product kept its sign here and forms 3 and 5 differed in that bit)
+      float x = __fmul_rn(av[u], bv[u][r]) + 0.f;
       if (d.bias) x += biv[u][r];
       x = act_apply(x, epi);
       if (mul != MUL_NONE) x *= act_deriv(hv[u][r], mul);
@@ -180,13 +182,23 @@ int gemm_prepare_ksplit(GemmDesc& d) {
   return d.ntiles;
 }
 
+int gemm_sumsq_partials(const GemmDesc& d, int shape) {
+  if (shape < 1 || shape > 4) return 0;
+  GemmBatch gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.d[gb.n++] = d;
+  if (prep_form(shape, gb) < 0) return -1;
+  const GemmDesc& p = gb.d[0];
+  return shape == 1 ? p.ntiles * 4 : (shape == 4 ? (p.ntiles / p.ksplit) * 4 : p.ntiles);
+}
+
 int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape) {
   GCRL_CHECK_ARG(n >= 1 && n <= kMaxProb, "launch_gemm_batch: %d problems (max %d)", n, kMaxProb);
   int shapes[kMaxProb];
   for (int i = 0; i < n; ++i) {
     GemmDesc& d = descs[i];
     GCRL_CHECK_ARG(d.M >= 1 && d.N >= 1 && d.K >= 1 && d.A && d.B && d.C, "launch_gemm_batch: bad problem %d (M=%d N=%d K=%d)", i, d.M, d.N, d.K);
-    GCRL_CHECK_ARG(!d.ones_col || (d.N >= 2 && d.col_out), "launch_gemm_batch: ones_col needs N >= 2 and col_out");
+    GCRL_CHECK_ARG(!d.ones_col || (d.N >= 2 && d.col_out), "launch_gemm_batch: problem %d: ones_col needs N >= 2 and col_out", i);
     d.a_vec = (d.a_cs == 1 && d.a_rs % 4 == 0 && ((uintptr_t)d.A & 15) == 0);
     d.b_vec = (d.b_rs == 1 && d.b_cs % 4 == 0 && ((uintptr_t)d.B & 15) == 0);
     d.a_rvec = (d.a_rs == 1 && d.a_cs % 4 == 0 && ((uintptr_t)d.A & 15) == 0);
@@ -198,7 +210,7 @@ int launch_gemm_batch(hipStream_t st, GemmDesc* descs, int n, int shape) {
                                   (shapes[i] == 1 || (shapes[i] == 4 && d.N % 4 == 0 && d.c_rs % 4 == 0 && ((uintptr_t)d.C & 15) == 0 &&
                                                       ((uintptr_t)d.bn_part & 15) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0) &&
                                                       d.mul == MUL_NONE && d.ksplit <= 1))),
-                   "launch_gemm_batch: bn_part needs the k-split 16x16 form or an unsplit LDS-tiled problem with aligned quads");
+                   "launch_gemm_batch: problem %d: bn_part needs the k-split 16x16 form or an unsplit LDS-tiled problem with aligned quads", i);
   }
   for (int i = 0; i < n; ++i) GCRL_CHECK_ARG(shapes[i] != 5 || outer_ok(descs[i]), "launch_gemm_batch: problem %d is not an aligned K = 1 outer product", i);
   for (int s = 1; s <= 5; ++s) {  // one launch per shape present (almost always exactly one)

@@ -799,6 +799,41 @@ int gcrl_gemm_f32(const float* a_dev, int64_t a_rs, int64_t a_cs, const float* b
 int gcrl_gemm_dw_split_f32(const float* g_dev, int64_t ldg, const float* x_dev, int64_t ldx, float* dw_dev, float* db_dev,
                            int out, int in, int batch, int ksplit, float* sumsq_dev, void* stream);
 
+/* One problem of gcrl_gemm_batch_f32: everything the engine's problem record (csrc/gemm_mfma.h, GemmDesc) lets a caller choose.
+ *   C[m*c_rs + n] = act(sum_k A(m,k) B(k,n) + bias[n]) * mul'(H[m*h_rs + n])      A(m,k) = a[m*a_rs + k*a_cs], B(k,n) = b[k*b_rs + n*b_cs]
+ * act: 0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 tanh.  mul: 0 none, 1 / 2 / 3 = the derivative of LeakyReLU / ReLU / tanh at the SAVED
+ * activation H (h > 0 decides; 1 - h^2).  ones_col: B(k, N-1) := 1 and column N-1 of the result goes to col_out[m] instead of C (the
+ * bias gradient of a dW | db problem; N >= 2).  slot_dev: if not null, a device word s; the operands are then a + s*a_slot,
+ * b + s*b_slot, c + s*c_slot, h + s*h_slot (element strides), read on the device at launch time.  shape_hint: the problem's own tile
+ * form (0: the launcher's rule); ksplit: the LDS-tiled form's reduction split (0 / 1: none).  bn_part_dev: per-row-tile (mean, M2)
+ * of every column of C, [2 * ceil(M / T)][N] floats, T = 16 on form 1 and 64 on form 4.  sumsq_dev: one float, the sum of squares of
+ * everything the problem wrote.  form_out: set by the call to the tile form (1..5) the problem ran on. */
+typedef struct gcrl_gemm_problem {
+  const float* a_dev; int64_t a_rs, a_cs;
+  const float* b_dev; int64_t b_rs, b_cs;
+  float* c_dev; int64_t c_rs;
+  const float* bias_dev;
+  const float* h_dev; int64_t h_rs;
+  float* col_out_dev;
+  int32_t M, N, K, act, mul, ones_col;
+  const int32_t* slot_dev;
+  int64_t a_slot, b_slot, c_slot, h_slot;
+  int32_t shape_hint, ksplit;
+  float* bn_part_dev;
+  float* sumsq_dev;
+  int32_t form_out, reserved;
+} gcrl_gemm_problem;
+
+/* The same GEMM with its whole problem record, 1..12 problems per call, exactly as the engine issues it per layer: one launch per tile
+ * form present.  shape: 1..5 forces one form on every problem; 0 = each problem's own (shape_hint, else the launcher's rule).  The
+ * call owns what the engine owns per layer: the split partials and a zeroed ticket array of every problem with ksplit > 1 (the batch
+ * is then launched TWICE — the tickets must return to zero by themselves — and everything such a problem wrote is set to all-ones
+ * words in between), the zero-filled sum-of-squares partials, sized from the launcher's own tile count, which are added on the host
+ * in index order to one float.  It allocates, synchronises and frees per call: for tests, not a fast path.  The launcher's
+ * refusals come back as GCRL_ERR_ARG with nothing written.  The kernels address an operand with 32-bit byte offsets: every operand
+ * (last element's index + 1, slot offset included) must stay below 2 GiB. */
+int gcrl_gemm_batch_f32(gcrl_gemm_problem* problems_host, int n, int shape, void* stream);
+
 /* nn.BatchNorm1d in training mode followed by ReLU, as the SAC / TQC actors run it per hidden layer
  * (src/model.py:106-108: Linear -> BatchNorm1d -> ReLU; eps 1e-5, momentum 0.1, running variance unbiased), forward and
  * backward as single problems.  All pointers are device memory, row-major [B, H]; H must be a multiple of 4 and every
