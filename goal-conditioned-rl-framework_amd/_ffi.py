@@ -238,6 +238,22 @@ PROTOTYPES = {
     "gcrl_agent_collect_get": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_u64)]),
     "gcrl_agent_collect": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp]),
     "gcrl_agent_collect_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_env_group_create": (_vp, [C.c_int, C.c_int, C.c_int, C.POINTER(_u64), C.c_int, _f32, C.c_int]),
+    "gcrl_env_group_destroy": (None, [_vp]),
+    "gcrl_env_group_dims": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_f32), C.POINTER(_u64), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gcrl_env_group_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "gcrl_env_group_reset": (C.c_int, [_vp, _vp, _vp]),
+    "gcrl_env_group_step": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "gcrl_env_group_stats": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64), _vp]),
+    "gcrl_env_group_state_bytes": (_i64, [_vp]),
+    "gcrl_env_group_save_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_env_group_load_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_agent_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64), _vp]),
+    "gcrl_pop_collect": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_i64), _vp]),
+    "gcrl_pop_collect_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_pop_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64), _vp]),
     "gcrl_her_process_step": (_i64, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "gcrl_her_process_step_g": (_i64, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "gcrl_sort_truncate_mean": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp]),

@@ -146,6 +146,7 @@ struct gcrl_agent {
   // float32 actions or eps [B][A]; the exploration stream's seed, scale and vector-step counter; which env's noise of which step the
   // noise block holds (written by the previous step's env launch); what the loop has issued (gcrl_agent_collect_counts)
   char* col_dev = nullptr;
+  char* eval_snap = nullptr;             // gcrl_agent_evaluate with reset == 0: the env counters as of the start of the call (device copy)
   unsigned long long col_seed = 0, col_ctr = 0;
   double col_noise_std = 0.0, col_epsilon = 0.0;
   const void* col_noise_env = nullptr; unsigned long long col_noise_ctr = 0; bool col_noise_valid = false;
@@ -1879,6 +1880,7 @@ void gcrl_agent_destroy(gcrl_agent* a) {
   if (a->act_fl_host) (void)hipHostFree(a->act_fl_host);
   if (a->oa_dev) (void)hipFree(a->oa_dev);
   if (a->col_dev) (void)hipFree(a->col_dev);
+  if (a->eval_snap) (void)hipFree(a->eval_snap);
   for (int i = 0; i < gcrl_agent::kProfPairs; ++i) {
     if (a->prof_a[i]) (void)hipEventDestroy(a->prof_a[i]);
     if (a->prof_b[i]) (void)hipEventDestroy(a->prof_b[i]);
@@ -3041,6 +3043,59 @@ int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* step
   if (launches) *launches = a->col_launches;
   if (copies) *copies = a->col_copies;
   if (syncs) *syncs = a->col_syncs;
+  return GCRL_OK;
+}
+
+int gcrl_agent_evaluate(gcrl_agent* a, gcrl_env* env, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, int episodes, int reset, int eval_mode,
+                        int64_t* episodes_out, int64_t* successes_out, double* reward_sum_out, void* stream) {
+  const char* who = "gcrl_agent_evaluate";
+  GCRL_CHECK_ARG(a && env, "%s: null argument", who);
+  GCRL_CHECK_ARG(episodes >= 1, "%s: episodes: %d (>= 1 required)", who, episodes);
+  GCRL_CHECK_ARG(env->device == a->cfg.device, "%s: env: it lives on device %d, the agent on device %d", who, env->device, a->cfg.device);
+  GCRL_CHECK_ARG(env->N <= a->B, "%s: env: %d envs exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, env->N, a->B);
+  GCRL_CHECK_ARG(env->D + kEnvG == a->S && kEnvA == a->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the agent has state_dim %d / action_dim %d", who,
+                 env->D, kEnvG, kEnvA, a->S, a->A);
+  TRY(act_dev_check(a, nz_obs, nz_dg, env->D, env->N, eval_mode, who));
+  const int N = env->N;
+  if (!reset)
+    for (int i = 0; i < N; ++i)
+      if (env->t_host[i] != 0)
+        return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d is at step %d of its episode; reset == 0 scores whole episodes only", who, i, env->t_host[i]);
+  hipStream_t st = a->pick(stream);
+  void* sarg = stream ? stream : (void*)a->stream;
+  ColBufs cb;
+  TRY(col_bufs(a, &cb));
+  const size_t cn_b = (size_t)N * 3 * sizeof(unsigned long long), rs_b = (size_t)N * sizeof(double);
+  if (reset) {
+    TRY(gcrl_env_reset(env, nullptr, sarg));
+  } else {   // the counters as they stand, kept on the device: the call's one synchronisation comes at its end
+    if (!a->eval_snap) GCRL_HIP(hipMalloc((void**)&a->eval_snap, (size_t)kEnvMaxN * (3 * sizeof(unsigned long long) + sizeof(double))));
+    GCRL_HIP(hipMemcpyAsync(a->eval_snap, env->cnt, cn_b, hipMemcpyDeviceToDevice, st));
+    GCRL_HIP(hipMemcpyAsync(a->eval_snap + cn_b, env->rsum, rs_b, hipMemcpyDeviceToDevice, st));
+  }
+  const int rounds = (episodes + N - 1) / N;
+  long long launches = 0;
+  for (int s = 0; s < rounds * env->T; ++s) {
+    TRY(act_dev_launch(a, nz_obs, nz_dg, env->rows, env->D, N, nullptr, nullptr, eval_mode, cb.out64, st, &launches));
+    TRY(gcrl::env_step_launch(env, cb.out64, 1, st));
+  }
+  std::vector<unsigned long long> cn0((size_t)N * 3, 0ull), cn1((size_t)N * 3);
+  std::vector<double> rs0((size_t)N, 0.0), rs1((size_t)N);
+  if (!reset) {
+    GCRL_HIP(hipMemcpyAsync(cn0.data(), a->eval_snap, cn_b, hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipMemcpyAsync(rs0.data(), a->eval_snap + cn_b, rs_b, hipMemcpyDeviceToHost, st));
+  }
+  GCRL_HIP(hipMemcpyAsync(cn1.data(), env->cnt, cn_b, hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipMemcpyAsync(rs1.data(), env->rsum, rs_b, hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipStreamSynchronize(st));
+  int64_t ep = 0, su = 0; double r1 = 0.0, r0 = 0.0;
+  for (int i = 0; i < N; ++i) {
+    ep += (int64_t)(cn1[(size_t)i * 3 + 1] - cn0[(size_t)i * 3 + 1]); su += (int64_t)(cn1[(size_t)i * 3 + 2] - cn0[(size_t)i * 3 + 2]);
+    r1 += rs1[i]; r0 += rs0[i];
+  }
+  if (episodes_out) *episodes_out = ep;
+  if (successes_out) *successes_out = su;
+  if (reward_sum_out) *reward_sum_out = r1 - r0;
   return GCRL_OK;
 }
 

@@ -10,7 +10,9 @@
 // TQC (gcrl_pop_create_layered): members on the layer-per-launch schedule; new forms tanh_gauss_fwd[2]_pop_kernel and tanh_gauss_bwd_pop_kernel;
 // the TD-loss launch and the single-workgroup metric launch of a step have none yet (DESIGN.md 4f).
 // The acting side (one launch per vector-env step for all members): gcrl_pop_observe_act (row-chain actors), gcrl_pop_observe_act_bn
-// (SAC's BatchNorm actors), gcrl_pop_process_step.
+// (SAC's BatchNorm actors), gcrl_pop_process_step.  On a gcrl_env_group (dev_env.h) the same three stages run without the host in the
+// loop: gcrl_pop_collect (acting launch, env_step_pop_kernel, device-block process-step: three launches per vector step for all
+// members) and gcrl_pop_evaluate (acting launch in eval mode, env step).
 //
 // Admission (meet.h): a launch whose workgroups wait for each other is issued in its waiting form only when the WHOLE population
 // launch is resident at once; otherwise the members record the no-wait form of that stage (same bits — except SAC's slab launches, whose
@@ -42,6 +44,10 @@ struct gcrl_pop {
   PopProcStep proc;
   int64_t act_calls = 0, act_launches = 0, act_staged = 0;
   PopTabCache clone_tabs;              // device segment tables of gcrl_pop_clone (pbt_host.h CloneSeg), by content
+  // gcrl_pop_collect / gcrl_pop_evaluate on a gcrl_env_group (dev_env.h): what the loops have issued (gcrl_pop_collect_counts), and the
+  // group's counters as of the start of an evaluate call with reset == 0 (device copy)
+  int64_t col_calls = 0, col_steps = 0, col_launches = 0, col_copies = 0, col_syncs = 0;
+  char* eval_snap = nullptr;
 };
 
 namespace {
@@ -875,6 +881,267 @@ int gcrl_pop_replace(gcrl_pop* p, int32_t i, const gcrl_agent_config* cfg) {
   return gcrl_agent_init_weights(a, cfg->seed, 1);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- population collect and evaluation on a gcrl_env_group (dev_env.h)
+namespace {
+
+// what gcrl_pop_collect and gcrl_pop_evaluate share of their checks: the group against the members (field names as gcrl_agent_collect's)
+int pop_group_check(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, int eval_mode, const char* who) {
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  GCRL_CHECK_ARG(g->P == P, "%s: env: the group has %d members, the population %d", who, g->P, P);
+  GCRL_CHECK_ARG(g->device == a0->cfg.device, "%s: env: it lives on device %d, the population on device %d", who, g->device, a0->cfg.device);
+  GCRL_CHECK_ARG(g->N <= a0->B, "%s: env: %d envs per member exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, g->N, a0->B);
+  GCRL_CHECK_ARG(g->N <= kEnvMaxN, "%s: env: %d envs per member (at most %d)", who, g->N, kEnvMaxN);
+  GCRL_CHECK_ARG(g->D + kEnvG == a0->S && kEnvA == a0->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the members have state_dim %d / action_dim %d", who,
+                 g->D, kEnvG, kEnvA, a0->S, a0->A);
+  GCRL_CHECK_ARG(4 * round_up(a0->S, 4) <= 2 * kRowThreads || a0->sac || !(nz_obs || nz_dg), "%s: env: fused normalisation supports state_dim <= 128", who);
+  for (int i = 0; i < P; ++i)
+    TRY(act_dev_check(p->m[i], nz_obs ? nz_obs[i] : nullptr, nz_dg ? nz_dg[i] : nullptr, g->D, g->N, eval_mode, who));
+  return GCRL_OK;
+}
+
+// The population acting launch on the group's rows: float64 actions of the members in `live` to the group's action block.  mode: 1 with the
+// group's noise block added (SAC / TQC: its eps), else the eval mode.  After every member's last update call and on fresh weight copies,
+// as gcrl_pop_observe_act orders and rebuilds them.
+int pop_group_act(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, unsigned int live, bool explore,
+                  int eval_mode, hipStream_t st, int64_t* launches) {
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  const int N = g->N, D = g->D, S = a0->S, A = a0->A;
+  p->act_ordered.resize(P, 0);
+  for (int i = 0; i < P; ++i) {
+    gcrl_agent* a = p->m[i];
+    if (a->calls != p->act_ordered[i]) {
+      GCRL_HIP(hipStreamWaitEvent(st, a->call_ev[(a->calls - 1) % kEventRing], 0));
+      p->act_ordered[i] = a->calls;
+    }
+    if (!a0->sac && ((live >> i) & 1u) && a->wt_dirty) {
+      *launches += 1 + (a->has_target_actor ? 1 : 0) + 2 * a->C;
+      TRY(rc_rebuild_wt(a, st));
+    }
+  }
+  void* tab_dev = nullptr;
+  if (a0->sac) {
+    ActBnArgs tab[kMaxPopMembers];
+    for (int i = 0; i < P; ++i) {
+      gcrl_agent* a = p->m[i];
+      ActBnArgs& ba = tab[i];
+      std::memset(&ba, 0, sizeof(ba));
+      ba.P = a->P_actor(); ba.rmean = a->bn_rmean; ba.rvar = a->bn_rvar;
+      ba.S = S; ba.H = a->H; ba.L = a->L; ba.A = A; ba.n = N; ba.D = D;
+      ba.ldl = (std::max(S, a->H) + 3) / 4 * 4;
+      gcrl::normalizer_view(nz_obs ? nz_obs[i] : nullptr, &ba.nz_mean, &ba.nz_var, nullptr, &ba.nz_clip, &ba.nz_mode);
+      gcrl::normalizer_view(nz_dg ? nz_dg[i] : nullptr, &ba.nzg_mean, &ba.nzg_var, nullptr, &ba.nzg_clip, &ba.nzg_mode);
+    }
+    if (p->act_tabs.get(tab, sizeof(ActBnArgs) * P, st, &tab_dev)) return fail(GCRL_ERR_HIP, "gcrl_pop_collect: argument table upload failed");
+    ActBnPop c;
+    c.tab = static_cast<const ActBnArgs*>(tab_dev);
+    c.rows = g->rows; c.eps = g->noise64; c.out = g->act64; c.flags = nullptr;
+    c.seq = ++p->act_seq;
+    c.with_eps = explore ? 1 : 0; c.stride_n = g->stride_n;
+    TRY(launch_act_bn_pop(st, c, tab[0], P));
+  } else {
+    const int mode = explore ? 1 : eval_mode;
+    RowActArgs tab[kMaxPopMembers];
+    for (int i = 0; i < P; ++i) {
+      gcrl_agent* a = p->m[i];
+      RowActArgs& ra = tab[i];
+      std::memset(&ra, 0, sizeof(ra));
+      ra.actor = make_rownet(a, a->actor, a->P_actor(), 0);
+      ra.ld_obs = S; ra.out = a->dact; ra.ld_out = a->Apad;
+      ra.n = N; ra.S = S; ra.A = A; ra.ldl = a->row_ldl;
+      ra.D = D;
+      gcrl::normalizer_view(nz_obs ? nz_obs[i] : nullptr, &ra.nz_mean, &ra.nz_var, nullptr, &ra.nz_clip, &ra.nz_mode);
+      gcrl::normalizer_view(nz_dg ? nz_dg[i] : nullptr, &ra.nzg_mean, &ra.nzg_var, nullptr, &ra.nzg_clip, &ra.nzg_mode);
+      ra.post = mode == 1 ? 1 : (mode == 0 ? 2 : 3);
+    }
+    if (p->act_tabs.get(tab, sizeof(RowActArgs) * P, st, &tab_dev)) return fail(GCRL_ERR_HIP, "gcrl_pop_collect: argument table upload failed");
+    RowActPop c;
+    c.tab = static_cast<const RowActArgs*>(tab_dev);
+    c.rows = g->rows; c.noise = g->noise64; c.out = g->act64; c.flags = nullptr;
+    c.seq = ++p->act_seq;
+    c.live = live; c.noisy = explore ? live : 0u; c.stride_n = g->stride_n;
+    TRY(launch_rowchain_act_pop(st, c, P, N, a0->row_ldl, A, a0->H));
+  }
+  *launches += 1;
+  return GCRL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int32_t update_stats,
+                     gcrl_normalizer* const* nz_dg, int32_t update_goal_stats, int32_t steps, int32_t explore, int32_t eval_mode, int64_t* rows_out,
+                     void* stream) {
+  const char* who = "gcrl_pop_collect";
+  // every refusal comes before a counter, a ring slot or a draw of an exploration stream is consumed
+  GCRL_CHECK_ARG(p, "%s: pop: null handle", who);
+  GCRL_CHECK_ARG(g, "%s: env: null group handle", who);
+  GCRL_CHECK_ARG(rings, "%s: rings: null array", who);
+  GCRL_CHECK_ARG(rows_out, "%s: rows_out: null array", who);
+  GCRL_CHECK_ARG(steps >= 1, "%s: steps: %d (>= 1 required)", who, steps);
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  TRY(pop_group_check(p, g, nz_obs, nz_dg, eval_mode, who));
+  const int N = g->N;
+  for (int i = 0; i < P; ++i) {
+    gcrl_her* h = rings[i];
+    GCRL_CHECK_ARG(h, "%s: rings: member %d has no replay ring", who, i);
+    for (int j = 0; j < i; ++j)
+      GCRL_CHECK_ARG(rings[j] != h, "%s: shared_ring: members %d and %d share a replay ring; one ring and one normaliser pair cannot take the merged staging launch", who, j, i);
+    GCRL_CHECK_ARG(N <= h->cfg.nenvs, "%s: env: %d envs per member for a ring of %d episode slots (member %d)", who, N, h->cfg.nenvs, i);
+    GCRL_CHECK_ARG(g->D + kEnvG == h->S && kEnvA == h->A && kEnvG == h->G, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, member %d's ring has state_dim %d / action_dim %d / goal_dim %d",
+                   who, g->D, kEnvG, kEnvA, i, h->S, h->A, h->G);
+    GCRL_CHECK_ARG(g->T == h->cfg.flush_len, "%s: max_steps: the group's horizon %d differs from the flush length %d of member %d's ring", who, g->T, h->cfg.flush_len, i);
+    GCRL_CHECK_ARG(h->cfg.reward_kind == GCRL_REWARD_SPARSE, "%s: compute_reward: the reward kind of member %d's ring is %s; the env's reward is the built-in sparse kind", who, i,
+                   h->cfg.reward_kind == GCRL_REWARD_HOST ? "a host callback" : "dense");
+    GCRL_CHECK_ARG(std::memcmp(&g->thr, &h->cfg.reward_threshold, sizeof(float)) == 0, "%s: threshold: the group's %g differs from the %g of member %d's ring", who, g->thr,
+                   h->cfg.reward_threshold, i);
+    GCRL_CHECK_ARG(h->normalize_mode == rings[0]->normalize_mode, "%s: normalize: member %d's ring has normalize mode %d, member 0's %d", who, i, h->normalize_mode,
+                   rings[0]->normalize_mode);
+    GCRL_CHECK_ARG(!update_stats || (nz_obs && nz_obs[i]), "%s: nz_obs: update_stats without an observation normaliser (member %d)", who, i);
+    GCRL_CHECK_ARG(!update_goal_stats || (nz_dg && nz_dg[i]), "%s: nz_dg: update_goal_stats without a goal normaliser (member %d)", who, i);
+  }
+  for (int i = 0; i < P; ++i)
+    for (int e = 0; e < N; ++e)
+      if (g->t_host[(size_t)i * N + e] != rings[i]->staged[e])
+        return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d of member %d is at step %d of its episode, the member's ring has %d transitions staged for it", who, e, i,
+                          g->t_host[(size_t)i * N + e], rings[i]->staged[e]);
+  if (P == 1) {   // nothing to merge: the member's own loop on the group's one member
+    gcrl_env* v = gcrl::env_group_view(g);
+    const long long s0 = a0->col_steps, l0 = a0->col_launches;
+    const int rc = gcrl_agent_collect(a0, v, rings[0], nz_obs ? nz_obs[0] : nullptr, update_stats, nz_dg ? nz_dg[0] : nullptr, update_goal_stats, steps, explore,
+                                      eval_mode, rows_out, stream);
+    gcrl::env_group_view_done(g);
+    p->col_calls += 1; p->col_steps += a0->col_steps - s0; p->col_launches += a0->col_launches - l0;
+    return rc;
+  }
+  hipStream_t st = a0->pick(stream);
+  void* sarg = stream ? stream : (void*)a0->stream;   // one stream for all handles: the loop is stream-ordered
+  p->col_calls += 1;
+  const bool ddpg = a0->cfg.kind == GCRL_AGENT_DDPG;
+  const unsigned long long per_step = (unsigned long long)N * kEnvA;
+  int flush_mul[kMaxPopMembers];
+  for (int i = 0; i < P; ++i) { flush_mul[i] = 1 + (gcrl::her_prio_on(rings[i]) ? 1 : 0) + (gcrl::her_td_on(rings[i]) ? 1 : 0); rows_out[i] = 0; }
+  gcrl::EnvPopMember mem[kMaxPopMembers];
+  int64_t rows_step[kMaxPopMembers];
+  for (int s = 0; s < steps; ++s) {
+    unsigned int live = 0;
+    std::memset(mem, 0, sizeof(mem));
+    for (int i = 0; i < P; ++i) {
+      gcrl_agent* a = p->m[i];
+      const unsigned long long c = a->col_ctr;
+      const double scale = a->sac ? 1.0 : a->col_noise_std;
+      double* noise_i = g->noise64 + (size_t)i * g->stride_n * kEnvA;
+      const bool eps_step = explore && ddpg && a->col_epsilon > 0.0 &&
+                            (double)gcrl::hash_below(a->col_seed, kEpsStream, c, 1u << 24) * (1.0 / 16777216.0) < a->col_epsilon;
+      gcrl::EnvPopMember& em = mem[i];
+      if (eps_step) {   // the member's envs form clip(randn) themselves: no network, no fill
+        em.src = gcrl::kEnvActEps; em.eps_ctr0 = c * per_step;
+      } else {
+        live |= 1u << i;
+        if (explore && !(a->col_noise_valid && a->col_noise_env == g->token && a->col_noise_ctr == c)) {   // (a first call, or after the stream was set)
+          TRY(gcrl::normal_fill(noise_i, 1, (int)per_step, a->col_seed, c * per_step, scale, st));
+          p->col_launches += 1;
+        }
+        em.src = gcrl::kEnvActF64; em.act = g->act64 + (size_t)i * g->stride_n * kEnvA;
+      }
+      em.eps_seed = a->col_seed ^ kEpsStream;
+      em.noise_on = explore ? 1 : 0; em.noise_seed = a->col_seed; em.noise_ctr0 = (c + 1) * per_step; em.noise_scale = scale;
+    }
+    if (live) TRY(pop_group_act(p, g, nz_obs, nz_dg, live, explore != 0, eval_mode, st, &p->col_launches));
+    TRY(gcrl::env_group_step_launch(g, mem, st));
+    p->col_launches += 1;
+    for (int i = 0; i < P; ++i) {
+      gcrl_agent* a = p->m[i];
+      if (explore) { a->col_noise_valid = true; a->col_noise_env = g->token; a->col_noise_ctr = a->col_ctr + 1; }
+      a->col_ctr += 1;
+    }
+    p->col_steps += 1;
+    int64_t f0[kMaxPopMembers];
+    for (int i = 0; i < P; ++i) f0[i] = rings[i]->flush_calls;
+    const int rc = gcrl::her_process_step_pop_dev(&p->proc, P, rings, nz_obs, update_stats, nz_dg, update_goal_stats, g->data, g->stride, g->raw_floats, g->D, N,
+                                                  rows_step, sarg);
+    p->col_launches += 1;
+    for (int i = 0; i < P; ++i) p->col_launches += (rings[i]->flush_calls - f0[i]) * flush_mul[i];
+    if (rc) return rc;
+    for (int i = 0; i < P; ++i) rows_out[i] += rows_step[i];
+  }
+  return GCRL_OK;
+}
+
+int gcrl_pop_collect_counts(const gcrl_pop* p, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs) {
+  GCRL_CHECK_ARG(p, "gcrl_pop_collect_counts: pop: null handle");
+  if (calls) *calls = p->col_calls;
+  if (steps) *steps = p->col_steps;
+  if (launches) *launches = p->col_launches;
+  if (copies) *copies = p->col_copies;
+  if (syncs) *syncs = p->col_syncs;
+  return GCRL_OK;
+}
+
+int gcrl_pop_evaluate(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, int32_t episodes, int32_t reset,
+                      int32_t eval_mode, int64_t* episodes_out, int64_t* successes_out, double* reward_sum_out, void* stream) {
+  const char* who = "gcrl_pop_evaluate";
+  GCRL_CHECK_ARG(p, "%s: pop: null handle", who);
+  GCRL_CHECK_ARG(g, "%s: env: null group handle", who);
+  GCRL_CHECK_ARG(episodes >= 1, "%s: episodes: %d (>= 1 required)", who, episodes);
+  const int P = (int)p->m.size();
+  gcrl_agent* a0 = p->m[0];
+  TRY(pop_group_check(p, g, nz_obs, nz_dg, eval_mode, who));
+  const int N = g->N;
+  const size_t PN = (size_t)P * N;
+  if (!reset)
+    for (size_t e = 0; e < PN; ++e)
+      if (g->t_host[e] != 0)
+        return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d of member %d is at step %d of its episode; reset == 0 scores whole episodes only", who, (int)(e % N),
+                          (int)(e / N), g->t_host[e]);
+  hipStream_t st = a0->pick(stream);
+  void* sarg = stream ? stream : (void*)a0->stream;
+  const size_t cn_b = PN * 3 * sizeof(unsigned long long), rs_b = PN * sizeof(double);
+  if (reset) {
+    TRY(gcrl_env_group_reset(g, nullptr, sarg));
+  } else {   // the counters as they stand, kept on the device: the call's one synchronisation comes at its end
+    if (!p->eval_snap) GCRL_HIP(hipMalloc((void**)&p->eval_snap, (size_t)kMaxPopMembers * kEnvMaxN * (3 * sizeof(unsigned long long) + sizeof(double))));
+    GCRL_HIP(hipMemcpyAsync(p->eval_snap, g->cnt, cn_b, hipMemcpyDeviceToDevice, st));
+    GCRL_HIP(hipMemcpyAsync(p->eval_snap + cn_b, g->rsum, rs_b, hipMemcpyDeviceToDevice, st));
+  }
+  gcrl::EnvPopMember mem[kMaxPopMembers];
+  std::memset(mem, 0, sizeof(mem));
+  for (int i = 0; i < P; ++i) { mem[i].src = gcrl::kEnvActF64; mem[i].act = g->act64 + (size_t)i * g->stride_n * kEnvA; }
+  const int rounds = (episodes + N - 1) / N;
+  const unsigned int live = P >= 32 ? ~0u : ((1u << P) - 1u);
+  int64_t launches = 0;
+  for (int s = 0; s < rounds * g->T; ++s) {
+    TRY(pop_group_act(p, g, nz_obs, nz_dg, live, false, eval_mode, st, &launches));
+    TRY(gcrl::env_group_step_launch(g, mem, st));
+  }
+  std::vector<unsigned long long> cn0(PN * 3, 0ull), cn1(PN * 3);
+  std::vector<double> rs0(PN, 0.0), rs1(PN);
+  if (!reset) {
+    GCRL_HIP(hipMemcpyAsync(cn0.data(), p->eval_snap, cn_b, hipMemcpyDeviceToHost, st));
+    GCRL_HIP(hipMemcpyAsync(rs0.data(), p->eval_snap + cn_b, rs_b, hipMemcpyDeviceToHost, st));
+  }
+  GCRL_HIP(hipMemcpyAsync(cn1.data(), g->cnt, cn_b, hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipMemcpyAsync(rs1.data(), g->rsum, rs_b, hipMemcpyDeviceToHost, st));
+  GCRL_HIP(hipStreamSynchronize(st));
+  for (int k = 0; k < P; ++k) {
+    int64_t ep = 0, su = 0; double r1 = 0.0, r0 = 0.0;
+    for (int i = 0; i < N; ++i) {
+      const size_t e = (size_t)k * N + i;
+      ep += (int64_t)(cn1[e * 3 + 1] - cn0[e * 3 + 1]); su += (int64_t)(cn1[e * 3 + 2] - cn0[e * 3 + 2]);
+      r1 += rs1[e]; r0 += rs0[e];
+    }
+    if (episodes_out) episodes_out[k] = ep;
+    if (successes_out) successes_out[k] = su;
+    if (reward_sum_out) reward_sum_out[k] = r1 - r0;
+  }
+  return GCRL_OK;
+}
+
 void gcrl_pop_destroy(gcrl_pop* p) {
   if (!p) return;
   for (gcrl_agent* a : p->m) gcrl_agent_destroy(a);   // (synchronises the device)
@@ -884,6 +1151,7 @@ void gcrl_pop_destroy(gcrl_pop* p) {
   if (p->act_st_host) (void)hipHostFree(p->act_st_host);
   if (p->act_st_dev) (void)hipFree(p->act_st_dev);
   her_process_step_pop_release(&p->proc);
+  if (p->eval_snap) (void)hipFree(p->eval_snap);
   for (auto& kv : p->tabs) (void)hipFree(kv.second);
   delete p;
 }

@@ -39,7 +39,58 @@ struct gcrl_env {
   }
 };
 
+// A group of P x N envs in single allocations (dev_env.hip): member m IS a gcrl_env(kind, N, seeds[m], ...) — same state, counters,
+// random-number keys and arithmetic — whose blocks are slices at the strides the population kernels take (rowchain.h RowActPop,
+// act_bn.h ActBnPop, her_ring.hip her_process_step_pop_kernel).
+constexpr int kEnvGroupMaxP = 16;        // a population's member limit
+struct gcrl_env_group {
+  int kind = 0, P = 0, N = 0, T = 0, D = 0, device = 0;
+  int stride_n = 0;                      // rows per member of rows / noise64 / act64 (> N: the rows past N are never touched)
+  int stride = 0, raw_floats = 0;        // floats per member of `data`; a member's slice is raw (raw_floats) | pay [N][kEnvPayW]
+  float thr = 0.f;
+  uint64_t seeds[kEnvGroupMaxP] = {};
+  hipStream_t stream = nullptr;
+  float* state = nullptr;                // [P][N][kEnvStateW]
+  int* t = nullptr;                      // [P][N]
+  unsigned long long* cnt = nullptr;     // [P][N][3]
+  double* rsum = nullptr;                // [P][N]
+  float* rows = nullptr;                 // [P][stride_n][D + G]
+  float* data = nullptr;                 // [P][stride]
+  double* noise64 = nullptr;             // [P][stride_n][A]: the exploration noise / eps of the next vector step (the collect loop's)
+  double* act64 = nullptr;               // [P][stride_n][A]: the acting launch's float64 actions (the collect and evaluate loops')
+  void* tabs = nullptr;                  // PopTabCache (pop.h) of the step launch's member tables
+  int64_t steps[kEnvGroupMaxP] = {}, launches = 0;
+  std::vector<int32_t> t_host;           // [P][N]: host mirror of t
+  const void* token = nullptr;           // unique per group ever created (a small serial, never an address): names the group in an agent's
+                                         // record of whose noise its stream last wrote, so a later group at a reused address is not mistaken for it
+  gcrl_env* view = nullptr;              // P == 1: the one member as a gcrl_env on the group's own memory (env_group_view)
+
+  hipStream_t pick(void* s) const {
+    if (!s) return stream;
+    if (s == GCRL_STREAM_LEGACY) return (hipStream_t) nullptr;
+    return (hipStream_t)s;
+  }
+};
+
 namespace gcrl {
+
+// What env_step_pop_kernel needs of member m for one vector step.  src: where its actions come from.
+enum { kEnvActF32 = 0, kEnvActF64 = 1, kEnvActEps = 2 };
+struct EnvPopMember {
+  const void* act;                       // [N][A] float32 (kEnvActF32) or float64 (kEnvActF64); ignored for kEnvActEps
+  int src;
+  // kEnvActEps: action (i, j) = clamp(hash_normal(eps_seed, eps_ctr0 + i * A + j), -1, 1), formed by the env's own thread
+  unsigned long long eps_seed, eps_ctr0;
+  // rider: the member's noise of the NEXT vector step into its slice of the group's noise64 block (float64); noise_on == 0: none
+  int noise_on;
+  unsigned long long noise_seed, noise_ctr0; double noise_scale;
+};
+// env_step_pop_kernel on `st`: one launch for all P x N envs; m[0 .. P)
+int env_group_step_launch(gcrl_env_group* g, const EnvPopMember* m, hipStream_t st);
+// A one-member group as the gcrl_env it is: a handle on the group's own memory for the entries that take a gcrl_env (it owns nothing).
+// env_group_view_done takes the host mirror and the step count back into the group after such an entry has stepped it.
+gcrl_env* env_group_view(gcrl_env_group* g);
+void env_group_view_done(gcrl_env_group* g);
 
 // env_step_kernel on `st`: actions [N][A] as float32 (f64 == 0) or as the float64 the acting kernels write (rounded to float32 first)
 int env_step_launch(gcrl_env* e, const void* actions_dev, int f64, hipStream_t st);

@@ -13,88 +13,20 @@
 // Random numbers: u(env, episode, component) = hash_below(seed, kEnvStream + env, 8 * episode + component, 2^24) * 2^-24.  No state
 // besides the counters, so an env's episode j is the same whatever N is and whenever it is reached.
 //
-// Kernel rules: every address comes from the handle (or, for the pack and fill launches, from the caller's checked arguments);
-// an env index >= N does nothing; no atomics; no waits between workgroups; no per-thread scratch (every loop is over a constant
-// 3 and unrolled); plain vector stores only.
+// What an env's thread does on a reset and on a step lives in dev_env_body.h (env_reset_body, env_step_body): the kernels here and the
+// population kernels of dev_env_group.hip (gcrl_env_group: P x N envs in single allocations) call the same text, each on the EnvArgs of
+// one standalone env — so member m of a group IS a gcrl_env of seeds[m].
+//
+// Kernel rules: every address comes from the handle or the group's member table (or, for the pack and fill launches, from the
+// caller's checked arguments); an env index >= N — for a group: a member index >= P — does nothing; no atomics; no waits between
+// workgroups; no per-thread scratch (every loop is over a constant 3 and unrolled); plain vector stores only.
 #include "dev_env.h"
 
 #include <vector>
 
-#include "her_ring.h"   // hash_below
-#include "ops.h"        // hash_normal
+#include "dev_env_body.h"   // EnvArgs, env_reset_body, env_step_body
 
 namespace {
-
-constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
-constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
-constexpr uint32_t kEnvMagic = 0x564e4547u;   // "GENV"
-
-struct EnvArgs {
-  float* state; int* t; unsigned long long* cnt; double* rsum;
-  float* rows; float* raw; float* pay;
-  const void* act; int act_f64;
-  int restart;
-  int kind, N, T, D;
-  float thr;
-  unsigned long long seed;
-  // rider of the collect loop: the exploration noise of the NEXT vector step, A elements per env, written by the env's thread
-  void* noise; int noise_f64; unsigned long long noise_seed, noise_ctr0; double noise_scale;
-};
-
-__device__ inline float u01(unsigned long long seed, int env, unsigned long long ep, int comp) {
-  return (float)gcrl::hash_below(seed, kEnvStream + (unsigned long long)env, 8ull * ep + (unsigned long long)comp, 1u << 24) * (1.0f / 16777216.0f);
-}
-__device__ inline float spawn(float u) { return (u * 2.0f - 1.0f) * kSpawn; }
-__device__ inline float clamp_box(float x) { return fminf(fmaxf(x, -kBox), kBox); }
-
-struct EnvState { float p[3], q[3], vel[3], goal[3]; };
-
-__device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, EnvState& s) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) s.vel[c] = 0.f;
-  if (a.kind == GCRL_ENV_REACH) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { s.p[c] = spawn(u01(a.seed, i, ep, c)); s.q[c] = 0.f; s.goal[c] = spawn(u01(a.seed, i, ep, 3 + c)); }
-  } else {
-    s.q[0] = spawn(u01(a.seed, i, ep, 0)); s.q[1] = spawn(u01(a.seed, i, ep, 1)); s.q[2] = 0.f;
-    s.p[0] = spawn(u01(a.seed, i, ep, 2)); s.p[1] = spawn(u01(a.seed, i, ep, 3)); s.p[2] = kLift;
-    const float two = 2.0f * a.thr;
-    const float m = two + u01(a.seed, i, ep, 4) * (kSpawn - two);
-    s.goal[0] = u01(a.seed, i, ep, 5) < 0.5f ? s.q[0] - m : s.q[0] + m;
-    s.goal[1] = spawn(u01(a.seed, i, ep, 6));
-    s.goal[2] = 0.f;
-  }
-}
-
-__device__ inline void load_state(const EnvArgs& a, int i, EnvState& s) {
-  const float* w = a.state + (size_t)i * kEnvStateW;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { s.p[c] = w[c]; s.q[c] = w[3 + c]; s.vel[c] = w[6 + c]; s.goal[c] = w[9 + c]; }
-}
-__device__ inline void store_state(const EnvArgs& a, int i, const EnvState& s) {
-  float* w = a.state + (size_t)i * kEnvStateW;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { w[c] = s.p[c]; w[3 + c] = s.q[c]; w[6 + c] = s.vel[c]; w[9 + c] = s.goal[c]; }
-}
-// obs of state s at step count t -> o[0 .. D)
-__device__ inline void write_obs(const EnvArgs& a, const EnvState& s, int t, float* o) {
-  const float tt = (float)t / (float)a.T;
-  if (a.kind == GCRL_ENV_REACH) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.vel[c]; }
-    o[6] = tt;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; }
-    o[12] = tt;
-  }
-}
-__device__ inline void write_row(const EnvArgs& a, int i, const EnvState& s, int t) {
-  float* row = a.rows + (size_t)i * (a.D + kEnvG);
-  write_obs(a, s, t, row);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) row[a.D + c] = s.goal[c];
-}
 
 // the selection travels inside the kernel arguments (N <= 1024): one byte per env, ignored on a restart
 struct ResetArgs { EnvArgs a; unsigned char mask[kEnvMaxN]; };
@@ -103,101 +35,14 @@ __global__ __launch_bounds__(64) void env_reset_kernel(ResetArgs q) {
   const EnvArgs& a = q.a;
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= a.N) return;
-  unsigned long long* cn = a.cnt + (size_t)i * 3;
-  unsigned long long ep;
-  if (a.restart) {
-    ep = 0; cn[1] = 0; cn[2] = 0; a.rsum[i] = 0.0;
-  } else {
-    if (!q.mask[i]) return;
-    ep = cn[0] + 1;
-  }
-  cn[0] = ep;
-  EnvState s;
-  seed_env(a, i, ep, s);
-  store_state(a, i, s);
-  a.t[i] = 0;
-  write_row(a, i, s, 0);
+  if (!a.restart && !q.mask[i]) return;
+  env_reset_body(a, i);
 }
 
 __global__ __launch_bounds__(64) void env_step_kernel(EnvArgs a) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= a.N) return;
-  const int N = a.N, D = a.D;
-  EnvState s;
-  load_state(a, i, s);
-  int t = a.t[i];
-  float* obs = a.raw + (size_t)i * D;
-  float* nobs = a.raw + (size_t)N * D + (size_t)i * D;
-  float* dg = a.raw + (size_t)2 * N * D + (size_t)i * kEnvG;
-  float* ndg = dg + (size_t)N * kEnvG;
-  float* ag = ndg + (size_t)N * kEnvG;
-  float* nag = ag + (size_t)N * kEnvG;
-  float* pw = a.pay + (size_t)i * kEnvPayW;
-  write_obs(a, s, t, obs);
-  float act[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    dg[c] = s.goal[c]; ndg[c] = s.goal[c];
-    ag[c] = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
-    act[c] = a.act_f64 ? (float)static_cast<const double*>(a.act)[(size_t)i * kEnvA + c] : static_cast<const float*>(a.act)[(size_t)i * kEnvA + c];
-  }
-  float pn[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float x = act[c];
-    x = (x == x) ? x : 0.0f;                       // a NaN component counts as 0
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    s.vel[c] = kStep * x;
-    pn[c] = clamp_box(s.p[c] + s.vel[c]);
-  }
-  if (a.kind == GCRL_ENV_PUSH) {
-    float d2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { const float df = pn[c] - s.q[c]; d2 = d2 + df * df; }
-    if (d2 < kContact * kContact) {
-      s.q[0] = clamp_box(s.q[0] + (pn[0] - s.p[0]));
-      s.q[1] = clamp_box(s.q[1] + (pn[1] - s.p[1]));
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) s.p[c] = pn[c];
-  pw[0] = __int_as_float(t);
-  t += 1;
-  write_obs(a, s, t, nobs);
-  float acc = 0.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float g = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
-    nag[c] = g;
-    pw[3 + c] = act[c];
-    pw[3 + kEnvA + c] = g;
-    const float df = g - s.goal[c];
-    acc = acc + df * df;
-  }
-  const float dist = sqrtf(acc);
-  const float r = dist > a.thr ? -1.0f : -0.0f;
-  pw[1] = r; pw[2] = 0.f;
-  a.rsum[i] = a.rsum[i] + (double)r;
-  if (t == a.T) {
-    unsigned long long* cn = a.cnt + (size_t)i * 3;
-    cn[1] = cn[1] + 1;
-    if (dist < a.thr) cn[2] = cn[2] + 1;
-    const unsigned long long ep = cn[0] + 1;
-    cn[0] = ep;
-    seed_env(a, i, ep, s);
-    t = 0;
-  }
-  store_state(a, i, s);
-  a.t[i] = t;
-  write_row(a, i, s, t);
-  if (a.noise) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float z = gcrl::hash_normal(a.noise_seed, a.noise_ctr0 + (unsigned long long)i * kEnvA + c);
-      if (a.noise_f64) static_cast<double*>(a.noise)[(size_t)i * kEnvA + c] = (double)z * a.noise_scale;
-      else static_cast<float*>(a.noise)[(size_t)i * kEnvA + c] = (float)((double)z * a.noise_scale);
-    }
-  }
+  env_step_body(a, i);
 }
 
 __global__ __launch_bounds__(256) void proc_pack_kernel(gcrl::ProcPack p) {
@@ -253,8 +98,6 @@ EnvArgs base_args(gcrl_env* e) {
   a.kind = e->kind; a.N = e->N; a.T = e->T; a.D = e->D; a.thr = e->thr; a.seed = e->seed;
   return a;
 }
-
-struct EnvHeader { uint32_t magic; int32_t kind, N, T; float thr; uint32_t pad; uint64_t seed; int64_t steps; };
 
 size_t state_bytes(const gcrl_env* e) {
   return sizeof(EnvHeader) + (size_t)e->N * (kEnvStateW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +

@@ -320,5 +320,12 @@ int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, g
                          const float* actions_host, const float* rewards_host, const uint8_t* dones_host, int env0, int n,
                          int64_t* rows_out, void* stream);
 void her_process_step_pop_release(PopProcStep* ps);
+// The device-block form (gcrl_pop_collect): the same one launch on CALLER-OWNED device memory data_dev [members][stride] floats, a
+// member's slice raw (raw_floats, all six blocks) | pay [n][kPayW] (dev_env.h gcrl_env_group), then the same host bookkeeping in
+// member order.  Nothing is uploaded besides the cached table and nothing is waited for.  The payloads' t words must be
+// the rings' staged counts: the caller checks its host mirror of them against every ring BEFORE the first step is issued.
+int her_process_step_pop_dev(PopProcStep* ps, int members, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int update_stats,
+                             gcrl_normalizer* const* nz_dg, int update_goal_stats, const float* data_dev, int stride, int raw_floats, int obs_dim,
+                             int n, int64_t* rows_out, void* stream);
 
 }  // namespace gcrl

@@ -1680,6 +1680,58 @@ int her_process_step_pop(PopProcStep* ps, int members, gcrl_her* const* rings, g
   return GCRL_OK;
 }
 
+int her_process_step_pop_dev(PopProcStep* ps, int members, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int update_stats,
+                             gcrl_normalizer* const* nz_dg, int update_goal_stats, const float* data_dev, int stride, int raw_floats, int obs_dim,
+                             int n, int64_t* rows_out, void* stream) {
+  const int P = members;
+  GCRL_CHECK_ARG(P >= 1 && P <= 32 && data_dev && rows_out, "gcrl_pop_collect: process-step: bad arguments");
+  gcrl_her* h0 = rings[0];
+  hipStream_t st = h0->pick(stream);
+  if (!ps->tabs) ps->tabs = new PopTabCache;
+  ps->calls++;
+  ProcArgs tab[32];
+  for (int i = 0; i < P; ++i) {
+    gcrl_her* h = rings[i];
+    ProcArgs& pa = tab[i];
+    std::memset(&pa, 0, sizeof(pa));
+    pa.stage = h->stage;
+    gcrl_normalizer* zo = nz_obs ? nz_obs[i] : nullptr;
+    gcrl_normalizer* zg = nz_dg ? nz_dg[i] : nullptr;
+    const double *mean = nullptr, *var = nullptr;
+    gcrl::normalizer_view(zo, &mean, &var, &pa.count, &pa.clip, &pa.mode);
+    pa.mean = const_cast<double*>(mean); pa.var = const_cast<double*>(var);
+    pa.update = (zo && update_stats) ? 1 : 0;
+    if (zg) {
+      const double *gm = nullptr, *gv = nullptr;
+      gcrl::normalizer_view(zg, &gm, &gv, &pa.gcount, &pa.gclip, &pa.gmode);
+      pa.gmean = const_cast<double*>(gm); pa.gvar = const_cast<double*>(gv);
+      pa.gupdate = update_goal_stats ? 1 : 0;
+    }
+    pa.n = n; pa.env0 = 0; pa.flush_len = h->cfg.flush_len; pa.D = obs_dim; pa.S = h->S; pa.A = h->A; pa.G = h->G;
+    pa.SA4 = h->SA4; pa.S4 = h->S4; pa.RG = h->RG;
+  }
+  void* tab_dev = nullptr;
+  if (static_cast<PopTabCache*>(ps->tabs)->get(tab, sizeof(ProcArgs) * P, st, &tab_dev)) return gcrl::fail(GCRL_ERR_HIP, "gcrl_pop_collect: argument table upload failed");
+  if (her_norm_on(h0)) {   // raw rings: the raw-store form of the launch (her_norm.hip)
+    if (int rc = her_process_step_raw_pop(static_cast<const ProcRawArgs*>(tab_dev), data_dev, stride, raw_floats, P, st)) return rc;
+  } else hipLaunchKernelGGL(her_process_step_pop_kernel, dim3(P), dim3(256), 0, st, static_cast<const ProcArgs*>(tab_dev), data_dev, stride, raw_floats);
+  GCRL_HIP(hipGetLastError());
+  ps->launches++;
+  for (int i = 0; i < P; ++i) {
+    if (tab[i].update) gcrl::normalizer_updated(nz_obs[i]);
+    if (tab[i].gupdate) gcrl::normalizer_updated(nz_dg[i]);
+  }
+  // the flushes stay per member, in member order (her_process_step_pop): the relabelling draws are consumed in that order
+  static thread_local std::vector<uint8_t> none;   // (no env terminated: episodes end when flush_len rows are staged)
+  none.assign((size_t)n, 0);
+  for (int i = 0; i < P; ++i) {
+    const int64_t r = finish_vector_step(rings[i], 0, n, none.data(), st);
+    rows_out[i] = r;
+    if (r < 0) return (int)r;
+  }
+  return GCRL_OK;
+}
+
 void her_process_step_pop_release(PopProcStep* ps) {
   if (!ps) return;
   if (ps->blk_host) (void)hipHostFree(ps->blk_host);

@@ -949,7 +949,7 @@ class _EngineAgent:
         appended.  Refusals name their field and come before anything is consumed (include/gcrl.h gcrl_agent_collect)."""
         who = f"{type(self).__name__}.collect"
         if getattr(self, "_owner", None) is not None:
-            raise _ffi.GcrlError(f"{who}: collect: a population member acts through its population's entries; the population forms of collect are not built")
+            raise _ffi.GcrlError(f"{who}: collect: a population member acts through its population's entries: call pop.collect(group, steps) with a DeviceGoalEnvGroup")
         if getattr(self, "_dp_driven", False):
             raise _ffi.GcrlError(f"{who}: collect: an agent driven by a DataParallelUpdater does not collect (the data-parallel form is not built)")
         from .device_env import DeviceGoalEnv
@@ -975,6 +975,32 @@ class _EngineAgent:
         _ffi.check(rc)
         buf._check_rows(int(rows.value))
         return int(rows.value)
+
+    def evaluate(self, env, episodes: int, reset: bool = True, obs_normalize: bool = True, g_normalize: bool = False) -> dict:
+        """Deterministic evaluation on a `DeviceGoalEnv` as ONE native call: ceil(episodes / N) * max_steps vector steps of the acting
+        launch in eval mode (`observe_act(eval_action=True)`) and the env's step — no ring, no process-step; the normalisers are read
+        and never updated, the exploration stream does not move.  `reset=True` resets the env first, so the call scores episodes 0, 1, ...
+        of the env's seed (a fixed evaluation set); `reset=False` needs every env at the start of an episode (refused by `t` otherwise)
+        and reports the counters' difference over the call.  Synchronises once, at the end.  Returns dict(episodes, successes,
+        success_rate, reward_sum); `episodes` is what was run, a multiple of N (include/gcrl.h gcrl_agent_evaluate)."""
+        who = f"{type(self).__name__}.evaluate"
+        from .device_env import DeviceGoalEnv
+        if not isinstance(env, DeviceGoalEnv):
+            raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnv required")
+        if int(episodes) < 1:
+            raise ValueError(f"{who}: episodes: {episodes} (>= 1 required)")
+        self._check_normalize_call("evaluate", obs_normalize, g_normalize)
+        nz = self._dev_normalizers("evaluate", obs_normalize, g_normalize)
+        if env.obs_dim + env.goal_dim != self.obs_dim or env.ac_dim != self.ac_dim:
+            raise ValueError(f"{who}: env: obs_dim {env.obs_dim} + goal_dim {env.goal_dim} / ac_dim {env.ac_dim} differ from the agent's "
+                             f"state_dim {self.obs_dim} / ac_dim {self.ac_dim}")
+        self.set_eval()
+        self._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+        ep, su, rs = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        _ffi.check(lib.gcrl_agent_evaluate(self._h, env.handle, nz[0], nz[1], int(episodes), 1 if reset else 0, 2 if self._sac else self._ACT_MODE_EVAL,
+                                           C.byref(ep), C.byref(su), C.byref(rs), _ffi.stream_handle()))
+        n = int(ep.value)
+        return dict(episodes=n, successes=int(su.value), success_rate=int(su.value) / n if n else 0.0, reward_sum=float(rs.value))
 
     def collect_counts(self) -> dict:
         """What `collect` (and `observe_act_dev`) have issued since this agent was created: calls and vector steps of `collect`, kernel

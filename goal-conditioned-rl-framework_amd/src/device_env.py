@@ -26,6 +26,150 @@ class _DevBlock:
         self.__cuda_array_interface__ = {"shape": (int(numel),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
 
 
+class _DevBlock64(_DevBlock):
+    """The same for a float64 block."""
+
+    def __init__(self, ptr: int, numel: int):
+        super().__init__(ptr, numel)
+        self.__cuda_array_interface__["typestr"] = "<f8"
+
+
+class DeviceGoalEnvGroup:
+    """`members` x `num_envs` envs in single allocations for a population (`pop.collect(group, steps)`, `pop.evaluate(group, episodes)`).
+    Member m IS a `DeviceGoalEnv(kind, num_envs, seeds[m], ...)` — the same state, counters, random-number keys and arithmetic — whose
+    blocks are slices at the strides the population kernels read.  One launch steps or resets all members."""
+
+    HEADER_BYTES = 24           # of the group's state blob; the members' records follow, each a standalone env's blob
+
+    def __init__(self, kind: str, members: int, num_envs: int, seeds, max_steps: int = 50, threshold: float = 0.05, device_index: int = 0):
+        if kind not in KINDS:
+            raise ValueError(f"DeviceGoalEnvGroup: kind: {kind!r} (one of {sorted(KINDS)})")
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if len(seeds) != int(members):
+            raise ValueError(f"DeviceGoalEnvGroup: seeds: {len(seeds)} seeds for {members} members")
+        self.kind, self.device_index = kind, int(device_index)
+        arr = (C.c_uint64 * max(1, len(seeds)))(*seeds)
+        self._h = _ffi.check_ptr(lib.gcrl_env_group_create(KINDS[kind], int(members), int(num_envs), arr, int(max_steps), float(threshold),
+                                                           self.device_index), "gcrl_env_group_create")
+        ints = [C.c_int() for _ in range(7)]
+        thr, tail = C.c_float(), [C.c_int() for _ in range(3)]
+        _ffi.check(lib.gcrl_env_group_dims(self._h, *[C.byref(x) for x in ints], C.byref(thr), None, *[C.byref(x) for x in tail]))
+        _, self.members, self.num_envs, self.obs_dim, self.goal_dim, self.ac_dim, self.max_steps = (int(x.value) for x in ints)
+        self.stride_n, self.stride, self.raw_floats = (int(x.value) for x in tail)
+        self.threshold = float(thr.value)
+        self._views = None
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.gcrl_env_group_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def seeds(self):
+        sd = (C.c_uint64 * self.members)()
+        _ffi.check(lib.gcrl_env_group_dims(self._h, None, None, None, None, None, None, None, None, sd, None, None, None))
+        return [int(x) for x in sd]
+
+    # ------------------------------------------------------------------ views of the handle's device blocks
+    def _blocks(self):
+        if self._views is None:
+            p = [C.c_void_p() for _ in range(4)]
+            _ffi.check(lib.gcrl_env_group_buffers(self._h, *[C.byref(x) for x in p]))
+            P, sn, W, A = self.members, self.stride_n, self.obs_dim + self.goal_dim, self.ac_dim
+            dev = f"cuda:{self.device_index}"
+            self._views = (torch.as_tensor(_DevBlock(p[0].value, P * sn * W), device=dev).view(P, sn, W),
+                           torch.as_tensor(_DevBlock(p[1].value, P * self.stride), device=dev).view(P, self.stride),
+                           torch.as_tensor(_DevBlock64(p[2].value, P * sn * A), device=dev).view(P, sn, A),
+                           torch.as_tensor(_DevBlock64(p[3].value, P * sn * A), device=dev).view(P, sn, A))
+        return self._views
+
+    def padded_blocks(self):
+        """(rows [P, stride_n, W], data [P, stride], noise64 [P, stride_n, A], act64 [P, stride_n, A]): the whole allocations, the rows
+        and floats past each member's share included (they are never read and never written)."""
+        return self._blocks()
+
+    def acting_rows(self):
+        """As `DeviceGoalEnv.acting_rows()` with a leading member dimension: views [P, N, .] of the group's memory."""
+        rows = self._blocks()[0][:, :self.num_envs]
+        return {"rows": rows, "observation": rows[:, :, :self.obs_dim], "desired_goal": rows[:, :, self.obs_dim:]}
+
+    def step_blocks(self):
+        """(raw [P, raw_floats], pay [P, N, 32]) of the LAST step: member m's slices as `DeviceGoalEnv.step_blocks()` lays them out."""
+        data = self._blocks()[1]
+        n = self.num_envs
+        return data[:, :self.raw_floats], data[:, self.raw_floats:self.raw_floats + n * PAY_W].unflatten(1, (n, PAY_W))
+
+    # ------------------------------------------------------------------ stepping by hand
+    def reset(self, mask=None, members=None):
+        """Nothing given: every env of every member back to its episode 0 and the counters to zero.  mask [P, N] bool (host): those envs go
+        on to their next episode; members=[...]: every env of those members does.  One launch."""
+        m = None
+        if members is not None:
+            if mask is not None:
+                raise ValueError("DeviceGoalEnvGroup.reset: mask: give a mask or members, not both")
+            m = np.zeros((self.members, self.num_envs), np.uint8)
+            for k in members:
+                if not 0 <= int(k) < self.members:
+                    raise ValueError(f"DeviceGoalEnvGroup.reset: members: {k} outside [0, {self.members})")
+                m[int(k)] = 1
+        elif mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1), np.uint8)
+            if m.size != self.members * self.num_envs:
+                raise ValueError(f"DeviceGoalEnvGroup.reset: mask: {m.size} entries for {self.members} x {self.num_envs} envs")
+        _ffi.check(lib.gcrl_env_group_reset(self._h, m.ctypes.data if m is not None else None, _ffi.stream_handle()))
+        return self.acting_rows()
+
+    def step(self, actions, eps=None):
+        """One vector step of every member from a CUDA float32 or float64 tensor [P, N, 3], one launch.  eps: {member: (seed, counter0)} —
+        those members' envs form their own actions clamp(hash_normal(seed, counter0 + env * 3 + component), -1, 1) (the epsilon step of
+        a DDPG collect) and their slice of `actions` is not read."""
+        shape = (self.members, self.num_envs, self.ac_dim)
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.is_contiguous() and actions.dtype in (torch.float32, torch.float64)
+                and tuple(actions.shape) == shape):
+            raise ValueError(f"DeviceGoalEnvGroup.step: actions: a contiguous CUDA float32 / float64 tensor {list(shape)} required")
+        sel = sd = ct = None
+        if eps:
+            sel, sd, ct = np.zeros(self.members, np.uint8), np.zeros(self.members, np.uint64), np.zeros(self.members, np.uint64)
+            for k, (seed, ctr0) in eps.items():
+                if not 0 <= int(k) < self.members:
+                    raise ValueError(f"DeviceGoalEnvGroup.step: eps: member {k} outside [0, {self.members})")
+                sel[int(k)], sd[int(k)], ct[int(k)] = 1, int(seed) & (2**64 - 1), int(ctr0) & (2**64 - 1)
+        _ffi.check(lib.gcrl_env_group_step(self._h, actions.data_ptr(), 1 if actions.dtype == torch.float64 else 0,
+                                           sel.ctypes.data if sel is not None else None, sd.ctypes.data if sel is not None else None,
+                                           ct.ctypes.data if sel is not None else None, _ffi.stream_handle()))
+
+    def stats(self) -> list:
+        """Synchronises once.  One dict per member: what `DeviceGoalEnv.stats()` reports for it."""
+        P = self.members
+        ep, su, rs = (C.c_int64 * P)(), (C.c_int64 * P)(), (C.c_double * P)()
+        _ffi.check(lib.gcrl_env_group_stats(self._h, ep, su, rs, _ffi.stream_handle()))
+        return [dict(episodes=int(ep[k]), successes=int(su[k]), reward_sum=float(rs[k])) for k in range(P)]
+
+    # ------------------------------------------------------------------ resume
+    def save_state(self) -> np.ndarray:
+        n = int(lib.gcrl_env_group_state_bytes(self._h))
+        blob = np.empty(n, np.uint8)
+        _ffi.check(lib.gcrl_env_group_save_state(self._h, blob.ctypes.data, n, _ffi.stream_handle()))
+        return blob
+
+    def load_state(self, blob):
+        """Refuses a state of other members, kind, num_envs, max_steps or threshold by that field's name before anything is overwritten."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        _ffi.check(lib.gcrl_env_group_load_state(self._h, blob.ctypes.data, blob.size, _ffi.stream_handle()))
+
+    def member_state(self, m: int) -> np.ndarray:
+        """The blob a standalone `DeviceGoalEnv` in member m's state would save, byte for byte."""
+        if not 0 <= int(m) < self.members:
+            raise ValueError(f"DeviceGoalEnvGroup.member_state: members: {m} outside [0, {self.members})")
+        blob = self.save_state()
+        per = (blob.size - self.HEADER_BYTES) // self.members
+        return blob[self.HEADER_BYTES + int(m) * per:self.HEADER_BYTES + (int(m) + 1) * per].copy()
+
+
 class DeviceGoalEnv:
     def __init__(self, kind: str, num_envs: int, seed: int = 0, max_steps: int = 50, threshold: float = 0.05, device_index: int = 0):
         if kind not in KINDS:

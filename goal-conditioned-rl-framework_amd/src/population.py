@@ -10,7 +10,8 @@ forms `forms()` reports).
 `update_many` on the member alone); `update_many(step0, n)` steps all of them and returns, per member, what the agent's own
 `update_many` returns.  `observe_act` / `process_step` are the members' fused acting entries for all members at once: one launch
 per call (gcrl_pop_observe_act — SAC's BatchNorm actors: gcrl_pop_observe_act_bn —, gcrl_pop_process_step), the host generators
-consumed in member order.
+consumed in member order.  `collect(group, steps)` / `evaluate(group, episodes)` run the same stages on a `DeviceGoalEnvGroup` as one
+native call each, with nothing crossing to the host between the launches (gcrl_pop_collect, gcrl_pop_evaluate).
 """
 from __future__ import annotations
 
@@ -398,6 +399,89 @@ class _Population:
         for r in streams:
             r.push_back()
         return [int(x) for x in arr["rows"]]
+
+    # ------------------------------------------------------------------ device-resident collect and evaluation (DeviceGoalEnvGroup)
+    def _group_call(self, name: str, group, obs_normalize: bool, g_normalize: bool, need_device: bool):
+        """What `collect` and `evaluate` check and gather before their native call: the group, the members' device normalisers."""
+        who = f"{type(self).__name__}.{name}"
+        from .device_env import DeviceGoalEnvGroup
+        if not isinstance(group, DeviceGoalEnvGroup):
+            raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnvGroup required")
+        ms = self.members
+        P = len(ms)
+        if group.members != P:
+            raise ValueError(f"{who}: env: the group has {group.members} members, the population {P}")
+        for i, m in enumerate(ms):
+            if getattr(m, "_dp_driven", False):
+                raise _ffi.GcrlError(f"{who}: {name}: member {i} is driven by a DataParallelUpdater (the data-parallel form is not built)")
+        if group.obs_dim + group.goal_dim != ms[0].obs_dim or group.ac_dim != ms[0].ac_dim:
+            raise ValueError(f"{who}: env: obs_dim {group.obs_dim} + goal_dim {group.goal_dim} / ac_dim {group.ac_dim} differ from the members' "
+                             f"state_dim {ms[0].obs_dim} / ac_dim {ms[0].ac_dim}")
+        nzo, nzg = (C.c_void_p * P)(), (C.c_void_p * P)()
+        for i, m in enumerate(ms):
+            m._check_normalize_call(name, obs_normalize, g_normalize, need_device=need_device)
+            nzo[i], nzg[i] = m._dev_normalizers(name, obs_normalize, g_normalize)
+        return who, nzo, nzg
+
+    def collect(self, group, steps: int, explore: bool = True, obs_normalize: bool = True, g_normalize: bool = False):
+        """`members[m].collect(env_m, steps)` for every member on a `DeviceGoalEnvGroup` as ONE native call: per vector step one acting
+        launch, one env-step launch and one process-step launch for ALL members, plus the rings' flush launches in member order — no
+        host <-> device copy and no synchronisation.  Each member keeps its own exploration stream (`set_collect_stream` on the
+        member) and leaves what a standalone agent's `collect` on `DeviceGoalEnv(kind, N, seeds[m])` leaves, bit for bit.  Returns the
+        ring rows appended per member.  Refusals name their field and come before anything is consumed (include/gcrl.h
+        gcrl_pop_collect); a population with `shared_ring` is refused."""
+        if self.shared_ring:
+            self._refuse("shared_ring", "collect is not built for a shared ring: one ring and one normaliser pair cannot take the merged staging launch")
+        who, nzo, nzg = self._group_call("collect", group, obs_normalize, g_normalize, True)
+        if int(steps) < 1:
+            raise ValueError(f"{who}: steps: {steps} (>= 1 required)")
+        ms = self.members
+        P = len(ms)
+        rings = (C.c_void_p * P)()
+        for i, m in enumerate(ms):
+            m.buffer._ensure(group.obs_dim + group.goal_dim, group.ac_dim, group.goal_dim)
+            m._collect_stream()
+            m.set_eval()
+            m._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+            rings[i] = m.buffer.handle
+        rows = (C.c_int64 * P)()
+        streams = list({id(m.buffer.rng): m.buffer.rng for m in ms}.values())   # (python mode: the one shared stream)
+        for r in streams:
+            r.pull()
+        rc = lib.gcrl_pop_collect(self._pop.h, group.handle, rings, nzo, 1 if obs_normalize else 0, nzg, 1 if g_normalize else 0, int(steps),
+                                  1 if explore else 0, 2 if ms[0]._sac else ms[0]._ACT_MODE_EVAL, rows, _ffi.stream_handle())
+        for r in streams:
+            r.push_back()
+        _ffi.check(rc)
+        for m in ms:
+            m.buffer._check_rows(0)
+        return [int(x) for x in rows]
+
+    def collect_counts(self) -> dict:
+        """What `collect` has issued since the population was created: calls, vector steps, kernel launches, host <-> device copies and
+        stream synchronisations (include/gcrl.h gcrl_pop_collect_counts)."""
+        v = [C.c_int64(0) for _ in range(5)]
+        _ffi.check(lib.gcrl_pop_collect_counts(self._pop.h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "steps", "launches", "copies", "syncs"), (int(x.value) for x in v)))
+
+    def evaluate(self, group, episodes: int, reset: bool = True, obs_normalize: bool = True, g_normalize: bool = False):
+        """`members[m].evaluate(env_m, episodes, ...)` for every member on a `DeviceGoalEnvGroup` as ONE native call: two launches per
+        vector step for ALL members (the acting launch in eval mode, the env step), one synchronisation at the end.  Nothing is pushed,
+        no normaliser is updated, no exploration stream moves.  Returns one dict(episodes, successes, success_rate, reward_sum) per
+        member; a group whose members share a seed ranks them on identical episodes (include/gcrl.h gcrl_pop_evaluate)."""
+        who, nzo, nzg = self._group_call("evaluate", group, obs_normalize, g_normalize, False)
+        if int(episodes) < 1:
+            raise ValueError(f"{who}: episodes: {episodes} (>= 1 required)")
+        ms = self.members
+        P = len(ms)
+        for m in ms:
+            m.set_eval()
+            m._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
+        ep, su, rs = (C.c_int64 * P)(), (C.c_int64 * P)(), (C.c_double * P)()
+        _ffi.check(lib.gcrl_pop_evaluate(self._pop.h, group.handle, nzo, nzg, int(episodes), 1 if reset else 0,
+                                         2 if ms[0]._sac else ms[0]._ACT_MODE_EVAL, ep, su, rs, _ffi.stream_handle()))
+        return [dict(episodes=int(ep[k]), successes=int(su[k]), success_rate=int(su[k]) / int(ep[k]) if ep[k] else 0.0, reward_sum=float(rs[k]))
+                for k in range(P)]
 
     def acting_counts(self):
         """(act_calls, act_launches, proc_calls, proc_launches, act_staged): native calls of `observe_act` / `process_step` and the

@@ -1182,6 +1182,75 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
  * from the flush's definition — one per flush group, plus one per priority tree it seeds).  Any pointer may be NULL. */
 int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs);
 
+/* ------------------------------------------------------------------------------------------
+ * Environment groups, population collect and on-device evaluation.  Nothing here has a counterpart in the reference beyond its
+ * trainer's test(path, num_episodes), which reports a success rate from a host loop.
+ *
+ * gcrl_env_group (csrc/dev_env_group.hip): members x num_envs envs in single allocations.  Member m IS a gcrl_env(kind, num_envs, seeds[m], ...): the same
+ * state, counters, random-number keys and arithmetic (one step body, csrc/dev_env_body.h, shared by env_step_kernel and env_step_pop_kernel; the
+ * definition stays tests/dev_env_ref.py, instantiated once per member).  The members' blocks are slices at the strides the
+ * population kernels take: acting rows [members][stride_n][obs_dim + 3], step data [members][stride] floats with a member's slice
+ * raw (raw_floats) | pay [num_envs][32], float64 noise / eps and float64 actions [members][stride_n][3].  stride_n > num_envs: the
+ * rows past num_envs of a slice are never read and never written.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct gcrl_env_group gcrl_env_group;
+/* members 1..16, seeds[members]; the other arguments as gcrl_env_create.  Every env starts at its episode 0. */
+gcrl_env_group* gcrl_env_group_create(int kind, int members, int num_envs, const uint64_t* seeds, int max_steps, float threshold, int device);
+void gcrl_env_group_destroy(gcrl_env_group* g);
+/* Any pointer may be NULL.  seeds_out[members]. */
+int gcrl_env_group_dims(const gcrl_env_group* g, int* kind, int* members, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps,
+                        float* threshold, uint64_t* seeds_out, int* stride_n, int* stride, int* raw_floats);
+/* Device addresses of the group's blocks in the layout above. */
+int gcrl_env_group_buffers(gcrl_env_group* g, float** rows, float** data, double** noise64, double** act64);
+/* One launch (env_reset_pop_kernel).  mask_host NULL: every env of every member back to its episode 0, the counters to zero.  Else
+ * members x num_envs bytes: the selected envs go on to their next episode (not counted as finished). */
+int gcrl_env_group_reset(gcrl_env_group* g, const uint8_t* mask_host, void* stream);
+/* One vector step of every member, one launch (env_step_pop_kernel): actions_dev [members][num_envs][3], float32 or float64.
+ * eps_members NULL, or one byte per member: a selected member's envs form their own actions,
+ * clamp(hash_normal(eps_seeds[m], eps_ctr0[m] + env * 3 + component), -1, 1), and its slice of actions_dev is not read
+ * (actions_dev may be NULL when every member is selected). */
+int gcrl_env_group_step(gcrl_env_group* g, const void* actions_dev, int actions_f64, const uint8_t* eps_members, const uint64_t* eps_seeds,
+                        const uint64_t* eps_ctr0, void* stream);
+/* Synchronises once.  Per member, what gcrl_env_stats reports for it: episodes[members], successes[members], reward_sum[members]. */
+int gcrl_env_group_stats(gcrl_env_group* g, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream);
+/* The blob is a 24-byte group header followed by one record per member, each byte for byte what gcrl_env_save_state writes for a
+ * standalone env in that member's state; resume is bitwise.  Loading refuses other members, kind, num_envs, max_steps or threshold
+ * by that field's name before anything is overwritten. */
+int64_t gcrl_env_group_state_bytes(const gcrl_env_group* g);
+int gcrl_env_group_save_state(gcrl_env_group* g, void* dst_host, int64_t n, void* stream);
+int gcrl_env_group_load_state(gcrl_env_group* g, const void* src_host, int64_t n, void* stream);
+/* Deterministic evaluation: ceil(episodes / N) * max_steps vector steps of the acting launch in mode eval_mode (gcrl_agent_observe_act's
+ * mode 0 or 2 for DDPG / TD3, 2 for SAC / TQC: tanh(mean)) followed by the env's step — two launches a step, no ring, no process-step;
+ * the normalisers are read and never updated and the exploration stream does not move.  reset != 0: gcrl_env_reset(env, NULL) first,
+ * so the call scores episodes 0, 1, ... of the env's seed.  reset == 0: every env must stand at step 0 of an episode (else
+ * GCRL_ERR_STATE naming `t`); the result is the counters' difference over the call.  One synchronisation, at the end.  *episodes_out
+ * (a multiple of N: what was run), *successes_out, *reward_sum_out.  Refused by field name before anything is launched: env
+ * (more envs than batch_size, other dimensions, another device), episodes (< 1), nz_obs / nz_dg (sizes), t. */
+int gcrl_agent_evaluate(gcrl_agent* a, gcrl_env* env, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, int episodes, int reset, int eval_mode,
+                        int64_t* episodes_out, int64_t* successes_out, double* reward_sum_out, void* stream);
+/* gcrl_agent_collect for all members of a population on a group, as a native loop; per vector step, in stream order, ONE launch each
+ * for all members: (a) the population acting launch on the group's rows (after each member's last update call and its weight-copy
+ * rebuild where due; a DDPG member on its epsilon branch is not in it, and with every member there the launch is not issued),
+ * (b) env_step_pop_kernel, which reads the float64 actions, forms an epsilon member's actions itself and leaves each member's noise of
+ * its NEXT vector step, (c) the population process-step launch on the group's blocks, followed by the rings' flush launches in member
+ * order.  No host <-> device copy and no synchronisation.  Each member keeps its own exploration stream (gcrl_agent_collect_set; element
+ * (c, i, j) with N = envs per member) and its counter; a first call, or a re-keyed stream, pays one fill launch per member concerned.
+ * Member m then holds, bit for bit, what a standalone agent's gcrl_agent_collect on gcrl_env(seeds[m]) leaves.  A one-member
+ * population hands the call to the member's own gcrl_agent_collect.  rows_out[members]: ring rows appended per member.
+ * Refused by field name before anything is consumed: env (null; members != the population's; more envs per member than ring slots,
+ * batch_size or 1024; dimensions; device), max_steps, threshold, compute_reward, steps, nz_obs / nz_dg, normalize, t (naming the
+ * member and the env), shared_ring (two members with one ring). */
+int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcrl_normalizer* const* nz_obs, int32_t update_stats,
+                     gcrl_normalizer* const* nz_dg, int32_t update_goal_stats, int32_t steps, int32_t explore, int32_t eval_mode, int64_t* rows_out,
+                     void* stream);
+/* what gcrl_pop_collect has issued since creation, counted as gcrl_agent_collect_counts counts.  Any pointer may be NULL. */
+int gcrl_pop_collect_counts(const gcrl_pop* p, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs);
+/* gcrl_agent_evaluate for all members on a group: the population acting launch in eval mode and env_step_pop_kernel, two launches a
+ * step for all members, one synchronisation at the end; episodes_out / successes_out / reward_sum_out [members].  reset != 0 resets
+ * the whole group first.  Refusals as gcrl_agent_evaluate's, `env` also for a group of another member count. */
+int gcrl_pop_evaluate(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, int32_t episodes, int32_t reset,
+                      int32_t eval_mode, int64_t* episodes_out, int64_t* successes_out, double* reward_sum_out, void* stream);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);

@@ -10,6 +10,10 @@ N in {8, 32, 256} envs.  Path (i) is what the parent commit can do: observe_act 
 (tests/dev_env_ref.py) + process_step per vector step; its env time is Python's and is reported separately, measured here.  Path
 (ii) is agent.collect.  Alternating in one process, seven samples each between two device synchronisations; prints env-steps/s of
 both, median and range.
+--members P [P ...]: a DDPG population of P members at the same network on a DeviceGoalEnvGroup, N in {8, 32} envs per member: aggregate
+env-steps/s of pop.collect (three launches per vector step for all members) against the same P standalone agents' own collect calls
+issued one after another (3 P launches per vector step) — what the code could do before pop.collect, measured in the same run;
+seven alternating samples.  With --run: the population's steps for the profiler; --parse then also lists the population kernels.
 --run issues, for the profiler, STEPS collect steps at every N; nothing is timed there.  --parse prints, per kernel, the launches
 after the warm-up ones: number, median, range in us.  No --pmc in that run.
 No GPU: --cost and --run fail."""
@@ -33,6 +37,76 @@ HOST_STEPS = {8: 100, 32: 50, 256: 10}        # vector steps of a host-loop samp
 DEV_STEPS = 500
 STEPS = 300
 NAMES = ("env_step_kernel", "rowchain_act_kernel", "her_process_step_kernel", "her_flush_kernel")
+POP_NS = (8, 32)
+POP_NAMES = ("env_step_pop_kernel", "rowchain_act_pop_kernel", "her_process_step_pop_kernel")
+
+
+def _normalizers(ag):
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+    from oracle import her_oracle
+    ag.buffer.obs_normalizer = DeviceRunningNormalizer(D)
+    ag.buffer.dg_normalizer = DeviceRunningNormalizer(G)
+    ag.buffer.compute_reward = her_oracle.sparse_reward
+
+
+def _population(P, n, max_len=100_000):
+    """a DDPG population on a group, and the same P agents standalone with an env each (same configs and seeds)"""
+    import gcrl_amd
+    from gcrl_amd.src.synthetic import agent_config
+    cfgs = [agent_config("DDPG", hidden_dim=H, layer_count=L, batch_size=B, max_len=max_len, k_future=4) for _ in range(P)]
+    seeds = list(range(1, P + 1))
+    pop = gcrl_amd.DDPGPopulation(D + G, A, cfgs, n, 40, rng="engine", seeds=seeds)
+    solo = [gcrl_amd.DDPG(D + G, A, c, None, nenvs=n, gradient_step=40, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
+    for ag in pop.members + solo:
+        _normalizers(ag)
+    group = gcrl_amd.DeviceGoalEnvGroup("reach", P, n, seeds, max_steps=T, threshold=THR)
+    envs = [gcrl_amd.DeviceGoalEnv("reach", n, seed=s, max_steps=T, threshold=THR) for s in seeds]
+    return pop, group, solo, envs
+
+
+def members_cost(ps, out):
+    import torch
+    lines = ["# aggregate env-steps/s of P DDPG agents (H 256 x 3, batch 256, reach dimensions), N envs each; %d alternating samples of %d vector steps" %
+             (SAMPLES, DEV_STEPS),
+             "# (i) the P standalone agents' collect calls, one after another   (ii) pop.collect on a DeviceGoalEnvGroup"]
+    for P in ps:
+        for n in POP_NS:
+            pop, group, solo, envs = _population(P, n)
+            pop.collect(group, T)
+            for ag, env in zip(solo, envs):
+                ag.collect(env, T)
+            torch.cuda.synchronize()
+            a, b = [], []
+            for _ in range(SAMPLES):
+                t0 = time.perf_counter()
+                for ag, env in zip(solo, envs):
+                    ag.collect(env, DEV_STEPS)
+                torch.cuda.synchronize(); dt = time.perf_counter() - t0
+                a.append(P * n * DEV_STEPS / dt)
+                t0 = time.perf_counter(); pop.collect(group, DEV_STEPS); torch.cuda.synchronize(); dt = time.perf_counter() - t0
+                b.append(P * n * DEV_STEPS / dt)
+            med = statistics.median
+            lines.append("P %2d N %3d  (i) standalone collects %10.0f [%.0f .. %.0f]   (ii) pop.collect %10.0f [%.0f .. %.0f]   (ii)/(i) %.2fx   "
+                         "us per vector step (i) %.1f (ii) %.1f" % (P, n, med(a), min(a), max(a), med(b), min(b), max(b), med(b) / med(a),
+                                                                    1e6 * P * n / med(a), 1e6 * P * n / med(b)))
+            lines.append("            pop collect counts: %s" % pop.collect_counts())
+            del pop, group, solo, envs
+    text = "\n".join(lines)
+    print(text)
+    if out:
+        with open(out, "a") as f:
+            f.write(text + "\n")
+
+
+def members_run(ps):
+    import torch
+    for P in ps:
+        for n in POP_NS:
+            pop, group, _, _ = _population(P, n)
+            pop.collect(group, T)
+            torch.cuda.synchronize()
+            pop.collect(group, STEPS)
+            torch.cuda.synchronize()
 
 
 def _agent(n, seed=1):
@@ -109,18 +183,26 @@ def run():
         torch.cuda.synchronize()
 
 
-def parse(d):
+def parse(d, pop_ps=None):
     rows = {}
     for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         with open(path) as f:
             for r in csv.DictReader(f):
                 name = r.get("Kernel_Name", "")
-                key = next((k for k in NAMES if k in name), None)
+                key = next((k for k in POP_NAMES + NAMES if k in name), None)
                 if key:
                     rows.setdefault(key, []).append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     # --run goes through NS in order with the same number of steps each: a kernel's launches in time order are len(NS) equal runs
     for key, v in sorted(rows.items()):
         v = [d for _, d in sorted(v)]
+        if key in POP_NAMES:    # --run --members P ...: per P the shapes POP_NS in order, T warm-up steps and STEPS steps each
+            shapes = [(P, n) for P in (pop_ps or [0]) for n in POP_NS]
+            per = len(v) // len(shapes)
+            for k, (P, n) in enumerate(shapes):
+                part = v[k * per:(k + 1) * per][T:]
+                if part:
+                    print("%-28s P %2d N %3d  launches %5d  median %.2f us  [%.2f .. %.2f]" % (key, P, n, len(part), statistics.median(part), min(part), max(part)))
+            continue
         per = len(v) // len(NS)
         for k, n in enumerate(NS):
             part = v[k * per:(k + 1) * per]
@@ -135,10 +217,13 @@ if __name__ == "__main__":
     ap.add_argument("--run", action="store_true")
     ap.add_argument("--parse", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--members", type=int, nargs="+", default=None, metavar="P", help="population sizes: pop.collect against P standalone collect calls")
     a = ap.parse_args()
+    if a.members and not (a.run or a.parse):
+        members_cost(a.members, a.out)
     if a.cost:
         cost(a.out)
     if a.run:
-        run()
+        members_run(a.members) if a.members else run()
     if a.parse:
-        parse(a.parse)
+        parse(a.parse, a.members)
