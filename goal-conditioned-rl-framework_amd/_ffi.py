@@ -233,6 +233,8 @@ PROTOTYPES = {
     "gcrl_proc_pack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gcrl_agent_observe_act_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "gcrl_her_process_step_dev": (_i64, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "gcrl_env_scripted_act": (C.c_int, [_vp, _vp, _f64, _u64, _u64, _vp]),
+    "gcrl_her_collect_scripted": (_i64, [_vp, _vp, _vp, _vp, C.c_int, _f64, _u64, _u64, _vp]),
     "gcrl_her_flush_calls": (_i64, [_vp]),
     "gcrl_agent_collect_set": (C.c_int, [_vp, _u64, _f64, _f64, _u64]),
     "gcrl_agent_collect_get": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_u64)]),

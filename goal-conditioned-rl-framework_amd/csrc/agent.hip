@@ -2970,8 +2970,8 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
   GCRL_CHECK_ARG(env->N <= a->B, "%s: env: %d envs exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, env->N, a->B);
   GCRL_CHECK_ARG(env->N <= kEnvMaxN, "%s: env: %d envs (at most %d)", who, env->N, kEnvMaxN);
   GCRL_CHECK_ARG(env->D + kEnvG == a->S && a->S == ring->S, "%s: env: obs_dim %d + goal_dim %d != state_dim %d (ring: %d)", who, env->D, kEnvG, a->S, ring->S);
-  GCRL_CHECK_ARG(kEnvA == a->A && kEnvA == ring->A && kEnvG == ring->G, "%s: env: action_dim %d / goal_dim %d, the agent has action_dim %d, the ring %d / %d", who,
-                 kEnvA, kEnvG, a->A, ring->A, ring->G);
+  GCRL_CHECK_ARG(env->A == a->A && env->A == ring->A && kEnvG == ring->G, "%s: env: action_dim %d / goal_dim %d, the agent has action_dim %d, the ring %d / %d", who,
+                 env->A, kEnvG, a->A, ring->A, ring->G);
   GCRL_CHECK_ARG(env->T == ring->cfg.flush_len, "%s: max_steps: the env's horizon %d differs from the ring's flush length %d", who, env->T, ring->cfg.flush_len);
   GCRL_CHECK_ARG(ring->cfg.reward_kind == GCRL_REWARD_SPARSE, "%s: compute_reward: the ring's reward kind is %s; the env's reward is the built-in sparse kind%s", who,
                  ring->cfg.reward_kind == GCRL_REWARD_HOST ? "a host callback" : "dense",
@@ -2993,7 +2993,7 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
   const bool ddpg = a->cfg.kind == GCRL_AGENT_DDPG;
   const double scale = a->sac ? 1.0 : a->col_noise_std;
   void* noise_buf = a->sac ? (void*)cb.f32 : (void*)cb.noise64;
-  const unsigned long long per_step = (unsigned long long)N * kEnvA;
+  const unsigned long long per_step = (unsigned long long)N * env->A;
   const int flush_mul = 1 + (gcrl::her_prio_on(ring) ? 1 : 0) + (gcrl::her_td_on(ring) ? 1 : 0);
   int64_t total = 0;
   for (int s = 0; s < steps; ++s) {
@@ -3053,8 +3053,8 @@ int gcrl_agent_evaluate(gcrl_agent* a, gcrl_env* env, gcrl_normalizer* nz_obs, g
   GCRL_CHECK_ARG(episodes >= 1, "%s: episodes: %d (>= 1 required)", who, episodes);
   GCRL_CHECK_ARG(env->device == a->cfg.device, "%s: env: it lives on device %d, the agent on device %d", who, env->device, a->cfg.device);
   GCRL_CHECK_ARG(env->N <= a->B, "%s: env: %d envs exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, env->N, a->B);
-  GCRL_CHECK_ARG(env->D + kEnvG == a->S && kEnvA == a->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the agent has state_dim %d / action_dim %d", who,
-                 env->D, kEnvG, kEnvA, a->S, a->A);
+  GCRL_CHECK_ARG(env->D + kEnvG == a->S && env->A == a->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the agent has state_dim %d / action_dim %d", who,
+                 env->D, kEnvG, env->A, a->S, a->A);
   TRY(act_dev_check(a, nz_obs, nz_dg, env->D, env->N, eval_mode, who));
   const int N = env->N;
   if (!reset)

@@ -894,8 +894,8 @@ int pop_group_check(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_o
   GCRL_CHECK_ARG(g->device == a0->cfg.device, "%s: env: it lives on device %d, the population on device %d", who, g->device, a0->cfg.device);
   GCRL_CHECK_ARG(g->N <= a0->B, "%s: env: %d envs per member exceed batch_size %d (the acting launch takes 1..batch_size rows)", who, g->N, a0->B);
   GCRL_CHECK_ARG(g->N <= kEnvMaxN, "%s: env: %d envs per member (at most %d)", who, g->N, kEnvMaxN);
-  GCRL_CHECK_ARG(g->D + kEnvG == a0->S && kEnvA == a0->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the members have state_dim %d / action_dim %d", who,
-                 g->D, kEnvG, kEnvA, a0->S, a0->A);
+  GCRL_CHECK_ARG(g->D + kEnvG == a0->S && g->A == a0->A, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, the members have state_dim %d / action_dim %d", who,
+                 g->D, kEnvG, g->A, a0->S, a0->A);
   GCRL_CHECK_ARG(4 * round_up(a0->S, 4) <= 2 * kRowThreads || a0->sac || !(nz_obs || nz_dg), "%s: env: fused normalisation supports state_dim <= 128", who);
   for (int i = 0; i < P; ++i)
     TRY(act_dev_check(p->m[i], nz_obs ? nz_obs[i] : nullptr, nz_dg ? nz_dg[i] : nullptr, g->D, g->N, eval_mode, who));
@@ -993,8 +993,8 @@ int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcr
     for (int j = 0; j < i; ++j)
       GCRL_CHECK_ARG(rings[j] != h, "%s: shared_ring: members %d and %d share a replay ring; one ring and one normaliser pair cannot take the merged staging launch", who, j, i);
     GCRL_CHECK_ARG(N <= h->cfg.nenvs, "%s: env: %d envs per member for a ring of %d episode slots (member %d)", who, N, h->cfg.nenvs, i);
-    GCRL_CHECK_ARG(g->D + kEnvG == h->S && kEnvA == h->A && kEnvG == h->G, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, member %d's ring has state_dim %d / action_dim %d / goal_dim %d",
-                   who, g->D, kEnvG, kEnvA, i, h->S, h->A, h->G);
+    GCRL_CHECK_ARG(g->D + kEnvG == h->S && g->A == h->A && kEnvG == h->G, "%s: env: obs_dim %d + goal_dim %d / action_dim %d, member %d's ring has state_dim %d / action_dim %d / goal_dim %d",
+                   who, g->D, kEnvG, g->A, i, h->S, h->A, h->G);
     GCRL_CHECK_ARG(g->T == h->cfg.flush_len, "%s: max_steps: the group's horizon %d differs from the flush length %d of member %d's ring", who, g->T, h->cfg.flush_len, i);
     GCRL_CHECK_ARG(h->cfg.reward_kind == GCRL_REWARD_SPARSE, "%s: compute_reward: the reward kind of member %d's ring is %s; the env's reward is the built-in sparse kind", who, i,
                    h->cfg.reward_kind == GCRL_REWARD_HOST ? "a host callback" : "dense");
@@ -1023,7 +1023,7 @@ int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcr
   void* sarg = stream ? stream : (void*)a0->stream;   // one stream for all handles: the loop is stream-ordered
   p->col_calls += 1;
   const bool ddpg = a0->cfg.kind == GCRL_AGENT_DDPG;
-  const unsigned long long per_step = (unsigned long long)N * kEnvA;
+  const unsigned long long per_step = (unsigned long long)N * g->A;
   int flush_mul[kMaxPopMembers];
   for (int i = 0; i < P; ++i) { flush_mul[i] = 1 + (gcrl::her_prio_on(rings[i]) ? 1 : 0) + (gcrl::her_td_on(rings[i]) ? 1 : 0); rows_out[i] = 0; }
   gcrl::EnvPopMember mem[kMaxPopMembers];
@@ -1035,7 +1035,7 @@ int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcr
       gcrl_agent* a = p->m[i];
       const unsigned long long c = a->col_ctr;
       const double scale = a->sac ? 1.0 : a->col_noise_std;
-      double* noise_i = g->noise64 + (size_t)i * g->stride_n * kEnvA;
+      double* noise_i = g->noise64 + (size_t)i * g->stride_n * g->A;
       const bool eps_step = explore && ddpg && a->col_epsilon > 0.0 &&
                             (double)gcrl::hash_below(a->col_seed, kEpsStream, c, 1u << 24) * (1.0 / 16777216.0) < a->col_epsilon;
       gcrl::EnvPopMember& em = mem[i];
@@ -1047,7 +1047,7 @@ int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcr
           TRY(gcrl::normal_fill(noise_i, 1, (int)per_step, a->col_seed, c * per_step, scale, st));
           p->col_launches += 1;
         }
-        em.src = gcrl::kEnvActF64; em.act = g->act64 + (size_t)i * g->stride_n * kEnvA;
+        em.src = gcrl::kEnvActF64; em.act = g->act64 + (size_t)i * g->stride_n * g->A;
       }
       em.eps_seed = a->col_seed ^ kEpsStream;
       em.noise_on = explore ? 1 : 0; em.noise_seed = a->col_seed; em.noise_ctr0 = (c + 1) * per_step; em.noise_scale = scale;
@@ -1111,7 +1111,7 @@ int gcrl_pop_evaluate(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz
   }
   gcrl::EnvPopMember mem[kMaxPopMembers];
   std::memset(mem, 0, sizeof(mem));
-  for (int i = 0; i < P; ++i) { mem[i].src = gcrl::kEnvActF64; mem[i].act = g->act64 + (size_t)i * g->stride_n * kEnvA; }
+  for (int i = 0; i < P; ++i) { mem[i].src = gcrl::kEnvActF64; mem[i].act = g->act64 + (size_t)i * g->stride_n * g->A; }
   const int rounds = (episodes + N - 1) / N;
   const unsigned int live = P >= 32 ? ~0u : ((1u << P) - 1u);
   int64_t launches = 0;

@@ -2,7 +2,7 @@
 // blocks of a vector step live in device memory.  One env_step_kernel launch writes a step's `raw` and `pay` blocks in the layout
 // her_ring.hip's her_process_step_body reads and the next step's acting rows [obs | goal] in the layout the acting kernels read,
 // so an agent's collect loop (agent.hip) is act -> step -> process-step with nothing crossing to the host.
-// The rule is restated in numpy in tests/dev_env_ref.py, which is its definition.
+// The rule is restated in numpy in tests/dev_env_ref.py (reach, push) and tests/dev_env_pick_ref.py (pick), which are its definition.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,18 +10,23 @@
 
 #include "common.h"
 
-constexpr int kEnvG = 3, kEnvA = 3;      // goal and action width of both kinds
+constexpr int kEnvG = 3;                 // goal width of every kind
 constexpr int kEnvPayW = 32;             // floats per env of the payload block (her_ring.hip kPayW)
 constexpr int kEnvMaxN = 1024;
-constexpr int kEnvStateW = 12;           // floats per env: p(3) q(3) vel(3) goal(3)
+// per kind: action width, observation width, and floats per env of the state record —
+// p(3) q(3) vel_p(3) goal(3), and for pick | w held vel_q(3) vel_w
+__host__ __device__ constexpr int env_action_dim(int kind) { return kind == GCRL_ENV_PICK ? 4 : 3; }
+__host__ __device__ constexpr int env_obs_dim(int kind) { return kind == GCRL_ENV_REACH ? 7 : kind == GCRL_ENV_PUSH ? 13 : 20; }
+__host__ __device__ constexpr int env_state_w(int kind) { return kind == GCRL_ENV_PICK ? 18 : 12; }
 
 struct gcrl_env {
   int kind = 0, N = 0, T = 0, D = 0, device = 0;
+  int A = 3, SW = 12;                    // env_action_dim(kind), env_state_w(kind)
   float thr = 0.f;
   uint64_t seed = 0;
   hipStream_t stream = nullptr;
   // device state: everything a resume needs
-  float* state = nullptr;                // [N][kEnvStateW]
+  float* state = nullptr;                // [N][SW]
   int* t = nullptr;                      // [N] steps taken in the running episode
   unsigned long long* cnt = nullptr;     // [N][3]: episode index (the RNG key), episodes finished, successes
   double* rsum = nullptr;                // [N] reward sum
@@ -29,6 +34,7 @@ struct gcrl_env {
   float* rows = nullptr;                 // [N][D + G] acting rows of the NEXT step
   float* raw = nullptr;                  // [obs N*D | next_obs N*D | dg N*G | next_dg N*G | ag N*G | next_ag N*G]
   float* pay = nullptr;                  // [N][kEnvPayW]: t | r | done = 0 | action(A) | next_ag(G)
+  float* script_act = nullptr;           // [N][A] the scripted controller's actions (gcrl_her_collect_scripted; allocated on first use)
   int64_t steps = 0, launches = 0;       // vector steps taken / kernel launches issued since creation
   std::vector<int32_t> t_host;           // host mirror of t: the step kernel's rule (t + 1, 0 at the horizon) needs no read-back
 
@@ -45,12 +51,13 @@ struct gcrl_env {
 constexpr int kEnvGroupMaxP = 16;        // a population's member limit
 struct gcrl_env_group {
   int kind = 0, P = 0, N = 0, T = 0, D = 0, device = 0;
+  int A = 3, SW = 12;                    // env_action_dim(kind), env_state_w(kind)
   int stride_n = 0;                      // rows per member of rows / noise64 / act64 (> N: the rows past N are never touched)
   int stride = 0, raw_floats = 0;        // floats per member of `data`; a member's slice is raw (raw_floats) | pay [N][kEnvPayW]
   float thr = 0.f;
   uint64_t seeds[kEnvGroupMaxP] = {};
   hipStream_t stream = nullptr;
-  float* state = nullptr;                // [P][N][kEnvStateW]
+  float* state = nullptr;                // [P][N][SW]
   int* t = nullptr;                      // [P][N]
   unsigned long long* cnt = nullptr;     // [P][N][3]
   double* rsum = nullptr;                // [P][N]
@@ -113,5 +120,8 @@ int clipped_normal_fill(float* out, int n, unsigned long long seed, unsigned lon
 int normal_fill(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale, hipStream_t st);
 // out32[i] = float(in64[i]) for i < n
 int round_to_f32(const double* in64, float* out32, int n, hipStream_t st);
+// env_scripted_kernel (dev_env_script.hip) on `st`: the pick kind's scripted controller, float32 actions [N][A] to out; noise_std > 0 adds
+// float(double(hash_normal(seed, ctr0 + i * A + c)) * noise_std) before a final clamp to [-1, 1]
+int env_scripted_launch(gcrl_env* e, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st);
 
 }  // namespace gcrl

@@ -1,14 +1,18 @@
-// dev_env.hip — two built-in goal environments that live on the device (dev_env.h), and the small launches the device-row acting
+// dev_env.hip — three built-in goal environments that live on the device (dev_env.h), and the small launches the device-row acting
 // entries and the collect loop of agent.hip need around them.
 //
-//   reach (D = 7)    a point mass in a box: obs = [pos, vel, t / T], achieved goal = pos
-//   push  (D = 13)   a pusher and a puck on the plane z = 0: obs = [p, q, q - p, vel_p, t / T], achieved goal = q; the puck moves by the
-//                    pusher's planar displacement while the pusher's new position is inside the contact radius
+//   reach (D = 7, A = 3)    a point mass in a box: obs = [pos, vel, t / T], achieved goal = pos
+//   push  (D = 13, A = 3)   a pusher and a puck on the plane z = 0: obs = [p, q, q - p, vel_p, t / T], achieved goal = q; the puck moves by
+//                           the pusher's planar displacement while the pusher's new position is inside the contact radius
+//   pick  (D = 20, A = 4)   a gripper with a finger opening w and an object that rests on the table: obs = [p, q, q - p, vel_p, vel_q, w,
+//                           vel_w, held, near, t / T], achieved goal = q; the object is grasped when the fingers close around it, moves
+//                           with the gripper while they stay closed and falls when released; half the goals lie in the air
 //
-// G = 3, A = 3, fixed horizon T, sparse reward -(dist > thr) formed as the replay ring's relabelling kernels form it, no termination.
+// G = 3, fixed horizon T, sparse reward -(dist > thr) formed as the replay ring's relabelling kernels form it, no termination.
 // All arithmetic is float32, one rounding per operation (the unit is built with -ffp-contract=off): + - * /, comparisons,
 // fminf / fmaxf and the correctly rounded square root of the reward's distance.  The rule — constants, operation order, what a NaN
-// action counts as, the random-number keys — is restated in numpy in tests/dev_env_ref.py, which is its definition.
+// action counts as, the random-number keys — is restated in numpy in tests/dev_env_ref.py (reach, push) and
+// tests/dev_env_pick_ref.py (pick), which are its definition.
 //
 // Random numbers: u(env, episode, component) = hash_below(seed, kEnvStream + env, 8 * episode + component, 2^24) * 2^-24.  No state
 // besides the counters, so an env's episode j is the same whatever N is and whenever it is reached.
@@ -19,7 +23,7 @@
 //
 // Kernel rules: every address comes from the handle or the group's member table (or, for the pack and fill launches, from the
 // caller's checked arguments); an env index >= N — for a group: a member index >= P — does nothing; no atomics; no waits between
-// workgroups; no per-thread scratch (every loop is over a constant 3 and unrolled); plain vector stores only.
+// workgroups; no per-thread scratch (every loop is over a small constant and unrolled); plain vector stores only.
 #include "dev_env.h"
 
 #include <vector>
@@ -99,8 +103,10 @@ EnvArgs base_args(gcrl_env* e) {
   return a;
 }
 
+bool known_kind(int kind) { return kind == GCRL_ENV_REACH || kind == GCRL_ENV_PUSH || kind == GCRL_ENV_PICK; }
+
 size_t state_bytes(const gcrl_env* e) {
-  return sizeof(EnvHeader) + (size_t)e->N * (kEnvStateW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
+  return sizeof(EnvHeader) + (size_t)e->N * (e->SW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
          (size_t)e->N * (e->D + kEnvG) * sizeof(float);
 }
 
@@ -151,11 +157,11 @@ extern "C" {
 
 gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device) {
   auto bad = [](const char* m) -> gcrl_env* { gcrl::fail(GCRL_ERR_ARG, "gcrl_env_create: %s", m); return nullptr; };
-  if (kind != GCRL_ENV_REACH && kind != GCRL_ENV_PUSH) return bad("kind: GCRL_ENV_REACH or GCRL_ENV_PUSH required");
+  if (!known_kind(kind)) return bad("kind: GCRL_ENV_REACH, GCRL_ENV_PUSH or GCRL_ENV_PICK required");
   if (num_envs < 1 || num_envs > kEnvMaxN) return bad("num_envs: 1..1024 required");
   if (max_steps < 1 || max_steps > 64) return bad("max_steps: 1..64 required (the replay ring's flush length limit)");
   if (!(threshold > 0.f) || !(threshold < kBox)) return bad("threshold: must lie in (0, 0.3)");
-  if (kind == GCRL_ENV_PUSH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push places the goal at least 2 * threshold from the puck and needs 2 * threshold <= 0.15");
+  if (kind != GCRL_ENV_REACH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push and pick place the goal at least 2 * threshold from the puck and need 2 * threshold <= 0.15");
   int ndev = gcrl_device_count();
   if (ndev <= 0 || device < 0 || device >= ndev) {
     gcrl::fail(GCRL_ERR_HIP, "gcrl_env_create: no usable HIP device (count=%d, requested %d); there is no CPU fallback", ndev, device);
@@ -163,7 +169,7 @@ gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, 
   }
   gcrl_env* e = new gcrl_env;
   e->kind = kind; e->N = num_envs; e->T = max_steps; e->thr = threshold; e->seed = seed; e->device = device;
-  e->D = kind == GCRL_ENV_REACH ? 7 : 13;
+  e->D = env_obs_dim(kind); e->A = env_action_dim(kind); e->SW = env_state_w(kind);
   const size_t N = (size_t)num_envs, raw_floats = N * (2 * e->D + 4 * kEnvG);
   auto ok = [&](hipError_t r, const char* what) {
     if (r == hipSuccess) return true;
@@ -171,11 +177,11 @@ gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, 
     return false;
   };
   bool good = ok(hipSetDevice(device), "hipSetDevice") && ok(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
-              ok(hipMalloc((void**)&e->state, N * kEnvStateW * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->t, N * sizeof(int)), "hipMalloc") &&
+              ok(hipMalloc((void**)&e->state, N * e->SW * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->t, N * sizeof(int)), "hipMalloc") &&
               ok(hipMalloc((void**)&e->cnt, N * 3 * sizeof(unsigned long long)), "hipMalloc") && ok(hipMalloc((void**)&e->rsum, N * sizeof(double)), "hipMalloc") &&
               ok(hipMalloc((void**)&e->rows, N * (e->D + kEnvG) * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->raw, raw_floats * sizeof(float)), "hipMalloc") &&
               ok(hipMalloc((void**)&e->pay, N * kEnvPayW * sizeof(float)), "hipMalloc");
-  if (good) good = ok(hipMemset(e->state, 0, N * kEnvStateW * sizeof(float)), "hipMemset") && ok(hipMemset(e->t, 0, N * sizeof(int)), "hipMemset") &&
+  if (good) good = ok(hipMemset(e->state, 0, N * e->SW * sizeof(float)), "hipMemset") && ok(hipMemset(e->t, 0, N * sizeof(int)), "hipMemset") &&
                    ok(hipMemset(e->cnt, 0, N * 3 * sizeof(unsigned long long)), "hipMemset") && ok(hipMemset(e->rsum, 0, N * sizeof(double)), "hipMemset") &&
                    ok(hipMemset(e->raw, 0, raw_floats * sizeof(float)), "hipMemset") && ok(hipMemset(e->pay, 0, N * kEnvPayW * sizeof(float)), "hipMemset");
   if (good) {
@@ -195,7 +201,7 @@ gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, 
 void gcrl_env_destroy(gcrl_env* e) {
   if (!e) return;
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  for (void* p : {(void*)e->state, (void*)e->t, (void*)e->cnt, (void*)e->rsum, (void*)e->rows, (void*)e->raw, (void*)e->pay})
+  for (void* p : {(void*)e->state, (void*)e->t, (void*)e->cnt, (void*)e->rsum, (void*)e->rows, (void*)e->raw, (void*)e->pay, (void*)e->script_act})
     if (p) (void)hipFree(p);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -207,7 +213,7 @@ int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int
   if (num_envs) *num_envs = e->N;
   if (obs_dim) *obs_dim = e->D;
   if (goal_dim) *goal_dim = kEnvG;
-  if (ac_dim) *ac_dim = kEnvA;
+  if (ac_dim) *ac_dim = e->A;
   if (max_steps) *max_steps = e->T;
   if (threshold) *threshold = e->thr;
   if (seed) *seed = e->seed;
@@ -260,7 +266,7 @@ int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* r
 
 int64_t gcrl_env_state_bytes(const gcrl_env* e) { return e ? (int64_t)state_bytes(e) : 0; }
 
-// blob: header | state [N][12] f32 | t [N] i32 | counters [N][3] u64 | reward sums [N] f64 | acting rows [N][D + G] f32
+// blob: header | state [N][12] f32 (pick: [N][18]) | t [N] i32 | counters [N][3] u64 | reward sums [N] f64 | acting rows [N][D + G] f32
 int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream) {
   GCRL_CHECK_ARG(e && dst_host && n == (int64_t)state_bytes(e), "gcrl_env_save_state: the blob is %lld bytes", e ? (long long)state_bytes(e) : 0ll);
   hipStream_t st = e->pick(stream);
@@ -269,7 +275,7 @@ int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream) {
   std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
   const size_t N = (size_t)e->N;
   const void* src[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
-  const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
+  const size_t len[5] = {N * e->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
   for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(o, src[k], len[k], hipMemcpyDeviceToHost, st)); o += len[k]; }
   GCRL_HIP(hipStreamSynchronize(st));
   return GCRL_OK;
@@ -289,7 +295,7 @@ int gcrl_env_load_state(gcrl_env* e, const void* src_host, int64_t n, void* stre
   const char* o = static_cast<const char*>(src_host) + sizeof(hd);
   const size_t N = (size_t)e->N;
   void* dst[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
-  const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
+  const size_t len[5] = {N * e->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
   for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(dst[k], o, len[k], hipMemcpyHostToDevice, st)); o += len[k]; }
   GCRL_HIP(hipStreamSynchronize(st));   // (the source is the caller's pageable memory)
   e->seed = hd.seed; e->steps = hd.steps;

@@ -1,8 +1,11 @@
 // dev_env_body.h — the device text the environment units share: what an env's thread does on a reset and on a step, on the EnvArgs of ONE
 // gcrl_env.  dev_env.hip's env_reset_kernel / env_step_kernel call it with the handle's arguments; dev_env_group.hip's population
 // kernels call it with the arguments a standalone env of the member's seed would pass, pointed at the member's slices — so a group
-// member's arithmetic is a standalone env's by construction.  The rule is restated in numpy in tests/dev_env_ref.py, which is its
-// definition.  Units that include this are built with -ffp-contract=off.
+// member's arithmetic is a standalone env's by construction.  The rule is restated in numpy in tests/dev_env_ref.py (reach, push) and
+// tests/dev_env_pick_ref.py (pick), which are its definition.  Units that include this are built with -ffp-contract=off.
+//
+// The action width and the state record's width follow the kind (dev_env.h env_action_dim, env_state_w).  Every small array is
+// indexed by the constants of a fully unrolled loop, a fourth action component behind `c < A`: nothing lives in per-thread scratch.
 #pragma once
 #include "dev_env.h"
 #include "her_ring.h"   // hash_below
@@ -12,6 +15,7 @@ namespace {
 
 constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
 constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
+constexpr float kFinger = 0.02f, kOpen = 0.08f, kClose = 0.04f, kFall = 0.04f;   // pick: finger travel per step, opening, grasp width, fall per step
 constexpr uint32_t kEnvMagic = 0x564e4547u;   // "GENV"
 // header of a saved env (gcrl_env_save_state); a group's blob holds one such record per member
 struct EnvHeader { uint32_t magic; int32_t kind, N, T; float thr; uint32_t pad; uint64_t seed; int64_t steps; };
@@ -35,12 +39,15 @@ __device__ inline float u01(unsigned long long seed, int env, unsigned long long
 }
 __device__ inline float spawn(float u) { return (u * 2.0f - 1.0f) * kSpawn; }
 __device__ inline float clamp_box(float x) { return fminf(fmaxf(x, -kBox), kBox); }
+__device__ inline float clamp_z(float x) { return fminf(fmaxf(x, 0.0f), kBox); }
 
-struct EnvState { float p[3], q[3], vel[3], goal[3]; };
+// pick alone uses w (finger opening), held (0 / 1), vq (the object's displacement of the last step) and vw (the fingers')
+struct EnvState { float p[3], q[3], vel[3], goal[3]; float w, held, vq[3], vw; };
 
 __device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, EnvState& s) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) s.vel[c] = 0.f;
+  for (int c = 0; c < 3; ++c) { s.vel[c] = 0.f; s.vq[c] = 0.f; }
+  s.w = kOpen; s.held = 0.f; s.vw = 0.f;
   if (a.kind == GCRL_ENV_REACH) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { s.p[c] = spawn(u01(a.seed, i, ep, c)); s.q[c] = 0.f; s.goal[c] = spawn(u01(a.seed, i, ep, 3 + c)); }
@@ -51,19 +58,37 @@ __device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, 
     const float m = two + u01(a.seed, i, ep, 4) * (kSpawn - two);
     s.goal[0] = u01(a.seed, i, ep, 5) < 0.5f ? s.q[0] - m : s.q[0] + m;
     s.goal[1] = spawn(u01(a.seed, i, ep, 6));
-    s.goal[2] = 0.f;
+    s.goal[2] = a.kind == GCRL_ENV_PICK ? fmaxf(spawn(u01(a.seed, i, ep, 7)), 0.0f) : 0.f;
   }
 }
 
 __device__ inline void load_state(const EnvArgs& a, int i, EnvState& s) {
-  const float* w = a.state + (size_t)i * kEnvStateW;
+  const float* w = a.state + (size_t)i * env_state_w(a.kind);
 #pragma unroll
-  for (int c = 0; c < 3; ++c) { s.p[c] = w[c]; s.q[c] = w[3 + c]; s.vel[c] = w[6 + c]; s.goal[c] = w[9 + c]; }
+  for (int c = 0; c < 3; ++c) { s.p[c] = w[c]; s.q[c] = w[3 + c]; s.vel[c] = w[6 + c]; s.goal[c] = w[9 + c]; s.vq[c] = 0.f; }
+  s.w = kOpen; s.held = 0.f; s.vw = 0.f;
+  if (a.kind == GCRL_ENV_PICK) {
+    s.w = w[12]; s.held = w[13]; s.vw = w[17];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s.vq[c] = w[14 + c];
+  }
 }
 __device__ inline void store_state(const EnvArgs& a, int i, const EnvState& s) {
-  float* w = a.state + (size_t)i * kEnvStateW;
+  float* w = a.state + (size_t)i * env_state_w(a.kind);
 #pragma unroll
   for (int c = 0; c < 3; ++c) { w[c] = s.p[c]; w[3 + c] = s.q[c]; w[6 + c] = s.vel[c]; w[9 + c] = s.goal[c]; }
+  if (a.kind == GCRL_ENV_PICK) {
+    w[12] = s.w; w[13] = s.held; w[17] = s.vw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[14 + c] = s.vq[c];
+  }
+}
+// squared distance of x and y, the squares summed in component order
+__device__ inline float dist2(const float* x, const float* y) {
+  float d2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { const float df = x[c] - y[c]; d2 = d2 + df * df; }
+  return d2;
 }
 // obs of state s at step count t -> o[0 .. D)
 __device__ inline void write_obs(const EnvArgs& a, const EnvState& s, int t, float* o) {
@@ -72,10 +97,16 @@ __device__ inline void write_obs(const EnvArgs& a, const EnvState& s, int t, flo
 #pragma unroll
     for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.vel[c]; }
     o[6] = tt;
-  } else {
+  } else if (a.kind == GCRL_ENV_PUSH) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; }
     o[12] = tt;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; o[12 + c] = s.vq[c]; }
+    o[15] = s.w; o[16] = s.vw; o[17] = s.held;
+    o[18] = dist2(s.p, s.q) < kContact * kContact ? 1.0f : 0.0f;
+    o[19] = tt;
   }
 }
 __device__ inline void write_row(const EnvArgs& a, int i, const EnvState& s, int t) {
@@ -102,9 +133,15 @@ __device__ inline void env_reset_body(const EnvArgs& a, int i) {
   write_row(a, i, s, 0);
 }
 
+// an action component as the rule takes it: a NaN counts as 0, then clamped to [-1, 1]
+__device__ inline float clean_action(float x) {
+  x = (x == x) ? x : 0.0f;
+  return fminf(fmaxf(x, -1.0f), 1.0f);
+}
+
 // one step of env i of `a`: the body env_step_kernel and env_step_pop_kernel share, so a group member's step is a standalone env's
 __device__ inline void env_step_body(const EnvArgs& a, int i) {
-  const int N = a.N, D = a.D;
+  const int N = a.N, D = a.D, A = env_action_dim(a.kind);
   EnvState s;
   load_state(a, i, s);
   int t = a.t[i];
@@ -116,44 +153,66 @@ __device__ inline void env_step_body(const EnvArgs& a, int i) {
   float* nag = ag + (size_t)N * kEnvG;
   float* pw = a.pay + (size_t)i * kEnvPayW;
   write_obs(a, s, t, obs);
-  float act[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     dg[c] = s.goal[c]; ndg[c] = s.goal[c];
     ag[c] = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
-    if (a.act_eps) act[c] = fminf(fmaxf(gcrl::hash_normal(a.eps_seed, a.eps_ctr0 + (unsigned long long)i * kEnvA + c), -1.0f), 1.0f);
-    else act[c] = a.act_f64 ? (float)static_cast<const double*>(a.act)[(size_t)i * kEnvA + c] : static_cast<const float*>(a.act)[(size_t)i * kEnvA + c];
+  }
+  float act[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    act[c] = 0.f;
+    if (c < A) {
+      if (a.act_eps) act[c] = fminf(fmaxf(gcrl::hash_normal(a.eps_seed, a.eps_ctr0 + (unsigned long long)i * A + c), -1.0f), 1.0f);
+      else act[c] = a.act_f64 ? (float)static_cast<const double*>(a.act)[(size_t)i * A + c] : static_cast<const float*>(a.act)[(size_t)i * A + c];
+    }
   }
   float pn[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    float x = act[c];
-    x = (x == x) ? x : 0.0f;                       // a NaN component counts as 0
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    s.vel[c] = kStep * x;
+    s.vel[c] = kStep * clean_action(act[c]);
     pn[c] = clamp_box(s.p[c] + s.vel[c]);
   }
   if (a.kind == GCRL_ENV_PUSH) {
-    float d2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { const float df = pn[c] - s.q[c]; d2 = d2 + df * df; }
-    if (d2 < kContact * kContact) {
+    if (dist2(pn, s.q) < kContact * kContact) {
       s.q[0] = clamp_box(s.q[0] + (pn[0] - s.p[0]));
       s.q[1] = clamp_box(s.q[1] + (pn[1] - s.p[1]));
     }
+  } else if (a.kind == GCRL_ENV_PICK) {
+    pn[2] = clamp_z(s.p[2] + s.vel[2]);                       // the gripper stays above the table
+    const float wn = fminf(fmaxf(s.w + kFinger * clean_action(act[3]), 0.0f), kOpen);
+    const bool near = dist2(pn, s.q) < kContact * kContact, closed = wn < kClose;
+    // a grasp: the fingers close while around the object; it lasts while they stay closed
+    const bool held = s.held != 0.f ? closed : (near && closed && s.w >= kClose);
+    float qn[3];
+    if (held) {
+      qn[0] = clamp_box(s.q[0] + (pn[0] - s.p[0]));
+      qn[1] = clamp_box(s.q[1] + (pn[1] - s.p[1]));
+      qn[2] = clamp_z(s.q[2] + (pn[2] - s.p[2]));
+    } else {
+      const bool shove = near && closed;                      // a closed fist pushes, as `push`
+      qn[0] = shove ? clamp_box(s.q[0] + (pn[0] - s.p[0])) : s.q[0];
+      qn[1] = shove ? clamp_box(s.q[1] + (pn[1] - s.p[1])) : s.q[1];
+      qn[2] = fmaxf(s.q[2] - kFall, 0.0f);                    // a released object falls
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s.vq[c] = qn[c] - s.q[c]; s.q[c] = qn[c]; }
+    s.vw = wn - s.w; s.w = wn; s.held = held ? 1.0f : 0.0f;
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) s.p[c] = pn[c];
   pw[0] = __int_as_float(t);
   t += 1;
   write_obs(a, s, t, nobs);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (c < A) pw[3 + c] = act[c];
   float acc = 0.f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float g = a.kind == GCRL_ENV_REACH ? s.p[c] : s.q[c];
     nag[c] = g;
-    pw[3 + c] = act[c];
-    pw[3 + kEnvA + c] = g;
+    pw[3 + A + c] = g;
     const float df = g - s.goal[c];
     acc = acc + df * df;
   }
@@ -175,10 +234,12 @@ __device__ inline void env_step_body(const EnvArgs& a, int i) {
   write_row(a, i, s, t);
   if (a.noise) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float z = gcrl::hash_normal(a.noise_seed, a.noise_ctr0 + (unsigned long long)i * kEnvA + c);
-      if (a.noise_f64) static_cast<double*>(a.noise)[(size_t)i * kEnvA + c] = (double)z * a.noise_scale;
-      else static_cast<float*>(a.noise)[(size_t)i * kEnvA + c] = (float)((double)z * a.noise_scale);
+    for (int c = 0; c < 4; ++c) {
+      if (c < A) {
+        const float z = gcrl::hash_normal(a.noise_seed, a.noise_ctr0 + (unsigned long long)i * A + c);
+        if (a.noise_f64) static_cast<double*>(a.noise)[(size_t)i * A + c] = (double)z * a.noise_scale;
+        else static_cast<float*>(a.noise)[(size_t)i * A + c] = (float)((double)z * a.noise_scale);
+      }
     }
   }
 }

@@ -32,7 +32,7 @@ struct EnvPopArgs {
 // member m's view of the group: the EnvArgs a standalone env of its seed would pass, on its slices
 __device__ inline void member_args(const EnvPopArgs& q, int m, EnvArgs& a) {
   const size_t o = (size_t)m * q.N;
-  a.state = q.state + o * kEnvStateW; a.t = q.t + o; a.cnt = q.cnt + o * 3; a.rsum = q.rsum + o;
+  a.state = q.state + o * env_state_w(q.kind); a.t = q.t + o; a.cnt = q.cnt + o * 3; a.rsum = q.rsum + o;
   a.rows = q.rows + (size_t)m * q.stride_n * (q.D + kEnvG);
   a.raw = q.data + (size_t)m * q.stride; a.pay = a.raw + q.raw_floats;
   a.kind = q.kind; a.N = q.N; a.T = q.T; a.D = q.D; a.thr = q.thr; a.restart = q.restart;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(64) void env_step_pop_kernel(EnvPopArgs q) {
   const int src = q.src[m];
   a.act = q.act[m]; a.act_f64 = src == gcrl::kEnvActF64 ? 1 : 0;
   a.act_eps = src == gcrl::kEnvActEps ? 1 : 0; a.eps_seed = q.tab[m].eps_seed; a.eps_ctr0 = q.eps_ctr0[m];
-  a.noise = q.noise_on[m] ? (void*)(q.noise64 + (size_t)m * q.stride_n * kEnvA) : nullptr; a.noise_f64 = 1;
+  a.noise = q.noise_on[m] ? (void*)(q.noise64 + (size_t)m * q.stride_n * env_action_dim(q.kind)) : nullptr; a.noise_f64 = 1;
   a.noise_seed = q.tab[m].noise_seed; a.noise_ctr0 = q.noise_ctr0[m]; a.noise_scale = q.tab[m].noise_scale;
   env_step_body(a, i);
 }
@@ -95,7 +95,7 @@ int group_table(gcrl_env_group* g, const gcrl::EnvPopMember* m, hipStream_t st, 
   return GCRL_OK;
 }
 size_t member_bytes(const gcrl_env_group* g) {
-  return sizeof(EnvHeader) + (size_t)g->N * (kEnvStateW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
+  return sizeof(EnvHeader) + (size_t)g->N * (g->SW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
          (size_t)g->N * (g->D + kEnvG) * sizeof(float);
 }
 size_t group_bytes(const gcrl_env_group* g) { return sizeof(GroupHeader) + (size_t)g->P * member_bytes(g); }
@@ -139,7 +139,7 @@ int env_group_step_launch(gcrl_env_group* g, const EnvPopMember* m, hipStream_t 
 gcrl_env* env_group_view(gcrl_env_group* g) {
   if (!g->view) g->view = new gcrl_env;
   gcrl_env* e = g->view;
-  e->kind = g->kind; e->N = g->N; e->T = g->T; e->D = g->D; e->device = g->device; e->thr = g->thr; e->seed = g->seeds[0]; e->stream = g->stream;
+  e->kind = g->kind; e->N = g->N; e->T = g->T; e->D = g->D; e->A = g->A; e->SW = g->SW; e->device = g->device; e->thr = g->thr; e->seed = g->seeds[0]; e->stream = g->stream;
   e->state = g->state; e->t = g->t; e->cnt = g->cnt; e->rsum = g->rsum; e->rows = g->rows; e->raw = g->data; e->pay = g->data + g->raw_floats;
   e->steps = g->steps[0]; e->launches = g->launches;
   e->t_host.assign(g->t_host.begin(), g->t_host.begin() + g->N);
@@ -158,13 +158,13 @@ extern "C" {
 // ---------------------------------------------------------------- gcrl_env_group (include/gcrl.h)
 gcrl_env_group* gcrl_env_group_create(int kind, int members, int num_envs, const uint64_t* seeds, int max_steps, float threshold, int device) {
   auto bad = [](const char* m) -> gcrl_env_group* { gcrl::fail(GCRL_ERR_ARG, "gcrl_env_group_create: %s", m); return nullptr; };
-  if (kind != GCRL_ENV_REACH && kind != GCRL_ENV_PUSH) return bad("kind: GCRL_ENV_REACH or GCRL_ENV_PUSH required");
+  if (kind != GCRL_ENV_REACH && kind != GCRL_ENV_PUSH && kind != GCRL_ENV_PICK) return bad("kind: GCRL_ENV_REACH, GCRL_ENV_PUSH or GCRL_ENV_PICK required");
   if (members < 1 || members > kEnvGroupMaxP) return bad("members: 1..16 required");
   if (!seeds) return bad("seeds: null array");
   if (num_envs < 1 || num_envs > kEnvMaxN) return bad("num_envs: 1..1024 required");
   if (max_steps < 1 || max_steps > 64) return bad("max_steps: 1..64 required (the replay ring's flush length limit)");
   if (!(threshold > 0.f) || !(threshold < kBox)) return bad("threshold: must lie in (0, 0.3)");
-  if (kind == GCRL_ENV_PUSH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push places the goal at least 2 * threshold from the puck and needs 2 * threshold <= 0.15");
+  if (kind != GCRL_ENV_REACH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push and pick place the goal at least 2 * threshold from the puck and need 2 * threshold <= 0.15");
   int ndev = gcrl_device_count();
   if (ndev <= 0 || device < 0 || device >= ndev) {
     gcrl::fail(GCRL_ERR_HIP, "gcrl_env_group_create: no usable HIP device (count=%d, requested %d); there is no CPU fallback", ndev, device);
@@ -172,7 +172,7 @@ gcrl_env_group* gcrl_env_group_create(int kind, int members, int num_envs, const
   }
   gcrl_env_group* g = new gcrl_env_group;
   g->kind = kind; g->P = members; g->N = num_envs; g->T = max_steps; g->thr = threshold; g->device = device;
-  g->D = kind == GCRL_ENV_REACH ? 7 : 13;
+  g->D = env_obs_dim(kind); g->A = env_action_dim(kind); g->SW = env_state_w(kind);
   for (int k = 0; k < members; ++k) g->seeds[k] = seeds[k];
   g->stride_n = (num_envs + 3) / 4 * 4 + 4;   // at least four rows past N in every member's slice: never read, never written
   g->raw_floats = num_envs * (2 * g->D + 4 * kEnvG);
@@ -187,10 +187,10 @@ gcrl_env_group* gcrl_env_group_create(int kind, int members, int num_envs, const
     return false;
   };
   struct Blk { void** p; size_t bytes; };
-  const Blk blks[8] = {{(void**)&g->state, PN * kEnvStateW * sizeof(float)}, {(void**)&g->t, PN * sizeof(int)},
+  const Blk blks[8] = {{(void**)&g->state, PN * g->SW * sizeof(float)}, {(void**)&g->t, PN * sizeof(int)},
                        {(void**)&g->cnt, PN * 3 * sizeof(unsigned long long)}, {(void**)&g->rsum, PN * sizeof(double)},
                        {(void**)&g->rows, PS * (g->D + kEnvG) * sizeof(float)}, {(void**)&g->data, (size_t)members * g->stride * sizeof(float)},
-                       {(void**)&g->noise64, PS * kEnvA * sizeof(double)}, {(void**)&g->act64, PS * kEnvA * sizeof(double)}};
+                       {(void**)&g->noise64, PS * g->A * sizeof(double)}, {(void**)&g->act64, PS * g->A * sizeof(double)}};
   bool good = ok(hipSetDevice(device), "hipSetDevice") && ok(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking), "hipStreamCreate");
   for (const Blk& b : blks) good = good && ok(hipMalloc(b.p, b.bytes), "hipMalloc") && ok(hipMemset(*b.p, 0, b.bytes), "hipMemset");
   if (good) {
@@ -220,7 +220,7 @@ int gcrl_env_group_dims(const gcrl_env_group* g, int* kind, int* members, int* n
   if (num_envs) *num_envs = g->N;
   if (obs_dim) *obs_dim = g->D;
   if (goal_dim) *goal_dim = kEnvG;
-  if (ac_dim) *ac_dim = kEnvA;
+  if (ac_dim) *ac_dim = g->A;
   if (max_steps) *max_steps = g->T;
   if (threshold) *threshold = g->thr;
   if (seeds_out) for (int k = 0; k < g->P; ++k) seeds_out[k] = g->seeds[k];
@@ -253,7 +253,7 @@ int gcrl_env_group_step(gcrl_env_group* g, const void* actions_dev, int actions_
   bool need_act = false;
   for (int k = 0; k < g->P; ++k) need_act = need_act || !(eps_members && eps_members[k]);
   GCRL_CHECK_ARG(actions_dev || !need_act, "gcrl_env_group_step: actions_dev: null array");
-  const size_t per = (size_t)g->N * kEnvA * (actions_f64 ? sizeof(double) : sizeof(float));
+  const size_t per = (size_t)g->N * g->A * (actions_f64 ? sizeof(double) : sizeof(float));
   for (int k = 0; k < g->P; ++k) {
     if (eps_members && eps_members[k]) { m[k].src = gcrl::kEnvActEps; m[k].eps_seed = eps_seeds[k]; m[k].eps_ctr0 = eps_ctr0[k]; }
     else { m[k].src = actions_f64 ? gcrl::kEnvActF64 : gcrl::kEnvActF32; m[k].act = static_cast<const char*>(actions_dev) + (size_t)k * per; }
@@ -296,8 +296,8 @@ int gcrl_env_group_save_state(gcrl_env_group* g, void* dst_host, int64_t n, void
   for (int k = 0; k < g->P; ++k) {
     EnvHeader hd{kEnvMagic, g->kind, g->N, g->T, g->thr, 0u, g->seeds[k], g->steps[k]};
     std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
-    const void* src[5] = {g->state + k * N * kEnvStateW, g->t + k * N, g->cnt + k * N * 3, g->rsum + k * N, g->rows + (size_t)k * g->stride_n * W};
-    const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * W * sizeof(float)};
+    const void* src[5] = {g->state + k * N * g->SW, g->t + k * N, g->cnt + k * N * 3, g->rsum + k * N, g->rows + (size_t)k * g->stride_n * W};
+    const size_t len[5] = {N * g->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * W * sizeof(float)};
     for (int b = 0; b < 5; ++b) { GCRL_HIP(hipMemcpyAsync(o, src[b], len[b], hipMemcpyDeviceToHost, st)); o += len[b]; }
   }
   GCRL_HIP(hipStreamSynchronize(st));
@@ -328,8 +328,8 @@ int gcrl_env_group_load_state(gcrl_env_group* g, const void* src_host, int64_t n
     EnvHeader hd;
     const char* o = base + k * mb;
     std::memcpy(&hd, o, sizeof(hd)); o += sizeof(hd);
-    void* dst[5] = {g->state + k * N * kEnvStateW, g->t + k * N, g->cnt + k * N * 3, g->rsum + k * N, g->rows + (size_t)k * g->stride_n * W};
-    const size_t len[5] = {N * kEnvStateW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * W * sizeof(float)};
+    void* dst[5] = {g->state + k * N * g->SW, g->t + k * N, g->cnt + k * N * 3, g->rsum + k * N, g->rows + (size_t)k * g->stride_n * W};
+    const size_t len[5] = {N * g->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * W * sizeof(float)};
     std::memcpy(g->t_host.data() + k * N, o + len[0], len[1]);
     for (int b = 0; b < 5; ++b) { GCRL_HIP(hipMemcpyAsync(dst[b], o, len[b], hipMemcpyHostToDevice, st)); o += len[b]; }
     g->seeds[k] = hd.seed; g->steps[k] = hd.steps;

@@ -709,6 +709,45 @@ class HERBuffer(_RingState):
         self.rng.push_back()
         return int(rows)
 
+    def collect_scripted(self, env, steps: int, noise_std: float = 0.0, seed: int = 0, counter: int | None = None) -> int:
+        """`steps` vector steps of a `DeviceGoalEnv("pick", ...)` under its scripted controller into this ring as ONE native call: per step
+        the controller's launch, the env's step and the process-step launch, plus the flush launches of the envs that finish — no
+        host <-> device copy, no synchronisation (include/gcrl.h gcrl_her_collect_scripted).  Demonstrations for a prior-data ring
+        without the host.  The normalisers assigned to `obs_normalizer` / `dg_normalizer` are used and updated where the constructor's
+        flags are on, as `process_step_dev` takes them (they must be DeviceRunningNormalizer objects); a normalize="sample" ring
+        stores the rows raw.  noise_std > 0 perturbs the actions with counter-hash normals keyed by `seed`; `counter` (default: the
+        vector steps this buffer has collected so far) is the first step's.  Returns the ring rows appended.  Refusals name their
+        field and come before anything is consumed."""
+        who = "HERBuffer.collect_scripted"
+        from .device_env import DeviceGoalEnv
+        from .utils import DeviceRunningNormalizer
+        if not isinstance(env, DeviceGoalEnv):
+            raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnv required")
+        if env.kind != "pick":
+            raise _ffi.GcrlError(f"{who}: kind: the scripted controller is the 'pick' kind's, this env is {env.kind!r}")
+        if int(steps) < 1:
+            raise ValueError(f"{who}: steps: {steps} (>= 1 required)")
+        nz = []
+        for flag, obj, name in ((self.obs_normalize, self._obs_normalizer, "obs_normalizer"), (self.g_normalize, self._dg_normalizer, "dg_normalizer")):
+            if flag and obj is not None and not isinstance(obj, DeviceRunningNormalizer):
+                raise _ffi.GcrlError(f"{who}: normalize: the device loop needs a DeviceRunningNormalizer as buffer.{name}, got a {type(obj).__name__}")
+            nz.append(obj if flag else None)
+        if self.normalize == "sample" and ((self.obs_normalize and nz[0] is None) or (self.g_normalize and nz[1] is None)):
+            raise _ffi.GcrlError(f"{who}: normalize: normalize='sample' needs DeviceRunningNormalizer objects assigned to buffer.obs_normalizer / "
+                                 "buffer.dg_normalizer for the flags that are on")
+        self._ensure(env.obs_dim + env.goal_dim, env.ac_dim, env.goal_dim)
+        for obj in nz:
+            if obj is not None:
+                obj.rows_dtype(np.float32)
+        c0 = int(getattr(self, "_scripted_steps", 0)) if counter is None else int(counter)
+        self.rng.pull()
+        rows = lib.gcrl_her_collect_scripted(self._h, env.handle, nz[0].handle if nz[0] is not None else None, nz[1].handle if nz[1] is not None else None,
+                                             int(steps), float(noise_std), int(seed) & (2**64 - 1), c0 & (2**64 - 1), _ffi.stream_handle())
+        self.rng.push_back()
+        self._check_rows(rows)
+        self._scripted_steps = c0 + int(steps)
+        return int(rows)
+
     def sample(self, batch_size: int, num_batches: int = 1, indices=None, return_indices: bool = False, beta: float | None = None):
         assert len(self) >= batch_size, "[ERROR] Not enough in buffer to sample"
         S, A, _ = self._dims

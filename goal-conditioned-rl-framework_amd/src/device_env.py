@@ -2,9 +2,12 @@
 step blocks live in device memory.  `agent.collect(env, steps)` drives them without the host in the loop; `acting_rows()` and
 `step_blocks()` hand out tensor views for callers who drive `observe_act_dev` / `process_step_dev` themselves.
 
-The rule of both kinds — constants, operation order, random-number keys — is restated in numpy in tests/dev_env_ref.py, which
-is its definition.  The envs are not panda-gym: `reach` is the point mass of examples/trainer_standin.py in float32, `push` a
-pusher that carries a puck along while it is inside a contact radius."""
+The rule of every kind — constants, operation order, random-number keys — is restated in numpy in tests/dev_env_ref.py (`reach`,
+`push`) and tests/dev_env_pick_ref.py (`pick`), which are its definition.  The envs are not panda-gym: `reach` is the point mass of
+examples/trainer_standin.py in float32 (obs 7, action 3), `push` a pusher that carries a puck along while it is inside a contact
+radius (obs 13, action 3), `pick` a gripper whose fingers grasp an object by closing around it, at the dimensions of
+PandaPickAndPlace (obs 20, goal 3, action 4: gripper velocity and finger velocity); half of its goals lie above the table.  `pick`
+has its scripted controller on the device: `scripted_actions()`, and `HERBuffer.collect_scripted(env, steps)` fills a ring from it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,7 +18,7 @@ import torch
 from .. import _ffi
 from .._ffi import lib
 
-KINDS = {"reach": 0, "push": 1}
+KINDS = {"reach": 0, "push": 1, "pick": 2}
 PAY_W = 32
 
 
@@ -124,8 +127,8 @@ class DeviceGoalEnvGroup:
         return self.acting_rows()
 
     def step(self, actions, eps=None):
-        """One vector step of every member from a CUDA float32 or float64 tensor [P, N, 3], one launch.  eps: {member: (seed, counter0)} —
-        those members' envs form their own actions clamp(hash_normal(seed, counter0 + env * 3 + component), -1, 1) (the epsilon step of
+        """One vector step of every member from a CUDA float32 or float64 tensor [P, N, ac_dim], one launch.  eps: {member: (seed, counter0)} —
+        those members' envs form their own actions clamp(hash_normal(seed, counter0 + env * ac_dim + component), -1, 1) (the epsilon step of
         a DDPG collect) and their slice of `actions` is not read."""
         shape = (self.members, self.num_envs, self.ac_dim)
         if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.is_contiguous() and actions.dtype in (torch.float32, torch.float64)
@@ -219,7 +222,7 @@ class DeviceGoalEnv:
 
     def step_blocks(self):
         """(raw, pay) of the LAST step in the layout `process_step_dev` takes: raw = [obs | next_obs | dg | next_dg | ag | next_ag] blocks,
-        pay [N, 32] = t | reward | done | action | next_ag.  `split_raw` cuts raw into its six [N, .] blocks."""
+        pay [N, 32] = t | reward | done | action(ac_dim) | next_ag.  `split_raw` cuts raw into its six [N, .] blocks."""
         return self._blocks()[1], self._blocks()[2]
 
     def split_raw(self, raw=None):
@@ -243,11 +246,23 @@ class DeviceGoalEnv:
         return self.acting_rows()
 
     def step(self, actions):
-        """One vector step from a CUDA float32 or float64 tensor [N, 3]; returns nothing: read `step_blocks()` / `acting_rows()`."""
+        """One vector step from a CUDA float32 or float64 tensor [N, ac_dim]; returns nothing: read `step_blocks()` / `acting_rows()`."""
         if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.is_contiguous() and actions.dtype in (torch.float32, torch.float64)
                 and tuple(actions.shape) == (self.num_envs, self.ac_dim)):
             raise ValueError(f"DeviceGoalEnv.step: actions: a contiguous CUDA float32 / float64 tensor [{self.num_envs}, {self.ac_dim}] required")
         _ffi.check(lib.gcrl_env_step(self._h, actions.data_ptr(), 1 if actions.dtype == torch.float64 else 0, _ffi.stream_handle()))
+
+    def scripted_actions(self, noise_std: float = 0.0, seed: int = 0, counter: int = 0):
+        """The `pick` kind's scripted controller on the envs as they stand, one launch: a CUDA float32 tensor [N, 4] (go to the object
+        with open fingers, close them over it, carry it to the goal; tests/dev_env_pick_ref.py scripted_action is the definition).
+        noise_std > 0 adds float32(float64(hash_normal(seed, (counter * N + env) * 4 + component)) * noise_std) before a final clamp
+        to [-1, 1].  `reach` / `push` have no controller: refused naming `kind`."""
+        if self.kind != "pick":
+            raise _ffi.GcrlError(f"DeviceGoalEnv.scripted_actions: kind: the scripted controller is the 'pick' kind's, this env is {self.kind!r}")
+        out = torch.empty((self.num_envs, self.ac_dim), dtype=torch.float32, device=f"cuda:{self.device_index}")
+        _ffi.check(lib.gcrl_env_scripted_act(self._h, out.data_ptr(), float(noise_std), int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
+                                             _ffi.stream_handle()))
+        return out
 
     def stats(self) -> dict:
         """Synchronises.  Episodes finished, episodes that ended within the threshold, reward sum — since the last full reset."""

@@ -1113,30 +1113,34 @@ int gcrl_bc_qfilter_f32(const float* spa_dev, const float* sa_dev, int ldx, int 
  * Device-resident goal environments, device-row acting entries and the collect loop.
  *
  * gcrl_env: N independent goal environments of one built-in kind in device memory (csrc/dev_env.hip; the rule is restated in
- * tests/dev_env_ref.py, which is its definition).  G = 3, A = 3, fixed horizon max_steps, sparse reward -(dist > threshold) as the
- * replay ring's built-in sparse kind forms it, no termination on success.  GCRL_ENV_REACH: obs = [pos, vel, t/T] (7), achieved goal =
- * pos.  GCRL_ENV_PUSH: obs = [pusher, puck, puck - pusher, pusher velocity, t/T] (13), achieved goal = puck.  Random numbers are a
- * counter hash keyed by (seed, episode index of the env, env, component): an env's episode j does not depend on N.
+ * tests/dev_env_ref.py and tests/dev_env_pick_ref.py, which are its definition).  G = 3, fixed horizon max_steps, sparse reward
+ * -(dist > threshold) as the replay ring's built-in sparse kind forms it, no termination on success.  A is the kind's:
+ * gcrl_env_dims reports it.  GCRL_ENV_REACH: A = 3, obs = [pos, vel, t/T] (7), achieved goal = pos.  GCRL_ENV_PUSH: A = 3, obs =
+ * [pusher, puck, puck - pusher, pusher velocity, t/T] (13), achieved goal = puck.  GCRL_ENV_PICK: A = 4 (gripper velocity, finger
+ * velocity), obs = [gripper, object, object - gripper, gripper velocity, object velocity, finger opening, finger velocity, held,
+ * near, t/T] (20), achieved goal = object; the object is grasped when the fingers close around it, moves with the gripper while
+ * they stay closed and falls when released; half the goals lie above the table.  Random numbers are a counter hash keyed by
+ * (seed, episode index of the env, env, component): an env's episode j does not depend on N.
  * ---------------------------------------------------------------------------------------- */
 typedef struct gcrl_env gcrl_env;
-enum { GCRL_ENV_REACH = 0, GCRL_ENV_PUSH = 1 };
-/* num_envs 1..1024, max_steps 1..64, 0 < threshold < 0.3 (push: 2 * threshold <= 0.15).  Every env starts at its episode 0. */
+enum { GCRL_ENV_REACH = 0, GCRL_ENV_PUSH = 1, GCRL_ENV_PICK = 2 };
+/* num_envs 1..1024, max_steps 1..64, 0 < threshold < 0.3 (push, pick: 2 * threshold <= 0.15).  Every env starts at its episode 0. */
 gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device);
 void gcrl_env_destroy(gcrl_env* e);
 int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps, float* threshold, uint64_t* seed);
 /* Device addresses of the handle's blocks: rows [N][obs_dim + 3] = the acting rows [obs | goal] of the NEXT step; raw = the last
- * step's [obs N*D | next_obs N*D | dg N*3 | next_dg N*3 | ag N*3 | next_ag N*3]; pay [N][32] = t | reward | done = 0 | action(3) |
+ * step's [obs N*D | next_obs N*D | dg N*3 | next_dg N*3 | ag N*3 | next_ag N*3]; pay [N][32] = t | reward | done = 0 | action(A) |
  * next_ag(3) — the layouts gcrl_agent_observe_act_dev and gcrl_her_process_step_dev read. */
 int gcrl_env_buffers(gcrl_env* e, float** rows, float** raw, float** pay);
 /* mask_host NULL: every env back to its episode 0, the counters to zero.  Else one byte per env: the selected envs go on to their
  * next episode (not counted as finished). */
 int gcrl_env_reset(gcrl_env* e, const uint8_t* mask_host, void* stream);
-/* One vector step, one launch: actions [N][3] on the device, float32 (actions_f64 == 0) or float64 (rounded to float32 first).  Any
+/* One vector step, one launch: actions [N][A] on the device, float32 (actions_f64 == 0) or float64 (rounded to float32 first).  Any
  * action bits leave a finite state (a NaN component counts as 0).  An env that reaches the horizon is counted and re-seeded. */
 int gcrl_env_step(gcrl_env* e, const void* actions_dev, int actions_f64, void* stream);
 /* Synchronises.  Episodes finished, those that ended with dist < threshold, and the reward sum, over all envs since the last full reset. */
 int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream);
-/* State arrays, counters, acting rows and the seed; resume is bitwise.  Loading refuses another kind, num_envs, max_steps or
+/* State arrays (12 floats per env; pick: 18), counters, acting rows and the seed; resume is bitwise.  Loading refuses another kind, num_envs, max_steps or
  * threshold by that field's name before anything is overwritten. */
 int64_t gcrl_env_state_bytes(const gcrl_env* e);
 int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream);
@@ -1162,6 +1166,20 @@ int gcrl_agent_observe_act_dev(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_norm
 int64_t gcrl_her_process_step_dev(gcrl_her* h, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg, int update_goal_stats,
                                   const float* raw_dev, const float* pay_dev, int obs_dim, const int32_t* t_host, const uint8_t* dones_host,
                                   int env0, int n, void* stream);
+/* The pick kind's scripted controller (env_scripted_kernel, csrc/dev_env_script.hip; tests/dev_env_pick_ref.py scripted_action is its
+ * definition), one launch: float32 actions [N][4] to out_dev.  noise_std > 0 adds float(double(hash_normal(seed, (counter * N + i) * 4 + j)) *
+ * noise_std) to element (i, j) before a final clamp to [-1, 1].  Refused: kind (reach and push have no controller), noise_std (negative
+ * or not finite). */
+int gcrl_env_scripted_act(gcrl_env* env, float* out_dev, double noise_std, uint64_t seed, uint64_t counter, void* stream);
+/* `steps` vector steps of a pick env under its scripted controller into ring, as a native loop: per step env_scripted_kernel, the env's
+ * step on those float32 actions and the process-step launch on the env's blocks (gcrl_her_process_step_dev: its normaliser
+ * arguments, its raw-store form on a normalize = "sample" ring), plus the flush launches — no host <-> device copy, no
+ * synchronisation.  The noise of vector step s of the call is that of counter counter0 + s.  Fills any ring, a prior-data ring
+ * included.  Refused by field name before anything is consumed, as gcrl_agent_collect refuses: env (more envs than ring slots;
+ * dimensions; device), max_steps, compute_reward, threshold, steps, nz_obs / nz_dg, t, and kind (not a pick env), noise_std.
+ * Returns the ring rows appended, or a negative error code. */
+int64_t gcrl_her_collect_scripted(gcrl_her* ring, gcrl_env* env, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, int steps, double noise_std,
+                                  uint64_t seed, uint64_t counter0, void* stream);
 /* flush groups issued by the vector-step entries' bookkeeping since creation */
 int64_t gcrl_her_flush_calls(const gcrl_her* h);
 /* The exploration stream of gcrl_agent_collect: element (c, i, j) of vector step c is double(hash_normal(seed, (c N + i) A + j)) *
@@ -1190,7 +1208,7 @@ int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* step
  * state, counters, random-number keys and arithmetic (one step body, csrc/dev_env_body.h, shared by env_step_kernel and env_step_pop_kernel; the
  * definition stays tests/dev_env_ref.py, instantiated once per member).  The members' blocks are slices at the strides the
  * population kernels take: acting rows [members][stride_n][obs_dim + 3], step data [members][stride] floats with a member's slice
- * raw (raw_floats) | pay [num_envs][32], float64 noise / eps and float64 actions [members][stride_n][3].  stride_n > num_envs: the
+ * raw (raw_floats) | pay [num_envs][32], float64 noise / eps and float64 actions [members][stride_n][A].  stride_n > num_envs: the
  * rows past num_envs of a slice are never read and never written.
  * ---------------------------------------------------------------------------------------- */
 typedef struct gcrl_env_group gcrl_env_group;
@@ -1205,9 +1223,9 @@ int gcrl_env_group_buffers(gcrl_env_group* g, float** rows, float** data, double
 /* One launch (env_reset_pop_kernel).  mask_host NULL: every env of every member back to its episode 0, the counters to zero.  Else
  * members x num_envs bytes: the selected envs go on to their next episode (not counted as finished). */
 int gcrl_env_group_reset(gcrl_env_group* g, const uint8_t* mask_host, void* stream);
-/* One vector step of every member, one launch (env_step_pop_kernel): actions_dev [members][num_envs][3], float32 or float64.
+/* One vector step of every member, one launch (env_step_pop_kernel): actions_dev [members][num_envs][A], float32 or float64.
  * eps_members NULL, or one byte per member: a selected member's envs form their own actions,
- * clamp(hash_normal(eps_seeds[m], eps_ctr0[m] + env * 3 + component), -1, 1), and its slice of actions_dev is not read
+ * clamp(hash_normal(eps_seeds[m], eps_ctr0[m] + env * A + component), -1, 1), and its slice of actions_dev is not read
  * (actions_dev may be NULL when every member is selected). */
 int gcrl_env_group_step(gcrl_env_group* g, const void* actions_dev, int actions_f64, const uint8_t* eps_members, const uint64_t* eps_seeds,
                         const uint64_t* eps_ctr0, void* stream);

@@ -16,6 +16,9 @@ issued one after another (3 P launches per vector step) — what the code could 
 seven alternating samples.  With --run: the population's steps for the profiler; --parse then also lists the population kernels.
 --run issues, for the profiler, STEPS collect steps at every N; nothing is timed there.  --parse prints, per kernel, the launches
 after the warm-up ones: number, median, range in us.  No --pmc in that run.
+--kind reach|push|pick (default reach): the env kind of every mode above.  `pick` has the headline's own dimensions (S 23 = obs 20 +
+goal 3, A 4), so --kind pick times the on-device loop on the network the project is measured on; its host path steps the numpy
+definition tests/dev_env_pick_ref.py.
 No GPU: --cost and --run fail."""
 import argparse
 import csv
@@ -30,6 +33,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 D, G, A, T, THR = 7, 3, 3, 50, 0.05
+KIND = "reach"
+DIMS = dict(reach=(7, 3), push=(13, 3), pick=(20, 4))      # obs_dim, action_dim per kind
 H, L, B = 256, 3, 256
 NS = (8, 32, 256)
 SAMPLES, WARM = 7, 10
@@ -39,6 +44,21 @@ STEPS = 300
 NAMES = ("env_step_kernel", "rowchain_act_kernel", "her_process_step_kernel", "her_flush_kernel")
 POP_NS = (8, 32)
 POP_NAMES = ("env_step_pop_kernel", "rowchain_act_pop_kernel", "her_process_step_pop_kernel")
+
+
+def _set_kind(kind):
+    global KIND, D, A
+    KIND = kind
+    D, A = DIMS[kind]
+
+
+def _ref_env(n):
+    """the numpy definition of the kind: the host path's env"""
+    if KIND == "pick":
+        import dev_env_pick_ref as PK
+        return PK.RefPickEnv(n, seed=3, max_steps=T, threshold=THR)
+    import dev_env_ref as E
+    return E.RefEnv(KIND, n, seed=3, max_steps=T, threshold=THR)
 
 
 def _normalizers(ag):
@@ -59,15 +79,15 @@ def _population(P, n, max_len=100_000):
     solo = [gcrl_amd.DDPG(D + G, A, c, None, nenvs=n, gradient_step=40, rng="engine", seed=s) for c, s in zip(cfgs, seeds)]
     for ag in pop.members + solo:
         _normalizers(ag)
-    group = gcrl_amd.DeviceGoalEnvGroup("reach", P, n, seeds, max_steps=T, threshold=THR)
-    envs = [gcrl_amd.DeviceGoalEnv("reach", n, seed=s, max_steps=T, threshold=THR) for s in seeds]
+    group = gcrl_amd.DeviceGoalEnvGroup(KIND, P, n, seeds, max_steps=T, threshold=THR)
+    envs = [gcrl_amd.DeviceGoalEnv(KIND, n, seed=s, max_steps=T, threshold=THR) for s in seeds]
     return pop, group, solo, envs
 
 
 def members_cost(ps, out):
     import torch
-    lines = ["# aggregate env-steps/s of P DDPG agents (H 256 x 3, batch 256, reach dimensions), N envs each; %d alternating samples of %d vector steps" %
-             (SAMPLES, DEV_STEPS),
+    lines = ["# aggregate env-steps/s of P DDPG agents (H 256 x 3, batch 256, %s dimensions: S %d, A %d), N envs each; %d alternating samples of %d vector steps" %
+             (KIND, D + G, A, SAMPLES, DEV_STEPS),
              "# (i) the P standalone agents' collect calls, one after another   (ii) pop.collect on a DeviceGoalEnvGroup"]
     for P in ps:
         for n in POP_NS:
@@ -141,13 +161,13 @@ def _host_steps(ag, ref, steps):
 def cost(out):
     import torch
     import gcrl_amd
-    import dev_env_ref as E
-    lines = ["# env-steps/s of one vector-env collection loop, DDPG H 256 x 3, batch 256, reach dimensions; %d alternating samples" % SAMPLES,
+    lines = ["# env-steps/s of one vector-env collection loop, DDPG H 256 x 3, batch 256, %s dimensions (S %d, A %d); %d alternating samples" %
+             (KIND, D + G, A, SAMPLES),
              "# (i) observe_act + numpy ref env + process_step per step; 'engine' leaves the Python env's own time out   (ii) agent.collect"]
     for n in NS:
         host, dev = _agent(n), _agent(n)
-        ref = E.RefEnv("reach", n, seed=3, max_steps=T, threshold=THR)
-        env = gcrl_amd.DeviceGoalEnv("reach", n, seed=3, max_steps=T, threshold=THR)
+        ref = _ref_env(n)
+        env = gcrl_amd.DeviceGoalEnv(KIND, n, seed=3, max_steps=T, threshold=THR)
         _host_steps(host, ref, WARM)
         dev.collect(env, WARM)
         torch.cuda.synchronize()
@@ -176,7 +196,7 @@ def run():
     import gcrl_amd
     for n in NS:
         ag = _agent(n)
-        env = gcrl_amd.DeviceGoalEnv("reach", n, seed=3, max_steps=T, threshold=THR)
+        env = gcrl_amd.DeviceGoalEnv(KIND, n, seed=3, max_steps=T, threshold=THR)
         ag.collect(env, WARM)
         torch.cuda.synchronize()
         ag.collect(env, STEPS)
@@ -218,7 +238,9 @@ if __name__ == "__main__":
     ap.add_argument("--parse", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--members", type=int, nargs="+", default=None, metavar="P", help="population sizes: pop.collect against P standalone collect calls")
+    ap.add_argument("--kind", default="reach", choices=sorted(DIMS), help="the env kind; pick has the headline's dimensions (S 23, A 4)")
     a = ap.parse_args()
+    _set_kind(a.kind)
     if a.members and not (a.run or a.parse):
         members_cost(a.members, a.out)
     if a.cost:
