@@ -143,8 +143,8 @@ struct gcrl_agent {
   long long oa_calls = 0, oa_launches = 0, oa_copies = 0, oa_syncs = 0;
   size_t oa_bytes = 0;
   // device-row acting (gcrl_agent_observe_act_dev) and the collect loop (gcrl_agent_collect): float64 actions [B][A] | float64 noise [B][A] |
-  // float32 actions or eps [B][A]; the exploration stream's seed, scale and vector-step counter; which env's noise of which step the
-  // noise block holds (written by the previous step's env launch); what the loop has issued (gcrl_agent_collect_counts)
+  // float32 actions or eps [B][A]; the exploration stream's seed, scale and vector-step counter; which env handle's noise (its token, dev_env.h)
+  // of which step the noise block holds (written by the previous step's env launch); what the loop has issued (gcrl_agent_collect_counts)
   char* col_dev = nullptr;
   char* eval_snap = nullptr;             // gcrl_agent_evaluate with reset == 0: the env counters as of the start of the call (device copy)
   unsigned long long col_seed = 0, col_ctr = 0;
@@ -2959,8 +2959,9 @@ int gcrl_agent_collect_get(const gcrl_agent* a, uint64_t* seed, double* noise_st
   return GCRL_OK;
 }
 
-int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
-                       int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
+// gcrl_agent_collect on a one-member group: the standalone env of the entry below, or a one-member population's group (gcrl_pop_collect)
+static int agent_collect_group(gcrl_agent* a, gcrl_env_group* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                               int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
   const char* who = "gcrl_agent_collect";
   GCRL_CHECK_ARG(a && env && ring && rows_out, "%s: null argument", who);
   // every refusal comes before a counter, a ring slot or a draw of the exploration stream is consumed
@@ -3006,7 +3007,7 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
       a->col_launches += 1;
       act = cb.f32; act_f64 = 0;
     } else {
-      if (explore && !(a->col_noise_valid && a->col_noise_env == env && a->col_noise_ctr == c)) {   // (a first call, or after the stream was set)
+      if (explore && !(a->col_noise_valid && a->col_noise_env == env->token && a->col_noise_ctr == c)) {   // (a first call, or after the stream was set)
         TRY(gcrl::normal_fill(noise_buf, a->sac ? 0 : 1, (int)per_step, a->col_seed, c * per_step, scale, st));
         a->col_launches += 1;
       }
@@ -3019,7 +3020,7 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
     a->col_t.assign(env->t_host.begin(), env->t_host.end());   // the payload's t words: the envs' step counts BEFORE the step
     if (explore) {
       TRY(gcrl::env_step_launch_noise(env, act, act_f64, noise_buf, a->sac ? 0 : 1, a->col_seed, (c + 1) * per_step, scale, st));
-      a->col_noise_valid = true; a->col_noise_env = env; a->col_noise_ctr = c + 1;
+      a->col_noise_valid = true; a->col_noise_env = env->token; a->col_noise_ctr = c + 1;
     } else {
       TRY(gcrl::env_step_launch(env, act, act_f64, st));
     }
@@ -3027,13 +3028,18 @@ int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normal
     a->col_ctr = c + 1;
     a->col_steps += 1;
     const int64_t f0 = ring->flush_calls;
-    const int64_t r = gcrl_her_process_step_dev(ring, nz_obs, update_stats, nz_dg, update_goal_stats, env->raw, env->pay, env->D, a->col_t.data(), nullptr, 0, N, sarg);
+    const int64_t r = gcrl_her_process_step_dev(ring, nz_obs, update_stats, nz_dg, update_goal_stats, env->raw(), env->pay(), env->D, a->col_t.data(), nullptr, 0, N, sarg);
     if (r < 0) return (int)r;
     a->col_launches += 1 + (ring->flush_calls - f0) * flush_mul;
     total += r;
   }
   *rows_out = total;
   return GCRL_OK;
+}
+
+int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                       int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
+  return agent_collect_group(a, env, ring, nz_obs, update_stats, nz_dg, update_goal_stats, steps, explore, eval_mode, rows_out, stream);
 }
 
 int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs) {

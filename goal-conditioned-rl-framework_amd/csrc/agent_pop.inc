@@ -1011,11 +1011,9 @@ int gcrl_pop_collect(gcrl_pop* p, gcrl_env_group* g, gcrl_her* const* rings, gcr
         return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d of member %d is at step %d of its episode, the member's ring has %d transitions staged for it", who, e, i,
                           g->t_host[(size_t)i * N + e], rings[i]->staged[e]);
   if (P == 1) {   // nothing to merge: the member's own loop on the group's one member
-    gcrl_env* v = gcrl::env_group_view(g);
     const long long s0 = a0->col_steps, l0 = a0->col_launches;
-    const int rc = gcrl_agent_collect(a0, v, rings[0], nz_obs ? nz_obs[0] : nullptr, update_stats, nz_dg ? nz_dg[0] : nullptr, update_goal_stats, steps, explore,
-                                      eval_mode, rows_out, stream);
-    gcrl::env_group_view_done(g);
+    const int rc = agent_collect_group(a0, g, rings[0], nz_obs ? nz_obs[0] : nullptr, update_stats, nz_dg ? nz_dg[0] : nullptr, update_goal_stats, steps, explore,
+                                       eval_mode, rows_out, stream);
     p->col_calls += 1; p->col_steps += a0->col_steps - s0; p->col_launches += a0->col_launches - l0;
     return rc;
   }

@@ -1,7 +1,8 @@
-// dev_env.h — device-resident goal environments (dev_env.hip): N independent envs of one built-in kind whose state, counters and the
-// blocks of a vector step live in device memory.  One env_step_kernel launch writes a step's `raw` and `pay` blocks in the layout
-// her_ring.hip's her_process_step_body reads and the next step's acting rows [obs | goal] in the layout the acting kernels read,
-// so an agent's collect loop (agent.hip) is act -> step -> process-step with nothing crossing to the host.
+// dev_env.h — device-resident goal environments: P x N independent envs of one built-in kind whose state, counters and the blocks of a
+// vector step live in device memory, behind ONE handle type, gcrl_env_group.  The ABI's gcrl_env is a group of one member and nothing
+// more.  One step launch writes every member's `raw` and `pay` blocks in the layout her_ring.hip's her_process_step_body reads and the
+// next step's acting rows [obs | goal] in the layout the acting kernels read, so a collect loop (agent.hip, agent_pop.inc) is
+// act -> step -> process-step with nothing crossing to the host.
 // The rule is restated in numpy in tests/dev_env_ref.py (reach, push) and tests/dev_env_pick_ref.py (pick), which are its definition.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,35 +20,10 @@ __host__ __device__ constexpr int env_action_dim(int kind) { return kind == GCRL
 __host__ __device__ constexpr int env_obs_dim(int kind) { return kind == GCRL_ENV_REACH ? 7 : kind == GCRL_ENV_PUSH ? 13 : 20; }
 __host__ __device__ constexpr int env_state_w(int kind) { return kind == GCRL_ENV_PICK ? 18 : 12; }
 
-struct gcrl_env {
-  int kind = 0, N = 0, T = 0, D = 0, device = 0;
-  int A = 3, SW = 12;                    // env_action_dim(kind), env_state_w(kind)
-  float thr = 0.f;
-  uint64_t seed = 0;
-  hipStream_t stream = nullptr;
-  // device state: everything a resume needs
-  float* state = nullptr;                // [N][SW]
-  int* t = nullptr;                      // [N] steps taken in the running episode
-  unsigned long long* cnt = nullptr;     // [N][3]: episode index (the RNG key), episodes finished, successes
-  double* rsum = nullptr;                // [N] reward sum
-  // blocks of a step
-  float* rows = nullptr;                 // [N][D + G] acting rows of the NEXT step
-  float* raw = nullptr;                  // [obs N*D | next_obs N*D | dg N*G | next_dg N*G | ag N*G | next_ag N*G]
-  float* pay = nullptr;                  // [N][kEnvPayW]: t | r | done = 0 | action(A) | next_ag(G)
-  float* script_act = nullptr;           // [N][A] the scripted controller's actions (gcrl_her_collect_scripted; allocated on first use)
-  int64_t steps = 0, launches = 0;       // vector steps taken / kernel launches issued since creation
-  std::vector<int32_t> t_host;           // host mirror of t: the step kernel's rule (t + 1, 0 at the horizon) needs no read-back
-
-  hipStream_t pick(void* s) const {
-    if (!s) return stream;
-    if (s == GCRL_STREAM_LEGACY) return (hipStream_t) nullptr;
-    return (hipStream_t)s;
-  }
-};
-
-// A group of P x N envs in single allocations (dev_env.hip): member m IS a gcrl_env(kind, N, seeds[m], ...) — same state, counters,
-// random-number keys and arithmetic — whose blocks are slices at the strides the population kernels take (rowchain.h RowActPop,
-// act_bn.h ActBnPop, her_ring.hip her_process_step_pop_kernel).
+// P x N envs in single allocations: the only struct that owns env memory.  Member m has its own seed, state, counters and
+// random-number keys; its blocks are slices at the strides the population kernels take (rowchain.h RowActPop, act_bn.h ActBnPop,
+// her_ring.hip her_process_step_pop_kernel).  The slices of member 0 of a one-member group are the contiguous blocks the single-agent
+// kernels take: no kernel reads the padding past N.
 constexpr int kEnvGroupMaxP = 16;        // a population's member limit
 struct gcrl_env_group {
   int kind = 0, P = 0, N = 0, T = 0, D = 0, device = 0;
@@ -57,31 +33,38 @@ struct gcrl_env_group {
   float thr = 0.f;
   uint64_t seeds[kEnvGroupMaxP] = {};
   hipStream_t stream = nullptr;
+  // device state: everything a resume needs
   float* state = nullptr;                // [P][N][SW]
-  int* t = nullptr;                      // [P][N]
-  unsigned long long* cnt = nullptr;     // [P][N][3]
-  double* rsum = nullptr;                // [P][N]
-  float* rows = nullptr;                 // [P][stride_n][D + G]
-  float* data = nullptr;                 // [P][stride]
-  double* noise64 = nullptr;             // [P][stride_n][A]: the exploration noise / eps of the next vector step (the collect loop's)
-  double* act64 = nullptr;               // [P][stride_n][A]: the acting launch's float64 actions (the collect and evaluate loops')
-  void* tabs = nullptr;                  // PopTabCache (pop.h) of the step launch's member tables
-  int64_t steps[kEnvGroupMaxP] = {}, launches = 0;
-  std::vector<int32_t> t_host;           // [P][N]: host mirror of t
-  const void* token = nullptr;           // unique per group ever created (a small serial, never an address): names the group in an agent's
-                                         // record of whose noise its stream last wrote, so a later group at a reused address is not mistaken for it
-  gcrl_env* view = nullptr;              // P == 1: the one member as a gcrl_env on the group's own memory (env_group_view)
+  int* t = nullptr;                      // [P][N] steps taken in the running episode
+  unsigned long long* cnt = nullptr;     // [P][N][3]: episode index (the RNG key), episodes finished, successes
+  double* rsum = nullptr;                // [P][N] reward sum
+  // blocks of a step
+  float* rows = nullptr;                 // [P][stride_n][D + G] acting rows of the NEXT step
+  float* data = nullptr;                 // [P][stride]: raw = [obs N*D | next_obs N*D | dg N*G | next_dg N*G | ag N*G | next_ag N*G], then
+                                         // pay [N][kEnvPayW] = t | r | done = 0 | action(A) | next_ag(G)
+  double* noise64 = nullptr;             // [P][stride_n][A]: the exploration noise / eps of the next vector step (the population collect loop's)
+  double* act64 = nullptr;               // [P][stride_n][A]: the acting launch's float64 actions (the population collect and evaluate loops')
+  float* script_act = nullptr;           // [N][A] the scripted controller's actions (gcrl_her_collect_scripted; allocated on first use)
+  void* tabs = nullptr;                  // P > 1: PopTabCache (pop.h) of the launches' member tables
+  int64_t steps[kEnvGroupMaxP] = {}, launches = 0;   // vector steps taken per member / kernel launches issued since creation
+  std::vector<int32_t> t_host;           // [P][N] host mirror of t: the step kernel's rule (t + 1, 0 at the horizon) needs no read-back
+  const void* token = nullptr;           // unique per handle ever created (a small serial, never an address): names the handle in an agent's
+                                         // record of whose noise its stream last wrote, so a later handle at a reused address is not mistaken for it
 
+  float* raw(int m = 0) const { return data + (size_t)m * stride; }
+  float* pay(int m = 0) const { return raw(m) + raw_floats; }
   hipStream_t pick(void* s) const {
     if (!s) return stream;
     if (s == GCRL_STREAM_LEGACY) return (hipStream_t) nullptr;
     return (hipStream_t)s;
   }
 };
+struct gcrl_env : gcrl_env_group {};     // the ABI's name of a one-member group
 
 namespace gcrl {
 
-// What env_step_pop_kernel needs of member m for one vector step.  src: where its actions come from.
+// ---- the handle's step launches (dev_env_group.hip, with all other host code of the handle)
+// What a step needs of member m.  src: where its actions come from.
 enum { kEnvActF32 = 0, kEnvActF64 = 1, kEnvActEps = 2 };
 struct EnvPopMember {
   const void* act;                       // [N][A] float32 (kEnvActF32) or float64 (kEnvActF64); ignored for kEnvActEps
@@ -92,19 +75,18 @@ struct EnvPopMember {
   int noise_on;
   unsigned long long noise_seed, noise_ctr0; double noise_scale;
 };
-// env_step_pop_kernel on `st`: one launch for all P x N envs; m[0 .. P)
+// One vector step of every member on `st`, m[0 .. P), one launch: env_step_pop_kernel for P > 1, and for a one-member group
+// env_step_kernel with the arguments built here from member 0's slices (no member table)
 int env_group_step_launch(gcrl_env_group* g, const EnvPopMember* m, hipStream_t st);
-// A one-member group as the gcrl_env it is: a handle on the group's own memory for the entries that take a gcrl_env (it owns nothing).
-// env_group_view_done takes the host mirror and the step count back into the group after such an entry has stepped it.
-gcrl_env* env_group_view(gcrl_env_group* g);
-void env_group_view_done(gcrl_env_group* g);
-
-// env_step_kernel on `st`: actions [N][A] as float32 (f64 == 0) or as the float64 the acting kernels write (rounded to float32 first)
-int env_step_launch(gcrl_env* e, const void* actions_dev, int f64, hipStream_t st);
-// the same with the collect loop's rider: the env's thread also writes the NEXT vector step's exploration noise, A elements per env —
-// noise[i * A + c] = hash_normal(noise_seed, noise_ctr0 + i * A + c) (as double) * noise_scale, stored as float64 or rounded to float32
-int env_step_launch_noise(gcrl_env* e, const void* actions_dev, int f64, void* noise, int noise_f64, unsigned long long noise_seed,
+// A one-member group's step from actions [N][A], float32 (f64 == 0) or the float64 the acting kernels write (rounded to float32 first)
+int env_step_launch(gcrl_env_group* g, const void* actions_dev, int f64, hipStream_t st);
+// the same with the collect loop's rider into a block of the caller's: the env's thread also writes the NEXT vector step's exploration
+// noise, A elements per env — noise[i * A + c] = hash_normal(noise_seed, noise_ctr0 + i * A + c) (as double) * noise_scale, stored as
+// float64 or rounded to float32
+int env_step_launch_noise(gcrl_env_group* g, const void* actions_dev, int f64, void* noise, int noise_f64, unsigned long long noise_seed,
                           unsigned long long noise_ctr0, double noise_scale, hipStream_t st);
+
+// ---- dev_env.hip's small launches
 // proc_pack_kernel: raw | pay from separate contiguous [n][.] float32 device tensors (the payload's t word: t[i] from device words, or t0 for every
 // env when t == null).  ag may be null (then that block and next_ag's are left as they are: no goal normaliser reads them).
 struct ProcPack {
@@ -120,8 +102,8 @@ int clipped_normal_fill(float* out, int n, unsigned long long seed, unsigned lon
 int normal_fill(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale, hipStream_t st);
 // out32[i] = float(in64[i]) for i < n
 int round_to_f32(const double* in64, float* out32, int n, hipStream_t st);
-// env_scripted_kernel (dev_env_script.hip) on `st`: the pick kind's scripted controller, float32 actions [N][A] to out; noise_std > 0 adds
-// float(double(hash_normal(seed, ctr0 + i * A + c)) * noise_std) before a final clamp to [-1, 1]
-int env_scripted_launch(gcrl_env* e, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st);
+// env_scripted_kernel (dev_env_script.hip) on `st` for a one-member group: the pick kind's scripted controller, float32 actions [N][A] to out;
+// noise_std > 0 adds float(double(hash_normal(seed, ctr0 + i * A + c)) * noise_std) before a final clamp to [-1, 1]
+int env_scripted_launch(gcrl_env_group* g, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st);
 
 }  // namespace gcrl

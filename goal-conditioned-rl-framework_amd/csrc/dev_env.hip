@@ -17,18 +17,15 @@
 // Random numbers: u(env, episode, component) = hash_below(seed, kEnvStream + env, 8 * episode + component, 2^24) * 2^-24.  No state
 // besides the counters, so an env's episode j is the same whatever N is and whenever it is reached.
 //
-// What an env's thread does on a reset and on a step lives in dev_env_body.h (env_reset_body, env_step_body): the kernels here and the
-// population kernels of dev_env_group.hip (gcrl_env_group: P x N envs in single allocations) call the same text, each on the EnvArgs of
-// one standalone env — so member m of a group IS a gcrl_env of seeds[m].
+// What an env's thread does on a reset and on a step lives in dev_env_body.h (env_reset_body, env_step_body).  This unit holds the
+// by-value kernels — one member's EnvArgs in the launch, no table — which every one-member group launches, a standalone gcrl_env
+// among them; dev_env_group.hip holds the member-table kernels of a group of several, which call the same text, and all host code of
+// the handle (gcrl_env_group, dev_env.h), the gcrl_env_* entries included.
 //
 // Kernel rules: every address comes from the handle or the group's member table (or, for the pack and fill launches, from the
 // caller's checked arguments); an env index >= N — for a group: a member index >= P — does nothing; no atomics; no waits between
 // workgroups; no per-thread scratch (every loop is over a small constant and unrolled); plain vector stores only.
-#include "dev_env.h"
-
-#include <vector>
-
-#include "dev_env_body.h"   // EnvArgs, env_reset_body, env_step_body
+#include "dev_env_body.h"   // dev_env.h, EnvArgs, env_reset_body, env_step_body
 
 namespace {
 
@@ -94,37 +91,23 @@ __global__ __launch_bounds__(256) void round_to_f32_kernel(const double* in64, f
   out32[i] = (float)in64[i];
 }
 
-EnvArgs base_args(gcrl_env* e) {
-  EnvArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.state = e->state; a.t = e->t; a.cnt = e->cnt; a.rsum = e->rsum;
-  a.rows = e->rows; a.raw = e->raw; a.pay = e->pay;
-  a.kind = e->kind; a.N = e->N; a.T = e->T; a.D = e->D; a.thr = e->thr; a.seed = e->seed;
-  return a;
-}
-
-bool known_kind(int kind) { return kind == GCRL_ENV_REACH || kind == GCRL_ENV_PUSH || kind == GCRL_ENV_PICK; }
-
-size_t state_bytes(const gcrl_env* e) {
-  return sizeof(EnvHeader) + (size_t)e->N * (e->SW * sizeof(float) + sizeof(int) + 3 * sizeof(unsigned long long) + sizeof(double)) +
-         (size_t)e->N * (e->D + kEnvG) * sizeof(float);
-}
-
 }  // namespace
 
 namespace gcrl {
 
-int env_step_launch(gcrl_env* e, const void* actions_dev, int f64, hipStream_t st) { return env_step_launch_noise(e, actions_dev, f64, nullptr, 0, 0, 0, 0.0, st); }
-
-int env_step_launch_noise(gcrl_env* e, const void* actions_dev, int f64, void* noise, int noise_f64, unsigned long long noise_seed,
-                          unsigned long long noise_ctr0, double noise_scale, hipStream_t st) {
-  EnvArgs a = base_args(e);
-  a.act = actions_dev; a.act_f64 = f64 ? 1 : 0;
-  a.noise = noise; a.noise_f64 = noise_f64; a.noise_seed = noise_seed; a.noise_ctr0 = noise_ctr0; a.noise_scale = noise_scale;
-  hipLaunchKernelGGL(env_step_kernel, dim3((e->N + 63) / 64), dim3(64), 0, st, a);
+int env_step_args_launch(const EnvArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(env_step_kernel, dim3((a.N + 63) / 64), dim3(64), 0, st, a);
   GCRL_HIP(hipGetLastError());
-  e->steps += 1; e->launches += 1;
-  for (int32_t& t : e->t_host) t = t + 1 == e->T ? 0 : t + 1;   // the kernel's rule for t
+  return GCRL_OK;
+}
+
+int env_reset_args_launch(const EnvArgs& a, const uint8_t* mask_host, hipStream_t st) {
+  ResetArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.a = a;
+  if (!a.restart) std::memcpy(q.mask, mask_host, (size_t)a.N);
+  hipLaunchKernelGGL(env_reset_kernel, dim3((a.N + 63) / 64), dim3(64), 0, st, q);
+  GCRL_HIP(hipGetLastError());
   return GCRL_OK;
 }
 
@@ -154,154 +137,6 @@ int round_to_f32(const double* in64, float* out32, int n, hipStream_t st) {
 }  // namespace gcrl
 
 extern "C" {
-
-gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device) {
-  auto bad = [](const char* m) -> gcrl_env* { gcrl::fail(GCRL_ERR_ARG, "gcrl_env_create: %s", m); return nullptr; };
-  if (!known_kind(kind)) return bad("kind: GCRL_ENV_REACH, GCRL_ENV_PUSH or GCRL_ENV_PICK required");
-  if (num_envs < 1 || num_envs > kEnvMaxN) return bad("num_envs: 1..1024 required");
-  if (max_steps < 1 || max_steps > 64) return bad("max_steps: 1..64 required (the replay ring's flush length limit)");
-  if (!(threshold > 0.f) || !(threshold < kBox)) return bad("threshold: must lie in (0, 0.3)");
-  if (kind != GCRL_ENV_REACH && !(2.0f * threshold <= kSpawn)) return bad("threshold: push and pick place the goal at least 2 * threshold from the puck and need 2 * threshold <= 0.15");
-  int ndev = gcrl_device_count();
-  if (ndev <= 0 || device < 0 || device >= ndev) {
-    gcrl::fail(GCRL_ERR_HIP, "gcrl_env_create: no usable HIP device (count=%d, requested %d); there is no CPU fallback", ndev, device);
-    return nullptr;
-  }
-  gcrl_env* e = new gcrl_env;
-  e->kind = kind; e->N = num_envs; e->T = max_steps; e->thr = threshold; e->seed = seed; e->device = device;
-  e->D = env_obs_dim(kind); e->A = env_action_dim(kind); e->SW = env_state_w(kind);
-  const size_t N = (size_t)num_envs, raw_floats = N * (2 * e->D + 4 * kEnvG);
-  auto ok = [&](hipError_t r, const char* what) {
-    if (r == hipSuccess) return true;
-    gcrl::fail(GCRL_ERR_HIP, "gcrl_env_create: %s failed: %s", what, hipGetErrorString(r));
-    return false;
-  };
-  bool good = ok(hipSetDevice(device), "hipSetDevice") && ok(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
-              ok(hipMalloc((void**)&e->state, N * e->SW * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->t, N * sizeof(int)), "hipMalloc") &&
-              ok(hipMalloc((void**)&e->cnt, N * 3 * sizeof(unsigned long long)), "hipMalloc") && ok(hipMalloc((void**)&e->rsum, N * sizeof(double)), "hipMalloc") &&
-              ok(hipMalloc((void**)&e->rows, N * (e->D + kEnvG) * sizeof(float)), "hipMalloc") && ok(hipMalloc((void**)&e->raw, raw_floats * sizeof(float)), "hipMalloc") &&
-              ok(hipMalloc((void**)&e->pay, N * kEnvPayW * sizeof(float)), "hipMalloc");
-  if (good) good = ok(hipMemset(e->state, 0, N * e->SW * sizeof(float)), "hipMemset") && ok(hipMemset(e->t, 0, N * sizeof(int)), "hipMemset") &&
-                   ok(hipMemset(e->cnt, 0, N * 3 * sizeof(unsigned long long)), "hipMemset") && ok(hipMemset(e->rsum, 0, N * sizeof(double)), "hipMemset") &&
-                   ok(hipMemset(e->raw, 0, raw_floats * sizeof(float)), "hipMemset") && ok(hipMemset(e->pay, 0, N * kEnvPayW * sizeof(float)), "hipMemset");
-  if (good) {
-    ResetArgs q;
-    std::memset(&q, 0, sizeof(q));
-    q.a = base_args(e);
-    q.a.restart = 1;
-    e->t_host.assign(N, 0);
-    hipLaunchKernelGGL(env_reset_kernel, dim3((e->N + 63) / 64), dim3(64), 0, (hipStream_t) nullptr, q);
-    good = ok(hipGetLastError(), "env_reset_kernel") && ok(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the first step runs on the CALLER's stream
-    e->launches += 1;
-  }
-  if (!good) { gcrl_env_destroy(e); return nullptr; }
-  return e;
-}
-
-void gcrl_env_destroy(gcrl_env* e) {
-  if (!e) return;
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  for (void* p : {(void*)e->state, (void*)e->t, (void*)e->cnt, (void*)e->rsum, (void*)e->rows, (void*)e->raw, (void*)e->pay, (void*)e->script_act})
-    if (p) (void)hipFree(p);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
-}
-
-int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps, float* threshold, uint64_t* seed) {
-  GCRL_CHECK_ARG(e, "gcrl_env_dims: null handle");
-  if (kind) *kind = e->kind;
-  if (num_envs) *num_envs = e->N;
-  if (obs_dim) *obs_dim = e->D;
-  if (goal_dim) *goal_dim = kEnvG;
-  if (ac_dim) *ac_dim = e->A;
-  if (max_steps) *max_steps = e->T;
-  if (threshold) *threshold = e->thr;
-  if (seed) *seed = e->seed;
-  return GCRL_OK;
-}
-
-int gcrl_env_buffers(gcrl_env* e, float** rows, float** raw, float** pay) {
-  GCRL_CHECK_ARG(e, "gcrl_env_buffers: null handle");
-  if (rows) *rows = e->rows;
-  if (raw) *raw = e->raw;
-  if (pay) *pay = e->pay;
-  return GCRL_OK;
-}
-
-int gcrl_env_reset(gcrl_env* e, const uint8_t* mask_host, void* stream) {
-  GCRL_CHECK_ARG(e, "gcrl_env_reset: null handle");
-  ResetArgs q;
-  std::memset(&q, 0, sizeof(q));
-  q.a = base_args(e);
-  q.a.restart = mask_host ? 0 : 1;
-  if (mask_host) std::memcpy(q.mask, mask_host, (size_t)e->N);
-  hipLaunchKernelGGL(env_reset_kernel, dim3((e->N + 63) / 64), dim3(64), 0, e->pick(stream), q);
-  GCRL_HIP(hipGetLastError());
-  e->launches += 1;
-  for (int i = 0; i < e->N; ++i) if (!mask_host || mask_host[i]) e->t_host[i] = 0;
-  if (!mask_host) e->steps = 0;
-  return GCRL_OK;
-}
-
-int gcrl_env_step(gcrl_env* e, const void* actions_dev, int actions_f64, void* stream) {
-  GCRL_CHECK_ARG(e && actions_dev, "gcrl_env_step: null argument");
-  return gcrl::env_step_launch(e, actions_dev, actions_f64, e->pick(stream));
-}
-
-int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream) {
-  GCRL_CHECK_ARG(e, "gcrl_env_stats: null handle");
-  std::vector<unsigned long long> cn((size_t)e->N * 3);
-  std::vector<double> rs((size_t)e->N);
-  hipStream_t st = e->pick(stream);
-  GCRL_HIP(hipMemcpyAsync(cn.data(), e->cnt, cn.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  GCRL_HIP(hipMemcpyAsync(rs.data(), e->rsum, rs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  GCRL_HIP(hipStreamSynchronize(st));
-  int64_t ep = 0, su = 0; double r = 0.0;
-  for (int i = 0; i < e->N; ++i) { ep += (int64_t)cn[(size_t)i * 3 + 1]; su += (int64_t)cn[(size_t)i * 3 + 2]; r += rs[i]; }
-  if (episodes) *episodes = ep;
-  if (successes) *successes = su;
-  if (reward_sum) *reward_sum = r;
-  return GCRL_OK;
-}
-
-int64_t gcrl_env_state_bytes(const gcrl_env* e) { return e ? (int64_t)state_bytes(e) : 0; }
-
-// blob: header | state [N][12] f32 (pick: [N][18]) | t [N] i32 | counters [N][3] u64 | reward sums [N] f64 | acting rows [N][D + G] f32
-int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream) {
-  GCRL_CHECK_ARG(e && dst_host && n == (int64_t)state_bytes(e), "gcrl_env_save_state: the blob is %lld bytes", e ? (long long)state_bytes(e) : 0ll);
-  hipStream_t st = e->pick(stream);
-  EnvHeader hd{kEnvMagic, e->kind, e->N, e->T, e->thr, 0u, e->seed, e->steps};
-  char* o = static_cast<char*>(dst_host);
-  std::memcpy(o, &hd, sizeof(hd)); o += sizeof(hd);
-  const size_t N = (size_t)e->N;
-  const void* src[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
-  const size_t len[5] = {N * e->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
-  for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(o, src[k], len[k], hipMemcpyDeviceToHost, st)); o += len[k]; }
-  GCRL_HIP(hipStreamSynchronize(st));
-  return GCRL_OK;
-}
-
-int gcrl_env_load_state(gcrl_env* e, const void* src_host, int64_t n, void* stream) {
-  GCRL_CHECK_ARG(e && src_host && n >= (int64_t)sizeof(EnvHeader), "gcrl_env_load_state: null argument or a blob shorter than its header");
-  EnvHeader hd;
-  std::memcpy(&hd, src_host, sizeof(hd));
-  GCRL_CHECK_ARG(hd.magic == kEnvMagic, "gcrl_env_load_state: not an environment state blob");
-  GCRL_CHECK_ARG(hd.kind == e->kind, "gcrl_env_load_state: kind: the blob holds kind %d, the handle %d", hd.kind, e->kind);
-  GCRL_CHECK_ARG(hd.N == e->N, "gcrl_env_load_state: num_envs: the blob holds %d envs, the handle %d", hd.N, e->N);
-  GCRL_CHECK_ARG(hd.T == e->T, "gcrl_env_load_state: max_steps: the blob holds %d, the handle %d", hd.T, e->T);
-  GCRL_CHECK_ARG(std::memcmp(&hd.thr, &e->thr, sizeof(float)) == 0, "gcrl_env_load_state: threshold: the blob holds %g, the handle %g", hd.thr, e->thr);
-  GCRL_CHECK_ARG(n == (int64_t)state_bytes(e), "gcrl_env_load_state: the blob is %lld bytes, expected %lld", (long long)n, (long long)state_bytes(e));
-  hipStream_t st = e->pick(stream);
-  const char* o = static_cast<const char*>(src_host) + sizeof(hd);
-  const size_t N = (size_t)e->N;
-  void* dst[5] = {e->state, e->t, e->cnt, e->rsum, e->rows};
-  const size_t len[5] = {N * e->SW * sizeof(float), N * sizeof(int), N * 3 * sizeof(unsigned long long), N * sizeof(double), N * (e->D + kEnvG) * sizeof(float)};
-  for (int k = 0; k < 5; ++k) { GCRL_HIP(hipMemcpyAsync(dst[k], o, len[k], hipMemcpyHostToDevice, st)); o += len[k]; }
-  GCRL_HIP(hipStreamSynchronize(st));   // (the source is the caller's pageable memory)
-  e->seed = hd.seed; e->steps = hd.steps;
-  std::memcpy(e->t_host.data(), static_cast<const char*>(src_host) + sizeof(hd) + len[0], len[1]);
-  return GCRL_OK;
-}
 
 // raw | pay of one vector step from separate contiguous float32 device tensors (for callers that hold the pieces separately)
 int gcrl_proc_pack(const float* obs, const float* next_obs, const float* dg, const float* next_dg, const float* ag, const float* next_ag,

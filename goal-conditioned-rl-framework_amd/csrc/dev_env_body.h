@@ -1,8 +1,10 @@
-// dev_env_body.h — the device text the environment units share: what an env's thread does on a reset and on a step, on the EnvArgs of ONE
-// gcrl_env.  dev_env.hip's env_reset_kernel / env_step_kernel call it with the handle's arguments; dev_env_group.hip's population
-// kernels call it with the arguments a standalone env of the member's seed would pass, pointed at the member's slices — so a group
-// member's arithmetic is a standalone env's by construction.  The rule is restated in numpy in tests/dev_env_ref.py (reach, push) and
-// tests/dev_env_pick_ref.py (pick), which are its definition.  Units that include this are built with -ffp-contract=off.
+// dev_env_body.h — what the environment units share: EnvArgs, the arguments of ONE member of a gcrl_env_group (a standalone gcrl_env is a
+// one-member group), and the device text of what an env's thread does with them on a reset and on a step.  dev_env.hip's
+// env_reset_kernel / env_step_kernel take an EnvArgs by value: the form every one-member group launches, with the arguments built on
+// the host from member 0's slices.  dev_env_group.hip's population kernels build the same EnvArgs per thread from the member table of
+// a group of several — so a member's arithmetic is the same text whichever form runs it.  The rule is restated in numpy in
+// tests/dev_env_ref.py (reach, push) and tests/dev_env_pick_ref.py (pick), which are its definition.  Units that include this are
+// built with -ffp-contract=off.
 //
 // The action width and the state record's width follow the kind (dev_env.h env_action_dim, env_state_w).  Every small array is
 // indexed by the constants of a fully unrolled loop, a fourth action component behind `c < A`: nothing lives in per-thread scratch.
@@ -10,15 +12,6 @@
 #include "dev_env.h"
 #include "her_ring.h"   // hash_below
 #include "ops.h"        // hash_normal
-
-namespace {
-
-constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
-constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
-constexpr float kFinger = 0.02f, kOpen = 0.08f, kClose = 0.04f, kFall = 0.04f;   // pick: finger travel per step, opening, grasp width, fall per step
-constexpr uint32_t kEnvMagic = 0x564e4547u;   // "GENV"
-// header of a saved env (gcrl_env_save_state); a group's blob holds one such record per member
-struct EnvHeader { uint32_t magic; int32_t kind, N, T; float thr; uint32_t pad; uint64_t seed; int64_t steps; };
 
 struct EnvArgs {
   float* state; int* t; unsigned long long* cnt; double* rsum;
@@ -33,6 +26,19 @@ struct EnvArgs {
   // rider of the collect loop: the exploration noise of the NEXT vector step, A elements per env, written by the env's thread
   void* noise; int noise_f64; unsigned long long noise_seed, noise_ctr0; double noise_scale;
 };
+
+namespace gcrl {
+// dev_env.hip, for the group's host code: the by-value kernels on `st`.  mask_host (a.N bytes) selects the envs that go on to their
+// next episode; it is ignored when a.restart is set
+int env_step_args_launch(const EnvArgs& a, hipStream_t st);
+int env_reset_args_launch(const EnvArgs& a, const uint8_t* mask_host, hipStream_t st);
+}  // namespace gcrl
+
+namespace {
+
+constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
+constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
+constexpr float kFinger = 0.02f, kOpen = 0.08f, kClose = 0.04f, kFall = 0.04f;   // pick: finger travel per step, opening, grasp width, fall per step
 
 __device__ inline float u01(unsigned long long seed, int env, unsigned long long ep, int comp) {
   return (float)gcrl::hash_below(seed, kEnvStream + (unsigned long long)env, 8ull * ep + (unsigned long long)comp, 1u << 24) * (1.0f / 16777216.0f);
@@ -139,7 +145,7 @@ __device__ inline float clean_action(float x) {
   return fminf(fmaxf(x, -1.0f), 1.0f);
 }
 
-// one step of env i of `a`: the body env_step_kernel and env_step_pop_kernel share, so a group member's step is a standalone env's
+// one step of env i of `a`: the body env_step_kernel and env_step_pop_kernel share, so a member's step is the same in a group of one and of many
 __device__ inline void env_step_body(const EnvArgs& a, int i) {
   const int N = a.N, D = a.D, A = env_action_dim(a.kind);
   EnvState s;

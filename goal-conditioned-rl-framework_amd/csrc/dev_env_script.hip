@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64) void env_scripted_kernel(ScriptArgs q) {
 
 namespace gcrl {
 
-int env_scripted_launch(gcrl_env* e, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st) {
+int env_scripted_launch(gcrl_env_group* e, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st) {
   ScriptArgs q;
   std::memset(&q, 0, sizeof(q));
   q.a.state = e->state; q.a.kind = e->kind; q.a.N = e->N;
@@ -116,7 +116,7 @@ int64_t gcrl_her_collect_scripted(gcrl_her* ring, gcrl_env* env, gcrl_normalizer
     if (int rc = gcrl::env_scripted_launch(env, env->script_act, noise_std, seed, (counter0 + (unsigned long long)s) * per_step, st)) return rc;
     t_before.assign(env->t_host.begin(), env->t_host.end());   // the payload's t words: the envs' step counts BEFORE the step
     if (int rc = gcrl::env_step_launch(env, env->script_act, 0, st)) return rc;
-    const int64_t r = gcrl_her_process_step_dev(ring, nz_obs, nz_obs ? 1 : 0, nz_dg, nz_dg ? 1 : 0, env->raw, env->pay, env->D, t_before.data(), nullptr, 0, N, sarg);
+    const int64_t r = gcrl_her_process_step_dev(ring, nz_obs, nz_obs ? 1 : 0, nz_dg, nz_dg ? 1 : 0, env->raw(), env->pay(), env->D, t_before.data(), nullptr, 0, N, sarg);
     if (r < 0) return r;
     total += r;
   }

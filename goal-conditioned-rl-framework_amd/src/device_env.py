@@ -40,7 +40,8 @@ class _DevBlock64(_DevBlock):
 class DeviceGoalEnvGroup:
     """`members` x `num_envs` envs in single allocations for a population (`pop.collect(group, steps)`, `pop.evaluate(group, episodes)`).
     Member m IS a `DeviceGoalEnv(kind, num_envs, seeds[m], ...)` — the same state, counters, random-number keys and arithmetic — whose
-    blocks are slices at the strides the population kernels read.  One launch steps or resets all members."""
+    blocks are slices at the strides the population kernels read.  One launch steps or resets all members.  The engine has this one
+    handle type: a `DeviceGoalEnv` is a group of one member under its own name, in the same layout."""
 
     HEADER_BYTES = 24           # of the group's state blob; the members' records follow, each a standalone env's blob
 
@@ -174,6 +175,9 @@ class DeviceGoalEnvGroup:
 
 
 class DeviceGoalEnv:
+    """`num_envs` envs of one kind and one seed: in the engine a one-member `DeviceGoalEnvGroup` (the same allocations, padded the
+    same way; the views below cover the envs' own share of them)."""
+
     def __init__(self, kind: str, num_envs: int, seed: int = 0, max_steps: int = 50, threshold: float = 0.05, device_index: int = 0):
         if kind not in KINDS:
             raise ValueError(f"DeviceGoalEnv: kind: {kind!r} (one of {sorted(KINDS)})")

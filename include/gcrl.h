@@ -1112,7 +1112,8 @@ int gcrl_bc_qfilter_f32(const float* spa_dev, const float* sa_dev, int ldx, int 
 /* ------------------------------------------------------------------------------------------
  * Device-resident goal environments, device-row acting entries and the collect loop.
  *
- * gcrl_env: N independent goal environments of one built-in kind in device memory (csrc/dev_env.hip; the rule is restated in
+ * gcrl_env: N independent goal environments of one built-in kind in device memory — a one-member gcrl_env_group (below) under a
+ * name and entries of its own (kernels csrc/dev_env.hip, host code csrc/dev_env_group.hip; the rule is restated in
  * tests/dev_env_ref.py and tests/dev_env_pick_ref.py, which are its definition).  G = 3, fixed horizon max_steps, sparse reward
  * -(dist > threshold) as the replay ring's built-in sparse kind forms it, no termination on success.  A is the kind's:
  * gcrl_env_dims reports it.  GCRL_ENV_REACH: A = 3, obs = [pos, vel, t/T] (7), achieved goal = pos.  GCRL_ENV_PUSH: A = 3, obs =
@@ -1209,7 +1210,8 @@ int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* step
  * definition stays tests/dev_env_ref.py, instantiated once per member).  The members' blocks are slices at the strides the
  * population kernels take: acting rows [members][stride_n][obs_dim + 3], step data [members][stride] floats with a member's slice
  * raw (raw_floats) | pay [num_envs][32], float64 noise / eps and float64 actions [members][stride_n][A].  stride_n > num_envs: the
- * rows past num_envs of a slice are never read and never written.
+ * rows past num_envs of a slice are never read and never written.  A group of one member launches env_step_kernel / env_reset_kernel
+ * (the member's arguments by value, no table) where a group of several launches env_step_pop_kernel / env_reset_pop_kernel.
  * ---------------------------------------------------------------------------------------- */
 typedef struct gcrl_env_group gcrl_env_group;
 /* members 1..16, seeds[members]; the other arguments as gcrl_env_create.  Every env starts at its episode 0. */
@@ -1254,7 +1256,7 @@ int gcrl_agent_evaluate(gcrl_agent* a, gcrl_env* env, gcrl_normalizer* nz_obs, g
  * order.  No host <-> device copy and no synchronisation.  Each member keeps its own exploration stream (gcrl_agent_collect_set; element
  * (c, i, j) with N = envs per member) and its counter; a first call, or a re-keyed stream, pays one fill launch per member concerned.
  * Member m then holds, bit for bit, what a standalone agent's gcrl_agent_collect on gcrl_env(seeds[m]) leaves.  A one-member
- * population hands the call to the member's own gcrl_agent_collect.  rows_out[members]: ring rows appended per member.
+ * population runs the member's own gcrl_agent_collect loop on the group.  rows_out[members]: ring rows appended per member.
  * Refused by field name before anything is consumed: env (null; members != the population's; more envs per member than ring slots,
  * batch_size or 1024; dimensions; device), max_steps, threshold, compute_reward, steps, nz_obs / nz_dg, normalize, t (naming the
  * member and the env), shared_ring (two members with one ring). */

@@ -1,7 +1,8 @@
 """GPU (-m gpu): the device-resident goal environments (gcrl_amd.DeviceGoalEnv; csrc/dev_env.hip) held bit for bit to their numpy
 definition tests/dev_env_ref.py: env_reset_kernel and env_step_kernel over two full episodes plus three steps — so an automatic
 reset and a mid-episode state are both covered — under actions with out-of-range, infinite and NaN components; the raw and pay
-blocks of every step, the acting rows, the counters, a state saved and loaded into a fresh handle, poison past N, refused loads.
+blocks of every step, the acting rows, the counters, a state saved and loaded into a fresh handle (also under agent.collect, after the
+saved handle is gone), poison past N, refused loads.
 
 No case provokes a fault: every buffer compared or poisoned is either the handle's own block (read only) or a test-owned tensor
 with room past N; the kernels' own guard (env index >= N does nothing) keeps every address inside its allocation."""
@@ -91,6 +92,40 @@ def test_reset_and_step_match_the_definition(gcrl, kind, n):
     fresh = E.RefEnv(kind, n, seed=3, max_steps=T_STEPS)
     _check_rows(dev, fresh)
     assert dev.stats() == dict(episodes=0, successes=0, reward_sum=0.0)
+
+
+@pytest.mark.parametrize("n", [5, 65])
+def test_collect_goes_on_bitwise_on_a_handle_loaded_from_a_blob(gcrl, n):
+    """agent.collect on a standalone env saved mid-episode and loaded into a fresh handle of another seed, after the first handle was
+    destroyed and a third created (which may get the first one's address): the ring blob, the normalisers and the env state are bit
+    for bit those of an uninterrupted twin.  The agent knows whose noise its stream last wrote by the handle's token, never by its
+    address, and the loaded record carries seed, step counts and the host mirror of t."""
+    import test_gpu_collect as TC
+    import test_gpu_her_prior as TP
+    from gcrl_amd.src.utils import DeviceRunningNormalizer
+
+    def agent():
+        cfg = TC.make_config("DDPG", hidden_dim=TC.H, layer_count=TC.L, batch_size=128, max_len=2000, k_future=4, **TC.TS.KINDS["DDPG"])
+        ag = gcrl.DDPG(TC.D + TC.G, TC.A, cfg, None, nenvs=n, gradient_step=4, rng="engine", seed=5)
+        ag.buffer.obs_normalizer, ag.buffer.dg_normalizer = DeviceRunningNormalizer(TC.D), DeviceRunningNormalizer(TC.G)
+        ag.buffer.compute_reward = TC.her_oracle.sparse_reward
+        return ag
+
+    mk = lambda seed: gcrl.DeviceGoalEnv("reach", n, seed=seed, max_steps=TC.T, threshold=TC.THR)
+    a, b = agent(), agent()
+    env, twin = mk(4), mk(4)
+    assert a.collect(env, 17) == b.collect(twin, 17)
+    blob = env.save_state()
+    loaded = mk(99)
+    loaded.load_state(blob)
+    env.__del__()                                     # the handle is destroyed here, not when the collector gets to it
+    third = mk(7)
+    assert loaded.seed == 4 and third.seed == 7
+    assert a.collect(loaded, TC.T) == b.collect(twin, TC.T) > 0      # across the horizon: every env flushes once
+    assert np.array_equal(TP._blob(a.buffer), TP._blob(b.buffer)), "ring blob"
+    assert TC._same_nz(a, b), "normalisers"
+    assert np.array_equal(loaded.save_state(), twin.save_state()), "env state"
+    assert loaded.stats() == twin.stats() and loaded.stats()["episodes"] == n
 
 
 def test_a_success_is_counted_with_a_strict_threshold(gcrl):

@@ -3,7 +3,7 @@ bit for bit to P standalone DeviceGoalEnv twins — which tests/test_gpu_dev_env
 actions: the step blocks, the acting rows, member_state(m), stats()[m]; a member on the epsilon step against a twin fed the clipped
 normals; masked, per-member and full resets; poison past n in every member's slice, the last member's included; a state loaded into a
 fresh group; refused loads.  P = 3 with n = 1, 5, 65 (65 crosses the 64-thread workgroup edge inside a member and between members)
-and P = 1; 2 T + 3 steps, float32 and float64 action tensors in turn.
+and P = 1 with n = 5, 65 (a one-member group runs env_step_kernel / env_reset_kernel, its one member also the epsilon member); 2 T + 3 steps, float32 and float64 action tensors in turn.
 
 No case provokes a fault: what is poisoned are the group's own padding rows and floats (inside its allocations), read back only."""
 import ctypes as C
@@ -71,7 +71,7 @@ def _check_state(group, twins, what):
 
 
 @pytest.mark.parametrize("kind", ["reach", "push"])
-@pytest.mark.parametrize("seeds,n", [([3, 8, 3], 1), ([3, 8, 3], 5), ([3, 8, 3], 65), ([6], 5)])
+@pytest.mark.parametrize("seeds,n", [([3, 8, 3], 1), ([3, 8, 3], 5), ([3, 8, 3], 65), ([6], 5), ([6], 65)])
 def test_group_members_are_standalone_envs(gcrl, kind, seeds, n):
     P = len(seeds)
     group, twins = _make(gcrl, kind, seeds, n)
