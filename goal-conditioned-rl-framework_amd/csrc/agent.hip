@@ -2489,6 +2489,15 @@ int gcrl_agent_rowchain_form(gcrl_agent* a) {
   return rc_lds_mul_forms(a);
 }
 
+int gcrl_agent_update_forms(gcrl_agent* a, int32_t* out, int n) {
+  GCRL_CHECK_ARG(a && out && n >= 0, "gcrl_agent_update_forms: null handle or output");
+  const int32_t v[10] = {4 * a->row_rg, a->rowchain, a->split_roles, a->rc_merge, a->split_k, a->rc_merge_k, a->ddpg_ksplit, a->opt_fuse,
+                         a->bn_slab, a->bn_rsplit};
+  const int m = std::min(n, 10);
+  for (int i = 0; i < m; ++i) out[i] = v[i];
+  return m;
+}
+
 int gcrl_agent_debug_meet_fault(gcrl_agent* a) {
   GCRL_CHECK_ARG(a, "gcrl_agent_debug_meet_fault: null handle");
   GCRL_HIP(hipDeviceSynchronize());

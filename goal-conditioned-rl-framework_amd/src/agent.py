@@ -411,6 +411,18 @@ class _EngineAgent:
         everywhere (GCRL_RC_GLOBAL_MUL=1, a shape the LDS rule refuses, or an agent without that launch).  Changes nothing."""
         return _ffi.check(lib.gcrl_agent_rowchain_form(self._h))
 
+    UPDATE_FORM_FIELDS = ("rows_per_workgroup", "rowchain", "split_roles", "rc_merge", "split_k", "rc_merge_k", "ddpg_ksplit", "opt_fuse",
+                          "bn_slab", "bn_rsplit")
+
+    def update_forms(self) -> dict:
+        """The launch rules this handle's update step runs under, as the engine settled them at creation (and switched since, where
+        a form with in-kernel waits went off): include/gcrl.h gcrl_agent_update_forms.  Read-only: for tests that name the form
+        they ran on."""
+        out = (C.c_int32 * len(self.UPDATE_FORM_FIELDS))()
+        n = _ffi.check(lib.gcrl_agent_update_forms(self._h, out, len(out)))
+        assert n == len(out), n
+        return dict(zip(self.UPDATE_FORM_FIELDS, (int(x) for x in out)))
+
     # ------------------------------------------------------------------ prior-data replay
     def _bind_prior(self):
         """Tell the engine which ring the tail rows of the next call's batches come from (gcrl_agent_set_prior); called by every update

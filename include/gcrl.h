@@ -692,6 +692,13 @@ int gcrl_agent_debug_meet_fault(gcrl_agent* a);
  * both; 0 also when no launch of the handle goes through that kernel (SAC, TQC).  Same results either way; changes nothing.
  * New design (the reference is eager PyTorch: no such forms). */
 int gcrl_agent_rowchain_form(gcrl_agent* a);
+/* The launch rules gcrl_agent_create settled for this handle, as they stand now (tests name the form they ran on): out[0..n) in this
+ * order, as many as n holds (at most 10) — rows per row-chain workgroup (4, 8 or 16), row chain (else the layer-per-launch schedule),
+ * split_roles (SAC: role-parallel chain launches), rc_merge (those merged into one launch), split_k (TD3: role-parallel critic phase),
+ * rc_merge_k (its two launches as one), ddpg_ksplit (DDPG: two-role critic phase), opt_fuse (fused dW + optimiser launch), bn_slab
+ * (SAC: BatchNorm slab launches), bn_rsplit (row groups per slab: 1 or 4).  Returns the number of fields written; reads the handle
+ * only: no kernel, launch or rule changes.  New design (the reference is eager PyTorch: no such forms). */
+int gcrl_agent_update_forms(gcrl_agent* a, int32_t* out, int n);
 /* device pointer of a named vector (parameters / grads), for zero-copy interop */
 int gcrl_agent_dev_ptr(gcrl_agent* a, const char* name, float** ptr_dev_out, int64_t* numel_out);
 
