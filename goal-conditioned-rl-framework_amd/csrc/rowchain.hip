@@ -196,7 +196,7 @@ __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int p
 // LM = false: the global-multiplier form (the chain's act' multipliers are loaded back from the global saves); true: from LDS
 template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {
-  kernarg_warm<sizeof(RowChainArgs)>();
+  kernarg_warm_once<sizeof(RowChainArgs)>();
 #include "rowchain_ddpg_body.inc"
 }
 
