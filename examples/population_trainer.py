@@ -16,7 +16,7 @@ overwritten slots are printed.  Without the flag the members run to the end as f
 `--shared-ring`: the members learn from ONE replay ring (and one pair of normalisers) that all their envs fill — every member sees the
 experience every member collects; with `--pbt` an exploit then copies weights and optimiser state only (there is no ring to copy).
 
-`--device-env reach|push|pick`: the envs live on the device (gcrl_amd.DeviceGoalEnvGroup) and the acting phase of a cycle is ONE native
+`--device-env reach|push|pick|glide`: the envs live on the device (gcrl_amd.DeviceGoalEnvGroup) and the acting phase of a cycle is ONE native
 call, `pop.collect(group, steps)`: three launches per vector step for all members, nothing crossing to the host.  The reported
 success rates — and the fitness of `--pbt` — come from `pop.evaluate` on a held-out group in which every member meets the same
 episodes (one seed for all members), run deterministically.  Without the flag the host path above is unchanged.
@@ -197,7 +197,7 @@ if __name__ == "__main__":
     ap.add_argument("--shared-ring", action="store_true", help="all members learn from one replay ring that all their envs fill")
     ap.add_argument("--relabel", default="push", choices=["push", "sample"],
                     help="push: relabelled copies stored at every flush (the reference's form); sample: rows stored once, relabelled when a batch is drawn")
-    ap.add_argument("--device-env", default=None, choices=["reach", "push", "pick"],
+    ap.add_argument("--device-env", default=None, choices=["reach", "push", "pick", "glide"],
                     help="device-resident envs: collect through pop.collect, success rates and the PBT fitness from pop.evaluate on a held-out group")
     args = ap.parse_args()
     out = train(args.agent, members=args.members, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, pbt=args.pbt,

@@ -12,10 +12,12 @@ and what it reports: success rate per cycle (does it learn?), env steps/s, gradi
 
     python examples/trainer_standin.py --agent DDPG --cycles 60
 
---device-env reach|push|pick runs the same cycle with the environment on the device (gcrl_amd.DeviceGoalEnv) and `agent.collect` in
+--device-env reach|push|pick|glide runs the same cycle with the environment on the device (gcrl_amd.DeviceGoalEnv) and `agent.collect` in
 place of the Python loop: acting, the env's step and _process_step are three launches per vector step and nothing crosses to the host.
 `pick` has the dimensions of PandaPickAndPlace (state 23, action 4); with it --prior-episodes fills the prior ring on the device too,
-from the env's scripted controller (HERBuffer.collect_scripted on a second DeviceGoalEnv of another seed).  With --bc-weight the agent
+from the env's scripted controller (HERBuffer.collect_scripted on a second DeviceGoalEnv of another seed).  `glide` (state 19, action 3:
+a puck that has to be struck towards goals out of the pusher's reach) has its controller too and fills the prior ring the same way.
+With --bc-weight the agent
 runs the layer-per-launch schedule, which `collect` does not serve: its actions then come from `observe_act`, while the env's step and
 `process_step_dev` stay on the device.
 """
@@ -110,7 +112,7 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     if device_env is not None:
         fused = True          # collect needs the normalisers on the device
-        if (prior_episodes or prior_rows) and device_env != "pick":
+        if (prior_episodes or prior_rows) and device_env not in ("pick", "glide"):
             raise SystemExit("--device-env: the scripted prior episodes come from the host point-mass environment; not combined here")
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
         RunningNormalizer = DeviceRunningNormalizer
@@ -134,8 +136,8 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     if prior_episodes or prior_rows:   # prior-data replay: prior_rows of every batch come from a second ring the agent never pushes into
         if not (prior_episodes and prior_rows):
             raise SystemExit("--prior-episodes and --prior-rows go together")
-        # pick: the demonstrations come from a second device env under its scripted controller, up to 16 episodes side by side
-        demo_envs = min(prior_episodes, 16) if device_env == "pick" else 1
+        # pick, glide: the demonstrations come from a second device env under its scripted controller, up to 16 episodes side by side
+        demo_envs = min(prior_episodes, 16) if device_env in ("pick", "glide") else 1
         demo_rounds = -(-prior_episodes // demo_envs)
         prior = gcrl_amd.HERBuffer(50 * demo_rounds * demo_envs, 50, demo_envs, threshold=env.thr, k_future=cfg.k_future, rng="device", seed=seed,
                                    relabel="sample", normalize=normalize)
@@ -152,11 +154,11 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
     agent.buffer.obs_normalizer = RunningNormalizer(env.obs_dim)
     agent.buffer.dg_normalizer = RunningNormalizer(env.goal_dim)
     agent.buffer.compute_reward = host_env.compute_reward
-    if prior is not None and device_env == "pick":
+    if prior is not None and device_env in ("pick", "glide"):
         # demonstrations without the host: the controller's launch, the env's step and the process-step launch per vector step.  The prior
         # ring takes the agent's normalisers: the scripted rows update them and (normalize="push") are stored normalised with them
         prior.obs_normalizer, prior.dg_normalizer = agent.buffer.obs_normalizer, agent.buffer.dg_normalizer
-        demo = gcrl_amd.DeviceGoalEnv("pick", demo_envs, seed=seed + 4242, max_steps=host_env.T, threshold=host_env.thr)
+        demo = gcrl_amd.DeviceGoalEnv(device_env, demo_envs, seed=seed + 4242, max_steps=host_env.T, threshold=host_env.thr)
         prior.collect_scripted(demo, demo_rounds * demo.max_steps)
         st = demo.stats()
         if verbose:
@@ -261,7 +263,7 @@ if __name__ == "__main__":
     ap.add_argument("--cycles", type=int, default=60)
     ap.add_argument("--nenv", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--device-env", default=None, choices=["reach", "push", "pick"],
+    ap.add_argument("--device-env", default=None, choices=["reach", "push", "pick", "glide"],
                     help="run the environment on the device (gcrl_amd.DeviceGoalEnv) and collect with agent.collect: no host in the acting loop")
     ap.add_argument("--per-env-push", action="store_true", help="push one env at a time, exactly as the reference's trainer does")
     ap.add_argument("--fused", action="store_true", help="device normalisers + one native call for acting and one for _process_step")
@@ -280,7 +282,7 @@ if __name__ == "__main__":
                          "--fused): rows are stored raw and every gathered batch is normalised with the statistics of that moment")
     ap.add_argument("--prior-episodes", type=int, default=0,
                     help="fill a prior ring with this many scripted episodes of the synthetic goal environment (with --prior-rows); with "
-                         "--device-env pick they come from the device env's scripted controller, rounded up to a multiple of min(E, 16)")
+                         "--device-env pick or glide they come from the device env's scripted controller, rounded up to a multiple of min(E, 16)")
     ap.add_argument("--prior-rows", type=int, default=0,
                     help="rows of every batch that come from the prior ring, 1 .. batch - 1 (prior-data replay; the batch is 256)")
     ap.add_argument("--bc-weight", type=float, default=None,

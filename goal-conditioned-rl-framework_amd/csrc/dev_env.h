@@ -3,7 +3,8 @@
 // more.  One step launch writes every member's `raw` and `pay` blocks in the layout her_ring.hip's her_process_step_body reads and the
 // next step's acting rows [obs | goal] in the layout the acting kernels read, so a collect loop (agent.hip, agent_pop.inc) is
 // act -> step -> process-step with nothing crossing to the host.
-// The rule is restated in numpy in tests/dev_env_ref.py (reach, push) and tests/dev_env_pick_ref.py (pick), which are its definition.
+// The rule is restated in numpy in tests/dev_env_ref.py (reach, push), tests/dev_env_pick_ref.py (pick) and tests/dev_env_glide_ref.py
+// (glide), which are its definition.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,10 +16,12 @@ constexpr int kEnvG = 3;                 // goal width of every kind
 constexpr int kEnvPayW = 32;             // floats per env of the payload block (her_ring.hip kPayW)
 constexpr int kEnvMaxN = 1024;
 // per kind: action width, observation width, and floats per env of the state record —
-// p(3) q(3) vel_p(3) goal(3), and for pick | w held vel_q(3) vel_w
+// p(3) q(3) vel_p(3) goal(3), for pick | w held vel_q(3) vel_w, for glide | vel_q(3)
 __host__ __device__ constexpr int env_action_dim(int kind) { return kind == GCRL_ENV_PICK ? 4 : 3; }
-__host__ __device__ constexpr int env_obs_dim(int kind) { return kind == GCRL_ENV_REACH ? 7 : kind == GCRL_ENV_PUSH ? 13 : 20; }
-__host__ __device__ constexpr int env_state_w(int kind) { return kind == GCRL_ENV_PICK ? 18 : 12; }
+__host__ __device__ constexpr int env_obs_dim(int kind) {
+  return kind == GCRL_ENV_REACH ? 7 : kind == GCRL_ENV_PUSH ? 13 : kind == GCRL_ENV_GLIDE ? 16 : 20;
+}
+__host__ __device__ constexpr int env_state_w(int kind) { return kind == GCRL_ENV_PICK ? 18 : kind == GCRL_ENV_GLIDE ? 15 : 12; }
 
 // P x N envs in single allocations: the only struct that owns env memory.  Member m has its own seed, state, counters and
 // random-number keys; its blocks are slices at the strides the population kernels take (rowchain.h RowActPop, act_bn.h ActBnPop,
@@ -102,7 +105,7 @@ int clipped_normal_fill(float* out, int n, unsigned long long seed, unsigned lon
 int normal_fill(void* out, int f64, int n, unsigned long long seed, unsigned long long ctr0, double scale, hipStream_t st);
 // out32[i] = float(in64[i]) for i < n
 int round_to_f32(const double* in64, float* out32, int n, hipStream_t st);
-// env_scripted_kernel (dev_env_script.hip) on `st` for a one-member group: the pick kind's scripted controller, float32 actions [N][A] to out;
+// env_scripted_kernel (dev_env_script.hip) on `st` for a one-member group: the pick or glide kind's scripted controller, float32 actions [N][A] to out;
 // noise_std > 0 adds float(double(hash_normal(seed, ctr0 + i * A + c)) * noise_std) before a final clamp to [-1, 1]
 int env_scripted_launch(gcrl_env_group* g, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st);
 

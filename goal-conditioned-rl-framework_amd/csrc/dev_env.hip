@@ -1,4 +1,4 @@
-// dev_env.hip — three built-in goal environments that live on the device (dev_env.h), and the small launches the device-row acting
+// dev_env.hip — four built-in goal environments that live on the device (dev_env.h), and the small launches the device-row acting
 // entries and the collect loop of agent.hip need around them.
 //
 //   reach (D = 7, A = 3)    a point mass in a box: obs = [pos, vel, t / T], achieved goal = pos
@@ -7,12 +7,15 @@
 //   pick  (D = 20, A = 4)   a gripper with a finger opening w and an object that rests on the table: obs = [p, q, q - p, vel_p, vel_q, w,
 //                           vel_w, held, near, t / T], achieved goal = q; the object is grasped when the fingers close around it, moves
 //                           with the gripper while they stay closed and falls when released; half the goals lie in the air
+//   glide (D = 16, A = 3)   a pusher and a puck that keeps moving: obs = [p, q, q - p, vel_p, vel_q, t / T], achieved goal = q; a touched
+//                           puck takes the pusher's displacement, a free one keeps 0.9 of its last displacement per step, a wall stops
+//                           the component that meets it; the goals lie beyond the pusher's box, so the puck has to be struck and let go
 //
 // G = 3, fixed horizon T, sparse reward -(dist > thr) formed as the replay ring's relabelling kernels form it, no termination.
 // All arithmetic is float32, one rounding per operation (the unit is built with -ffp-contract=off): + - * /, comparisons,
 // fminf / fmaxf and the correctly rounded square root of the reward's distance.  The rule — constants, operation order, what a NaN
 // action counts as, the random-number keys — is restated in numpy in tests/dev_env_ref.py (reach, push) and
-// tests/dev_env_pick_ref.py (pick), which are its definition.
+// tests/dev_env_pick_ref.py (pick) and tests/dev_env_glide_ref.py (glide), which are its definition.
 //
 // Random numbers: u(env, episode, component) = hash_below(seed, kEnvStream + env, 8 * episode + component, 2^24) * 2^-24.  No state
 // besides the counters, so an env's episode j is the same whatever N is and whenever it is reached.

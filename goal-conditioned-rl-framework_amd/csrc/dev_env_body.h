@@ -3,8 +3,8 @@
 // env_reset_kernel / env_step_kernel take an EnvArgs by value: the form every one-member group launches, with the arguments built on
 // the host from member 0's slices.  dev_env_group.hip's population kernels build the same EnvArgs per thread from the member table of
 // a group of several — so a member's arithmetic is the same text whichever form runs it.  The rule is restated in numpy in
-// tests/dev_env_ref.py (reach, push) and tests/dev_env_pick_ref.py (pick), which are its definition.  Units that include this are
-// built with -ffp-contract=off.
+// tests/dev_env_ref.py (reach, push), tests/dev_env_pick_ref.py (pick) and tests/dev_env_glide_ref.py (glide), which are its
+// definition.  Units that include this are built with -ffp-contract=off.
 //
 // The action width and the state record's width follow the kind (dev_env.h env_action_dim, env_state_w).  Every small array is
 // indexed by the constants of a fully unrolled loop, a fourth action component behind `c < A`: nothing lives in per-thread scratch.
@@ -39,6 +39,7 @@ namespace {
 constexpr unsigned long long kEnvStream = 0x4445562d454e5621ull;   // "DEV-ENV!"
 constexpr float kStep = 0.04f, kBox = 0.3f, kSpawn = 0.15f, kContact = 0.05f, kLift = 0.1f;
 constexpr float kFinger = 0.02f, kOpen = 0.08f, kClose = 0.04f, kFall = 0.04f;   // pick: finger travel per step, opening, grasp width, fall per step
+constexpr float kFriction = 0.9f, kFar = 0.9f;                                   // glide: share of its displacement a free puck keeps, the far wall in x
 
 __device__ inline float u01(unsigned long long seed, int env, unsigned long long ep, int comp) {
   return (float)gcrl::hash_below(seed, kEnvStream + (unsigned long long)env, 8ull * ep + (unsigned long long)comp, 1u << 24) * (1.0f / 16777216.0f);
@@ -47,7 +48,7 @@ __device__ inline float spawn(float u) { return (u * 2.0f - 1.0f) * kSpawn; }
 __device__ inline float clamp_box(float x) { return fminf(fmaxf(x, -kBox), kBox); }
 __device__ inline float clamp_z(float x) { return fminf(fmaxf(x, 0.0f), kBox); }
 
-// pick alone uses w (finger opening), held (0 / 1), vq (the object's displacement of the last step) and vw (the fingers')
+// pick alone uses w (finger opening), held (0 / 1) and vw (the fingers' displacement of the last step); pick and glide use vq (the object's)
 struct EnvState { float p[3], q[3], vel[3], goal[3]; float w, held, vq[3], vw; };
 
 __device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, EnvState& s) {
@@ -57,6 +58,12 @@ __device__ inline void seed_env(const EnvArgs& a, int i, unsigned long long ep, 
   if (a.kind == GCRL_ENV_REACH) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { s.p[c] = spawn(u01(a.seed, i, ep, c)); s.q[c] = 0.f; s.goal[c] = spawn(u01(a.seed, i, ep, 3 + c)); }
+  } else if (a.kind == GCRL_ENV_GLIDE) {
+    s.q[0] = spawn(u01(a.seed, i, ep, 0)); s.q[1] = spawn(u01(a.seed, i, ep, 1)); s.q[2] = 0.f;
+    s.p[0] = spawn(u01(a.seed, i, ep, 2)); s.p[1] = spawn(u01(a.seed, i, ep, 3)); s.p[2] = kLift;
+    s.goal[0] = 0.45f + u01(a.seed, i, ep, 4) * 0.2f;          // beyond the pusher's box
+    s.goal[1] = spawn(u01(a.seed, i, ep, 5));
+    s.goal[2] = 0.f;
   } else {
     s.q[0] = spawn(u01(a.seed, i, ep, 0)); s.q[1] = spawn(u01(a.seed, i, ep, 1)); s.q[2] = 0.f;
     s.p[0] = spawn(u01(a.seed, i, ep, 2)); s.p[1] = spawn(u01(a.seed, i, ep, 3)); s.p[2] = kLift;
@@ -77,6 +84,9 @@ __device__ inline void load_state(const EnvArgs& a, int i, EnvState& s) {
     s.w = w[12]; s.held = w[13]; s.vw = w[17];
 #pragma unroll
     for (int c = 0; c < 3; ++c) s.vq[c] = w[14 + c];
+  } else if (a.kind == GCRL_ENV_GLIDE) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s.vq[c] = w[12 + c];
   }
 }
 __device__ inline void store_state(const EnvArgs& a, int i, const EnvState& s) {
@@ -87,6 +97,9 @@ __device__ inline void store_state(const EnvArgs& a, int i, const EnvState& s) {
     w[12] = s.w; w[13] = s.held; w[17] = s.vw;
 #pragma unroll
     for (int c = 0; c < 3; ++c) w[14 + c] = s.vq[c];
+  } else if (a.kind == GCRL_ENV_GLIDE) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[12 + c] = s.vq[c];
   }
 }
 // squared distance of x and y, the squares summed in component order
@@ -107,6 +120,10 @@ __device__ inline void write_obs(const EnvArgs& a, const EnvState& s, int t, flo
 #pragma unroll
     for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; }
     o[12] = tt;
+  } else if (a.kind == GCRL_ENV_GLIDE) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; o[12 + c] = s.vq[c]; }
+    o[15] = tt;
   } else {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { o[c] = s.p[c]; o[3 + c] = s.q[c]; o[6 + c] = s.q[c] - s.p[c]; o[9 + c] = s.vel[c]; o[12 + c] = s.vq[c]; }
@@ -204,6 +221,14 @@ __device__ inline void env_step_body(const EnvArgs& a, int i) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { s.vq[c] = qn[c] - s.q[c]; s.q[c] = qn[c]; }
     s.vw = wn - s.w; s.w = wn; s.held = held ? 1.0f : 0.0f;
+  } else if (a.kind == GCRL_ENV_GLIDE) {
+    // a touched puck takes the pusher's displacement, a free one keeps kFriction of its own; a wall stops that component
+    const bool contact = dist2(pn, s.q) < kContact * kContact;
+    const float dx = contact ? pn[0] - s.p[0] : kFriction * s.vq[0];
+    const float dy = contact ? pn[1] - s.p[1] : kFriction * s.vq[1];
+    const float qx = fminf(fmaxf(s.q[0] + dx, -kBox), kFar), qy = clamp_box(s.q[1] + dy);
+    s.vq[0] = qx - s.q[0]; s.vq[1] = qy - s.q[1]; s.vq[2] = 0.0f - s.q[2];
+    s.q[0] = qx; s.q[1] = qy; s.q[2] = 0.f;
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) s.p[c] = pn[c];

@@ -172,14 +172,15 @@ int env_group_reset(gcrl_env_group* g, const uint8_t* mask_host, hipStream_t st)
 
 int env_group_init(gcrl_env_group* g, const char* who, int kind, int members, int num_envs, const uint64_t* seeds, int max_steps, float threshold,
                    int device) {
-  GCRL_CHECK_ARG(kind == GCRL_ENV_REACH || kind == GCRL_ENV_PUSH || kind == GCRL_ENV_PICK, "%s: kind: GCRL_ENV_REACH, GCRL_ENV_PUSH or GCRL_ENV_PICK required", who);
+  GCRL_CHECK_ARG(kind == GCRL_ENV_REACH || kind == GCRL_ENV_PUSH || kind == GCRL_ENV_PICK || kind == GCRL_ENV_GLIDE,
+                 "%s: kind: GCRL_ENV_REACH, GCRL_ENV_PUSH, GCRL_ENV_PICK or GCRL_ENV_GLIDE required", who);
   GCRL_CHECK_ARG(members >= 1 && members <= kEnvGroupMaxP, "%s: members: 1..16 required", who);
   GCRL_CHECK_ARG(seeds, "%s: seeds: null array", who);
   GCRL_CHECK_ARG(num_envs >= 1 && num_envs <= kEnvMaxN, "%s: num_envs: 1..1024 required", who);
   GCRL_CHECK_ARG(max_steps >= 1 && max_steps <= 64, "%s: max_steps: 1..64 required (the replay ring's flush length limit)", who);
   GCRL_CHECK_ARG(threshold > 0.f && threshold < kBox, "%s: threshold: must lie in (0, 0.3)", who);
   GCRL_CHECK_ARG(kind == GCRL_ENV_REACH || 2.0f * threshold <= kSpawn,
-                 "%s: threshold: push and pick place the goal at least 2 * threshold from the puck and need 2 * threshold <= 0.15", who);
+                 "%s: threshold: push and pick place the goal at least 2 * threshold from the puck and need 2 * threshold <= 0.15; glide keeps the limit", who);
   const int ndev = gcrl_device_count();
   if (ndev <= 0 || device < 0 || device >= ndev)
     return gcrl::fail(GCRL_ERR_HIP, "%s: no usable HIP device (count=%d, requested %d); there is no CPU fallback", who, ndev, device);

@@ -1,13 +1,24 @@
-// dev_env_script.hip — the pick kind's scripted controller as a device kernel, and the native loop that fills a HER ring from it
-// (include/gcrl.h gcrl_env_scripted_act, gcrl_her_collect_scripted).  The controller is defined by scripted_action in
-// tests/dev_env_pick_ref.py, in float32 with one rounding per operation:
+// dev_env_script.hip — the pick and glide kinds' scripted controllers as one device kernel, and the native loop that fills a HER ring
+// from it (include/gcrl.h gcrl_env_scripted_act, gcrl_her_collect_scripted).  Both are stateless functions of the env's state record,
+// in float32 with one rounding per operation.  pick, defined by scripted_action in tests/dev_env_pick_ref.py:
 //
 //   held:  a[c] = clamp((goal[c] - q[c]) / STEP, -1, 1);  a[3] = -1                      carry the object to the goal, fingers closed
 //   else:  d = q - p;  s = sum_c d[c]^2
 //          s < 0.01 * 0.01 ?  a = (0, 0, 0, -1)                                           over the object: close the fingers
 //                          :  a[c] = clamp(d[c] / STEP, -1, 1), a[3] = +1                 go to the object, fingers open
 //
-// Optional noise, float(double(hash_normal(seed, ctr0 + i * 4 + c)) * noise_std), is added before a final clamp to [-1, 1].
+// glide, defined by scripted_action in tests/dev_env_glide_ref.py — strike the puck so that its glide ends on the goal, then let go:
+//
+//   d = goal.xy - q.xy;  L = sqrt(d.x^2 + d.y^2);  L < 1e-6 ?  a = 0
+//   u = d / L;  rest = (sqrt(vq.x^2 + vq.y^2) * FRICTION) / (1 - FRICTION)              the way the puck still glides by itself
+//   rest >= L - 0.5 * thr ?  a = (unit(-u.x), unit(-u.y), 0)                             hands off: it will arrive
+//   e = (q.xy - 0.03 * u) - p.xy;  off = e.x^2 + e.y^2                                   the striking position behind the puck
+//   off > 0.005^2:  p.z < LIFT - 0.005 and off > 0.02^2 ?  a = (0, 0, unit((LIFT - p.z) / STEP))        rise before travelling
+//                   else a.xy = unit(e / STEP), a.z = unit(((off > 0.02^2 ? LIFT : 0) - p.z) / STEP)
+//   p.z > 0.005:    a.xy = unit(e / STEP), a.z = unit((0 - p.z) / STEP)                  descend behind the puck
+//   else            v = L > 0.9 * (STEP / (1 - FRICTION)) ? STEP : L * (1 - FRICTION);  a.xy = unit(u * v / STEP), a.z = 0
+//
+// Optional noise, float(double(hash_normal(seed, ctr0 + i * A + c)) * noise_std), is added before a final clamp to [-1, 1].
 //
 // Kernel rules (dev_env.hip's): every address comes from the handle or the caller's checked arguments; an env index >= N does
 // nothing; no atomics; no waits; no per-thread scratch; plain vector stores only; the unit is built with -ffp-contract=off.
@@ -16,10 +27,14 @@
 namespace {
 
 constexpr float kReached = 0.01f * 0.01f;
+// glide: 1 - FRICTION, the striking position's distance behind the puck, "in place" and "travel at LIFT" squared distances, the
+// slack in z, and the distance beyond which one strike cannot reach the goal
+constexpr float kOneMinusF = 1.0f - kFriction, kBehind = 0.03f, kNear2 = 0.005f * 0.005f, kAway2 = 0.02f * 0.02f, kSlack = 0.005f;
+constexpr float kCarry = 0.9f * (kStep / kOneMinusF);
 
 struct ScriptArgs {
-  EnvArgs a;              // state, kind and N alone are read
-  float* out;             // [N][4]
+  EnvArgs a;              // state, kind, N and thr alone are read
+  float* out;             // [N][A]
   int noisy; double noise_std; unsigned long long seed, ctr0;
 };
 
@@ -30,8 +45,36 @@ __global__ __launch_bounds__(64) void env_scripted_kernel(ScriptArgs q) {
   if (i >= q.a.N) return;
   EnvState s;
   load_state(q.a, i, s);
+  const int A = env_action_dim(q.a.kind);
   float act[4];
-  if (s.held != 0.f) {
+  if (q.a.kind == GCRL_ENV_GLIDE) {
+    act[0] = 0.f; act[1] = 0.f; act[2] = 0.f; act[3] = 0.f;
+    const float dx = s.goal[0] - s.q[0], dy = s.goal[1] - s.q[1];
+    const float L = sqrtf(dx * dx + dy * dy);
+    if (!(L < 1e-6f)) {
+      const float ux = dx / L, uy = dy / L;
+      const float rest = (sqrtf(s.vq[0] * s.vq[0] + s.vq[1] * s.vq[1]) * kFriction) / kOneMinusF;
+      const float ex = (s.q[0] - kBehind * ux) - s.p[0], ey = (s.q[1] - kBehind * uy) - s.p[1];
+      const float off = ex * ex + ey * ey;
+      if (rest >= L - 0.5f * q.a.thr) {
+        act[0] = unit(-ux); act[1] = unit(-uy);
+      } else if (off > kNear2) {
+        const bool away = off > kAway2;
+        if (s.p[2] < kLift - kSlack && away) {
+          act[2] = unit((kLift - s.p[2]) / kStep);
+        } else {
+          act[0] = unit(ex / kStep); act[1] = unit(ey / kStep);
+          act[2] = unit(((away ? kLift : 0.0f) - s.p[2]) / kStep);
+        }
+      } else if (s.p[2] > kSlack) {
+        act[0] = unit(ex / kStep); act[1] = unit(ey / kStep);
+        act[2] = unit((0.0f - s.p[2]) / kStep);
+      } else {
+        const float v = L > kCarry ? kStep : L * kOneMinusF;
+        act[0] = unit((ux * v) / kStep); act[1] = unit((uy * v) / kStep);
+      }
+    }
+  } else if (s.held != 0.f) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) act[c] = unit((s.goal[c] - s.q[c]) / kStep);
     act[3] = -1.0f;
@@ -44,12 +87,14 @@ __global__ __launch_bounds__(64) void env_scripted_kernel(ScriptArgs q) {
     for (int c = 0; c < 3; ++c) act[c] = over ? 0.0f : unit(d[c] / kStep);
     act[3] = over ? -1.0f : 1.0f;
   }
-  float* o = q.out + (size_t)i * 4;
+  float* o = q.out + (size_t)i * A;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    float x = act[c];
-    if (q.noisy) x = unit(x + (float)((double)gcrl::hash_normal(q.seed, q.ctr0 + (unsigned long long)i * 4 + c) * q.noise_std));
-    o[c] = x;
+    if (c < A) {
+      float x = act[c];
+      if (q.noisy) x = unit(x + (float)((double)gcrl::hash_normal(q.seed, q.ctr0 + (unsigned long long)i * A + c) * q.noise_std));
+      o[c] = x;
+    }
   }
 }
 
@@ -60,7 +105,7 @@ namespace gcrl {
 int env_scripted_launch(gcrl_env_group* e, float* out, double noise_std, unsigned long long seed, unsigned long long ctr0, hipStream_t st) {
   ScriptArgs q;
   std::memset(&q, 0, sizeof(q));
-  q.a.state = e->state; q.a.kind = e->kind; q.a.N = e->N;
+  q.a.state = e->state; q.a.kind = e->kind; q.a.N = e->N; q.a.thr = e->thr;
   q.out = out; q.noisy = noise_std > 0.0 ? 1 : 0; q.noise_std = noise_std; q.seed = seed; q.ctr0 = ctr0;
   hipLaunchKernelGGL(env_scripted_kernel, dim3((e->N + 63) / 64), dim3(64), 0, st, q);
   GCRL_HIP(hipGetLastError());
@@ -75,7 +120,8 @@ extern "C" {
 int gcrl_env_scripted_act(gcrl_env* env, float* out_dev, double noise_std, uint64_t seed, uint64_t counter, void* stream) {
   const char* who = "gcrl_env_scripted_act";
   GCRL_CHECK_ARG(env && out_dev, "%s: null argument", who);
-  GCRL_CHECK_ARG(env->kind == GCRL_ENV_PICK, "%s: kind: the scripted controller is the pick kind's; this env has kind %d", who, env->kind);
+  GCRL_CHECK_ARG(env->kind == GCRL_ENV_PICK || env->kind == GCRL_ENV_GLIDE, "%s: kind: the pick and glide kinds alone have a scripted controller; this env has kind %d", who,
+                 env->kind);
   GCRL_CHECK_ARG(noise_std >= 0.0 && noise_std <= 1e30, "%s: noise_std: a finite value >= 0 required", who);
   return gcrl::env_scripted_launch(env, out_dev, noise_std, seed, counter * (unsigned long long)env->N * env->A, env->pick(stream));
 }
@@ -86,7 +132,8 @@ int64_t gcrl_her_collect_scripted(gcrl_her* ring, gcrl_env* env, gcrl_normalizer
   GCRL_CHECK_ARG(ring && env, "%s: null argument", who);
   // every refusal comes before a ring slot or a step of the env is consumed
   GCRL_CHECK_ARG(steps >= 1, "%s: steps: %d (>= 1 required)", who, steps);
-  GCRL_CHECK_ARG(env->kind == GCRL_ENV_PICK, "%s: kind: the scripted controller is the pick kind's; this env has kind %d", who, env->kind);
+  GCRL_CHECK_ARG(env->kind == GCRL_ENV_PICK || env->kind == GCRL_ENV_GLIDE, "%s: kind: the pick and glide kinds alone have a scripted controller; this env has kind %d", who,
+                 env->kind);
   GCRL_CHECK_ARG(noise_std >= 0.0 && noise_std <= 1e30, "%s: noise_std: a finite value >= 0 required", who);
   GCRL_CHECK_ARG(env->device == ring->cfg.device, "%s: env: it lives on device %d, the ring on device %d", who, env->device, ring->cfg.device);
   GCRL_CHECK_ARG(env->N <= ring->cfg.nenvs, "%s: env: %d envs for a ring of %d episode slots", who, env->N, ring->cfg.nenvs);

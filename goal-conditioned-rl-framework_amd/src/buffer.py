@@ -710,7 +710,7 @@ class HERBuffer(_RingState):
         return int(rows)
 
     def collect_scripted(self, env, steps: int, noise_std: float = 0.0, seed: int = 0, counter: int | None = None) -> int:
-        """`steps` vector steps of a `DeviceGoalEnv("pick", ...)` under its scripted controller into this ring as ONE native call: per step
+        """`steps` vector steps of a `DeviceGoalEnv("pick", ...)` or `DeviceGoalEnv("glide", ...)` under its scripted controller into this ring as ONE native call: per step
         the controller's launch, the env's step and the process-step launch, plus the flush launches of the envs that finish — no
         host <-> device copy, no synchronisation (include/gcrl.h gcrl_her_collect_scripted).  Demonstrations for a prior-data ring
         without the host.  The normalisers assigned to `obs_normalizer` / `dg_normalizer` are used and updated where the constructor's
@@ -719,12 +719,12 @@ class HERBuffer(_RingState):
         vector steps this buffer has collected so far) is the first step's.  Returns the ring rows appended.  Refusals name their
         field and come before anything is consumed."""
         who = "HERBuffer.collect_scripted"
-        from .device_env import DeviceGoalEnv
+        from .device_env import SCRIPTED, DeviceGoalEnv
         from .utils import DeviceRunningNormalizer
         if not isinstance(env, DeviceGoalEnv):
             raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnv required")
-        if env.kind != "pick":
-            raise _ffi.GcrlError(f"{who}: kind: the scripted controller is the 'pick' kind's, this env is {env.kind!r}")
+        if env.kind not in SCRIPTED:
+            raise _ffi.GcrlError(f"{who}: kind: the 'pick' and 'glide' kinds alone have a scripted controller, this env is {env.kind!r}")
         if int(steps) < 1:
             raise ValueError(f"{who}: steps: {steps} (>= 1 required)")
         nz = []

@@ -3,11 +3,13 @@ step blocks live in device memory.  `agent.collect(env, steps)` drives them with
 `step_blocks()` hand out tensor views for callers who drive `observe_act_dev` / `process_step_dev` themselves.
 
 The rule of every kind — constants, operation order, random-number keys — is restated in numpy in tests/dev_env_ref.py (`reach`,
-`push`) and tests/dev_env_pick_ref.py (`pick`), which are its definition.  The envs are not panda-gym: `reach` is the point mass of
+`push`), tests/dev_env_pick_ref.py (`pick`) and tests/dev_env_glide_ref.py (`glide`), which are its definition.  The envs are not panda-gym: `reach` is the point mass of
 examples/trainer_standin.py in float32 (obs 7, action 3), `push` a pusher that carries a puck along while it is inside a contact
 radius (obs 13, action 3), `pick` a gripper whose fingers grasp an object by closing around it, at the dimensions of
-PandaPickAndPlace (obs 20, goal 3, action 4: gripper velocity and finger velocity); half of its goals lie above the table.  `pick`
-has its scripted controller on the device: `scripted_actions()`, and `HERBuffer.collect_scripted(env, steps)` fills a ring from it."""
+PandaPickAndPlace (obs 20, goal 3, action 4: gripper velocity and finger velocity); half of its goals lie above the table, `glide` a
+pusher and a puck that keeps 0.9 of its displacement per step once it is let go (obs 16, action 3), with goals beyond the pusher's box:
+the puck has to be struck, not carried (it is not PandaSlide; the name "slide" stays an unknown kind).  `pick` and `glide` have their
+scripted controllers on the device: `scripted_actions()`, and `HERBuffer.collect_scripted(env, steps)` fills a ring from them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +20,8 @@ import torch
 from .. import _ffi
 from .._ffi import lib
 
-KINDS = {"reach": 0, "push": 1, "pick": 2}
+KINDS = {"reach": 0, "push": 1, "pick": 2, "glide": 3}
+SCRIPTED = ("pick", "glide")      # the kinds whose scripted controller is built
 PAY_W = 32
 
 
@@ -257,12 +260,14 @@ class DeviceGoalEnv:
         _ffi.check(lib.gcrl_env_step(self._h, actions.data_ptr(), 1 if actions.dtype == torch.float64 else 0, _ffi.stream_handle()))
 
     def scripted_actions(self, noise_std: float = 0.0, seed: int = 0, counter: int = 0):
-        """The `pick` kind's scripted controller on the envs as they stand, one launch: a CUDA float32 tensor [N, 4] (go to the object
-        with open fingers, close them over it, carry it to the goal; tests/dev_env_pick_ref.py scripted_action is the definition).
-        noise_std > 0 adds float32(float64(hash_normal(seed, (counter * N + env) * 4 + component)) * noise_std) before a final clamp
-        to [-1, 1].  `reach` / `push` have no controller: refused naming `kind`."""
-        if self.kind != "pick":
-            raise _ffi.GcrlError(f"DeviceGoalEnv.scripted_actions: kind: the scripted controller is the 'pick' kind's, this env is {self.kind!r}")
+        """The `pick` or `glide` kind's scripted controller on the envs as they stand, one launch: a CUDA float32 tensor [N, ac_dim].
+        `pick`: go to the object with open fingers, close them over it, carry it to the goal (tests/dev_env_pick_ref.py scripted_action
+        is the definition).  `glide`: travel to a point behind the puck, descend, carry it while the goal is too far for one strike,
+        strike it with the speed whose glide ends on the goal, and let go (tests/dev_env_glide_ref.py scripted_action).
+        noise_std > 0 adds float32(float64(hash_normal(seed, (counter * N + env) * ac_dim + component)) * noise_std) before a final
+        clamp to [-1, 1].  `reach` / `push` have no controller: refused naming `kind`."""
+        if self.kind not in SCRIPTED:
+            raise _ffi.GcrlError(f"DeviceGoalEnv.scripted_actions: kind: the 'pick' and 'glide' kinds alone have a scripted controller, this env is {self.kind!r}")
         out = torch.empty((self.num_envs, self.ac_dim), dtype=torch.float32, device=f"cuda:{self.device_index}")
         _ffi.check(lib.gcrl_env_scripted_act(self._h, out.data_ptr(), float(noise_std), int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
                                              _ffi.stream_handle()))

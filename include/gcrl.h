@@ -1121,18 +1121,21 @@ int gcrl_bc_qfilter_f32(const float* spa_dev, const float* sa_dev, int ldx, int 
  *
  * gcrl_env: N independent goal environments of one built-in kind in device memory — a one-member gcrl_env_group (below) under a
  * name and entries of its own (kernels csrc/dev_env.hip, host code csrc/dev_env_group.hip; the rule is restated in
- * tests/dev_env_ref.py and tests/dev_env_pick_ref.py, which are its definition).  G = 3, fixed horizon max_steps, sparse reward
+ * tests/dev_env_ref.py, tests/dev_env_pick_ref.py and tests/dev_env_glide_ref.py, which are its definition).  G = 3, fixed horizon max_steps, sparse reward
  * -(dist > threshold) as the replay ring's built-in sparse kind forms it, no termination on success.  A is the kind's:
  * gcrl_env_dims reports it.  GCRL_ENV_REACH: A = 3, obs = [pos, vel, t/T] (7), achieved goal = pos.  GCRL_ENV_PUSH: A = 3, obs =
  * [pusher, puck, puck - pusher, pusher velocity, t/T] (13), achieved goal = puck.  GCRL_ENV_PICK: A = 4 (gripper velocity, finger
  * velocity), obs = [gripper, object, object - gripper, gripper velocity, object velocity, finger opening, finger velocity, held,
  * near, t/T] (20), achieved goal = object; the object is grasped when the fingers close around it, moves with the gripper while
- * they stay closed and falls when released; half the goals lie above the table.  Random numbers are a counter hash keyed by
+ * they stay closed and falls when released; half the goals lie above the table.  GCRL_ENV_GLIDE: A = 3, obs = [pusher, puck, puck -
+ * pusher, pusher velocity, puck velocity, t/T] (16), achieved goal = puck; a touched puck takes the pusher's displacement, a free one
+ * keeps 0.9 of its last displacement per step, walls at x = -0.3 / 0.9 and y = +-0.3 stop that component; the goals lie at x in
+ * [0.45, 0.65], beyond the pusher's box, so the puck has to be struck and let go.  Random numbers are a counter hash keyed by
  * (seed, episode index of the env, env, component): an env's episode j does not depend on N.
  * ---------------------------------------------------------------------------------------- */
 typedef struct gcrl_env gcrl_env;
-enum { GCRL_ENV_REACH = 0, GCRL_ENV_PUSH = 1, GCRL_ENV_PICK = 2 };
-/* num_envs 1..1024, max_steps 1..64, 0 < threshold < 0.3 (push, pick: 2 * threshold <= 0.15).  Every env starts at its episode 0. */
+enum { GCRL_ENV_REACH = 0, GCRL_ENV_PUSH = 1, GCRL_ENV_PICK = 2, GCRL_ENV_GLIDE = 3 };
+/* num_envs 1..1024, max_steps 1..64, 0 < threshold < 0.3 (push, pick, glide: 2 * threshold <= 0.15).  Every env starts at its episode 0. */
 gcrl_env* gcrl_env_create(int kind, int num_envs, uint64_t seed, int max_steps, float threshold, int device);
 void gcrl_env_destroy(gcrl_env* e);
 int gcrl_env_dims(const gcrl_env* e, int* kind, int* num_envs, int* obs_dim, int* goal_dim, int* ac_dim, int* max_steps, float* threshold, uint64_t* seed);
@@ -1148,7 +1151,7 @@ int gcrl_env_reset(gcrl_env* e, const uint8_t* mask_host, void* stream);
 int gcrl_env_step(gcrl_env* e, const void* actions_dev, int actions_f64, void* stream);
 /* Synchronises.  Episodes finished, those that ended with dist < threshold, and the reward sum, over all envs since the last full reset. */
 int gcrl_env_stats(gcrl_env* e, int64_t* episodes, int64_t* successes, double* reward_sum, void* stream);
-/* State arrays (12 floats per env; pick: 18), counters, acting rows and the seed; resume is bitwise.  Loading refuses another kind, num_envs, max_steps or
+/* State arrays (12 floats per env; pick: 18; glide: 15), counters, acting rows and the seed; resume is bitwise.  Loading refuses another kind, num_envs, max_steps or
  * threshold by that field's name before anything is overwritten. */
 int64_t gcrl_env_state_bytes(const gcrl_env* e);
 int gcrl_env_save_state(gcrl_env* e, void* dst_host, int64_t n, void* stream);
@@ -1174,17 +1177,17 @@ int gcrl_agent_observe_act_dev(gcrl_agent* a, gcrl_normalizer* nz_obs, gcrl_norm
 int64_t gcrl_her_process_step_dev(gcrl_her* h, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg, int update_goal_stats,
                                   const float* raw_dev, const float* pay_dev, int obs_dim, const int32_t* t_host, const uint8_t* dones_host,
                                   int env0, int n, void* stream);
-/* The pick kind's scripted controller (env_scripted_kernel, csrc/dev_env_script.hip; tests/dev_env_pick_ref.py scripted_action is its
- * definition), one launch: float32 actions [N][4] to out_dev.  noise_std > 0 adds float(double(hash_normal(seed, (counter * N + i) * 4 + j)) *
- * noise_std) to element (i, j) before a final clamp to [-1, 1].  Refused: kind (reach and push have no controller), noise_std (negative
- * or not finite). */
+/* The pick or glide kind's scripted controller (env_scripted_kernel, csrc/dev_env_script.hip; scripted_action of tests/dev_env_pick_ref.py
+ * and of tests/dev_env_glide_ref.py is its definition), one launch: float32 actions [N][A] to out_dev (A = 4 / 3).  noise_std > 0 adds
+ * float(double(hash_normal(seed, (counter * N + i) * A + j)) * noise_std) to element (i, j) before a final clamp to [-1, 1].  Refused: kind
+ * (reach and push have no controller), noise_std (negative or not finite). */
 int gcrl_env_scripted_act(gcrl_env* env, float* out_dev, double noise_std, uint64_t seed, uint64_t counter, void* stream);
-/* `steps` vector steps of a pick env under its scripted controller into ring, as a native loop: per step env_scripted_kernel, the env's
+/* `steps` vector steps of a pick or glide env under its scripted controller into ring, as a native loop: per step env_scripted_kernel, the env's
  * step on those float32 actions and the process-step launch on the env's blocks (gcrl_her_process_step_dev: its normaliser
  * arguments, its raw-store form on a normalize = "sample" ring), plus the flush launches — no host <-> device copy, no
  * synchronisation.  The noise of vector step s of the call is that of counter counter0 + s.  Fills any ring, a prior-data ring
  * included.  Refused by field name before anything is consumed, as gcrl_agent_collect refuses: env (more envs than ring slots;
- * dimensions; device), max_steps, compute_reward, threshold, steps, nz_obs / nz_dg, t, and kind (not a pick env), noise_std.
+ * dimensions; device), max_steps, compute_reward, threshold, steps, nz_obs / nz_dg, t, and kind (neither a pick nor a glide env), noise_std.
  * Returns the ring rows appended, or a negative error code. */
 int64_t gcrl_her_collect_scripted(gcrl_her* ring, gcrl_env* env, gcrl_normalizer* nz_obs, gcrl_normalizer* nz_dg, int steps, double noise_std,
                                   uint64_t seed, uint64_t counter0, void* stream);

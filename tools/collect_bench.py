@@ -16,9 +16,9 @@ issued one after another (3 P launches per vector step) — what the code could 
 seven alternating samples.  With --run: the population's steps for the profiler; --parse then also lists the population kernels.
 --run issues, for the profiler, STEPS collect steps at every N; nothing is timed there.  --parse prints, per kernel, the launches
 after the warm-up ones: number, median, range in us.  No --pmc in that run.
---kind reach|push|pick (default reach): the env kind of every mode above.  `pick` has the headline's own dimensions (S 23 = obs 20 +
+--kind reach|push|pick|glide (default reach): the env kind of every mode above.  `pick` has the headline's own dimensions (S 23 = obs 20 +
 goal 3, A 4), so --kind pick times the on-device loop on the network the project is measured on; its host path steps the numpy
-definition tests/dev_env_pick_ref.py.
+definition tests/dev_env_pick_ref.py.  `glide` (S 19, A 3) steps tests/dev_env_glide_ref.py there.
 No GPU: --cost and --run fail."""
 import argparse
 import csv
@@ -34,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 D, G, A, T, THR = 7, 3, 3, 50, 0.05
 KIND = "reach"
-DIMS = dict(reach=(7, 3), push=(13, 3), pick=(20, 4))      # obs_dim, action_dim per kind
+DIMS = dict(reach=(7, 3), push=(13, 3), pick=(20, 4), glide=(16, 3))      # obs_dim, action_dim per kind
 H, L, B = 256, 3, 256
 NS = (8, 32, 256)
 SAMPLES, WARM = 7, 10
@@ -57,6 +57,9 @@ def _ref_env(n):
     if KIND == "pick":
         import dev_env_pick_ref as PK
         return PK.RefPickEnv(n, seed=3, max_steps=T, threshold=THR)
+    if KIND == "glide":
+        import dev_env_glide_ref as GL
+        return GL.RefGlideEnv(n, seed=3, max_steps=T, threshold=THR)
     import dev_env_ref as E
     return E.RefEnv(KIND, n, seed=3, max_steps=T, threshold=THR)
 
