@@ -107,13 +107,16 @@ def fill_prior_ring(agent, prior, episodes, normalize, seed):
 
 def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step=40, hidden=64, layers=3, batch=256,
           seed=0, verbose=True, per_env_push=False, fused=False, relabel="push", n_step=1, prioritise=None,
-          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0, bc_weight=None, q_filter=True, device_env=None):
+          goal_strategy="future", normalize="push", prior_episodes=0, prior_rows=0, bc_weight=None, q_filter=True, device_env=None,
+          practice=False, practice_share=0.5, practice_radius=0.05):
     import gcrl_amd
     from gcrl_amd.src.utils import DeviceRunningNormalizer, RunningNormalizer
     if device_env is not None:
         fused = True          # collect needs the normalisers on the device
         if (prior_episodes or prior_rows) and device_env not in ("pick", "glide"):
             raise SystemExit("--device-env: the scripted prior episodes come from the host point-mass environment; not combined here")
+    if practice and device_env is None:
+        raise SystemExit("--practice proposes goals for a device env: it needs --device-env")
     if fused:   # the normalisers live on the device; acting and _process_step are one native call each per vector step
         RunningNormalizer = DeviceRunningNormalizer
     if normalize == "sample" and not fused:
@@ -168,6 +171,8 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
 
     if device_env is None:
         state, _ = env.reset()
+    # practice goals: an env that finishes an episode may start the next one on an archived achieved goal of low density instead of its task goal
+    proposer = gcrl_amd.GoalProposer(candidates=16, radius=practice_radius, share=practice_share, min_fill=max(256, num_envs), seed=seed) if practice else None
     grad_counter, env_steps = 1, 0
     success_per_cycle, final_success = [], []
     t_env = t_upd = 0.0
@@ -179,7 +184,7 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
             rounds = -(-max_episode // num_envs)
             before = env.stats()
             if bc_weight is None:
-                agent.collect(env, rounds * env.max_steps)
+                agent.collect(env, rounds * env.max_steps, practice=proposer)
             else:
                 # a behaviour-cloning agent runs the layer-per-launch schedule, which has no one-launch acting kernel for `collect`:
                 # its actions come from the host entry, the env's step and the process-step stay on the device
@@ -188,6 +193,8 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
                     act = agent.observe_act(rows["observation"].cpu().numpy(), rows["desired_goal"].cpu().numpy())
                     act = torch.from_numpy(np.asarray(act, dtype=np.float32)).cuda()
                     env.step(act)
+                    if proposer is not None:     # the host-loop call order: observe_act -> env.step -> proposer.step(env) -> process_step
+                        proposer.step(env)
                     raw, pay = env.step_blocks()
                     o, no, g, ng, a_, na = env.split_raw(raw)
                     agent.process_step_dev(dict(observation=o, desired_goal=g, achieved_goal=a_), act,
@@ -253,6 +260,12 @@ def train(agent_name="DDPG", num_envs=8, cycles=60, max_episode=8, gradient_step
             if bc_weight is not None and grad_counter > 1:
                 print("            bc_loss %.4g  accepted share of the prior rows %.2f" % agent.bc_metrics())
     wall = time.perf_counter() - t0
+    if proposer is not None:
+        # with practice goals the per-cycle success above is measured against the goals the episodes had, practised ones included;
+        # evaluate() restarts the env and so scores the task goals of the env's seed alone
+        task = agent.evaluate(env, 4 * num_envs)
+        print(f"practice goals: {proposer.stats()}, archive {len(proposer)}; task success of agent.evaluate: "
+              f"{task['successes']} / {task['episodes']} = {task['success_rate']:.2f}")
     return dict(success_per_cycle=success_per_cycle, env_steps=env_steps, gradient_steps=grad_counter - 1, wall_s=wall,
                 env_steps_per_s=env_steps / max(t_env, 1e-9), gradient_steps_per_s=(grad_counter - 1) / max(t_upd, 1e-9))
 
@@ -265,6 +278,11 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device-env", default=None, choices=["reach", "push", "pick", "glide"],
                     help="run the environment on the device (gcrl_amd.DeviceGoalEnv) and collect with agent.collect: no host in the acting loop")
+    ap.add_argument("--practice", action="store_true",
+                    help="with --device-env: practice goals (gcrl_amd.GoalProposer) — a finished env may start its next episode on an archived "
+                         "achieved goal of low density; prints the proposer's stats and the task success of agent.evaluate at the end")
+    ap.add_argument("--practice-share", type=float, default=0.5, help="with --practice: the share of finished envs that take a proposal, in (0, 1]")
+    ap.add_argument("--practice-radius", type=float, default=0.05, help="with --practice: the radius inside which archive entries count as neighbours")
     ap.add_argument("--per-env-push", action="store_true", help="push one env at a time, exactly as the reference's trainer does")
     ap.add_argument("--fused", action="store_true", help="device normalisers + one native call for acting and one for _process_step")
     ap.add_argument("--relabel", default="push", choices=["push", "sample"],
@@ -294,7 +312,8 @@ if __name__ == "__main__":
     out = train(args.agent, num_envs=args.nenv, cycles=args.cycles, seed=args.seed, per_env_push=args.per_env_push, fused=args.fused,
                 relabel=args.relabel, n_step=args.n_step, prioritise=args.prioritise, goal_strategy=args.goal_strategy,
                 normalize=args.normalize, prior_episodes=args.prior_episodes, prior_rows=args.prior_rows,
-                bc_weight=args.bc_weight, q_filter=not args.no_q_filter, device_env=args.device_env)
+                bc_weight=args.bc_weight, q_filter=not args.no_q_filter, device_env=args.device_env,
+                practice=args.practice, practice_share=args.practice_share, practice_radius=args.practice_radius)
     tail = out["success_per_cycle"][-10:]
     print(f"{args.agent}: success over the last 10 cycles {np.mean(tail):.2f}; {out['env_steps']} env steps "
           f"({out['env_steps_per_s']:.0f}/s in the acting phase), {out['gradient_steps']} gradient steps "

@@ -14,6 +14,7 @@ from .src.agent import DDPG, SACAgent, TD3Agent, TQCAgent  # noqa: F401
 from .src.population import DDPGPopulation, SACPopulation, TD3Population, TQCPopulation  # noqa: F401
 from .src.buffer import HERBuffer, MTStream, PERBuffer, ReplayBuffer  # noqa: F401
 from .src.device_env import DeviceGoalEnv, DeviceGoalEnvGroup  # noqa: F401
+from .src.goal_propose import GoalProposer  # noqa: F401
 
-__all__ = ["DDPG", "DDPGPopulation", "TD3Agent", "TD3Population", "SACAgent", "SACPopulation", "TQCAgent", "TQCPopulation", "HERBuffer", "DeviceGoalEnv", "DeviceGoalEnvGroup", "ReplayBuffer", "PERBuffer", "MTStream", "agent", "buffer",
+__all__ = ["DDPG", "DDPGPopulation", "TD3Agent", "TD3Population", "SACAgent", "SACPopulation", "TQCAgent", "TQCPopulation", "HERBuffer", "DeviceGoalEnv", "DeviceGoalEnvGroup", "GoalProposer", "ReplayBuffer", "PERBuffer", "MTStream", "agent", "buffer",
            "model", "utils"]

@@ -331,6 +331,19 @@ PROTOTYPES = {
     "gcrl_agent_bc_metrics": (C.c_int, [_vp, _i64, _vp]),
     "gcrl_bc_qfilter_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _f64, _vp, C.c_int,
                                       _vp, _vp, _vp]),
+    "gcrl_goal_proposer_create": (_vp, [C.c_int, C.c_int, _f32, _f32, C.c_int, _u64, C.c_int]),
+    "gcrl_goal_proposer_destroy": (None, [_vp]),
+    "gcrl_goal_proposer_bind_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gcrl_goal_proposer_step": (C.c_int, [_vp, _vp, _vp]),
+    "gcrl_goal_proposer_stats": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "gcrl_goal_proposer_get": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(C.c_int),
+                                         C.POINTER(_u64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.POINTER(_u64), C.POINTER(C.c_int)]),
+    "gcrl_goal_proposer_read": (C.c_int, [_vp, _vp, _vp]),
+    "gcrl_goal_proposer_state_bytes": (_i64, [_vp]),
+    "gcrl_goal_proposer_save_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_goal_proposer_load_state": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gcrl_agent_collect_practice": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "gcrl_event_create": (_vp, []),
     "gcrl_event_destroy": (None, [_vp]),
     "gcrl_event_record": (C.c_int, [_vp, _vp]),

@@ -30,6 +30,7 @@
 
 #include "act_bn.h"
 #include "dev_env.h"
+#include "goal_propose.h"
 #include "dw_adam.h"
 #include "gemm_mfma.h"
 #include "her_ring.h"
@@ -2968,10 +2969,12 @@ int gcrl_agent_collect_get(const gcrl_agent* a, uint64_t* seed, double* noise_st
   return GCRL_OK;
 }
 
-// gcrl_agent_collect on a one-member group: the standalone env of the entry below, or a one-member population's group (gcrl_pop_collect)
+// gcrl_agent_collect on a one-member group: the standalone env of the entry below, or a one-member population's group (gcrl_pop_collect).
+// practice: null, or the goal proposer whose launches follow each env step (gcrl_agent_collect_practice)
 static int agent_collect_group(gcrl_agent* a, gcrl_env_group* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
-                               int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
-  const char* who = "gcrl_agent_collect";
+                               int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream,
+                               gcrl_goal_proposer* practice = nullptr) {
+  const char* who = practice ? "gcrl_agent_collect_practice" : "gcrl_agent_collect";
   GCRL_CHECK_ARG(a && env && ring && rows_out, "%s: null argument", who);
   // every refusal comes before a counter, a ring slot or a draw of the exploration stream is consumed
   GCRL_CHECK_ARG(steps >= 1, "%s: steps: %d (>= 1 required)", who, steps);
@@ -2995,6 +2998,7 @@ static int agent_collect_group(gcrl_agent* a, gcrl_env_group* env, gcrl_her* rin
   for (int i = 0; i < N; ++i)
     if (env->t_host[i] != ring->staged[i])
       return gcrl::fail(GCRL_ERR_STATE, "%s: t: env %d is at step %d of its episode, the ring has %d transitions staged for it", who, i, env->t_host[i], ring->staged[i]);
+  if (practice) TRY(gcrl::goal_proposer_bind_check(practice, env, who));
   hipStream_t st = a->pick(stream);
   void* sarg = stream ? stream : (void*)a->stream;   // one stream for the three handles: the loop is stream-ordered
   ColBufs cb;
@@ -3034,6 +3038,7 @@ static int agent_collect_group(gcrl_agent* a, gcrl_env_group* env, gcrl_her* rin
       TRY(gcrl::env_step_launch(env, act, act_f64, st));
     }
     a->col_launches += 1;
+    if (practice) TRY(gcrl::goal_proposer_step_launch(practice, env, st, &a->col_launches));
     a->col_ctr = c + 1;
     a->col_steps += 1;
     const int64_t f0 = ring->flush_calls;
@@ -3049,6 +3054,12 @@ static int agent_collect_group(gcrl_agent* a, gcrl_env_group* env, gcrl_her* rin
 int gcrl_agent_collect(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
                        int update_goal_stats, int steps, int explore, int eval_mode, int64_t* rows_out, void* stream) {
   return agent_collect_group(a, env, ring, nz_obs, update_stats, nz_dg, update_goal_stats, steps, explore, eval_mode, rows_out, stream);
+}
+
+int gcrl_agent_collect_practice(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                                int update_goal_stats, int steps, int explore, int eval_mode, gcrl_goal_proposer* proposer, int64_t* rows_out, void* stream) {
+  GCRL_CHECK_ARG(proposer, "gcrl_agent_collect_practice: proposer: null handle");
+  return agent_collect_group(a, env, ring, nz_obs, update_stats, nz_dg, update_goal_stats, steps, explore, eval_mode, rows_out, stream, proposer);
 }
 
 int gcrl_agent_collect_counts(const gcrl_agent* a, int64_t* calls, int64_t* steps, int64_t* launches, int64_t* copies, int64_t* syncs) {

@@ -51,6 +51,8 @@ struct gcrl_env_group {
   void* tabs = nullptr;                  // P > 1: PopTabCache (pop.h) of the launches' member tables
   int64_t steps[kEnvGroupMaxP] = {}, launches = 0;   // vector steps taken per member / kernel launches issued since creation
   std::vector<int32_t> t_host;           // [P][N] host mirror of t: the step kernel's rule (t + 1, 0 at the horizon) needs no read-back
+  std::vector<uint8_t> rolled;           // [P][N] whether the LAST step launch took the env over its horizon (a reset is not a roll-over)
+  int64_t vsteps = 0;                    // step launches since creation, never reset: names "the last step" for goal_propose.hip
   const void* token = nullptr;           // unique per handle ever created (a small serial, never an address): names the handle in an agent's
                                          // record of whose noise its stream last wrote, so a later handle at a reused address is not mistaken for it
 

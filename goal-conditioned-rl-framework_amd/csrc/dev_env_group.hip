@@ -131,7 +131,13 @@ int group_table(gcrl_env_group* g, const gcrl::EnvPopMember* m, hipStream_t st, 
 int stepped(gcrl_env_group* g) {
   g->launches += 1;
   for (int k = 0; k < g->P; ++k) g->steps[k] += 1;
-  for (int32_t& t : g->t_host) t = t + 1 == g->T ? 0 : t + 1;   // the kernel's rule for t
+  g->vsteps += 1;
+  g->rolled.resize(g->t_host.size());
+  for (size_t e = 0; e < g->t_host.size(); ++e) {   // the kernel's rule for t
+    int32_t& t = g->t_host[e];
+    g->rolled[e] = t + 1 == g->T ? 1 : 0;
+    t = g->rolled[e] ? 0 : t + 1;
+  }
   return GCRL_OK;
 }
 

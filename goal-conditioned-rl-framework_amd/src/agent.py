@@ -953,12 +953,15 @@ class _EngineAgent:
         raw.record_stream(torch.cuda.current_stream()); pay.record_stream(torch.cuda.current_stream())
         return int(rows)
 
-    def collect(self, env, steps: int, explore: bool = True, obs_normalize: bool = True, g_normalize: bool = False) -> int:
+    def collect(self, env, steps: int, explore: bool = True, obs_normalize: bool = True, g_normalize: bool = False, practice=None) -> int:
         """`steps` vector steps of a `DeviceGoalEnv` into this agent's ring as ONE native call: per step the acting launch on the env's
         rows, the env's step and the process-step launch, plus the flush launches of the envs that finish — no host <-> device copy and
         no synchronisation.  `explore=True`: the device exploration stream (DESIGN.md §4q: counter-hash normals scaled by noise_std;
         DDPG's epsilon branch from one counter-hash uniform per vector step); False: `observe_act`'s eval action.  Returns the ring rows
-        appended.  Refusals name their field and come before anything is consumed (include/gcrl.h gcrl_agent_collect)."""
+        appended.  Refusals name their field and come before anything is consumed (include/gcrl.h gcrl_agent_collect).
+        `practice`: None, or a `GoalProposer` whose `step(env)` launches follow each env step inside the native loop (the host loop
+        `observe_act -> env.step -> proposer.step(env) -> process_step`): one more launch a step, and one more in a step in which an env
+        rolled over and the archive held `min_fill` entries; still no copy and no synchronisation."""
         who = f"{type(self).__name__}.collect"
         if getattr(self, "_owner", None) is not None:
             raise _ffi.GcrlError(f"{who}: collect: a population member acts through its population's entries: call pop.collect(group, steps) with a DeviceGoalEnvGroup")
@@ -969,6 +972,10 @@ class _EngineAgent:
             raise ValueError(f"{who}: env: a gcrl_amd.DeviceGoalEnv required")
         if int(steps) < 1:
             raise ValueError(f"{who}: steps: {steps} (>= 1 required)")
+        if practice is not None:
+            from .goal_propose import GoalProposer
+            if not isinstance(practice, GoalProposer):
+                raise ValueError(f"{who}: practice: a gcrl_amd.GoalProposer or None required")
         self._check_normalize_call("collect", obs_normalize, g_normalize, need_device=True)
         nz = self._dev_normalizers("collect", obs_normalize, g_normalize)
         buf = self.buffer
@@ -981,8 +988,12 @@ class _EngineAgent:
         self._rows_dtypes(np.float32, np.float32, obs_normalize, g_normalize)
         rows = C.c_int64(0)
         buf.rng.pull()
-        rc = lib.gcrl_agent_collect(self._h, env.handle, buf.handle, nz[0], 1 if obs_normalize else 0, nz[1], 1 if g_normalize else 0, int(steps),
-                                    1 if explore else 0, 2 if self._sac else self._ACT_MODE_EVAL, C.byref(rows), _ffi.stream_handle())
+        args = (self._h, env.handle, buf.handle, nz[0], 1 if obs_normalize else 0, nz[1], 1 if g_normalize else 0, int(steps),
+                1 if explore else 0, 2 if self._sac else self._ACT_MODE_EVAL)
+        if practice is None:
+            rc = lib.gcrl_agent_collect(*args, C.byref(rows), _ffi.stream_handle())
+        else:
+            rc = lib.gcrl_agent_collect_practice(*args, practice.handle, C.byref(rows), _ffi.stream_handle())
         buf.rng.push_back()
         _ffi.check(rc)
         buf._check_rows(int(rows.value))

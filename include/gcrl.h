@@ -1281,6 +1281,57 @@ int gcrl_pop_collect_counts(const gcrl_pop* p, int64_t* calls, int64_t* steps, i
 int gcrl_pop_evaluate(gcrl_pop* p, gcrl_env_group* g, gcrl_normalizer* const* nz_obs, gcrl_normalizer* const* nz_dg, int32_t episodes, int32_t reset,
                       int32_t eval_mode, int64_t* episodes_out, int64_t* successes_out, double* reward_sum_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Practice goals (csrc/goal_propose.hip; tests/goal_propose_ref.py is the definition).  Nothing here has a counterpart in the
+ * reference.  A proposer owns an archive, a circular buffer of `capacity` raw achieved goals [capacity][3] float32 in the env's own
+ * units, and serves ONE gcrl_env of N envs, bound at its first use.  Behind every vector step of that env, in stream order:
+ *   append   the step's N next_ag rows go to logical positions len .. len + N - 1; a full archive drops its oldest entries;
+ *   propose  only in a step in which an env rolled over (its host t was max_steps - 1 before the step; an env put to t = 0 by
+ *            gcrl_env_reset has not rolled over and keeps its task goal): the counter q is read, then incremented; with L = len >=
+ *            min_fill every rolled-over env i takes a proposal iff float(hash_below(seed, TAKE, q N + i, 2^24)) * 2^-24 < share; its
+ *            candidate k = 0 .. C - 1 is logical index hash_below(seed, CAND, (q N + i) C + k, L); a candidate's count is the number
+ *            of archive entries m in [0, L) with ((dx dx + dy dy) + dz dz) < radius * radius in float32 without contraction (it
+ *            counts itself); the smallest count wins, ties to the smallest k; the winner's three words go to floats 9..11 of the
+ *            env's state record and to columns obs_dim .. obs_dim + 2 of its acting row.  The finished step's raw / pay blocks keep
+ *            the old goal.  TAKE = 0x5052414354414b45, CAND = 0x5052414343414e44; hash_below is the replay ring's counter hash.
+ * The env's stats count an episode's success against the goal the episode had, practised or task; gcrl_agent_evaluate never
+ * appends and never proposes, and with reset != 0 scores task goals only.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct gcrl_goal_proposer gcrl_goal_proposer;
+/* Refused naming the field, in this order: capacity (1..65536), candidates (1..64), radius (finite, > 0), share (in (0, 1]),
+ * min_fill (1..capacity); then a device that is not usable.  NULL on failure. */
+gcrl_goal_proposer* gcrl_goal_proposer_create(int capacity, int candidates, float radius, float share, int min_fill, uint64_t seed, int device);
+void gcrl_goal_proposer_destroy(gcrl_goal_proposer* p);
+/* The binding rules on plain numbers, as gcrl_goal_proposer_step and gcrl_agent_collect_practice apply them to their handles (no
+ * device needed): members (env_members != 1), device (env_device != device), env (bound_num_envs != 0 and another env handle or
+ * another env count), capacity (< env_num_envs). */
+int gcrl_goal_proposer_bind_check(int capacity, int bound_num_envs, int same_env, int device, int env_members, int env_num_envs, int env_device);
+/* The host-loop entry, called after gcrl_env_step on the same stream: goal_archive_append_kernel and, as above, goal_propose_kernel
+ * (one workgroup per rolled-over env); one or two launches, no copy, no synchronisation.  Refused before anything is consumed:
+ * the binding rules above, and with GCRL_ERR_STATE naming `env` when the env has not stepped since the proposer's last step. */
+int gcrl_goal_proposer_step(gcrl_goal_proposer* p, gcrl_env* env, void* stream);
+/* rows appended, steps in which an env rolled over, proposals patched — since creation (or as loaded).  Any pointer may be NULL. */
+int gcrl_goal_proposer_stats(const gcrl_goal_proposer* p, int64_t* appended, int64_t* roll_steps, int64_t* patched);
+/* Settings, the bound env count (0: not bound), head (slot of the oldest entry), len, the counter q, and the number of archive slots
+ * goal_propose_kernel stages per pass.  Any pointer may be NULL. */
+int gcrl_goal_proposer_get(const gcrl_goal_proposer* p, int* capacity, int* candidates, float* radius, float* share, int* min_fill, uint64_t* seed,
+                           int* device, int* num_envs, int* head, int* len, uint64_t* counter, int* tile);
+/* The archive in logical order, len * 3 floats, to host memory.  Synchronises. */
+int gcrl_goal_proposer_read(gcrl_goal_proposer* p, float* dst_host, void* stream);
+/* An 80-byte header (magic, capacity, candidates, min_fill, radius, share, seed, num_envs, head, len, pad, q, the three stats) and the
+ * archive's capacity * 3 floats at their physical slots; resume is bitwise.  Loading refuses other settings (capacity, candidates,
+ * radius, share, min_fill, seed), another num_envs than the handle is bound to, and a head or len outside the archive, by that
+ * field's name before anything is overwritten.  Save behind gcrl_goal_proposer_step, not between it and the env's step. */
+int64_t gcrl_goal_proposer_state_bytes(const gcrl_goal_proposer* p);
+int gcrl_goal_proposer_save_state(gcrl_goal_proposer* p, void* dst_host, int64_t n, void* stream);
+int gcrl_goal_proposer_load_state(gcrl_goal_proposer* p, const void* src_host, int64_t n, void* stream);
+/* gcrl_agent_collect with the proposer's launches behind each env step: the same loop, arguments and refusals, plus the proposer's
+ * (members, device, env, capacity), all before anything is consumed.  No copy, no synchronisation;
+ * gcrl_agent_collect_counts' launches grow by one more per step (the append) and one more per step in which an env rolled over and
+ * the archive held min_fill entries (the propose). */
+int gcrl_agent_collect_practice(gcrl_agent* a, gcrl_env* env, gcrl_her* ring, gcrl_normalizer* nz_obs, int update_stats, gcrl_normalizer* nz_dg,
+                                int update_goal_stats, int steps, int explore, int eval_mode, gcrl_goal_proposer* proposer, int64_t* rows_out, void* stream);
+
 /* hipEvent helpers so a Python caller can time the engine's own stream (torch.cuda.Event only
  * sees torch's current stream). */
 void* gcrl_event_create(void);

@@ -19,7 +19,11 @@ after the warm-up ones: number, median, range in us.  No --pmc in that run.
 --kind reach|push|pick|glide (default reach): the env kind of every mode above.  `pick` has the headline's own dimensions (S 23 = obs 20 +
 goal 3, A 4), so --kind pick times the on-device loop on the network the project is measured on; its host path steps the numpy
 definition tests/dev_env_pick_ref.py.  `glide` (S 19, A 3) steps tests/dev_env_glide_ref.py there.
-No GPU: --cost and --run fail."""
+--practice: agent.collect without and with practice=GoalProposer(...) (defaults: capacity 8192, 16 candidates) at every N, alternating in
+one process, seven samples each: env-steps/s of both, and the proposer's stats.  With --run: for the profiler, N 256 and C 16 with the
+archive pre-loaded to L = 8192 and then to L = 65536, six roll-overs each; --parse DIR --practice lists goal_propose_kernel and
+goal_archive_append_kernel per L.
+No GPU: --cost, --practice and --run fail."""
 import argparse
 import csv
 import glob
@@ -206,6 +210,77 @@ def run():
         torch.cuda.synchronize()
 
 
+PRACTICE_LS = (8192, 65536)
+PRACTICE_NAMES = ("goal_propose_kernel", "goal_archive_append_kernel")
+
+
+def practice_cost(out):
+    import torch
+    import gcrl_amd
+    lines = ["# env-steps/s of agent.collect without and with practice=GoalProposer() (capacity 8192, 16 candidates, radius 0.05, share 0.5, min_fill 256),",
+             "# DDPG H 256 x 3, batch 256, %s dimensions (S %d, A %d); %d alternating samples of %d vector steps" % (KIND, D + G, A, SAMPLES, DEV_STEPS)]
+    for n in NS:
+        plain, prac = _agent(n), _agent(n)
+        e0, e1 = (gcrl_amd.DeviceGoalEnv(KIND, n, seed=3, max_steps=T, threshold=THR) for _ in range(2))
+        prop = gcrl_amd.GoalProposer(seed=1)
+        plain.collect(e0, 2 * T)
+        prac.collect(e1, 2 * T, practice=prop)
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(SAMPLES):
+            t0 = time.perf_counter(); plain.collect(e0, DEV_STEPS); torch.cuda.synchronize(); dt = time.perf_counter() - t0
+            a.append(n * DEV_STEPS / dt)
+            t0 = time.perf_counter(); prac.collect(e1, DEV_STEPS, practice=prop); torch.cuda.synchronize(); dt = time.perf_counter() - t0
+            b.append(n * DEV_STEPS / dt)
+        med = statistics.median
+        lines.append("N %4d  collect %10.0f [%.0f .. %.0f]   collect(practice=) %10.0f [%.0f .. %.0f]   ratio %.3f   us per vector step %.1f / %.1f" %
+                     (n, med(a), min(a), max(a), med(b), min(b), max(b), med(b) / med(a), 1e6 * n / med(a), 1e6 * n / med(b)))
+        lines.append("        proposer: len %d, %s; collect counts: %s" % (len(prop), prop.stats(), prac.collect_counts()))
+    text = "\n".join(lines)
+    print(text)
+    if out:
+        with open(out, "a") as f:
+            f.write(text + "\n")
+
+
+def practice_run():
+    """for the profiler: N 256, C 16, the archive pre-loaded to L entries (a full archive of capacity L), six roll-overs per L"""
+    import numpy as np
+    import torch
+    import gcrl_amd
+    from gcrl_amd.src.goal_propose import STATE_HEADER
+    n = 256
+    for L in PRACTICE_LS:
+        ag = _agent(n)
+        env = gcrl_amd.DeviceGoalEnv(KIND, n, seed=3, max_steps=T, threshold=THR)
+        prop = gcrl_amd.GoalProposer(capacity=L, candidates=16, radius=0.05, share=1.0, min_fill=L, seed=1)
+        blob = prop.save_state()
+        blob[:STATE_HEADER.itemsize].view(STATE_HEADER)["len"] = L
+        blob[STATE_HEADER.itemsize:].view(np.float32)[:] = np.random.default_rng(L).uniform(-0.3, 0.3, 3 * L).astype(np.float32)
+        prop.load_state(blob)
+        ag.collect(env, 6 * T, practice=prop)
+        torch.cuda.synchronize()
+        assert prop.stats()["patched"] == 6 * n, prop.stats()
+
+
+def practice_parse(d):
+    rows = {}
+    for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                key = next((k for k in PRACTICE_NAMES if k in r.get("Kernel_Name", "")), None)
+                if key:
+                    rows.setdefault(key, []).append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    for key, v in sorted(rows.items()):     # --run --practice goes through PRACTICE_LS in order with the same number of launches each
+        v = [d for _, d in sorted(v)]
+        per = len(v) // len(PRACTICE_LS)
+        for k, L in enumerate(PRACTICE_LS):
+            part = v[k * per:(k + 1) * per]
+            part = part[1:] if len(part) > 2 else part          # the first launch of a shape loads code
+            if part:
+                print("%-28s N 256 C 16 L %6d  launches %5d  median %.2f us  [%.2f .. %.2f]" % (key, L, len(part), statistics.median(part), min(part), max(part)))
+
+
 def parse(d, pop_ps=None):
     rows = {}
     for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
@@ -242,8 +317,17 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--members", type=int, nargs="+", default=None, metavar="P", help="population sizes: pop.collect against P standalone collect calls")
     ap.add_argument("--kind", default="reach", choices=sorted(DIMS), help="the env kind; pick has the headline's dimensions (S 23, A 4)")
+    ap.add_argument("--practice", action="store_true", help="collect without and with practice=GoalProposer(); with --run / --parse: the proposer's kernels")
     a = ap.parse_args()
     _set_kind(a.kind)
+    if a.practice:
+        if a.run:
+            practice_run()
+        elif a.parse:
+            practice_parse(a.parse)
+        else:
+            practice_cost(a.out)
+        sys.exit(0)
     if a.members and not (a.run or a.parse):
         members_cost(a.members, a.out)
     if a.cost:
