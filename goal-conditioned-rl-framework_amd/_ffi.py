@@ -295,6 +295,7 @@ PROTOTYPES = {
     "gcrl_agent_set_meetings": (C.c_int, [_vp, C.c_int]),
     "gcrl_agent_get_meetings": (C.c_int, [_vp]),
     "gcrl_agent_rowchain_form": (C.c_int, [_vp]),
+    "gcrl_agent_rowchain_stream": (C.c_int, [_vp]),
     "gcrl_agent_update_forms": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
     "gcrl_agent_debug_meet_fault": (C.c_int, [_vp]),
     "gcrl_hash_normal_fill": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),

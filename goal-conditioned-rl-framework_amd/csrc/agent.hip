@@ -195,6 +195,7 @@ struct gcrl_agent {
   int n_cus = 0;              // compute units of the device (residency checks of the launches whose workgroups meet)
   bool rc_merge = false;      // ... forward and backward part in ONE launch each (part 3; GCRL_NO_RC_MERGE=1: two launches)
   bool rc_merge_k = false;    // TD3 (split_k): the critic phase's two launches as one, producers / consumers form (meet.h)
+  bool rc_no_stream = false;    // GCRL_RC_NO_STREAM=1 (A/B switch): the fused DDPG launch keeps the loop form of its chained passes (rowchain.h WStream)
   bool rc_global_mul = false;   // GCRL_RC_GLOBAL_MUL=1 (A/B switch): the fused DDPG launch keeps its act' multipliers in the global saves (rowchain.h)
   bool ddpg_ksplit = false, ddpg_ksplit_can = false;   // DDPG: the critic phase as two roles of the fused launch (rowchain.hip, k_split)
   // the dW | db GEMMs, the clip and the optimiser step of the row-chain DDPG step as ONE launch (dw_adam.hip; GCRL_NO_OPT_FUSE=1: the
@@ -1669,6 +1670,7 @@ int build(gcrl_agent* a) {
     if (const char* e = std::getenv("GCRL_HEAD_BATCHES")) a->head_batches = std::max(1, std::min(8, std::atoi(e)));   // experiment knob
     a->main_idx_staged = std::getenv("GCRL_MAIN_IDX_STAGED") != nullptr;   // A/B knob (finish_deferred_draw)
     a->rc_global_mul = std::getenv("GCRL_RC_GLOBAL_MUL") != nullptr;       // A/B knob (rowchain.h: rowchain_lds_mul_ok)
+    a->rc_no_stream = std::getenv("GCRL_RC_NO_STREAM") != nullptr;         // A/B knob (rowchain.h: rowchain_stream_ok)
     (void)rc_lds_mul_forms(a);   // (asks the device about both forms' residency now, not at the first launch)
     a->bn_fused_tiled = std::getenv("GCRL_NO_BN_TILED_STATS") == nullptr;
     a->layer_adv_off = std::getenv("GCRL_NO_LAYER_ADV") != nullptr;
@@ -2488,6 +2490,11 @@ int gcrl_agent_get_meetings(gcrl_agent* a) {
 int gcrl_agent_rowchain_form(gcrl_agent* a) {
   GCRL_CHECK_ARG(a, "gcrl_agent_rowchain_form: null handle");
   return rc_lds_mul_forms(a);
+}
+
+int gcrl_agent_rowchain_stream(gcrl_agent* a) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_rowchain_stream: null handle");
+  return rc_stream_form(a) ? 1 : 0;
 }
 
 int gcrl_agent_update_forms(gcrl_agent* a, int32_t* out, int n) {

@@ -66,6 +66,12 @@ int rc_lds_mul_forms(const gcrl_agent* a) {
   return ((k_fused && ok(false, nk)) ? 1 : 0) | (ok(true, nblk) ? 2 : 0) | ((k_fused && ok(true, nk + nblk)) ? 4 : 0);
 }
 
+// whether the agent's fused DDPG launches take the stream form of their chained passes (rowchain.h rowchain_stream_ok, in the agent's terms)
+bool rc_stream_form(const gcrl_agent* a) {
+  return a->rowchain && !a->sac && !a->split_roles && !a->split_k && !a->rc_no_stream && a->cfg.kind == GCRL_AGENT_DDPG && a->row_rg == 1 &&
+         a->C == 1 && a->H <= kRowChunk && a->L >= 2;
+}
+
 // SAC on the role-parallel row-chain launches: the BatchNorm actor's heads and its sampling run inside them (rowchain.h HeadsFold)
 bool heads_fold_on(const gcrl_agent* a) {
   return a->rowchain && a->cfg.kind == GCRL_AGENT_SAC && a->split_roles && a->slab_on() && !a->heads_fold_off && a->A <= 16 && a->bn_sync.world <= 1;
@@ -148,21 +154,21 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
       rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev; rc.producers_first = 1;
       TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 3));
     } else if (what & 1) { TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 1)); TRY(launch_rowchain_split(st, rc, a->row_rg, 0, 2)); }
-    if (what & 2) { rc.nblk_k = 0; TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul)); }
+    if (what & 2) { rc.nblk_k = 0; TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul, !a->rc_no_stream)); }
     return GCRL_OK;
   }
   if (a->ddpg_ksplit && (what & 1)) {   // the critic phase as two roles of the fused launch (rowchain.hip: k_split)
     rc.k_split = 1; rc.producers_first = 1;
     rc.bar = reinterpret_cast<unsigned int*>(a->rc_bar); rc.status = a->status_dev;
   }
-  if (!a->prof || what != 3) return launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul);
+  if (!a->prof || what != 3) return launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul, !a->rc_no_stream);
   // measurement mode (never inside a graph capture): the overlapped launch, bracketed
   if (a->prof_used == gcrl_agent::kProfPairs) TRY(prof_drain(a));
   const unsigned long long init[2] = {~0ull, 0ull};
   rc.clk = a->prof_clk + 2 * a->prof_used;
   GCRL_HIP(hipMemcpyAsync(rc.clk, init, sizeof(init), hipMemcpyHostToDevice, st));
   GCRL_HIP(hipEventRecord(a->prof_a[a->prof_used], st));
-  TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul));
+  TRY(launch_rowchain_ddpg(st, rc, a->row_rg, !a->rc_global_mul, !a->rc_no_stream));
   GCRL_HIP(hipEventRecord(a->prof_b[a->prof_used], st));
   a->prof_used++;
   a->prof_launches++;

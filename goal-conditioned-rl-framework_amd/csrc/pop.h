@@ -21,7 +21,7 @@ namespace gcrl {
 
 enum PopKind {
   POP_ALONE = 0,       // no population form: each member's own launch, in member order
-  POP_ROWCHAIN = 1,    // rowchain_ddpg_kernel<sub & 15, sub & 16> (rows per block / 4; + 16: the LDS-multiplier form)
+  POP_ROWCHAIN = 1,    // rowchain_ddpg_kernel<sub & 15, sub & 16> (rows per block / 4; + 16: the LDS-multiplier form; + 32: the stream form)
   POP_DW_ADAM = 2,     // dw_adam_kernel
   POP_BEGIN_STEP = 3,  // begin_step_kernel
   POP_GEMM_BATCH = 4,  // one form's launch of launch_gemm_batch (sub = the form, 1..5; only form 1, gemm_batch_kernel<1, 1, 4>, merges)

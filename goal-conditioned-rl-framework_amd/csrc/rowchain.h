@@ -191,6 +191,214 @@ __device__ __forceinline__ void rows_linear(const float* xs, int ldx, int J, con
   }
 }
 
+// ---------------------------------------------------------------- carried weight stream (chained passes, 4 rows per workgroup)
+// The parent's loop above ends every wave's share with a stage of loads nobody reads (rows of the next wave, or zeros), waits for them
+// in its epilogue, and starts the next pass's stream only after the exchange, the epilogue and the save.  The stream form keeps the
+// `wa` stage registers ALIVE across passes: the slot of the dead tail loads requests the first stage of the wave's share of the NEXT
+// pass's matrix (none of these addresses depends on computed data), together with that pass's bias items, which are therefore older
+// than the carried stage and never waited for on their own.  Same MFMA sequence per accumulator, same exchange, same epilogue: the
+// parent's bits.  At most 16 weight loads of a wave in flight, as before.
+constexpr int TAIL_NONE = 0;   // the pass requests nothing for a successor
+constexpr int TAIL_FULL = 1;   // successor: an H x H matrix of the same H (every wave's share is full stages) — requested in the tail slot
+constexpr int TAIL_ANY = 2;    // successor of any shape (a first layer: J = jpad0) — requested behind the last stage's MFMAs
+
+struct WNext { const float* M; int ldm, J, N; const float* bias; };   // the successor pass: matrix [J][ldm], N outputs, bias or null
+
+// a wave's epilogue item of a chained pass at 4 rows (rows_linear: idx = lane): row r, columns cc .. cc+3
+struct ChainItem { int r, cc; bool ok; };
+__device__ __forceinline__ ChainItem chain_item(int pern, int N, int wave, int lane) {
+  const int q4 = pern >> 2, cb = wave * pern;
+  ChainItem t;
+  t.r = lane / q4;
+  t.cc = cb + 4 * (lane - t.r * q4);
+  t.ok = lane < 4 * q4 && t.cc < N;
+  return t;
+}
+
+template <int U>
+struct WStream {
+  v4u w[U];      // first stage of the wave's share of the pass to come (raw: rows the share does not have were never requested)
+  v4f eb;        // that pass's bias item of the lane (raw: lanes without an item hold the bias's first floats, unused)
+  // Whether the stream is primed at a pass's top is a property of the call site, not a run-time flag: every stream pass is primed by
+  // the pass before it or by the prologue.  With a flag the compiler joins the two cases through register copies, and every copy of
+  // a requested register is a full wait.
+
+  // any shape.  Nothing is requested for a wave whose share is empty, no row past the share's end.
+  template <bool HASB>
+  __device__ __forceinline__ void prime(const float* M, int ldm, int J, int N, const float* bias) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int per = ((J + 3) / 4 + 3) & ~3;
+    const int jb = wave * per, je = min(J, jb + per);
+    if constexpr (HASB) {
+      const ChainItem t = chain_item(((N + 3) / 4 + 3) & ~3, N, wave, lane);
+      eb = *(const v4f*)(bias + (t.ok ? t.cc : 0));
+    }
+    const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(M, (long long)J * ldm);
+    const int col_b = 4 * lane * 4;
+#pragma unroll
+    for (int u4 = 0; u4 < U; u4 += 4)
+      if (jb + u4 < je) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u4 + u] = __builtin_amdgcn_raw_buffer_load_b128(rs, col_b + (jb + u4 + u) * ldm * 4, 0, 0);
+      }
+  }
+  // an N x N matrix, N = 4 * KS: every wave's share is KS >= U rows — a fixed number of loads, so that the waits around it count exactly
+  template <int KS, bool HASB>
+  __device__ __forceinline__ void prime_full(const float* M, const float* bias) {
+    static_assert(KS >= U, "a full first stage");
+    constexpr int N = 4 * KS;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (HASB) {
+      const ChainItem t = chain_item(KS, N, wave, lane);
+      eb = *(const v4f*)(bias + (t.ok ? t.cc : 0));
+    }
+    const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(M, (long long)N * N);
+    const int col_b = 4 * lane * 4, jb = wave * KS;
+#pragma unroll
+    for (int u = 0; u < U; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, col_b + (jb + u) * N * 4, 0, 0);
+  }
+};
+
+// partial-sum exchange and epilogue of a chained pass at 4 rows: rows_linear's, statement for statement
+__device__ __forceinline__ void chain_exchange(const v4f (&acc)[1][4], float* part, int wave, int lane, const ChainItem& t, v4f eb, v4f eh,
+                                               int epi, int mul, float* ys, int ldy, float* save, long long ld_save, int rows_valid) {
+  constexpr int R = 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    *(v4f*)(part + ((wave * R + i) * kRowChunk) + 4 * lane) = (v4f){acc[0][0][i], acc[0][1][i], acc[0][2][i], acc[0][3][i]};
+  __syncthreads();
+  if (t.ok) {
+    const int r = t.r, cc = t.cc;
+    v4f v = *(const v4f*)(part + r * kRowChunk + cc);
+#pragma unroll
+    for (int w = 1; w < 4; ++w) v += *(const v4f*)(part + (w * R + r) * kRowChunk + cc);
+    v += eb;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      v[q] = act_apply(v[q], epi);
+      if (mul != MUL_NONE) v[q] *= act_deriv(eh[q], mul);
+    }
+    *(v4f*)(ys + r * ldy + cc) = v;
+    if (save && r < rows_valid) *(v4f*)(save + (long long)r * ld_save + cc) = v;
+  }
+}
+
+__device__ __forceinline__ void chain_mfma4(v4f (&acc)[1][4], const float* xs, int ldx, int lane, const v4u* w, int j) {
+  const v4f xa = *(const v4f*)(xs + (lane & 3) * ldx + j);
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[0][q] = __builtin_amdgcn_mfma_f32_4x4x1f32(xa[u], __uint_as_float(w[u][q]), acc[0][q], 0, 0, 0);
+}
+
+// A chained H x H pass at a dispatched size, N = J = ldm = 4 * KS: straight-line, KS / 8 full stages, no load past the share.  The
+// first stage comes from the stream; TAIL_FULL: the last pair's free `wa` slot requests the successor.
+template <int KS, int TAIL, bool HASB, bool HASB_N>
+__device__ __forceinline__ void rows_pass_st(WStream<8>& ws, const float* xs, int ldx, const float* M, const float* bias, int epi, float* part,
+                                             float* ys, int ldy, float* save, long long ld_save, int rows_valid, const float* mulH,
+                                             long long ld_mul, int mul, int pbuf, const WNext& nx) {
+  constexpr int U = 8, N = 4 * KS, NP = KS / (2 * U);
+  static_assert(KS % (2 * U) == 0, "whole stage pairs");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  part += pbuf * (4 * 4 * kRowChunk);
+  const ChainItem t = chain_item(KS, N, wave, lane);
+  const v4f eb_raw = ws.eb;
+  const v4f eh = (mulH && t.ok && t.r < rows_valid) ? *(const v4f*)(mulH + (long long)t.r * ld_mul + t.cc) : (v4f){0.f, 0.f, 0.f, 0.f};
+  const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(M, (long long)N * N);
+  const int col_b = 4 * lane * 4, jb = wave * KS;
+  v4f acc[1][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[0][q] = (v4f){0.f, 0.f, 0.f, 0.f};
+  v4u wb[U];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int j = jb + p * 2 * U;
+#pragma unroll
+    for (int u = 0; u < U; ++u) wb[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, col_b + (j + U + u) * N * 4, 0, 0);
+    // (scheduling fences: in straight-line code the scheduler otherwise sinks every load to its first use — one row in flight)
+    __builtin_amdgcn_sched_barrier(0);
+    chain_mfma4(acc, xs, ldx, lane, ws.w, j);
+    chain_mfma4(acc, xs, ldx, lane, ws.w + 4, j + 4);
+    __builtin_amdgcn_sched_barrier(0);
+    if (p + 1 < NP) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) ws.w[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, col_b + (j + 2 * U + u) * N * 4, 0, 0);
+    } else if constexpr (TAIL == TAIL_FULL) {
+      ws.template prime_full<KS, HASB_N>(nx.M, nx.bias);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    chain_mfma4(acc, xs, ldx, lane, wb, j + U);
+    chain_mfma4(acc, xs, ldx, lane, wb + 4, j + U + 4);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (TAIL == TAIL_ANY) ws.template prime<HASB_N>(nx.M, nx.ldm, nx.J, nx.N, nx.bias);
+  const v4f eb = (HASB && t.ok) ? eb_raw : (v4f){0.f, 0.f, 0.f, 0.f};
+  chain_exchange(acc, part, wave, lane, t, eb, eh, epi, mul, ys, ldy, save, ld_save, rows_valid);
+}
+
+// The same structure with run-time counts (a first layer's J = jpad0, an H outside the dispatched sizes; KS > 0: the successor's N / 4): partial stages and empty
+// shares are skipped in groups of four rows, as the parent's MFMA groups are; the successor is requested behind the last MFMAs.
+template <int KS, int TAIL, bool HASB, bool HASB_N>
+__device__ __forceinline__ void rows_pass_rt(WStream<8>& ws, const float* xs, int ldx, int J, const float* M, int ldm, int N, const float* bias,
+                                             int epi, float* part, float* ys, int ldy, float* save, long long ld_save, int rows_valid,
+                                             const float* mulH, long long ld_mul, int mul, int pbuf, const WNext& nx) {
+  constexpr int U = 8;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  part += pbuf * (4 * 4 * kRowChunk);
+  const int per = ((J + 3) / 4 + 3) & ~3;
+  const int jb = wave * per, je = min(J, jb + per);
+  const ChainItem t = chain_item(((N + 3) / 4 + 3) & ~3, N, wave, lane);
+  const v4f eb_raw = ws.eb;
+  const v4f eh = (mulH && t.ok && t.r < rows_valid) ? *(const v4f*)(mulH + (long long)t.r * ld_mul + t.cc) : (v4f){0.f, 0.f, 0.f, 0.f};
+  const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(M, (long long)J * ldm);
+  const int col_b = 4 * lane * 4;
+  v4f acc[1][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[0][q] = (v4f){0.f, 0.f, 0.f, 0.f};
+  v4u wb[U];
+  auto load = [&](v4u* w, int j) {
+#pragma unroll
+    for (int u4 = 0; u4 < U; u4 += 4)
+      if (j + u4 < je) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u4 + u] = __builtin_amdgcn_raw_buffer_load_b128(rs, col_b + (j + u4 + u) * ldm * 4, 0, 0);
+      }
+  };
+  auto compute = [&](const v4u* w, int j) {
+#pragma unroll
+    for (int u4 = 0; u4 < U; u4 += 4)
+      if (j + u4 < je) chain_mfma4(acc, xs, ldx, lane, w + u4, j + u4);
+  };
+  for (int j = jb; j < je; j += 2 * U) {
+    load(wb, j + U);
+    compute(ws.w, j);
+    if (j + 2 * U < je) load(ws.w, j + 2 * U);
+    compute(wb, j + U);
+  }
+  if constexpr (TAIL == TAIL_FULL && KS > 0) ws.template prime_full<KS, HASB_N>(nx.M, nx.bias);
+  else if constexpr (TAIL != TAIL_NONE) ws.template prime<HASB_N>(nx.M, nx.ldm, nx.J, nx.N, nx.bias);
+  const v4f eb = (HASB && t.ok) ? eb_raw : (v4f){0.f, 0.f, 0.f, 0.f};
+  chain_exchange(acc, part, wave, lane, t, eb, eh, epi, mul, ys, ldy, save, ld_save, rows_valid);
+}
+
+// (`bias` in rows_pass_st / rows_pass_rt / rows_linear_stream is deliberately unread: the pass's bias item arrives in ws.eb, requested
+// by whoever primed the stream; the parameter keeps the call sites' argument lists those of rows_linear.)
+// the stream form of rows_linear's chained branch (RG = 1, N <= kRowChunk), the stream primed by the pass before (or the prologue).
+// KS: N / 4 where the caller runs in a branch of its own for that N (64, 128, 256), 0: any N; L0: a first layer (J = jpad0);
+// HASB / HASB_N: this pass / its successor has a bias.  The branch on N is the CALLER's, once per role: a join of differently compiled
+// passes while the stream is live costs register copies, and a copy of a requested register is a full wait.
+template <int KS, bool L0, int TAIL, bool HASB, bool HASB_N>
+__device__ __forceinline__ void rows_linear_stream(WStream<8>& ws, const float* xs, int ldx, int J, const float* M, int ldm, int N,
+                                                   const float* bias, int epi, float* part, float* ys, int ldy, float* save, long long ld_save,
+                                                   int rows_valid, const float* mulH, long long ld_mul, int mul, int pbuf, const WNext& nx) {
+  if constexpr (KS > 0 && !L0) rows_pass_st<KS, TAIL, HASB, HASB_N>(ws, xs, ldx, M, bias, epi, part, ys, ldy, save, ld_save, rows_valid, mulH, ld_mul, mul, pbuf, nx);
+  else rows_pass_rt<KS, TAIL, HASB, HASB_N>(ws, xs, ldx, J, M, ldm, N, bias, epi, part, ys, ldy, save, ld_save, rows_valid, mulH, ld_mul, mul, pbuf, nx);
+}
+
 // small heads: out[r][o] = epi(sum_k x[r][k] * W[o*ldw + k] + bias[o]) for o < n_out <= 16, into
 // LDS sm[r*16 + o].  A wave owns the (r, o) pairs wave, wave+4, ... and works on all of them AT ONCE:
 // G = 64 / pairs lanes per pair (a power of two), lane-strided partial sums, an xor-shuffle reduce
@@ -371,7 +579,10 @@ int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int
 
 // rows per workgroup = 4*rg, rg in {1, 2, 4}
 // lds_mul: the LDS-multiplier form (below) where the launch's shape admits it; false: the global-multiplier form
-int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul);
+// stream: the stream form of the chained passes (WStream above) where rowchain_stream_ok admits the launch; false: the loop of rows_matmul_wave
+// (GCRL_RC_NO_STREAM=1, read when an agent is created, is the A/B switch; both forms give the same bits)
+int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul, bool stream = false);
+bool rowchain_stream_ok(const RowChainArgs& a, int rg);
 size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C);
 // LDS-multiplier form of the fused DDPG launch (rowchain.hip): every hidden layer's output of a net with a backward chain keeps LDS rows of
 // its own and the chain's act' multipliers are read from there, not from the global saves — L - 1 more [R][ldl] buffers for a launch of

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 namespace gcrl {
 namespace {
@@ -139,6 +140,56 @@ __device__ inline float* grad_chain_keep(const RowNet& net, float* G, float* X1,
   return in;
 }
 
+// Stream form (rowchain.h WStream) of the four walks above, 4 rows per workgroup and H <= kRowChunk (always chained): every pass requests
+// the first stage of the next layer's matrix, the walk's last pass the caller's `nx` (TAIL, HASB_N: its kind, whether it has a bias).
+// KEEP: the LDS-multiplier form's buffers (A1 = keep rows, `last` = the last layer's rows); else the ping-pong pair A1 / A2, the last
+// layer into `last` when given.  KS: H / 4 at a dispatched H (the caller's branch: no join of branches while the stream is live), 0: any H.
+// The walk's first pass is always requested by somebody before it.  A walk needs L >= 2 (the launcher's rule).
+template <int KS, bool KEEP, int TAIL, bool HASB_N>
+__device__ __forceinline__ float* mlp_hidden_st(WStream<8>& ws, const RowNet& net, const float* X0, float* A1, float* A2, float* last, int ldl,
+                                                float* part, float* save, long long BH, long long row0, int rv, const WNext& nx) {
+  constexpr int R = 4;
+  const int H = net.H, L = net.L;
+  auto out_of = [&](int l) -> float* {
+    if (KEEP) return l == L - 1 ? last : A1 + l * R * ldl;
+    return (last && l == L - 1) ? last : ((l & 1) ? A2 : A1);
+  };
+  auto next_of = [&](int l) { return WNext{net.Wt + net.wt[l + 1], H, H, H, net.P + net.b[l + 1]}; };
+  auto save_of = [&](int l) -> float* { return save ? save + l * BH + row0 * H : nullptr; };
+  rows_linear_stream<KS, true, TAIL_FULL, true, true>(ws, X0, ldl, net.jpad0, net.Wt + net.wt[0], H, H, net.P + net.b[0], EPI_LEAKY, part, out_of(0), ldl,
+                                            save_of(0), H, rv, nullptr, 0, MUL_NONE, 0, next_of(0));
+  for (int l = 1; l < L - 1; ++l)
+    rows_linear_stream<KS, false, TAIL_FULL, true, true>(ws, out_of(l - 1), ldl, H, net.Wt + net.wt[l], H, H, net.P + net.b[l], EPI_LEAKY, part, out_of(l), ldl,
+                                              save_of(l), H, rv, nullptr, 0, MUL_NONE, l & 1, next_of(l));
+  rows_linear_stream<KS, false, TAIL, true, HASB_N>(ws, out_of(L - 2), ldl, H, net.Wt + net.wt[L - 1], H, H, net.P + net.b[L - 1], EPI_LEAKY, part, out_of(L - 1), ldl,
+                                         save_of(L - 1), H, rv, nullptr, 0, MUL_NONE, (L - 1) & 1, nx);
+  __syncthreads();   // the callers read the result across waves
+  return out_of(L - 1);
+}
+// mulbase: KEEP: the kept rows (LDS); else the global saves [L][B][H].  The walk's first pass is always requested by the caller's side
+// (the forward walk's last pass, or the head section's predecessor).
+template <int KS, bool KEEP, int TAIL, bool HASB_N>
+__device__ __forceinline__ float* grad_chain_st(WStream<8>& ws, const RowNet& net, float* G, float* X1, float* X2, int ldl, float* part,
+                                                const float* mulbase, float* gsave, long long BH, long long row0, int rv, const WNext& nx) {
+  constexpr int R = 4;
+  const int H = net.H;
+  float* in = G;
+  auto mul_of = [&](int l) -> const float* { return KEEP ? mulbase + (l - 1) * R * ldl : mulbase + (l - 1) * BH + row0 * H; };
+  auto save_of = [&](int l) -> float* { return gsave ? gsave + (l - 1) * BH + row0 * H : nullptr; };
+  const long long ld_mul = KEEP ? ldl : H;
+  for (int l = net.L - 1; l >= 2; --l) {
+    float* out = (in == X1) ? X2 : X1;
+    rows_linear_stream<KS, false, TAIL_FULL, false, false>(ws, in, ldl, H, net.P + net.w[l], H, H, nullptr, EPI_NONE, part, out, ldl, save_of(l), H, rv,
+                                                mul_of(l), ld_mul, MUL_DLEAKY, l & 1, WNext{net.P + net.w[l - 1], H, H, H, nullptr});
+    in = out;
+  }
+  float* out = (in == X1) ? X2 : X1;
+  rows_linear_stream<KS, false, TAIL, false, HASB_N>(ws, in, ldl, H, net.P + net.w[1], H, H, nullptr, EPI_NONE, part, out, ldl, save_of(1), H, rv,
+                                          mul_of(1), ld_mul, MUL_DLEAKY, 1, nx);
+  __syncthreads();
+  return out;
+}
+
 // stage `n` floats of global memory into LDS (all threads)
 // Prologue staging in two phases — every global load of the block's inputs is requested (into registers)
 // before the first LDS store waits for any of them: the phases used to alternate per region and the
@@ -193,10 +244,26 @@ __device__ inline void stage(float* dst, const float* src, int n) {
 template <int RG, bool HF = false, bool LM = false>
 __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int phase, int part, int bid, const HeadsFold& hfr = HeadsFold{});
 
+#ifndef RC_STAMP
+#define RC_STAMP(i)   // (tools/rc_stamps_build.py: device-clock stamps of the development build)
+#endif
 // LM = false: the global-multiplier form (the chain's act' multipliers are loaded back from the global saves); true: from LDS
 template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {
   kernarg_warm_once<sizeof(RowChainArgs)>();
+  constexpr bool ST = false;
+#include "rowchain_ddpg_body.inc"
+}
+// the stream form (rowchain.h WStream) of the launch at 4 rows per workgroup: the same body, its chained passes carry the weight stream
+template <bool LM>
+__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel_stream(RowChainArgs args) {
+  kernarg_warm_once<sizeof(RowChainArgs)>();
+  // the arguments are read in place, as the population kernel reads its table: with this body's larger number of walks hipcc otherwise
+  // copies the by-value record to per-thread scratch (1.8 KB) and indexes it there.  `args` is the kernel's only parameter, so it is
+  // what the kernarg segment begins with (offset 0; implicit arguments follow the explicit ones): the same bytes, read where they lie.
+  const RowChainArgs& a = *(const RowChainArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  constexpr int RG = 1;
+  constexpr bool ST = true;
 #include "rowchain_ddpg_body.inc"
 }
 
@@ -205,6 +272,14 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs
 template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_pop_kernel(const RowChainArgs* __restrict__ tab) {
   const RowChainArgs& a = tab[blockIdx.y];
+  constexpr bool ST = false;
+#include "rowchain_ddpg_body.inc"
+}
+template <bool LM>
+__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_pop_kernel_stream(const RowChainArgs* __restrict__ tab) {
+  const RowChainArgs& a = tab[blockIdx.y];
+  constexpr int RG = 1;
+  constexpr bool ST = true;
 #include "rowchain_ddpg_body.inc"
 }
 
@@ -760,7 +835,14 @@ bool rowchain_merge_ok(int rg, int ldl, int A, int H, int C, int B) {
   return 2LL * C * nblk <= meet_capacity(k, kRowThreads, lds) && 2LL * C * nblk <= meet_capacity(kh, kRowThreads, lds);
 }
 
-int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul) {
+// the stream form's shapes: the plain DDPG launch at 4 rows per workgroup, chained passes (H <= kRowChunk), walks of two layers or more
+bool rowchain_stream_ok(const RowChainArgs& a, int rg) {
+  const int H = a.critic[0].H, L = a.critic[0].L;
+  return rg == 1 && a.C == 1 && !a.p_critic_only && !a.given_next && a.target_kind == TGT_DDPG && H <= kRowChunk && L >= 2 &&
+         a.actor.H == H && a.tactor.H == H && a.tcritic[0].H == H && a.actor.L == L && a.tactor.L == L && a.tcritic[0].L == L;
+}
+
+int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul, bool stream) {
   GCRL_CHECK_ARG(rg == 1 || rg == 2 || rg == 4, "rowchain: rows per block must be 4, 8 or 16");
   GCRL_CHECK_ARG(a.critic[0].H % 4 == 0 && a.ldl % 4 == 0 && a.A <= 16 && a.C >= 1 && a.C <= 2,
                  "rowchain: unsupported shape (H=%d, A=%d, C=%d)", a.critic[0].H, a.A, a.C);
@@ -772,8 +854,9 @@ int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds
   GCRL_CHECK_ARG(lds <= 160 * 1024, "rowchain: %zu bytes of LDS needed", lds);
   GCRL_CHECK_ARG(!a.k_split || (a.bar && a.qt && a.producers_first && a.C == 1), "rowchain: the two-role critic phase needs its meeting counters");
   if (grid < 1) return GCRL_OK;
+  const bool sf = stream && rowchain_stream_ok(a, rg);   // the stream form of the chained passes (rowchain.h WStream)
   if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
-    return pop_record(r, POP_ROWCHAIN, rg | (lm ? 16 : 0), dim3(grid), lds, &a, sizeof(a), [ac = a, rg, lds_mul](hipStream_t s) { return launch_rowchain_ddpg(s, ac, rg, lds_mul); });
+    return pop_record(r, POP_ROWCHAIN, rg | (lm ? 16 : 0) | (sf ? 32 : 0), dim3(grid), lds, &a, sizeof(a), [ac = a, rg, lds_mul, stream](hipStream_t s) { return launch_rowchain_ddpg(s, ac, rg, lds_mul, stream); });
   auto go = [&](auto kern) -> int {
     static thread_local size_t raised = 0;   // (per kernel: a generic lambda's statics belong to its instantiation)
     if (lds > 64 * 1024 && lds > raised) {
@@ -784,6 +867,7 @@ int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds
     GCRL_HIP(hipGetLastError());
     return GCRL_OK;
   };
+  if (sf) return lm ? go(rowchain_ddpg_kernel_stream<true>) : go(rowchain_ddpg_kernel_stream<false>);
   if (lm) {
     if (rg == 1) return go(rowchain_ddpg_kernel<1, true>);
     if (rg == 2) return go(rowchain_ddpg_kernel<2, true>);
@@ -898,10 +982,10 @@ int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int
   return GCRL_OK;
 }
 
-// sub: rows per block / 4, + 16 for the LDS-multiplier form (the members' own launches chose it: launch_rowchain_ddpg, same shape, same LDS)
+// sub: rows per block / 4, + 16 for the LDS-multiplier form, + 32 for the stream form (the members' own launches chose them: launch_rowchain_ddpg, same shape, same LDS)
 int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int sub, dim3 grid, size_t lds) {
   const int rg = sub & 15;
-  const bool lm = (sub & 16) != 0;
+  const bool lm = (sub & 16) != 0, sf = (sub & 32) != 0;
   GCRL_CHECK_ARG(rg == 1 || rg == 2 || rg == 4, "rowchain population: rows per block must be 4, 8 or 16");
   GCRL_CHECK_ARG(members >= 1 && members <= 65535 && grid.y == 1 && grid.z == 1 && lds <= 160 * 1024, "rowchain population: bad launch");
   const RowChainArgs* t = static_cast<const RowChainArgs*>(tab);
@@ -912,6 +996,10 @@ int launch_rowchain_ddpg_pop(hipStream_t st, const void* tab, int members, int s
     GCRL_HIP(hipGetLastError());
     return GCRL_OK;
   };
+  if (sf) {
+    GCRL_CHECK_ARG(rg == 1, "rowchain population: the stream form runs 4 rows per block");
+    return lm ? go(rowchain_ddpg_pop_kernel_stream<true>) : go(rowchain_ddpg_pop_kernel_stream<false>);
+  }
   if (lm) {
     if (rg == 1) return go(rowchain_ddpg_pop_kernel<1, true>);
     if (rg == 2) return go(rowchain_ddpg_pop_kernel<2, true>);

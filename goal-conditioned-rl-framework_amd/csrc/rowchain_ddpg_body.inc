@@ -4,6 +4,7 @@
 // rowchain_lds_bytes_mul) — the hidden activations of every net with a backward chain keep LDS rows of their own behind the head biases,
 // KP = [L - 1][R][ldl] per net, and the chains read their multipliers there.  hA / gA / hC / gC still leave for the dW launch; hC2, which
 // only this launch read, is neither written nor read.  The SAC form (p_critic_only) is never launched with LM (launch_rowchain_ddpg).
+// constexpr bool ST: the stream form of the actor phase's chained passes (rowchain_ddpg_kernel_stream, RG = 1); RC_STAMP: development stamps.
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // k_split (round 4, DDPG): the critic phase K as TWO roles in this launch — its target chain (target actor -> target critic -> Q')
   // and its online critic's forward are independent, so K's critical path shrinks from 11 layer passes to 6 + 2 (the split kernel's
@@ -209,6 +210,102 @@
       }
       __syncthreads();
     }
+  } else if constexpr (ST) {
+    // The actor phase in the stream form (rowchain.h WStream; 4 rows per workgroup, walks of two layers or more: rowchain_stream_ok) —
+    // the branch below with one weight stream carried through the role's passes: the prologue requests the first stage of the actor's
+    // layer 0 with its other requests, every pass requests its successor, and the last pass in front of a head section requests the
+    // first pass behind it (actor -> critic layer 0 -> critic's first backward matrix -> actor's first backward matrix).  The whole
+    // role runs in a branch of its own per dispatched H: no join of differently compiled passes while the stream is live.
+    auto p_role = [&](auto ks_tag) {
+      constexpr int KS = decltype(ks_tag)::value;   // H / 4 at H = 64, 128, 256; 0: any other H
+      RC_STAMP(0);
+      const StepCtrl c = *a.cur_p;
+      const float* sa_rows = a.sa + (long long)c.batch_slot * a.slot_x + row0 * a.ldx;
+      constexpr int NX = 2 * RG;
+      const int jp_s = max(a.actor.jpad0, a.critic[0].jpad0);
+      float* hw_a = hw; float* hw_c = hw + A * H; float* hw_da = hw_c + H;
+      const float* src_a = a.actor.P + a.actor.w[a.actor.L];
+      const float* src_c = a.critic[0].P + a.critic[0].w[a.critic[0].L];
+      const float* src_da = a.critic[0].Wt + a.critic[0].wt[0] + (long long)S * H;   // rows S..S+A-1 of W0^T
+      Staged<NX> s_s;
+      rows_load<RG>(s_s, sa_rows, a.ldx, S, jp_s, rv);
+      Staged<8> s_a, s_hc, s_da;
+      seg_load(s_a, src_a, A * H);
+      seg_load(s_hc, src_c, H);
+      seg_load(s_da, src_da, A * H);
+      float v_hb = 0.f;
+      if (tid < A) v_hb = a.actor.P[a.actor.b[a.actor.L] + tid];
+      if (tid == 32) v_hb = a.critic[0].P[a.critic[0].b[a.critic[0].L]];
+      WStream<8> ws;
+      ws.eb = (v4f){0.f, 0.f, 0.f, 0.f};
+      ws.template prime<true>(a.actor.Wt + a.actor.wt[0], H, a.actor.jpad0, H, a.actor.P + a.actor.b[0]);
+      const WNext nx_c0 = {a.critic[0].Wt + a.critic[0].wt[0], H, a.critic[0].jpad0, H, a.critic[0].P + a.critic[0].b[0]};   // critic, layer 0
+      const WNext nx_cb = {a.critic[0].P + a.critic[0].w[a.critic[0].L - 1], H, H, H, nullptr};                            // critic, first backward matrix
+      const WNext nx_ab = {a.actor.P + a.actor.w[a.actor.L - 1], H, H, H, nullptr};                                        // actor, first backward matrix
+      const WNext nx_none = {nullptr, 0, 0, 0, nullptr};
+      rows_store<RG>(s_s, X0, ldl, sa_rows, a.ldx, S, jp_s, rv);
+      seg_store(s_a, hw_a, src_a, A * H);
+      seg_store(s_hc, hw_c, src_c, H);
+      seg_store(s_da, hw_da, src_da, A * H);
+      if (tid < A) hb[tid] = v_hb;
+      if (tid == 32) hb[16] = v_hb;
+      const bool fuse_q = head_fusable(H);
+      if (fuse_q && tid < R) sm2[tid * 16] = (tid < rv) ? -1.0f / (float)B : 0.f;   // d(-mean Q)/dq, constant
+      __syncthreads();
+      RC_STAMP(1);
+      float* h;
+      if constexpr (LM) h = mlp_hidden_st<KS, true, TAIL_ANY, true>(ws, a.actor, X0, KP, nullptr, XS, ldl, part + R * 16, a.hA, BH, row0, rv, nx_c0);
+      else h = mlp_hidden_st<KS, false, TAIL_ANY, true>(ws, a.actor, X0, X1, X2, XS, ldl, part + R * 16, a.hA, BH, row0, rv, nx_c0);
+      RC_STAMP(2);
+      rows_head<RG>(h, ldl, H, hw_a, H, hb, A, EPI_TANH, sm);
+      __syncthreads();
+      if (tid < R * A) { const int r = tid / A, o = tid - r * A; X0[r * ldl + S + o] = sm[r * 16 + o]; }
+      __syncthreads();
+      RC_STAMP(3);
+      if constexpr (LM) h = mlp_hidden_st<KS, true, TAIL_FULL, false>(ws, a.critic[0], X0, KPC, nullptr, X1, ldl, part + R * 16, nullptr, BH, row0, rv, nx_cb);
+      else h = mlp_hidden_st<KS, false, TAIL_FULL, false>(ws, a.critic[0], X0, X1, X2, nullptr, ldl, part + R * 16, a.hC2, BH, row0, rv, nx_cb);
+      RC_STAMP(4);
+      if (fuse_q) {
+        head_backward<RG>(h, ldl, H, hw_c, 1, sm2, nullptr, rv, sm3, hb[16]);
+        __syncthreads();
+        if (tid < rv) a.q2[row0 + tid] = sm3[tid * 16];
+      } else {
+        rows_head<RG>(h, ldl, H, hw_c, H, hb + 16, 1, EPI_NONE, sm2);
+        __syncthreads();
+        if (tid < R) {
+          if (tid < rv) a.q2[row0 + tid] = sm2[tid * 16];
+          sm2[tid * 16] = (tid < rv) ? -1.0f / (float)B : 0.f;   // d(-mean Q)/dq
+        }
+        __syncthreads();
+        head_backward<RG>(h, ldl, H, hw_c, 1, sm2, nullptr, rv);
+        __syncthreads();
+      }
+      RC_STAMP(6);
+      float* g0;
+      if constexpr (LM) g0 = grad_chain_st<KS, true, TAIL_FULL, false>(ws, a.critic[0], h, X1, X2, ldl, part + R * 16, KPC, nullptr, BH, row0, rv, nx_ab);
+      else g0 = grad_chain_st<KS, false, TAIL_FULL, false>(ws, a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv, nx_ab);
+      RC_STAMP(7);
+      rows_head<RG>(g0, ldl, H, hw_da, H, nullptr, A, EPI_NONE, sm2);
+      __syncthreads();
+      if (tid < R * A) {
+        const int r = tid / A, o = tid - r * A;
+        const float act = sm[r * 16 + o];
+        const float g = sm2[r * 16 + o] * act_deriv(act, MUL_DTANH);
+        sm2[r * 16 + o] = g;
+        if (r < rv) a.dz[(row0 + r) * a.Apad + o] = g;
+      }
+      __syncthreads();
+      head_backward<RG>(XS, ldl, H, hw_a, A, sm2, a.gA + (a.actor.L - 1) * BH + row0 * H, rv);
+      __syncthreads();
+      RC_STAMP(9);
+      if constexpr (LM) grad_chain_st<KS, true, TAIL_NONE, false>(ws, a.actor, XS, X1, X2, ldl, part + R * 16, KP, a.gA, BH, row0, rv, nx_none);
+      else grad_chain_st<KS, false, TAIL_NONE, false>(ws, a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv, nx_none);
+      RC_STAMP(10);
+    };
+    if (H == 256) p_role(std::integral_constant<int, 64>{});
+    else if (H == 128) p_role(std::integral_constant<int, 32>{});
+    else if (H == 64) p_role(std::integral_constant<int, 16>{});
+    else p_role(std::integral_constant<int, 0>{});
   } else {
     const StepCtrl c = *a.cur_p;
     const float* sa_rows = a.sa + (long long)c.batch_slot * a.slot_x + row0 * a.ldx;

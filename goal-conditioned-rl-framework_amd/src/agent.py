@@ -411,6 +411,12 @@ class _EngineAgent:
         everywhere (GCRL_RC_GLOBAL_MUL=1, a shape the LDS rule refuses, or an agent without that launch).  Changes nothing."""
         return _ffi.check(lib.gcrl_agent_rowchain_form(self._h))
 
+    def rowchain_stream(self) -> bool:
+        """Whether the fused DDPG row-chain launches of this handle take the stream form of their chained layer passes
+        (csrc/rowchain.h WStream); False under GCRL_RC_NO_STREAM=1, at another shape, or for an agent without that launch.
+        Same bits either way.  Changes nothing."""
+        return bool(_ffi.check(lib.gcrl_agent_rowchain_stream(self._h)))
+
     UPDATE_FORM_FIELDS = ("rows_per_workgroup", "rowchain", "split_roles", "rc_merge", "split_k", "rc_merge_k", "ddpg_ksplit", "opt_fuse",
                           "bn_slab", "bn_rsplit")
 

@@ -692,6 +692,11 @@ int gcrl_agent_debug_meet_fault(gcrl_agent* a);
  * both; 0 also when no launch of the handle goes through that kernel (SAC, TQC).  Same results either way; changes nothing.
  * New design (the reference is eager PyTorch: no such forms). */
 int gcrl_agent_rowchain_form(gcrl_agent* a);
+/* 1 when the handle's fused DDPG row-chain launches take the stream form of their chained layer passes (csrc/rowchain.h WStream: the
+ * first stage of a pass's weight rows is requested by the pass before it; plain DDPG at 4 rows per workgroup, hidden width <= 256, two
+ * hidden layers or more), 0 otherwise (GCRL_RC_NO_STREAM=1 at creation, another shape, or an agent without that launch).  Same bits
+ * either way; changes nothing.  New design (the reference is eager PyTorch: no such forms). */
+int gcrl_agent_rowchain_stream(gcrl_agent* a);
 /* The launch rules gcrl_agent_create settled for this handle, as they stand now (tests name the form they ran on): out[0..n) in this
  * order, as many as n holds (at most 10) — rows per row-chain workgroup (4, 8 or 16), row chain (else the layer-per-launch schedule),
  * split_roles (SAC: role-parallel chain launches), rc_merge (those merged into one launch), split_k (TD3: role-parallel critic phase),

@@ -34,10 +34,16 @@ names_k = {0: "start", 1: "prologue", 2: "target actor hidden", 3: "its head + a
            7: "head, loss, head bwd", 8: "critic dX chain"}
 names_p = {0: "start", 1: "prologue", 2: "actor hidden", 3: "actor head + action", 4: "critic hidden", 6: "Q head + head bwd", 7: "critic dX chain",
            9: "da head, tanh', actor head bwd", 10: "actor dX chain"}
+# the two K roles of the default form (rowchain_split_body): entry and exit, on the P role's clock
+if st[0][16] and st[1][0]:
+    for name, i in (("K target role", 16), ("K online-critic role", 18)):
+        print(f"{name}: entry at {(st[0][i] - st[1][0]) / 100:7.2f} us, exit at {(st[0][i + 1] - st[1][0]) / 100:7.2f} us of the P role's clock")
 for role, names in ((0, names_k), (1, names_p)):
     t0 = st[role][0]
     print("role", "K" if role == 0 else "P")
     prev = t0
+    if st[role][11]:   # (stamp 11: the kernel's first instruction, in front of the argument warm-up)
+        print(f"  {'entry, before the argument warm-up':32s} at {(st[role][11] - t0) / 100:7.2f} us")
     for i in sorted(names):
         t = st[role][i]
         print(f"  {names[i]:32s} at {(t - t0) / 100:7.2f} us   (+{(t - prev) / 100:5.2f})")

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Development tool: builds tools/abl/libgcrl_rcstamps.so = the library with device-clock stamps at the section boundaries of
-rowchain_ddpg_kernel (first K-role and first P-role workgroup), read back by tools/rc_stamps.py.  The product build carries
-no stamps: this script patches a temporary copy of csrc/rowchain.hip."""
+rowchain_ddpg_kernel_stream (the stream form of the fused DDPG launch at 4 rows per workgroup; first K-role and first P-role workgroup),
+read back by tools/rc_stamps.py.  The loop-form kernels (GCRL_RC_NO_STREAM=1) carry none: an A/B of stamps against the parent needs the
+parent tree's own build of this tool.  The two K roles of the default form are stamped at entry and exit only.  The product build carries no stamps: this script
+patches a temporary copy of csrc/rowchain.hip."""
 import glob
 import os
 import re
@@ -11,11 +13,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "csrc")
 src = open(os.path.join(CSRC, "rowchain.hip")).read()
-# the kernel's body lives in rowchain_ddpg_body.inc (shared with the population kernel): inlined into the single-agent kernel, which is
-# the first to include it, so that the stamps below land in that kernel only
+# the kernel's body lives in rowchain_ddpg_body.inc (shared by the loop-form, stream-form and population kernels): inlined into the
+# single-agent stream kernel, the second to include it, so that the stamps below land in that kernel only
 INC = '#include "rowchain_ddpg_body.inc"\n'
-assert src.count(INC) == 2, "rowchain.hip no longer includes the DDPG body twice: follow it here"
-src = src.replace(INC, open(os.path.join(CSRC, "rowchain_ddpg_body.inc")).read(), 1)
+assert src.count(INC) == 4, "rowchain.hip no longer includes the DDPG body four times: follow it here"
+HEAD = "template <bool LM>\n__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel_stream(RowChainArgs args) {"
+assert src.count(HEAD) == 1, "rowchain_ddpg_kernel_stream's head moved: follow it here"
+at = src.index(INC, src.index(HEAD))
+assert src.count(INC, 0, at) == 1, "the stream kernel is no longer the second to include the body"
+src = src[:at] + open(os.path.join(CSRC, "rowchain_ddpg_body.inc")).read() + src[at + len(INC):]
 
 
 def after(anchor, stamp, nth=0):
@@ -27,30 +33,29 @@ def after(anchor, stamp, nth=0):
     src = src[:end] + f"\n    RC_STAMP({stamp});" + src[end:]
 
 
-HEAD = "template <int RG, bool LM>\n__global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {"
-assert src.count(HEAD) == 1, "rowchain_ddpg_kernel's head moved: follow it here"
-src = src.replace(HEAD,
+STUB = "#ifndef RC_STAMP\n#define RC_STAMP(i)   // (tools/rc_stamps_build.py: device-clock stamps of the development build)\n#endif\n"
+assert src.count(STUB) == 1, "rowchain.hip's RC_STAMP stub moved: follow it here"
+COND = "threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == (A.k_split ? 2 : 1) * A.nblk_k)"
+src = src.replace(STUB,
                   "__device__ unsigned long long g_rc_stamps[2][32];\n"
-                  "#define RC_STAMP(i) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == (a.k_split ? 2 : 1) * a.nblk_k)) g_rc_stamps[blockIdx.x == 0 ? 0 : 1][i] = wall_clock64(); } while (0)\n"
-                  + HEAD, 1)
-# P role (the plain DDPG branch)
-marks_p = [
-    ("    const float* src_da = a.critic[0].Wt + a.critic[0].wt[0] + (long long)S * H;   // rows S..S+A-1 of W0^T", 0, "start"),
-    ("    else h = mlp_hidden<RG>(a.actor, X0, X1, X2, ldl, part + R * 16, a.hA, BH, row0, rv, XS);", 2, "actor hidden"),
-    ("    if (tid < R * A) { const int r = tid / A, o = tid - r * A; X0[r * ldl + S + o] = sm[r * 16 + o]; }\n    __syncthreads();", 3, "actor head + act"),
-    ("    else h = mlp_hidden<RG>(a.critic[0], X0, X1, X2, ldl, part + R * 16, a.hC2, BH, row0, rv);", 4, "critic hidden"),
-    ("    else g0 = grad_chain<RG>(a.critic[0], h, X1, X2, ldl, part + R * 16, a.hC2, nullptr, BH, row0, rv);", 7, "critic dX chain"),
-    ("    head_backward<RG>(XS, ldl, H, hw_a, A, sm2, a.gA + (a.actor.L - 1) * BH + row0 * H, rv);\n    __syncthreads();", 9, "da head, tanh', actor head bwd"),
-    ("    else grad_chain<RG>(a.actor, XS, X1, X2, ldl, part + R * 16, a.hA, a.gA, BH, row0, rv);", 10, "actor dX chain"),
-]
-names_p = {}
-for anchor, i, name in marks_p:
-    after(anchor, i)
-    names_p[i] = name
-# "prologue done" and "head value + head bwd" in P
-after("    if (fuse_q && tid < R) sm2[tid * 16] = (tid < rv) ? -1.0f / (float)B : 0.f;   // d(-mean Q)/dq, constant\n    __syncthreads();", 1)
-after("      head_backward<RG>(h, ldl, H, hw_c, 1, sm2, nullptr, rv, sm3, hb[16]);\n      __syncthreads();", 6)
-# K role
+                  "#define RC_STAMP_AT(A, i) do { if (" + COND + ") g_rc_stamps[blockIdx.x == 0 ? 0 : 1][i] = wall_clock64(); } while (0)\n"
+                  "#define RC_STAMP(i) RC_STAMP_AT(a, i)\n", 1)
+# in front of the argument warm-up (stamp 11)
+src = src.replace(HEAD, HEAD + "\n  RC_STAMP_AT(args, 11);", 1)
+# the P role's stamps (the stream branch of the body) stand in the text as RC_STAMP(i): 0 start, 1 prologue, 2 actor hidden, 3 actor head +
+# action, 4 critic hidden, 6 Q head + head bwd, 7 critic dX chain, 9 da head / tanh' / actor head bwd, 10 actor dX chain
+# the two K roles of the default form run rowchain_split_body (phase 0, part 3): entry and exit of the first target-role workgroup
+# (stamps 16, 17 of row 0) and of the first online-critic workgroup (18, 19), on the same device clock as the P role's
+BODY = "  const bool merged = part == 3;                 // parts 1 and 2 in this launch (rowchain.h)\n"
+assert src.count(BODY) == 1, "rowchain_split_body's head moved: follow it here"
+src = src.replace(BODY, BODY + "  if (tid == 0 && phase == 0 && (bid == 0 || bid == nblk)) g_rc_stamps[0][bid == 0 ? 16 : 18] = wall_clock64();\n", 1)
+T_END = "      else rc_meet(meet, 2 * C, false, &s_flag, a.status);\n    }\n"
+assert src.count(T_END) == 1
+src = src.replace(T_END, T_END + "    if (tid == 0 && bid == 0) g_rc_stamps[0][17] = wall_clock64();\n", 1)
+O_END = "    else grad_chain<RG>(a.critic[k], XS, X1, X2, ldl, part_ + R * 16, hs, gsave, BH, row0, rv);\n"
+assert src.count(O_END) == 1
+src = src.replace(O_END, O_END + "    if (tid == 0 && bid == nblk) g_rc_stamps[0][19] = wall_clock64();\n", 1)
+# K role of the one-role form (GCRL_NO_DDPG_KSPLIT=1)
 after("  if (role_k) {", 0)
 after("      part[tid] = fminf(fmaxf(__fmul_rn(e, a.policy_noise), -a.noise_clamp), a.noise_clamp);\n    }\n    __syncthreads();", 1)
 after("      h = mlp_hidden<RG>(a.tactor, X0, X1, X2, ldl, part + R * 16, nullptr, BH, row0, rv);", 2)
