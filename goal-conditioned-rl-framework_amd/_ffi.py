@@ -296,6 +296,7 @@ PROTOTYPES = {
     "gcrl_agent_get_meetings": (C.c_int, [_vp]),
     "gcrl_agent_rowchain_form": (C.c_int, [_vp]),
     "gcrl_agent_rowchain_stream": (C.c_int, [_vp]),
+    "gcrl_agent_rowchain_warm": (C.c_int, [_vp]),
     "gcrl_agent_update_forms": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
     "gcrl_agent_debug_meet_fault": (C.c_int, [_vp]),
     "gcrl_hash_normal_fill": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
@@ -356,6 +357,9 @@ PROTOTYPES = {
     "gcrl_memcpy_d2h": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
 }
 
+# bound only where the library has them: an older build of the library (GCRL_HIP_LIB, the A/B of two builds) still loads
+OPTIONAL = {"gcrl_agent_rowchain_warm"}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -368,6 +372,8 @@ def _load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -195,6 +195,7 @@ struct gcrl_agent {
   int n_cus = 0;              // compute units of the device (residency checks of the launches whose workgroups meet)
   bool rc_merge = false;      // ... forward and backward part in ONE launch each (part 3; GCRL_NO_RC_MERGE=1: two launches)
   bool rc_merge_k = false;    // TD3 (split_k): the critic phase's two launches as one, producers / consumers form (meet.h)
+  int rc_warm = 0;              // L2-warming rider workgroups of a fused DDPG stream-form launch (rowchain.hip rc_warm_rider); GCRL_RC_NO_WARM=1: 0
   bool rc_no_stream = false;    // GCRL_RC_NO_STREAM=1 (A/B switch): the fused DDPG launch keeps the loop form of its chained passes (rowchain.h WStream)
   bool rc_global_mul = false;   // GCRL_RC_GLOBAL_MUL=1 (A/B switch): the fused DDPG launch keeps its act' multipliers in the global saves (rowchain.h)
   bool ddpg_ksplit = false, ddpg_ksplit_can = false;   // DDPG: the critic phase as two roles of the fused launch (rowchain.hip, k_split)
@@ -1671,6 +1672,7 @@ int build(gcrl_agent* a) {
     a->main_idx_staged = std::getenv("GCRL_MAIN_IDX_STAGED") != nullptr;   // A/B knob (finish_deferred_draw)
     a->rc_global_mul = std::getenv("GCRL_RC_GLOBAL_MUL") != nullptr;       // A/B knob (rowchain.h: rowchain_lds_mul_ok)
     a->rc_no_stream = std::getenv("GCRL_RC_NO_STREAM") != nullptr;         // A/B knob (rowchain.h: rowchain_stream_ok)
+    a->rc_warm = std::getenv("GCRL_RC_NO_WARM") ? 0 : kRowChainWarm;        // A/B knob (rowchain.hip: rc_warm_rider)
     (void)rc_lds_mul_forms(a);   // (asks the device about both forms' residency now, not at the first launch)
     a->bn_fused_tiled = std::getenv("GCRL_NO_BN_TILED_STATS") == nullptr;
     a->layer_adv_off = std::getenv("GCRL_NO_LAYER_ADV") != nullptr;
@@ -2495,6 +2497,12 @@ int gcrl_agent_rowchain_form(gcrl_agent* a) {
 int gcrl_agent_rowchain_stream(gcrl_agent* a) {
   GCRL_CHECK_ARG(a, "gcrl_agent_rowchain_stream: null handle");
   return rc_stream_form(a) ? 1 : 0;
+}
+
+int gcrl_agent_rowchain_warm(gcrl_agent* a) {
+  GCRL_CHECK_ARG(a, "gcrl_agent_rowchain_warm: null handle");
+  const long long nblk = (a->B + 4 * a->row_rg - 1) / (4 * a->row_rg);
+  return rc_warm_riders(a, (a->ddpg_ksplit ? 3 : 2) * nblk);
 }
 
 int gcrl_agent_update_forms(gcrl_agent* a, int32_t* out, int n) {

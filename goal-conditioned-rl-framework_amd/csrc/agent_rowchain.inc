@@ -72,6 +72,16 @@ bool rc_stream_form(const gcrl_agent* a) {
          a->C == 1 && a->H <= kRowChunk && a->L >= 2;
 }
 
+// L2-warming rider workgroups of the agent's fused DDPG launches (rowchain.hip rc_warm_rider): the stream form's launches only, and only
+// where a launch of `wgs` role workgroups leaves them CUs of their own (the two-role admission's count, one workgroup per CU); 0: none.
+// They wait for nothing, so meetings being off or the device being shared does not take them away.  GCRL_RC_NO_WARM=1 at creation: none.
+// The count is against the CUs (n_cus, as the two-role admission 3 * nblk <= n_cus counts), not against meet_capacity: riders carry the launch's
+// last indices and wait for nobody, so nothing depends on their being resident — the rule only keeps them off CUs that hold a role workgroup.
+int rc_warm_riders(const gcrl_agent* a, long long wgs) {
+  if (!rc_stream_form(a) || a->rc_warm <= 0) return 0;
+  return wgs + a->rc_warm <= std::max(a->n_cus, 1) ? a->rc_warm : 0;
+}
+
 // SAC on the role-parallel row-chain launches: the BatchNorm actor's heads and its sampling run inside them (rowchain.h HeadsFold)
 bool heads_fold_on(const gcrl_agent* a) {
   return a->rowchain && a->cfg.kind == GCRL_AGENT_SAC && a->split_roles && a->slab_on() && !a->heads_fold_off && a->A <= 16 && a->bn_sync.world <= 1;
@@ -110,6 +120,7 @@ int rc_launch_chain(gcrl_agent* a, hipStream_t st, const PipeCtx& k, const PipeC
   rc.gamma = (float)a->cfg.gamma;
   rc.clamp_lo = (float)(-1.0 / (1.0 - a->cfg.gamma));
   rc.qt = a->qt;
+  rc.reserved0 = rc_warm_riders(a, (long long)((a->ddpg_ksplit && (what & 1)) ? 2 : 1) * rc.nblk_k + rc.nblk_p);
   if (a->split_roles) {
     // twin critics at a latency-bound batch size: each network's chain in its own workgroups (rowchain.h)
     HeadsFold hfold;

@@ -470,7 +470,7 @@ struct RowChainArgs {
   long long slot_x, slot_rd;
   int ldx, ldl, B, S, A, Apad;
   int nblk_k, nblk_p;
-  int reserved0;              // (was linear_roles: the by-XCD role placement, measured and never asked for — the slot stays so that no later field moves)
+  int reserved0;              // the single-agent stream launch: L2-warming rider workgroups behind the roles' (rowchain.hip rc_warm_rider); 0 none; unread elsewhere
   float *hC, *gC, *q, *y, *dq;      // K: activations / pre-activation gradients [C][L][B][H], q / dq [C][B], y [B]
   float *hA, *gA, *hC2, *q2, *dz;   // P: ..., critic activations (scratch) [C][L][B][H], Q(s, pi(s)) [C][B], d(pre-tanh) [C][B][Apad]
   float gamma, clamp_lo;
@@ -581,6 +581,10 @@ int launch_rowchain_act_pop(hipStream_t st, const RowActPop& c, int members, int
 // lds_mul: the LDS-multiplier form (below) where the launch's shape admits it; false: the global-multiplier form
 // stream: the stream form of the chained passes (WStream above) where rowchain_stream_ok admits the launch; false: the loop of rows_matmul_wave
 // (GCRL_RC_NO_STREAM=1, read when an agent is created, is the A/B switch; both forms give the same bits)
+// a.reserved0: rider workgroups added behind the roles' where the launch takes the stream form (GCRL_RC_NO_WARM=1 at creation: none; same bits)
+// chosen at the headline shape only (H 256, L 3, B 256: 8 riders 1.0 us/step slower, 32 and 64 no faster; round 38) — the same count runs at every
+// stream-form shape, where it was checked for bits, not timed
+constexpr int kRowChainWarm = 16;   // two per XCD under round-robin dispatch
 int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds_mul, bool stream = false);
 bool rowchain_stream_ok(const RowChainArgs& a, int rg);
 size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C);

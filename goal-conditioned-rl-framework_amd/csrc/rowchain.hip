@@ -244,6 +244,45 @@ __device__ inline void stage(float* dst, const float* src, int n) {
 template <int RG, bool HF = false, bool LM = false>
 __device__ __forceinline__ void rowchain_split_body(const RowChainArgs& a, int phase, int part, int bid, const HeadsFold& hfr = HeadsFold{});
 
+// ---- L2-warming riders of the single-agent stream launch (rowchain_ddpg_kernel_stream; round 38) ----
+// L2 contents do not survive a kernel boundary, and the optimiser launch in front has just written every weight through to the memory
+// side: the first touch of a matrix on an XCD is a miss that the XCD's role workgroups, running in lockstep, all wait behind.  The launch
+// leaves CUs idle (192 workgroups on 256 CUs at the headline shape), so it grows by a.reserved0 workgroups with its LAST indices — under
+// round-robin dispatch rider r lands on XCD (first rider's index + r) % 8 — that only LOAD, and discard, the H x H matrices the roles will
+// stream, in the order of first need.  A rider uses no LDS and no barrier, stores nothing, stamps nothing, waits for nothing another
+// workgroup writes, and returns once its loads are back: it cannot change a bit of the result, and a wrong guess about its placement
+// costs speed only.  With 8 k riders, k of them share an XCD and each takes every k-th 4 KB piece of a matrix.
+__device__ __forceinline__ void rc_warm_matrix(const float* M, int nfloats, int part, int share) {
+  const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(M, nfloats);   // a piece past the matrix's end reads zeros and moves nothing
+  const int bytes = nfloats * 4;
+  constexpr int U = 16;                                         // loads of a thread in flight: 64 KB per rider
+  const int step = kRowThreads * 16;                            // a workgroup-wide 16-byte load covers 4 KB: whole lines
+  const int mine = part * step + (int)threadIdx.x * 16;
+  for (int base = 0; base < bytes; base += share * step * U) {
+    v4u w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + u * share * step + mine, 0, 0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) asm volatile("" ::"v"(w[u]));   // the loads stay alive without a store
+  }
+}
+__device__ __forceinline__ void rc_warm_rider(const RowChainArgs& a, int rid) {
+  const int nw = a.reserved0;
+  const int share = (nw >= 8 && nw % 8 == 0) ? nw / 8 : 1, part = share > 1 ? rid / 8 : 0;
+  const int H = a.critic[0].H, L = a.critic[0].L, HH = H * H;
+  const bool k = a.nblk_k > 0, p = a.nblk_p > 0;
+  // the [in][out] copies of layers >= 1: the three roles walk actor, critic and target actor side by side; the target critic follows
+  for (int l = 1; l < L; ++l) {
+    if (p) rc_warm_matrix(a.actor.Wt + a.actor.wt[l], HH, part, share);
+    rc_warm_matrix(a.critic[0].Wt + a.critic[0].wt[l], HH, part, share);
+    if (k) rc_warm_matrix(a.tactor.Wt + a.tactor.wt[l], HH, part, share);
+  }
+  if (k) for (int l = 1; l < L; ++l) rc_warm_matrix(a.tcritic[0].Wt + a.tcritic[0].wt[l], HH, part, share);
+  // the torch-layout matrices of the dX chains, last layer first: the critic's (online role, then the actor phase), then the actor's
+  for (int l = L - 1; l >= 1; --l) rc_warm_matrix(a.critic[0].P + a.critic[0].w[l], HH, part, share);
+  if (p) for (int l = L - 1; l >= 1; --l) rc_warm_matrix(a.actor.P + a.actor.w[l], HH, part, share);
+}
+
 #ifndef RC_STAMP
 #define RC_STAMP(i)   // (tools/rc_stamps_build.py: device-clock stamps of the development build)
 #endif
@@ -252,6 +291,7 @@ template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel(RowChainArgs a) {
   kernarg_warm_once<sizeof(RowChainArgs)>();
   constexpr bool ST = false;
+  constexpr bool WR = false;
 #include "rowchain_ddpg_body.inc"
 }
 // the stream form (rowchain.h WStream) of the launch at 4 rows per workgroup: the same body, its chained passes carry the weight stream
@@ -264,6 +304,7 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_kernel_stream(RowCh
   const RowChainArgs& a = *(const RowChainArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   constexpr int RG = 1;
   constexpr bool ST = true;
+  constexpr bool WR = true;   // the L2-warming riders (rc_warm_rider above): this kernel only
 #include "rowchain_ddpg_body.inc"
 }
 
@@ -273,6 +314,7 @@ template <int RG, bool LM>
 __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_pop_kernel(const RowChainArgs* __restrict__ tab) {
   const RowChainArgs& a = tab[blockIdx.y];
   constexpr bool ST = false;
+  constexpr bool WR = false;
 #include "rowchain_ddpg_body.inc"
 }
 template <bool LM>
@@ -280,6 +322,7 @@ __global__ __launch_bounds__(kRowThreads) void rowchain_ddpg_pop_kernel_stream(c
   const RowChainArgs& a = tab[blockIdx.y];
   constexpr int RG = 1;
   constexpr bool ST = true;
+  constexpr bool WR = false;
 #include "rowchain_ddpg_body.inc"
 }
 
@@ -857,13 +900,15 @@ int launch_rowchain_ddpg(hipStream_t st, const RowChainArgs& a, int rg, bool lds
   const bool sf = stream && rowchain_stream_ok(a, rg);   // the stream form of the chained passes (rowchain.h WStream)
   if (PopRec* r = pop_recording())   // a population step is being recorded (pop.h)
     return pop_record(r, POP_ROWCHAIN, rg | (lm ? 16 : 0) | (sf ? 32 : 0), dim3(grid), lds, &a, sizeof(a), [ac = a, rg, lds_mul, stream](hipStream_t s) { return launch_rowchain_ddpg(s, ac, rg, lds_mul, stream); });
+  // the L2-warming riders (rc_warm_rider): a.reserved0 more workgroups behind the roles', the single-agent stream kernel's only
+  const int nw = sf ? a.reserved0 : 0;
   auto go = [&](auto kern) -> int {
     static thread_local size_t raised = 0;   // (per kernel: a generic lambda's statics belong to its instantiation)
     if (lds > 64 * 1024 && lds > raised) {
       GCRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       raised = lds;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kRowThreads), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(grid + nw), dim3(kRowThreads), lds, st, a);
     GCRL_HIP(hipGetLastError());
     return GCRL_OK;
   };

@@ -5,6 +5,7 @@
 // KP = [L - 1][R][ldl] per net, and the chains read their multipliers there.  hA / gA / hC / gC still leave for the dW launch; hC2, which
 // only this launch read, is neither written nor read.  The SAC form (p_critic_only) is never launched with LM (launch_rowchain_ddpg).
 // constexpr bool ST: the stream form of the actor phase's chained passes (rowchain_ddpg_kernel_stream, RG = 1); RC_STAMP: development stamps.
+// constexpr bool WR: the launch may carry L2-warming riders behind its roles (the single-agent stream kernel only; a.reserved0 of them).
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // k_split (round 4, DDPG): the critic phase K as TWO roles in this launch — its target chain (target actor -> target critic -> Q')
   // and its online critic's forward are independent, so K's critical path shrinks from 11 layer passes to 6 + 2 (the split kernel's
@@ -19,6 +20,10 @@
     }
   }
   const int kblocks = (a.k_split && a.nblk_k) ? 2 * a.nblk_k : a.nblk_k;
+  if constexpr (WR) {
+    // the launch's last a.reserved0 workgroups: L2-warming riders (rowchain.hip rc_warm_rider), behind every role's workgroups
+    if ((int)blockIdx.x >= kblocks + a.nblk_p) { rc_warm_rider(a, (int)blockIdx.x - kblocks - a.nblk_p); return; }
+  }
   constexpr int R = 4 * RG;
   const int ldl = a.ldl, H = a.critic[0].H, S = a.S, A = a.A, B = a.B;
   float* X0 = lds;

@@ -417,6 +417,14 @@ class _EngineAgent:
         Same bits either way.  Changes nothing."""
         return bool(_ffi.check(lib.gcrl_agent_rowchain_stream(self._h)))
 
+    def rowchain_warm(self) -> int:
+        """Number of L2-warming rider workgroups behind the role workgroups of this handle's overlapped fused DDPG row-chain launch
+        (csrc/rowchain.hip rc_warm_rider); 0 under GCRL_RC_NO_WARM=1, for a launch that does not take the stream form or leaves no
+        idle CUs, for an agent without that launch, or with a library built before the riders.  Same bits either way.  Changes nothing."""
+        if not hasattr(lib, "gcrl_agent_rowchain_warm"):
+            return 0
+        return _ffi.check(lib.gcrl_agent_rowchain_warm(self._h))
+
     UPDATE_FORM_FIELDS = ("rows_per_workgroup", "rowchain", "split_roles", "rc_merge", "split_k", "rc_merge_k", "ddpg_ksplit", "opt_fuse",
                           "bn_slab", "bn_rsplit")
 

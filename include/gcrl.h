@@ -697,6 +697,12 @@ int gcrl_agent_rowchain_form(gcrl_agent* a);
  * hidden layers or more), 0 otherwise (GCRL_RC_NO_STREAM=1 at creation, another shape, or an agent without that launch).  Same bits
  * either way; changes nothing.  New design (the reference is eager PyTorch: no such forms). */
 int gcrl_agent_rowchain_stream(gcrl_agent* a);
+/* Number of L2-warming rider workgroups the handle's overlapped fused DDPG row-chain launch carries behind its role workgroups
+ * (csrc/rowchain.hip rc_warm_rider: workgroups on otherwise idle CUs that only load, and discard, the weight matrices the roles are
+ * about to stream, so that each XCD's L2 holds them at first use); 0 when the launch has none (GCRL_RC_NO_WARM=1 at creation, a launch
+ * that does not take the stream form, no idle CUs left, or an agent without that launch).  Riders store nothing: same bits either way;
+ * changes nothing.  New design (the reference is eager PyTorch: no such forms). */
+int gcrl_agent_rowchain_warm(gcrl_agent* a);
 /* The launch rules gcrl_agent_create settled for this handle, as they stand now (tests name the form they ran on): out[0..n) in this
  * order, as many as n holds (at most 10) — rows per row-chain workgroup (4, 8 or 16), row chain (else the layer-per-launch schedule),
  * split_roles (SAC: role-parallel chain launches), rc_merge (those merged into one launch), split_k (TD3: role-parallel critic phase),

@@ -2,8 +2,10 @@
 """Development tool: builds tools/abl/libgcrl_rcstamps.so = the library with device-clock stamps at the section boundaries of
 rowchain_ddpg_kernel_stream (the stream form of the fused DDPG launch at 4 rows per workgroup; first K-role and first P-role workgroup),
 read back by tools/rc_stamps.py.  The loop-form kernels (GCRL_RC_NO_STREAM=1) carry none: an A/B of stamps against the parent needs the
-parent tree's own build of this tool.  The two K roles of the default form are stamped at entry and exit only.  The product build carries no stamps: this script
-patches a temporary copy of csrc/rowchain.hip."""
+parent tree's own build of this tool.  Every role's first workgroup also stamps the end of each of its layer passes (round 38: the K
+target role, the K online-critic role and the P role, per pass).  `--nosave` builds tools/abl/libgcrl_rcstamps_nosave.so, a timing-only
+variant whose results are wrong by construction (see below).  The product build carries no stamps: this script patches a temporary copy
+of csrc/rowchain.hip."""
 import glob
 import os
 import re
@@ -68,17 +70,56 @@ after("      else grad_chain<RG>(a.critic[k], h, X1, X2, ldl, part + R * 16, a.h
 src = src.replace("size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C) {",
                   'extern "C" int gcrl_debug_rc_stamps(unsigned long long* out64) {\n'
                   "  return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_rc_stamps), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;\n}\n"
+                  'extern "C" int gcrl_debug_rc_pass(unsigned long long* out96) {\n'
+                  "  return hipMemcpyFromSymbol(out96, HIP_SYMBOL(g_rc_pass), sizeof(unsigned long long) * 96) == hipSuccess ? 0 : -1;\n}\n"
                   "size_t rowchain_lds_bytes(int rg, int ldl, int A, int H, int C) {", 1)
+# ---- per-pass stamps (round 38): every layer pass of the six walks (mlp_hidden, grad_chain, their _keep and _st forms) ends with a stamp
+# of thread 0 into g_rc_pass[row][n], n counting the workgroup's passes in the order it runs them.  The row and the count live in two
+# words of static LDS that only thread 0 touches; the stream kernel's entry sets them for the first workgroup of each role (row 0: K
+# target role, or the one-role K; 1: K online-critic role; 2: P role), every other workgroup and kernel finds a row out of range and
+# stamps nothing.  The passes of a role in order: K target = target actor 0..L-1, target critic 0..L-1; K online = critic 0..L-1, its dX
+# chain L-1..1; P = actor 0..L-1, critic 0..L-1, critic dX L-1..1, actor dX L-1..1.
+W0 = src.index("template <int RG>\n__device__ inline float* mlp_hidden(")
+W1 = src.index("// stage `n` floats of global memory into LDS (all threads)")
+walks, n_pass = re.subn(r"(rows_linear(?:_stream)?<[^;]*?\);)", r"{ \1 RC_PASS(); }", src[W0:W1], flags=re.S)
+assert n_pass == 9, f"{n_pass} layer-pass statements in the six walks, 9 expected: follow them here"
+src = (src[:W0] +
+       "__device__ unsigned long long g_rc_pass[3][32];\n"
+       "__shared__ int s_rc_row, s_rc_n;\n"
+       "#define RC_PASS() do { if (threadIdx.x == 0) { const unsigned r_ = (unsigned)s_rc_row, n_ = (unsigned)s_rc_n;"
+       " if (r_ < 3u && n_ < 32u) { g_rc_pass[r_][n_] = wall_clock64(); s_rc_n = (int)n_ + 1; } } } while (0)\n" + walks + src[W1:])
+src = src.replace(HEAD + "\n  RC_STAMP_AT(args, 11);",
+                  HEAD + "\n  RC_STAMP_AT(args, 11);\n"
+                  "  if (threadIdx.x == 0) { const int b_ = (int)blockIdx.x, nk_ = args.nblk_k; s_rc_n = 0;\n"
+                  "    s_rc_row = args.k_split ? (b_ == 0 ? 0 : (b_ == nk_ ? 1 : (b_ == 2 * nk_ ? 2 : -1))) : (b_ == nk_ ? 2 : (b_ == 0 ? 0 : -1));\n"
+                  "    if (nk_ == 0 || args.nblk_p == 0) s_rc_row = -1; }   // the overlapped launch only: a call's last launch is the actor phase alone", 1)
+assert "s_rc_row = args.k_split" in src
+# every OTHER kernel of the file (loop-form, population, split, acting) reaches RC_PASS through the same walks, and static LDS keeps what
+# an earlier kernel on the CU left there: each of them sets the row out of range at its entry, so only the stream kernel ever stamps
+KERNEL_HEAD = re.compile(r"(__global__ __launch_bounds__\(kRowThreads\) void (\w+)\([^)]*\) \{\n)")
+others = [m.group(2) for m in KERNEL_HEAD.finditer(src) if m.group(2) != "rowchain_ddpg_kernel_stream"]
+assert len(others) == 10, f"{others}: ten other kernels with kRowThreads expected, follow them here"
+src = KERNEL_HEAD.sub(lambda m: m.group(1) if m.group(2) == "rowchain_ddpg_kernel_stream" else m.group(1) + "  if (threadIdx.x == 0) s_rc_row = -1;\n", src)
+# --nosave: the TIMING-ONLY variant of round 38's part 0 — the actor's forward and backward walks of the P role run with save = nullptr
+# (hA / gA are not written: the step's results are WRONG by construction; never a product build), nothing else changed
+if "--nosave" in sys.argv:
+    for old, new in (("part + R * 16, a.hA, BH, row0, rv, nx_c0)", "part + R * 16, nullptr, BH, row0, rv, nx_c0)"),
+                     ("KP, a.gA, BH, row0, rv, nx_none)", "KP, nullptr, BH, row0, rv, nx_none)"),
+                     ("a.hA, a.gA, BH, row0, rv, nx_none)", "a.hA, nullptr, BH, row0, rv, nx_none)")):
+        assert src.count(old) >= 1, old
+        src = src.replace(old, new)
+LIBNAME = "libgcrl_rcstamps_nosave.so" if "--nosave" in sys.argv else "libgcrl_rcstamps.so"
 tmp = os.path.join(CSRC, "_rowchain_stamps.hip")
 open(tmp, "w").write(src)
 out_dir = os.path.join(ROOT, "tools", "abl")
+OBJ = os.path.join(out_dir, LIBNAME[:-3] + ".o")
 os.makedirs(out_dir, exist_ok=True)
 try:
     subprocess.run(["make", "-C", CSRC, "-j8"], check=True, stdout=subprocess.DEVNULL)
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-ffp-contract=off"]
-    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", tmp, "-o", "/tmp/rowchain_st.o"], check=True, cwd=CSRC)
+    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", tmp, "-o", OBJ], check=True, cwd=CSRC)
     objs = [o for o in glob.glob(os.path.join(ROOT, "goal-conditioned-rl-framework_amd", "build", "*.o")) if not o.endswith("rowchain.o")]
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(out_dir, "libgcrl_rcstamps.so")] + objs + ["/tmp/rowchain_st.o", "-ldl"], check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(out_dir, LIBNAME)] + objs + [OBJ, "-ldl"], check=True)
 finally:
     os.remove(tmp)
-print("built", os.path.join(out_dir, "libgcrl_rcstamps.so"))
+print("built", os.path.join(out_dir, LIBNAME))
